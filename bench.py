@@ -15,9 +15,15 @@ N = 1: BASELINE.json configs[1] (V = 1 M rows, B = 65 536, bf16).
 N > 1: configs[4] scaled weakly: 125 M rows and 65 536 samples per GPU, table row-sharded over the ranks,
        lookup by RCCL all-to-all, gradient returned by the reverse all-to-all (torecsys_amd/dist.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the fused lookup+FM
-forward kernel, timed live with HIP events on its launch stream) and `cpu_baseline` (the CPU oracle timed
-on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0 (the last line of stdout).  A plain run does only what that headline needs: set
+up, warm up, time the K steps, print the line.  ``--full`` adds everything else the benchmark measures or checks:
+`roofline` (the fused lookup+FM forward kernel, sampled with HIP events / device timestamps), the large-table and
+model-kernel rooflines, the DCN / xDeepFM and zipf / skewed legs, the end-to-end self check against the CPU oracle and
+`cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample).
+
+``--dump-outputs DIR``: after the timed steps, what the last timed step computed -- the loss and every parameter
+gradient (a fixed, seeded sample of rows for a table too large to dump whole) -- as DIR/<name>.npy in float32, so that
+two builds can be compared output for output (the inputs are seeded: identical from run to run).
 """
 import argparse
 import json
@@ -61,6 +67,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: kernel rooflines (incl. the "
+                         "large-table ones), the DCN / xDeepFM and zipf / skewed legs, the self check against the CPU "
+                         "oracle, the CPU baseline, the sharded phase diagnostics (the --no-* options below opt out of "
+                         "single parts); a plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss and the parameter gradients of the last timed step as "
+                         "DIR/<name>.npy (float32; a seeded row sample of a table too large to dump whole; with more "
+                         "than one rank, rank 0 writes its own shard of a row-sharded table)")
     ap.add_argument("--batch", type=int, default=65536, help="samples per GPU")
     ap.add_argument("--fields", type=int, default=39)
     ap.add_argument("--embed", type=int, default=64)
@@ -129,7 +144,10 @@ def parse():
     ap.add_argument("--aten-head", action="store_true",
                     help="A/B: the models' scalar head and BCEWithLogitsLoss as ATen ops (~35 launches) instead of "
                          "functional.ctr_logit / fused.BCEWithLogitsLoss (csrc/head.hip)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:       # a plain run: the headline figure only (module docstring)
+        a.no_cpu_baseline = a.no_large_table = a.no_other_models = a.no_variants = True
+    return a
 
 
 def field_sizes(total_rows, n_fields, layout="uniform"):
@@ -238,6 +256,53 @@ def self_check(a, inputs, model, idx, sizes, rows=4096):
     return {"rows": rows, "max_rel_err_logits": round(err, 6), "tolerance": 1e-2 if a.dtype == "bf16" else 1e-5,
             "ok": bool(err <= (1e-2 if a.dtype == "bf16" else 1e-5)),
             "what": "product-path logits of the first rows of timed batch 0 vs the fp32 oracle on the same parameters"}
+
+
+DUMP_SAMPLE_ROWS = 65536          # rows kept of a tensor above DUMP_WHOLE_MAX elements (the E = 64 table's gradient)
+DUMP_WHOLE_MAX = 1 << 22
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sampled_sparse_rows(t, rows):
+    """rows ``rows`` (sorted) of a sparse COO gradient over dim 0 -- what a row-sharded table beyond
+    dist.DENSE_GRAD_MAX_ROWS returns -- as a dense block; rows the step did not touch are zero"""
+    t = t.coalesce()
+    ids, vals = t.indices()[0], t.values()
+    out = torch.zeros((rows.numel(),) + tuple(t.shape[1:]), dtype=vals.dtype, device=vals.device)
+    if ids.numel():
+        pos = torch.searchsorted(ids, rows).clamp_max(ids.numel() - 1)
+        hit = ids[pos] == rows
+        out[hit] = vals[pos[hit]]
+    return out
+
+
+def dump_outputs(out_dir, loss, named_params, with_params):
+    """--dump-outputs: what a caller of the timed step receives from its last step -- the loss and the gradient of every
+    parameter (and, when an optimizer step is part of the step, the updated parameters) -- as <out_dir>/<name>.npy in
+    float32.  A tensor above DUMP_WHOLE_MAX elements is reduced to DUMP_SAMPLE_ROWS rows drawn with a fixed seed (sorted),
+    the same rows in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    for n, p in named_params:
+        if p.grad is not None:
+            arrays["grad." + n] = p.grad
+        if with_params:
+            arrays["param." + n] = p
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.rename(None) if t.has_names() else t
+        if t.numel() > DUMP_WHOLE_MAX and t.dim() >= 1:
+            g = torch.Generator().manual_seed(0)
+            rows = torch.randint(0, t.shape[0], (DUMP_SAMPLE_ROWS,), generator=g).sort().values.to(t.device)
+            t = _sampled_sparse_rows(t, rows) if t.is_sparse else t[rows]
+        elif t.is_sparse:
+            t = t.to_dense()
+        arr = t.float().cpu().numpy()
+        total += arr.nbytes
+        assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def _mlp_params(sd, prefix):
@@ -513,6 +578,7 @@ def variant_legs(a):
         for k, v in kw.items():
             setattr(b, k, v)
         b.steps, b.warmup = a.variant_steps, max(2, a.variant_steps // 4)
+        b.dump_outputs = None
         b.no_cpu_baseline = b.no_large_table = b.no_other_models = b.no_variants = True
         try:
             r = run(b)
@@ -864,8 +930,8 @@ def run(a):
         if first_kernel:       # the E = 1 first-order lookup of the same indices: the other half of SURVEY 8d's unit
             _abi.time_kernel(first_kernel, True, expect=a.steps // every + 2, every=every)
 
-    if not sharded and not use_graph:   # the sharded step reports no single-kernel roofline (alg bytes depend on the routing)
-        enable_kernel_timing()
+    if not sharded and not use_graph and a.full:   # the sharded step reports no single-kernel roofline (alg bytes depend on
+        enable_kernel_timing()                     # the routing)
     graph_fn = None
     ksteps_used = [1]
     if use_graph:
@@ -944,7 +1010,8 @@ def run(a):
             use_graph = False
             step = eager_step
             torch.cuda.synchronize()
-            enable_kernel_timing()
+            if a.full:
+                enable_kernel_timing()
             for _ in range(a.warmup):
                 step()
             _abi.kernel_times_ms(roof_kernel)
@@ -1005,6 +1072,9 @@ def run(a):
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:      # before anything below re-runs or re-captures the step
+        dump_outputs(a.dump_outputs, loss, [("inputs." + n, p) for n, p in inputs.named_parameters()]
+                     + [("model." + n, p) for n, p in model.named_parameters()], a.optimizer != "none")
     if prof:
         import pstats
         pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(18)
@@ -1041,7 +1111,7 @@ def run(a):
     _stage("timed region done")
     device_span_ms = span0.elapsed_time(span1)
     shard_diag = None
-    if sharded:
+    if sharded and a.full:
         # diagnostic leg, outside the timed region: a few more steps with a HIP event pair around every phase of the
         # sharded lookup (on the stream it runs on) and the bytes each rank puts on the wire
         from torecsys_amd import dist as _d
@@ -1063,7 +1133,7 @@ def run(a):
                       "pipelined": bool(pipelined), "lookups": dict(_d.lookup_stats), "routes": dict(_d.route_stats),
                       "note": "device ms per call of each phase (two tables per step share the route); rank 0 only"}
     sampled_replays = 0
-    if use_graph and not sharded:
+    if use_graph and not sharded and a.full:
         # the roofline kernel inside the step, sampled AFTER the timed region: a second capture of the same step with its
         # launches of the roofline kernel (and of the first-order lookup) bracketed by two device timestamp marks each;
         # every replay adds one sample per kernel.  The timed replays above carried none of these launches.

@@ -193,103 +193,243 @@ def test_fused_optimizer_state_dict_roundtrip():
         FusedSparseAdam().load_state_dict(sd, [("other", p2)])
 
 
-REFERENCE = "/root/reference"
+STANDIN = "trs_standin"       # a package laid out like torecsys: layers / inputs modules, models that import layers by name
+
+_STANDIN_MODELS_SRC = '''
+import torch
+import torch.nn as nn
 
 
-def _import_real_reference():
-    """The stub recipe of SURVEY 8c (tests/golden/make_golden.py): skip torecsys/__init__.py, stub torchvision."""
-    import importlib
-    saved = {k: sys.modules.get(k) for k in ("torecsys", "torchvision", "torchvision.transforms")}
-    pkg = types.ModuleType("torecsys")
-    pkg.__path__ = [REFERENCE + "/torecsys"]
-    sys.modules["torecsys"] = pkg
-    tv, tvt = types.ModuleType("torchvision"), types.ModuleType("torchvision.transforms")
-    tv.transforms = tvt
-    sys.modules["torchvision"], sys.modules["torchvision.transforms"] = tv, tvt
-    mods = [importlib.import_module("torecsys." + m) for m in ("inputs", "layers", "models")]
-    return pkg, mods, saved
+class FactorizationMachineModel(nn.Module):
+    def __init__(self, use_bias=True, dropout_p=None):
+        super().__init__()
+        self.use_bias = use_bias
+        self.fm = FMLayer(dropout_p)
+        self.bias = nn.Parameter(torch.empty(1, 1).uniform_()) if use_bias else None
+
+    def forward(self, feat_inputs, emb_inputs):
+        emb_inputs.names = ("B", "N", "E")                    # in-place renaming of the incoming block
+        first = feat_inputs.flatten(("N", "E"), "O").sum("O", keepdim=True).rename(None)
+        out = self.fm(emb_inputs).rename(None).sum(dim=1, keepdim=True) + first
+        return out + self.bias if self.use_bias else out
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REFERENCE + "/torecsys"),
-                    reason="the reference never travels to the GPU box: build-container test")
-def test_patch_on_the_real_reference_models():
-    """patch() on the REAL reference: the four north-star models (models/ctr/factorization_machine.py:35,
-    deep_fm.py:46-53, deep_and_cross_network.py:43-56, xdeep_fm.py:60-79) and the Inputs router build on torecsys_amd
-    classes for every hot-path child -- interaction layer, deep MLP, embeddings, router -- with the reference's
-    state_dict keys, and a patched MultiIndicesEmbedding fuses the FM term by default."""
+class DeepFactorizationMachineModel(nn.Module):
+    def __init__(self, embed_size, num_fields, deep_layer_sizes, fm_dropout_p=None, deep_dropout_p=None):
+        super().__init__()
+        self.fm = FMLayer(fm_dropout_p)
+        self.deep = DNNLayer(inputs_size=num_fields * embed_size, output_size=1, layer_sizes=deep_layer_sizes,
+                             dropout_p=deep_dropout_p, activation=nn.ReLU())
+
+    def forward(self, feat_inputs, emb_inputs):
+        emb_inputs.names = ("B", "N", "E")
+        first = feat_inputs.flatten(("N", "E"), "O").sum("O", keepdim=True).rename(None)
+        fm = self.fm(emb_inputs).rename(None).sum(dim=1, keepdim=True)
+        deep = self.deep(emb_inputs.flatten(("N", "E"), "E"))
+        return (deep.rename(None) if deep.has_names() else deep) + fm + first
+
+
+class DeepAndCrossNetworkModel(nn.Module):
+    def __init__(self, inputs_size, num_fields, deep_output_size, deep_layer_sizes, cross_num_layers, output_size=1):
+        super().__init__()
+        self.cross = CrossNetworkLayer(inputs_size=inputs_size, num_layers=cross_num_layers)
+        self.deep = DNNLayer(inputs_size=inputs_size, output_size=deep_output_size, layer_sizes=deep_layer_sizes,
+                             activation=nn.ReLU())
+        self.fc = nn.Linear(num_fields * (inputs_size + deep_output_size), output_size)
+
+    def forward(self, emb_inputs):
+        both = torch.cat((self.cross(emb_inputs).rename(None), self.deep(emb_inputs).rename(None)), dim=2)
+        return self.fc(both.reshape(both.shape[0], -1))
+
+
+class XDeepFactorizationMachineModel(nn.Module):
+    def __init__(self, embed_size, num_fields, cin_layer_sizes, deep_layer_sizes):
+        super().__init__()
+        self.cin = CINLayer(embed_size=embed_size, num_fields=num_fields, output_size=1, layer_sizes=cin_layer_sizes,
+                            is_direct=False, use_bias=True, use_batchnorm=True, activation=nn.ReLU())
+        self.deep = DNNLayer(inputs_size=embed_size * num_fields, output_size=1, layer_sizes=deep_layer_sizes,
+                             activation=nn.ReLU())
+        self.bias = nn.Parameter(torch.empty(1).uniform_())
+
+    def forward(self, feat_inputs, emb_inputs):
+        first = feat_inputs.flatten(("N", "E"), "O").sum("O", keepdim=True).rename(None)
+        deep = self.deep(emb_inputs.flatten(("N", "E"), "E"))
+        return self.cin(emb_inputs).rename(None) + deep.rename(None) + first + self.bias
+'''
+
+
+def _standin_layer(name, dropin):
+    """a stand-in layer class: same constructor and parameter layout (hence state_dict keys) as the drop-in, but a class
+    of the stand-in package, not a torecsys_amd one"""
+    def __init__(self, *args, **kwargs):
+        nn.Module.__init__(self)
+        proto = dropin(*args, **kwargs)
+        for n, c in proto.named_children():
+            self.add_module(n, c)
+        for n, p in proto.named_parameters(recurse=False):
+            self.register_parameter(n, p)
+        for n, b in proto.named_buffers(recurse=False):
+            self.register_buffer(n, b)
+    return type(name, (nn.Module,), {"__init__": __init__, "__module__": STANDIN + ".layers"})
+
+
+def _build_standin_package():
+    """``trs_standin``: ``.layers`` holds every class name patch() rebinds (aliases share one class, as in torecsys),
+    ``.inputs`` the three index embeddings and the ``Inputs`` router, ``.models`` four CTR models whose module holds
+    ``from .layers import ...`` copies of the names and whose forwards do named-tensor plumbing of their own."""
+    from torecsys_amd import inputs as I, layers as L
+    from torecsys_amd import patching as P
+    pkg, lay, inp, mdl = (types.ModuleType(STANDIN + s) for s in ("", ".layers", ".inputs", ".models"))
+    seen = {}
+    for n in P._LAYER_NAMES + P._MLP_NAMES:
+        dropin = getattr(L, n)
+        if dropin not in seen:
+            seen[dropin] = _standin_layer(dropin.__name__, dropin)
+        setattr(lay, n, seen[dropin])
+
+    class MultiIndicesEmbedding(nn.Module):
+        def __init__(self, embed_size, field_sizes):
+            super().__init__()
+            self.fuse_fm = False
+            self.embedding = nn.Embedding(sum(field_sizes), embed_size)
+
+        def set_schema(self, inputs):
+            self.schema = list(inputs)
+
+    class Inputs(nn.Module):
+        def __init__(self, schema):
+            super().__init__()
+            for k, m in schema.items():
+                self.add_module(k, m)
+
+    for c in (MultiIndicesEmbedding, Inputs):
+        c.__module__ = STANDIN + ".inputs"
+    inp.MultiIndicesEmbedding, inp.Inputs = MultiIndicesEmbedding, Inputs
+    inp.SingleIndexEmbedding = _standin_layer("SingleIndexEmbedding", I.SingleIndexEmbedding)
+    inp.MultiIndicesFieldAwareEmbedding = _standin_layer("MultiIndicesFieldAwareEmbedding", I.MultiIndicesFieldAwareEmbedding)
+    for n in ("FMLayer", "DNNLayer", "CrossNetworkLayer", "CINLayer"):
+        setattr(mdl, n, getattr(lay, n))          # `from torecsys.layers import FMLayer, DNNLayer` in a model module
+    mdl.__dict__["__name__"] = mdl.__name__
+    exec(_STANDIN_MODELS_SRC, mdl.__dict__)
+    pkg.layers, pkg.inputs, pkg.models = lay, inp, mdl
+    return pkg, lay, inp, mdl
+
+
+@pytest.fixture
+def standin_pkg():
+    import torecsys_amd
+    mods = _build_standin_package()
+    saved = {m.__name__: sys.modules.get(m.__name__) for m in mods}
+    for m in mods:
+        sys.modules[m.__name__] = m
+    try:
+        yield mods
+    finally:
+        torecsys_amd.unpatch()
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+
+
+def _build_standin_models(lay, inp, mdl, N, E, sizes):
+    mods = {
+        "fm": mdl.FactorizationMachineModel(use_bias=True, dropout_p=0.0),
+        "deepfm": mdl.DeepFactorizationMachineModel(embed_size=E, num_fields=N, deep_layer_sizes=[16, 16],
+                                                    fm_dropout_p=0.0, deep_dropout_p=[0.0, 0.0]),
+        "dcn": mdl.DeepAndCrossNetworkModel(inputs_size=E, num_fields=N, deep_output_size=4, deep_layer_sizes=[16, 16],
+                                            cross_num_layers=3),
+        "xdeepfm": mdl.XDeepFactorizationMachineModel(embed_size=E, num_fields=N, cin_layer_sizes=[6, 6],
+                                                      deep_layer_sizes=[16, 16]),
+    }
+    emb = inp.MultiIndicesEmbedding(embed_size=E, field_sizes=sizes)
+    feat = inp.MultiIndicesEmbedding(embed_size=1, field_sizes=sizes)
+    emb.set_schema(["c%d" % i for i in range(N)])
+    feat.set_schema(["c%d" % i for i in range(N)])
+    router = inp.Inputs(schema={"feat_inputs": feat, "emb_inputs": emb})
+    return mods, emb, router
+
+
+def test_patch_on_a_standin_package(standin_pkg):
+    """patch() / unpatch() on a package laid out like torecsys: every hot-path name of the layers and inputs modules and
+    the `from ... import` copies inside the models module are rebound (the MLP aliases included), the models built
+    afterwards hold torecsys_amd classes for every hot-path child with unchanged state_dict keys and load a checkpoint of
+    the un-patched models, the models' forwards are wrapped with the one-kernel heads, the router is rebound and a
+    patched MultiIndicesEmbedding fuses the FM term by default; the mlp / router / fuse_fm / heads opt-outs hold and
+    unpatch() restores every name, every forward and inputs.DEFAULT_FUSE_FM."""
     import warnings
     import torecsys_amd
     from torecsys_amd import inputs as I, layers as L
+    from torecsys_amd import patching as P
     warnings.filterwarnings("ignore")
-    pkg, (ref_inputs, ref_layers, ref_models), saved = _import_real_reference()
+    pkg, lay, inp, mdl = standin_pkg
+    N, E, sizes = 5, 8, [7, 3, 11, 5, 9]
+    orig_names = {(m.__name__, n): getattr(m, n) for m in (lay, inp, mdl) for n in list(vars(m))
+                  if n in P._LAYER_NAMES + P._MLP_NAMES + P._INPUT_NAMES + P._ROUTER_NAMES}
+    model_classes = [getattr(mdl, n) for n in P._HEADS]
+    orig_forwards = {c: c.__dict__["forward"] for c in model_classes}
+    fuse_default = I.DEFAULT_FUSE_FM
+
+    ref_mods, ref_emb, ref_router = _build_standin_models(lay, inp, mdl, N, E, sizes)
+    ref_keys = {k: list(m.state_dict().keys()) for k, m in ref_mods.items()}
+    ref_router_keys = list(ref_router.state_dict().keys())
+    assert type(ref_mods["deepfm"].deep).__module__ == STANDIN + ".layers"
+
+    assert torecsys_amd.patch(pkg) is pkg
     try:
-        N, E = 5, 8
-        sizes = [7, 3, 11, 5, 9]
-
-        def build_all():
-            mods = {
-                "fm": ref_models.FactorizationMachineModel(use_bias=True, dropout_p=0.0),
-                "deepfm": ref_models.DeepFactorizationMachineModel(embed_size=E, num_fields=N, deep_layer_sizes=[16, 16],
-                                                                   fm_dropout_p=0.0),
-                "dcn": ref_models.DeepAndCrossNetworkModel(inputs_size=E, num_fields=N, deep_output_size=4,
-                                                           deep_layer_sizes=[16, 16], cross_num_layers=3),
-                "xdeepfm": ref_models.XDeepFactorizationMachineModel(embed_size=E, num_fields=N, cin_layer_sizes=[6, 6],
-                                                                     deep_layer_sizes=[16, 16]),
-            }
-            emb = ref_inputs.MultiIndicesEmbedding(embed_size=E, field_sizes=sizes)
-            feat = ref_inputs.MultiIndicesEmbedding(embed_size=1, field_sizes=sizes)
-            emb.set_schema(["c%d" % i for i in range(N)])
-            feat.set_schema(["c%d" % i for i in range(N)])
-            router = ref_inputs.Inputs(schema={"feat_inputs": feat, "emb_inputs": emb})
-            return mods, emb, router
-
-        ref_mods, ref_emb, ref_router = build_all()                       # the reference's own classes
-        ref_keys = {k: list(m.state_dict().keys()) for k, m in ref_mods.items()}
-        ref_router_keys = list(ref_router.state_dict().keys())
-        assert type(ref_mods["deepfm"].deep).__module__.startswith("torecsys.")
-
-        torecsys_amd.patch(pkg)
-        try:
-            mods, emb, router = build_all()
-            assert isinstance(mods["fm"].fm, L.FactorizationMachineLayer)
-            assert isinstance(mods["deepfm"].fm, L.FactorizationMachineLayer)
-            assert isinstance(mods["deepfm"].deep, L.MultilayerPerceptionLayer)
-            assert isinstance(mods["dcn"].cross, L.CrossNetworkLayer)
-            assert isinstance(mods["dcn"].deep, L.MultilayerPerceptionLayer)       # the per-field MLP (SURVEY 8f N4)
-            assert isinstance(mods["xdeepfm"].cin, L.CompressInteractionNetworkLayer)
-            assert isinstance(mods["xdeepfm"].deep, L.MultilayerPerceptionLayer)
-            assert isinstance(emb, I.MultiIndicesEmbedding) and emb.fuse_fm is True
-            assert isinstance(router, I.Inputs)
-            for alias in ("DNNLayer", "DenseLayer", "FullyConnectLayer", "FeedForwardLayer", "MultilayerPerceptionLayer"):
-                assert getattr(ref_layers, alias) is L.MultilayerPerceptionLayer, alias
-            for k, m in mods.items():
-                assert list(m.state_dict().keys()) == ref_keys[k], k
-                for c in m.modules():      # nothing of the reference's layer package is left inside the models
-                    assert not type(c).__module__.startswith("torecsys.layers"), (k, type(c))
-            assert list(router.state_dict().keys()) == ref_router_keys
-            # reference checkpoints load unchanged
-            for k, m in mods.items():
-                m.load_state_dict(ref_mods[k].state_dict())
-            # opt-outs
-            torecsys_amd.unpatch()
-            assert I.DEFAULT_FUSE_FM is False
-            torecsys_amd.patch(pkg, fuse_fm=False, mlp=False, router=False)
-            m2, e2, r2 = build_all()
-            assert e2.fuse_fm is False and not isinstance(r2, I.Inputs)
-            assert not isinstance(m2["deepfm"].deep, L.MultilayerPerceptionLayer)
-            assert isinstance(m2["deepfm"].fm, L.FactorizationMachineLayer)
-        finally:
-            torecsys_amd.unpatch()
-        m3, e3, _ = build_all()
-        assert type(m3["deepfm"].fm).__module__.startswith("torecsys.layers") and not isinstance(e3, I.MultiIndicesEmbedding)
+        for (mod_name, n), old in orig_names.items():
+            new = getattr(sys.modules[mod_name], n)
+            assert new is not old and new is getattr(I if n in P._INPUT_NAMES + P._ROUTER_NAMES else L, n), (mod_name, n)
+        for alias in P._MLP_NAMES:
+            assert getattr(lay, alias) is L.MultilayerPerceptionLayer, alias
+        assert mdl.DNNLayer is L.MultilayerPerceptionLayer and mdl.CrossNetworkLayer is L.CrossNetworkLayer
+        assert I.DEFAULT_FUSE_FM is True
+        for c in model_classes:
+            assert getattr(c.__dict__["forward"], "_trs_head", False), c
+        mods, emb, router = _build_standin_models(lay, inp, mdl, N, E, sizes)
+        assert isinstance(mods["fm"].fm, L.FactorizationMachineLayer)
+        assert isinstance(mods["deepfm"].fm, L.FactorizationMachineLayer)
+        assert isinstance(mods["deepfm"].deep, L.MultilayerPerceptionLayer)
+        assert isinstance(mods["dcn"].cross, L.CrossNetworkLayer)
+        assert isinstance(mods["dcn"].deep, L.MultilayerPerceptionLayer)
+        assert isinstance(mods["xdeepfm"].cin, L.CompressInteractionNetworkLayer)
+        assert isinstance(mods["xdeepfm"].deep, L.MultilayerPerceptionLayer)
+        assert isinstance(emb, I.MultiIndicesEmbedding) and emb.fuse_fm is True
+        assert isinstance(router, I.Inputs)
+        for k, m in mods.items():
+            assert list(m.state_dict().keys()) == ref_keys[k], k
+            for c in m.modules():      # nothing of the stand-in's layer module is left inside the models
+                assert not type(c).__module__.startswith(STANDIN + ".layers"), (k, type(c))
+            m.load_state_dict(ref_mods[k].state_dict())
+        assert list(router.state_dict().keys()) == ref_router_keys
+        router.load_state_dict(ref_router.state_dict())
+        assert torecsys_amd.patch(pkg) is pkg          # a second patch() changes nothing
+        assert lay.FMLayer is L.FMLayer and getattr(mdl.DeepFactorizationMachineModel.forward, "_trs_head", False)
     finally:
-        for k in [k for k in sys.modules if k == "torecsys" or k.startswith("torecsys.")]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
+        torecsys_amd.unpatch()
+    for (mod_name, n), old in orig_names.items():
+        assert getattr(sys.modules[mod_name], n) is old, (mod_name, n)
+    for c in model_classes:
+        assert c.__dict__["forward"] is orig_forwards[c], c
+    assert I.DEFAULT_FUSE_FM is fuse_default is False
+
+    # opt-outs
+    torecsys_amd.patch(pkg, fuse_fm=False, mlp=False, router=False, heads=False)
+    try:
+        m2, e2, r2 = _build_standin_models(lay, inp, mdl, N, E, sizes)
+        assert isinstance(e2, I.MultiIndicesEmbedding) and e2.fuse_fm is False and I.DEFAULT_FUSE_FM is False
+        assert not isinstance(r2, I.Inputs) and inp.Inputs is orig_names[(inp.__name__, "Inputs")]
+        assert not isinstance(m2["deepfm"].deep, L.MultilayerPerceptionLayer)
+        assert all(getattr(lay, a) is orig_names[(lay.__name__, a)] for a in P._MLP_NAMES)
+        assert isinstance(m2["deepfm"].fm, L.FactorizationMachineLayer) and isinstance(m2["dcn"].cross, L.CrossNetworkLayer)
+        for c in model_classes:
+            assert c.__dict__["forward"] is orig_forwards[c], c
+    finally:
+        torecsys_amd.unpatch()
+    m3, e3, r3 = _build_standin_models(lay, inp, mdl, N, E, sizes)
+    assert type(m3["deepfm"].fm).__module__ == STANDIN + ".layers" and not isinstance(e3, I.MultiIndicesEmbedding)
+    assert not isinstance(r3, I.Inputs)
 
 
 def _install_cpu_standins(monkeypatch):
@@ -336,190 +476,64 @@ def _install_cpu_standins(monkeypatch):
     return calls
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REFERENCE + "/torecsys"),
-                    reason="the reference never travels to the GPU box: build-container test")
-def test_reference_model_forwards_run_over_the_dropins(monkeypatch):
-    """The REAL reference's model code drives the drop-in modules: ``patch()`` the imported reference, build its four
-    north-star models and its Inputs router from ITS classes, and run forward + backward through
-    ``Inputs -> model.forward`` -- the reference's own named-tensor plumbing (models/ctr/deep_fm.py:68-108
-    ``flatten(('N','E'),'E')`` / ``cat(dim='O')`` / ``sum(dim='O')``, deep_and_cross_network.py:71-98, xdeep_fm.py:100-122,
-    factorization_machine.py:56-71) on tensors that come out of this package's modules.  The HIP entry points are
-    replaced by oracle-backed CPU stand-ins INSIDE this test only (as tests/test_dist_gloo.py does for the exchange).
-    Checked: the ``_trs_fused_fm`` side channel survives the models' in-place ``names = ...`` assignments and is consumed by
-    the patched FMLayer (no second FM pass); outputs are (B,1) and un-named like the reference's; logits and the
-    embedding-table gradients equal the un-patched reference with the same parameters."""
+def test_standin_model_forwards_carry_the_fused_fm_term(standin_pkg, monkeypatch):
+    """Model code of the user's package drives the drop-ins: after ``patch()``, the stand-in FM / DeepFM models' own
+    forwards -- named-tensor plumbing on the blocks that come out of this package's lookups (in-place
+    ``emb_inputs.names = ...``, ``flatten(('N', 'E'), ...)``, ``sum('O')``) -- run forward + backward through ``Inputs``.
+    The HIP entry points are replaced by oracle-backed CPU stand-ins inside this test only.  Checked: the fused FM term
+    rides from the lookup to FMLayer through the renaming (one fused lookup per wide-table pass and NOT ONE separate FM
+    pass); logits and the table gradients equal the oracle models on the same parameters; with fuse_fm off the FM
+    layer runs its own pass and the logits are the same."""
     import warnings
     import torecsys_amd
-    from torecsys_amd import inputs as I
     warnings.filterwarnings("ignore")
-    pkg, (ref_inputs, ref_layers, ref_models), saved = _import_real_reference()
-    try:
-        B, N, E = 6, 5, 8
-        sizes = [7, 3, 11, 5, 9]
-        g = torch.Generator().manual_seed(3)
-        cols = {"c%d" % i: torch.randint(0, sizes[i], (B,), generator=g) for i in range(N)}
+    pkg, lay, inp, mdl = standin_pkg
+    B, N, E, sizes = 6, 5, 8, [7, 3, 11, 5, 9]
+    g = torch.Generator().manual_seed(3)
+    cols = {"c%d" % i: torch.randint(0, sizes[i], (B,), generator=g) for i in range(N)}
+    idx = torch.stack([cols["c%d" % i] for i in range(N)], dim=1)
+    off = O.field_offsets(sizes)
 
-        def build_all():
+    def run(fuse_fm):
+        torecsys_amd.patch(pkg, fuse_fm=fuse_fm)
+        try:
+            calls = _install_cpu_standins(monkeypatch)
             torch.manual_seed(5)
-            mods = {
-                "fm": ref_models.FactorizationMachineModel(use_bias=True, dropout_p=0.0),
-                "deepfm": ref_models.DeepFactorizationMachineModel(embed_size=E, num_fields=N, deep_layer_sizes=[16, 16],
-                                                                   fm_dropout_p=0.0, deep_dropout_p=[0.0, 0.0]),
-                "dcn": ref_models.DeepAndCrossNetworkModel(inputs_size=E, num_fields=N, deep_output_size=4,
-                                                           deep_layer_sizes=[16, 16], cross_num_layers=3,
-                                                           deep_dropout_p=[0.0, 0.0]),
-                "xdeepfm": ref_models.XDeepFactorizationMachineModel(embed_size=E, num_fields=N, cin_layer_sizes=[6, 6],
-                                                                     deep_layer_sizes=[16, 16], deep_dropout_p=[0.0, 0.0]),
-            }
-            emb = ref_inputs.MultiIndicesEmbedding(embed_size=E, field_sizes=sizes)
-            feat = ref_inputs.MultiIndicesEmbedding(embed_size=1, field_sizes=sizes)
-            emb.set_schema(["c%d" % i for i in range(N)])
-            feat.set_schema(["c%d" % i for i in range(N)])
-            router = ref_inputs.Inputs(schema={"feat_inputs": feat, "emb_inputs": emb})
-            return mods, router
-
-        def run(mods, router):
+            mods, _, router = _build_standin_models(lay, inp, mdl, N, E, sizes)
             out = {}
-            for k, m in mods.items():
+            for k in ("fm", "deepfm"):
+                m = mods[k]
                 for p in list(router.parameters()) + list(m.parameters()):
                     p.grad = None
                 d = router({c: v.clone() for c, v in cols.items()})
-                y = m(emb_inputs=d["emb_inputs"]) if k == "dcn" else m(**d)
-                y.rename(None).sum().backward()
-                grads = {n: p.grad.clone() for n, p in router.named_parameters() if p.grad is not None}
-                out[k] = (y, grads)
-            return out
-
-        ref_mods, ref_router = build_all()                 # un-patched: the reference's own layers end to end
-        ref_out = run(ref_mods, ref_router)
-
-        torecsys_amd.patch(pkg)
-        try:
-            calls = _install_cpu_standins(monkeypatch)
-            mods, router = build_all()
-            assert isinstance(router, I.Inputs)
-            router.load_state_dict(ref_router.state_dict())
-            for k in mods:
-                mods[k].load_state_dict(ref_mods[k].state_dict())
-            got = run(mods, router)
-            for k in mods:
-                y, grads = got[k]
-                y0, grads0 = ref_out[k]
-                assert tuple(y.shape) == (B, 1) == tuple(y0.shape), k
-                assert y.names == y0.names, (k, y.names, y0.names)
-                err = float((y.rename(None) - y0.rename(None)).abs().max() / y0.rename(None).abs().max())
-                assert err <= 1e-5, (k, err)
-                assert set(grads) == set(grads0), (k, sorted(grads), sorted(grads0))
-                for n in grads:
-                    gerr = float((grads[n] - grads0[n]).abs().max() / grads0[n].abs().max().clamp_min(1e-30))
-                    assert gerr <= 1e-5, (k, n, gerr)
-            # the fused FM term travelled from the lookup to FMLayer through the models' own renaming: one fused lookup per
-            # wide-table pass, and NOT ONE separate FM pass (fm and deepfm each have an FMLayer)
-            assert calls["embed_fm"] == 4 and calls["gather_rows"] == 4 and calls["fm_layer"] == 0, calls
-            assert calls["cross_network"] == 1 and calls["cin_contract"] == 2, calls
-            # and without the side channel (fuse_fm off) the same models fall back to the FM layer's own pass
-            torecsys_amd.unpatch()
-            torecsys_amd.patch(pkg, fuse_fm=False)
-            calls2 = _install_cpu_standins(monkeypatch)
-            mods2, router2 = build_all()
-            router2.load_state_dict(ref_router.state_dict())
-            for k in mods2:
-                mods2[k].load_state_dict(ref_mods[k].state_dict())
-            got2 = run(mods2, router2)
-            for k in mods2:
-                err = float((got2[k][0].rename(None) - ref_out[k][0].rename(None)).abs().max())
-                assert err <= 1e-5 * float(ref_out[k][0].rename(None).abs().max()), (k, err)
-            assert calls2["embed_fm"] == 0 and calls2["fm_layer"] == 2, calls2
+                y = m(**d)
+                assert tuple(y.shape) == (B, 1) and not y.has_names(), (k, y.names)
+                y.sum().backward()
+                sd = {n: p.detach() for n, p in m.named_parameters()}
+                w, w1 = router.emb_inputs.embedding.weight, router.feat_inputs.embedding.weight
+                wr, w1r = w.detach().clone().requires_grad_(), w1.detach().clone().requires_grad_()
+                emb, feat = O.multi_indices_embedding(wr, idx, off), O.multi_indices_embedding(w1r, idx, off)
+                if k == "fm":
+                    ref = O.fm_model(feat, emb, sd["bias"])
+                else:
+                    names = [n[:-len(".weight")] for n in sd if n.startswith("deep.") and n.endswith(".weight")]
+                    ref = O.deepfm_model(feat, emb, [sd[n + ".weight"] for n in names], [sd[n + ".bias"] for n in names])
+                ref.sum().backward()
+                assert float((y.detach() - ref.detach()).abs().max()) <= 1e-5 * float(ref.abs().max()), k
+                for got, want in ((w.grad, wr.grad), (w1.grad, w1r.grad)):
+                    assert float((got - want).abs().max()) <= 1e-5 * float(want.abs().max()), k
+                out[k] = y.detach()
+            return out, calls
         finally:
             torecsys_amd.unpatch()
-    finally:
-        for k in [k for k in sys.modules if k == "torecsys" or k.startswith("torecsys.")]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
 
-
-@pytest.mark.skipif(not __import__("os").path.isdir(REFERENCE + "/torecsys"),
-                    reason="the reference never travels to the GPU box: build-container test")
-def test_reference_stacked_input_of_single_index_embeddings_is_one_lookup(monkeypatch):
-    """The REAL reference's ``StackedInput`` (inputs/base/stacked_inp.py:94-134) over patched ``SingleIndexEmbedding``s
-    inside the patched ``Inputs`` router: the router recognises the schema and issues ONE table-list lookup
-    (F_.gather_rows_tables; replaced here by an oracle-backed CPU stand-in, as the other entry points are) instead of N
-    lookups + a cat; output names / shape / values and every table's gradient equal the un-patched reference."""
-    import warnings
-    import torecsys_amd
-    from oracle import cpu_ref as O
-    from torecsys_amd import functional as F_
-    from torecsys_amd import inputs as I
-    warnings.filterwarnings("ignore")
-    pkg, (ref_inputs, ref_layers, ref_models), saved = _import_real_reference()
-    try:
-        B, E = 9, 8
-        sizes = [7, 3, 11, 5]
-        g = torch.Generator().manual_seed(4)
-        cols = {"c%d" % i: torch.randint(0, v, (B,), generator=g) for i, v in enumerate(sizes)}
-
-        def build():
-            torch.manual_seed(2)
-            children = []
-            for i, v in enumerate(sizes):
-                c = ref_inputs.SingleIndexEmbedding(E, v)
-                c.set_schema(["c%d" % i])
-                children.append(c)
-            return ref_inputs.Inputs(schema={"emb_inputs": ref_inputs.StackedInput(children)})
-
-        def run(router):
-            out = router({k: v.clone() for k, v in cols.items()})["emb_inputs"]
-            (out.rename(None) * torch.arange(1, E + 1).float()).sum().backward()
-            return out, {n: p.grad.clone() for n, p in router.named_parameters()}
-
-        ref_router = build()
-        y0, g0 = run(ref_router)
-        torecsys_amd.patch(pkg)
-        try:
-            calls = {"tables": 0, "rows": 0}
-
-            def gather_rows_tables(weights, idx):
-                calls["tables"] += 1
-                idx = idx.rename(None) if idx.has_names() else idx
-                return torch.cat([O.single_index_embedding(w, idx[:, i:i + 1], None) for i, w in enumerate(weights)], 1)
-
-            def gather_rows(weight, idx, offsets=None, padding_idx=None, opt=None):
-                calls["rows"] += 1
-                return O.single_index_embedding(weight, idx.rename(None) if idx.has_names() else idx, padding_idx)
-
-            monkeypatch.setattr(F_, "gather_rows_tables", gather_rows_tables)
-            monkeypatch.setattr(F_, "gather_rows", gather_rows)
-            monkeypatch.setattr(F_, "pack_columns_supported", lambda cols: False)
-            monkeypatch.setattr(I, "_on_hip", lambda t: True)
-            router = build()
-            assert isinstance(router, I.Inputs) and router.schema["emb_inputs"].__class__.__name__ == "StackedInput"
-            assert all(type(c) is I.SingleIndexEmbedding for c in router.schema["emb_inputs"].inputs)
-            router.load_state_dict(ref_router.state_dict())
-            y, gr = run(router)
-            assert calls == {"tables": 1, "rows": 0}, calls
-            assert y.names == y0.names and tuple(y.shape) == tuple(y0.shape) == (B, len(sizes), E)
-            assert torch.equal(y.rename(None), y0.rename(None))
-            assert set(gr) == set(g0)
-            for n in gr:
-                assert torch.allclose(gr[n], g0[n], rtol=1e-6, atol=0), n
-            # a child with a padding row is outside the one-launch form: the StackedInput's own forward runs
-            monkeypatch.setattr(I, "STACKED_ONE_LAUNCH", False)
-            run(router)
-            assert calls["tables"] == 1 and calls["rows"] == len(sizes), calls
-        finally:
-            torecsys_amd.unpatch()
-    finally:
-        for k in [k for k in sys.modules if k == "torecsys" or k.startswith("torecsys.")]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
+    fused, calls = run(True)
+    # two wide-table lookups (one per model), each fused with the FM term, and no separate FM pass
+    assert calls["embed_fm"] == 2 and calls["gather_rows"] == 2 and calls["fm_layer"] == 0, calls
+    plain, calls2 = run(False)
+    assert calls2["embed_fm"] == 0 and calls2["fm_layer"] == 2, calls2
+    for k in fused:
+        assert torch.allclose(fused[k], plain[k], rtol=1e-5, atol=1e-6), k
 
 
 @pytest.mark.parametrize("N", [2, 3, 7, 16, 32, 33, 39, 40, 48])
@@ -650,3 +664,66 @@ def test_bench_self_launches_for_more_than_one_gpu(monkeypatch):
         bench.main()
     assert seen["path"] == sys.executable and seen["args"][seen["args"].index("--nproc-per-node") + 1] == "2"
     assert seen["args"][-5:] == ["--gpus", "2", "--steps", "4", "--no-tunableop"]
+
+
+def _load_bench(monkeypatch):
+    import importlib.util
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-tunableop"])       # module import must not touch TunableOp files
+    spec = importlib.util.spec_from_file_location("trs_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_leaves_the_extra_legs_to_full(monkeypatch):
+    """a plain `bench.py` run measures the headline only: every extra leg is off unless --full is given, and under --full
+    the --no-* options still opt out of single legs"""
+    bench = _load_bench(monkeypatch)
+    legs = ("no_cpu_baseline", "no_large_table", "no_other_models", "no_variants")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 3 and a.dump_outputs is None
+    assert all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and not any(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not (a.no_large_table or a.no_other_models or a.no_variants)
+
+
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """--dump-outputs: loss and gradients as float32 .npy; a tensor above DUMP_WHOLE_MAX elements -- dense, or the sparse
+    COO gradient of a large row-sharded table -- is cut to the same seeded rows in every call; 64 MB at most"""
+    import numpy as np
+    bench = _load_bench(monkeypatch)
+
+    class P:
+        def __init__(self, grad):
+            self.grad = grad
+
+    V, E = 1_000_000, 64
+    g = torch.Generator().manual_seed(1)
+    big = torch.randn(V, E, generator=g).to(torch.bfloat16)
+    ids = torch.randint(0, 20_000_000, (200_000,), generator=g)
+    sp = torch.sparse_coo_tensor(ids.unsqueeze(0), torch.randn(200_000, 4, generator=g), size=(20_000_000, 4))
+    small_sp = torch.sparse_coo_tensor(torch.tensor([[1, 1, 5]]), torch.ones(3, 3), size=(100, 3))
+    named = [("emb", P(big)), ("shard", P(sp)), ("small", P(small_sp)), ("w", P(torch.randn(400, 400, generator=g))),
+             ("frozen", P(None))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.25), named, False)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grad.emb.npy", "grad.shard.npy", "grad.small.npy", "grad.w.npy", "loss.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+    rows = torch.randint(0, V, (bench.DUMP_SAMPLE_ROWS,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.emb.npy"), big[rows].float().numpy())
+    rows = torch.randint(0, 20_000_000, (bench.DUMP_SAMPLE_ROWS,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.shard.npy"), sp.coalesce().index_select(0, rows).to_dense().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.small.npy"), small_sp.to_dense().numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.25]
+    # the cap: five tensors of DUMP_WHOLE_MAX fp32 elements (16 MB each) are more than 64 MB
+    many = [("t%d" % i, P(torch.zeros(bench.DUMP_WHOLE_MAX))) for i in range(5)]
+    with pytest.raises(AssertionError, match="dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "c"), torch.tensor(0.0), many, False)
