@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TRS_ABI_VERSION 1
+#define TRS_ABI_VERSION 2
 
 enum { TRS_F32 = 0, TRS_BF16 = 1 };
 enum { TRS_I64 = 0, TRS_I32 = 1 };
@@ -361,45 +361,24 @@ int trs_mlp_fused_supported(int32_t num_layers, const int32_t* widths);
 #define TRS_MLP_FAMILY_ROW_OWNER 2
 #define TRS_MLP_FAMILY_MIXED 3      /* row-owner forward, tile backward reading the row-owner sign-bit layout (covered
                                        shapes below 131 072 rows: each direction on the family that is faster there) */
-/* Phases.  Both entry points (and trs_rows_gemm) first copy the weights into MFMA fragment order in the workspace, then run.
- * The copy depends on the parameters only, so a caller may take it off the critical path of its step:
- *   phase = ALL : copy, then run (one call does everything);
- *   phase = PACK: only the copy (+ zeroing of the workspace's partial sums) -- enqueue it on ANY stream as soon as the
- *                 parameters are final, e.g. on a side stream at the start of the step; pointers to rows / outputs /
- *                 masks may be NULL, `rows`, `widths`, `weights`, `biases`, `family` and the workspace must be the ones
- *                 of the RUN call;
- *   phase = RUN : the workspace holds what a PACK call with the same arguments left (the caller orders the two calls:
- *                 same stream, or an event); nothing is copied.                                                       */
+/* Workspace: both entry points (and trs_rows_gemm) first copy the weights into MFMA fragment order in the workspace,
+ * then run.                                                                                                          */
 /* x_stride (trs_mlp_fused_fwd): elements between consecutive rows of x; 0 = widths[0].  A larger stride (a multiple of 8)
  * makes the stack read the first widths[0] columns of wider rows -- the 416-wide tail of a deep branch on the 512-wide
  * output of the library GEMM in front of it; row-owner and mixed family only (TRS_ESHAPE otherwise).  The matching
  * backward may then be called with widths[0] = that stride under TRS_MLP_FAMILY_MIXED: it computes the gradient of all
  * x_stride columns (those past the forward's width meet zero weights and come out as zeros).                       */
-#define TRS_MLP_PHASE_ALL 0
-#define TRS_MLP_PHASE_PACK 1
-#define TRS_MLP_PHASE_RUN 2
 int32_t trs_mlp_fused_family(int32_t num_layers, const int32_t* widths, int64_t rows, int32_t request);
 size_t trs_mlp_fused_workspace_bytes(int32_t num_layers, const int32_t* widths);
 size_t trs_mlp_fused_mask_bytes(int64_t rows);
 int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers, const int32_t* widths,
                       const void* const* weights, const void* const* biases, void* const* hidden, void* const* masks,
-                      void* mask_in, void* y, int32_t dtype, int32_t family, int32_t phase, int32_t x_stride,
-                      void* workspace, size_t ws_bytes, trs_stream_t stream);
+                      void* mask_in, void* y, int32_t dtype, int32_t family, int32_t x_stride, void* workspace,
+                      size_t ws_bytes, trs_stream_t stream);
 int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
                            const void* const* weights, const void* const* masks, void* const* gz, float* const* gbias,
-                           void* gx, const void* mask_in, float* gbias_in, int32_t dtype, int32_t family, int32_t phase,
+                           void* gx, const void* mask_in, float* gbias_in, int32_t dtype, int32_t family,
                            void* workspace, size_t ws_bytes, trs_stream_t stream);
-
-/* Every weight copy a deep branch needs, in ONE launch: the PACK phases of trs_mlp_fused_fwd (into ws_fwd), of
- * trs_mlp_fused_bwd_data (into ws_bwd, same size; NULL: none) and of the trs_rows_gemm of the Linear in front of the stack
- * (gemm_W (gemm_out_f, gemm_in_f) into ws_gemm; NULL: none); the three RUN-phase calls then find what their own PACK call
- * would have left.  For stacks that `family` resolves to the tile kernels (TRS_ESHAPE otherwise: use the PACK phases).
- * multilayer_perceptron.py:53-61 -- three 6-9 us launches with 5 us gaps in front of a 65 536-row deep branch's kernels
- * become one that runs beside the first layer's GEMM.                                                                */
-int trs_mlp_pack_branch(int64_t rows, int32_t num_layers, const int32_t* widths, const void* const* weights,
-                        const void* const* biases, int32_t family, void* ws_fwd, void* ws_bwd, size_t ws_bytes,
-                        const void* gemm_W, int32_t gemm_out_f, int32_t gemm_in_f, void* ws_gemm, size_t ws_gemm_bytes,
-                        trs_stream_t stream);
 
 /* dst (rows, c_out) = [src (rows, c_in) | zeros], bf16: the gradient of the first c_in columns of a padded output (the
  * logit column of a deep branch whose last layer runs at 8 columns) in one launch.                                   */
@@ -410,12 +389,11 @@ int trs_pad_cols(const void* src, int32_t c_in, void* dst, int32_t c_out, int64_
  * y (rows, in_f) = x[:, :out_f] @ W, x (rows, x_stride) and W (out_f, in_f) = nn.Linear(in_f, out_f).weight, bf16:
  * dL/d(input) of that layer from dL/d(pre-activation) (multilayer_perceptron.py:53-61 under autograd).  out_f <= 512
  * (a 128-row tile of x stays in LDS), in_f % 8 == 0, x_stride % 8 == 0 and >= out_f rounded up to 32 (the columns
- * past out_f meet zero weight rows).  workspace: trs_rows_gemm_workspace_bytes (fragment-order copy of W); phase:
- * TRS_MLP_PHASE_* as above (PACK: x and y may be NULL).                                                              */
+ * past out_f meet zero weight rows).  workspace: trs_rows_gemm_workspace_bytes (fragment-order copy of W).          */
 size_t trs_rows_gemm_workspace_bytes(int32_t out_f, int32_t in_f);
 int trs_rows_gemm_supported(int32_t out_f, int32_t in_f, int32_t x_stride);
 int trs_rows_gemm(const void* x, int64_t rows, int32_t x_stride, const void* W, int32_t out_f, int32_t in_f,
-                  int32_t dtype, int32_t phase, void* y, void* workspace, size_t ws_bytes, trs_stream_t stream);
+                  int32_t dtype, void* y, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
 /* ---- row-sharded tables (multi-GPU lookup) -----------------------------
  * Bucket the B*N global row ids of the local batch by owner rank (owner = id / rows_per_rank):
@@ -496,8 +474,7 @@ int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int3
 /* dW partials by a hand-written kernel instead of a batched library GEMM: part (S, M, N) fp32, slice s = g[rows_s, :M]^T
  * x[rows_s, :N] over the s-th of S contiguous row ranges (bf16 operands, row strides ldg / ldx, M and N multiples of
  * 8); trs_wgrad_finish then folds the slices.  S comes from trs_wgrad_rows_splits (0: shape not handled -- more than
- * 32 blocks of 224 x 224, or fewer than 256 rows); that number halved any number of times down to 8 is accepted too
- * (longer row ranges on fewer workgroups, for two weight gradients that share the chip on two streams).              */
+ * 32 blocks of 224 x 224, or fewer than 256 rows); trs_wgrad_rows takes exactly that S.                                */
 int32_t trs_wgrad_rows_splits(int32_t M, int32_t N, int64_t rows);
 int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t ldx, int64_t rows, int32_t M, int32_t N,
                    int32_t dtype, int32_t S, float* part, trs_stream_t stream);

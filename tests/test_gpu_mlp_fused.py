@@ -303,7 +303,7 @@ def test_backward_runs_the_family_its_forward_ran_whatever_is_requested_later(de
     assert all(torch.equal(a, b) for a, b in zip(same, switched))
 
 
-def test_backward_refuses_a_family_the_forward_did_not_report(dev):
+def test_bwd_data_refuses_a_family_the_forward_did_not_report(dev):
     """C ABI: trs_mlp_fused_bwd_data takes the family as an argument -- AUTO (a policy, not a record) and values outside
     {TILE, ROW_OWNER} are TRS_EINVAL, and so is ROW_OWNER for a stack those kernels do not cover; the Python wrapper
     raises before the call."""
@@ -329,40 +329,7 @@ def test_backward_refuses_a_family_the_forward_did_not_report(dev):
         with pytest.raises(RuntimeError, match="family"):
             F_.call("trs_mlp_fused_bwd_data", F_.ptr(gy), 512, 3, wl, F_._ptr_array(Ws), F_._ptr_array(masks),
                     F_._ptr_array(gz), F_._ptr_array(gb), F_.ptr(gx), F_.ptr(None), F_.ptr(None), F_._abi.TRS_BF16, bad,
-                    F_.MLP_PHASE_ALL, F_.ptr(ws), ws_bytes, F_.stream_ptr())
-
-
-@pytest.mark.parametrize("widths,rows", [([32, 104, 200, 40], 700), ([416, 400, 400, 8], 3000)])
-@pytest.mark.parametrize("fam_req", [1, 2, 3])
-def test_pack_and_run_phases_equal_the_one_call_form(dev, widths, rows, fam_req):
-    """C ABI phases: a PACK call (weights into fragment order, on a SIDE stream) followed by a RUN call on the packed
-    workspace gives bit for bit what the one-call form gives -- forward, data gradient, bias gradients, and trs_rows_gemm."""
-    from torecsys_amd import functional as F_
-    g = torch.Generator().manual_seed(5)
-    Ws, bs = _params(widths, g)
-    Ws, bs = [w.to(dev) for w in Ws], [b.to(dev) for b in bs]
-    x = torch.randn(rows, widths[0], generator=g).relu().bfloat16().to(dev)
-    gy = torch.randn(rows, widths[-1], generator=g).bfloat16().to(dev)
-    fam = F_.mlp_fused_family(widths, rows, fam_req)
-    y0, h0, m0, mi0, _ = F_.fused_mlp_forward_raw(x, Ws, bs, input_mask=True, family=fam)
-    ref_b = F_.fused_mlp_backward_raw(gy, widths, Ws, m0, mi0, family=fam)
-    (wsf, wsb), ev, side = F_.run_on_side(dev, "pack", lambda: (F_.fused_mlp_pack(Ws, bs, widths, rows, fam, False),
-                                                                F_.fused_mlp_pack(Ws, None, widths, rows, fam, True)))
-    torch.cuda.current_stream().wait_event(ev)
-    y1, h1, m1, mi1, _ = F_.fused_mlp_forward_raw(x, Ws, bs, input_mask=True, family=fam, packed_ws=wsf)
-    got_b = F_.fused_mlp_backward_raw(gy, widths, Ws, m1, mi1, family=fam, packed_ws=wsb)
-    torch.cuda.synchronize()
-    assert torch.equal(y0, y1) and all(torch.equal(a, b) for a, b in zip(h0, h1))
-    assert torch.equal(ref_b[0], got_b[0]) and all(torch.equal(a, b) for a, b in zip(ref_b[1], got_b[1]))
-    for a, b in zip(list(ref_b[2]) + [ref_b[3]], list(got_b[2]) + [got_b[3]]):
-        assert torch.equal(a, b)
-    # the wide input gradient in front of such a stack
-    out_f, in_f = widths[0] - (16 if widths[0] == 416 else 0), 1024
-    W1 = (torch.randn(out_f, in_f, generator=g) * 0.05).bfloat16().to(dev)
-    gz = torch.randn(4096, widths[0], generator=g).bfloat16().to(dev)
-    if F_.rows_gemm_supported(gz, W1, out_f, in_f):
-        ws = F_.rows_gemm_pack(W1, 4096, widths[0], out_f, in_f)
-        assert torch.equal(F_.rows_gemm(gz, W1, out_f, in_f), F_.rows_gemm(gz, W1, out_f, in_f, packed_ws=ws))
+                    F_.ptr(ws), ws_bytes, F_.stream_ptr())
 
 
 def test_mixed_family_reads_the_first_columns_of_wider_rows(dev):
@@ -423,68 +390,21 @@ def test_wgrad_rows_long_row_ranges_take_the_four_wave_dma_kernel(dev, M, N):
     assert float((gw.double() - ref).abs().max() / ref.abs().max()) <= 1e-5
 
 
-@pytest.mark.parametrize("div", [2, 4, 64])
-def test_wgrad_rows_with_fewer_row_ranges_than_planned(dev, div):
-    """trs_wgrad_rows accepts the planned number of row ranges halved down to 8 (longer ranges on fewer workgroups:
-    layers.WGRAD_PAIR runs two such launches side by side); any other count is refused"""
+def test_wgrad_rows_takes_exactly_the_planned_row_ranges(dev):
+    """trs_wgrad_rows takes exactly the number of row ranges S0 that trs_wgrad_rows_splits planned; any other count
+    (S0 / 2, S0 / 4, S0 / 64, 24, 2 S0) is refused"""
     from torecsys_amd import functional as F_
     from torecsys_amd.functional import call, ptr, stream_ptr, _abi
     rows, M, N = 65536, 400, 400
-    gen = torch.Generator().manual_seed(div)
+    gen = torch.Generator().manual_seed(2)
     g = torch.randn(rows, 416, generator=gen).bfloat16().to(dev)
     x = torch.randn(rows, 416, generator=gen).bfloat16().to(dev)
     S0 = int(_abi.load().trs_wgrad_rows_splits(M, N, rows))
     assert S0 >= 16
-    gw = F_._wgrad_rows(g, x, M, N, torch.float32, splits_div=div)
+    gw = F_._wgrad_rows(g, x, M, N, torch.float32)
     ref = (g.double().t() @ x.double())[:M, :N]
     assert float((gw.double() - ref).abs().max() / ref.abs().max()) <= 1e-5
-    part = torch.empty(S0, M, N, dtype=torch.float32, device=dev)
-    with pytest.raises(RuntimeError):
-        call("trs_wgrad_rows", ptr(g), 416, ptr(x), 416, rows, M, N, _abi.TRS_BF16, 24, ptr(part), stream_ptr())
-    with pytest.raises(RuntimeError):
-        call("trs_wgrad_rows", ptr(g), 416, ptr(x), 416, rows, M, N, _abi.TRS_BF16, 2 * S0, ptr(part), stream_ptr())
-
-
-def test_hybrid_branch_with_paired_tail_weight_gradients(dev):
-    """layers.WGRAD_PAIR: the two square tail layers' weight gradients as half-size launches on two streams -- the same
-    gradients up to the fp32 summation order of the row ranges, eagerly and replayed from a hipGraph"""
-    from torecsys_amd import layers as L
-    from torecsys_amd.graph import GraphedStep
-    torch.manual_seed(11)
-    lay = L.DNNLayer(inputs_size=2496, output_size=1, layer_sizes=[400, 400, 400]).to(dev).bfloat16()
-    params = list(lay.parameters())
-    x = (0.5 * torch.randn(16384, 2496, device=dev)).bfloat16()
-    go = torch.randn(16384, 1, device=dev).bfloat16()
-
-    def run(xin):
-        xa = xin.clone().requires_grad_()
-        (lay(xa).rename(None) * go).sum().backward()
-        return xa.grad
-
-    def fresh():
-        for p in params:
-            p.grad = None
-
-    fresh()
-    gx0 = run(x)
-    g0 = [p.grad.clone() for p in params]
-    saved = L.WGRAD_PAIR
-    L.WGRAD_PAIR = True
-    try:
-        fresh()
-        gx1 = run(x)
-        torch.cuda.synchronize()
-        assert torch.equal(gx0, gx1)
-        for a, p in zip(g0, params):
-            assert rel_err(a.float(), p.grad.float()) <= 1e-3
-        g1 = [p.grad.clone() for p in params]
-        fresh()
-        xs = x.clone()
-        step = GraphedStep(lambda xin: run(xin).float().sum(), (xs,), params=params, warmup=2)
-        for _ in range(3):
-            step(xs)
-        torch.cuda.synchronize()
-        for a, p in zip(g1, params):
-            assert torch.equal(a, p.grad)
-    finally:
-        L.WGRAD_PAIR = saved
+    part = torch.empty(2 * S0, M, N, dtype=torch.float32, device=dev)
+    for S in (S0 // 2, S0 // 4, S0 // 64, 24, 2 * S0):
+        with pytest.raises(RuntimeError):
+            call("trs_wgrad_rows", ptr(g), 416, ptr(x), 416, rows, M, N, _abi.TRS_BF16, S, ptr(part), stream_ptr())

@@ -92,9 +92,8 @@ struct MlpPackJob {
   int out_f, in_f, NTt, KS, bias_n;
   int transpose;
 };
-constexpr int MF_MAXJOBS = 2 * MF_MAXL + 1;      // a stack's forward and backward copies + the layer in front of it (trs_mlp_pack_branch)
 struct MlpPackArgs {
-  MlpPackJob job[MF_MAXJOBS];
+  MlpPackJob job[MF_MAXL];
 };
 __global__ __launch_bounds__(256) void mlp_prepack_many_kernel(MlpPackArgs a) {
   const MlpPackJob& j = a.job[blockIdx.y];
@@ -804,7 +803,7 @@ int mlp_resolve_family(int L, const int32_t* widths, int64_t rows, int request);
 size_t mlp_ro_mask_bytes(int64_t rows);
 int mlp_ro_fwd(const void* x, int64_t rows, int L, const int32_t* widths, const void* const* weights,
                const void* const* biases, void* const* hidden, void* const* masks, void* mask_in, void* y, void* workspace,
-               hipStream_t s, int phase, int x_stride);
+               hipStream_t s, int x_stride);
 struct RoColsum {
   const float* part[9];
   float* out[9];
@@ -813,7 +812,7 @@ struct RoColsum {
 };
 int mlp_ro_bwd(const void* gy, int64_t rows, int L, const int32_t* widths, const void* const* weights,
                const void* const* masks, void* const* gz, float* const* gbias, void* gx, const void* mask_in,
-               float* gbias_in, void* workspace, hipStream_t s, RoColsum* cs, int phase);
+               float* gbias_in, void* workspace, hipStream_t s, RoColsum* cs);
 
 static int mlp_act_str(int L, const int32_t* w) {
   int mx = 0;
@@ -827,8 +826,7 @@ static size_t mlp_frag_bytes(int L, const int32_t* w) {
   return (b + 255) / 256 * 256;
 }
 
-// The weight copies of the tile kernels as job lists (the entry points below and trs_mlp_pack_branch build the SAME jobs:
-// what a PACK call leaves is what a RUN call reads).  Return the grid width the jobs want.
+// The weight copies of the tile kernels as job lists for mlp_prepack_many_kernel.  Return the grid width the jobs want.
 static int mlp_fwd_pack_jobs(int L, const int32_t* widths, const void* const* weights, const void* const* biases, char* wsp,
                              MlpPackJob* job) {
   float* bias_base = (float*)(wsp + mlp_frag_bytes(L, widths));
@@ -894,15 +892,11 @@ extern "C" int trs_mlp_fused_supported(int32_t num_layers, const int32_t* widths
 extern "C" int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers, const int32_t* widths,
                                  const void* const* weights, const void* const* biases, void* const* hidden,
                                  void* const* masks, void* mask_in, void* y, int32_t dtype, int32_t family,
-                                 int32_t phase, int32_t x_stride, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+                                 int32_t x_stride, void* workspace, size_t ws_bytes, trs_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "mlp_fused_fwd: bf16 only");
   TRS_REQUIRE(trs_mlp_fused_supported(num_layers, widths), TRS_ESHAPE, "mlp_fused_fwd: unsupported layer widths");
-  TRS_REQUIRE(phase == TRS_MLP_PHASE_ALL || phase == TRS_MLP_PHASE_PACK || phase == TRS_MLP_PHASE_RUN, TRS_EINVAL,
-              "mlp_fused_fwd: phase %d", phase);
-  // (a PACK call reads the parameters only: the input rows may not exist yet)
-  TRS_REQUIRE(weights && biases && workspace && (phase == TRS_MLP_PHASE_PACK || (x && y && hidden && masks)), TRS_EINVAL,
-              "mlp_fused_fwd: NULL pointer");
+  TRS_REQUIRE(weights && biases && workspace && x && y && hidden && masks, TRS_EINVAL, "mlp_fused_fwd: NULL pointer");
   TRS_REQUIRE(ws_bytes >= trs_mlp_fused_workspace_bytes(num_layers, widths), TRS_EWORKSPACE,
               "mlp_fused_fwd: workspace too small");
   const int L = num_layers;
@@ -913,7 +907,7 @@ extern "C" int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers
   TRS_REQUIRE(x_stride == 0 || x_stride == widths[0] || fam != TRS_MLP_FAMILY_TILE, TRS_ESHAPE,
               "mlp_fused_fwd: rows wider than the stack's input (x_stride %d > %d) are read by the row-owner kernels only", x_stride, widths[0]);
   if (fam == TRS_MLP_FAMILY_ROW_OWNER || fam == TRS_MLP_FAMILY_MIXED)
-    return mlp_ro_fwd(x, rows, L, widths, weights, biases, hidden, masks, mask_in, y, workspace, s, phase,
+    return mlp_ro_fwd(x, rows, L, widths, weights, biases, hidden, masks, mask_in, y, workspace, s,
                       x_stride ? x_stride : widths[0]);
   MlpArgs a;
   a.nsteps = L;
@@ -939,15 +933,14 @@ extern "C" int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers
     st.K = K;
     st.N = N;
     st.relu = l + 1 < L ? 1 : 0;
-    st.out = phase == TRS_MLP_PHASE_PACK ? nullptr : (l + 1 < L ? hidden[l] : y);
+    st.out = l + 1 < L ? hidden[l] : y;
     st.out_stride = l + 1 < L ? N : widths[L];
-    st.mask = (l + 1 < L && phase != TRS_MLP_PHASE_PACK) ? (uint8_t*)masks[l] : nullptr;
+    st.mask = l + 1 < L ? (uint8_t*)masks[l] : nullptr;
     st.colsum = nullptr;
     woff += (size_t)K * N * 2;
     boff += N;
   }
-  if (phase != TRS_MLP_PHASE_RUN) hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, L), dim3(256), 0, s, pk);
-  if (phase == TRS_MLP_PHASE_PACK) return check_launch("mlp_fused_fwd(pack)");
+  hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, L), dim3(256), 0, s, pk);
   a.nbias = (int)boff;
   const size_t lds = (size_t)MF_ROWS * a.act_str + boff * 4;
   static bool attr = false;
@@ -967,15 +960,11 @@ extern "C" int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers
 extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
                                       const void* const* weights, const void* const* masks, void* const* gz,
                                       float* const* gbias, void* gx, const void* mask_in, float* gbias_in, int32_t dtype,
-                                      int32_t family, int32_t phase, void* workspace, size_t ws_bytes,
-                                      trs_stream_t stream) {
+                                      int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "mlp_fused_bwd_data: bf16 only");
   TRS_REQUIRE(trs_mlp_fused_supported(num_layers, widths), TRS_ESHAPE, "mlp_fused_bwd_data: unsupported layer widths");
-  TRS_REQUIRE(phase == TRS_MLP_PHASE_ALL || phase == TRS_MLP_PHASE_PACK || phase == TRS_MLP_PHASE_RUN, TRS_EINVAL,
-              "mlp_fused_bwd_data: phase %d", phase);
-  const bool pack_only = phase == TRS_MLP_PHASE_PACK;      // reads the parameters only: no gradient exists yet
-  TRS_REQUIRE(weights && workspace && (pack_only || (gy && masks && gz && gbias)), TRS_EINVAL, "mlp_fused_bwd_data: NULL pointer");
+  TRS_REQUIRE(weights && workspace && gy && masks && gz && gbias, TRS_EINVAL, "mlp_fused_bwd_data: NULL pointer");
   TRS_REQUIRE(ws_bytes >= trs_mlp_fused_workspace_bytes(num_layers, widths), TRS_EWORKSPACE,
               "mlp_fused_bwd_data: workspace too small");
   const int L = num_layers;
@@ -994,10 +983,10 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
   }
   TRS_REQUIRE(fam_ok, TRS_EINVAL,
               "mlp_fused_bwd_data: family must be the TILE / ROW_OWNER / MIXED value the forward ran under (got %d)", family);
-  TRS_REQUIRE(pack_only || family != TRS_MLP_FAMILY_ROW_OWNER || gx != nullptr, TRS_EINVAL, "mlp_fused_bwd_data: the row-owner kernels need gx");
-  TRS_REQUIRE(pack_only || ((mask_in == nullptr) == (gbias_in == nullptr) && (mask_in == nullptr || (L + 1 <= MF_MAXL && gx != nullptr))),
+  TRS_REQUIRE(family != TRS_MLP_FAMILY_ROW_OWNER || gx != nullptr, TRS_EINVAL, "mlp_fused_bwd_data: the row-owner kernels need gx");
+  TRS_REQUIRE((mask_in == nullptr) == (gbias_in == nullptr) && (mask_in == nullptr || (L + 1 <= MF_MAXL && gx != nullptr)),
               TRS_EINVAL, "mlp_fused_bwd_data: mask_in and gbias_in come together (and with gx, at most %d layers)", MF_MAXL - 1);
-  if (rows == 0 && !pack_only) {
+  if (rows == 0) {
     for (int l = 0; l < L; ++l)
       if (int rc = zero_bytes(gbias[l], (size_t)pad32(widths[l + 1]) * 4, s)) return rc;
     if (gbias_in) return zero_bytes(gbias_in, (size_t)pad32(widths[0]) * 4, s);
@@ -1005,8 +994,8 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
   }
   if (family == TRS_MLP_FAMILY_ROW_OWNER) {
     RoColsum rc;
-    const int rcode = mlp_ro_bwd(gy, rows, L, widths, weights, masks, gz, gbias, gx, mask_in, gbias_in, workspace, s, &rc, phase);
-    if (rcode != TRS_OK || pack_only) return rcode;
+    const int rcode = mlp_ro_bwd(gy, rows, L, widths, weights, masks, gz, gbias, gx, mask_in, gbias_in, workspace, s, &rc);
+    if (rcode != TRS_OK) return rcode;
     MlpColsumArgs cs;
     cs.nparts = rc.nparts;
     int kmax = 0;
@@ -1043,9 +1032,9 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
     st.K = K;
     st.N = N;
     st.relu = 0;
-    st.out = pack_only ? nullptr : (l > 0 ? gz[l - 1] : gx);
+    st.out = l > 0 ? gz[l - 1] : gx;
     st.out_stride = l > 0 ? N : widths[0];
-    st.mask = pack_only ? nullptr : (l > 0 ? (uint8_t*)masks[l - 1] : (uint8_t*)mask_in);
+    st.mask = l > 0 ? (uint8_t*)masks[l - 1] : (uint8_t*)mask_in;
     st.colsum = part_base + poff;
     woff += (size_t)K * N * 2;
     poff += (size_t)grid * K;
@@ -1063,8 +1052,7 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
       return check_launch("mlp_fused_bwd_data: LDS attribute");
     attr = true;
   }
-  if (phase != TRS_MLP_PHASE_RUN) hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, L), dim3(256), 0, s, pk);
-  if (pack_only) return check_launch("mlp_fused_bwd_data(pack)");
+  hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, L), dim3(256), 0, s, pk);
   if (a.ro_masks) hipLaunchKernelGGL(mlp_fused_bwd_kernel<true>, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
   else hipLaunchKernelGGL(mlp_fused_bwd_kernel<false>, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
   MlpColsumArgs cs;
@@ -1104,21 +1092,18 @@ extern "C" int trs_rows_gemm_supported(int32_t out_f, int32_t in_f, int32_t x_st
 }
 
 extern "C" int trs_rows_gemm(const void* x, int64_t rows, int32_t x_stride, const void* W, int32_t out_f, int32_t in_f,
-                             int32_t dtype, int32_t phase, void* y, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+                             int32_t dtype, void* y, void* workspace, size_t ws_bytes, trs_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "rows_gemm: bf16 only");
   TRS_REQUIRE(trs_rows_gemm_supported(out_f, in_f, x_stride), TRS_ESHAPE, "rows_gemm: unsupported shape (K %d, N %d)", out_f, in_f);
-  TRS_REQUIRE(phase == TRS_MLP_PHASE_ALL || phase == TRS_MLP_PHASE_PACK || phase == TRS_MLP_PHASE_RUN, TRS_EINVAL, "rows_gemm: phase %d", phase);
-  const bool pack_only = phase == TRS_MLP_PHASE_PACK;
-  TRS_REQUIRE(W && workspace && (pack_only || (x && y)), TRS_EINVAL, "rows_gemm: NULL pointer");
+  TRS_REQUIRE(W && workspace && x && y, TRS_EINVAL, "rows_gemm: NULL pointer");
   TRS_REQUIRE(ws_bytes >= trs_rows_gemm_workspace_bytes(out_f, in_f), TRS_EWORKSPACE, "rows_gemm: workspace too small");
   TRS_REQUIRE(aligned16(x) && aligned16(y) && aligned16(workspace), TRS_EALIGN, "rows_gemm: 16-byte alignment");
-  if (rows == 0 && !pack_only) return TRS_OK;
+  if (rows == 0) return TRS_OK;
   const int K = pad32(out_f), N = pad32(in_f);
   MlpPackArgs pk;
   const int pk_blocks = mlp_gemm_pack_job(W, out_f, in_f, workspace, pk.job);
-  if (phase != TRS_MLP_PHASE_RUN) hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, 1), dim3(256), 0, s, pk);
-  if (pack_only) return check_launch("rows_gemm(pack)");
+  hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, 1), dim3(256), 0, s, pk);
   RowsGemmArgs a;
   a.in = x;
   a.wf = (const uint4*)workspace;
@@ -1141,38 +1126,4 @@ extern "C" int trs_rows_gemm(const void* x, int64_t rows, int32_t x_stride, cons
   const int64_t ntiles = (rows + MF_ROWS - 1) / MF_ROWS;
   hipLaunchKernelGGL(mlp_rows_gemm_kernel, dim3((int)std::min<int64_t>(ntiles, MF_GRID)), dim3(64 * MF_WAVES), lds, s, a);
   return check_launch("rows_gemm");
-}
-
-/* Every weight copy of a deep branch in ONE launch: the PACK phases of trs_mlp_fused_fwd (into ws_fwd), of
- * trs_mlp_fused_bwd_data (into ws_bwd; NULL: none) and of the trs_rows_gemm of the layer in front of the stack (gemm_W
- * (gemm_out_f x gemm_in_f) into ws_gemm; NULL: none).  The three RUN calls then find what their own PACK call would have
- * left.  Tile family only (TRS_ESHAPE for a stack that `family` resolves to the row-owner kernels: use the PACK phases). */
-extern "C" int trs_mlp_pack_branch(int64_t rows, int32_t num_layers, const int32_t* widths, const void* const* weights,
-                                   const void* const* biases, int32_t family, void* ws_fwd, void* ws_bwd, size_t ws_bytes,
-                                   const void* gemm_W, int32_t gemm_out_f, int32_t gemm_in_f, void* ws_gemm,
-                                   size_t ws_gemm_bytes, trs_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRS_REQUIRE(trs_mlp_fused_supported(num_layers, widths), TRS_ESHAPE, "mlp_pack_branch: unsupported layer widths");
-  TRS_REQUIRE(weights && biases && ws_fwd, TRS_EINVAL, "mlp_pack_branch: NULL pointer");
-  TRS_REQUIRE(ws_bytes >= trs_mlp_fused_workspace_bytes(num_layers, widths), TRS_EWORKSPACE, "mlp_pack_branch: workspace too small");
-  TRS_REQUIRE(mlp_resolve_family(num_layers, widths, rows, family) == TRS_MLP_FAMILY_TILE, TRS_ESHAPE,
-              "mlp_pack_branch: the tile kernels only (family %d resolves to another one for this stack)", family);
-  const int L = num_layers;
-  MlpPackArgs pk;
-  int njobs = L;
-  int blocks = mlp_fwd_pack_jobs(L, widths, weights, biases, (char*)ws_fwd, pk.job);
-  if (ws_bwd != nullptr) {
-    blocks = std::max(blocks, mlp_bwd_pack_jobs(L, widths, weights, (char*)ws_bwd, pk.job + njobs));
-    njobs += L;
-  }
-  if (gemm_W != nullptr) {
-    TRS_REQUIRE(ws_gemm != nullptr && trs_rows_gemm_supported(gemm_out_f, gemm_in_f, pad32(gemm_out_f)), TRS_ESHAPE,
-                "mlp_pack_branch: rows_gemm shape (K %d, N %d)", gemm_out_f, gemm_in_f);
-    TRS_REQUIRE(ws_gemm_bytes >= trs_rows_gemm_workspace_bytes(gemm_out_f, gemm_in_f), TRS_EWORKSPACE,
-                "mlp_pack_branch: rows_gemm workspace too small");
-    blocks = std::max(blocks, mlp_gemm_pack_job(gemm_W, gemm_out_f, gemm_in_f, ws_gemm, pk.job + njobs));
-    njobs += 1;
-  }
-  hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(blocks, njobs), dim3(256), 0, s, pk);
-  return check_launch("mlp_pack_branch");
 }

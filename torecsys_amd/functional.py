@@ -112,9 +112,8 @@ PREFETCH_EARLY = os.environ.get("TRS_PREFETCH_EARLY", "0") not in ("", "0")
 def side_stream(dev: torch.device, role: str) -> torch.cuda.Stream:
     """The per-device side stream of a ROLE: "buckets" (row-bucket builds, beside the dense forward), "lookup" (the
     lookups of a batch beyond the first, beside it -- and, because autograd runs a node's backward on its forward's stream,
-    their bucket walks beside the first one's), "pack" (weight copies into MFMA fragment order, beside the first GEMM of
-    a deep branch).  One stream per role: work of one role must never queue behind another's (a weight copy behind a
-    bucket build would stall the main stream for the whole build)."""
+    their bucket walks beside the first one's).  One stream per role: work of one role must never queue behind another's
+    (a lookup behind a bucket build would stall the main stream for the whole build)."""
     side = _side_streams.get((dev, role))
     if side is None:
         side = _side_streams[(dev, role)] = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
@@ -1974,54 +1973,8 @@ def mlp_fused_family(widths: Sequence[int], rows: int, request: Optional[int] = 
     return fam
 
 
-MLP_PHASE_ALL, MLP_PHASE_PACK, MLP_PHASE_RUN = 0, 1, 2
-
-
-def fused_mlp_pack(Ws: Sequence[torch.Tensor], bs: Optional[Sequence[torch.Tensor]], widths: Sequence[int], rows: int,
-                   family: int, backward: bool) -> torch.Tensor:
-    """The PACK phase of trs_mlp_fused_fwd / _bwd_data on the current stream: the weights in MFMA fragment order (and the
-    zeroed partial sums) in a fresh workspace, which the matching ``fused_mlp_*_raw(packed_ws=...)`` call then runs on.
-    Depends on the parameters only -- callers enqueue it on a side stream while the layer in front of the stack runs."""
-    L = len(Ws)
-    wl = _i32_array(widths)
-    ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=Ws[0].device)
-    if backward:
-        call("trs_mlp_fused_bwd_data", ptr(None), rows, L, wl, _ptr_array(Ws), ptr(None), ptr(None), ptr(None), ptr(None),
-             ptr(None), ptr(None), _abi.TRS_BF16, int(family), MLP_PHASE_PACK, ptr(ws), ws_bytes, stream_ptr())
-    else:
-        call("trs_mlp_fused_fwd", ptr(None), rows, L, wl, _ptr_array(Ws), _ptr_array(bs), ptr(None), ptr(None), ptr(None),
-             ptr(None), _abi.TRS_BF16, int(family), MLP_PHASE_PACK, 0, ptr(ws), ws_bytes, stream_ptr())
-    return ws
-
-
-def fused_mlp_pack_branch(Ws: Sequence[torch.Tensor], bs: Sequence[torch.Tensor], widths: Sequence[int], rows: int,
-                          family: int, backward: bool, gemm: Optional[tuple] = None):
-    """(ws_fwd, ws_bwd | None, ws_gemm | None): what fused_mlp_pack(forward), fused_mlp_pack(backward) and
-    rows_gemm_pack(*gemm) -- gemm = (W, x_stride, out_f, in_f) -- leave, on the current stream.  The tile family does it
-    in ONE launch (trs_mlp_pack_branch), the row-owner family in one per workspace."""
-    if family != MLP_FAMILY_TILE:
-        return (fused_mlp_pack(Ws, bs, widths, rows, family, False),
-                fused_mlp_pack(Ws, None, widths, rows, family, True) if backward else None,
-                rows_gemm_pack(gemm[0], rows, gemm[1], gemm[2], gemm[3]) if gemm is not None else None)
-    L, dev = len(Ws), Ws[0].device
-    wl = _i32_array(widths)
-    ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
-    ws_f = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    ws_b = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if backward else None
-    ws_g, g_bytes, gW, g_out, g_in = None, 0, None, 0, 0
-    if gemm is not None:
-        gW, _, g_out, g_in = gemm
-        g_bytes = size_query("trs_rows_gemm_workspace_bytes", g_out, g_in)
-        ws_g = torch.empty(g_bytes, dtype=torch.uint8, device=dev)
-    call("trs_mlp_pack_branch", rows, L, wl, _ptr_array(Ws), _ptr_array(bs), int(family), ptr(ws_f), ptr(ws_b), ws_bytes,
-         ptr(gW), g_out, g_in, ptr(ws_g), g_bytes, stream_ptr())
-    return ws_f, ws_b, ws_g
-
-
 def fused_mlp_forward_raw(x2: torch.Tensor, Ws: Sequence[torch.Tensor], bs: Sequence[torch.Tensor],
-                          input_mask: bool = False, family: Optional[int] = None,
-                          packed_ws: Optional[torch.Tensor] = None, x_stride: int = 0):
+                          input_mask: bool = False, family: Optional[int] = None, x_stride: int = 0):
     """trs_mlp_fused_fwd on rows x2 (rows, widths[0]): returns (y (rows, widths[L]), hidden [(rows, pad32(w))] -- the
     ReLU outputs of the hidden layers, zero in the padding columns --, masks [the sign bits of the hidden layers in the
     kernel's own order: opaque bytes for trs_mlp_fused_bwd_data], [with ``input_mask`` (x2 is itself a ReLU output): the
@@ -2041,21 +1994,17 @@ def fused_mlp_forward_raw(x2: torch.Tensor, Ws: Sequence[torch.Tensor], bs: Sequ
     mask_in = torch.empty(mask_bytes, dtype=torch.uint8, device=dev) if input_mask else None
     y = torch.empty(rows, widths[L], dtype=torch.bfloat16, device=dev)
     wl = _i32_array(widths)
-    if packed_ws is not None:      # fused_mlp_pack(..., family=fam) ran before (the caller ordered the two)
-        ws, ws_bytes, phase = packed_ws, packed_ws.numel(), MLP_PHASE_RUN
-    else:
-        ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
-        ws, phase = torch.empty(ws_bytes, dtype=torch.uint8, device=dev), MLP_PHASE_ALL
+    ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     call("trs_mlp_fused_fwd", ptr(x2), rows, L, wl, _ptr_array(Ws), _ptr_array(bs), _ptr_array(hidden),
-         _ptr_array(masks), ptr(mask_in), ptr(y), _abi.TRS_BF16, fam, phase, int(x_stride), ptr(ws), ws_bytes, stream_ptr())
+         _ptr_array(masks), ptr(mask_in), ptr(y), _abi.TRS_BF16, fam, int(x_stride), ptr(ws), ws_bytes, stream_ptr())
     if input_mask:
         return y, hidden, masks, mask_in, fam
     return y, hidden, masks, fam
 
 
 def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequence[torch.Tensor],
-                           masks: Sequence[torch.Tensor], mask_in: Optional[torch.Tensor] = None, *, family: int,
-                           packed_ws: Optional[torch.Tensor] = None):
+                           masks: Sequence[torch.Tensor], mask_in: Optional[torch.Tensor] = None, *, family: int):
     """trs_mlp_fused_bwd_data: (gx, gz [d(pre-activation) of the hidden layers], gb [fp32 bias gradients, padded]) and,
     with ``mask_in``, gb_in: gx is then masked by the upstream ReLU and gb_in holds its column sums.  ``family``: what
     fused_mlp_forward_raw returned with these masks."""
@@ -2068,14 +2017,10 @@ def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequenc
     gx = torch.empty(rows, widths[0], dtype=torch.bfloat16, device=dev)   # the kernel always writes dL/dx (its last GEMM)
     gb_in = torch.empty(_pad32(widths[0]), dtype=torch.float32, device=dev) if mask_in is not None else None
     wl = _i32_array(widths)
-    if packed_ws is not None:
-        ws, ws_bytes, phase = packed_ws, packed_ws.numel(), MLP_PHASE_RUN
-    else:
-        ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
-        ws, phase = torch.empty(ws_bytes, dtype=torch.uint8, device=dev), MLP_PHASE_ALL
+    ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     call("trs_mlp_fused_bwd_data", ptr(gy2), rows, L, wl, _ptr_array(Ws), _ptr_array(masks), _ptr_array(gz),
-         _ptr_array(gb), ptr(gx), ptr(mask_in), ptr(gb_in), _abi.TRS_BF16, int(family), phase, ptr(ws), ws_bytes,
-         stream_ptr())
+         _ptr_array(gb), ptr(gx), ptr(mask_in), ptr(gb_in), _abi.TRS_BF16, int(family), ptr(ws), ws_bytes, stream_ptr())
     return gx, gz, gb, gb_in
 
 
@@ -2111,15 +2056,12 @@ class _FusedMLP(Function):
         for l in range(L):
             inp = x2 if l == 0 else hidden[l - 1]               # (rows, widths[l] | pad32)
             g = gy2 if l == L - 1 else gz[l]                    # (rows, widths[l+1] | pad32)
-            gw = gbias = None
             need_w, need_b = ctx.needs_input_grad[1 + 2 * l], ctx.needs_input_grad[2 + 2 * l]
-            if need_w and need_b and pdt[2 * l] == pdt[2 * l + 1]:
-                gw, gbias = _wgrad_rows(g, inp, widths[l + 1], widths[l], pdt[2 * l], gb[l])
-            else:
-                if need_w:
-                    gw = _wgrad_rows(g, inp, widths[l + 1], widths[l], pdt[2 * l])
-                if need_b:
-                    gbias = gb[l][:widths[l + 1]].to(pdt[2 * l + 1])
+            if pdt[2 * l] == pdt[2 * l + 1]:
+                gw, gbias = _tail_layer_grads(g, inp, widths[l + 1], widths[l], pdt[2 * l], gb[l], need_w, need_b)
+            else:                                               # (_tail_layer_grads casts both to the weight's dtype)
+                gw = _wgrad_rows(g, inp, widths[l + 1], widths[l], pdt[2 * l]) if need_w else None
+                gbias = gb[l][:widths[l + 1]].to(pdt[2 * l + 1]) if need_b else None
             grads += [gw, gbias]
         return (gx.reshape(xshape) if ctx.needs_input_grad[0] else None, *grads)
 
@@ -2144,76 +2086,21 @@ def rows_gemm_supported(g: torch.Tensor, W: torch.Tensor, out_f: int, in_f: int)
     return rows_gemm_supported_for(g.shape[0], g.shape[1], W, out_f, in_f)
 
 
-def rows_gemm_pack(W: torch.Tensor, rows: int, x_stride: int, out_f: int, in_f: int) -> torch.Tensor:
-    """The PACK phase of trs_rows_gemm on the current stream (see fused_mlp_pack): W in fragment order in a fresh
-    workspace for ``rows_gemm(..., packed_ws=...)``"""
-    ws_bytes = size_query("trs_rows_gemm_workspace_bytes", out_f, in_f)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=W.device)
-    call("trs_rows_gemm", ptr(None), rows, x_stride, ptr(W), out_f, in_f, _abi.TRS_BF16, MLP_PHASE_PACK, ptr(None), ptr(ws),
-         ws_bytes, stream_ptr())
-    return ws
-
-
-def rows_gemm(g: torch.Tensor, W: torch.Tensor, out_f: int, in_f: int,
-              packed_ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+def rows_gemm(g: torch.Tensor, W: torch.Tensor, out_f: int, in_f: int) -> torch.Tensor:
     y = torch.empty(g.shape[0], in_f, dtype=torch.bfloat16, device=g.device)
-    if packed_ws is not None:
-        ws, ws_bytes, phase = packed_ws, packed_ws.numel(), MLP_PHASE_RUN
-    else:
-        ws_bytes = size_query("trs_rows_gemm_workspace_bytes", out_f, in_f)
-        ws, phase = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device), MLP_PHASE_ALL
-    call("trs_rows_gemm", ptr(g), g.shape[0], g.shape[1], ptr(W), out_f, in_f, _abi.TRS_BF16, phase, ptr(y), ptr(ws),
-         ws_bytes, stream_ptr())
+    ws_bytes = size_query("trs_rows_gemm_workspace_bytes", out_f, in_f)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
+    call("trs_rows_gemm", ptr(g), g.shape[0], g.shape[1], ptr(W), out_f, in_f, _abi.TRS_BF16, ptr(y), ptr(ws), ws_bytes,
+         stream_ptr())
     return y
 
 
-def _tail_layer_grads(g, inp, out_f, in_f, dtype, gb_f32, need_w, need_b, splits_div=1):
+def _tail_layer_grads(g, inp, out_f, in_f, dtype, gb_f32, need_w, need_b):
     """(dW, db) of one layer behind the fused kernels: the bias cast rides in the weight gradient's finish launch"""
     if need_w and need_b:
-        return _wgrad_rows(g, inp, out_f, in_f, dtype, gb_f32, splits_div=splits_div)
-    gw = _wgrad_rows(g, inp, out_f, in_f, dtype, splits_div=splits_div) if need_w else None
+        return _wgrad_rows(g, inp, out_f, in_f, dtype, gb_f32)
+    gw = _wgrad_rows(g, inp, out_f, in_f, dtype) if need_w else None
     return gw, (gb_f32[:out_f].to(dtype) if need_b else None)
-
-
-class _FusedMLPTail(Function):
-    """The layers BEHIND a wide first layer (DeepFM / xDeepFM deep branch: 2496 -> 400 | -> 400 -> 400 -> 1) as one HIP
-    kernel per direction: x2 is the first layer's ReLU output at its zero-padded GEMM width, the tail's first weight is
-    padded on the input side to match and its last on the output side to the kernel's minimum width (8 columns; only the
-    first ``out_f`` are returned).  ``tensors`` per layer: weight, bias (the parameters: they receive the gradients),
-    w_use, b_use (what the kernel reads: the parameter itself when None)."""
-
-    @staticmethod
-    def forward(ctx, x2, *tensors):
-        require_device(x2, *[t for t in tensors if t is not None])
-        L = len(tensors) // 4
-        Ws = [(tensors[4 * l] if tensors[4 * l + 2] is None else tensors[4 * l + 2]).contiguous() for l in range(L)]
-        bs = [(tensors[4 * l + 1] if tensors[4 * l + 3] is None else tensors[4 * l + 3]).contiguous() for l in range(L)]
-        y, hidden, masks, fam = fused_mlp_forward_raw(x2, Ws, bs)
-        out_f = tensors[4 * (L - 1)].shape[0]
-        ctx.save_for_backward(x2, *Ws, *hidden, *masks)
-        ctx.meta = (L, [x2.shape[1]] + [w.shape[0] for w in Ws], [tuple(tensors[4 * l].shape) for l in range(L)],
-                    [tensors[4 * l].dtype for l in range(L)], fam)
-        return y[:, :out_f] if out_f != y.shape[1] else y      # (a view of the padded output: consumers read it strided)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        L, widths, wshapes, wdt, fam = ctx.meta
-        saved = ctx.saved_tensors
-        x2, Ws = saved[0], saved[1:1 + L]
-        hidden, masks = saved[1 + L:L + L], saved[L + L:]
-        rows, dev = x2.shape[0], x2.device
-        gy2 = pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
-        gx, gz, gb, _ = fused_mlp_backward_raw(gy2, widths, Ws, masks, family=fam)
-        grads = []
-        for l in range(L):
-            inp = x2 if l == 0 else hidden[l - 1]
-            g = gy2 if l == L - 1 else gz[l]
-            out_f, in_f = wshapes[l]
-            gw, gbias = _tail_layer_grads(g, inp, out_f, in_f, wdt[l], gb[l], ctx.needs_input_grad[1 + 4 * l],
-                                          ctx.needs_input_grad[2 + 4 * l])
-            grads += [gw, gbias, None, None]
-        return (gx if ctx.needs_input_grad[0] else None, *grads)
 
 
 WGRAD_ROWS = os.environ.get("TRS_WGRAD_ROWS", "1") not in ("", "0")
@@ -2227,30 +2114,20 @@ def pad_cols(g: torch.Tensor, width: int) -> torch.Tensor:
     return out
 
 
-def _wgrad_rows(g: torch.Tensor, inp: torch.Tensor, out_f: int, in_f: int, dtype, gb_f32: Optional[torch.Tensor] = None,
-                splits_div: int = 1):
+def _wgrad_rows(g: torch.Tensor, inp: torch.Tensor, out_f: int, in_f: int, dtype, gb_f32: Optional[torch.Tensor] = None):
     """dW = g^T @ inp over the rows (K = rows): split-K batched GEMM with fp32 partials, folded / sliced / cast by
     trs_wgrad_finish (the padding columns of g / inp are dropped there).  With ``gb_f32`` (the layer's fp32 bias
     gradient, at least out_f entries) returns (dW, db): the cast of the bias gradient rides in the same finish launch."""
     if gb_f32 is not None:
         gb = torch.empty(out_f, dtype=dtype, device=g.device)
         if out_f <= (in_f + 255) // 256 * 256:
-            return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb, splits_div), gb
+            return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb), gb
         gb.copy_(gb_f32[:out_f])
-        return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, None, None, splits_div), gb
-    return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, None, None, splits_div)
+        return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, None, None), gb
+    return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, None, None)
 
 
-def wgrad_rows_splits(g: torch.Tensor, inp: torch.Tensor, out_f: int, in_f: int) -> int:
-    """row ranges trs_wgrad_rows cuts this layer's weight gradient into (0: the kernel does not take the shape)"""
-    if not (WGRAD_ROWS and g.is_cuda and g.dtype == torch.bfloat16 and inp.dtype == torch.bfloat16 and g.is_contiguous()
-            and inp.is_contiguous()):
-        return 0
-    M, N = min(g.shape[1], (out_f + 7) // 8 * 8), min(inp.shape[1], (in_f + 7) // 8 * 8)
-    return int(_abi.load().trs_wgrad_rows_splits(M, N, int(g.shape[0])))
-
-
-def _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb, splits_div=1):
+def _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb):
     rows = g.shape[0]
     if (WGRAD_ROWS and g.is_cuda and g.dtype == torch.bfloat16 and inp.dtype == torch.bfloat16 and g.is_contiguous()
             and inp.is_contiguous()):
@@ -2259,9 +2136,6 @@ def _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb, splits_div=1):
         M, N = min(g.shape[1], (out_f + 7) // 8 * 8), min(inp.shape[1], (in_f + 7) // 8 * 8)
         S = int(_abi.load().trs_wgrad_rows_splits(M, N, int(rows)))
         if S > 0:
-            while splits_div > 1 and S % 2 == 0 and S // 2 >= 8:      # (S is 8 x a power of two)
-                S //= 2
-                splits_div //= 2
             part = torch.empty(S, M, N, dtype=torch.float32, device=g.device)
             call("trs_wgrad_rows", ptr(g), g.shape[1], ptr(inp), inp.shape[1], rows, M, N,
                  _abi.TRS_BF16, S, ptr(part), stream_ptr())

@@ -538,27 +538,10 @@ class CompressInteractionNetworkLayer(BaseLayer):
 
 
 TRANSPOSE_PAD = os.environ.get("TRS_TRANSPOSE_PAD", "1") not in ("", "0")   # CIN entry: (B,N,E) -> (B,E,ld0) in one pass
-PAD_MULTIPLE = int(os.environ.get("TRS_PAD_MULTIPLE", "128"))        # hidden widths are zero-padded to a multiple of this inside the GEMMs
+PAD_MULTIPLE = 128        # hidden widths are zero-padded to a multiple of this inside the GEMMs
 PAD_MIN_WIDTH = 192
 PAD_MIN_ROWS = 4096
-HYBRID_ONE_NODE = os.environ.get("TRS_HYBRID_ONE_NODE", "1") not in ("", "0")
 HYBRID_MLP = os.environ.get("TRS_HYBRID_MLP", "1") not in ("", "0")   # fused tail behind a wide first layer
-# _HybridMLP's weight copies into fragment order: 0 (default) in front of each kernel; 1 one launch on the "pack" side stream
-# beside the first GEMM; 2 one launch on the caller's stream in front of the first GEMM.  Measured alternately on one box
-# (gpurun_out/r05e, r05f; DeepFM step replayed from a hipGraph): 0: 1.259 ms, 2: 1.279 ms, 1: 1.277 ms -- three launches
-# fewer on the critical path and still 20 us slower (what the graph's branches overlap with moves: the bucket build no
-# longer runs beside the first GEMM).  Kept as a switch and as the ABI's PACK / RUN phases; off.
-HOIST_PACK = int(os.environ.get("TRS_HOIST_PACK", "0") or 0)
-# _HybridMLP.backward: the tail's weight-gradient launches on a side stream beside the first layer's gradient GEMMs.
-# Measured alternately on one box (gpurun_out/r05p): 1.1956 ms off, 1.1975 ms on -- matrix-core kernels beside matrix-core
-# kernels only move time.  Off.
-WGRAD_STREAM = os.environ.get("TRS_WGRAD_STREAM", "0") not in ("", "0")
-# _HybridMLP.backward: the two square tail layers' weight gradients as half-size launches on two streams (see tail_grads)
-WGRAD_PAIR = os.environ.get("TRS_WGRAD_PAIR", "0") not in ("", "0")
-# _dense_layer_grads: the input gradient behind the weight gradient (see there)
-GX_LAST = os.environ.get("TRS_GX_LAST", "1") not in ("", "0")
-# the fused tail's forward on the first 416 columns of the 512-wide first-layer output, by the row-owner kernel (mixed family)
-MIXED_TAIL = os.environ.get("TRS_MIXED_TAIL", "1") not in ("", "0")
 
 
 def _pad_width(width: int) -> int:
@@ -731,23 +714,11 @@ class _LinearSplitK(torch.autograd.Function):
         return gx, gw, gb, None, None, None
 
 
-def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b, rows_gemm_ws=None):
+def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b):
     """Gradients of y = xin @ W^T + b from g2 = dL/dy (rows, padded width; ``gbf``: its fp32 column sums when a fused
-    ReLU-backward already produced them): (dL/dxin, dL/dW, dL/db), None where not needed.  ``rows_gemm_ws``: W already in
-    fragment order for trs_rows_gemm (F_.rows_gemm_pack at forward time)."""
+    ReLU-backward already produced them): (dL/dxin, dL/dW, dL/db), None where not needed."""
     rows = xin.shape[0]
     gw_out = gb_out = None
-
-    def input_grad():
-        if need_x and F_.rows_gemm_supported(g2, W, out_f, xin.shape[1]) and W.shape[1] == xin.shape[1]:
-            # wide input, short contraction (2496 <- 400): our own kernel, K not padded to the library's tile
-            return F_.rows_gemm(g2, W, out_f, xin.shape[1], packed_ws=rows_gemm_ws)
-        return (g2 @ W) if need_x else None
-
-    # GX_LAST: the input gradient is enqueued BEHIND the weight gradient, i.e. right in front of its consumer (the bucket
-    # walk of the embedding backward reads the (B,N,E) gradient next): what of it is still in the Infinity Cache then
-    # does not come from HBM
-    gx = None if GX_LAST else input_grad()
     S = _split_count(rows, _LinearSplitK.SPLIT_ROWS)
     if need_w or (need_b and gbf is not None):
         if need_w and S >= 4 and rows % S == 0 and 32 <= g2.shape[1] <= 1024 and 32 <= xin.shape[1] <= 4096 \
@@ -780,17 +751,24 @@ def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b
             gw_out = gw if gw.is_contiguous() else gw.contiguous()
     if need_b and gb_out is None:
         gb_out = gbf[:out_f].to(wdt) if gbf is not None else g2.sum(0)[:out_f]
-    if GX_LAST:
-        gx = input_grad()
+    # the input gradient is enqueued BEHIND the weight gradient, i.e. right in front of its consumer (the bucket walk of
+    # the embedding backward reads the (B,N,E) gradient next): what of it is still in the Infinity Cache then does not
+    # come from HBM
+    gx = None
+    if need_x and F_.rows_gemm_supported(g2, W, out_f, xin.shape[1]) and W.shape[1] == xin.shape[1]:
+        # wide input, short contraction (2496 <- 400): our own kernel, K not padded to the library's tile
+        gx = F_.rows_gemm(g2, W, out_f, xin.shape[1])
+    elif need_x:
+        gx = g2 @ W
     return gx, gw_out, gb_out
 
 
 class _HybridMLP(torch.autograd.Function):
     """A deep branch whose first layer is too wide for the fused kernel, as ONE autograd node: first Linear + ReLU on
-    hipBLASLt, every layer behind it in trs_mlp_fused_fwd / _bwd_data (F_._FusedMLPTail's arrangement).  One node instead
-    of two so that the first layer's ReLU-backward and bias gradient come out of the fused backward kernel (it masks its
-    input gradient with the sign bits of h1 the forward kernel took while loading h1, and sums the columns) instead of a
-    pass of their own over the (rows, 400) gradient: trs_relu_bwd_bias, 32 us of a 1.4 ms DeepFM step.
+    hipBLASLt, every layer behind it in trs_mlp_fused_fwd / _bwd_data.  One node instead of two so that the first
+    layer's ReLU-backward and bias gradient come out of the fused backward kernel (it masks its input gradient with the
+    sign bits of h1 the forward kernel took while loading h1, and sums the columns) instead of a pass of their own over
+    the (rows, 400) gradient: trs_relu_bwd_bias, 32 us of a 1.4 ms DeepFM step.
     ``tensors``: weight, bias, w_use, b_use of the first layer, then of every tail layer (w_use / b_use: the zero-padded
     copies the kernels read, or None)."""
 
@@ -804,40 +782,13 @@ class _HybridMLP(torch.autograd.Function):
         L = len(tail) // 4
         Ws = [(tail[4 * l] if tail[4 * l + 2] is None else tail[4 * l + 2]).contiguous() for l in range(L)]
         bs = [(tail[4 * l + 1] if tail[4 * l + 3] is None else tail[4 * l + 3]).contiguous() for l in range(L)]
-        # TRS_HOIST_PACK (off by default, see HOIST_PACK): every copy of weights into MFMA fragment order this node needs --
-        # the tail's forward and backward kernels, the first layer's input-gradient kernel -- depends on the parameters
-        # only and can be ONE launch in front of (or, on the "pack" side stream, beside) the first layer's GEMM.
-        rows, wpack = cur.shape[0], None
-        widths_t = [W1.shape[0]] + [w.shape[0] for w in Ws]
-        if HOIST_PACK and rows >= PAD_MIN_ROWS:
-            fam_t = F_.mlp_fused_family(widths_t, rows)
-            need_bwd = any(ctx.needs_input_grad)
-            gx_ws = need_bwd and ctx.needs_input_grad[0] and W1.is_contiguous() and W1.shape[1] == cur.shape[1] and \
-                F_.rows_gemm_supported_for(rows, W1.shape[0], W1, w1.shape[0], cur.shape[1])
-
-            gemm = (W1, W1.shape[0], w1.shape[0], cur.shape[1]) if gx_ws else None
-            if HOIST_PACK == 2:
-                wpack, ev = F_.fused_mlp_pack_branch(Ws, bs, widths_t, rows, fam_t, need_bwd, gemm), None
-            else:
-                wpack, ev, side = F_.run_on_side(cur.device, "pack", lambda: F_.fused_mlp_pack_branch(
-                    Ws, bs, widths_t, rows, fam_t, need_bwd, gemm))
         h1 = torch._addmm_activation(B1, cur, W1.t(), use_gelu=False)
-        if wpack is not None:
-            if ev is not None:
-                main = F_._abi.current_stream_of(cur.device)
-                main.wait_event(ev)
-                for t in wpack:
-                    if t is not None:
-                        t.record_stream(main)      # allocated under the side stream, read (and freed) under this one
-            y, hidden, masks, mask_in, fam = F_.fused_mlp_forward_raw(h1, Ws, bs, input_mask=True, family=fam_t,
-                                                                      packed_ws=wpack[0])
-        elif w_narrow is not None:
+        if w_narrow is not None:
             # mixed family on the first h_n columns of the 512-wide rows (see _forward_hybrid)
             y, hidden, masks, mask_in, fam = F_.fused_mlp_forward_raw(h1, [w_narrow] + Ws[1:], bs, input_mask=True,
                                                                       family=F_.MLP_FAMILY_MIXED, x_stride=h1.shape[1])
         else:
             y, hidden, masks, mask_in, fam = F_.fused_mlp_forward_raw(h1, Ws, bs, input_mask=True)
-        ctx.wpack = wpack
         out_f = tail[4 * (L - 1)].shape[0]
         ctx.save_for_backward(cur, W1, h1, mask_in, *Ws, *hidden, *masks)
         ctx.meta = (L, [h1.shape[1]] + [w.shape[0] for w in Ws], [tuple(tail[4 * l].shape) for l in range(L)],
@@ -854,54 +805,17 @@ class _HybridMLP(torch.autograd.Function):
         Ws = saved[4:4 + L]
         hidden, masks = saved[4 + L:3 + L + L], saved[3 + L + L:]
         needs = ctx.needs_input_grad
-        rows, dev = h1.shape[0], h1.device
-        gy = gy.reshape(rows, -1)
+        gy = gy.reshape(h1.shape[0], -1)
         gy2 = F_.pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
-        wpack = ctx.wpack if ctx.wpack is not None else (None, None, None)
-        g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam, packed_ws=wpack[1])
-        def layer_grads(l, splits_div=1):
+        g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam)
+        grads = []
+        for l in range(L):
             inp = h1 if l == 0 else hidden[l - 1]
             g = gy2 if l == L - 1 else gz[l]
             out_f, in_f = wshapes[l]
-            return F_._tail_layer_grads(g, inp, out_f, in_f, wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l], splits_div)
-
-        def tail_grads():
-            # WGRAD_PAIR: the first two tail layers' weight gradients (400 x 400 from 65 536 rows each: 256 workgroups of
-            # 1024 rows, where start-up and the fp32 partial cost as much as the loop) as two launches of HALF as many
-            # workgroups over twice the rows, one on the "wgrad" side stream, sharing the chip
-            pair = (WGRAD_PAIR and L >= 3 and rows >= PAD_MIN_ROWS and wshapes[0] == wshapes[1]
-                    and all(needs[6 + 4 * l] for l in (0, 1))
-                    and F_.wgrad_rows_splits(gz[0], h1, *wshapes[0]) >= 16
-                    and F_.wgrad_rows_splits(gz[1], hidden[0], *wshapes[1]) >= 16)
-            if not pair:
-                return [t for l in range(L) for t in (*layer_grads(l), None, None)]
-            (gw1_, gb1_), ev1, side1 = F_.run_on_side(dev, "wgrad", lambda: layer_grads(1, 2))
-            for t in (gz[1], hidden[0], gb[1]):
-                t.record_stream(side1)
-            per_layer = [layer_grads(0, 2), (gw1_, gb1_)] + [layer_grads(l) for l in range(2, L)]
-            main_ = F_._abi.current_stream_of(dev)
-            main_.wait_event(ev1)
-            for t in (gw1_, gb1_):
-                if t is not None:
-                    t.record_stream(main_)
-            return [t for pr in per_layer for t in (*pr, None, None)]
-
-        # The tail's weight gradients (three GEMMs over the rows + their finish passes: six launches nobody waits for
-        # until the step ends) on the "wgrad" side stream, beside the first layer's input- and weight-gradient GEMMs;
-        # this node's stream waits for them before it returns (the gradients go to AccumulateGrad on this stream).
-        ev = None
-        if WGRAD_STREAM and rows >= PAD_MIN_ROWS:
-            grads, ev, side = F_.run_on_side(dev, "wgrad", tail_grads)
-        else:
-            grads = tail_grads()
-        gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3],
-                                             rows_gemm_ws=wpack[2])
-        if ev is not None:
-            main = F_._abi.current_stream_of(dev)
-            main.wait_event(ev)
-            for t in grads:
-                if t is not None:
-                    t.record_stream(main)
+            grads += [*F_._tail_layer_grads(g, inp, out_f, in_f, wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]),
+                      None, None]
+        gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3])
         return (gx.reshape(xshape) if needs[0] else None, None, gw1, gbias1, None, None, *grads)
 
 
@@ -915,8 +829,7 @@ class _MLPStack(torch.autograd.Function):
     ``spec``: per layer (fuse_relu, rowdot); ``tensors``: per layer weight, bias, w_use, b_use (the last two: the
     zero-padded copies the GEMMs read, or None)."""
 
-    # rows per split-K slice of a wide-input layer's weight gradient (TRS_SPLIT_ROWS_WIDE: tuning)
-    SPLIT_ROWS_WIDE = int(os.environ.get("TRS_SPLIT_ROWS_WIDE", "4096"))
+    SPLIT_ROWS_WIDE = 4096      # rows per split-K slice of a wide-input layer's weight gradient
 
     @staticmethod
     def forward(ctx, x, spec, *tensors):
@@ -1016,6 +929,23 @@ def _public_out(t: torch.Tensor) -> torch.Tensor:
     return c
 
 
+def _linear_relu_stack(mods, dtype: torch.dtype) -> Optional[List[Tuple[nn.Linear, bool]]]:
+    """[(nn.Linear, followed by an nn.ReLU)] of a stack of Linear layers with biases in ``dtype``, each optionally followed
+    by a plain nn.ReLU (Dropout modules are skipped: the callers run only stacks whose Dropout is inactive); None when the
+    modules are anything else."""
+    mods = [m for m in mods if not isinstance(m, nn.Dropout)]
+    layers = []
+    i = 0
+    while i < len(mods):
+        mod = mods[i]
+        if not isinstance(mod, nn.Linear) or mod.bias is None or mod.weight.dtype != dtype:
+            return None
+        relu = i + 1 < len(mods) and type(mods[i + 1]) is nn.ReLU
+        layers.append((mod, relu))
+        i += 2 if relu else 1
+    return layers
+
+
 class MultilayerPerceptionLayer(BaseLayer):
     """Linear/activation/dropout stack + output Linear.  layers/ctr/multilayer_perceptron.py:24-84.
     Plain GEMMs: stays on nn.Linear parameters and hipBLASLt kernels (outside the hand-written path, inside the timed
@@ -1046,20 +976,15 @@ class MultilayerPerceptionLayer(BaseLayer):
         self.model.add_module('LinearOutput', nn.Linear(layer_sizes[-1], output_size))
 
     def _forward_stacked(self, outputs: torch.Tensor, mods) -> Optional[torch.Tensor]:
-        """The whole stack through one autograd node (_MLPStack) when it is Linear -> ReLU ... -> Linear with biases
-        (inactive Dropout modules are skipped); None when the stack has any other shape."""
-        lin = [m for m in mods if not isinstance(m, nn.Dropout)]
-        spec, tensors, padded, mods_used = [], [], [], []
+        """The whole stack through one autograd node (_MLPStack) when it is Linear -> ReLU ... -> Linear (-> ReLU) with
+        biases (inactive Dropout modules are skipped); None when the stack has any other shape."""
+        layers = _linear_relu_stack(mods, outputs.dtype)
+        if not layers or not all(relu for _, relu in layers[:-1]) or not outputs.is_contiguous():
+            return None
+        spec, tensors, padded = [], [], []
         width = outputs.shape[-1]
-        i = 0
-        while i < len(lin):
-            mod = lin[i]
-            if not isinstance(mod, nn.Linear) or mod.bias is None or mod.weight.dtype != outputs.dtype:
-                return None
-            fuse = i + 1 < len(lin) and type(lin[i + 1]) is nn.ReLU
-            last = i + (2 if fuse else 1) >= len(lin)
-            if not fuse and not last:
-                return None
+        for i, (mod, fuse) in enumerate(layers):
+            last = i == len(layers) - 1
             out_pad = _pad_width(mod.out_features) if not last else mod.out_features
             row_bytes = out_pad * outputs.element_size()
             if fuse and (row_bytes % 16 != 0 or row_bytes > 4096):       # trs_relu_bwd_bias row limits
@@ -1069,13 +994,9 @@ class MultilayerPerceptionLayer(BaseLayer):
                       and (width * outputs.element_size()) % 16 == 0
                       and F_.rowdot_width_supported(width, outputs.element_size()))
             spec.append((fuse, rowdot))
-            mods_used.append(mod)
             width = out_pad
-            i += 2 if fuse else 1
-        if not spec or not outputs.is_contiguous():
-            return None
         copies = iter(_PaddedLinear.get_many([p for p in padded if p is not None]))     # one launch for the whole stack
-        for mod, p in zip(mods_used, padded):
+        for (mod, _), p in zip(layers, padded):
             w_use, b_use = next(copies) if p is not None else (None, None)
             tensors += [mod.weight, mod.bias, w_use, b_use]
         out = _MLPStack.apply(outputs, tuple(spec), *tensors)
@@ -1088,30 +1009,20 @@ class MultilayerPerceptionLayer(BaseLayer):
     def _forward_hybrid(self, outputs: torch.Tensor, mods) -> Optional[torch.Tensor]:
         """A first layer too wide for the fused kernel (the 2496-wide input of the DeepFM / xDeepFM deep branch) on
         hipBLASLt, every layer behind it -- ReLU hidden layers and the output Linear -- as ONE kernel per direction
-        (F_._FusedMLPTail): 65 536 x 400 x 400 GEMMs are too small for the library's 256-wide macro tiles (300-450
-        TFLOP/s each, plus a ReLU-backward pass per layer).  None when the stack does not have that shape."""
-        lin = [m for m in mods if not isinstance(m, nn.Dropout)]
-        layers = []
-        i = 0
-        while i < len(lin):
-            mod = lin[i]
-            if not isinstance(mod, nn.Linear) or mod.bias is None or mod.weight.dtype != outputs.dtype:
-                return None
-            relu = i + 1 < len(lin) and type(lin[i + 1]) is nn.ReLU
-            last = i + (2 if relu else 1) >= len(lin)
-            if relu == last:
-                return None
-            layers.append(mod)
-            i += 2 if relu else 1
-        if len(layers) < 3 or not HYBRID_MLP or not outputs.is_contiguous() or outputs.dim() != 2:
+        (_HybridMLP): 65 536 x 400 x 400 GEMMs are too small for the library's 256-wide macro tiles (300-450 TFLOP/s
+        each, plus a ReLU-backward pass per layer).  None when the stack does not have that shape or has more layers
+        than the fused backward takes behind a masked input (8 in all)."""
+        layers = _linear_relu_stack(mods, outputs.dtype)
+        if (not layers or not 3 <= len(layers) <= 8 or layers[-1][1] or not all(relu for _, relu in layers[:-1])
+                or not HYBRID_MLP or not outputs.is_contiguous() or outputs.dim() != 2):
             return None
-        first, tail = layers[0], layers[1:]
+        first, tail = layers[0][0], [mod for mod, _ in layers[1:]]
         h_pad = _pad_width(first.out_features)
         if (h_pad * outputs.element_size()) % 16 != 0 or h_pad * outputs.element_size() > 4096:
             return None
         out_pad = max(8, (tail[-1].out_features + 7) // 8 * 8)
         widths = [h_pad] + [m.out_features for m in tail[:-1]] + [out_pad]
-        if any(a.in_features != b.out_features for a, b in zip(tail, layers[:-1])):
+        if any(a.in_features != b.out_features for a, b in zip(tail, [first] + tail[:-1])):
             return None
         if first.in_features <= 512 or not F_.mlp_fused_supported_for(outputs.shape[0], outputs.dtype, outputs.is_cuda,
                                                                        widths):
@@ -1131,7 +1042,7 @@ class MultilayerPerceptionLayer(BaseLayer):
         # columns meet zero weights (the gradient the first layer's weight-gradient GEMM reads stays 512 wide).
         narrow = None
         h_n = (first.out_features + 31) // 32 * 32
-        if (MIXED_TAIL and len(tail) >= 2 and h_n < h_pad and len(tail) + 1 <= 8 and HYBRID_ONE_NODE
+        if (len(tail) >= 2 and h_n < h_pad
                 and F_.mlp_fused_family([h_n] + widths[1:], outputs.shape[0]) == F_.MLP_FAMILY_MIXED):
             narrow = (tail[0], h_n, tail[0].out_features)
         copies = iter(_PaddedLinear.get_many([p for p in padded if p is not None] + ([narrow] if narrow else [])))
@@ -1140,11 +1051,7 @@ class MultilayerPerceptionLayer(BaseLayer):
         tensors = [first.weight, first.bias, use[0][0], use[0][1]]
         for mod, (w_use, b_use) in zip(tail, use[1:]):
             tensors += [mod.weight, mod.bias, w_use, b_use]
-        if len(tail) + 1 <= 8 and HYBRID_ONE_NODE:
-            out = _HybridMLP.apply(outputs, w_narrow, *tensors)
-        else:
-            h1 = _MLPStack.apply(outputs, ((True, False),), *tensors[:4])
-            out = F_._FusedMLPTail.apply(h1, *tensors[4:])
+        out = _HybridMLP.apply(outputs, w_narrow, *tensors)
         out.names = ('B', 'O',)
         return out
 
@@ -1152,22 +1059,11 @@ class MultilayerPerceptionLayer(BaseLayer):
         """Narrow stacks (every width <= 512: the per-field MLP of DeepAndCrossNetwork, 64 -> 400 -> 400 -> 400 -> 64 on
         B*N rows) as ONE kernel per direction with the activations of a row tile kept in LDS (trs_mlp_fused_*,
         SURVEY.md 8f N4); None when the stack is not Linear -> ReLU ... -> Linear with biases or does not fit."""
-        lin = [m for m in mods if not isinstance(m, nn.Dropout)]
-        Ws, bs = [], []
-        i = 0
-        while i < len(lin):
-            mod = lin[i]
-            if not isinstance(mod, nn.Linear) or mod.bias is None or mod.weight.dtype != outputs.dtype:
-                return None
-            relu = i + 1 < len(lin) and type(lin[i + 1]) is nn.ReLU
-            last = i + (2 if relu else 1) >= len(lin)
-            if relu == last:                      # hidden layers carry a ReLU, the output layer does not
-                return None
-            Ws.append(mod.weight)
-            bs.append(mod.bias)
-            i += 2 if relu else 1
-        if len(Ws) < 2:
+        layers = _linear_relu_stack(mods, outputs.dtype)
+        if not layers or len(layers) < 2 or layers[-1][1] or not all(relu for _, relu in layers[:-1]):
             return None
+        Ws = [mod.weight for mod, _ in layers]
+        bs = [mod.bias for mod, _ in layers]
         widths = [Ws[0].shape[1]] + [w.shape[0] for w in Ws]
         if any(a.shape[1] != b for a, b in zip(Ws[1:], widths[1:-1])) or outputs.shape[-1] != widths[0]:
             return None
