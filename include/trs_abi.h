@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TRS_ABI_VERSION 2
+#define TRS_ABI_VERSION 3
 
 enum { TRS_F32 = 0, TRS_BF16 = 1 };
 enum { TRS_I64 = 0, TRS_I32 = 1 };
@@ -350,10 +350,10 @@ int trs_mlp_fused_supported(int32_t num_layers, const int32_t* widths);
  * layer) have a second pair of kernels (csrc/mlp_ro.hpp: a wave owns 64 / 32 rows for the whole stack) behind the same
  * two entry points, and the two families lay the sign bits out differently.  Which family runs is a PER-CALL argument --
  * the library keeps no mode:
- *   trs_mlp_fused_fwd(family = AUTO | TILE | ROW_OWNER); AUTO = ROW_OWNER for the covered shapes from 131 072 rows on
- *   (the start-up environment may set TRS_MLP_RO=0: never / 2: at any size -- read once when the library is loaded);
- *   trs_mlp_fused_family(num_layers, widths, rows, request) -> the family (TILE or ROW_OWNER) that request runs, 0 when it
- *   cannot be met (ROW_OWNER on an uncovered shape; the forward then returns TRS_EINVAL).  A pure function.
+ *   trs_mlp_fused_fwd(family = AUTO | TILE | ROW_OWNER | MIXED); AUTO = ROW_OWNER for the covered shapes from 131 072
+ *   rows on, MIXED for them from 32 768 rows on, TILE otherwise;
+ *   trs_mlp_fused_family(num_layers, widths, rows, request) -> the family (TILE, ROW_OWNER or MIXED) that request runs, 0
+ *   when it cannot be met (ROW_OWNER on an uncovered shape; the forward then returns TRS_EINVAL).  A pure function.
  *   trs_mlp_fused_bwd_data(family) must be given THAT value (TILE, ROW_OWNER or MIXED; AUTO is TRS_EINVAL): the caller records
  *   what its forward ran, so a policy or size threshold cannot come between a forward and its backward.              */
 #define TRS_MLP_FAMILY_AUTO 0
@@ -417,9 +417,6 @@ int trs_embed_fm_sharded(const void* back, int64_t back_rows, const void* local,
                          int32_t E, int32_t dtype, const int32_t* inv_pos, const int32_t* send_ids, int32_t self_lo,
                          int32_t self_n, int64_t B, int32_t N, void* emb, void* fm, float* fm_sum, int32_t* err_flag,
                          trs_stream_t stream);
-/* out[pos[k],:] = rows[k,:]  (un-permute received rows into the (B*N,E) block) */
-int trs_scatter_by_pos(const void* rows, const int32_t* pos, int64_t K, int32_t E, int32_t dtype,
-                       void* out, trs_stream_t stream);
 /* out[k,:] = g_block[pos[k],:] + g_fm[b,:]*(fm_sum[b,:] - x[pos[k],:]), b = pos[k]/N: the block gradient (and
  * the FM second-order backward when the FM term was fused into the sharded lookup) in exchange order, one pass.
  * g_block or the (g_fm, fm_sum, x) triple may be NULL.  pos[k] < 0 marks a padding slot of a fixed-capacity
@@ -427,9 +424,6 @@ int trs_scatter_by_pos(const void* rows, const int32_t* pos, int64_t K, int32_t 
 int trs_permute_grad(const void* g_block, const void* g_fm, const float* fm_sum, const void* x,
                      const int32_t* pos, int64_t K, int32_t N, int32_t E, int32_t dtype, void* out,
                      trs_stream_t stream);
-/* out[k,:] = rows[pos[k],:]  (permute the block gradient into exchange order) */
-int trs_gather_by_pos(const void* rows, const int32_t* pos, int64_t K, int32_t E, int32_t dtype,
-                      void* out, trs_stream_t stream);
 
 /* ---- Linear with one output unit (the logit layer of the DeepFM / xDeepFM MLP, multilayer_perceptron.py:51) -------
  * out[r] = h[r,:] . w + bias[0]: a row-wise dot product, not a GEMM.  h (rows, C), w (C); C * sizeof(T) / 16 must be
@@ -596,13 +590,21 @@ int trs_pair_epilogue_fwd(void* T, const void* x, const void* bias, int32_t bias
 int trs_pair_epilogue_bwd(const void* g, const void* x, void* T, int32_t mode, int64_t B, int32_t N, int32_t E,
                           int32_t dtype, void* gxj, trs_stream_t stream);
 
-/* AttentionalFactorizationMachineLayer (attentional_factorization_machine.py:86-125, dropouts outside):
- *   prod[b,p,:] = x[b,i_p,:] * x[b,j_p,:];  attn[b,p] = softmax_p(w2 . relu(W1 prod + b1) + b2);
- *   out[b,:] = sum_p attn[b,p] prod[b,p,:]            W1 (A,E), b1 (A), w2 (A), b2 (1); out (B,E), attn (B,NC2)
- * bwd: g_out (B,E) / g_attn (B,NC2) may be NULL; gx (B,N,E); gW1 (A,E), gb1 (A), gw2 (A), gb2 (1) fp32,
- * ACCUMULATED into.  E, A <= 128.                                                                   */
-int trs_afm_fwd(const void* x, const void* W1, const void* b1, const void* w2, const void* b2, int64_t B, int32_t N,
-                int32_t E, int32_t A, int32_t dtype, void* out, void* attn, trs_stream_t stream);
+/* AttentionalFactorizationMachineLayer (attentional_factorization_machine.py:82-125) with the reference's dropout on the
+ * attention scores applied INSIDE the pass (nn.Dropout is the last module of ``self.attention``, so in training the
+ * weighted sum and the returned scores both see the dropped scores):
+ *   prod[b,p,:] = x[b,i_p,:] * x[b,j_p,:];  attn[b,p] = softmax_p(w2 . relu(W1 prod + b1) + b2)
+ *   keep (B,NC2) uint8, nonzero = kept; multiplier m[b,p] = keep ? keep_scale : 0   (keep_scale = 1/(1-p))
+ *   attn      (B,NC2) = the softmax BEFORE dropout (what the backward needs)
+ *   attn_drop (B,NC2) = attn * m   (what the layer returns);   out[b,:] = sum_p attn_drop[b,p] prod[b,p,:]
+ *   W1 (A,E), b1 (A), w2 (A), b2 (1); out (B,E).  E, A <= 128.
+ * keep == NULL: no dropout -- out[b,:] = sum_p attn[b,p] prod[b,p,:]; attn_drop is not written (may be NULL).
+ * bwd: g_out (B,E) / g_attn (B,NC2) may be NULL; g_attn is the gradient of attn_drop (of attn when keep == NULL),
+ * ``attn`` the un-dropped softmax written by the forward; gx (B,N,E); gW1 (A,E), gb1 (A), gw2 (A), gb2 (1) fp32,
+ * ACCUMULATED into.                                                                                                  */
+int trs_afm_fwd_dropout(const void* x, const void* W1, const void* b1, const void* w2, const void* b2,
+                        const uint8_t* keep, float keep_scale, int64_t B, int32_t N, int32_t E, int32_t A,
+                        int32_t dtype, void* out, void* attn, void* attn_drop, trs_stream_t stream);
 /* Host-side helper (no device work): the backward kernel's schedule of 16-pair tiles for N fields -- every pair (i < j)
  * exactly once, the pairs of a tile sharing no field (what lets a wave add into per-field gradient rows without
  * atomics), packed greedily from the round-robin rounds.  tiles[16 t + k] = (i << 8) | j, 0xffff = empty slot;
@@ -610,22 +612,6 @@ int trs_afm_fwd(const void* x, const void* W1, const void* b1, const void* w2, c
  * attentional_factorization_machine.py:86-120 (the pair enumeration the attention runs over).                   */
 int trs_afm_pair_tiles(int32_t N, uint16_t* tiles, int32_t capacity, int32_t* ntiles);
 size_t trs_afm_bwd_workspace_bytes(int64_t B, int32_t N, int32_t E, int32_t A);
-int trs_afm_bwd(const void* g_out, const void* g_attn, const void* x, const void* attn, const void* W1,
-                const void* b1, const void* w2, int64_t B, int32_t N, int32_t E, int32_t A, int32_t dtype, void* gx,
-                float* gW1, float* gb1, float* gw2, float* gb2, void* workspace, size_t ws_bytes,
-                trs_stream_t stream);
-
-/* The same layer with the reference's dropout on the attention scores applied INSIDE the pass
- * (attentional_factorization_machine.py:82, 105-113: nn.Dropout is the last module of ``self.attention``, so in training
- * the weighted sum and the returned scores both see the dropped scores):
- *   keep (B,NC2) uint8, nonzero = kept; multiplier m[b,p] = keep ? keep_scale : 0   (keep_scale = 1/(1-p))
- *   attn      (B,NC2) = the softmax BEFORE dropout (what the backward needs)
- *   attn_drop (B,NC2) = attn * m   (what the layer returns);   out[b,:] = sum_p attn_drop[b,p] prod[b,p,:]
- * keep == NULL: no dropout, attn_drop is not written (== trs_afm_fwd / trs_afm_bwd).
- * bwd: g_attn is the gradient of attn_drop; ``attn`` is the un-dropped softmax written by the forward.        */
-int trs_afm_fwd_dropout(const void* x, const void* W1, const void* b1, const void* w2, const void* b2,
-                        const uint8_t* keep, float keep_scale, int64_t B, int32_t N, int32_t E, int32_t A,
-                        int32_t dtype, void* out, void* attn, void* attn_drop, trs_stream_t stream);
 int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const void* x, const void* attn, const uint8_t* keep,
                         float keep_scale, const void* W1, const void* b1, const void* w2, int64_t B, int32_t N, int32_t E,
                         int32_t A, int32_t dtype, void* gx, float* gW1, float* gb1, float* gw2, float* gb2,

@@ -31,8 +31,8 @@ def test_exports_every_declared_symbol(lib):
     assert sorted(_abi.SIGNATURES) == names, "ctypes SIGNATURES out of sync with the header"
 
 
-def test_abi_version_2_and_sizes(lib):
-    assert lib.trs_version() == 2
+def test_abi_version_3_and_sizes(lib):
+    assert lib.trs_version() == 3
     assert lib.trs_csr_workspace_bytes(1000, 100) >= 400
     assert lib.trs_scatter_workspace_bytes(100000, 10, 16, 1) >= 8
 

@@ -2,7 +2,6 @@
 median of HIP-event timings on the launch stream, with and without the (B,N,E) block written.
 
     python tools/embed_bench.py [--rows 32000000] [--batch 65536] [--zipf] [--layout uniform|skewed]
-    TRS_EMBED_PIPE=4|8: the pipelined walk (ids of the next chunk requested beside the current chunk's rows)
 """
 import argparse
 import os
@@ -39,5 +38,5 @@ for fm_only in (False, True):
     _abi.time_kernel("trs_embed_fm", False)
     med = ts[len(ts) // 2] * 1e-3
     alg = B * N * (8 + E * 2) + (0 if fm_only else B * N * E * 2) + B * E * 2
-    print(f"rows {a.rows:>9d} pipe {os.environ.get('TRS_EMBED_PIPE', '0')} {'fm-only' if fm_only else 'with block'}: "
+    print(f"rows {a.rows:>9d} {'fm-only' if fm_only else 'with block'}: "
           f"median {med * 1e6:7.2f} us  min {ts[0] * 1e3:7.2f}  {alg / med / 1e9:7.1f} GB/s  frac {alg / med / 8e12:.4f}")

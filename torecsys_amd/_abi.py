@@ -62,7 +62,6 @@ SIGNATURES = {
     "trs_pair_bilinear_bwd_w_mfma": (c_int32, [_P, _P, _I32, _I64, _I32, _I32, _I32, _P, _P, _SZ, _P]),
     "trs_pair_epilogue_fwd": (c_int32, [_P, _P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_epilogue_bwd": (c_int32, [_P, _P, _P, _I32, _I64, _I32, _I32, _I32, _P, _P]),
-    "trs_afm_fwd": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "trs_afm_fwd_dropout": (c_int32, [_P, _P, _P, _P, _P, _P, _F32, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "trs_afm_bwd_dropout": (c_int32, [_P, _P, _P, _P, _P, _F32, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P,
                                       _P, _P, _SZ, _P]),
@@ -72,7 +71,6 @@ SIGNATURES = {
     "trs_rows_gemm_supported": (c_int32, [_I32, _I32, _I32]),
     "trs_rows_gemm": (c_int32, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _SZ, _P]),
     "trs_afm_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
-    "trs_afm_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "trs_pack_columns": (c_int32, [_P, _P, _I32, _I32, _I64, _P, _I32, _P]),
     "trs_mark_timestamp": (c_int32, [_P, _I32, _P]),
     "trs_wall_clock_khz": (_I64, []),
@@ -135,8 +133,6 @@ SIGNATURES = {
     "trs_embed_fm_sharded": (c_int32, [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _I32, _I32, _I64, _I32, _P, _P, _P, _P,
                                        _P]),
     "trs_permute_grad": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
-    "trs_scatter_by_pos": (c_int32, [_P, _P, _I64, _I32, _I32, _P, _P]),
-    "trs_gather_by_pos": (c_int32, [_P, _P, _I64, _I32, _I32, _P, _P]),
 }
 
 _lib = None

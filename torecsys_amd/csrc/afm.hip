@@ -7,8 +7,6 @@
 // block of one sample, the attention weights and the NC2 logits in LDS and the products never leave registers.
 // Generic path (any dtype / shape with E, A <= 128): lanes along the attention units for the hidden layer
 // (wavefront reduction for the logit), lanes along e for the weighted sum and the backward.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include <type_traits>
@@ -874,11 +872,6 @@ using namespace trs;
   TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, name ": dtype %d", dtype);           \
   TRS_REQUIRE(E <= AFM_MAX && A <= AFM_MAX, TRS_ESHAPE, name ": E = %d, A = %d (both <= %d)", E, A, AFM_MAX)
 
-extern "C" int trs_afm_fwd(const void* x, const void* W1, const void* b1, const void* w2, const void* b2, int64_t B,
-                           int32_t N, int32_t E, int32_t A, int32_t dtype, void* out, void* attn, trs_stream_t stream) {
-  return trs_afm_fwd_dropout(x, W1, b1, w2, b2, nullptr, 1.f, B, N, E, A, dtype, out, attn, nullptr, stream);
-}
-
 extern "C" int trs_afm_fwd_dropout(const void* x, const void* W1, const void* b1, const void* w2, const void* b2,
                                    const uint8_t* keep, float keep_scale, int64_t B, int32_t N, int32_t E, int32_t A,
                                    int32_t dtype, void* out, void* attn, void* attn_drop, trs_stream_t stream) {
@@ -889,8 +882,7 @@ extern "C" int trs_afm_fwd_dropout(const void* x, const void* W1, const void* b1
   TRS_REQUIRE(keep == nullptr || attn_drop != nullptr, TRS_EINVAL, "afm_fwd: a keep mask needs the attn_drop output");
   const int P = N * (N - 1) / 2;
   hipStream_t s = (hipStream_t)stream;
-  static const bool no_mfma = getenv("TRS_AFM_GENERIC") != nullptr;      // tests pin the MFMA path to the generic one
-  if (!no_mfma && dtype == TRS_BF16 && (E == 32 || E == 64 || E == 128) && A % 16 == 0 && A <= 128 &&
+  if (dtype == TRS_BF16 && (E == 32 || E == 64 || E == 128) && A % 16 == 0 && A <= 128 &&
       afm_fwd_mfma_lds(N, E) <= 64 * 1024 && aligned16(x) && aligned16(W1)) {
     const size_t lds = afm_fwd_mfma_lds(N, E);
     // one round of workgroups, each walking its share of the samples (A = E = 64: 162 registers = 3 workgroups per CU;
@@ -959,14 +951,6 @@ extern "C" size_t trs_afm_bwd_workspace_bytes(int64_t B, int32_t N, int32_t E, i
   return (size_t)afm_grid(B) * ((size_t)A * E + 2 * A + 1) * 4 + 256;
 }
 
-extern "C" int trs_afm_bwd(const void* g_out, const void* g_attn, const void* x, const void* attn, const void* W1,
-                           const void* b1, const void* w2, int64_t B, int32_t N, int32_t E, int32_t A, int32_t dtype,
-                           void* gx, float* gW1, float* gb1, float* gw2, float* gb2, void* workspace, size_t ws_bytes,
-                           trs_stream_t stream) {
-  return trs_afm_bwd_dropout(g_out, g_attn, x, attn, nullptr, 1.f, W1, b1, w2, B, N, E, A, dtype, gx, gW1, gb1, gw2, gb2,
-                             workspace, ws_bytes, stream);
-}
-
 extern "C" int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const void* x, const void* attn,
                                    const uint8_t* keep, float keep_scale, const void* W1, const void* b1, const void* w2,
                                    int64_t B, int32_t N, int32_t E, int32_t A, int32_t dtype, void* gx, float* gW1,
@@ -984,14 +968,12 @@ extern "C" int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const 
   TRS_REQUIRE(lds <= 160 * 1024, TRS_ESHAPE, "afm_bwd: N = %d, E = %d, A = %d need %zu bytes of LDS", N, E, A, lds);
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)workspace;
-  static const bool no_mfma = getenv("TRS_AFM_GENERIC") != nullptr;
-  if (!no_mfma && dtype == TRS_BF16 && (E == 32 || E == 64 || E == 128) && A % 32 == 0 && A <= 128 &&
+  if (dtype == TRS_BF16 && (E == 32 || E == 64 || E == 128) && A % 32 == 0 && A <= 128 &&
       (A / 16) * (E / 32) <= 12 &&
       afm_bwd_mfma_lds(N, E, A) <= 160 * 1024 && aligned16(x) && aligned16(W1)) {
     int T = 0;
-    static const bool rounds_only = getenv("TRS_AFM_ROUNDS") != nullptr;
     const AfmTiles* packed = afm_packed_tiles(N, &T);
-    if (N <= 32 || rounds_only) T = 0;               // a round IS a maximal tile there
+    if (N <= 32) T = 0;  // a round IS a maximal tile there
     // (four waves = one per SIMD: A = 64, E = 64 already holds 388 registers per wave -- W1 / W1^T fragments, the dW1
     // accumulators, both x rows of the tile -- so a second wave per SIMD would spill; measured with six: 536 B of scratch)
     const int waves = 4;

@@ -316,18 +316,12 @@ __device__ __forceinline__ void layer_matmul_pre(const uint4* Wl, const float* b
 // k0..k0+3 first on even lane groups, k0+4..k0+7 first on odd ones (the two groups of a 32-lane half then cover all 64
 // banks; the permutation of k is the same for both MFMA operands).
 // LDS at E = 64, L = 6: W 48 KiB + W^T (layers 1..5) 40 KiB + biases 1.5 KiB + slabs 48 KiB = 137.5 KiB.
-// wave roles per workgroup by E (NT = E / 16): E = 64 may trade chain waves for dW waves (TRS_B3_CHAIN64 / TRS_B3_DW64);
-// E = 32 has only NT * NT = 4 dW tiles per layer, i.e. at most two dW waves that own whole row tiles
-#ifndef TRS_B3_CHAIN64
-#define TRS_B3_CHAIN64 6
-#endif
-#ifndef TRS_B3_DW64
-#define TRS_B3_DW64 2
-#endif
+// wave roles per workgroup, the same for both E (NT = E / 16): E = 32 has only NT * NT = 4 dW tiles per layer, i.e. at
+// most two dW waves that own whole row tiles
 template <int NT>
 struct B3 {
-  static constexpr int CHAIN = NT >= 4 ? TRS_B3_CHAIN64 : 6;      // chain waves per workgroup (one 16-row tile each)
-  static constexpr int DW = NT >= 4 ? TRS_B3_DW64 : 2;            // weight-gradient waves
+  static constexpr int CHAIN = 6;                                 // chain waves per workgroup (one 16-row tile each)
+  static constexpr int DW = 2;                                    // weight-gradient waves
   static constexpr int ROWS = CHAIN * 16;                         // rows per workgroup step
   static constexpr int PANEL = ROWS * 32;                         // bytes of one 16-column panel of a slab
 };
@@ -386,30 +380,7 @@ __device__ __forceinline__ void layer_matmul_ks(const uint4* Wl, const float* bi
   }
 }
 
-#ifdef B3_TRACE      // developer build (tools/cross_trace.py): time stamps of workgroup 0's wave 0 (chain) and first dW wave
-__device__ long long b3_trace[2][1024];
-#define B3_STAMP(who, idx) \
-  do { if (blockIdx.x == 0 && lane == 0 && (idx) < 1024) b3_trace[who][idx] = (long long)wall_clock64(); } while (0)
-#else
-#define B3_STAMP(who, idx) do {} while (0)
-#endif
-
-// -DTRS_B3_FLAGS (round 6 experiment, OFF: measured 760-780 us against 633-679 us for the barrier form on one box,
-// profiles/r06_logs/ab_cross_flags.txt): slab hand-over between the two wave roles without workgroup barriers -- a
-// counter per slab slot and direction in LDS.  ready[slot] counts the chain waves that have written their piece of the slot's current use, done[slot] the dW
-// waves that have finished reading it; both only ever grow, so use k of a slot is complete at CHAIN * (k + 1) /
-// DW * (k + 1).  A chain wave no longer waits for the OTHER chain waves at every layer (the s_barrier made all eight waves
-// meet eleven times per group: the slowest wave of every step set the pace), only -- before it overwrites a slot -- for the
-// dW waves to be done with that slot's previous use, two steps earlier.  LDS operations of one wave execute in order, and
-// the counter is bumped behind an explicit s_waitcnt, so a reader that sees the count sees the data.
-__device__ __forceinline__ void b3_wait_ge(int* flag, int target) {
-  while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
-}
-__device__ __forceinline__ void b3_signal(int* flag, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
+// (slab hand-over by LDS counters instead of barriers: 760-780 vs 633-679 us, profiles/r06_logs/ab_cross_flags.txt)
 template <int NT, int L, bool DETACH>
 __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mfma_bwd3_kernel(
     const uint4* __restrict__ x, const uint4* __restrict__ gout, const uint4* __restrict__ Wp,
@@ -429,10 +400,6 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
   float* bs = reinterpret_cast<float*>(Wts + (L - 1) * FRAG);
   char* duslab = reinterpret_cast<char*>(bs + L * E);         // [slot 2][panel NT][B3_ROWS][32 B]
   char* xslab = duslab + 2 * TENSOR;                          // same
-#ifdef TRS_B3_FLAGS
-  __shared__ int flags[4];                                    // ready[2], done[2] (static: their address is a constant)
-  if (threadIdx.x < 4) flags[threadIdx.x] = 0;
-#endif
   for (int i = threadIdx.x; i < L * FRAG; i += blockDim.x) Ws[i] = Wp[i];
   for (int i = threadIdx.x; i < (L - 1) * FRAG; i += blockDim.x) Wts[i] = Wtp[i];
   for (int i = threadIdx.x; i < L * E; i += blockDim.x) bs[i] = bp[i] + 1.f;      // the backward only ever needs u_l + 1
@@ -472,9 +439,7 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
     // this lane's 16-byte pieces of a slab: piece c covers columns 32c+8q .. +7 -> panel 2c + (q>>1), half q&1 (swapped
     // for rows with bit 2 set)
     const int piece0 = (q >> 1) * B3_PANEL + (wave * 16 + r) * 32 + (((q & 1) ^ ((r >> 2) & 1)) * 16);
-    int gi = 0;
-    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x, ++gi) {
-      if (wave == 0) B3_STAMP(0, gi * 8);
+    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
       // LDS addresses are re-derived from two laundered lane offsets in every group: left alone, LICM keeps ~40
       // loop-invariant per-fragment / per-slot addresses in registers for the whole kernel (LDS offsets beyond 64 KiB
       // do not fit the DS immediate) and the wave, which lives on 168 registers, spills its g_l to scratch
@@ -509,7 +474,6 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
           }
         }
       }
-      if (wave == 0) B3_STAMP(0, gi * 8 + 1);
       // ---- phase B: forward recompute; dx0, and du_l / x_l for the dW waves
       XTile<NT> dx0;
 #pragma unroll
@@ -539,9 +503,6 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
         pack_tile<NT>(du, Bdu);
         char* dslot = duslab + ((step & 1) ? TENSOR : 0) + pc0;
         char* xslot = xslab + ((step & 1) ? TENSOR : 0) + pc0;
-#ifdef TRS_B3_FLAGS
-        if (step >= 2) b3_wait_ge(flags + 2 + (step & 1), B3_DW * (step >> 1));      // the slot's previous use has been read
-#endif
 #pragma unroll
         for (int c = 0; c < KS; ++c) {
           *reinterpret_cast<uint4*>(dslot + 2 * c * B3_PANEL) = Bdu[c];
@@ -555,16 +516,8 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
             for (int i = 0; i < 4; ++i) nx.v[mt][i] = x0f.v[mt][i] * up[mt][i];
           pack_tile<NT>(nx, Bx);
         }
-#ifndef TRS_B3_FLAGS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (wave == 0 && l < 3) B3_STAMP(0, gi * 8 + 2 + 2 * l);      // before / after the barrier of steps 0..2
         __builtin_amdgcn_s_barrier();
-        if (wave == 0 && l < 3) B3_STAMP(0, gi * 8 + 3 + 2 * l);
-#else
-        if (wave == 0 && l < 3) B3_STAMP(0, gi * 8 + 2 + 2 * l);
-        b3_signal(flags + (step & 1), lane);                            // this wave's piece of the slot is in LDS
-        if (wave == 0 && l < 3) B3_STAMP(0, gi * 8 + 3 + 2 * l);
-#endif
       }
       if (detach_first == 0) {
 #pragma unroll
@@ -599,25 +552,15 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
 #pragma unroll
       for (int k = 0; k < TPW; ++k) dWacc[l][k] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    int gi = 0;
-    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x, ++gi) {
+    for (int64_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
 #pragma unroll
       for (int l = 0; l < L; ++l, ++step) {
-#ifndef TRS_B3_FLAGS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (wq == 0 && l < 4) B3_STAMP(1, gi * 8 + 2 * l);             // arrival at / release from the barrier
         __builtin_amdgcn_s_barrier();                   // the chain waves have written slot step & 1 (layer l)
-        if (wq == 0 && l < 4) B3_STAMP(1, gi * 8 + 2 * l + 1);
-#else
-        if (wq == 0 && l < 4) B3_STAMP(1, gi * 8 + 2 * l);
-        b3_wait_ge(flags + (step & 1), B3_CHAIN * ((step >> 1) + 1));   // every chain wave has written slot step & 1 (layer l)
-        if (wq == 0 && l < 4) B3_STAMP(1, gi * 8 + 2 * l + 1);
-#endif
         const char* du_t = duslab + ((step & 1) ? TENSOR : 0);
         const char* x_t = xslab + ((step & 1) ? TENSOR : 0);
         const unsigned hot = (r == l) ? 0x3f803f80u : 0u;               // bf16 1.0 pairs in column l
         const uint4 onehot = make_uint4(hot, hot, hot, hot);
-#ifndef B3_NO_DW        // (ablation switch of tools/cross_trace.py)
 #pragma unroll
         for (int ks = 0; ks < B3_ROWS / 32; ++ks) {
           s16x8 Bf[NT];
@@ -634,10 +577,6 @@ __global__ __launch_bounds__(64 * (B3<NT>::CHAIN + B3<NT>::DW), 2) void cross_mf
                                                                __builtin_bit_cast(bf16x8, onehot), dbacc[m], 0, 0, 0);
           }
         }
-#endif
-#ifdef TRS_B3_FLAGS
-        b3_signal(flags + 2 + (step & 1), lane);                        // this wave has read the slot
-#endif
       }
     }
     // partial results of this workgroup: D layout -> (row m = 4q+i -> e_out, col n = r -> e_in)
@@ -760,12 +699,6 @@ static int cross_bwd_launch(const void* x, const void* g, const uint4* Wp, const
   hipLaunchKernelGGL(cross_reduce_partials_kernel, dim3((L * E + 63) / 64), dim3(1024), 0, s, dbpart, grid, L * E, db);
   return check_launch("cross_bwd(mfma)");
 }
-
-#ifdef B3_TRACE
-extern "C" int trs_debug_b3_trace(long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(b3_trace), sizeof(long long) * 2 * 1024, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 int cross_mfma_bwd(const void* x, const void* W, const void* b, const void* g, int64_t rows, int E, int L, void* dx,
                    float* dW, float* db, int detach_first, void* workspace, size_t ws_bytes, hipStream_t s) {

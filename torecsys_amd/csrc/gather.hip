@@ -259,59 +259,6 @@ __global__ __launch_bounds__(256) void fa_gather_elem_kernel(
   }
 }
 
-// ---- permutation helpers for the sharded lookup
-template <bool SCATTER>
-__global__ __launch_bounds__(256) void permute_rows_vec_kernel(const uint4* __restrict__ rows,
-                                                               const int32_t* __restrict__ pos,
-                                                               uint4* __restrict__ out, int64_t K, int vpr) {
-  const int64_t total = K * vpr;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const bool f32 = total < ((int64_t)1 << 32);
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t k = udiv_fast(t, vpr, f32);
-    const int lv = (int)(t - k * vpr);
-    const int64_t p = pos[k];
-    if (SCATTER) store_stream(&out[p * vpr + lv], rows[t]);
-    else store_stream(&out[t], rows[p * vpr + lv]);
-  }
-}
-template <typename T, bool SCATTER>
-__global__ __launch_bounds__(256) void permute_rows_elem_kernel(const T* __restrict__ rows,
-                                                                const int32_t* __restrict__ pos,
-                                                                T* __restrict__ out, int64_t K, int E) {
-  const int64_t total = K * E;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t k = t / E;
-    const int e = (int)(t - k * E);
-    const int64_t p = pos[k];
-    if (SCATTER) out[p * E + e] = rows[t];
-    else out[t] = rows[p * E + e];
-  }
-}
-
-template <bool SCATTER>
-static int permute_rows(const void* rows, const int32_t* pos, int64_t K, int E, int dtype, void* out,
-                        hipStream_t s) {
-  TRS_REQUIRE(rows && pos && out, TRS_EINVAL, "permute_rows: NULL pointer");
-  TRS_REQUIRE(K >= 0 && E > 0, TRS_EINVAL, "permute_rows: bad size");
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "permute_rows: dtype %d", dtype);
-  if (K == 0) return TRS_OK;
-  const int row_bytes = E * dtype_size(dtype);
-  if (row_bytes % 16 == 0 && aligned16(rows) && aligned16(out)) {
-    const int vpr = row_bytes / 16;
-    hipLaunchKernelGGL((permute_rows_vec_kernel<SCATTER>), dim3(stream_grid(K * vpr, 256, 8192)), dim3(256), 0,
-                       s, (const uint4*)rows, pos, (uint4*)out, K, vpr);
-  } else if (dtype == TRS_F32) {
-    hipLaunchKernelGGL((permute_rows_elem_kernel<float, SCATTER>), dim3(stream_grid(K * E, 256, 8192)),
-                       dim3(256), 0, s, (const float*)rows, pos, (float*)out, K, E);
-  } else {
-    hipLaunchKernelGGL((permute_rows_elem_kernel<bf16_t, SCATTER>), dim3(stream_grid(K * E, 256, 8192)),
-                       dim3(256), 0, s, (const bf16_t*)rows, pos, (bf16_t*)out, K, E);
-  }
-  return check_launch("permute_rows");
-}
-
 // ---- index staging: per-field columns -> (B, W) index matrix ---------------------------------------
 constexpr int PACK_MAX_W = 256;
 constexpr int PACK_TB = 64;          // samples per tile
@@ -580,15 +527,4 @@ extern "C" int trs_fa_gather_rows(const void* const* tables, int64_t V, int32_t 
   if (idx_dtype == TRS_I64)
     return fa_dispatch<int64_t>(tables, V, E, dtype, (const int64_t*)idx, offsets, B, N, out, err_flag, s);
   return fa_dispatch<int32_t>(tables, V, E, dtype, (const int32_t*)idx, offsets, B, N, out, err_flag, s);
-}
-
-extern "C" int trs_scatter_by_pos(const void* rows, const int32_t* pos, int64_t K, int32_t E, int32_t dtype,
-                                  void* out, trs_stream_t stream) {
-  if (K == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
-  return permute_rows<true>(rows, pos, K, E, dtype, out, (hipStream_t)stream);
-}
-extern "C" int trs_gather_by_pos(const void* rows, const int32_t* pos, int64_t K, int32_t E, int32_t dtype,
-                                 void* out, trs_stream_t stream) {
-  if (K == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
-  return permute_rows<false>(rows, pos, K, E, dtype, out, (hipStream_t)stream);
 }

@@ -26,21 +26,10 @@ typedef __attribute__((ext_vector_type(8))) __bf16 mf_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float mf_f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned mf_u32x4;
 
-#ifndef TRS_MF_ROWS
-#define TRS_MF_ROWS 128
-#endif
-#ifndef TRS_ROWS_GEMM_PLAIN_STORES
-#define TRS_ROWS_GEMM_PLAIN_STORES 0      // 1: the wide input gradient written with cache-allocating stores (experiment)
-#endif
-#ifndef TRS_MF_GRID
-#define TRS_MF_GRID 256
-#endif
-#ifndef TRS_MF_MINW
-#define TRS_MF_MINW 2      // waves per SIMD the kernels are compiled for (2 = one 8-wave workgroup per CU)
-#endif
-constexpr int MF_ROWS = TRS_MF_ROWS;  // rows per workgroup pass
+constexpr int MF_ROWS = 128;          // rows per workgroup pass
 constexpr int MF_MT = MF_ROWS / 16;   // 16-row tiles
 constexpr int MF_WAVES = 8;
+constexpr int MF_MINW = 2;            // waves per SIMD the kernels are compiled for (2 = one 8-wave workgroup per CU)
 constexpr int MF_MAXP = 2;            // 32-column pairs per wave: widths up to 8 * 2 * 32 = 512
 constexpr int MF_MAXL = 8;
 constexpr int MF_MASK_TILE = 64 * MF_WAVES * 16;   // mask bytes per 128-row pass and layer: 16 per lane (see mlp_fused_fwd_kernel)
@@ -388,7 +377,7 @@ __device__ __forceinline__ void mlp_load_in(char* act, int act_str, const void* 
 __device__ __forceinline__ unsigned mf_mask_byte(unsigned m) { return (m & 0xFu) | ((m >> 12) & 0xF0u); }
 __device__ __forceinline__ int mf_mask_bit(int j) { return (j >> 1) + 4 * (j & 1); }
 #define MF_BAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-__global__ __launch_bounds__(64 * MF_WAVES, TRS_MF_MINW) void mlp_fused_fwd_kernel(MlpArgs a) {
+__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_fwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;                                          // [MF_ROWS][act_str]
   float* bias_s = reinterpret_cast<float*>(act + MF_ROWS * a.act_str);      // all layers' padded biases, back to back
@@ -528,7 +517,7 @@ struct RowsGemmArgs {
   int64_t rows;
   int in_stride, K, N, out_cols, out_stride, act_str;
 };
-__global__ __launch_bounds__(64 * MF_WAVES, TRS_MF_MINW) void mlp_rows_gemm_kernel(RowsGemmArgs a) {
+__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_rows_gemm_kernel(RowsGemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, r = lane & 15;
@@ -572,12 +561,8 @@ __global__ __launch_bounds__(64 * MF_WAVES, TRS_MF_MINW) void mlp_rows_gemm_kern
               v[4 + i] = acc[mi][2 * pi + 1][i];
             }
             if (colok && 16 * mi < left) {
-#if TRS_ROWS_GEMM_PLAIN_STORES
-              *reinterpret_cast<uint4*>(out0 + (size_t)mi * 16 * a.out_stride + 32 * sh.pair[pi]) = Vec16<bf16_t>::pack(v);
-#else
               store_stream(reinterpret_cast<uint4*>(out0 + (size_t)mi * 16 * a.out_stride + 32 * sh.pair[pi]),
                            Vec16<bf16_t>::pack(v));
-#endif
             }
           }
         }
@@ -592,7 +577,7 @@ __global__ __launch_bounds__(64 * MF_WAVES, TRS_MF_MINW) void mlp_rows_gemm_kern
 // step s works on layer l = L-1-s: input = d(pre-activation of layer l) (rows x N_l) in LDS, output = d(input of layer l)
 // = d(output of layer l-1), masked by layer l-1's ReLU mask into d(pre-activation of layer l-1).
 template <bool RO_MASKS>
-__global__ __launch_bounds__(64 * MF_WAVES, TRS_MF_MINW) void mlp_fused_bwd_kernel(MlpArgs a) {
+__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;
   float* scratch = reinterpret_cast<float*>(act + MF_ROWS * a.act_str);              // [8 row slices][512]
@@ -789,7 +774,7 @@ __global__ __launch_bounds__(256) void mlp_colsum_reduce_kernel(const float* __r
 }
 
 static inline int pad32(int v) { return (v + 31) / 32 * 32; }
-constexpr int MF_GRID = TRS_MF_GRID;
+constexpr int MF_GRID = 256;
 
 static bool mlp_fused_covers(int L, const int32_t* w) {
   if (L < 1 || L > MF_MAXL) return false;

@@ -50,22 +50,13 @@ static bool ro_matches(int L, const int32_t* w, bool reversed) {
 static inline int ro_ks(int w) { return w <= 16 ? 2 : (w + 15) / 16; }
 
 // Which kernel family runs a stack is a PER-CALL argument of the two entry points (trs_mlp_fused_family resolves a
-// request; the backward is told the family its forward ran -- the sign-bit layouts differ).  There is no mutable state:
-// the only process-wide input is the policy of TRS_MLP_FAMILY_AUTO, read once from the environment when the library is
-// loaded -- TRS_MLP_RO = 0: never the row-owner kernels; 1 (default): for the shapes they are built for from RO_MIN_ROWS
-// rows on (below that a workgroup sees one or two passes and the pipeline between passes -- next input, previous
-// epilogue -- has nothing to run against: DeepFM's tail at B = 65 536, one pass per CU, forward 74 vs 101 us but
-// backward 125 vs 92 us); 2: for those shapes at any size.
-static const int RO_AUTO_POLICY = [] {
-  const char* e = getenv("TRS_MLP_RO");
-  return e != nullptr && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1;
-}();
+// request; the backward is told the family its forward ran -- the sign-bit layouts differ).  There is no mutable state.
+// TRS_MLP_FAMILY_AUTO takes the row-owner kernels for the shapes they are built for from RO_MIN_ROWS rows on (below that
+// a workgroup sees one or two passes and the pipeline between passes -- next input, previous epilogue -- has nothing to
+// run against: DeepFM's tail at B = 65 536, one pass per CU, forward 74 vs 101 us but backward 125 vs 92 us), the mixed
+// family for those shapes from RO_MIXED_MIN_ROWS rows on, and the tile kernels otherwise.
 constexpr int64_t RO_MIN_ROWS = 131072;
 constexpr int64_t RO_MIXED_MIN_ROWS = 32768;
-static const bool RO_MIXED = [] {      // TRS_MLP_MIXED=0: AUTO never picks the mixed family
-  const char* e = getenv("TRS_MLP_MIXED");
-  return !(e != nullptr && e[0] == '0');
-}();
 
 bool mlp_ro_shape_ok(int L, const int32_t* widths, int64_t rows) {
   if (rows * 1024 >= ((int64_t)1 << 32)) return false;
@@ -80,11 +71,11 @@ int mlp_resolve_family(int L, const int32_t* widths, int64_t rows, int request) 
     case TRS_MLP_FAMILY_ROW_OWNER: return ok ? TRS_MLP_FAMILY_ROW_OWNER : 0;
     case TRS_MLP_FAMILY_MIXED: return ok ? TRS_MLP_FAMILY_MIXED : 0;
     case TRS_MLP_FAMILY_AUTO:
-      if (ok && (RO_AUTO_POLICY == 2 || (RO_AUTO_POLICY == 1 && rows >= RO_MIN_ROWS))) return TRS_MLP_FAMILY_ROW_OWNER;
+      if (ok && rows >= RO_MIN_ROWS) return TRS_MLP_FAMILY_ROW_OWNER;
       // below that: the row-owner FORWARD (one pass per CU at 65 536 rows: 74 us against the tile kernel's 94-101) with the
       // tile BACKWARD (92 against 119-125), which reads the row-owner sign-bit layout -- from RO_MIXED_MIN_ROWS rows on
       // (fewer rows do not fill the 256-row passes of 256 workgroups)
-      if (ok && RO_AUTO_POLICY == 1 && RO_MIXED && rows >= RO_MIXED_MIN_ROWS) return TRS_MLP_FAMILY_MIXED;
+      if (ok && rows >= RO_MIXED_MIN_ROWS) return TRS_MLP_FAMILY_MIXED;
       return TRS_MLP_FAMILY_TILE;
     default: return 0;
   }

@@ -35,8 +35,6 @@
 // 2.5 ms: partial lines written through), a value used right behind its load (the compiler's wait counts the weight
 // copies it cannot see), loop-invariant address arithmetic (hoisted out of the pass loop by the hundred, then spilled).
 #pragma once
-#include <stdlib.h>
-
 #include <algorithm>
 #include <type_traits>
 
@@ -56,28 +54,13 @@ constexpr int RO_MAXCT = RO_MAXKS / 2;
 constexpr int RO_SLOTS = 3;                     // weight ring
 constexpr int RO_AHEAD = 2;                     // chunks between a copy's issue and its first use
 constexpr int RO_MASK_WORDS = 16 * 256;         // 32-bit words of sign bits per pass and layer (16 KB; layout below)
-#ifndef TRS_RO_PF
-#define TRS_RO_PF 2      // weight fragments read ahead of the MFMAs (3: six registers more, and they are not there)
-#endif
-constexpr int RO_PF = TRS_RO_PF;
-#ifndef TRS_RO_PFB
-#define TRS_RO_PFB 2      // the same in the backward kernels
-#endif
-#ifndef TRS_RO_STAGGER
-#define TRS_RO_STAGGER 2      // groups of waves that store at different k-steps (forward; 1: 2.35 ms, 2: 2.24, 4: 2.26)
-#endif
-#ifndef TRS_RO_NREG
-#define TRS_RO_NREG 9
-#endif
+// weight fragments read ahead of the MFMAs, forward / backward kernels (3: six registers more, and they are not there)
+constexpr int RO_PF = 2;
+constexpr int RO_PFB = 2;
+constexpr int RO_STAGGER = 2;   // groups of waves that store at different k-steps (forward; 1: 2.35 ms, 2: 2.24, 4: 2.26)
 // chunks of a layer's output that wait for the next layer in registers; the ones before them wait in LDS (64 bytes per
 // chunk and row)
-__host__ __device__ constexpr int ro_nreg(bool, int) { return TRS_RO_NREG; }
-#ifndef TRS_RO_NT
-#define TRS_RO_NT 0      // cache policy of the output stores (2 = nt: measured 2x SLOWER, 5.2 vs 2.5 ms -- partial lines written through)
-#endif
-#ifndef TRS_RO_ABL
-#define TRS_RO_ABL 0      // timing experiments (wrong results): 1 no weight copies, 2 no stores, 4 no wait + barrier,
-#endif                    // 16 no fragment reads, 32 no column sums, 64 no sign bits (backward)
+constexpr int RO_NREG = 9;
 
 template <int V>
 using ro_ic = std::integral_constant<int, V>;
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
   constexpr int L = Cfg::L, NC = Cfg::NC, NB = Cfg::NB;
   constexpr int NW = 8 / RT, NT = 64 * NW;             // waves, threads
   constexpr int NQ = 2 * RT;                           // quarters (t = 2 r + h) of a chunk's 32 columns x 32 RT rows per lane
-  constexpr int NREGK = ro_nreg(BWD, RT), NLDSK = RO_MAXCT - NREGK;
+  constexpr int NREGK = RO_NREG, NLDSK = RO_MAXCT - NREGK;
   constexpr int STASH_WAVE = NLDSK * 2048 * RT;
   constexpr int SLOT = Cfg::max_ks() * 1024;          // bytes per ring slot
   constexpr unsigned RING = RO_SLOTS * SLOT;
@@ -249,7 +232,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
   auto dma_piece = [&](auto cq_, int i) __attribute__((always_inline)) {      // piece i of this wave's share of chunk cq
     constexpr int cq = decltype(cq_)::value, c2 = cq % NC, l2 = Cfg::layer_of(c2), ct2 = Cfg::ct_of(c2), P = Cfg::ks(l2);
     const int p0 = (P * wave) / NW, p1 = (P * (wave + 1)) / NW;      // the chunk's P (= its layer's KS) KB are split over the waves
-    if (!(TRS_RO_ABL & 1) && p0 + i < p1)
+    if (p0 + i < p1)
       ro_dma1(wfl[l2] + (unsigned)((ct2 * P + p0 + i) * 1024), lane16, dma_at + (p0 + i) * 1024);
   };
   constexpr int MAXP = (RO_MAXKS + NW - 1) / NW;      // pieces per wave and chunk, at most
@@ -287,8 +270,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
   // pass loop into scalar registers and spills them; as it is they are one register + an immediate offset each)
   asm volatile("" : "+v"(stash_at), "+v"(bias_at));
   auto lds_frag = [&](unsigned at, int ks) __attribute__((always_inline)) {
-    if constexpr (TRS_RO_ABL & 16) return ro_u32x4{at, (unsigned)ks, at, at};
-    else return *reinterpret_cast<const ro_u32x4*>(smem + at + ks * 1024);
+    return *reinterpret_cast<const ro_u32x4*>(smem + at + ks * 1024);
   };
   auto bias16 = [&](int col0) __attribute__((always_inline)) {      // columns col0 + 8 g + (0..7), col0 + 16 + 8 g + (0..7)
     const float* p = reinterpret_cast<const float*>(smem + bias_at) + col0;
@@ -303,7 +285,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
   ro_u32x4 afn[RO_PF];        // the next chunk's first weight fragments
   ro_f32x16 init;             // the next chunk's initial accumulators (bias): the C operand of its first MFMAs
   {
-    constexpr int PF0 = Cfg::ks(0) < (BWD ? TRS_RO_PFB : RO_PF) ? Cfg::ks(0) : (BWD ? TRS_RO_PFB : RO_PF);
+    constexpr int PF0 = Cfg::ks(0) < (BWD ? RO_PFB : RO_PF) ? Cfg::ks(0) : (BWD ? RO_PFB : RO_PF);
     ro_for<0, PF0>([&](auto i) __attribute__((always_inline)) { afn[i] = lds_frag(rd_at, i); });
     if constexpr (!BWD) init = bias16(0);
     else init = zero16;
@@ -376,7 +358,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
       const unsigned f = ro_pk_flag(w);
       mq[t] = k2 == 0 ? f : (mq[t] | (f << k2));
     }
-    if constexpr (BWD && !(TRS_RO_ABL & (64 | 128))) {      // times [forward activation > 0], two columns per instruction (all ones when the step has no mask)
+    if constexpr (BWD) {      // times [forward activation > 0], two columns per instruction (all ones when the step has no mask)
       // (mcur: see the end of the chunk body -- a word's two flags are 16 bits apart)
       const unsigned e = (mcur >> (8 * r + 4 * h + k2)) & 0x00010001u;
       w = ro_pk_mul_u16(w, e);
@@ -437,9 +419,9 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
       for (int sidx = 0; sidx < 2; ++sidx) {
         unsigned o = off[r][sidx] + 32 * pct * 2;
         if constexpr (!hidden) o = 32 * pct + 16 * ((lane >> 4) & 1) + 8 * g < ly.out_cols ? o : 0xfffffff0u;
-        if constexpr (TRS_RO_ABL & 2) o = lo[0] == 0x12345678u ? o : 0xfffffff0u;
         o = on ? o : 0xfffffff0u;      // past the end of every tensor: dropped
-        __builtin_amdgcn_raw_buffer_store_b128(sidx == 0 ? lo : hi, rs, o, 0, TRS_RO_NT);
+        // (cache policy 0: nt stores measured 2x SLOWER, 5.2 vs 2.5 ms -- partial lines written through)
+        __builtin_amdgcn_raw_buffer_store_b128(sidx == 0 ? lo : hi, rs, o, 0, 0);
       }
     }
   };
@@ -456,7 +438,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
       if constexpr (sl == 3 || pct == CTp - 1) {
         if constexpr (sl < 2) mreg[1] = 0;
         const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(a.layer[pl].mask, 0, (unsigned)(ntiles * RO_MASK_WORDS * 4), 0x00020000);
-        const unsigned o = (on && (!(TRS_RO_ABL & 2) || mw == 0x13572468u)) ? mrec + (pct >> 2) * 4096 : 0xfffffff0u;
+        const unsigned o = on ? mrec + (pct >> 2) * 4096 : 0xfffffff0u;
         typedef __attribute__((ext_vector_type(2))) unsigned ro_u32x2;
         __builtin_amdgcn_raw_buffer_store_b64(ro_u32x2{mreg[0], mreg[1]}, rm, o, 0, 0);
       }
@@ -524,7 +506,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
       constexpr int c = decltype(c_)::value;
       constexpr int l = Cfg::layer_of(c), ct = Cfg::ct_of(c), KS = Cfg::ks(l), CT = Cfg::ct(l);
       constexpr int MID = KS / 2;
-      constexpr int PFD = BWD ? TRS_RO_PFB : RO_PF;
+      constexpr int PFD = BWD ? RO_PFB : RO_PF;
       constexpr int PF = KS < PFD ? KS : PFD;
       constexpr int cn = (c + 1) % NC, ln = Cfg::layer_of(cn), ctn = Cfg::ct_of(cn), KSn = Cfg::ks(ln);
       constexpr int PFn = KSn < PFD ? KSn : PFD;
@@ -592,7 +574,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
 
       ro_for<0, KS>([&](auto ks_) __attribute__((always_inline)) {
         constexpr int ks = decltype(ks_)::value;
-        if constexpr (BWD && ks == 0 && ct == 0 && !(TRS_RO_ABL & 64)) mask_load(ro_ic<l>{}, mtile);
+        if constexpr (BWD && ks == 0 && ct == 0) mask_load(ro_ic<l>{}, mtile);
         words(ks_, ro_ic<1>{});
         if constexpr (ks + PF < KS) af[ks + PF] = lds_frag(rd_at, ks + PF);
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ro_bf16x8, af[ks]), __builtin_bit_cast(ro_bf16x8, B[0][ks]), acc[0], 0, 0, 0);
@@ -601,10 +583,8 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
           acc[RT - 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ro_bf16x8, af[ks]), __builtin_bit_cast(ro_bf16x8, B[RT - 1][ks]), acc[RT - 1], 0, 0, 0);
         if constexpr (ks == MID - 1) {
           // chunk c+1's copy (issued a chunk ago) must have landed in every wave before anybody reads it
-          if constexpr (!(TRS_RO_ABL & 4)) {
-            ro_wait_vm<0>();
-            ro_barrier();
-          }
+          ro_wait_vm<0>();
+          ro_barrier();
         }
         if constexpr (ks >= MID - 1) {
           // after the barrier: chunk c-1's slot is free -> copy chunk c+2 into it, a piece or so per k-step
@@ -614,11 +594,10 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
           for (int i = per * (ks - (MID - 1)); i < per * (ks - (MID - 1) + 1) && i < NP; ++i) dma_piece(ro_ic<c + RO_AHEAD>{}, i);      // (staggering these between the waves: no change)
         }
         if constexpr (ks >= MID) {
-#if TRS_RO_STAGGER > 1
-          // the waves do not store at the same k-step: group gq (of TRS_RO_STAGGER; the two waves of a SIMD are in different
+          // the waves do not store at the same k-step: group gq (of RO_STAGGER; the two waves of a SIMD are in different
           // groups) a share of the half chunk later, so that they are not parked on the memory path together
           // (one wave per SIMD, the backward: 2 or 4 groups measured no different from none)
-          constexpr int NG = (RT == 1 && KS - MID >= 8) ? TRS_RO_STAGGER : 1;
+          constexpr int NG = (RT == 1 && KS - MID >= 8) ? RO_STAGGER : 1;
           const int gq = NG == 1 ? 0 : (NG == 2 ? wave >> 2 : 2 * (wave >> 2) + (wave & 1));
           ro_for<0, NQ>([&](auto t_) __attribute__((always_inline)) {
             ro_for<0, NG>([&](auto g_) __attribute__((always_inline)) {
@@ -631,17 +610,9 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
               }
             });
           });
-#else
-          ro_for<0, NQ>([&](auto t_) __attribute__((always_inline)) {
-            if constexpr (store_step(decltype(t_)::value) == ks) {
-              if constexpr (c > 0) epi_store(ro_ic<pc>{}, t_, off_out[pl], mw, true);
-              else epi_store(ro_ic<pc>{}, t_, off_last_prev, mw, have_prev);
-            }
-          });
-#endif
           // backward: column sums of this step's input, a few 16-column units per chunk while the registers are not yet
           // full of the next step's input; units in ascending order (the last two arrive with chunk 0's first half)
-          if constexpr (BWD && !(TRS_RO_ABL & 32)) {
+          if constexpr (BWD) {
             constexpr int NCH = CT < 9 ? CT : 9, UPC = (KS + NCH - 1) / NCH, SU = UPC * RT;
             // piece m = i RT + r (unit j = ct UPC + i of row tile r): into LDS and back at k-step pa(m), its MFMA two
             // k-steps later (the LDS round trip), but not behind the next piece's turn
@@ -760,8 +731,8 @@ struct RoPackArgs {
 template <class Cfg, bool BWD, int IN_COLS, int RT>
 inline int ro_launch(const RoArgs& a, hipStream_t s) {
   static bool attr = false;
-  const size_t lds = (size_t)RO_SLOTS * Cfg::max_ks() * 1024 + 8 * (RO_MAXCT - ro_nreg(BWD, RT)) * 2048 + (BWD ? (8 / RT) * (1024 + 4096) : Cfg::NB * 4);
-  static_assert(RO_SLOTS * Cfg::max_ks() * 1024 + 8 * (RO_MAXCT - ro_nreg(BWD, RT)) * 2048 + (BWD ? (8 / RT) * (1024 + 4096) : Cfg::NB * 4) <= 160 * 1024, "LDS");
+  const size_t lds = (size_t)RO_SLOTS * Cfg::max_ks() * 1024 + 8 * (RO_MAXCT - RO_NREG) * 2048 + (BWD ? (8 / RT) * (1024 + 4096) : Cfg::NB * 4);
+  static_assert(RO_SLOTS * Cfg::max_ks() * 1024 + 8 * (RO_MAXCT - RO_NREG) * 2048 + (BWD ? (8 / RT) * (1024 + 4096) : Cfg::NB * 4) <= 160 * 1024, "LDS");
   if (!attr) {
     if (hipFuncSetAttribute((const void*)mlp_ro_kernel<Cfg, BWD, IN_COLS, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
         hipSuccess)
@@ -775,10 +746,7 @@ inline int ro_launch(const RoArgs& a, hipStream_t s) {
 
 // the stacks of the models: the per-field MLP of DeepAndCrossNetwork (64 -> 400 x 3 -> 64 on B*N rows) and the layers
 // behind the first one of a 400-400-400 deep branch (DeepFM / xDeepFM: 416 -> 400 -> 400 -> 8)
-#ifndef TRS_RO_BWD_RT
-#define TRS_RO_BWD_RT 2
-#endif
-constexpr int RO_BWD_RT = TRS_RO_BWD_RT;      // the backward kernels: 64 rows per wave (with 32 they do not fit 256 registers)
+constexpr int RO_BWD_RT = 2;      // the backward kernels: 64 rows per wave (with 32 they do not fit 256 registers)
 using RoDcn = RoCfg<64, 400, 400, 400, 64>;
 using RoTail = RoCfg<416, 400, 400, 8>;
 using RoTailB = RoCfg<8, 400, 400, 416>;      // the same stack walked backwards

@@ -8,15 +8,9 @@
 // no float atomics; the FM second-order backward dx = g*(S - x) is folded into the same walk:
 //   sum_p g_fm[b_p]*(S[b_p] - W[r]) = sum_p g_fm[b_p]*S[b_p]  -  W[r] * sum_p g_fm[b_p].
 // HBM-bound: reads B*N*(E*s + 4) (+ 2*B*E*s L2-resident FM operands), writes V*E*s.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "trs_common.hpp"
-
-#ifndef TRS_SCATTER_NT_LOADS
-#define TRS_SCATTER_NT_LOADS 1      // nontemporal loads of the block gradient in the bucket walks (0: plain loads)
-#endif
 
 namespace trs {
 
@@ -282,7 +276,8 @@ __global__ __launch_bounds__(256) void csr2_rowid_kernel(const IdxT* __restrict_
       const int64_t lo = csr2_clamp(offsets[n], V), hi = n + 1 < N ? csr2_clamp(offsets[n + 1], V) : V;
       if (hi > lo) items += (hi - lo + chunk - 1) / chunk;
     }
-    // need_cover (the build that does not zero the counters first): rows in front of the first field belong to no chunk
+    // need_cover (a build that does not zero the counters first; every caller passes 0): rows in front of the first
+    // field belong to no chunk
     if (items > max_items || (need_cover && offsets[0] > 0)) flags[0] = 1;
   }
   const int64_t b0 = (int64_t)blockIdx.x * CSR2_TB;
@@ -601,11 +596,7 @@ __device__ __forceinline__ void accumulate_bucket(float* acc, float* gsum, const
             const unsigned b = (unsigned)p[c] / (unsigned)N;
             row = (int64_t)b * gbs + ((unsigned)p[c] - b * (unsigned)N);
           }
-#if TRS_SCATTER_NT_LOADS
           gv[c] = load_stream(&g_rows[row * L + lane_v]);
-#else
-          gv[c] = g_rows[row * L + lane_v];
-#endif
         }
         if (HAS_FM) {
           const int64_t b = (int64_t)((unsigned)p[c] / (unsigned)N);
@@ -762,11 +753,7 @@ __global__ __launch_bounds__(256, 8) void scatter_rows_fm1_kernel(
           gs[c] = 0.f;
           if (p[c] >= 0) {
             const unsigned b = __umulhi((unsigned)p[c], rcpN);      // p / N for p < 2^31, N < 2^16 (host-checked)
-#if TRS_SCATTER_NT_LOADS
             if (HAS_G) gv[c] = load_stream(&g_rows[(unsigned)p[c] * L + lane_v]);      // read once: see load_stream
-#else
-            if (HAS_G) gv[c] = g_rows[(unsigned)p[c] * L + lane_v];
-#endif
             tv[c] = tg[b * L + lane_v];
             gs[c] = to_f32(g1[b]);
           }
@@ -1156,7 +1143,6 @@ static void scatter_group_launch(const void* g_rows, const void* g_fm, const flo
   const int L = 1 << LOG2L;
   FmSrc fs{nullptr, nullptr, 0, 0};
   bool scal = false;
-  static const int variant = getenv("TRS_SCATTER_VARIANT") ? atoi(getenv("TRS_SCATTER_VARIANT")) : 1;   // 0: the generic FM walk (A/B)
   if (g_fm != nullptr && fm_sum != nullptr) {
     if (gcols == 1) {      // (L == 1 too: a (B,1) buffer must never be read as B 16-byte rows)
       uint4* gvec = (uint4*)tg + B * L;
@@ -1164,7 +1150,7 @@ static void scatter_group_launch(const void* g_rows, const void* g_fm, const flo
                          fm_sum, (uint4*)tg, gvec, B, L);
       fs = FmSrc{(const uint4*)tg, gvec, L, 1};
       fs.g1 = g_fm;
-      scal = variant != 0 && g_first == nullptr;
+      scal = g_first == nullptr;
     } else {
       hipLaunchKernelGGL((build_tg_kernel<T>), dim3(stream_grid(B * L, 256, 4096)), dim3(256), 0, s, (const uint4*)g_fm,
                          fm_sum, (uint4*)tg, B, L);
@@ -1202,7 +1188,7 @@ static void scatter_group_launch(const void* g_rows, const void* g_fm, const flo
                        V, N, gbs, padding_row, (uint4*)grad, long_rows, sink, fs);                               \
     TRS_SC_TAIL(HG, true, true);                                                                                \
   } while (0)
-  const bool lean = scal && variant == 1 && (B * N) * (int64_t)L < ((int64_t)1 << 31) && V * (int64_t)L < ((int64_t)1 << 31) &&
+  const bool lean = scal && (B * N) * (int64_t)L < ((int64_t)1 << 31) && V * (int64_t)L < ((int64_t)1 << 31) &&
                     N >= 2 && (B * N) * (int64_t)N < ((int64_t)1 << 32) && gbs == N;   // (mulhi by ceil(2^32/N) is exact)
   if (lean) {
     const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + (unsigned)N - 1) / (unsigned)N);
@@ -1293,25 +1279,6 @@ __global__ __launch_bounds__(256) void zero2_i32_kernel(int32_t* __restrict__ p,
   }
 }
 
-// partitioned build: the LDS-counter count pass writes EVERY entry of row_start[0, V) itself, so the 4 MB zero fill of
-// the counters (54 us inside the DeepFM step, squeezed in beside the fused MLP backward) is only needed when the build
-// falls back to global atomics: a few words here (fall-back flags, the scan's status words, row_start[V]) ...
-__global__ __launch_bounds__(256) void csr_zero_small_kernel(int32_t* __restrict__ flags, int32_t* __restrict__ status,
-                                                            int nstatus, int32_t* __restrict__ last) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 64 + nstatus + 1; i += gridDim.x * blockDim.x) {
-    if (i < 64) flags[i] = 0;
-    else if (i < 64 + nstatus) status[i - 64] = 0;
-    else *last = 0;
-  }
-}
-// ... and the whole fill only behind a raised fall-back flag
-__global__ __launch_bounds__(256) void zero_gated_i32_kernel(int32_t* __restrict__ p, int64_t n,
-                                                            const int32_t* __restrict__ gate) {
-  if (*gate == 0) return;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = 0;
-}
-
 }  // namespace trs
 
 using namespace trs;
@@ -1347,8 +1314,7 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
   // partitioned (LDS-counter) build when the per-field ranges are few chunks each; otherwise global atomics
   // chunk size: enough (field, chunk) workgroups to cover the chip (each rescans its field's column of the batch,
   // so no more than ~16 per field on average), at most CSR2_CHUNK counters
-  static const int64_t target_env = getenv("TRS_CSR_TARGET") ? atoll(getenv("TRS_CSR_TARGET")) : 0;      // (tuning: workgroups aimed at)
-  const int64_t target = target_env > N ? target_env : std::max<int64_t>(256, 4 * (int64_t)N);
+  const int64_t target = std::max<int64_t>(256, 4 * (int64_t)N);      // workgroups aimed at
   int64_t chunk = (V + (target - N) - 1) / std::max<int64_t>(1, target - N);
   chunk = std::min<int64_t>(CSR2_CHUNK, std::max<int64_t>(1024, (chunk + 255) / 256 * 256));
   const int64_t max_items = (int64_t)N + (V + chunk - 1) / chunk;
@@ -1356,31 +1322,24 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
                     max_items <= 16384;
   // one-pass scan: the status words hold 30-bit sums (B*N lookups in total) and are zeroed with the counters
   const bool onepass = (n + SCAN_TILE - 1) / SCAN_TILE <= 2048 && BN < ((int64_t)1 << 30);
-  // TRS_CSR_LAZY_ZERO=1 (off by default): measured alternately on one box, DeepFM step 1.152-1.158 ms with the fill,
-  // 1.159-1.166 without (profiles/r06_logs/ab_csr_lazy_zero.txt): the fill's 54 us inside the step were time spent WAITING
-  // for wave slots beside the fused MLP backward, not work -- what replaces it on the side stream waits just the same
-  static const bool lazy_zero = getenv("TRS_CSR_LAZY_ZERO") && getenv("TRS_CSR_LAZY_ZERO")[0] == '1';
-  if (part && lazy_zero)
-    hipLaunchKernelGGL(csr_zero_small_kernel, dim3(8), dim3(256), 0, s, flags, tile_sums, onepass ? ntiles + 1 : 0,
-                       row_start + V);
-  else
-    hipLaunchKernelGGL(zero2_i32_kernel, dim3(stream_grid(n, 256, 1024)), dim3(256), 0, s, row_start, n, tile_sums,
-                       (int64_t)(onepass ? ntiles + 1 : 0));
+  // (zeroing the counters only behind a raised fall-back flag measured slower: DeepFM step 1.159-1.166 ms against
+  // 1.152-1.158 with this fill, profiles/r06_logs/ab_csr_lazy_zero.txt)
+  hipLaunchKernelGGL(zero2_i32_kernel, dim3(stream_grid(n, 256, 1024)), dim3(256), 0, s, row_start, n, tile_sums,
+                     (int64_t)(onepass ? ntiles + 1 : 0));
   const int32_t* gate = nullptr;
   if (part) {
-    if (!lazy_zero) zero_i32(flags, 64, s);
+    zero_i32(flags, 64, s);
     const int tiles = (int)((B + CSR2_TB - 1) / CSR2_TB);
     const size_t lds = (size_t)N * (CSR2_TB + 1) * 4;
     if (idx_dtype == TRS_I64)
       hipLaunchKernelGGL((csr2_rowid_kernel<int64_t>), dim3(tiles), dim3(256), lds, s, (const int64_t*)idx, offsets, B,
-                         N, V, rowT, flags, err_flag, (int)max_items, (int)chunk, lazy_zero ? 1 : 0);
+                         N, V, rowT, flags, err_flag, (int)max_items, (int)chunk, 0);
     else
       hipLaunchKernelGGL((csr2_rowid_kernel<int32_t>), dim3(tiles), dim3(256), lds, s, (const int32_t*)idx, offsets, B,
-                         N, V, rowT, flags, err_flag, (int)max_items, (int)chunk, lazy_zero ? 1 : 0);
+                         N, V, rowT, flags, err_flag, (int)max_items, (int)chunk, 0);
     hipLaunchKernelGGL((csr2_pass_kernel<false>), dim3((int)max_items), dim3(CSR2_THREADS), 0, s, rowT, offsets, B, N, V,
                        row_start, perm, flags, (int)chunk, 0);
     gate = flags;
-    if (lazy_zero) hipLaunchKernelGGL(zero_gated_i32_kernel, dim3(256), dim3(256), 0, s, row_start, n, gate);
   }
   if (BN > 0) {
     // behind the partitioned build these kernels normally exit at once: a small grid keeps them off the CUs (the
@@ -1403,12 +1362,9 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
   }
   if (part) {
     // stage for a chunk's piece of perm: what the LDS holds behind the 60 KB of counters (24 576 positions = 96 KB)
-    static const int stage_cap = [] {
-      const char* e = getenv("TRS_CSR_STAGE");
-      if (e && e[0] == '0') return 0;
-      return hipFuncSetAttribute((const void*)csr2_pass_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 CSR2_STAGE * 4) == hipSuccess ? CSR2_STAGE : 0;
-    }();
+    static const int stage_cap = hipFuncSetAttribute((const void*)csr2_pass_kernel<true>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     CSR2_STAGE * 4) == hipSuccess ? CSR2_STAGE : 0;
     hipLaunchKernelGGL((csr2_pass_kernel<true>), dim3((int)max_items), dim3(CSR2_THREADS), (size_t)stage_cap * 4, s, rowT,
                        offsets, B, N, V, row_start, perm, flags, (int)chunk, stage_cap);
   }

@@ -25,8 +25,6 @@
 // distinct bytes, the MFMAs alone 0.64 ms -- with one wave per SIMD the two overlap badly (every wait of the wave is a
 // wait of the matrix pipe), and 13 % fewer MFMAs bought 13 % of the time at 384 columns; hence the second form.
 // 416 x 64: 0.43 ms = 5.7 TB/s (0.52 ms).
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "trs_common.hpp"
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_rows_kernel(WgradArgs a
 // barrier that ends step k-1 (three later steps' pieces may still be in flight: s_waitcnt vmcnt(9 | 12)), so four steps
 // = ~100 KB per CU are under way at any time -- what the register-staged form keeps in flight with 64 VGPRs per thread.
 // Used when both operands cover whole 13-tile blocks in memory (ld >= 208 columns behind every block start) and the rows
-// are a multiple of 128; TRS_WGRAD_DMA=0 keeps the register-staged kernel.
+// are a multiple of 128; other shapes keep the register-staged kernel.
 constexpr int WD_S = 416;                 // bytes per image row (208 columns)
 constexpr int WD_IMG = WG_KS * WD_S;      // one operand block of one step
 constexpr int WD_SLOT = 2 * WD_IMG;
@@ -555,20 +553,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(WgradArgs a) {
   else run.template operator()<13, 6>();
 }
 
-static const bool WGRAD_DMA = [] {
-  const char* e = getenv("TRS_WGRAD_DMA");
-  return !(e && e[0] == '0');
-}();
-static const bool WGRAD_DMA2 = [] {
-  const char* e = getenv("TRS_WGRAD_DMA2");
-  return !(e && e[0] == '0');
-}();
-
-static const bool WGRAD_EIGHT = [] {
-  const char* e = getenv("TRS_WGRAD_EIGHT");
-  return !(e && e[0] == '0');
-}();
-
 struct WgradPlan {
   int wm, wn, mc, nc, MB, NB, slots_per_xcd;
   int dma = 0;      // 0: register-staged kernel; 1: wgrad_dma_kernel (eight waves, 13 x 13 tiles); 2: wgrad_dma2_kernel (four waves, 13 x 26)
@@ -594,11 +578,11 @@ static WgradPlan wgrad_plan(int M, int N, int64_t rows) {
     if (((Nt + p.NB - 1) / p.NB + 1) / 2 <= 5) p.nc = 5;
     // blocks of 12..14 x 12..16 tiles (416 x 416: 13 x 13): eight waves with exact shares of 7|6 x 4|3 tiles
     const int pm_lo = Mt / p.MB, pm_hi = (Mt + p.MB - 1) / p.MB, pn_lo = Nt / p.NB, pn_hi = (Nt + p.NB - 1) / p.NB;
-    if (WGRAD_EIGHT && pm_lo >= 12 && pm_hi <= 14 && pn_lo >= 12 && pn_hi <= 16) {
+    if (pm_lo >= 12 && pm_hi <= 14 && pn_lo >= 12 && pn_hi <= 16) {
       p.wn = 4;
       p.mc = 7;
       p.nc = 4;
-    } else if (WGRAD_EIGHT && pm_lo >= 12 && pm_hi <= 14 && pn_lo >= 8 && pn_hi <= 12) {
+    } else if (pm_lo >= 12 && pm_hi <= 14 && pn_lo >= 8 && pn_hi <= 12) {
       p.wn = 4;      // 2496 columns in 16 blocks of 9 | 10 tiles: shares of 3 | 2
       p.mc = 7;
       p.nc = 3;
@@ -613,9 +597,9 @@ static WgradPlan wgrad_plan(int M, int N, int64_t rows) {
     }
     return true;
   };
-  if (WGRAD_DMA && p.wm == 2 && p.wn == 4 && p.nc == 4 && rows % (4 * WG_KS) == 0 && blocks_ok(Mt, p.MB, M) &&
+  if (p.wm == 2 && p.wn == 4 && p.nc == 4 && rows % (4 * WG_KS) == 0 && blocks_ok(Mt, p.MB, M) &&
       blocks_ok(Nt, p.NB, N))
-    p.dma = (WGRAD_DMA2 && p.NB == 2 && rows >= WD2_MIN_ROWS) ? 2 : 1;
+    p.dma = (p.NB == 2 && rows >= WD2_MIN_ROWS) ? 2 : 1;
   int slots = 32 / (p.dma == 2 ? p.MB : p.MB * p.NB);
   // every row range at least 4 stages long
   const int64_t stages = (rows + WG_KR - 1) / WG_KR;
