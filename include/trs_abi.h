@@ -95,6 +95,16 @@ int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* offsets, in
                   int64_t V, int32_t* row_start, int32_t* perm, void* workspace, size_t ws_bytes,
                   int32_t* err_flag, trs_stream_t stream);
 
+/* The same index with the lookups of ONE row left out: row skip_row gets an empty bucket (row_start[skip_row + 1] ==
+ * row_start[skip_row]) and its positions do not appear in perm (the tail of perm past row_start[V] is unspecified); the
+ * flag is not raised for them.  skip_row = -1: identical to trs_csr_build.  For a padded list field (the (B, L) ids of
+ * list_indices_emb.py:124, padding_idx = 0): the walks skip the padding row anyway, while filing a third or more of all
+ * B*L positions under it is one returning atomic per position on a single counter -- measured at B*L = 3.3 M, 1 M rows:
+ * 0.22 ms without padding, 22 ms with 60 % (profiles/bag_kernels.md).                                                  */
+int trs_csr_build_skip(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N, int64_t V,
+                       int64_t skip_row, int32_t* row_start, int32_t* perm, void* workspace, size_t ws_bytes,
+                       int32_t* err_flag, trs_stream_t stream);
+
 /* ---- K1 backward: dense-gradient scatter ----------------------------------------------------
  * grad_table[r,:] = sum_{p in row r} ( g_rows[p,:]  +  g_fm[b_p,:] * (fm_sum[b_p,:] - table[r,:]) )
  * for EVERY r in [0,V) (rows without lookups are written as zeros: nn.Embedding's default
@@ -182,6 +192,36 @@ int trs_embed_fm_fields(const void* table, int64_t V, int32_t E, int32_t dtype,
                         const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,
                         void* emb, void* fm, float* fm_sum, const void* first_table, void* first_vals,
                         int32_t* err_flag, trs_stream_t stream);
+
+/* ---- bag pooling: a padded list of ids per sample, looked up in one table and pooled to one row -----------------------
+ * idx (B, L) int64/int32 RAW row ids (no offsets), table (V, E):
+ *   mode 0 (sum):  out[b,:] = sum_l table[idx[b,l], :]
+ *   mode 1 (mean): out[b,:] = (sum_l table[idx[b,l], :]) * (1/L)        every position counts, padding ids included
+ *   mode 2 (max):  out[b,e] = max_l table[idx[b,l], e];  argmax[b,e] (uint16) = the FIRST list position l that holds it
+ *                  (a later value wins only when it is greater or NaN: ATen's adaptive_max_pool rule)
+ * out (B, E) of the table's dtype; argmax (B, E) uint16, required for mode 2, ignored otherwise; 1 <= L <= 65535.
+ * fp32 accumulation, one rounding on store; the max is a selection (bit-exact).  An id outside [0, V) reads as a zero
+ * row and raises *err_flag.  The (B, L, E) block is never formed.  Rows that are a power-of-two number (<= 64) of whole
+ * 16-byte vectors take the lane-group path; any other E one thread per (b, e).
+ * replaces aten::embedding + align_to + AdaptiveAvgPool1d(1) / AdaptiveMaxPool1d(1) of
+ *   torecsys/inputs/base/list_indices_emb.py:124-152 (use_attn=False).
+ * Backward of sum / mean: trs_csr_build on the (B, L) ids (N = L) + trs_scatter_rows with g_rows = NULL, g_fm = the
+ * (B, E) output gradient (times 1/L for the mean), fm_sum = NULL, g_fm_cols = E.                                      */
+int trs_bag_pool_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                     int64_t B, int32_t L, int32_t mode, void* out, uint16_t* argmax, int32_t* err_flag,
+                     trs_stream_t stream);
+
+/* Backward of mode 2 on the row buckets of the same ids (trs_csr_build, N = L):
+ *   grad_table[r,e] = sum over the lookups p = (b,l) of row r of ( argmax[b,e] == l ? g[b,e] : 0 )
+ * for EVERY r in [0,V) (rows without lookups and padding_row are written as zeros; -1: no padding row).  g (B, E) of the
+ * table's dtype, argmax (B, E) as written by trs_bag_pool_fwd.  No atomics on values, fixed summation order; rows with
+ * more than 64 lookups are queued in `workspace` and reduced by whole waves, 256 lookups at a time.
+ * replaces the adaptive_max_pool backward + transpose + embedding_dense_backward reached from
+ *   list_indices_emb.py:124-152 through autograd.                                                                     */
+size_t trs_scatter_argmax_workspace_bytes(int64_t BN, int32_t E);
+int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, const int32_t* row_start, const int32_t* perm,
+                            int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                            void* grad_table, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
 /* ---- K2: FM layer on a materialised block -------------------------------------------------
  * fwd: fm[b,:] = 0.5*((sum_n x)^2 - sum_n x^2), fm_sum[b,:] = sum_n x (fp32, optional)

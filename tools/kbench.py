@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks (developer tool): time each C-ABI kernel at the BASELINE shape with HIP events
-on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]"""
+on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]
+--what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag)."""
 import argparse
 import os
 import sys
@@ -25,6 +26,106 @@ def timeit(fn, iters=20, warm=3):
     return ts[len(ts) // 2] * 1e-3, ts[0] * 1e-3
 
 
+def bench_bag(a):
+    """Bag pooling (csrc/bag.hip) at (B, L, E, V): forward and forward+backward of sum / mean / max, alternating in this
+    process with two baselines on the same inputs -- the reference's composition (F.embedding -> transpose -> adaptive
+    pooling; the sum has no pooling module: block.sum(1)) and torch.nn.functional.embedding_bag without padding_idx.
+    Every figure is the median of ``--rounds`` per-round medians with their min..max; the candidates take turns inside a
+    round.  Then the row-bucket build on a batch with 60 % padding against one without."""
+    import torch.nn.functional as TF
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, L, E, V = a.B, a.L, a.E, a.V
+    g = torch.Generator(device=dev).manual_seed(1234)
+
+    def bags(pad):
+        idx = torch.randint(1, V, (B, L), generator=g, device=dev)
+        if pad > 0:      # trailing padding, mean padded share = pad
+            keep = torch.rand(B, 1, generator=g, device=dev) * 2 * (1 - pad) * L
+            idx = torch.where(torch.arange(L, device=dev).view(1, L) < keep, idx, torch.zeros_like(idx))
+        return idx
+
+    idx = bags(a.pad)
+    w = torch.randn(V, E, generator=g, device=dev, dtype=dt).requires_grad_()
+    gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+    print(f"bag pooling B={B} L={L} E={E} V={V} {a.dtype} table {V * E * s / 2**30:.2f} GiB, padded share "
+          f"{float((idx == 0).float().mean()):.2f}, {a.rounds} rounds x {a.iters} launches", flush=True)
+    alg = B * L * (8 + E * s) + B * E * s
+
+    def ours(mode):
+        return lambda: F_.bag_pool(w, idx, mode, padding_idx=0)
+
+    def comp(mode):
+        def f():
+            block = TF.embedding(idx, w, padding_idx=0)
+            if mode == "sum":
+                return block.sum(1, keepdim=True)
+            pool = TF.adaptive_max_pool1d if mode == "max" else TF.adaptive_avg_pool1d
+            return pool(block.transpose(1, 2), 1).transpose(1, 2)
+        return f
+
+    def bag(mode):
+        return lambda: TF.embedding_bag(idx, w, mode=mode).unsqueeze(1)
+
+    def fwd_bwd(f):
+        def run():
+            F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+            w.grad = None
+            f().backward(gout)
+        return run
+
+    for mode in ("sum", "mean", "max"):
+        cands = [("bag_pool (HIP)", ours(mode)), ("composition (ATen)", comp(mode)), ("embedding_bag (ATen)", bag(mode))]
+        live = []
+        for name, f in cands:
+            try:
+                f().backward(gout)
+                w.grad = None
+                torch.cuda.synchronize()
+                live.append((name, f))
+            except Exception as e:      # noqa: BLE001 -- a mode / dtype this torch build does not serve
+                print(f"{mode:5s} {name:22s} not supported on this torch build ({type(e).__name__}: {str(e)[:80]}); "
+                      f"the other baseline stands alone for this case", flush=True)
+        res = {}
+        for what in ("fwd", "fwd+bwd"):
+            per = {name: [] for name, _ in live}
+            for _ in range(a.rounds):
+                for name, f in live:
+                    if what == "fwd":
+                        with torch.no_grad():
+                            per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                    else:
+                        per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+            for name, ts in per.items():
+                ts = sorted(ts)
+                res[(what, name)] = (ts[len(ts) // 2], ts[0], ts[-1])
+                extra = ""
+                if what == "fwd":
+                    extra = f"  {alg / ts[len(ts) // 2] / 8e12 * 100:5.1f}% of 8 TB/s on {alg / 1e6:.0f} MB (alg)"
+                print(f"{mode:5s} {what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                      f"{ts[-1] * 1e6:9.1f} us{extra}", flush=True)
+        w.grad = None
+    # the bucket build: does a padding-heavy batch (60 % of all positions on row 0) cost more than one without?
+    nopad, pad60 = bags(0.0), bags(0.6)
+
+    def csr(ix, skip=None):
+        def run():
+            F_.clear_caches()
+            return F_.row_buckets(ix, None, V, skip_row=skip)
+        return run
+    cases = [("no padding", csr(nopad)), ("60 % padding", csr(pad60)),
+             ("no padding, padding id skipped", csr(nopad, 0)), ("60 % padding, padding id skipped", csr(pad60, 0))]
+    per = {name: [] for name, _ in cases}
+    for _ in range(a.rounds):
+        for name, f in cases:
+            per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+    for name, ts in per.items():
+        ts = sorted(ts)
+        print(f"csr_build (B, L) {name:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us",
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -34,7 +135,13 @@ def main():
     ap.add_argument("--V", type=int, default=1_000_000)
     ap.add_argument("--zipf", action="store_true")
     ap.add_argument("--what", default="all")
+    ap.add_argument("--L", type=int, default=50, help="bag: list length")
+    ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
+    ap.add_argument("--rounds", type=int, default=5, help="bag: alternating rounds")
+    ap.add_argument("--iters", type=int, default=10, help="bag: timed launches per round")
     a = ap.parse_args()
+    if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"
+        return bench_bag(a)
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     s = 2 if dt == torch.bfloat16 else 4
     dev = torch.device("cuda:0")

@@ -79,6 +79,7 @@ SIGNATURES = {
     "trs_fa_gather_rows": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P]),
     "trs_csr_workspace_bytes": (_SZ, [_I64, _I64]),
     "trs_csr_build": (c_int32, [_P, _I32, _P, _I64, _I32, _I64, _P, _P, _P, _SZ, _P, _P]),
+    "trs_csr_build_skip": (c_int32, [_P, _I32, _P, _I64, _I32, _I64, _I64, _P, _P, _P, _SZ, _P, _P]),
     "trs_scatter_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "trs_scatter_rows": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P]),
     "trs_scatter_rows_first": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _P, _P,
@@ -92,6 +93,9 @@ SIGNATURES = {
                                                  ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ, _P]),
     "trs_embed_fm": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "trs_embed_fm_fields": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "trs_bag_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "trs_scatter_argmax_workspace_bytes": (_SZ, [_I64, _I32]),
+    "trs_scatter_rows_argmax": (c_int32, [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P]),
     "trs_fm_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_bwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_dot_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

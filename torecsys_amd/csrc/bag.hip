@@ -1,0 +1,507 @@
+// Bag pooling: a padded (B, Lb) list of ids looked up in one table and reduced to ONE row per sample (sum / mean / max),
+// and the backward of the max.  The reference's ListIndicesEmbedding (inputs/base/list_indices_emb.py:124-152) forms the
+// (B, Lb, E) block with aten::embedding, transposes it and pools it; here the block never exists.
+//
+// Forward layout, as embed_fm_group_kernel (fm.hip): a row of E values is L = E*sizeof(T)/16 sixteen-byte vectors, a GROUP of
+// L adjacent lanes owns a sample and walks its bag CH rows at a time, every lane keeping the running sum (or the running
+// maximum and the list position that holds it) of its own VE columns in registers -- no cross-lane traffic, no LDS.
+// HBM-bound: algorithmic bytes per sample = Lb * (idx bytes + E*s) read, E*s (+ 2*E for the max positions) written.
+// Rows in flight: the walk keeps VE sums (max: VE maxima + VE positions) where the FM kernel keeps two sets of VE sums and a
+// first-order term, so CH = 8 stays within 64 registers for the sums (compiler resource report) -- the
+// occupancy that made 4 beat 8 in fm.hip is not lost here.  The max walk keeps CH = 4.
+//
+// Max backward: the bucket walk of scatter.hip with the term of lookup p = (b, l) being g[b, e] where amax[b, e] == l and 0
+// elsewhere.  It reads g (B, E) and amax (B, E), never a (B, Lb, E) block; every table row is written (padding row: zeros);
+// no atomics on values, fixed summation order.  Rows with more than BAG_LONG_ROW lookups are queued and reduced by whole
+// waves in chunks of BAG_LONG_CHUNK, as scatter.hip's hot rows are.
+#include <algorithm>
+#include <cmath>
+
+#include "trs_common.hpp"
+
+namespace trs {
+
+constexpr int BAG_SUM = 0, BAG_MEAN = 1, BAG_MAX = 2;
+constexpr int BAG_LONG_ROW = 64;        // lookups a single lane group walks by itself (scatter.hip: LONG_ROW)
+constexpr int BAG_LONG_CHUNK = 256;     // lookups per queue entry of a hot row (scatter.hip: LONG_CHUNK)
+constexpr int BAG_LONG_ROW_ELEM = 32;   // the same for the one-thread-per-element path
+constexpr size_t BAG_STREAM_BYTES = (size_t)512 << 20;      // twice the Infinity Cache: the STREAM rule of fm.hip
+
+// ATen's rule (adaptive_max_pool): a later value replaces the running maximum when it is greater or NaN
+__device__ __forceinline__ bool bag_takes(float v, float m) { return v > m || v != v; }
+
+template <typename T, typename IdxT, int LOG2L, bool MAXP, int CH, bool STREAM>
+__global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __restrict__ table,
+                                                             const IdxT* __restrict__ idx, int64_t B, int Lb, int64_t V,
+                                                             float scale, uint4* __restrict__ out,
+                                                             uint16_t* __restrict__ amax, int32_t* __restrict__ err_flag) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  const int lane_v = threadIdx.x & (L - 1);
+  const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> LOG2L;
+  for (int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> LOG2L; b < B; b += groups) {
+    float s[VE];
+    int am[VE];
+#pragma unroll
+    for (int k = 0; k < VE; ++k) { s[k] = MAXP ? -INFINITY : 0.f; am[k] = 0; }
+    for (int l0 = 0; l0 < Lb; l0 += CH) {
+      int64_t r[CH];
+      uint4 v[CH];
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        r[c] = -1;
+        if (l0 + c < Lb) {
+          r[c] = (int64_t)idx[b * Lb + l0 + c];
+          if (r[c] < 0 || r[c] >= V) {      // reads as a zero row
+            if (err_flag != nullptr) *err_flag = 1;
+            r[c] = -1;
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        v[c] = make_uint4(0, 0, 0, 0);
+        if (r[c] >= 0) v[c] = STREAM ? load_stream(&table[r[c] * L + lane_v]) : table[r[c] * L + lane_v];
+      }
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        if (l0 + c < Lb) {
+          float x[VE];
+          Vec16<T>::unpack(v[c], x);
+#pragma unroll
+          for (int k = 0; k < VE; ++k) {
+            if (MAXP) {
+              if (bag_takes(x[k], s[k])) { s[k] = x[k]; am[k] = l0 + c; }
+            } else {
+              s[k] += x[k];
+            }
+          }
+        }
+      }
+    }
+    if (!MAXP) {
+#pragma unroll
+      for (int k = 0; k < VE; ++k) s[k] *= scale;
+    }
+    out[b * L + lane_v] = Vec16<T>::pack(s);
+    if (MAXP) {
+      uint32_t w[VE / 2];
+#pragma unroll
+      for (int k = 0; k < VE; k += 2) w[k / 2] = (uint32_t)am[k] | ((uint32_t)am[k + 1] << 16);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(amax + (b * L + lane_v) * VE);
+      if (VE == 8) *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[VE / 2 - 2], w[VE / 2 - 1]);
+      else *reinterpret_cast<uint2*>(dst) = make_uint2(w[0], w[1]);
+    }
+  }
+}
+
+// generic path: any E; one thread per (b, e)
+template <typename T, typename IdxT, bool MAXP>
+__global__ __launch_bounds__(256) void bag_pool_elem_kernel(const T* __restrict__ table, const IdxT* __restrict__ idx,
+                                                            int64_t B, int Lb, int E, int64_t V, float scale,
+                                                            T* __restrict__ out, uint16_t* __restrict__ amax,
+                                                            int32_t* __restrict__ err_flag) {
+  const int64_t total = B * E;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const bool f32 = total < ((int64_t)1 << 32);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t b = udiv_fast(t, E, f32);
+    const int e = (int)(t - b * E);
+    float s = MAXP ? -INFINITY : 0.f;
+    int am = 0;
+    for (int l = 0; l < Lb; ++l) {
+      const int64_t r = (int64_t)idx[b * Lb + l];
+      T raw = T{};
+      if (r < 0 || r >= V) {
+        if (err_flag != nullptr) *err_flag = 1;
+      } else {
+        raw = table[r * E + e];
+      }
+      const float x = to_f32(raw);
+      if (MAXP) {
+        if (bag_takes(x, s)) { s = x; am = l; }
+      } else {
+        s += x;
+      }
+    }
+    out[t] = from_f32<T>(MAXP ? s : s * scale);
+    if (MAXP) amax[t] = (uint16_t)am;
+  }
+}
+
+static int bag_log2_lanes(int row_bytes) {
+  if (row_bytes % 16 != 0) return -1;
+  const int L = row_bytes / 16;
+  if (!is_pow2(L) || L > 64) return -1;
+  int l = 0;
+  while ((1 << l) < L) ++l;
+  return l;
+}
+
+template <typename T, typename IdxT>
+static int bag_pool_launch(const void* table, const IdxT* idx, int64_t B, int Lb, int E, int64_t V, int mode, void* out,
+                           uint16_t* amax, int32_t* err_flag, hipStream_t s) {
+  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  const float scale = mode == BAG_MEAN ? 1.f / (float)Lb : 1.f;
+  if (lg >= 0 && aligned16(table) && aligned16(out) && aligned16(amax)) {
+    const int grid = stream_grid(B << lg, 256, 256 * 16);
+    const bool stream = (size_t)V * E * sizeof(T) > BAG_STREAM_BYTES;
+#define TRS_BAG2(LG, MX, CH_, ST)                                                                              \
+  hipLaunchKernelGGL((bag_pool_group_kernel<T, IdxT, LG, MX, CH_, ST>), dim3(grid), dim3(256), 0, s,             \
+                     (const uint4*)table, idx, B, Lb, V, scale, (uint4*)out, amax, err_flag)
+#define TRS_BAG(LG)                                      \
+  if (mode == BAG_MAX) {                                 \
+    if (stream) TRS_BAG2(LG, true, 4, true);             \
+    else TRS_BAG2(LG, true, 4, false);                   \
+  } else {                                               \
+    if (stream) TRS_BAG2(LG, false, 8, true);            \
+    else TRS_BAG2(LG, false, 8, false);                  \
+  }
+    switch (lg) {
+      case 0: TRS_BAG(0); break;
+      case 1: TRS_BAG(1); break;
+      case 2: TRS_BAG(2); break;
+      case 3: TRS_BAG(3); break;
+      case 4: TRS_BAG(4); break;
+      case 5: TRS_BAG(5); break;
+      default: TRS_BAG(6); break;
+    }
+#undef TRS_BAG
+#undef TRS_BAG2
+  } else {
+    const int grid = stream_grid(B * E, 256, 256 * 16);
+    if (mode == BAG_MAX)
+      hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, true>), dim3(grid), dim3(256), 0, s, (const T*)table, idx, B, Lb,
+                         E, V, scale, (T*)out, amax, err_flag);
+    else
+      hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, false>), dim3(grid), dim3(256), 0, s, (const T*)table, idx, B,
+                         Lb, E, V, scale, (T*)out, amax, err_flag);
+  }
+  return check_launch("bag_pool_fwd");
+}
+
+// ---------------------------------------------------------------------------------------------
+// max backward: bucket walk with the winner mask
+
+// the lookups q = beg, beg + step, ... < end of one bucket, CH in flight per lane: acc[k] += g[b, k] where amax[b, k] == l
+template <typename T, int LOG2L, int CH>
+__device__ __forceinline__ void bag_argmax_bucket(float* acc, const uint4* __restrict__ g,
+                                                  const uint16_t* __restrict__ amax, const int32_t* __restrict__ perm,
+                                                  int beg, int end, int step, unsigned N, int lane_v) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  for (int q = beg; q < end; q += CH * step) {
+    int p[CH];
+    uint4 gv[CH], av[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) p[c] = (q + c * step) < end ? perm[q + c * step] : -1;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      gv[c] = make_uint4(0, 0, 0, 0);
+      av[c] = make_uint4(0, 0, 0, 0);
+      if (p[c] >= 0) {
+        const int64_t b = (int64_t)((unsigned)p[c] / N);
+        gv[c] = g[b * L + lane_v];
+        const uint16_t* ap = amax + (b * L + lane_v) * VE;
+        if (VE == 8) {
+          av[c] = *reinterpret_cast<const uint4*>(ap);
+        } else {
+          const uint2 a2 = *reinterpret_cast<const uint2*>(ap);
+          av[c] = make_uint4(a2.x, a2.y, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      if (p[c] >= 0) {
+        const unsigned b = (unsigned)p[c] / N;
+        const unsigned l = (unsigned)p[c] - b * N;
+        float x[VE];
+        Vec16<T>::unpack(gv[c], x);
+        const uint32_t w[4] = {av[c].x, av[c].y, av[c].z, av[c].w};
+#pragma unroll
+        for (int k = 0; k < VE; ++k) {
+          const unsigned a = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
+          acc[k] += a == l ? x[k] : 0.f;
+        }
+      }
+    }
+  }
+}
+
+template <typename T, int LOG2L>
+__global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __restrict__ g,
+                                                              const uint16_t* __restrict__ amax,
+                                                              const int32_t* __restrict__ row_start,
+                                                              const int32_t* __restrict__ perm, int64_t V, unsigned N,
+                                                              int64_t padding_row, uint4* __restrict__ grad,
+                                                              int32_t* __restrict__ long_rows /* [0] = count */) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  const int lane_v = threadIdx.x & (L - 1);
+  const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> LOG2L;
+  for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> LOG2L; r < V; r += groups) {
+    const int beg = row_start[r], end = row_start[r + 1];
+    float acc[VE];
+#pragma unroll
+    for (int k = 0; k < VE; ++k) acc[k] = 0.f;
+    if (r != padding_row) {
+      if (end - beg > BAG_LONG_ROW) {
+        if (lane_v == 0) {
+          const int nch = (end - beg + BAG_LONG_CHUNK - 1) / BAG_LONG_CHUNK;
+          const int slot = atomicAdd(&long_rows[0], nch);      // the chunks of a row are adjacent in the queue
+          for (int c = 0; c < nch; ++c) {
+            long_rows[1 + 2 * (slot + c)] = (int32_t)r;
+            long_rows[2 + 2 * (slot + c)] = c;
+          }
+        }
+        continue;
+      }
+      bag_argmax_bucket<T, LOG2L, 4>(acc, g, amax, perm, beg, end, 1, N, lane_v);
+    }
+    store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
+  }
+}
+
+// hot rows: one wave per (row, chunk) entry, its 64 / L lane groups stride the chunk, partial sums folded by shuffles.
+// Rows of a single chunk are finished here; otherwise the partial goes to scratch[entry][E] (fp32) for the finish kernel.
+template <typename T, int LOG2L>
+__global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __restrict__ g,
+                                                              const uint16_t* __restrict__ amax,
+                                                              const int32_t* __restrict__ row_start,
+                                                              const int32_t* __restrict__ perm, unsigned N,
+                                                              uint4* __restrict__ grad,
+                                                              const int32_t* __restrict__ long_rows,
+                                                              float* __restrict__ scratch) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  constexpr int G = 64 / L;
+  const int lane = threadIdx.x & 63;
+  const int lane_v = lane & (L - 1);
+  const int grp = lane >> LOG2L;
+  const int nlong = long_rows[0];
+  const int waves = gridDim.x * (blockDim.x >> 6);
+  for (int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < nlong; i += waves) {
+    const int64_t r = long_rows[1 + 2 * i];
+    const int c = long_rows[2 + 2 * i];
+    const int rbeg = row_start[r], rend = row_start[r + 1];
+    const int beg = rbeg + c * BAG_LONG_CHUNK, end = rend < beg + BAG_LONG_CHUNK ? rend : beg + BAG_LONG_CHUNK;
+    float acc[VE];
+#pragma unroll
+    for (int k = 0; k < VE; ++k) acc[k] = 0.f;
+    bag_argmax_bucket<T, LOG2L, 4>(acc, g, amax, perm, beg + grp, end, G, N, lane_v);
+#pragma unroll
+    for (int m = L; m < 64; m <<= 1) {
+#pragma unroll
+      for (int k = 0; k < VE; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
+    }
+    if (grp == 0) {
+      if (rend - rbeg <= BAG_LONG_CHUNK) {
+        store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
+      } else {
+        float* sa = scratch + (size_t)i * (L * VE) + lane_v * VE;
+#pragma unroll
+        for (int k = 0; k < VE; ++k) sa[k] = acc[k];
+      }
+    }
+  }
+}
+
+// rows of several chunks: the first chunk's entry adds the row's partials in chunk order
+template <typename T, int LOG2L>
+__global__ __launch_bounds__(256) void bag_argmax_finish_kernel(const int32_t* __restrict__ row_start,
+                                                                uint4* __restrict__ grad,
+                                                                const int32_t* __restrict__ long_rows,
+                                                                const float* __restrict__ scratch) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  const int lane_v = threadIdx.x & (L - 1);
+  const int nlong = long_rows[0];
+  const int groups = (gridDim.x * blockDim.x) >> LOG2L;
+  for (int i = (blockIdx.x * blockDim.x + threadIdx.x) >> LOG2L; i < nlong; i += groups) {
+    if (long_rows[2 + 2 * i] != 0) continue;
+    const int64_t r = long_rows[1 + 2 * i];
+    const int len = row_start[r + 1] - row_start[r];
+    if (len <= BAG_LONG_CHUNK) continue;
+    const int nch = (len + BAG_LONG_CHUNK - 1) / BAG_LONG_CHUNK;
+    float acc[VE];
+#pragma unroll
+    for (int k = 0; k < VE; ++k) acc[k] = 0.f;
+    for (int c = 0; c < nch; ++c) {
+      const float* sa = scratch + (size_t)(i + c) * (L * VE) + lane_v * VE;
+#pragma unroll
+      for (int k = 0; k < VE; ++k) acc[k] += sa[k];
+    }
+    store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
+  }
+}
+
+// generic path (any E): one thread per (row, e); rows with more than BAG_LONG_ROW_ELEM lookups are queued (one id each)
+// and reduced by one wave per row
+template <typename T>
+__device__ __forceinline__ float bag_argmax_term(const T* __restrict__ g, const uint16_t* __restrict__ amax, int p,
+                                                 unsigned N, int E, int e) {
+  const unsigned b = (unsigned)p / N;
+  const unsigned l = (unsigned)p - b * N;
+  const int64_t o = (int64_t)b * E + e;
+  return (unsigned)amax[o] == l ? to_f32(g[o]) : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __restrict__ g,
+                                                                   const uint16_t* __restrict__ amax,
+                                                                   const int32_t* __restrict__ row_start,
+                                                                   const int32_t* __restrict__ perm, int64_t V, int E,
+                                                                   unsigned N, int64_t padding_row, T* __restrict__ grad,
+                                                                   int32_t* __restrict__ long_rows) {
+  const int64_t total = V * E;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const bool f32 = total < ((int64_t)1 << 32);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t r = udiv_fast(t, E, f32);
+    const int e = (int)(t - r * E);
+    float acc = 0.f;
+    if (r != padding_row) {
+      const int beg = row_start[r], end = row_start[r + 1];
+      if (end - beg > BAG_LONG_ROW_ELEM) {
+        if (e == 0) long_rows[1 + atomicAdd(&long_rows[0], 1)] = (int32_t)r;
+        continue;
+      }
+      for (int q = beg; q < end; ++q) acc += bag_argmax_term<T>(g, amax, perm[q], N, E, e);
+    }
+    grad[t] = from_f32<T>(acc);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __restrict__ g,
+                                                                   const uint16_t* __restrict__ amax,
+                                                                   const int32_t* __restrict__ row_start,
+                                                                   const int32_t* __restrict__ perm, int E, unsigned N,
+                                                                   T* __restrict__ grad,
+                                                                   const int32_t* __restrict__ long_rows) {
+  const int nlong = long_rows[0];
+  const int lane = threadIdx.x & 63;
+  const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (int i = wid; i < nlong; i += nwaves) {
+    const int64_t r = long_rows[1 + i];
+    const int beg = row_start[r], end = row_start[r + 1];
+    for (int e = 0; e < E; ++e) {
+      float acc = 0.f;
+      constexpr int U = 4;
+      for (int q = beg + lane; q < end; q += 64 * U) {
+        int pp[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) pp[u] = (q + 64 * u) < end ? perm[q + 64 * u] : -1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (pp[u] >= 0) acc += bag_argmax_term<T>(g, amax, pp[u], N, E, e);
+      }
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+      if (lane == 0) grad[r * E + e] = from_f32<T>(acc);
+    }
+  }
+}
+
+__global__ void bag_zero_counter_kernel(int32_t* __restrict__ p) {
+  if (threadIdx.x == 0) *p = 0;
+}
+
+static size_t bag_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// queue entries: a row is queued with more than 32 (element path; one id) or 64 lookups (one (row, chunk) pair per chunk)
+static size_t bag_queue_entries(int64_t BN) { return (size_t)(BN / BAG_LONG_ROW + BN / BAG_LONG_CHUNK + 2); }
+static size_t bag_queue_bytes(int64_t BN) {
+  return bag_align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
+}
+
+template <typename T>
+static int bag_argmax_launch(const void* g, const uint16_t* amax, const int32_t* row_start, const int32_t* perm,
+                             int64_t V, int E, int N, int64_t padding_row, void* grad, int32_t* long_rows,
+                             float* scratch, hipStream_t s) {
+  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  hipLaunchKernelGGL(bag_zero_counter_kernel, dim3(1), dim3(64), 0, s, long_rows);
+  if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(grad)) {
+    const int grid = stream_grid(V << lg, 256, 256 * 32);
+#define TRS_BAGB(LG)                                                                                                  \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, row_start, \
+                       perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);                                    \
+    hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, row_start, \
+                       perm, (unsigned)N, (uint4*)grad, long_rows, scratch);                                           \
+    hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,          \
+                       long_rows, scratch);                                                                            \
+  } while (0)
+    switch (lg) {
+      case 0: TRS_BAGB(0); break;
+      case 1: TRS_BAGB(1); break;
+      case 2: TRS_BAGB(2); break;
+      case 3: TRS_BAGB(3); break;
+      case 4: TRS_BAGB(4); break;
+      case 5: TRS_BAGB(5); break;
+      default: TRS_BAGB(6); break;
+    }
+#undef TRS_BAGB
+  } else {
+    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
+                       (const T*)g, amax, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows);
+    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, row_start,
+                       perm, E, (unsigned)N, (T*)grad, long_rows);
+  }
+  return check_launch("scatter_rows_argmax");
+}
+
+}  // namespace trs
+
+using namespace trs;
+
+extern "C" int trs_bag_pool_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx,
+                                int32_t idx_dtype, int64_t B, int32_t L, int32_t mode, void* out, uint16_t* argmax,
+                                int32_t* err_flag, trs_stream_t stream) {
+  if (B == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
+  TRS_REQUIRE(table && idx && out, TRS_EINVAL, "bag_pool_fwd: NULL pointer");
+  TRS_REQUIRE(mode == BAG_SUM || mode == BAG_MEAN || mode == BAG_MAX, TRS_EINVAL,
+              "bag_pool_fwd: mode %d (0 = sum, 1 = mean, 2 = max)", mode);
+  TRS_REQUIRE(mode != BAG_MAX || argmax != nullptr, TRS_EINVAL, "bag_pool_fwd: max pooling needs the argmax output");
+  TRS_REQUIRE(V > 0 && E > 0 && B >= 0, TRS_EINVAL, "bag_pool_fwd: bad size V=%lld E=%d B=%lld", (long long)V, E,
+              (long long)B);
+  TRS_REQUIRE(L >= 1 && L <= 65535, TRS_EINVAL, "bag_pool_fwd: list length L=%d outside [1, 65535]", L);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "bag_pool_fwd: dtype %d", dtype);
+  TRS_REQUIRE(idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EDTYPE, "bag_pool_fwd: idx dtype %d", idx_dtype);
+  hipStream_t s = (hipStream_t)stream;
+#define TRS_CALL(T, I) return bag_pool_launch<T, I>(table, (const I*)idx, B, L, E, V, mode, out, argmax, err_flag, s)
+  if (dtype == TRS_F32) {
+    if (idx_dtype == TRS_I64) TRS_CALL(float, int64_t);
+    TRS_CALL(float, int32_t);
+  }
+  if (idx_dtype == TRS_I64) TRS_CALL(bf16_t, int64_t);
+  TRS_CALL(bf16_t, int32_t);
+#undef TRS_CALL
+}
+
+extern "C" size_t trs_scatter_argmax_workspace_bytes(int64_t BN, int32_t E) {
+  // [queue of hot rows + its counter][chunk partials of the rows of several chunks: entries x E fp32]
+  if (BN < 0 || E < 0) return 0;
+  return bag_queue_bytes(BN) + bag_align_up(bag_queue_entries(BN) * (size_t)E * 4, 256);
+}
+
+extern "C" int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, const int32_t* row_start,
+                                       const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                                       int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
+                                       trs_stream_t stream) {
+  TRS_REQUIRE(g && argmax && row_start && perm && grad_table && workspace, TRS_EINVAL,
+              "scatter_rows_argmax: NULL pointer");
+  TRS_REQUIRE(V > 0 && E > 0 && BN >= 0, TRS_EINVAL, "scatter_rows_argmax: bad size");
+  TRS_REQUIRE(N >= 1 && N <= 65535, TRS_EINVAL, "scatter_rows_argmax: list length L=%d outside [1, 65535]", N);
+  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "scatter_rows_argmax: B*L=%lld not a multiple of L=%d", (long long)BN, N);
+  TRS_REQUIRE(BN < (int64_t)0x7fffffff, TRS_ESHAPE, "scatter_rows_argmax: B*L=%lld must fit int32", (long long)BN);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_argmax: dtype %d", dtype);
+  TRS_REQUIRE(ws_bytes >= trs_scatter_argmax_workspace_bytes(BN, E), TRS_EWORKSPACE,
+              "scatter_rows_argmax: workspace %zu < %zu", ws_bytes, trs_scatter_argmax_workspace_bytes(BN, E));
+  int32_t* long_rows = (int32_t*)workspace;
+  float* scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TRS_F32)
+    return bag_argmax_launch<float>(g, argmax, row_start, perm, V, E, N, padding_row, grad_table, long_rows, scratch, s);
+  return bag_argmax_launch<bf16_t>(g, argmax, row_start, perm, V, E, N, padding_row, grad_table, long_rows, scratch, s);
+}

@@ -35,12 +35,14 @@ constexpr int LONG_CHUNK = 256;
 constexpr int ELEM_SPLIT = 2048;
 
 // 4 independent lookups per thread per iteration: 4 index loads, then 4 returning atomics in flight
-template <typename IdxT>
+// SKIP (trs_csr_build_skip): the lookups of skip_row are left out of the index like out-of-range ones, without raising
+// the flag -- the padding id of a list field, whose millions of returning atomics on ONE counter serialise the build
+template <typename IdxT, bool SKIP = false>
 __global__ __launch_bounds__(256) void csr_count_kernel(const IdxT* __restrict__ idx,
                                                         const int64_t* __restrict__ offsets, int64_t BN, int N,
                                                         int64_t V, int32_t* __restrict__ count,
                                                         int32_t* __restrict__ slot, int32_t* __restrict__ err_flag,
-                                                        const int32_t* __restrict__ gate) {
+                                                        const int32_t* __restrict__ gate, int64_t skip_row = -1) {
   constexpr int U = 4;
   if (gate != nullptr && *gate == 0) return;      // the partitioned build (below) handles this batch
   const unsigned n_items = (unsigned)BN, uN = (unsigned)N;
@@ -57,6 +59,7 @@ __global__ __launch_bounds__(256) void csr_count_kernel(const IdxT* __restrict__
           if (err_flag != nullptr) *err_flag = 1;
           r[u] = -1;
         }
+        if (SKIP && r[u] == skip_row) r[u] = -1;
       }
     }
     int sl[U];
@@ -1289,9 +1292,9 @@ extern "C" size_t trs_csr_workspace_bytes(int64_t V, int64_t BN) {
   return 2 * align_up((size_t)BN * 4, 256) + align_up((ntiles + 1) * 4, 256) + 512;   // + the scan's ticket word
 }
 
-extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,
-                             int64_t V, int32_t* row_start, int32_t* perm, void* workspace, size_t ws_bytes,
-                             int32_t* err_flag, trs_stream_t stream) {
+static int csr_build_impl(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,
+                          int64_t V, int32_t* row_start, int32_t* perm, void* workspace, size_t ws_bytes,
+                          int32_t* err_flag, trs_stream_t stream, int64_t skip_row) {
   TRS_REQUIRE(row_start && workspace && (B == 0 || (idx && perm)), TRS_EINVAL, "csr_build: NULL pointer");
   TRS_REQUIRE(V > 0 && B >= 0 && N > 0, TRS_EINVAL, "csr_build: bad size");
   TRS_REQUIRE(idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EDTYPE, "csr_build: idx dtype %d", idx_dtype);
@@ -1319,7 +1322,7 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
   chunk = std::min<int64_t>(CSR2_CHUNK, std::max<int64_t>(1024, (chunk + 255) / 256 * 256));
   const int64_t max_items = (int64_t)N + (V + chunk - 1) / chunk;
   const bool part = offsets != nullptr && N <= CSR2_MAX_FIELDS && B >= 2048 && max_items <= 16 * (int64_t)N + 256 &&
-                    max_items <= 16384;
+                    max_items <= 16384 && skip_row < 0;
   // one-pass scan: the status words hold 30-bit sums (B*N lookups in total) and are zeroed with the counters
   const bool onepass = (n + SCAN_TILE - 1) / SCAN_TILE <= 2048 && BN < ((int64_t)1 << 30);
   // (zeroing the counters only behind a raised fall-back flag measured slower: DeepFM step 1.159-1.166 ms against
@@ -1345,12 +1348,19 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
     // behind the partitioned build these kernels normally exit at once: a small grid keeps them off the CUs (the
     // grid-stride loops still cover every lookup when the fall-back flag is set)
     const int grid = part ? 256 : stream_grid(BN, 256, 256 * 16);
-    if (idx_dtype == TRS_I64)
+    if (skip_row >= 0) {
+      if (idx_dtype == TRS_I64)
+        hipLaunchKernelGGL((csr_count_kernel<int64_t, true>), dim3(grid), dim3(256), 0, s, (const int64_t*)idx, offsets,
+                           BN, N, V, row_start, slot, err_flag, gate, skip_row);
+      else
+        hipLaunchKernelGGL((csr_count_kernel<int32_t, true>), dim3(grid), dim3(256), 0, s, (const int32_t*)idx, offsets,
+                           BN, N, V, row_start, slot, err_flag, gate, skip_row);
+    } else if (idx_dtype == TRS_I64)
       hipLaunchKernelGGL((csr_count_kernel<int64_t>), dim3(grid), dim3(256), 0, s, (const int64_t*)idx, offsets, BN, N,
-                         V, row_start, slot, err_flag, gate);
+                         V, row_start, slot, err_flag, gate, (int64_t)-1);
     else
       hipLaunchKernelGGL((csr_count_kernel<int32_t>), dim3(grid), dim3(256), 0, s, (const int32_t*)idx, offsets, BN, N,
-                         V, row_start, slot, err_flag, gate);
+                         V, row_start, slot, err_flag, gate, (int64_t)-1);
   }
   if (onepass) {             // every tile's workgroup resident at once: one pass
     hipLaunchKernelGGL(scan_onepass_kernel, dim3(ntiles), dim3(SCAN_THREADS), 0, s, row_start, n, (unsigned*)tile_sums,
@@ -1380,6 +1390,22 @@ extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* 
                          row_start, slot, perm, gate);
   }
   return check_launch("csr_build");
+}
+
+extern "C" int trs_csr_build(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,
+                             int64_t V, int32_t* row_start, int32_t* perm, void* workspace, size_t ws_bytes,
+                             int32_t* err_flag, trs_stream_t stream) {
+  return csr_build_impl(idx, idx_dtype, offsets, B, N, V, row_start, perm, workspace, ws_bytes, err_flag, stream, -1);
+}
+
+/* see include/trs_abi.h: the same index with the lookups of one row (a list field's padding id) left out */
+extern "C" int trs_csr_build_skip(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,
+                                  int64_t V, int64_t skip_row, int32_t* row_start, int32_t* perm, void* workspace,
+                                  size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  TRS_REQUIRE(skip_row >= -1 && skip_row < V, TRS_EINVAL, "csr_build_skip: skip_row %lld outside [-1, V)",
+              (long long)skip_row);
+  return csr_build_impl(idx, idx_dtype, offsets, B, N, V, row_start, perm, workspace, ws_bytes, err_flag, stream,
+                        skip_row);
 }
 
 static size_t long_row_entries(int64_t BN) { return (size_t)(BN / LONG_ROW + BN / LONG_CHUNK + 2); }

@@ -165,15 +165,16 @@ def _offsets_key(offsets):
     return v
 
 
-def _bucket_key(idx, offsets, V, check=True):
+def _bucket_key(idx, offsets, V, check=True, skip_row=None):
     # ``check`` is part of the key: a build that skipped out-of-range ids silently (fixed-capacity padding) must not be
     # handed to a caller that expects the index flag to have been raised for them, nor the other way round
-    return (idx.data_ptr(), idx._version, tuple(idx.shape), idx.dtype, _offsets_key(offsets), V, bool(check))
+    return (idx.data_ptr(), idx._version, tuple(idx.shape), idx.dtype, _offsets_key(offsets), V, bool(check), skip_row)
 
 
-def _build_buckets(idx, offsets, V, check: bool = True) -> RowBuckets:
+def _build_buckets(idx, offsets, V, check: bool = True, skip_row: Optional[int] = None) -> RowBuckets:
     """``check=False``: ids outside [0, V) are skipped WITHOUT raising the index flag (the padding slots of a
-    fixed-capacity exchange carry -1; real ids were range-checked when they were looked up)."""
+    fixed-capacity exchange carry -1; real ids were range-checked when they were looked up).  ``skip_row``: the lookups
+    of that row are left out of the index (trs_csr_build_skip: the padding id of a list field, which no walk reads)."""
     B, N = idx.shape
     BN = B * N
     dev = idx.device
@@ -182,23 +183,28 @@ def _build_buckets(idx, offsets, V, check: bool = True) -> RowBuckets:
     ws_bytes = size_query("trs_csr_workspace_bytes", V, BN)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     flag = _ErrFlag(dev) if check else None
-    call("trs_csr_build", ptr(idx), index_dtype_code(idx), ptr(offsets), B, N, V, ptr(row_start), ptr(perm),
-         ptr(ws), ws_bytes, ptr(flag.t if check else None), stream_ptr())
+    if skip_row is None:
+        call("trs_csr_build", ptr(idx), index_dtype_code(idx), ptr(offsets), B, N, V, ptr(row_start), ptr(perm),
+             ptr(ws), ws_bytes, ptr(flag.t if check else None), stream_ptr())
+    else:
+        call("trs_csr_build_skip", ptr(idx), index_dtype_code(idx), ptr(offsets), B, N, V, int(skip_row), ptr(row_start),
+             ptr(perm), ptr(ws), ws_bytes, ptr(flag.t if check else None), stream_ptr())
     if check:
         flag.check("row_buckets")
     return RowBuckets(row_start, perm, V, BN, N)
 
 
-def row_buckets(idx: torch.Tensor, offsets: Optional[torch.Tensor], V: int, check: bool = True) -> RowBuckets:
+def row_buckets(idx: torch.Tensor, offsets: Optional[torch.Tensor], V: int, check: bool = True,
+                skip_row: Optional[int] = None) -> RowBuckets:
     """Build (or fetch) the CSR for ``idx`` (B,N).  The cache keeps a reference to the index tensor,
     so its storage cannot be recycled for another batch while the entry is live; in-place edits bump
     ``_version`` and miss."""
-    key = _bucket_key(idx, offsets, V, check)
+    key = _bucket_key(idx, offsets, V, check, skip_row)
     for k, _, rb in _bucket_cache:
         if k == key:
             rb.wait()
             return rb
-    rb = _build_buckets(idx, offsets, V, check)
+    rb = _build_buckets(idx, offsets, V, check, skip_row)
     # an inline build is shared like a prefetched one (two tables looked up with the same indices, possibly on two
     # streams): it carries its event and stream too
     rb.built_on(_abi.current_stream_of(idx.device))
@@ -226,22 +232,22 @@ class defer_prefetch:
         if _defer_depth[0] == 0:
             reqs = list(_pending_prefetch)
             _pending_prefetch.clear()
-            for idx, offsets, V, check in reqs:
-                prefetch_row_buckets(idx, offsets, V, check)
+            for idx, offsets, V, check, skip_row in reqs:
+                prefetch_row_buckets(idx, offsets, V, check, skip_row=skip_row)
         return False
 
 
 def prefetch_row_buckets(idx: torch.Tensor, offsets: Optional[torch.Tensor], V: int, check: bool = True,
-                         now: bool = False) -> None:
+                         now: bool = False, skip_row: Optional[int] = None) -> None:
     """Start building the CSR of this batch on a side stream at FORWARD time: it depends only on the
     indices, is latency-bound (int32 atomics), and hides behind the forward/backward of the dense part
     of the model; the backward's scatter then just waits on an event."""
     if not PREFETCH_BUCKETS:
         return
     if _defer_depth[0] > 0 and not now:
-        _pending_prefetch.append((idx, offsets, V, check))
+        _pending_prefetch.append((idx, offsets, V, check, skip_row))
         return
-    key = _bucket_key(idx, offsets, V, check)
+    key = _bucket_key(idx, offsets, V, check, skip_row)
     for k, _, _rb in _bucket_cache:
         if k == key:
             return
@@ -251,7 +257,7 @@ def prefetch_row_buckets(idx: torch.Tensor, offsets: Optional[torch.Tensor], V: 
     side.wait_stream(main)
     torch.cuda.set_stream(side)          # not `with torch.cuda.stream(side)`: its constructor and __enter__ each resolve
     try:                                 # the current device through hipGetDeviceCount (~0.1 ms apiece)
-        rb = _build_buckets(idx, offsets, V, check)
+        rb = _build_buckets(idx, offsets, V, check, skip_row)
         rb.built_on(side)
     finally:
         torch.cuda.set_stream(main)
@@ -474,6 +480,87 @@ def gather_rows(weight: torch.Tensor, idx: torch.Tensor, offsets: Optional[torch
     if padding_idx is not None and padding_idx < 0:
         padding_idx = weight.shape[0] + padding_idx
     return _GatherRows.apply(weight, idx, offsets, padding_idx, opt)
+
+
+# --------------------------------------------------------------------------------------------
+# bag pooling: (B, L) list of ids -> one pooled row per sample
+# --------------------------------------------------------------------------------------------
+BAG_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+class _BagPool(Function):
+    @staticmethod
+    def forward(ctx, weight, idx, mode, padding_idx, opt=None):
+        require_device(weight, idx)
+        B, L = idx.shape
+        V, E = weight.shape
+        w = weight.contiguous()
+        out = torch.empty(B, E, dtype=w.dtype, device=w.device)
+        # the winning list positions, uint16 bit patterns (L <= 65535) in an int16 tensor
+        amax = torch.empty(B, E, dtype=torch.int16, device=w.device) if mode == 2 else None
+        flag = _ErrFlag(w.device)
+        call("trs_bag_pool_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, mode,
+             ptr(out), ptr(amax), ptr(flag.t), stream_ptr())
+        flag.check("bag_pool")
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        # the padding id is left out of the row buckets: no walk reads that bucket, and filing a third or more of all
+        # B*L positions under one row serialises the build (22 ms against 0.2 ms, profiles/bag_kernels.md)
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        if ctx.needs_input_grad[0]:
+            prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
+            if amax is None:
+                ctx.save_for_backward(idx, weight)
+            else:
+                ctx.save_for_backward(idx, weight, amax)
+        ctx.mode = mode
+        ctx.opt = opt
+        return out.unsqueeze(1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        idx, weight = ctx.saved_tensors[:2]
+        _adopt_grads(g)
+        V, E = weight.shape
+        L = idx.shape[1]
+        rb = row_buckets(idx, None, V, skip_row=ctx.skip)
+        g2 = g.reshape(g.shape[0], E)
+        if ctx.mode == 2:
+            amax = ctx.saved_tensors[2]
+            g2 = g2.contiguous()
+            grad = torch.empty(V, E, dtype=weight.dtype, device=weight.device)
+            ws_bytes = size_query("trs_scatter_argmax_workspace_bytes", rb.BN, E)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
+            call("trs_scatter_rows_argmax", ptr(g2), ptr(amax), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, L,
+                 value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+            return grad, None, None, None, None
+        # sum / mean: the per-sample gradient broadcast over the L positions (mean: times 1/L first, on (B,E))
+        g2 = g2 * (1.0 / L) if ctx.mode == 1 else g2.contiguous()
+        grad = _apply_or_grad(rb, weight, ctx.opt, g_bcast=g2, padding_row=ctx.padding_idx)
+        return grad, None, None, None, None
+
+
+def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", padding_idx: Optional[int] = None,
+             opt=None) -> torch.Tensor:
+    """(B,1,E) pooled rows of a padded (B,L) list of ids: ``sum`` / ``mean`` (= sum / L: every position counts, the
+    padding row is read like any other, as F.embedding does) / ``max`` (first position wins a tie) in one pass over the
+    looked-up rows -- the (B,L,E) block of list_indices_emb.py:124-152 is never formed.  ``padding_idx``: the table row
+    that receives no gradient.  ``opt``: fused sparse optimizer (sum / mean only)."""
+    if mode not in BAG_MODES:
+        raise ValueError(f'bag_pool: mode must be one of {sorted(BAG_MODES)}, got {mode!r}')
+    idx = _as_index(idx)
+    if idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError(f"indices must be (B, L) with L >= 1, got shape {tuple(idx.shape)}")
+    if idx.shape[1] > 65535:
+        raise ValueError(f"bag_pool: list length {idx.shape[1]} exceeds 65535")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
+    if opt is not None and mode == "max":
+        raise NotImplementedError("torecsys_amd: max pooling with a fused sparse optimizer is not implemented "
+                                  "(use sum / mean pooling, or a dense optimizer)")
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = weight.shape[0] + padding_idx
+    return _BagPool.apply(weight, idx, BAG_MODES[mode], padding_idx, opt)
 
 
 # --------------------------------------------------------------------------------------------

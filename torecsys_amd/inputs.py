@@ -173,6 +173,91 @@ class MultiIndicesFieldAwareEmbedding(BaseInput):
         return out
 
 
+def _no_attention(query, key, value):
+    return query, None
+
+
+class ListIndicesEmbedding(BaseInput):
+    """list_indices_emb.py:12-161: a padded (B,L) list of ids -> one table -> one pooled row per sample, (B,1,E) named
+    ('B','N','E') (``output_method='none'``: the plain (B,L,E) lookup).  Same constructor, defaults (``padding_idx=0``),
+    attributes and ``state_dict`` keys as the reference.
+
+    ``avg_pooling`` / ``max_pooling`` run as one HIP pass over the looked-up rows (``functional.bag_pool``): the
+    (B,L,E) block of the reference is never formed, forward or backward.  Every list position counts, padding included
+    (the padding row is read like any other row, as the reference does).
+
+    Deliberate difference: ``output_method='mean'`` and ``'sum'`` RAISE in the reference (it strips the tensor names and
+    then reduces over ``dim='N'``); here they do what its docstring promises -- ``mean`` equals ``avg_pooling``, ``sum``
+    is the unscaled sum, both (B,1,E).
+
+    ``use_attn=True``: the HIP gather produces (B,L,E), the module's own ``nn.MultiheadAttention`` (ATen) runs on
+    (L,B,E) and the pooling runs in ATen too -- same parameters and keys as the reference; not a hot path, no kernel of
+    its own.  ``show_attention`` (a plotting helper) is not provided."""
+
+    _POOL = {'avg_pooling': 'mean', 'max_pooling': 'max', 'mean': 'mean', 'sum': 'sum'}
+
+    def __init__(self, embed_size: Optional[int] = None, field_size: Optional[int] = None,
+                 padding_idx: Optional[int] = 0, nn_embedding: Optional[nn.Parameter] = None,
+                 use_attn: Optional[bool] = False, output_method: Optional[str] = 'avg_pooling', **kwargs):
+        super().__init__()
+        if nn_embedding is not None:
+            self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
+        elif field_size is not None and embed_size is not None:
+            self.embedding = nn.Embedding(field_size, embed_size, padding_idx=padding_idx)
+        else:
+            raise ValueError('missing required arguments')
+        self.field_size = self.embedding.num_embeddings
+        self.embed_size = self.embedding.embedding_dim
+        self.padding_idx = self.embedding.padding_idx
+        self.length = self.embed_size
+        self.use_attn = use_attn
+        if self.use_attn:
+            self.attn_args = {
+                'embed_dim': self.embed_size,
+                'num_heads': kwargs.get('num_heads', 1),
+                'dropout': kwargs.get('dropout', 0.0),
+                'bias': kwargs.get('bias', True),
+                'add_bias_kv': kwargs.get('add_bias_kv', False),
+                'add_zero_attn': kwargs.get('add_zero_attn', False)
+            }
+            self.attention = nn.MultiheadAttention(**self.attn_args)
+        else:
+            self.attention = _no_attention
+        if output_method not in ('avg_pooling', 'max_pooling', 'mean', 'none', 'sum'):
+            raise ValueError('output_method only allows ["avg_pooling", "max_pooling", "mean", "none", "sum"].')
+        self.output_method = output_method
+
+    def set_fused_optimizer(self, opt):
+        if opt is not None and self.output_method == 'max_pooling' and not self.use_attn:
+            raise NotImplementedError('torecsys_amd: max_pooling with a fused sparse optimizer is not implemented')
+        return super().set_fused_optimizer(opt)
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        idx = _strip(inputs)
+        if idx.dim() != 2:
+            raise ValueError(f'inputs must be (B, L), got {tuple(idx.shape)}')
+        w = self.embedding.weight
+        if self.use_attn or self.output_method == 'none':
+            out = F_.gather_rows(w, idx, None, self.padding_idx, self.fused_optimizer)      # (B,L,E)
+            if self.use_attn:
+                seq = out.transpose(0, 1)                                                   # (L,B,E)
+                seq, _ = self.attention(seq, seq, seq)
+                out = seq.transpose(0, 1)
+                pool = self._POOL.get(self.output_method)
+                if pool == 'max':
+                    out = out.max(dim=1, keepdim=True)[0]
+                elif pool == 'mean':
+                    out = out.mean(dim=1, keepdim=True)
+                elif pool == 'sum':
+                    out = out.sum(dim=1, keepdim=True)
+        else:
+            out = F_.bag_pool(w, idx, self._POOL[self.output_method], self.padding_idx, self.fused_optimizer)
+        return out.refine_names('B', 'N', 'E')
+
+    def show_attention(self, inputs: torch.Tensor, save_dir: Optional[str] = None):
+        raise NotImplementedError('torecsys_amd: show_attention (a plotting helper) is not provided')
+
+
 class ValueInput(BaseInput):
     """inputs/base/value_inp.py:26-44 (pass-through; no kernel)."""
 

@@ -7,7 +7,7 @@ What is rebound: the interaction layers of SURVEY §8a/§8f-N3, the per-field / 
 ``FeedForwardLayer`` -- layers/ctr/__init__.py:23-35; this is what ``DeepAndCrossNetworkModel.deep``,
 ``DeepFactorizationMachineModel.deep`` and ``XDeepFactorizationMachineModel.deep`` are built from,
 models/ctr/deep_and_cross_network.py:44, deep_fm.py:47, xdeep_fm.py:71), the three index-embedding
-inputs and the ``Inputs`` router (inputs/inputs.py:56-89).  ``patch(pkg, mlp=False)`` /
+inputs, the list-of-ids embedding ``ListIndicesEmbedding`` and the ``Inputs`` router (inputs/inputs.py:56-89).  ``patch(pkg, mlp=False)`` /
 ``patch(pkg, router=False)`` leave the MLP / the router with the reference.
 
 ``heads`` (default on): the scalar heads of ``FactorizationMachineModel``, ``DeepFactorizationMachineModel`` and
@@ -40,7 +40,7 @@ _LAYER_NAMES = [
     "BilinearInteractionLayer", "FieldAllTypeBilinear", "FieldEachTypeBilinear",
 ]
 _MLP_NAMES = ["MultilayerPerceptionLayer", "DNNLayer", "DenseLayer", "FullyConnectLayer", "FeedForwardLayer"]
-_INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFieldAwareEmbedding"]
+_INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFieldAwareEmbedding", "ListIndicesEmbedding"]
 _ROUTER_NAMES = ["Inputs"]
 _saved = {}
 _saved_defaults = {}
