@@ -657,6 +657,49 @@ int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const void* x, co
                         int32_t A, int32_t dtype, void* gx, float* gW1, float* gb1, float* gw2, float* gb2,
                         void* workspace, size_t ws_bytes, trs_stream_t stream);
 
+/* ---- SENET / compose-excitation gate (FiBiNET, FAT-DeepFFM) ----------------------------------------------------------
+ *   z[b,m] = mean_e x[b,m,e];  h = relu(W1 z + b1);  a = relu(W2 h + b2);  out[b,m,:] = x[b,m,:] * a[b,m]
+ * x, out (B, M, E); W1 (H, M), b1 (H), W2 (M, H), b2 (M): nn.Linear layouts, all of x's dtype.
+ * replaces AdaptiveAvgPool1d + Sequential(Linear, ReLU, Linear, ReLU) + einsum('ijk,ijh->ijk') of
+ *   torecsys/layers/ctr/compose_excitation_network.py:85-107.
+ *
+ * Fused family (trs_senet_fused_supported: M <= 64, 1 <= H <= M, rows of whole 16-byte vectors, M*E*sizeof <= 16 KiB):
+ * one kernel, a wave owns a sample and keeps its rows in registers; x is read once and out written once.  gates (B, M) and
+ * hidden (B, H), fp32, are written for a backward; both NULL: nothing but out is written.  Every intermediate is fp32,
+ * one rounding on store.  Other shapes are refused (TRS_ESHAPE): the caller composes the three streaming entries below. */
+int trs_senet_fused_supported(int32_t M, int32_t H, int32_t E, int32_t dtype);
+int trs_senet_fwd(const void* x, const void* W1, const void* b1, const void* W2, const void* b2, int64_t B, int32_t M,
+                  int32_t H, int32_t E, int32_t dtype, void* out, float* gates, float* hidden, trs_stream_t stream);
+
+/* Backward of trs_senet_fwd; g (B, M, E) of x's dtype, gates / hidden as written by the forward.  With
+ *   ga[m] = sum_e g[m,e] x[m,e],  gv = ga [a > 0],  gu = (W2^T gv) [h > 0],  gz = W1^T gu:
+ *   dx[m,e] = g[m,e] a[m] + gz[m] / E;   dW2 = sum_b gv (x) h,  db2 = sum_b gv,  dW1 = sum_b gu (x) z,  db1 = sum_b gu
+ * x and g are read once, dx is written once, z is recomputed.  dx and each of the four parameter gradients (x's dtype,
+ * the parameters' layouts) may be NULL.  The sums over the batch are accumulated in fp32 on chip, one partial slab per
+ * workgroup goes to `workspace` and a finish kernel adds the slabs in a fixed order: no float atomics, bit-reproducible
+ * from run to run.  The workspace (only needed with a parameter gradient) does not depend on B.
+ * replaces the autograd backward of compose_excitation_network.py:85-107 (einsum backward twice, the pooling backward
+ * expanded to (B, M, E), the accumulation of the two input gradients, two Linear + ReLU backwards).                    */
+size_t trs_senet_bwd_workspace_bytes(int64_t B, int32_t M, int32_t H);
+int trs_senet_bwd(const void* x, const void* g, const float* gates, const float* hidden, const void* W1, const void* W2,
+                  int64_t B, int32_t M, int32_t H, int32_t E, int32_t dtype, void* dx, void* dW1, void* db1, void* dW2,
+                  void* db2, void* workspace, size_t ws_bytes, trs_stream_t stream);
+
+/* General family: any M, any E (rows that are not whole 16-byte vectors take an element loop), any excitation -- the
+ * caller runs it between these single-pass kernels, on fp32 (B, M) tensors.
+ *   trs_senet_squeeze:    z[b,m] = mean_e x[b,m,e]                    fp32        (compose_excitation_network.py:85-91)
+ *   trs_senet_scale_fwd:  out[b,m,:] = x[b,m,:] * a[b,m]              a fp32      (compose_excitation_network.py:103-106)
+ *   trs_senet_scale_bwd:  ga[b,m] = sum_e g[b,m,e] x[b,m,e]           fp32, when ga != NULL (needs x and g)
+ *                         dx[b,m,e] = g[b,m,e] a[b,m] + gz[b,m] / E   when dx != NULL; gz NULL: the first term alone;
+ *                                                                     g NULL: the second alone (squeeze backward)
+ * The excitation's backward turns ga into gz, so a layer calls trs_senet_scale_bwd twice: for ga (x and g read), then
+ * for dx (g read, dx written).  No (B, M, E) temporary exists besides out and dx.                                      */
+int trs_senet_squeeze(const void* x, int64_t B, int32_t M, int32_t E, int32_t dtype, float* z, trs_stream_t stream);
+int trs_senet_scale_fwd(const void* x, const float* a, int64_t B, int32_t M, int32_t E, int32_t dtype, void* out,
+                        trs_stream_t stream);
+int trs_senet_scale_bwd(const void* x, const void* g, const float* a, const float* gz, int64_t B, int32_t M, int32_t E,
+                        int32_t dtype, float* ga, void* dx, trs_stream_t stream);
+
 /* ---- index staging: pack per-field columns into the (B,N) index matrix --------
  * out[b, c] = src_j[b * width_j + t]  for the c-th output column = column t of source j.
  * replaces the per-field unsqueeze + torch.cat of inputs/inputs.py:75-80 by one pass.

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks (developer tool): time each C-ABI kernel at the BASELINE shape with HIP events
 on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]
---what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag)."""
+--what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag).
+--what senet: the SENET / compose-excitation layer, both kernel families, against the ATen composition of the same module
+(own inputs, see bench_senet)."""
 import argparse
 import os
 import sys
@@ -126,6 +128,82 @@ def bench_bag(a):
               flush=True)
 
 
+def bench_senet(a):
+    """ComposeExcitationNetworkLayer (csrc/senet.hip): forward under no_grad and forward + backward, bf16 and fp32, the
+    fused family at (65 536, 39, 64, reduction 3) and the general family at a FAT-DeepFFM-like (4096, 400, 16, reduction 4),
+    each against the ATen composition of the SAME module on the same inputs (pool -> fc -> einsum,
+    compose_excitation_network.py:85-107), the candidates taking turns inside every round."""
+    import torch.nn as nn
+    from torecsys_amd.layers import SENETLayer
+    dev = torch.device("cuda:0")
+
+    def aten(m):
+        def run(x):
+            pooled = m.pooling(x).flatten(1)
+            return torch.einsum("ijk,ijh->ijk", x, m.fc(pooled).unsqueeze(-1))
+        return run
+
+    for (B, M, E, r, family) in ((65536, 39, 64, 3, "fused"), (4096, 400, 16, 4, "general")):
+        for dt in (torch.bfloat16, torch.float32):
+            s = 2 if dt == torch.bfloat16 else 4
+            g = torch.Generator(device=dev).manual_seed(77)
+            torch.manual_seed(78)
+            m = SENETLayer(M, r, squared=False).to(dev).to(dt)
+            x = (0.5 * torch.randn(B, M, E, generator=g, device=dev) + torch.randn(B, M, 1, generator=g, device=dev)).to(dt)
+            gout = torch.randn(B, M, E, generator=g, device=dev).to(dt)
+            xg = x.clone().requires_grad_()
+            block = B * M * E * s
+            cands = [("senet (HIP, %s)" % family, lambda t: m(t).rename(None)), ("composition (ATen)", aten(m))]
+            with torch.no_grad():
+                d = float((cands[0][1](x).float() - cands[1][1](x).float()).abs().max())
+            print(f"senet B={B} M={M} H={M // r} E={E} {str(dt)[6:]} block {block / 1e6:.0f} MB; max |HIP - ATen| = {d:.3e}",
+                  flush=True)
+
+            def fwd(f):
+                return lambda: f(x)
+
+            def fwd_bwd(f):
+                def run():
+                    xg.grad = None
+                    for p in m.parameters():
+                        p.grad = None
+                    f(xg).backward(gout)
+                return run
+
+            for what, alg in (("fwd", 2 * block), ("fwd+bwd", 5 * block)):
+                per = {name: [] for name, _ in cands}
+                for _ in range(a.rounds):
+                    for name, f in cands:
+                        if what == "fwd":
+                            with torch.no_grad():
+                                per[name].append(timeit(fwd(f), iters=a.iters, warm=2)[0])
+                        else:
+                            per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+                for name, ts in per.items():
+                    ts = sorted(ts)
+                    med = ts[len(ts) // 2]
+                    print(f"{family:7s} {str(dt)[6:]:8s} {what:8s} {name:24s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                          f"{ts[-1] * 1e6:9.1f} us  {alg / med / 8e12 * 100:5.1f}% of 8 TB/s on {alg / 1e6:.0f} MB (alg)",
+                          flush=True)
+            if family == "general":
+                # the share of the fp32 excitation (two Linear + ReLU on (B, M) / (B, H), forward and backward)
+                z = torch.randn(B, M, device=dev, requires_grad=True)
+                ga = torch.randn(B, M, device=dev)
+
+                def exc():
+                    z.grad = None
+                    for p in m.parameters():
+                        p.grad = None
+                    red, add = m.fc.ReductionLinear, m.fc.AdditionLinear
+                    h = torch.relu(nn.functional.linear(z, red.weight.float(), red.bias.float()))
+                    torch.relu(nn.functional.linear(h, add.weight.float(), add.bias.float())).backward(ga)
+                ts = sorted(timeit(exc, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+                print(f"general {str(dt)[6:]:8s} fwd+bwd  fp32 excitation alone (ATen) med {ts[len(ts) // 2] * 1e6:9.1f} us  spread "
+                      f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us", flush=True)
+            del x, gout, xg, m
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -137,11 +215,13 @@ def main():
     ap.add_argument("--what", default="all")
     ap.add_argument("--L", type=int, default=50, help="bag: list length")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
-    ap.add_argument("--rounds", type=int, default=5, help="bag: alternating rounds")
-    ap.add_argument("--iters", type=int, default=10, help="bag: timed launches per round")
+    ap.add_argument("--rounds", type=int, default=5, help="bag / senet: alternating rounds")
+    ap.add_argument("--iters", type=int, default=10, help="bag / senet: timed launches per round")
     a = ap.parse_args()
     if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"
         return bench_bag(a)
+    if a.what == "senet":        # own inputs and modules: not part of "all"
+        return bench_senet(a)
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     s = 2 if dt == torch.bfloat16 else 4
     dev = torch.device("cuda:0")

@@ -96,6 +96,13 @@ SIGNATURES = {
     "trs_bag_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "trs_scatter_argmax_workspace_bytes": (_SZ, [_I64, _I32]),
     "trs_scatter_rows_argmax": (c_int32, [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P]),
+    "trs_senet_fused_supported": (c_int32, [_I32, _I32, _I32, _I32]),
+    "trs_senet_fwd": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "trs_senet_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "trs_senet_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "trs_senet_squeeze": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
+    "trs_senet_scale_fwd": (c_int32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P]),
+    "trs_senet_scale_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_bwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_dot_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

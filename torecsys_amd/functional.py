@@ -1448,6 +1448,175 @@ def afm(x: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b
 
 
 # --------------------------------------------------------------------------------------------
+# SENET / compose-excitation gate: out[b,m,:] = x[b,m,:] * a[b,m],  a = relu(W2 relu(W1 mean_E(x[b]) + b1) + b2)
+# --------------------------------------------------------------------------------------------
+def senet_fused_supported(x: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor) -> bool:
+    """True when the one-kernel family serves these operands (ReLU excitation is the caller's side of the rule): a HIP
+    (B, M, E) block and four parameters of ONE dtype (fp32 / bf16), M <= 64, 1 <= H <= M, rows of whole 16-byte vectors,
+    a sample of at most 16 KiB.  Decided from shapes and dtypes alone."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    if any(p is None or not p.is_cuda or p.dtype != x.dtype for p in (W1, b1, W2, b2)):
+        return False
+    M, E = int(x.shape[1]), int(x.shape[2])
+    H = int(W1.shape[0]) if W1.dim() == 2 else -1
+    if tuple(W1.shape) != (H, M) or tuple(W2.shape) != (M, H) or tuple(b1.shape) != (H,) or tuple(b2.shape) != (M,):
+        return False
+    return bool(size_query("trs_senet_fused_supported", M, H, E, value_dtype_code(x)))
+
+
+class _SENet(Function):
+    """The fused family: trs_senet_fwd / trs_senet_bwd.  The gates (B,M) and hidden activations (B,H) are kept in fp32
+    when a backward can follow, and not written at all otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2):
+        require_device(x, W1, b1, W2, b2)
+        x = x.contiguous()
+        W1, b1, W2, b2 = (t.contiguous() for t in (W1, b1, W2, b2))
+        B, M, E = x.shape
+        H = W1.shape[0]
+        out = torch.empty_like(x)
+        a = h = None
+        if any(ctx.needs_input_grad):
+            a = torch.empty(B, M, dtype=torch.float32, device=x.device)
+            h = torch.empty(B, H, dtype=torch.float32, device=x.device)
+            ctx.save_for_backward(x, a, h, W1, W2)
+        call("trs_senet_fwd", ptr(x), ptr(W1), ptr(b1), ptr(W2), ptr(b2), B, M, H, E, value_dtype_code(x), ptr(out),
+             ptr(a), ptr(h), stream_ptr())
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, a, h, W1, W2 = ctx.saved_tensors
+        B, M, E = x.shape
+        H = W1.shape[0]
+        need = ctx.needs_input_grad
+        dev, dt = x.device, x.dtype
+        dx = torch.empty_like(x) if need[0] else None
+        gW1 = torch.empty(H, M, dtype=dt, device=dev) if need[1] else None
+        gb1 = torch.empty(H, dtype=dt, device=dev) if need[2] else None
+        gW2 = torch.empty(M, H, dtype=dt, device=dev) if need[3] else None
+        gb2 = torch.empty(M, dtype=dt, device=dev) if need[4] else None
+        ws, ws_bytes = None, 0
+        if any(need[1:]):
+            ws_bytes = size_query("trs_senet_bwd_workspace_bytes", B, M, H)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        call("trs_senet_bwd", ptr(x), ptr(g.contiguous()), ptr(a), ptr(h), ptr(W1), ptr(W2), B, M, H, E,
+             value_dtype_code(x), ptr(dx), ptr(gW1), ptr(gb1), ptr(gW2), ptr(gb2), ptr(ws), ws_bytes, stream_ptr())
+        return dx, gW1, gb1, gW2, gb2
+
+
+def senet(x: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """(B, M, E) -> (B, M, E): squeeze, ReLU excitation (W1 (H,M), b1 (H), W2 (M,H), b2 (M): nn.Linear layouts) and
+    re-weighting in one pass.  Raises when ``senet_fused_supported`` does not hold (no fallback)."""
+    x = x.rename(None) if x.has_names() else x
+    if x.dim() != 3:
+        raise ValueError(f"SENET input must be (B, M, E), got {tuple(x.shape)}")
+    require_device(x, W1, b1, W2, b2)
+    if not senet_fused_supported(x, W1, b1, W2, b2):
+        raise ValueError(f"senet: shapes / dtypes outside the fused family (x {tuple(x.shape)} {x.dtype}, W1 "
+                         f"{tuple(W1.shape)} {W1.dtype}); compose senet_squeeze / senet_scale instead")
+    return _SENet.apply(x, W1, b1, W2, b2)
+
+
+class SENetLink:
+    """Ties the two ends of the general family together in the backward.  dx = g * a + gz / E needs the output gradient g
+    and the gates a (known to ``senet_scale``) and gz (known to ``senet_squeeze`` once the excitation's backward has
+    run): with a link, ``senet_scale``'s backward hands g and a over instead of writing g * a, and ``senet_squeeze``'s
+    backward writes dx once -- no second (B, M, E) tensor and no accumulation of two input gradients.  Both calls of a
+    layer's forward must use the same link, and the gates must be computed from the squeezed means."""
+    __slots__ = ("z_needs_grad", "defer", "g", "a")
+
+    def __init__(self):
+        self.z_needs_grad = self.defer = False
+        self.g = self.a = None
+
+
+class _SENetSqueeze(Function):
+    @staticmethod
+    def forward(ctx, x, link):
+        require_device(x)
+        x = x.contiguous()
+        B, M, E = x.shape
+        z = torch.empty(B, M, dtype=torch.float32, device=x.device)
+        call("trs_senet_squeeze", ptr(x), B, M, E, value_dtype_code(x), ptr(z), stream_ptr())
+        ctx.shape, ctx.dtype, ctx.link = (B, M, E), x.dtype, link
+        if link is not None:
+            link.z_needs_grad = bool(ctx.needs_input_grad[0])
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz):
+        B, M, E = ctx.shape
+        gz = gz.contiguous().float()
+        g = a = None
+        link = ctx.link
+        if link is not None and link.g is not None:
+            g, a, link.g, link.a = link.g, link.a, None, None
+        dx = torch.empty(B, M, E, dtype=ctx.dtype, device=gz.device)
+        code = _abi.TRS_F32 if ctx.dtype == torch.float32 else _abi.TRS_BF16
+        call("trs_senet_scale_bwd", None, ptr(g), ptr(a), ptr(gz), B, M, E, code, None, ptr(dx), stream_ptr())
+        return dx, None
+
+
+class _SENetScale(Function):
+    @staticmethod
+    def forward(ctx, x, a, link):
+        require_device(x, a)
+        x = x.contiguous()
+        B, M, E = x.shape
+        a = a.contiguous()
+        out = torch.empty_like(x)
+        call("trs_senet_scale_fwd", ptr(x), ptr(a), B, M, E, value_dtype_code(x), ptr(out), stream_ptr())
+        ctx.save_for_backward(x, a)
+        ctx.link = link
+        if link is not None:
+            link.defer = bool(link.z_needs_grad and ctx.needs_input_grad[0] and ctx.needs_input_grad[1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, a = ctx.saved_tensors
+        B, M, E = x.shape
+        g = g.contiguous()
+        code = value_dtype_code(x)
+        ga = dx = None
+        if ctx.needs_input_grad[1]:
+            ga = torch.empty(B, M, dtype=torch.float32, device=x.device)
+            call("trs_senet_scale_bwd", ptr(x), ptr(g), None, None, B, M, E, code, ptr(ga), None, stream_ptr())
+        if ctx.needs_input_grad[0]:
+            link = ctx.link
+            if link is not None and link.defer:
+                link.g, link.a = g, a            # senet_squeeze's backward writes dx = g * a + gz / E
+            else:
+                dx = torch.empty_like(x)
+                call("trs_senet_scale_bwd", None, ptr(g), ptr(a), None, B, M, E, code, None, ptr(dx), stream_ptr())
+        return dx, ga, None
+
+
+def senet_squeeze(x: torch.Tensor, link: Optional[SENetLink] = None) -> torch.Tensor:
+    """(B, M, E) -> (B, M) fp32 means over E, one pass (any M, any E)."""
+    x = x.rename(None) if x.has_names() else x
+    if x.dim() != 3:
+        raise ValueError(f"SENET input must be (B, M, E), got {tuple(x.shape)}")
+    return _SENetSqueeze.apply(x, link)
+
+
+def senet_scale(x: torch.Tensor, a: torch.Tensor, link: Optional[SENetLink] = None) -> torch.Tensor:
+    """out[b,m,:] = x[b,m,:] * a[b,m] with fp32 gates a (B, M), one pass; the gradient of a is sum_e g * x (fp32)."""
+    x = x.rename(None) if x.has_names() else x
+    a = a.rename(None) if a.has_names() else a
+    if x.dim() != 3 or tuple(a.shape) != tuple(x.shape[:2]) or a.dtype != torch.float32:
+        raise ValueError(f"senet_scale: x (B, M, E) and fp32 gates (B, M) expected, got {tuple(x.shape)} and "
+                         f"{tuple(a.shape)} {a.dtype}")
+    return _SENetScale.apply(x, a, link)
+
+
+# --------------------------------------------------------------------------------------------
 # K3: field-aware FM pair products
 # --------------------------------------------------------------------------------------------
 class _FFM(Function):

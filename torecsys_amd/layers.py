@@ -3,7 +3,7 @@ output names and parameter names as ``torecsys.layers.ctr``), running on libtrs_
 
 Reference: torecsys/layers/__init__.py (BaseLayer), torecsys/layers/ctr/__init__.py (aliases),
 layers/ctr/{factorization_machine,field_aware_factorization_machine,cross_network,
-compress_interaction_network,inner_product_network,multilayer_perceptron}.py.
+compress_interaction_network,inner_product_network,multilayer_perceptron,compose_excitation_network}.py.
 """
 from __future__ import annotations
 
@@ -328,6 +328,67 @@ class BilinearInteractionLayer(BaseLayer):
             output = F_.pair_bilinear(x, self.bilinear.weight, self.bilinear.bias, 1)
         output.names = ('B', 'N', 'O',)
         return output
+
+
+class ComposeExcitationNetworkLayer(BaseLayer):
+    """Compose excitation network (FAT-DeepFFM) / squeeze-and-excitation network (FiBiNET), (B,M,E) -> (B,M,E) named
+    ('B','N','E'):  out[b,m,:] = x[b,m,:] * a[b,m],  a = act(W2 act(W1 mean_E(x[b]) + b1) + b2), with M = num_fields**2
+    when ``squared`` (the default) else num_fields and H = M // reduction hidden units.
+    layers/ctr/compose_excitation_network.py:47-109.  Children and parameters as in the reference: ``pooling``
+    (AdaptiveAvgPool1d, kept as a module, never called) and ``fc`` = Sequential(ReductionLinear, ReductionActivation,
+    AdditionLinear, AdditionActivation), both activation slots holding the SAME module; the activation follows BOTH linears,
+    so with the default the gates are relu(...), not a sigmoid: >= 0, unbounded, and exactly 0 for dead units.
+    Two families, chosen from shapes and dtypes alone:
+      fused    ReLU excitation, M <= 64, 1 <= H, rows of whole 16-byte vectors, a sample of at most 16 KiB, x and the four
+               parameters of one dtype (fp32 / bf16): one kernel forward, one (+ a small finish) backward
+               (functional.senet); x is read once and out written once, every intermediate is fp32.
+      general  everything else (M = N**2 in the hundreds, other activations, odd rows, H = 0): squeeze and re-weighting
+               are single HIP passes (functional.senet_squeeze / senet_scale), the excitation between them runs in ATen
+               under autograd in fp32 whatever the module's dtype (bf16 parameters still receive bf16 gradients).
+    Deviations: an input whose field count is not M raises ValueError here (the reference fails inside F.linear); CPU
+    tensors raise (no CPU path).  H = 0 (reduction > M) is legal as in the reference: the gates are act(b2)."""
+
+    @property
+    def inputs_size(self):
+        return {'inputs': ('B', 'N^2', 'E',)}
+
+    @property
+    def outputs_size(self):
+        return {'outputs': ('B', 'N^2', 'E',)}
+
+    def __init__(self, num_fields: int, reduction: int, squared: Optional[bool] = True,
+                 activation: Optional[nn.Module] = nn.ReLU()):
+        super().__init__()
+        inputs_num_fields = num_fields ** 2 if squared else num_fields
+        reduced_num_fields = inputs_num_fields // reduction
+        self.pooling = nn.AdaptiveAvgPool1d(1)
+        self.fc = nn.Sequential()
+        self.fc.add_module('ReductionLinear', nn.Linear(inputs_num_fields, reduced_num_fields))
+        self.fc.add_module('ReductionActivation', activation)
+        self.fc.add_module('AdditionLinear', nn.Linear(reduced_num_fields, inputs_num_fields))
+        self.fc.add_module('AdditionActivation', activation)
+
+    def forward(self, emb_inputs: torch.Tensor) -> torch.Tensor:
+        x = _strip(emb_inputs)
+        red, add = self.fc.ReductionLinear, self.fc.AdditionLinear
+        act1, act2 = self.fc.ReductionActivation, self.fc.AdditionActivation
+        M = red.in_features
+        if x.dim() != 3:
+            raise ValueError(f'expected (B, {M}, E), got {tuple(x.shape)}')
+        if x.shape[1] != M:
+            raise ValueError(f'expected {M} fields, got {x.shape[1]}')
+        F_.require_device(x, red.weight, red.bias, add.weight, add.bias)
+        if (type(act1) is nn.ReLU and type(act2) is nn.ReLU
+                and F_.senet_fused_supported(x, red.weight, red.bias, add.weight, add.bias)):
+            outputs = F_.senet(x, red.weight, red.bias, add.weight, add.bias)
+        else:
+            link = F_.SENetLink()
+            z = F_.senet_squeeze(x, link)
+            h = act1(nn.functional.linear(z, red.weight.float(), red.bias.float()))
+            a = act2(nn.functional.linear(h, add.weight.float(), add.bias.float()))
+            outputs = F_.senet_scale(x, a, link)
+        outputs.names = ('B', 'N', 'E',)
+        return outputs
 
 
 class AttentionalFactorizationMachineLayer(BaseLayer):
@@ -1132,6 +1193,9 @@ AFMLayer = AttentionalFactorizationMachineLayer
 FMLayer = FactorizationMachineLayer
 FFMLayer = FieldAwareFactorizationMachineLayer
 CINLayer = CompressInteractionNetworkLayer
+CENLayer = ComposeExcitationNetworkLayer
+SqueezeAndExcitationNetworkLayer = ComposeExcitationNetworkLayer
+SENETLayer = ComposeExcitationNetworkLayer
 DenseLayer = MultilayerPerceptionLayer
 DNNLayer = MultilayerPerceptionLayer
 FullyConnectLayer = MultilayerPerceptionLayer

@@ -2,7 +2,10 @@
 ``torecsys.models.ctr.*`` (which import layers by alias, e.g. ``from torecsys.layers import FMLayer,
 DNNLayer`` -- models/ctr/deep_fm.py:6) build on them unchanged.  See INTEGRATION.md.
 
-What is rebound: the interaction layers of SURVEY §8a/§8f-N3, the per-field / deep MLP
+What is rebound: the interaction layers of SURVEY §8a/§8f-N3, the SENET / compose-excitation gate
+(``ComposeExcitationNetworkLayer`` and its aliases ``CENLayer``, ``SqueezeAndExcitationNetworkLayer``, ``SENETLayer`` --
+layers/ctr/__init__.py:24,34,35; the first layer of the FiBiNET and FAT-DeepFFM models, whose ``forward``s run as they are
+over the drop-ins), the per-field / deep MLP
 (``MultilayerPerceptionLayer`` and its aliases ``DNNLayer``, ``DenseLayer``, ``FullyConnectLayer``,
 ``FeedForwardLayer`` -- layers/ctr/__init__.py:23-35; this is what ``DeepAndCrossNetworkModel.deep``,
 ``DeepFactorizationMachineModel.deep`` and ``XDeepFactorizationMachineModel.deep`` are built from,
@@ -38,6 +41,7 @@ _LAYER_NAMES = [
     "OuterProductNetworkLayer",
     "AttentionalFactorizationMachineLayer", "AFMLayer",
     "BilinearInteractionLayer", "FieldAllTypeBilinear", "FieldEachTypeBilinear",
+    "ComposeExcitationNetworkLayer", "CENLayer", "SqueezeAndExcitationNetworkLayer", "SENETLayer",
 ]
 _MLP_NAMES = ["MultilayerPerceptionLayer", "DNNLayer", "DenseLayer", "FullyConnectLayer", "FeedForwardLayer"]
 _INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFieldAwareEmbedding", "ListIndicesEmbedding"]
