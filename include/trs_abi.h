@@ -172,6 +172,57 @@ int trs_scatter_rows_update_mapped(const void* g_rows, void* table, const int32_
                                    int32_t optimizer, float lr, float eps, float beta1, float beta2, float* state,
                                    float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
+/* ---- fused optimizer steps whose step size lives on the DEVICE (hipGraph-capturable optimizers) ------------------
+ * trs_scatter_rows_update / _adam / _mapped with the by-value step size replaced by a pointer to ONE fp32 in device
+ * memory, read by the kernels when they apply a row: a launch captured into a hipGraph follows a learning rate written
+ * between replays (FusedSparse*.set_lr) and Adam's per-step bias correction (trs_adam_step_size below) instead of
+ * repeating the capture-time value.  Everything else -- arguments, arithmetic, workspace -- is that of the sibling. */
+int trs_scatter_rows_update_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
+                                const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
+                                int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                                int32_t optimizer, const float* lr_dev, float eps, float* state, void* workspace,
+                                size_t ws_bytes, trs_stream_t stream);
+int trs_scatter_rows_update_adam_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
+                                     const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
+                                     int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                                     const float* step_size_dev, float beta1, float beta2, float eps, float* exp_avg,
+                                     float* exp_avg_sq, void* workspace, size_t ws_bytes, trs_stream_t stream);
+/* optimizer 3 (lazy Adam): lr_dev points at the bias-corrected step size */
+int trs_scatter_rows_update_mapped_dev(const void* g_rows, void* table, const int32_t* row_map, const int32_t* row_start,
+                                       const int32_t* perm, int64_t K, int64_t U, int64_t V, int32_t E, int32_t dtype,
+                                       int32_t optimizer, const float* lr_dev, float eps, float beta1, float beta2,
+                                       float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
+
+/* Adam's per-step scalars, on the device (one thread):  *step += 1;  *step_size_dev = *lr_dev * sqrt(1 - beta2^t) /
+ * (1 - beta1^t) with t the new *step -- computed in double, rounded once to fp32 (what the host computes for
+ * trs_scatter_rows_update_adam).  Enqueued once per table per backward in front of the *_dev update. */
+int trs_adam_step_size(int64_t* step, const float* lr_dev, double beta1, double beta2, float* step_size_dev,
+                       trs_stream_t stream);
+
+/* ---- device-side row compaction (owner side of a large row-sharded table) ---------------------------------------
+ * ids (K int32, local row ids with repeats) -> row_map (T + 1 int32) and inv (K int32), T = trs_compact_rows_slots(K) =
+ * the smallest power of two >= max(2K, 2): fixed shapes, no read-back, no allocation -- replaces torch.unique(ids,
+ * return_inverse=True) in front of trs_scatter_rows_update_mapped, so the step can be captured into a hipGraph.
+ *   - every id >= 0 owns exactly one slot s < T: row_map[s] == id and inv[k] == s wherever ids[k] == id; distinct ids
+ *     own distinct slots (ids >= the table's rows are stored like any other: the mapped update skips them);
+ *   - every id < 0 (the -1 padding of a fixed-capacity exchange) gets inv[k] == T, and row_map[T] == -1;
+ *   - every slot that holds no id reads -1.
+ * Which slot an id gets is unspecified and differs from run to run (an open-addressing hash table filled by racing
+ * workgroups: atomics on the integer keys only).  `slots` must equal trs_compact_rows_slots(K); K < 2^29.             */
+int64_t trs_compact_rows_slots(int64_t K);
+int trs_compact_rows(const int32_t* ids, int64_t K, int32_t* row_map, int64_t slots, int32_t* inv, trs_stream_t stream);
+
+/* The same compaction with the U distinct ids numbered DENSELY, for consumers whose cost grows with the row space they
+ * are handed (the bucket build and the bucket walk: what the owner-side optimizer step uses): two more passes give every
+ * occupied slot a rank in [0, U).  dense_map (K + 1 int32) and inv (K int32):
+ *   - every id >= 0 owns exactly one row u < U <= K: dense_map[u] == id and inv[k] == u wherever ids[k] == id;
+ *   - every id < 0 gets inv[k] == K; dense_map[u] == -1 for every u in [U, K];
+ *   - which row an id gets is unspecified.  U itself stays on the device.
+ * workspace (trs_compact_rows_dense_workspace_bytes) holds the hash table; same limits and guarantees otherwise.        */
+size_t trs_compact_rows_dense_workspace_bytes(int64_t K);
+int trs_compact_rows_dense(const int32_t* ids, int64_t K, int32_t* dense_map, int32_t* inv, void* workspace,
+                           size_t ws_bytes, trs_stream_t stream);
+
 /* ---- K1+K2(+K8): fused embedding lookup + FM second order ----------------------------------
  * emb[b,n,:]  = table[idx[b,n]+offsets[n], :]                       (optional, may be NULL)
  * fm[b,:]     = 0.5 * ((sum_n x)^2 - sum_n x^2)                     (optional, may be NULL)

@@ -3,7 +3,9 @@
 on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]
 --what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag).
 --what senet: the SENET / compose-excitation layer, both kernel families, against the ATen composition of the same module
-(own inputs, see bench_senet)."""
+(own inputs, see bench_senet).
+--what compact [--shard-rows 125000000]: device-side row compaction against torch.unique, and the owner-side fused update
+of a large shard through either (own inputs, see bench_compact)."""
 import argparse
 import os
 import sys
@@ -204,6 +206,62 @@ def bench_senet(a):
             torch.cuda.empty_cache()
 
 
+def bench_compact(a):
+    """Owner side of a large row-sharded table: K = B * N received ids over ``--shard-rows`` rows, uniform and Zipf(1.05).
+    First the compaction alone: functional.compact_rows (hash slots) and compact_rows_dense (densely numbered, what
+    dist.py uses) against torch.unique(return_inverse=True), which also reads the distinct count on the host.  Then the
+    whole owner update through each: compaction, bucket build over the compact rows, mapped Adagrad update of a
+    (rows, E) table.  The candidates take turns inside a round; median of the per-round medians with their min..max."""
+    from torecsys_amd.optim import FusedSparseAdagrad
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    dev = torch.device("cuda:0")
+    K, V, E = a.B * a.N, a.shard_rows, a.E
+    g = torch.Generator(device=dev).manual_seed(1234)
+    u = torch.rand(K, generator=g, device=dev, dtype=torch.float64)
+    zipf = ((V ** -0.05 - 1.0) * u + 1.0) ** (1.0 / -0.05)      # Zipf(1.05) ranks: the continuous CDF inverted
+    ids = {"uniform": torch.randint(0, V, (K,), generator=g, device=dev).to(torch.int32),
+           "zipf(1.05)": (zipf.long() - 1).clamp_(0, V - 1).to(torch.int32)}
+    table = torch.zeros(V, E, dtype=dt, device=dev)
+    grad = torch.randn(K, E, generator=g, device=dev, dtype=dt)
+    opt = FusedSparseAdagrad(0.01)
+    opt.state_for(table, table)
+    print(f"row compaction K={K} ids over {V} rows, E={E} {a.dtype}; {a.rounds} rounds x {a.iters} launches", flush=True)
+
+    def unique_route(x):
+        uniq, inv = torch.unique(x, return_inverse=True)
+        return uniq.to(torch.int32), inv.to(torch.int32).view(-1, 1)
+
+    def slot_route(x):
+        row_map, inv = F_.compact_rows(x)
+        return row_map, inv.view(-1, 1)
+
+    def dense_route(x):
+        dense_map, inv = F_.compact_rows_dense(x)
+        return dense_map, inv.view(-1, 1)
+
+    def update(route, x):
+        def run():
+            F_.clear_caches()          # the buckets are rebuilt every step, as in training
+            row_map, inv = route(x)
+            rb = F_.row_buckets(inv, None, row_map.numel())
+            F_.scatter_rows_update_mapped(rb, table, opt, grad, row_map, key=table)
+        return run
+
+    routes = [("compact_rows", slot_route), ("compact_rows_dense", dense_route), ("torch.unique", unique_route)]
+    for name, x in ids.items():
+        cands = [(label, lambda route=route, x=x: route(x)) for label, route in routes]
+        cands += [("owner update, " + label, update(route, x)) for label, route in routes]
+        meds = {c: [] for c, _ in cands}
+        for _ in range(a.rounds):
+            for c, fn in cands:
+                meds[c].append(timeit(fn, iters=a.iters, warm=2)[0])
+        print(f"  {name}: {int(torch.unique(x).numel())} distinct rows", flush=True)
+        for c, _ in cands:
+            ts = sorted(meds[c])
+            print(f"    {c:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us   ({ts[0] * 1e6:.1f} .. {ts[-1] * 1e6:.1f})",
+                  flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -215,9 +273,12 @@ def main():
     ap.add_argument("--what", default="all")
     ap.add_argument("--L", type=int, default=50, help="bag: list length")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
-    ap.add_argument("--rounds", type=int, default=5, help="bag / senet: alternating rounds")
-    ap.add_argument("--iters", type=int, default=10, help="bag / senet: timed launches per round")
+    ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact: alternating rounds")
+    ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact: timed launches per round")
+    ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
     a = ap.parse_args()
+    if a.what == "compact":      # own inputs (a 125 M-row table and its Adagrad state): not part of "all"
+        return bench_compact(a)
     if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"
         return bench_bag(a)
     if a.what == "senet":        # own inputs and modules: not part of "all"

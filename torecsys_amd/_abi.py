@@ -91,6 +91,18 @@ SIGNATURES = {
                                                _P, _SZ, _P]),
     "trs_scatter_rows_update_mapped": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_float,
                                                  ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ, _P]),
+    "trs_scatter_rows_update_dev": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _I32,
+                                              _P, ctypes.c_float, _P, _P, _SZ, _P]),
+    "trs_scatter_rows_update_adam_dev": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64,
+                                                   _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ,
+                                                   _P]),
+    "trs_scatter_rows_update_mapped_dev": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P,
+                                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ, _P]),
+    "trs_adam_step_size": (c_int32, [_P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "trs_compact_rows_slots": (_I64, [_I64]),
+    "trs_compact_rows": (c_int32, [_P, _I64, _P, _I64, _P, _P]),
+    "trs_compact_rows_dense_workspace_bytes": (_SZ, [_I64]),
+    "trs_compact_rows_dense": (c_int32, [_P, _I64, _P, _P, _P, _SZ, _P]),
     "trs_embed_fm": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "trs_embed_fm_fields": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "trs_bag_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),

@@ -468,7 +468,12 @@ struct RowSink {
   // the owner side of a row-sharded table, whose 125 M-row shard cannot afford a V-sized bucket index per step.
   const int32_t* row_map = nullptr;
   int64_t map_rows = 0;     // rows of the table row_map points into: an entry outside [0, map_rows) is skipped
+  // Optional: the step size lives on the DEVICE (one fp32, the *_dev entries): a launch captured into a hipGraph then
+  // follows set_lr() / Adam's per-step bias correction from replay to replay; `lr` is ignored when this is set
+  const float* lr_dev = nullptr;
 };
+// the step size of this launch: a uniform load (once per touched row, cached) when it lives on the device
+__device__ __forceinline__ float sink_lr(const RowSink& k) { return k.lr_dev != nullptr ? *k.lr_dev : k.lr; }
 // table row a bucketed row lands on; -1 = a row_map entry outside the table (the sinks skip negative positions)
 __device__ __forceinline__ int64_t sink_row(const RowSink& k, int64_t r) {
   if (k.row_map == nullptr) return r;
@@ -490,16 +495,17 @@ __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ o
   if (!touched) return;
   float w[VE];
   Vec16<T>::unpack(out[vec], w);
+  const float lr = sink_lr(k);
   if (k.mode == 1) {
 #pragma unroll
-    for (int i = 0; i < VE; ++i) w[i] = fmaf(-k.lr, acc[i], w[i]);
+    for (int i = 0; i < VE; ++i) w[i] = fmaf(-lr, acc[i], w[i]);
   } else if (k.mode == 2) {
     float* st = k.state + vec * VE;
 #pragma unroll
     for (int i = 0; i < VE; ++i) {
       const float s2 = fmaf(acc[i], acc[i], st[i]);
       st[i] = s2;
-      w[i] -= k.lr * acc[i] / (sqrtf(s2) + k.eps);
+      w[i] -= lr * acc[i] / (sqrtf(s2) + k.eps);
     }
   } else {
     float* m1 = k.state + vec * VE;
@@ -510,7 +516,7 @@ __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ o
       const float v = m2[i] + (acc[i] * acc[i] - m2[i]) * (1.f - k.beta2);
       m1[i] = a;
       m2[i] = v;
-      w[i] -= k.lr * a / (sqrtf(v) + k.eps);
+      w[i] -= lr * a / (sqrtf(v) + k.eps);
     }
   }
   out[vec] = Vec16<T>::pack(w);
@@ -525,18 +531,19 @@ __device__ __forceinline__ void sink_elem(const RowSink& k, T* __restrict__ out,
   }
   if (!touched) return;
   float w = to_f32(out[idx]);
+  const float lr = sink_lr(k);
   if (k.mode == 1) {
-    w = fmaf(-k.lr, acc, w);
+    w = fmaf(-lr, acc, w);
   } else if (k.mode == 2) {
     const float s2 = fmaf(acc, acc, k.state[idx]);
     k.state[idx] = s2;
-    w -= k.lr * acc / (sqrtf(s2) + k.eps);
+    w -= lr * acc / (sqrtf(s2) + k.eps);
   } else {
     const float a = k.state[idx] + (acc - k.state[idx]) * (1.f - k.beta1);
     const float v = k.state2[idx] + (acc * acc - k.state2[idx]) * (1.f - k.beta2);
     k.state[idx] = a;
     k.state2[idx] = v;
-    w -= k.lr * a / (sqrtf(v) + k.eps);
+    w -= lr * a / (sqrtf(v) + k.eps);
   }
   out[idx] = from_f32<T>(w);
 }
@@ -1480,17 +1487,66 @@ extern "C" int trs_scatter_rows(const void* g_rows, int64_t g_rows_batch_stride,
                            perm, BN, V, E, N, dtype, padding_row, grad_table, workspace, ws_bytes, stream);
 }
 
+// the three fused-optimizer entries and their *_dev twins share these: ``lr_dev`` (device fp32, may be NULL) replaces ``lr``
+static int update_impl(const char* who, float lr, const float* lr_dev, const void* g_rows, int64_t g_rows_batch_stride,
+                       const void* g_fm, int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start,
+                       const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                       int64_t padding_row, int32_t optimizer, float eps, float* state, void* workspace, size_t ws_bytes,
+                       trs_stream_t stream) {
+  TRS_REQUIRE(table, TRS_EINVAL, "%s: NULL table", who);
+  TRS_REQUIRE(optimizer == 1 || optimizer == 2, TRS_EINVAL, "%s: optimizer %d (1 = SGD, 2 = Adagrad)", who, optimizer);
+  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: Adagrad needs the state buffer", who);
+  RowSink sink{optimizer, lr, eps, state};
+  sink.lr_dev = lr_dev;
+  return scatter_rows_impl(sink, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN, V, E, N,
+                           dtype, padding_row, table, workspace, ws_bytes, stream);
+}
+
+static int update_adam_impl(const char* who, float step_size, const float* step_size_dev, const void* g_rows,
+                            int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols, const float* fm_sum,
+                            void* table, const int32_t* row_start, const int32_t* perm, int64_t BN, int64_t V, int32_t E,
+                            int32_t N, int32_t dtype, int64_t padding_row, float beta1, float beta2, float eps,
+                            float* exp_avg, float* exp_avg_sq, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(table && exp_avg && exp_avg_sq, TRS_EINVAL, "%s: NULL table / moment buffer", who);
+  TRS_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, TRS_EINVAL, "%s: betas (%g, %g) must be in [0, 1)",
+              who, (double)beta1, (double)beta2);
+  RowSink sink{3, step_size, eps, exp_avg};
+  sink.beta1 = beta1;
+  sink.beta2 = beta2;
+  sink.state2 = exp_avg_sq;
+  sink.lr_dev = step_size_dev;
+  return scatter_rows_impl(sink, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN, V, E, N, dtype,
+                           padding_row, table, workspace, ws_bytes, stream);
+}
+
+static int update_mapped_impl(const char* who, float lr, const float* lr_dev, const void* g_rows, void* table,
+                              const int32_t* row_map, const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
+                              int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float eps, float beta1, float beta2,
+                              float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(g_rows && table && row_map, TRS_EINVAL, "%s: NULL pointer", who);
+  TRS_REQUIRE(optimizer >= 1 && optimizer <= 3, TRS_EINVAL, "%s: optimizer %d", who, optimizer);
+  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: missing optimizer state", who);
+  TRS_REQUIRE(optimizer != 3 || state2 != nullptr, TRS_EINVAL, "%s: Adam needs both moments", who);
+  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
+  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
+  RowSink sink{optimizer, lr, eps, state};
+  sink.map_rows = V;
+  sink.beta1 = beta1;
+  sink.beta2 = beta2;
+  sink.state2 = state2;
+  sink.row_map = row_map;
+  sink.lr_dev = lr_dev;
+  return scatter_rows_impl(sink, g_rows, 0, nullptr, 0, nullptr, table, row_start, perm, K, U, E, 1, dtype, -1, table,
+                           workspace, ws_bytes, stream);
+}
+
 extern "C" int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
                                        const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
                                        int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
                                        int32_t optimizer, float lr, float eps, float* state, void* workspace,
                                        size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(table, TRS_EINVAL, "scatter_rows_update: NULL table");
-  TRS_REQUIRE(optimizer == 1 || optimizer == 2, TRS_EINVAL, "scatter_rows_update: optimizer %d (1 = SGD, 2 = Adagrad)",
-              optimizer);
-  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "scatter_rows_update: Adagrad needs the state buffer");
-  return scatter_rows_impl(RowSink{optimizer, lr, eps, state}, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table,
-                           row_start, perm, BN, V, E, N, dtype, padding_row, table, workspace, ws_bytes, stream);
+  return update_impl("scatter_rows_update", lr, nullptr, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table,
+                     row_start, perm, BN, V, E, N, dtype, padding_row, optimizer, eps, state, workspace, ws_bytes, stream);
 }
 
 extern "C" int trs_scatter_rows_update_adam(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
@@ -1499,15 +1555,9 @@ extern "C" int trs_scatter_rows_update_adam(const void* g_rows, int64_t g_rows_b
                                             int32_t dtype, int64_t padding_row, float step_size, float beta1,
                                             float beta2, float eps, float* exp_avg, float* exp_avg_sq, void* workspace,
                                             size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(table && exp_avg && exp_avg_sq, TRS_EINVAL, "scatter_rows_update_adam: NULL table / moment buffer");
-  TRS_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, TRS_EINVAL,
-              "scatter_rows_update_adam: betas (%g, %g) must be in [0, 1)", (double)beta1, (double)beta2);
-  RowSink sink{3, step_size, eps, exp_avg};
-  sink.beta1 = beta1;
-  sink.beta2 = beta2;
-  sink.state2 = exp_avg_sq;
-  return scatter_rows_impl(sink, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN, V, E, N, dtype,
-                           padding_row, table, workspace, ws_bytes, stream);
+  return update_adam_impl("scatter_rows_update_adam", step_size, nullptr, g_rows, g_rows_batch_stride, g_fm, g_fm_cols,
+                          fm_sum, table, row_start, perm, BN, V, E, N, dtype, padding_row, beta1, beta2, eps, exp_avg,
+                          exp_avg_sq, workspace, ws_bytes, stream);
 }
 
 /* see include/trs_abi.h: the fused sparse optimizer step on a COMPACT list of distinct rows */
@@ -1516,18 +1566,63 @@ extern "C" int trs_scatter_rows_update_mapped(const void* g_rows, void* table, c
                                               int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float lr, float eps,
                                               float beta1, float beta2, float* state, float* state2, void* workspace,
                                               size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(g_rows && table && row_map, TRS_EINVAL, "scatter_rows_update_mapped: NULL pointer");
-  TRS_REQUIRE(optimizer >= 1 && optimizer <= 3, TRS_EINVAL, "scatter_rows_update_mapped: optimizer %d", optimizer);
-  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "scatter_rows_update_mapped: missing optimizer state");
-  TRS_REQUIRE(optimizer != 3 || state2 != nullptr, TRS_EINVAL, "scatter_rows_update_mapped: Adam needs both moments");
-  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "scatter_rows_update_mapped: bad row counts");
-  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
-  RowSink sink{optimizer, lr, eps, state};
-  sink.map_rows = V;
-  sink.beta1 = beta1;
-  sink.beta2 = beta2;
-  sink.state2 = state2;
-  sink.row_map = row_map;
-  return scatter_rows_impl(sink, g_rows, 0, nullptr, 0, nullptr, table, row_start, perm, K, U, E, 1, dtype, -1, table,
-                           workspace, ws_bytes, stream);
+  return update_mapped_impl("scatter_rows_update_mapped", lr, nullptr, g_rows, table, row_map, row_start, perm, K, U, V, E,
+                            dtype, optimizer, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream);
+}
+
+/* ---- the same three entries with the step size read from DEVICE memory (see include/trs_abi.h) ---- */
+extern "C" int trs_scatter_rows_update_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
+                                           int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start,
+                                           const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                                           int64_t padding_row, int32_t optimizer, const float* lr_dev, float eps,
+                                           float* state, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(lr_dev, TRS_EINVAL, "scatter_rows_update_dev: NULL lr_dev");
+  return update_impl("scatter_rows_update_dev", 0.f, lr_dev, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table,
+                     row_start, perm, BN, V, E, N, dtype, padding_row, optimizer, eps, state, workspace, ws_bytes, stream);
+}
+
+extern "C" int trs_scatter_rows_update_adam_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
+                                                int32_t g_fm_cols, const float* fm_sum, void* table,
+                                                const int32_t* row_start, const int32_t* perm, int64_t BN, int64_t V,
+                                                int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                                                const float* step_size_dev, float beta1, float beta2, float eps,
+                                                float* exp_avg, float* exp_avg_sq, void* workspace, size_t ws_bytes,
+                                                trs_stream_t stream) {
+  TRS_REQUIRE(step_size_dev, TRS_EINVAL, "scatter_rows_update_adam_dev: NULL step_size_dev");
+  return update_adam_impl("scatter_rows_update_adam_dev", 0.f, step_size_dev, g_rows, g_rows_batch_stride, g_fm, g_fm_cols,
+                          fm_sum, table, row_start, perm, BN, V, E, N, dtype, padding_row, beta1, beta2, eps, exp_avg,
+                          exp_avg_sq, workspace, ws_bytes, stream);
+}
+
+extern "C" int trs_scatter_rows_update_mapped_dev(const void* g_rows, void* table, const int32_t* row_map,
+                                                  const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
+                                                  int64_t V, int32_t E, int32_t dtype, int32_t optimizer,
+                                                  const float* lr_dev, float eps, float beta1, float beta2, float* state,
+                                                  float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(lr_dev, TRS_EINVAL, "scatter_rows_update_mapped_dev: NULL lr_dev");
+  return update_mapped_impl("scatter_rows_update_mapped_dev", 0.f, lr_dev, g_rows, table, row_map, row_start, perm, K, U, V,
+                            E, dtype, optimizer, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream);
+}
+
+namespace trs {
+// Adam's per-step scalars on the device, one thread: t += 1; step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t).  In double
+// (1 - 0.999^t in fp32 loses four digits at small t), one rounding to fp32 on store -- what the host-side path passes by value.
+__global__ void adam_step_size_kernel(int64_t* __restrict__ step, const float* __restrict__ lr_dev, double beta1,
+                                      double beta2, float* __restrict__ step_size) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t t = *step + 1;
+  *step = t;
+  const double c2 = 1.0 - pow(beta2, (double)t), c1 = 1.0 - pow(beta1, (double)t);
+  *step_size = (float)((double)*lr_dev * sqrt(c2) / c1);
+}
+}  // namespace trs
+
+extern "C" int trs_adam_step_size(int64_t* step, const float* lr_dev, double beta1, double beta2, float* step_size_dev,
+                                  trs_stream_t stream) {
+  TRS_REQUIRE(step && lr_dev && step_size_dev, TRS_EINVAL, "adam_step_size: NULL pointer");
+  TRS_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, TRS_EINVAL,
+              "adam_step_size: betas (%g, %g) must be in [0, 1)", beta1, beta2);
+  hipLaunchKernelGGL(adam_step_size_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, lr_dev, beta1, beta2,
+                     step_size_dev);
+  return check_launch("adam_step_size");
 }

@@ -18,7 +18,10 @@ into ``world`` contiguous ranges; every rank keeps its local batch (data paralle
             sparse=False default).
 
 With ``set_fused_optimizer(opt)`` the owner applies the optimizer step to the rows it received gradients for inside
-the backward pass (no gradient tensor at all: the mandatory mode for 125 M-row shards).
+the backward pass (no gradient tensor at all: the mandatory mode for 125 M-row shards).  Shards above
+``dense_grad_max_rows`` find the distinct rows they received with a device-side hash table of fixed shape
+(``functional.compact_rows_dense``): no sort, no host read, so the step is capturable at any shard size.  (``dedup=True`` routing
+keeps its torch.unique, and a large shard without a fused optimizer its uncoalesced sparse gradient.)
 ``dedup=True`` sends every distinct row id of the local batch once (torch.unique before the exchange): the block is
 rebuilt from the distinct rows and the gradients of duplicate lookups are summed before they travel -- pays on skewed
 (Zipf) data, costs a sort on uniform data, default off.  A process group of one rank takes no collective and no host
@@ -70,7 +73,7 @@ OWNER_PREFETCH = __import__("os").environ.get("TRS_SHARD_PREFETCH", "auto")
 
 class HipOps:
     """Device-side pieces of the sharded lookup, on libtrs_hip.so."""
-    _uniq_cache = None      # (key, ids kept alive, distinct ids, inverse) of the last compact-row optimizer step
+    _uniq_cache = None      # (key, ids kept alive, row_map, inv, event, stream) of the last compact-row optimizer step
 
     def bucket_by_owner(self, idx: torch.Tensor, offsets: torch.Tensor, rows_per_rank: int, world: int):
         require_device(idx, offsets)
@@ -141,26 +144,32 @@ class HipOps:
                 rb = F_.row_buckets(ids.view(-1, 1), None, weight.shape[0], check=not padded)
                 F_.scatter_rows_update(rb, weight.data, opt, g_rows=grad_rows.contiguous(), key=weight)
             else:
-                # the distinct touched rows of this step: shared by every table looked up with the same indices (the
-                # E = 64 table and its E = 1 companion receive the same owner ids: one sort instead of two)
+                # The distinct touched rows of this step, compacted on the device (functional.compact_rows_dense): a
+                # hash table of fixed shape whose occupied slots are numbered densely.  No sort and nothing read on the
+                # host, so the step stays capturable.  One compaction serves every table looked up with the same
+                # indices (the E = 64 table and its E = 1 companion receive the same owner ids).
                 key = (ids.data_ptr(), ids._version, ids.numel())
                 cur = torch.cuda.current_stream(ids.device)
                 hit = HipOps._uniq_cache if HipOps._uniq_cache is not None and HipOps._uniq_cache[0] == key else None
                 if hit is None:
-                    uniq, inv = torch.unique(ids, return_inverse=True)
-                    inv32 = inv.to(torch.int32).view(-1, 1)
+                    row_map, inv = F_.compact_rows_dense(ids if ids.dtype == torch.int32 else ids.to(torch.int32))
                     ev = torch.cuda.Event()
                     ev.record(cur)
-                    HipOps._uniq_cache = hit = (key, ids, uniq, inv32, ev, cur)
-                _, _, uniq, inv32, ev, made_on = hit
+                    HipOps._uniq_cache = hit = (key, ids, row_map, inv.view(-1, 1), ev, cur)
+                _, _, row_map, inv, ev, made_on = hit
                 if cur != made_on:        # the companion table's backward may run on the "lookup" side stream
                     cur.wait_event(ev)
-                    uniq.record_stream(cur)
-                    inv32.record_stream(cur)
-                rb = F_.row_buckets(inv32, None, uniq.numel())
-                # ids outside the shard (the lookup read them as zero rows and raised the index flag) stay in ``uniq``:
-                # trs_scatter_rows_update_mapped skips row_map entries outside [0, V), so they update nothing
-                F_.scatter_rows_update_mapped(rb, weight.data, opt, grad_rows, uniq.to(torch.int32), key=weight)
+                    row_map.record_stream(cur)
+                    inv.record_stream(cur)
+                # The bucketed row space is K + 1 rows with the distinct ids in front.  (Over the T + 1 >= 2K + 1 hash
+                # slots themselves the build and the walk cost 0.3 ms more per step: profiles/capturable_optimizer.md.)
+                # Rows behind the distinct ids, row K included, have the key -1; padding (-1) maps to row K.
+                # Ids outside the shard keep a row (the lookup read them as zero rows and raised the index flag).
+                # trs_scatter_rows_update_mapped skips row_map entries outside [0, V), so neither updates anything.
+                # With ``padded`` the padding positions are left out of the index altogether: filed under row K they
+                # would be one returning atomic per position on a single counter (see trs_csr_build_skip).
+                rb = F_.row_buckets(inv, None, row_map.numel(), skip_row=row_map.numel() - 1 if padded else None)
+                F_.scatter_rows_update_mapped(rb, weight.data, opt, grad_rows, row_map, key=weight)
 
     def prefetch_owner_buckets(self, weight: torch.Tensor, ids: torch.Tensor, padded: bool = False,
                                pipelined: bool = False) -> None:
@@ -831,7 +840,7 @@ class _ShardedLookup(Function):
         if mod.fused_optimizer is not None:
             # the owner steps its rows right here: no gradient tensor of any kind (weight.grad stays None); small shards
             # through a bucket index over all their rows, large ones through the compact list of distinct touched rows
-            # (torch.unique, a sort of the B*N ids)
+            # (functional.compact_rows_dense, a device-side hash table of fixed shape)
             ops.shard_update(weight, ids, rows, mod.fused_optimizer, weight.shape[0] <= mod.dense_index_max_rows, **pad_kw)
             return None
         if dense_index:
@@ -958,7 +967,9 @@ class RowShardedMultiIndicesEmbedding(BaseInput):
         # fused optimizer: shards up to this many rows are stepped through a bucket index over ALL their rows, larger ones
         # through the compact list of distinct touched rows (_owner_reduce).  TRS_SHARD_DENSE_INDEX_ROWS raises the limit;
         # measured at 125 M rows (round 6, one rank, Adagrad): index over all rows 6.37 ms per step (owner update 2.85 ms:
-        # zero + scan + walk over 125 M mostly empty rows), compact rows 3.04 ms (0.89 ms) -- the default stays
+        # zero + scan + walk over 125 M mostly empty rows), compact rows found by torch.unique 3.04 ms (0.89 ms); the
+        # device-side compaction that replaced torch.unique keeps the owner update at 0.90 ms
+        # (profiles/capturable_optimizer.md) -- the default stays
         self.dense_index_max_rows = max(int(dense_grad_max_rows), int(__import__("os").environ.get(
             "TRS_SHARD_DENSE_INDEX_ROWS", "0"))) if dense_grad_max_rows > 0 else 0
         self.register_buffer('offsets_local', self.offsets - self.row_range[0], persistent=False)

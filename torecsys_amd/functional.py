@@ -364,17 +364,36 @@ def scatter_rows_first(rb: RowBuckets, like_table: torch.Tensor, like_first: tor
     return grad, gfirst
 
 
+def _adam_step_dev(opt, table: torch.Tensor, key) -> torch.Tensor:
+    """capturable Adam: advance the table's device step counter and refresh its bias-corrected step size (one thread,
+    trs_adam_step_size), in front of the update on the same stream; returns the step-size scalar the update reads"""
+    step, step_size = opt.step_tensors(table, key)
+    call("trs_adam_step_size", ptr(step), ptr(opt.lr_tensor(table.device)), float(opt.beta1), float(opt.beta2),
+         ptr(step_size), stream_ptr())
+    return step_size
+
+
 def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
                         g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
                         padding_row: int = -1, key=None) -> None:
     """Fused sparse optimizer step: the bucketed gradient of every looked-up row is applied to ``table`` in
-    place (see trs_scatter_rows_update); no gradient tensor is produced."""
+    place (see trs_scatter_rows_update); no gradient tensor is produced.  A ``capturable`` optimizer goes through the
+    ``_dev`` entries, which read the step size from device memory (eagerly and under capture alike)."""
     V, E = table.shape
     if not table.is_contiguous():
         raise ValueError("fused optimizer needs a contiguous table")
+    capturable = getattr(opt, "capturable", False)
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, rb.N, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
     if opt.kind == 3:
+        if capturable:
+            m1, m2 = opt.state_for(table, key)
+            step_size = _adam_step_dev(opt, table, key)
+            call("trs_scatter_rows_update_adam_dev", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum),
+                 ptr(table), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
+                 ptr(step_size), float(opt.beta1), float(opt.beta2), float(opt.eps), ptr(m1), ptr(m2), ptr(ws), ws_bytes,
+                 stream_ptr())
+            return
         if torch.cuda.is_current_stream_capturing():
             # the bias-corrected step size lr*sqrt(1-b2^t)/(1-b1^t) is computed on the host per step and passed by
             # value: a captured launch would replay the capture-time t for ever (~0.18*lr with default betas)
@@ -388,6 +407,11 @@ def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Option
              float(opt.beta1), float(opt.beta2), float(opt.eps), ptr(m1), ptr(m2), ptr(ws), ws_bytes, stream_ptr())
         return
     state = opt.state_for(table, key)
+    if capturable:
+        call("trs_scatter_rows_update_dev", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
+             ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row, opt.kind,
+             ptr(opt.lr_tensor(table.device)), float(opt.eps), ptr(state), ptr(ws), ws_bytes, stream_ptr())
+        return
     call("trs_scatter_rows_update", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
          ptr(rb.row_start),
          ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row, opt.kind, float(opt.lr), float(opt.eps),
@@ -398,25 +422,81 @@ def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows:
                                key=None):
     """Fused sparse optimizer step where the bucketed rows are a compact list of distinct table rows:
     ``rb`` buckets the K rows of ``g_rows`` by compact row u (rb.V = U), ``row_map[u]`` (int32, distinct) is the table
-    row that u updates.  See trs_scatter_rows_update_mapped."""
+    row that u updates; entries outside [0, V) -- the empty slots of ``compact_rows`` -- update nothing.  See
+    trs_scatter_rows_update_mapped (``capturable`` optimizers: trs_scatter_rows_update_mapped_dev)."""
     V, E = table.shape
     if not table.is_contiguous():
         raise ValueError("fused optimizer needs a contiguous table")
     if row_map.dtype != torch.int32 or row_map.numel() != rb.V:
         raise ValueError("row_map must be int32 with one entry per bucketed row")
+    capturable = getattr(opt, "capturable", False)
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, 1, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
     lr, st1, st2, b1, b2 = float(opt.lr), None, None, 0.0, 0.0
+    lr_dev = opt.lr_tensor(table.device) if capturable else None
     if opt.kind == 3:
-        if torch.cuda.is_current_stream_capturing():
+        if not capturable and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("torecsys_amd: FusedSparseAdam cannot be captured into a hipGraph")
         st1, st2 = opt.state_for(table, key)
-        lr, b1, b2 = float(opt.next_step_size(table, key)), float(opt.beta1), float(opt.beta2)
+        b1, b2 = float(opt.beta1), float(opt.beta2)
+        if capturable:
+            lr_dev = _adam_step_dev(opt, table, key)
+        else:
+            lr = float(opt.next_step_size(table, key))
     elif opt.kind == 2:
         st1 = opt.state_for(table, key)
+    if capturable:
+        call("trs_scatter_rows_update_mapped_dev", ptr(g_rows.contiguous()), ptr(table), ptr(row_map), ptr(rb.row_start),
+             ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), opt.kind, ptr(lr_dev), float(opt.eps), b1, b2,
+             ptr(st1), ptr(st2), ptr(ws), ws_bytes, stream_ptr())
+        return
     call("trs_scatter_rows_update_mapped", ptr(g_rows.contiguous()), ptr(table), ptr(row_map), ptr(rb.row_start),
          ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), opt.kind, lr, float(opt.eps), b1, b2, ptr(st1), ptr(st2),
          ptr(ws), ws_bytes, stream_ptr())
+
+
+def compact_rows(ids: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Distinct rows of ``ids`` (K int32 row ids with repeats; negative = padding) without a sort or a host read:
+    ``row_map`` (T + 1 int32, T = the smallest power of two >= 2K) holds every id >= 0 in exactly one slot and -1 in the
+    others, ``inv`` (K int32) the slot of every position (T, whose key is -1, for negative ids).  Shapes depend on K
+    alone; which slot an id gets is unspecified.  ``out``: (row_map, inv) buffers of those shapes to write into.  See
+    trs_compact_rows."""
+    require_device(ids)
+    if ids.dtype != torch.int32:
+        raise TypeError(f"compact_rows: ids must be int32, got {ids.dtype}")
+    ids = ids.reshape(-1).contiguous()
+    K = ids.numel()
+    T = size_query("trs_compact_rows_slots", K)
+    if out is not None:
+        row_map, inv = out
+        require_device(ids, row_map, inv)
+        if (row_map.dtype != torch.int32 or inv.dtype != torch.int32 or row_map.numel() != T + 1 or inv.numel() != K
+                or not row_map.is_contiguous() or not inv.is_contiguous()):
+            raise ValueError(f"compact_rows: out must be contiguous int32 tensors of {T + 1} and {K} elements")
+    else:
+        row_map = torch.empty(T + 1, dtype=torch.int32, device=ids.device)
+        inv = torch.empty(K, dtype=torch.int32, device=ids.device)
+    call("trs_compact_rows", ptr(ids), K, ptr(row_map), T, ptr(inv), stream_ptr())
+    return row_map, inv
+
+
+def compact_rows_dense(ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``compact_rows`` with the U distinct ids numbered densely: ``dense_map`` (K + 1 int32) holds them in rows
+    [0, U) and -1 behind (row K included), ``inv`` (K int32) the row of every position (K for negative ids).  The row
+    space a bucket build / walk behind it covers is K + 1 instead of the T + 1 >= 2K + 1 hash slots; U is not read
+    back.  See trs_compact_rows_dense."""
+    require_device(ids)
+    if ids.dtype != torch.int32:
+        raise TypeError(f"compact_rows_dense: ids must be int32, got {ids.dtype}")
+    ids = ids.reshape(-1).contiguous()
+    K = ids.numel()
+    dense_map = torch.empty(K + 1, dtype=torch.int32, device=ids.device)
+    inv = torch.empty(K, dtype=torch.int32, device=ids.device)
+    ws_bytes = size_query("trs_compact_rows_dense_workspace_bytes", K)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=ids.device)
+    call("trs_compact_rows_dense", ptr(ids), K, ptr(dense_map), ptr(inv), ptr(ws), ws_bytes, stream_ptr())
+    return dense_map, inv
 
 
 def _apply_or_grad(rb, weight, opt, key=None, **kw):

@@ -11,11 +11,15 @@ stream that builds the row buckets forks from and joins the capturing stream).
         loss = step(idx, label)        # copies the batch into the static buffers, replays
 
 The callable must be shape-static and must not branch on tensor values.  Scalars passed by value to kernels (the
-learning rate of a fused sparse optimizer) are frozen at capture time; call ``recapture()`` after changing them.
-``FusedSparseAdam`` refuses to be captured: its bias-corrected step size changes every step and is a host scalar
-(FusedSparseSGD / FusedSparseAdagrad have no per-step host state and capture fine).
+learning rate of a default fused sparse optimizer) are frozen at capture time; call ``recapture()`` after changing them.
+A default ``FusedSparseAdam`` refuses to be captured: its bias-corrected step size changes every step and is a host scalar.
+``FusedSparse{SGD,Adagrad,Adam}(..., capturable=True)`` keep the learning rate -- and Adam its step count and step size --
+on the device: replays advance them, ``set_lr()`` between replays needs no ``recapture()``.  Their state tensors are
+re-created by ``load_state_dict``: ``recapture()`` after loading a checkpoint into an optimizer a graph was captured with.
 The row-sharded multi-GPU lookup is capturable where it reads nothing on the host: one rank, or fixed-capacity slots
-(``RowShardedMultiIndicesEmbedding(capacity=...)``: equal all-to-all splits); with exact split sizes it stays eager.
+(``RowShardedMultiIndicesEmbedding(capacity=...)``: equal all-to-all splits); with exact split sizes it stays eager.  Its
+owner-side fused optimizer step is capturable at any shard size (large shards compact the touched rows on the device);
+``dedup=True`` routing (torch.unique) is not.
 """
 from typing import Callable, Iterable, Optional, Sequence
 

@@ -12,6 +12,12 @@ without ever forming the dense gradient or sweeping the table.  The other parame
 State (Adagrad accumulators, Adam moments and step counts) is kept per table, keyed by the ``nn.Parameter`` object, so
 it follows ``module.to(...)`` (the state tensors move to the table's device on the next step) and can be saved /
 restored with ``state_dict(named_parameters)`` / ``load_state_dict(sd, named_parameters)``.
+
+``capturable=True`` keeps what changes from step to step on the DEVICE, so a step captured into a hipGraph
+(``graph.GraphedStep``) stays correct over its replays: the learning rate is a one-element fp32 tensor that ``set_lr()``
+writes (replays see the new value, no ``recapture()``), and Adam keeps a per-table step counter (int64) and its
+bias-corrected step size there, advanced by a one-thread kernel in front of every update.  Eager and replayed steps of a
+capturable optimizer run the same kernels.  The default (``capturable=False``) passes these scalars by value, as before.
 """
 from __future__ import annotations
 
@@ -24,11 +30,44 @@ class _FusedSparse:
     kind = 0
     _buffers: Tuple[str, ...] = ()          # names of the per-table fp32 state tensors
 
-    def __init__(self, lr: float, eps: float = 0.0):
+    def __init__(self, lr: float, eps: float = 0.0, capturable: bool = False):
         if lr < 0:
             raise ValueError(f"invalid learning rate {lr}")
+        if not isinstance(capturable, bool):
+            raise TypeError(f"capturable must be a bool, got {type(capturable).__name__}")
         self.lr, self.eps = float(lr), float(eps)
+        self._capturable = capturable
+        self._lr_dev: Dict[torch.device, torch.Tensor] = {}      # capturable: the learning rate, one fp32 per device
         self._state: Dict[object, dict] = {}
+
+    @property
+    def capturable(self) -> bool:
+        return self._capturable
+
+    # ---- learning rate ---------------------------------------------------------------------------------
+    def set_lr(self, lr: float) -> None:
+        """Change the learning rate.  Capturable optimizers write it into their device scalar (a ``fill_`` on the
+        current stream: call it between replays, not inside a capture); captured steps read the new value."""
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)):
+            raise TypeError(f"learning rate must be a number, got {type(lr).__name__}")
+        if not lr >= 0:
+            raise ValueError(f"invalid learning rate {lr}")
+        self.lr = float(lr)
+        for t in self._lr_dev.values():
+            t.fill_(self.lr)
+
+    def lr_tensor(self, device) -> torch.Tensor:
+        """the device-resident learning rate of a capturable optimizer (created on first use, outside any capture)"""
+        if not self._capturable:
+            raise RuntimeError("lr_tensor: the optimizer was not built with capturable=True")
+        device = torch.device(device)
+        t = self._lr_dev.get(device)
+        if t is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("torecsys_amd: a capturable fused optimizer met a table on a new device inside a "
+                                   "capture; run one eager step first (GraphedStep's warm-up does)")
+            t = self._lr_dev[device] = torch.full((1,), self.lr, dtype=torch.float32, device=device)
+        return t
 
     # ---- per-table state -------------------------------------------------------------------------------
     def _init_value(self, name: str) -> float:
@@ -47,7 +86,23 @@ class _FusedSparse:
                 st[name] = torch.full(table.shape, self._init_value(name), dtype=torch.float32, device=table.device)
             elif t.device != table.device:
                 st[name] = t.to(table.device)
+        for name, dtype in self._scalars:
+            t = st.get(name)
+            if t is None:
+                st[name] = torch.full((1,), st["step"] if name == "step_dev" else 0, dtype=dtype, device=table.device)
+            elif t.device != table.device:
+                st[name] = t.to(table.device)
         return st
+
+    @property
+    def _scalars(self) -> Tuple[tuple, ...]:
+        """(name, dtype) of the per-table one-element device tensors of a capturable optimizer"""
+        return ()
+
+    @staticmethod
+    def _step_of(st: dict) -> int:
+        # a capturable Adam counts on the device: one host read per table, at checkpoint time only
+        return int(st["step_dev"].item()) if "step_dev" in st else int(st["step"])
 
     def state_for(self, table: torch.Tensor, key=None):
         return None
@@ -60,13 +115,17 @@ class _FusedSparse:
         tables = {}
         for i, (k, st) in enumerate(self._state.items()):
             name = names.get(k if isinstance(k, int) else None, f"table{i}")
-            tables[name] = {"step": st["step"], **{b: st[b].detach().clone() for b in self._buffers if b in st}}
-        return {"hyper": {k: v for k, v in self.__dict__.items() if isinstance(v, (int, float))}, "tables": tables}
+            tables[name] = {"step": self._step_of(st), **{b: st[b].detach().clone() for b in self._buffers if b in st}}
+        return {"hyper": {k: v for k, v in self.__dict__.items()
+                          if isinstance(v, (int, float)) and not isinstance(v, bool)}, "tables": tables}
 
     def load_state_dict(self, sd: dict, named_parameters: Iterable) -> None:
+        """State tensors (a capturable Adam's device step counter included) are re-created: a graph captured before the
+        load still points at the old ones and must be ``recapture()``d."""
         params = dict(named_parameters)
         for k, v in sd.get("hyper", {}).items():
             setattr(self, k, v)
+        self.set_lr(self.lr)          # a capturable optimizer's device scalar follows the loaded learning rate
         for name, entry in sd.get("tables", {}).items():
             if name not in params:
                 raise KeyError(f"load_state_dict: no parameter named {name!r}")
@@ -90,8 +149,9 @@ class FusedSparseAdagrad(_FusedSparse):
     kind = 2
     _buffers = ("sum",)
 
-    def __init__(self, lr: float = 1e-2, eps: float = 1e-10, initial_accumulator_value: float = 0.0):
-        super().__init__(lr, eps)
+    def __init__(self, lr: float = 1e-2, eps: float = 1e-10, initial_accumulator_value: float = 0.0,
+                 capturable: bool = False):
+        super().__init__(lr, eps, capturable)
         self.initial = float(initial_accumulator_value)
 
     def _init_value(self, name: str) -> float:
@@ -108,8 +168,8 @@ class FusedSparseAdam(_FusedSparse):
     kind = 3
     _buffers = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
-        super().__init__(lr, eps)
+    def __init__(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, capturable: bool = False):
+        super().__init__(lr, eps, capturable)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"invalid betas {betas}")
         self.beta1, self.beta2 = float(betas[0]), float(betas[1])
@@ -118,7 +178,18 @@ class FusedSparseAdam(_FusedSparse):
         st = self._entry(table, key)
         return st["exp_avg"], st["exp_avg_sq"]
 
+    @property
+    def _scalars(self):
+        return (("step_dev", torch.int64), ("step_size_dev", torch.float32)) if self._capturable else ()
+
+    def step_tensors(self, table: torch.Tensor, key=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """capturable: the table's device step counter (int64) and bias-corrected step size (fp32), one element each"""
+        st = self._entry(table, key)
+        return st["step_dev"], st["step_size_dev"]
+
     def next_step_size(self, table: torch.Tensor, key=None) -> float:
+        if self._capturable:
+            raise RuntimeError("next_step_size: a capturable FusedSparseAdam steps on the device (trs_adam_step_size)")
         st = self._entry(table, key)
         st["step"] += 1
         t = st["step"]
