@@ -751,6 +751,28 @@ int trs_senet_scale_fwd(const void* x, const float* a, int64_t B, int32_t M, int
 int trs_senet_scale_bwd(const void* x, const void* g, const float* a, const float* gz, int64_t B, int32_t M, int32_t E,
                         int32_t dtype, float* ga, void* dx, trs_stream_t stream);
 
+/* ---- mixture-of-experts gating (MoE / MMoE) ----------------------------------------------------------------------------
+ *   z[b,g,:] = logits[b,g,:] + bias[g,:];  p = softmax_K(z) (row maximum subtracted);  out[b,g,k] = p[b,g,k] * experts[b,k]
+ * logits (B, G*K) is the fp32 result of ONE GEMM of the (B, D) input with the G stacked gate weights (G*K, D), WITHOUT the
+ * bias; bias (G*K) or NULL, experts (B, K) -- the concatenated expert outputs -- and out (B, G, K) are of `dtype`.
+ * replaces G x (Linear + Softmax + unflatten), the cat to (B, G, K) and einsum('ik,ijk->ijk') of
+ *   torecsys/layers/ctr/mixture_of_experts.py:137-160.
+ * Backward: p is recomputed from the logits (nothing else is saved); with t = gout * experts:
+ *   glogits[b,g,k] = p (t - sum_k p t)   (B, G*K) of dtype -- the operand of the two gradient GEMMs and of the bias sum;
+ *   gexperts[b,k]  = sum_g gout[b,g,k] p[b,g,k]   (B, K) of dtype.
+ * Everything between the loads and the final stores is fp32; one pass per direction, no workspace, no atomics, a fixed
+ * summation order.  Rows of whole 16-byte vectors with K <= 1024 and 16-byte aligned pointers take the vector path (a
+ * lane group owns a sample for all gates; trs_moe_gate_vector_shape tells the shape half of that rule, a pure function);
+ * any other K >= 1 or alignment takes an element path.  B == 0 returns TRS_OK and touches nothing.
+ * trs_moe_gate_last_path: the branch the calling thread's last trs_moe_gate_fwd / _bwd launch took -- 0 none yet, 1 vector,
+ * 2 element (a host-side record set where the kernel is launched; for tests and diagnostics).                           */
+int trs_moe_gate_vector_shape(int32_t K, int32_t dtype);
+int trs_moe_gate_last_path(void);
+int trs_moe_gate_fwd(const float* logits, const void* bias, const void* experts, int64_t B, int32_t G, int32_t K,
+                     int32_t dtype, void* out, trs_stream_t stream);
+int trs_moe_gate_bwd(const float* logits, const void* bias, const void* experts, const void* gout, int64_t B, int32_t G,
+                     int32_t K, int32_t dtype, void* glogits, void* gexperts, trs_stream_t stream);
+
 /* ---- index staging: pack per-field columns into the (B,N) index matrix --------
  * out[b, c] = src_j[b * width_j + t]  for the c-th output column = column t of source j.
  * replaces the per-field unsqueeze + torch.cat of inputs/inputs.py:75-80 by one pass.

@@ -5,7 +5,9 @@ on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtyp
 --what senet: the SENET / compose-excitation layer, both kernel families, against the ATen composition of the same module
 (own inputs, see bench_senet).
 --what compact [--shard-rows 125000000]: device-side row compaction against torch.unique, and the owner-side fused update
-of a large shard through either (own inputs, see bench_compact)."""
+of a large shard through either (own inputs, see bench_compact).
+--what moe: the gate part of MixtureOfExpertsLayer against the ATen composition of the same module, the two gate kernels
+alone, and the experts' share of the whole layer (own inputs, see bench_moe)."""
 import argparse
 import os
 import sys
@@ -262,6 +264,121 @@ def bench_compact(a):
                   flush=True)
 
 
+def bench_moe(a):
+    """MixtureOfExpertsLayer (csrc/moe.hip) at B = 65 536, D = 2496, 8 experts x 16 outputs (hidden layers 128, 64),
+    G = 4 gates, bf16 and fp32.  The gate part -- everything behind the concatenated expert outputs: the stacking of the
+    gate parameters, the GEMM, the kernel -- against the ATen composition of the SAME module (G x Linear + Softmax,
+    unflatten, cat, einsum: mixture_of_experts.py:137-160), forward under no_grad and forward + backward, the candidates
+    taking turns inside every round; every figure is the median over all rounds x iters timed launches (events on the
+    launch stream) after 10 warm-ups.  Then the two kernels alone against their algorithmic bytes, and the experts' share
+    of the whole layer's forward + backward."""
+    from torecsys_amd.layers import DNNLayer, MOELayer
+    dev = torch.device("cuda:0")
+    B, N, E, X, Oi, G = 65536, 39, 64, 8, 16, 4
+    D, K = N * E, X * Oi
+
+    def samples(fn, iters):
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s0, s1 in evs:
+            s0.record()
+            fn()
+            s1.record()
+        torch.cuda.synchronize()
+        return [s0.elapsed_time(s1) * 1e-3 for s0, s1 in evs]
+
+    def race(cands):
+        """{name: sorted seconds of rounds x iters launches}, 10 warm-ups each, the candidates taking turns"""
+        per = {name: [] for name, _ in cands}
+        for _, f in cands:
+            for _ in range(10):
+                f()
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for name, f in cands:
+                per[name] += samples(f, a.iters)
+        return {name: sorted(ts) for name, ts in per.items()}
+
+    def show(tag, name, ts, alg=None):
+        med = ts[len(ts) // 2]
+        extra = "" if alg is None else f"  {alg / med / 1e9:7.1f} GB/s = {alg / med / 8e12 * 100:5.1f}% of 8 TB/s on {alg / 1e6:.0f} MB (alg)"
+        print(f"{tag:22s} {name:26s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us "
+              f"({len(ts)} launches){extra}", flush=True)
+        return med
+
+    for dt in (torch.bfloat16, torch.float32):
+        s = 2 if dt == torch.bfloat16 else 4
+        name_dt = str(dt)[6:]
+        g = torch.Generator(device=dev).manual_seed(91)
+        torch.manual_seed(92)
+        m = MOELayer(inputs_size=D, output_size=K, num_experts=X, expert_func=DNNLayer, num_gates=G,
+                     expert_inputs_size=D, expert_output_size=Oi, expert_layer_sizes=[128, 64]).to(dev).to(dt)
+        x = torch.randn(B, N, E, generator=g, device=dev).to(dt).requires_grad_()
+        gout = torch.randn(B, G, K, generator=g, device=dev).to(dt)
+        x2 = x.detach().reshape(B, D).requires_grad_()
+        e = torch.randn(B, K, generator=g, device=dev).to(dt).requires_grad_()
+        linears = [gate.Linear for gate in m.gates.values()]
+        gate_params = [p for lin in linears for p in lin.parameters()]
+
+        def gate_hip():
+            return F_.moe_gate(x2, torch.cat([lin.weight for lin in linears]), torch.cat([lin.bias for lin in linears]), e)
+
+        def gate_aten():
+            w = torch.cat([torch.softmax(lin(x2), dim=1).unflatten(1, (1, K)) for lin in linears], dim=1)
+            return torch.einsum("ik,ijk->ijk", e, w)
+
+        def fwd_bwd(f, leaves):
+            def run():
+                for t in leaves:
+                    t.grad = None
+                f().backward(gout)
+            return run
+
+        with torch.no_grad():
+            d = float((gate_hip().float() - gate_aten().float()).abs().max())
+        print(f"moe B={B} D={D} experts {X} x {Oi} (K={K}) G={G} {name_dt}; max |HIP - ATen| of the gate part = {d:.3e}; "
+              f"{a.rounds} rounds x {a.iters} launches", flush=True)
+        cands = [("moe_gate (HIP)", gate_hip), ("composition (ATen)", gate_aten)]
+        with torch.no_grad():
+            for name, ts in race(cands).items():
+                show(f"gate {name_dt} fwd", name, ts)
+        leaves = [x2, e] + gate_params
+        for name, ts in race([(n, fwd_bwd(f, leaves)) for n, f in cands]).items():
+            show(f"gate {name_dt} fwd+bwd", name, ts)
+        # the two kernels alone
+        with torch.no_grad():
+            logits = torch.randn(B, G * K, generator=g, device=dev)
+            bias = torch.cat([lin.bias for lin in linears]).detach()
+            ed = e.detach()
+            res = race([("trs_moe_gate_fwd", lambda: F_.moe_gate_forward_raw(logits, bias, ed)),
+                        ("trs_moe_gate_bwd", lambda: F_.moe_gate_backward_raw(logits, bias, ed, gout))])
+            show(f"kernel {name_dt}", "trs_moe_gate_fwd", res["trs_moe_gate_fwd"], B * G * K * 4 + B * K * s + B * G * K * s)
+            show(f"kernel {name_dt}", "trs_moe_gate_bwd", res["trs_moe_gate_bwd"],
+                 B * G * K * (4 + s) + B * K * s + B * G * K * s + B * K * s)
+            del logits
+        # the experts' share of the whole layer
+        gk = torch.randn(B, K, generator=g, device=dev).to(dt)
+
+        def experts_only():
+            return torch.cat([ex(x2).rename(None) for ex in m.experts.values()], dim=1)
+
+        def layer():
+            for t in [x] + list(m.parameters()):
+                t.grad = None
+            m(x).rename(None).backward(gout)
+
+        def experts():
+            for t in [x2] + list(m.experts.parameters()):
+                t.grad = None
+            experts_only().backward(gk)
+
+        res = race([("whole layer", layer), ("experts alone", experts)])
+        t_layer = show(f"layer {name_dt} fwd+bwd", "whole layer", res["whole layer"])
+        t_exp = show(f"layer {name_dt} fwd+bwd", "experts alone (+ cat)", res["experts alone"])
+        print(f"layer {name_dt}: the experts take {t_exp / t_layer * 100:.0f}% of the layer's forward + backward", flush=True)
+        del m, x, x2, e, gout, gk
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -273,8 +390,8 @@ def main():
     ap.add_argument("--what", default="all")
     ap.add_argument("--L", type=int, default=50, help="bag: list length")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
-    ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact: alternating rounds")
-    ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact: timed launches per round")
+    ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe: alternating rounds")
+    ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact / moe: timed launches per round")
     ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
     a = ap.parse_args()
     if a.what == "compact":      # own inputs (a 125 M-row table and its Adagrad state): not part of "all"
@@ -283,6 +400,8 @@ def main():
         return bench_bag(a)
     if a.what == "senet":        # own inputs and modules: not part of "all"
         return bench_senet(a)
+    if a.what == "moe":          # own inputs and modules: not part of "all"
+        return bench_moe(a)
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     s = 2 if dt == torch.bfloat16 else 4
     dev = torch.device("cuda:0")

@@ -115,6 +115,10 @@ SIGNATURES = {
     "trs_senet_squeeze": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_senet_scale_fwd": (c_int32, [_P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_senet_scale_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "trs_moe_gate_vector_shape": (c_int32, [_I32, _I32]),
+    "trs_moe_gate_last_path": (c_int32, []),
+    "trs_moe_gate_fwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
+    "trs_moe_gate_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_bwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_dot_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

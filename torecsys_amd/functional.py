@@ -1697,6 +1697,111 @@ def senet_scale(x: torch.Tensor, a: torch.Tensor, link: Optional[SENetLink] = No
 
 
 # --------------------------------------------------------------------------------------------
+# Mixture-of-experts gating: out[b,g,k] = softmax_k(x W_g^T + b_g)[b,k] * experts[b,k]
+# --------------------------------------------------------------------------------------------
+MOE_GATE_MAX_K = 1024      # widest row of the kernels' vector path (moe.hip: 64 lanes x 16 columns); wider rows take the element path
+
+
+MOE_PATH_VECTOR, MOE_PATH_ELEMENT = 1, 2
+
+
+def moe_gate_last_path() -> int:
+    """The branch the last trs_moe_gate_fwd / _bwd launch of this thread took, as the library recorded it where it
+    launched: MOE_PATH_VECTOR, MOE_PATH_ELEMENT, or 0 before the first launch (tests and diagnostics)."""
+    return size_query("trs_moe_gate_last_path")
+
+
+def _moe_gate_operands(logits, bias, experts, gout=None):
+    for name, t in (("logits", logits), ("bias", bias), ("experts", experts), ("gout", gout)):
+        if t is not None and not t.is_contiguous():      # the entries read dense rows: a strided operand would be misread
+            raise ValueError(f"moe_gate: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+    require_device(logits, bias, experts, gout)
+    if logits.dim() != 2 or experts.dim() != 2 or logits.dtype != torch.float32 or logits.shape[0] != experts.shape[0]:
+        raise ValueError(f"moe_gate: fp32 logits (B, G*K) and experts (B, K) expected, got {tuple(logits.shape)} "
+                         f"{logits.dtype} and {tuple(experts.shape)}")
+    B, K = experts.shape
+    if K < 1 or logits.shape[1] < K or logits.shape[1] % K != 0:
+        raise ValueError(f"moe_gate: logits of width {logits.shape[1]} are not G rows of K = {K} expert outputs")
+    G = logits.shape[1] // K
+    if bias is not None and (tuple(bias.shape) != (G * K,) or bias.dtype != experts.dtype):
+        raise ValueError(f"moe_gate: bias ({G * K},) of {experts.dtype} expected, got {tuple(bias.shape)} {bias.dtype}")
+    if gout is not None and (tuple(gout.shape) != (B, G, K) or gout.dtype != experts.dtype):
+        raise ValueError(f"moe_gate: output gradient ({B}, {G}, {K}) of {experts.dtype} expected, got "
+                         f"{tuple(gout.shape)} {gout.dtype}")
+    return B, G, K
+
+
+def moe_gate_forward_raw(logits: torch.Tensor, bias: Optional[torch.Tensor], experts: torch.Tensor) -> torch.Tensor:
+    """trs_moe_gate_fwd as it is (no autograd): fp32 logits (B, G*K) WITHOUT bias, bias (G*K) or None, experts (B, K)
+    -> (B, G, K) of the experts' dtype.  A non-contiguous operand raises ValueError."""
+    B, G, K = _moe_gate_operands(logits, bias, experts)
+    out = torch.empty(B, G, K, dtype=experts.dtype, device=experts.device)
+    call("trs_moe_gate_fwd", ptr(logits), ptr(bias), ptr(experts), B, G, K, value_dtype_code(experts), ptr(out),
+         stream_ptr())
+    return out
+
+
+def moe_gate_backward_raw(logits: torch.Tensor, bias: Optional[torch.Tensor], experts: torch.Tensor,
+                          gout: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """trs_moe_gate_bwd as it is: -> glogits (B, G*K), gexperts (B, K), both of the experts' dtype."""
+    B, G, K = _moe_gate_operands(logits, bias, experts, gout)
+    glogits = torch.empty(B, G * K, dtype=experts.dtype, device=experts.device)
+    gexperts = torch.empty_like(experts)
+    call("trs_moe_gate_bwd", ptr(logits), ptr(bias), ptr(experts), ptr(gout), B, G, K, value_dtype_code(experts),
+         ptr(glogits), ptr(gexperts), stream_ptr())
+    return glogits, gexperts
+
+
+class _MoEGate(Function):
+    """The gate GEMM stays inside the node: its result is fp32 (logits rounded to bf16 cost 0.5-2e-2 of the output), while
+    the gradient of the logits has to be of the value dtype for the two gradient GEMMs."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, experts):
+        experts = experts.contiguous()
+        weight = weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        if x.dtype == torch.float32:
+            logits = torch.mm(x, weight.t())
+        else:
+            logits = torch.mm(x, weight.t(), out_dtype=torch.float32)
+        out = moe_gate_forward_raw(logits, bias, experts)
+        ctx.save_for_backward(x, weight, bias, logits, experts)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, weight, bias, logits, experts = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        glogits, gexperts = moe_gate_backward_raw(logits, bias, experts, g.contiguous())
+        gx = torch.mm(glogits, weight) if need[0] else None
+        gw = torch.mm(glogits.t(), x) if need[1] else None
+        gb = glogits.sum(dim=0, dtype=torch.float32).to(bias.dtype) if bias is not None and need[2] else None
+        return gx, gw, gb, gexperts if need[3] else None
+
+
+def moe_gate(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], experts: torch.Tensor) -> torch.Tensor:
+    """(B, D) input, stacked gate weights (G*K, D) and biases (G*K) or None (nn.Linear layouts, gate after gate), experts
+    (B, K) -> (B, G, K):  out[b,g,:] = softmax(x W_g^T + b_g) * experts[b].  One GEMM with an fp32 result, then one kernel;
+    the backward is one kernel, two GEMMs and the bias sum.  All operands of one dtype (fp32 / bf16)."""
+    x, weight, experts = (t.rename(None) if t.has_names() else t for t in (x, weight, experts))
+    require_device(x, weight, bias, experts)
+    if x.dim() != 2 or weight.dim() != 2 or experts.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"moe_gate: x (B, D), weight (G*K, D) and experts (B, K) expected, got {tuple(x.shape)}, "
+                         f"{tuple(weight.shape)} and {tuple(experts.shape)}")
+    K = experts.shape[1]
+    if K < 1 or weight.shape[0] < K or weight.shape[0] % K != 0 or experts.shape[0] != x.shape[0]:
+        raise ValueError(f"moe_gate: weight of {weight.shape[0]} rows is not G gates over the K = {K} expert outputs of "
+                         f"{experts.shape[0]} samples (x has {x.shape[0]})")
+    if weight.dtype != x.dtype or experts.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise TypeError(f"moe_gate: operands of one dtype expected, got x {x.dtype}, weight {weight.dtype}, bias "
+                        f"{None if bias is None else bias.dtype}, experts {experts.dtype}")
+    value_dtype_code(x)
+    return _MoEGate.apply(x, weight, bias, experts)
+
+
+# --------------------------------------------------------------------------------------------
 # K3: field-aware FM pair products
 # --------------------------------------------------------------------------------------------
 class _FFM(Function):

@@ -1188,7 +1188,69 @@ class MultilayerPerceptionLayer(BaseLayer):
         return outputs
 
 
+class MixtureOfExpertsLayer(BaseLayer):
+    """Mixture of experts (MoE; with ``num_gates`` > 1 the multi-gate MMoE), (B,N,E) -> (B, num_gates, K) named
+    ('B','N','O'):  out[b,g,:] = softmax(x2 W_g^T + b_g) * cat_i(expert_i(x2))[b],  x2 = x.reshape(B, N*E) and
+    K = output_size = the summed widths of the experts' outputs.  layers/ctr/mixture_of_experts.py:41-162.
+    Children and parameters as in the reference: ``experts`` = ModuleDict(Expert_{i} = expert_func(**expert kwargs)),
+    ``gates`` = ModuleDict(Gate_{g} = Sequential(Linear, Softmax)); the gate modules hold the parameters and are never
+    called.  The experts run as they are (with ``expert_func=DNNLayer`` the drop-in MLP), their outputs are concatenated
+    once, the G gate Linears run as ONE GEMM over the stacked weights with an fp32 result, and bias + softmax + the
+    multiply by the expert outputs are one kernel per direction (functional.moe_gate).
+    Deviations: the caller's tensor keeps its names (the reference renames it in place); experts whose widths do not sum to
+    ``output_size``, or that return anything but (B, O), raise ValueError here (the reference fails inside einsum); the
+    softmax is over the K columns explicitly (no implicit-dim warning); CPU tensors raise (no CPU path)."""
+
+    @property
+    def inputs_size(self):
+        return {'inputs': ('B', 'N', 'E',)}
+
+    @property
+    def outputs_size(self):
+        return {'outputs': ('B', '1', 'Number of Experts * Expert Output Size',)}
+
+    def __init__(self, inputs_size: int, output_size: int, num_experts: int, expert_func: type, num_gates: int = 1,
+                 **kwargs):
+        super().__init__()
+        expert_kwargs = {k[7:]: v for k, v in kwargs.items() if k.startswith('expert_')}
+        self.experts = nn.ModuleDict()
+        for i in range(num_experts):
+            self.experts[f'Expert_{i}'] = expert_func(**expert_kwargs)
+        self.gates = nn.ModuleDict()
+        for i in range(num_gates):
+            gate = nn.Sequential()
+            gate.add_module('Linear', nn.Linear(inputs_size, output_size))
+            gate.add_module('Softmax', nn.Softmax(dim=1))
+            self.gates[f'Gate_{i}'] = gate
+
+    def forward(self, emb_inputs: torch.Tensor) -> torch.Tensor:
+        x = _strip(emb_inputs)
+        if x.dim() != 3:
+            raise ValueError(f'expected (B, N, E), got {tuple(x.shape)}')
+        x2 = x.reshape(x.shape[0], -1)
+        outs = []
+        for name, expert in self.experts.items():
+            o = _strip(expert(x2))
+            if o.dim() != 2 or o.shape[0] != x2.shape[0]:
+                raise ValueError(f'{name} must return ({x2.shape[0]}, O), got {tuple(o.shape)}')
+            outs.append(o)
+        linears = [gate.Linear for gate in self.gates.values()]
+        if not outs or not linears:
+            raise ValueError(f'a mixture needs an expert and a gate, got {len(outs)} and {len(linears)}')
+        width, K = sum(o.shape[1] for o in outs), linears[0].out_features
+        if width != K:
+            raise ValueError(f'the experts return {width} columns in all, the gates weight output_size = {K}')
+        experts_output = torch.cat(outs, dim=1) if len(outs) > 1 else outs[0]
+        # under autograd: every gate's own parameters receive their slice of the stacked gradient
+        weight = torch.cat([lin.weight for lin in linears], dim=0) if len(linears) > 1 else linears[0].weight
+        bias = torch.cat([lin.bias for lin in linears], dim=0) if len(linears) > 1 else linears[0].bias
+        outputs = F_.moe_gate(x2, weight, bias, experts_output)
+        outputs.names = ('B', 'N', 'O',)
+        return outputs
+
+
 # aliases, layers/ctr/__init__.py:23-35
+MOELayer = MixtureOfExpertsLayer
 AFMLayer = AttentionalFactorizationMachineLayer
 FMLayer = FactorizationMachineLayer
 FFMLayer = FieldAwareFactorizationMachineLayer

@@ -5,7 +5,9 @@ DNNLayer`` -- models/ctr/deep_fm.py:6) build on them unchanged.  See INTEGRATION
 What is rebound: the interaction layers of SURVEY §8a/§8f-N3, the SENET / compose-excitation gate
 (``ComposeExcitationNetworkLayer`` and its aliases ``CENLayer``, ``SqueezeAndExcitationNetworkLayer``, ``SENETLayer`` --
 layers/ctr/__init__.py:24,34,35; the first layer of the FiBiNET and FAT-DeepFFM models, whose ``forward``s run as they are
-over the drop-ins), the per-field / deep MLP
+over the drop-ins), the mixture-of-experts layer (``MixtureOfExpertsLayer`` and its alias ``MOELayer`` --
+layers/ctr/__init__.py:16,32; ``MultiGateMixtureOfExpertsModel`` and ``DeepMixtureOfExpertsModel`` construct on it unchanged,
+models/ctr/multigate_moe.py:56, deep_moe.py:55, and need no head wrapper), the per-field / deep MLP
 (``MultilayerPerceptionLayer`` and its aliases ``DNNLayer``, ``DenseLayer``, ``FullyConnectLayer``,
 ``FeedForwardLayer`` -- layers/ctr/__init__.py:23-35; this is what ``DeepAndCrossNetworkModel.deep``,
 ``DeepFactorizationMachineModel.deep`` and ``XDeepFactorizationMachineModel.deep`` are built from,
@@ -46,6 +48,7 @@ _LAYER_NAMES = [
 _MLP_NAMES = ["MultilayerPerceptionLayer", "DNNLayer", "DenseLayer", "FullyConnectLayer", "FeedForwardLayer"]
 _INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFieldAwareEmbedding", "ListIndicesEmbedding"]
 _ROUTER_NAMES = ["Inputs"]
+_MOE_NAMES = ["MixtureOfExpertsLayer", "MOELayer"]
 _saved = {}
 _saved_defaults = {}
 
@@ -166,7 +169,7 @@ def patch(torecsys_pkg=None, fuse_fm: bool = True, mlp: bool = True, router: boo
     ``heads``: wrap the three first-order models' ``forward`` with the one-kernel head (module docstring)."""
     if torecsys_pkg is None:
         torecsys_pkg = importlib.import_module("torecsys")
-    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs)]
+    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs), (_MOE_NAMES, _layers)]
     if mlp:
         groups.append((_MLP_NAMES, _layers))
     if router:
