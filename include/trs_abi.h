@@ -773,6 +773,37 @@ int trs_moe_gate_fwd(const float* logits, const void* bias, const void* experts,
 int trs_moe_gate_bwd(const float* logits, const void* bias, const void* experts, const void* gout, int64_t B, int32_t G,
                      int32_t K, int32_t dtype, void* glogits, void* gexperts, trs_stream_t stream);
 
+/* ---- attention pooling of a bag of ids (csrc/attn_pool.hip) -------------------------------------------------------
+ * Self-attention over the looked-up rows of a padded (B, L) list followed by a sum / mean over the list, collapsed.  Per
+ * sample and head h (d = E / H, X the (L, E) rows, c = 1 for mode 0 (sum) and 1 / L for mode 1 (mean)):
+ *   [Q | K] = X w_qk^T + b_qk;   P = softmax_rows(Q_h K_h^T / sqrt(d));   pbar_h[m] = c sum_l P[l, m]
+ *   out[b, h, :] = sum_m pbar_h[m] X[m, :]                                                    (B, H, E) of the table's dtype
+ * The pooled layer output is concat_h(out_h Wv_h^T + c' bv_h) Wout^T + c' bout with c' = 1 (mean) or L (sum): two small
+ * GEMMs the caller runs.  replaces aten::embedding + nn.MultiheadAttention + the pooling of list_indices_emb.py:124-152;
+ * no (B, L, E) or (B, L, 2E) write.  w_qk (2E, E): the first 2E rows of in_proj_weight, b_qk (2E) or NULL, both of the
+ * table's dtype.  Every list position takes part (no key-padding mask, as in the reference); an id outside [0, V) reads
+ * as a zero row and raises *err_flag.
+ * trs_attn_pool_path (a pure function): 0 unsupported, 1 vector path (fp32 FMA; any 1 <= L <= 64, E <= 128, E % H == 0),
+ *   2 MFMA path (bf16 with E % 16 == 0 and d % 16 == 0; operands bf16, fp32 accumulation).
+ * trs_attn_pool_blocks: the workgroups a launch uses (persistent: min(B, resident workgroups)); the backward is launched
+ *   with the count the caller passes (1 <= blocks <= B), which sizes its per-workgroup outputs.
+ * Backward, g = gout (B, H, E); Q, K and P are recomputed from the table rows:
+ *   dx (B, L, E) of the table's dtype: the gradient of every looked-up row (input of trs_scatter_rows*);
+ *   dw_part (blocks, 2E, E), db_part (blocks, 2E) fp32: per-workgroup partial gradients of w_qk / b_qk, fully written;
+ *   the caller adds them over `blocks`.  No atomics, samples are dealt to workgroups statically: reproducible bits.
+ *   workspace: trs_attn_pool_bwd_workspace_bytes (0 unless H * L floats do not fit in LDS beside the sample).
+ * Errors: NULL pointer TRS_EINVAL; bad dtype / mode, and a shape trs_attn_pool_path refuses, TRS_EDTYPE (-2).       */
+int trs_attn_pool_path(int32_t L, int32_t E, int32_t H, int32_t dtype);
+int trs_attn_pool_blocks(int64_t B, int32_t L, int32_t E, int32_t H, int32_t dtype, int32_t backward);
+size_t trs_attn_pool_bwd_workspace_bytes(int32_t blocks, int32_t L, int32_t E, int32_t H);
+int trs_attn_pool_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                      int64_t B, int32_t L, const void* w_qk, const void* b_qk, int32_t H, int32_t mode, void* out,
+                      int32_t* err_flag, trs_stream_t stream);
+int trs_attn_pool_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                      int64_t B, int32_t L, const void* w_qk, const void* b_qk, int32_t H, int32_t mode,
+                      const void* gout, void* dx, float* dw_part, float* db_part, int32_t blocks, void* workspace,
+                      size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
 /* ---- index staging: pack per-field columns into the (B,N) index matrix --------
  * out[b, c] = src_j[b * width_j + t]  for the c-th output column = column t of source j.
  * replaces the per-field unsqueeze + torch.cat of inputs/inputs.py:75-80 by one pass.

@@ -2,6 +2,8 @@
 """Kernel micro-benchmarks (developer tool): time each C-ABI kernel at the BASELINE shape with HIP events
 on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]
 --what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag).
+--what attn [--L 50] [--H 1] [--pad 0.3]: attention pooling of ListIndicesEmbedding, the fused path against the same module
+with the switch off, and the two kernels alone (own inputs, see bench_attn).
 --what senet: the SENET / compose-excitation layer, both kernel families, against the ATen composition of the same module
 (own inputs, see bench_senet).
 --what compact [--shard-rows 125000000]: device-side row compaction against torch.unique, and the owner-side fused update
@@ -130,6 +132,107 @@ def bench_bag(a):
         ts = sorted(ts)
         print(f"csr_build (B, L) {name:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us",
               flush=True)
+
+
+def bench_attn(a):
+    """Attention pooling (csrc/attn_pool.hip) at (B, L, E, H, V): forward and forward+backward of
+    ListIndicesEmbedding(use_attn=True, output_method='avg_pooling'), the fused path against the SAME module with the switch
+    off (inputs.ATTN_POOL = False: HIP gather + nn.MultiheadAttention + mean in ATen, the path before the kernel), taking
+    turns inside every round; then the two new kernels alone.  Every figure is the median of ``--rounds`` per-round medians
+    with their min..max, and the forward's peak allocation of either path is printed."""
+    from torecsys_amd import inputs as I
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, L, E, V, H = a.B, a.L, a.E, a.V, a.H
+    g = torch.Generator(device=dev).manual_seed(1234)
+    idx = torch.randint(1, V, (B, L), generator=g, device=dev)
+    if a.pad > 0:
+        keep = torch.rand(B, 1, generator=g, device=dev) * 2 * (1 - a.pad) * L
+        idx = torch.where(torch.arange(L, device=dev).view(1, L) < keep, idx, torch.zeros_like(idx))
+    m = I.ListIndicesEmbedding(embed_size=E, field_size=V, use_attn=True, num_heads=H, output_method="avg_pooling")
+    with torch.no_grad():
+        m.attention.in_proj_bias.normal_(0, 0.1)
+    m = m.to(dev).to(dt)
+    gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+    alg = B * L * (8 + E * s) + B * E * s + B * H * E * s
+    flops = B * (4 * L * E * E + 2 * L * L * E)
+    print(f"attention pooling B={B} L={L} E={E} H={H} V={V} {a.dtype} path {F_.attn_pool_path(L, E, H, dt)}, padded share "
+          f"{float((idx == 0).float().mean()):.2f}, {a.rounds} rounds x {a.iters} launches; forward: {alg / 1e6:.0f} MB (alg), "
+          f"{flops / 1e9:.1f} GFLOP", flush=True)
+
+    def module(fused):
+        def f():
+            I.ATTN_POOL = fused
+            return m(idx).rename(None)
+        return f
+
+    def fwd_bwd(f):
+        def run():
+            F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+            for p in m.parameters():
+                p.grad = None
+            f().backward(gout)
+        return run
+
+    cands = [("attn_pool (HIP)", module(True)), ("composition (ATen)", module(False))]
+    for name, f in cands:
+        F_.clear_caches()
+        with torch.no_grad():
+            f()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        y = f()
+        torch.cuda.synchronize()
+        print(f"{name:22s} forward peak allocation {(torch.cuda.max_memory_allocated() - base) / 2**20:9.1f} MiB "
+              f"((B, L, E) block: {B * L * E * s / 2**20:.1f} MiB)", flush=True)
+        del y
+    res = {}
+    for what in ("fwd", "fwd+bwd"):
+        per = {name: [] for name, _ in cands}
+        for _ in range(a.rounds):
+            for name, f in cands:
+                if what == "fwd":
+                    with torch.no_grad():
+                        per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                else:
+                    per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+        for name, ts in per.items():
+            ts = sorted(ts)
+            res[(what, name)] = ts[len(ts) // 2]
+            print(f"{what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                  f"{ts[-1] * 1e6:9.1f} us", flush=True)
+        print(f"{what:8s} composition / attn_pool = "
+              f"{res[(what, 'composition (ATen)')] / res[(what, 'attn_pool (HIP)')]:.2f}x", flush=True)
+    I.ATTN_POOL = True
+    # the two kernels alone (the backward without the bucket walk behind it)
+    from torecsys_amd._abi import call, index_dtype_code, ptr, size_query, stream_ptr, value_dtype_code
+    w = m.embedding.weight.detach()
+    wqk, bqk = m.attention.in_proj_weight.detach()[:2 * E].contiguous(), m.attention.in_proj_bias.detach()[:2 * E].contiguous()
+    code = value_dtype_code(w)
+    xt = torch.empty(B, H, E, dtype=dt, device=dev)
+    gx = torch.randn(B, H, E, generator=g, device=dev, dtype=dt)
+    blocks = size_query("trs_attn_pool_blocks", B, L, E, H, code, 1)
+    dx = torch.empty(B, L, E, dtype=dt, device=dev)
+    dwp = torch.empty(blocks, 2 * E, E, dtype=torch.float32, device=dev)
+    dbp = torch.empty(blocks, 2 * E, dtype=torch.float32, device=dev)
+    ws_bytes = size_query("trs_attn_pool_bwd_workspace_bytes", blocks, L, E, H)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+
+    def k_fwd():
+        call("trs_attn_pool_fwd", ptr(w), V, E, code, ptr(idx), index_dtype_code(idx), B, L, ptr(wqk), ptr(bqk), H, 1,
+             ptr(xt), None, stream_ptr())
+
+    def k_bwd():
+        call("trs_attn_pool_bwd", ptr(w), V, E, code, ptr(idx), index_dtype_code(idx), B, L, ptr(wqk), ptr(bqk), H, 1,
+             ptr(gx), ptr(dx), ptr(dwp), ptr(dbp), blocks, ptr(ws), ws_bytes, None, stream_ptr())
+
+    for name, f, fl in (("trs_attn_pool_fwd", k_fwd, flops), ("trs_attn_pool_bwd", k_bwd, 4 * flops)):
+        ts = sorted(timeit(f, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+        med = ts[len(ts) // 2]
+        print(f"kernel   {name:22s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
+              f"{fl / med / 1e12:6.1f} TFLOP/s ({blocks} workgroups in the backward)", flush=True)
 
 
 def bench_senet(a):
@@ -388,7 +491,8 @@ def main():
     ap.add_argument("--V", type=int, default=1_000_000)
     ap.add_argument("--zipf", action="store_true")
     ap.add_argument("--what", default="all")
-    ap.add_argument("--L", type=int, default=50, help="bag: list length")
+    ap.add_argument("--L", type=int, default=50, help="bag / attn: list length")
+    ap.add_argument("--H", type=int, default=1, help="attn: attention heads")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
     ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe: alternating rounds")
     ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact / moe: timed launches per round")
@@ -398,6 +502,8 @@ def main():
         return bench_compact(a)
     if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"
         return bench_bag(a)
+    if a.what == "attn":         # own inputs and module: not part of "all"
+        return bench_attn(a)
     if a.what == "senet":        # own inputs and modules: not part of "all"
         return bench_senet(a)
     if a.what == "moe":          # own inputs and modules: not part of "all"

@@ -108,6 +108,12 @@ SIGNATURES = {
     "trs_bag_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "trs_scatter_argmax_workspace_bytes": (_SZ, [_I64, _I32]),
     "trs_scatter_rows_argmax": (c_int32, [_P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P]),
+    "trs_attn_pool_path": (c_int32, [_I32, _I32, _I32, _I32]),
+    "trs_attn_pool_blocks": (c_int32, [_I64, _I32, _I32, _I32, _I32, _I32]),
+    "trs_attn_pool_bwd_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "trs_attn_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
+    "trs_attn_pool_bwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32,
+                                    _P, _SZ, _P, _P]),
     "trs_senet_fused_supported": (c_int32, [_I32, _I32, _I32, _I32]),
     "trs_senet_fwd": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "trs_senet_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32]),

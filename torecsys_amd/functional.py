@@ -644,6 +644,132 @@ def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", paddin
 
 
 # --------------------------------------------------------------------------------------------
+# attention pooling: self-attention over the rows of a (B, L) list of ids, then sum / mean over the list
+# --------------------------------------------------------------------------------------------
+ATTN_POOL_MODES = {"sum": 0, "mean": 1}
+
+
+def attn_pool_path(L: int, E: int, H: int, dtype: torch.dtype) -> int:
+    """0: no fused kernel for this shape (callers keep the ATen composition), 1: vector path, 2: MFMA path
+    (trs_attn_pool_path; a pure function, callable without a device)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return 0
+    code = _abi.TRS_F32 if dtype == torch.float32 else _abi.TRS_BF16
+    return size_query("trs_attn_pool_path", int(L), int(E), int(H), code)
+
+
+class _AttnPool(Function):
+    @staticmethod
+    def forward(ctx, weight, idx, w_qk, b_qk, num_heads, mode, padding_idx, opt=None):
+        require_device(weight, idx, w_qk, b_qk)
+        B, L = idx.shape
+        V, E = weight.shape
+        H = int(num_heads)
+        w = weight.contiguous()
+        wq = w_qk.contiguous()
+        bq = b_qk.contiguous() if b_qk is not None else None
+        out = torch.empty(B, H, E, dtype=w.dtype, device=w.device)
+        flag = _ErrFlag(w.device)
+        call("trs_attn_pool_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, ptr(wq),
+             ptr(bq), H, mode, ptr(out), ptr(flag.t), stream_ptr())
+        flag.check("attn_pool")
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None      # as _BagPool: no walk reads that bucket
+        if ctx.needs_input_grad[0]:
+            prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
+        # nothing but the inputs is kept: the backward recomputes Q, K and the probabilities from the table rows
+        ctx.save_for_backward(idx, weight, w_qk, b_qk)
+        ctx.H, ctx.mode, ctx.opt = H, mode, opt
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        idx, weight, w_qk, b_qk = ctx.saved_tensors
+        _adopt_grads(g)
+        B, L = idx.shape
+        V, E = weight.shape
+        H = ctx.H
+        dev = weight.device
+        if B == 0:
+            return (torch.zeros_like(weight) if ctx.opt is None else None, None, torch.zeros_like(w_qk),
+                    None if b_qk is None else torch.zeros_like(b_qk), None, None, None, None)
+        w = weight.contiguous()
+        wq = w_qk.contiguous()
+        bq = b_qk.contiguous() if b_qk is not None else None
+        code = value_dtype_code(w)
+        blocks = size_query("trs_attn_pool_blocks", B, L, E, H, code, 1)
+        dx = torch.empty(B, L, E, dtype=w.dtype, device=dev)
+        dw_part = torch.empty(blocks, 2 * E, E, dtype=torch.float32, device=dev)
+        db_part = torch.empty(blocks, 2 * E, dtype=torch.float32, device=dev)
+        ws_bytes = size_query("trs_attn_pool_bwd_workspace_bytes", blocks, L, E, H)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        # the row flag was raised by the forward; the backward range-checks without a flag of its own
+        call("trs_attn_pool_bwd", ptr(w), V, E, code, ptr(idx), index_dtype_code(idx), B, L, ptr(wq), ptr(bq), H, ctx.mode,
+             ptr(g.contiguous()), ptr(dx), ptr(dw_part), ptr(db_part), blocks, ptr(ws), ws_bytes, None, stream_ptr())
+        g_wqk = dw_part.sum(0).to(w_qk.dtype) if ctx.needs_input_grad[2] else None          # fixed order: reproducible
+        g_bqk = db_part.sum(0).to(b_qk.dtype) if b_qk is not None and ctx.needs_input_grad[3] else None
+        grad = None
+        if ctx.needs_input_grad[0]:
+            rb = row_buckets(idx, None, V, skip_row=ctx.skip)
+            grad = _apply_or_grad(rb, weight, ctx.opt, g_rows=dx, padding_row=ctx.padding_idx)
+        return grad, None, g_wqk, g_bqk, None, None, None, None
+
+
+def attn_pool(weight: torch.Tensor, idx: torch.Tensor, w_qk: torch.Tensor, b_qk: Optional[torch.Tensor], num_heads: int,
+              mode: str = "mean", padding_idx: Optional[int] = None, opt=None) -> torch.Tensor:
+    """(B, H, E): per head the attention-weighted pooled table rows of a padded (B, L) list of ids,
+    ``sum_m pbar_h[m] * weight[idx[b, m]]`` with ``pbar_h`` the column sums (``sum``) or means (``mean``) of
+    ``softmax((X Wq_h^T + bq_h)(X Wk_h^T + bk_h)^T / sqrt(E / H))`` -- everything of "multi-head self-attention over the
+    bag, then pool" that depends on the list positions, in one HIP pass per direction (csrc/attn_pool.hip).  ``w_qk``
+    (2E, E) / ``b_qk`` (2E) or None: the query and key rows of ``in_proj_weight`` / ``in_proj_bias``.  Every position
+    takes part, padding included.  ``padding_idx``: the table row that receives no gradient.  ``opt``: fused sparse
+    optimizer for the table.  Raises for shapes ``attn_pool_path`` refuses."""
+    if mode not in ATTN_POOL_MODES:
+        raise ValueError(f'attn_pool: mode must be one of {sorted(ATTN_POOL_MODES)}, got {mode!r}')
+    idx = _as_index(idx)
+    if idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError(f"indices must be (B, L) with L >= 1, got shape {tuple(idx.shape)}")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
+    E = weight.shape[1]
+    if tuple(w_qk.shape) != (2 * E, E) or (b_qk is not None and tuple(b_qk.shape) != (2 * E,)):
+        raise ValueError(f"attn_pool: w_qk must be ({2 * E}, {E}) and b_qk ({2 * E},)")
+    if w_qk.dtype != weight.dtype or (b_qk is not None and b_qk.dtype != weight.dtype):
+        raise TypeError("attn_pool: w_qk / b_qk must have the table's dtype")
+    if attn_pool_path(idx.shape[1], E, num_heads, weight.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: attn_pool does not cover L={idx.shape[1]}, E={E}, H={num_heads}, "
+                                  f"{weight.dtype} (1 <= L <= 64, E <= 128, E % H == 0, fp32 / bf16)")
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = weight.shape[0] + padding_idx
+    return _AttnPool.apply(weight, idx, w_qk, b_qk, num_heads, ATTN_POOL_MODES[mode], padding_idx, opt)
+
+
+def attn_pool_layer(weight: torch.Tensor, idx: torch.Tensor, in_proj_weight: torch.Tensor,
+                    in_proj_bias: Optional[torch.Tensor], out_w: torch.Tensor, out_b: Optional[torch.Tensor],
+                    num_heads: int, mode: str = "mean", padding_idx: Optional[int] = None, opt=None) -> torch.Tensor:
+    """(B, 1, E): ``nn.MultiheadAttention`` (no masks, no dropout) over the looked-up rows of a (B, L) list followed by the
+    sum / mean over the list.  ``attn_pool`` covers what depends on the positions; the value and output projections act
+    on its (B, H, E) result: ``y = concat_h(xt_h Wv_h^T + c' bv_h) Wout^T + c' bout`` with c' = 1 (mean) or L (sum)."""
+    E = weight.shape[1]
+    H = int(num_heads)
+    d = E // H
+    L = idx.shape[1]
+    xt = attn_pool(weight, idx, in_proj_weight[:2 * E], None if in_proj_bias is None else in_proj_bias[:2 * E], H, mode,
+                   padding_idx, opt)
+    B = xt.shape[0]
+    cb = 1.0 if mode == "mean" else float(L)
+    wv = in_proj_weight[2 * E:].reshape(H, d, E)
+    o = torch.bmm(xt.transpose(0, 1), wv.transpose(1, 2)).transpose(0, 1).reshape(B, E)      # (H,B,E)x(H,E,d) -> (B, H*d)
+    if in_proj_bias is not None:
+        o = o + cb * in_proj_bias[2 * E:]
+    y = torch.nn.functional.linear(o, out_w)
+    if out_b is not None:
+        y = y + cb * out_b
+    return y.unsqueeze(1)
+
+
+# --------------------------------------------------------------------------------------------
 # K1+K2(+K8): fused lookup + FM (+ first-order sum)
 # --------------------------------------------------------------------------------------------
 class _EmbedFM(Function):

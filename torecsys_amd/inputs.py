@@ -173,6 +173,11 @@ class MultiIndicesFieldAwareEmbedding(BaseInput):
         return out
 
 
+# TRS_ATTN_POOL=0: ListIndicesEmbedding(use_attn=True) keeps the gather + nn.MultiheadAttention + pooling composition
+# (the A/B baseline of functional.attn_pool_layer)
+ATTN_POOL = os.environ.get("TRS_ATTN_POOL", "1") not in ("", "0")
+
+
 def _no_attention(query, key, value):
     return query, None
 
@@ -190,11 +195,30 @@ class ListIndicesEmbedding(BaseInput):
     then reduces over ``dim='N'``); here they do what its docstring promises -- ``mean`` equals ``avg_pooling``, ``sum``
     is the unscaled sum, both (B,1,E).
 
-    ``use_attn=True``: the HIP gather produces (B,L,E), the module's own ``nn.MultiheadAttention`` (ATen) runs on
-    (L,B,E) and the pooling runs in ATen too -- same parameters and keys as the reference; not a hot path, no kernel of
-    its own.  ``show_attention`` (a plotting helper) is not provided."""
+    ``use_attn=True`` with ``avg_pooling`` / ``mean`` / ``sum``: self-attention over the bag followed by the pooling runs
+    as one HIP pass per direction (``functional.attn_pool_layer``, csrc/attn_pool.hip): the pooling collapses the value
+    and output projections onto one row per sample and head, so neither the (B,L,E) block nor Q, K, V or the scores are
+    formed in the forward.  Same parameters and ``state_dict`` keys as the reference (the module's own
+    ``nn.MultiheadAttention`` holds them).  Served for 1 <= L <= 64, E <= 128, fp32 / bf16, no ``add_bias_kv`` /
+    ``add_zero_attn``, attention dropout 0 or eval mode, and the switch ``TRS_ATTN_POOL`` not ``0``; every other case --
+    ``max_pooling`` and ``none`` with attention among them -- runs as the HIP gather to (B,L,E), ``nn.MultiheadAttention``
+    (ATen) on (L,B,E) and the pooling in ATen.  ``show_attention`` (a plotting helper) is not provided."""
 
     _POOL = {'avg_pooling': 'mean', 'max_pooling': 'max', 'mean': 'mean', 'sum': 'sum'}
+
+    def _attn_pool_mode(self, idx: torch.Tensor) -> Optional[str]:
+        """the pooling mode when this call takes the fused attention-pooling kernel, None when it keeps the composition"""
+        pool = self._POOL.get(self.output_method)
+        if not ATTN_POOL or not self.use_attn or pool not in ('mean', 'sum') or idx.shape[1] < 1:
+            return None
+        a = self.attention
+        if (a.bias_k is not None or a.bias_v is not None or a.add_zero_attn or not a._qkv_same_embed_dim
+                or (a.dropout > 0.0 and self.training)):
+            return None
+        w = self.embedding.weight
+        if not w.is_cuda or a.in_proj_weight.dtype != w.dtype:
+            return None
+        return pool if F_.attn_pool_path(idx.shape[1], self.embed_size, a.num_heads, w.dtype) != 0 else None
 
     def __init__(self, embed_size: Optional[int] = None, field_size: Optional[int] = None,
                  padding_idx: Optional[int] = 0, nn_embedding: Optional[nn.Parameter] = None,
@@ -237,7 +261,12 @@ class ListIndicesEmbedding(BaseInput):
         if idx.dim() != 2:
             raise ValueError(f'inputs must be (B, L), got {tuple(idx.shape)}')
         w = self.embedding.weight
-        if self.use_attn or self.output_method == 'none':
+        mode = self._attn_pool_mode(idx)
+        if mode is not None:
+            a = self.attention
+            out = F_.attn_pool_layer(w, idx, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+                                     a.num_heads, mode, self.padding_idx, self.fused_optimizer)
+        elif self.use_attn or self.output_method == 'none':
             out = F_.gather_rows(w, idx, None, self.padding_idx, self.fused_optimizer)      # (B,L,E)
             if self.use_attn:
                 seq = out.transpose(0, 1)                                                   # (L,B,E)
