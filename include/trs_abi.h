@@ -804,6 +804,30 @@ int trs_attn_pool_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, co
                       const void* gout, void* dx, float* dw_part, float* db_part, int32_t blocks, void* workspace,
                       size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
 
+/* ---- behaviour-to-interest dynamic routing, MIND (csrc/dynamic_routing.hip) ----------------------------------------
+ * priors (B, N, R) fp32 = x @ S (the caller's GEMM, fp32 result), noise (B, K, N, R) of the value dtype, c[b,k,n] = 0:
+ *   num_iter - 1 times:  w = softmax_k(noise[b,k,n,r] + c[b,k,n]);  z[b,k,r] = sum_n w priors[b,n,r];  v = squash(z)
+ *                        c[b,k,n] += sum_r priors[b,n,r] v[b,k,r]
+ *   out (B, K, R) of the value dtype = squash(sum_n softmax_k(noise + c) priors),
+ *   squash(z) = n2 / (1 + n2) * z / (sqrt(n2) + 1e-8), n2 = sum_r z^2
+ * replaces the repeat / randn_like / softmax / mul / sum / squash / matmul / add chain of layers/ctr/dynamic_routing.py:
+ * 113-172; one workgroup keeps a sample's state on chip for all iterations.  c_out (B, K, N) and z_out (B, K, R), fp32,
+ * both or neither: the final routing sum and the final z, all the backward needs beside the noise.
+ * Backward (the loop runs on detached priors, so w is a constant):
+ *   dpri[b,n,r] = sum_k softmax_k(noise + c)[b,k,n,r] dz[b,k,r], dz = the squash backward of gout (B, K, R) at z
+ *   -> dpri (B, N, R) of the value dtype; the caller's two GEMMs turn it into the gradients of x and S.
+ * A sample with n2 == 0 gives zero output and zero dz (the reference's autograd gives NaN there).  fp32 between loads and
+ * stores, the maximum over k is subtracted, fixed summation order, no atomics: reproducible bits.
+ * trs_dynamic_routing_path (a pure function): 0 outside 1 <= N <= 128, 1 <= R <= 128, 1 <= K <= 8, fp32 / bf16; 1 rows of
+ *   whole 16-byte vectors (16-byte loads where the pointers are aligned as well); 2 element loads.
+ * B == 0 returns TRS_OK and touches nothing.  Errors: NULL pointer, B < 0, num_iter < 1 TRS_EINVAL; dtype TRS_EDTYPE; a
+ * shape the path function refuses TRS_ESHAPE.                                                                        */
+int trs_dynamic_routing_path(int32_t N, int32_t R, int32_t K, int32_t dtype);
+int trs_dynamic_routing_fwd(const float* priors, const void* noise, int64_t B, int32_t N, int32_t R, int32_t K,
+                            int32_t num_iter, int32_t dtype, void* out, float* c_out, float* z_out, trs_stream_t stream);
+int trs_dynamic_routing_bwd(const void* noise, const float* c, const float* z, const void* gout, int64_t B, int32_t N,
+                            int32_t R, int32_t K, int32_t dtype, void* dpri, trs_stream_t stream);
+
 /* ---- index staging: pack per-field columns into the (B,N) index matrix --------
  * out[b, c] = src_j[b * width_j + t]  for the c-th output column = column t of source j.
  * replaces the per-field unsqueeze + torch.cat of inputs/inputs.py:75-80 by one pass.

@@ -9,7 +9,10 @@ with the switch off, and the two kernels alone (own inputs, see bench_attn).
 --what compact [--shard-rows 125000000]: device-side row compaction against torch.unique, and the owner-side fused update
 of a large shard through either (own inputs, see bench_compact).
 --what moe: the gate part of MixtureOfExpertsLayer against the ATen composition of the same module, the two gate kernels
-alone, and the experts' share of the whole layer (own inputs, see bench_moe)."""
+alone, and the experts' share of the whole layer (own inputs, see bench_moe).
+--what routing [--L 50] [--R 64] [--caps 8] [--routing-iters 3]: DynamicRoutingLayer over lists of L behaviours, the fused
+path against the same module with the switch off, the two kernels alone, the noise draw and the peak allocations (own
+inputs, see bench_routing)."""
 import argparse
 import os
 import sys
@@ -482,6 +485,102 @@ def bench_moe(a):
         torch.cuda.empty_cache()
 
 
+def bench_routing(a):
+    """Dynamic routing (csrc/dynamic_routing.hip) at (B, N, E, R, max_num_caps, num_iter): forward and forward+backward of
+    DynamicRoutingLayer with its own noise draw, the fused path against the SAME module with the switch off
+    (layers.DYNAMIC_ROUTING = False: the ATen composition), taking turns inside every round; the peak allocation of
+    either; then the two kernels alone with their algorithmic bytes (the noise once per direction dominates) as a
+    fraction of 8 TB/s, and the noise draw by itself.  Every figure is the median of ``--rounds`` per-round medians with
+    their min..max."""
+    from torecsys_amd import layers as L
+    from torecsys_amd._abi import call, ptr, stream_ptr, value_dtype_code
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, N, E, R, iters, launches = a.B, a.L, a.E, a.R, a.routing_iters, a.iters
+    g = torch.Generator(device=dev).manual_seed(1234)
+    m = L.DynamicRoutingLayer(E, R, a.caps, iters).to(dev).to(dt)
+    K = m._dynamic_interest_number(N)
+    x = (0.3 * torch.randn(B, N, E, generator=g, device=dev)).to(dt).requires_grad_()
+    gout = torch.randn(B, K, R, generator=g, device=dev, dtype=dt)
+    alg_f = B * (K * N * R * s + 4 * N * R + K * R * s + 4 * K * (N + R))
+    alg_b = B * (K * N * R * s + 4 * K * (N + R) + K * R * s + N * R * s)
+    print(f"dynamic routing B={B} N={N} E={E} R={R} K'={K} num_iter={iters} {a.dtype} path "
+          f"{F_.dynamic_routing_path(N, R, K, dt)}, {a.rounds} rounds x {launches} launches; one (B, K', N, R) tensor: "
+          f"{B * K * N * R * s / 2**20:.0f} MiB; exp per forward {B * K * N * R * iters / 1e9:.2f} G", flush=True)
+
+    def module(fused):
+        def f():
+            L.DYNAMIC_ROUTING = fused
+            return m(x).rename(None)
+        return f
+
+    def fwd_bwd(f):
+        def run():
+            x.grad = m.S.grad = None
+            f().backward(gout)
+        return run
+
+    cands = [("dynamic_routing (HIP)", module(True)), ("composition (ATen)", module(False))]
+    for name, f in cands:
+        for what, run in (("fwd", f), ("fwd+bwd", fwd_bwd(f))):
+            ctx = torch.no_grad() if what == "fwd" else torch.enable_grad()
+            with ctx:
+                run()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                y = run()
+                torch.cuda.synchronize()
+            print(f"{name:22s} {what:8s} peak allocation {(torch.cuda.max_memory_allocated() - base) / 2**20:9.1f} MiB",
+                  flush=True)
+            del y
+    res = {}
+    for what in ("fwd", "fwd+bwd"):
+        per = {name: [] for name, _ in cands}
+        for _ in range(a.rounds):
+            for name, f in cands:
+                if what == "fwd":
+                    with torch.no_grad():
+                        per[name].append(timeit(f, iters=launches, warm=2)[0])
+                else:
+                    per[name].append(timeit(fwd_bwd(f), iters=launches, warm=2)[0])
+        for name, ts in per.items():
+            ts = sorted(ts)
+            res[(what, name)] = ts[len(ts) // 2]
+            print(f"{what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                  f"{ts[-1] * 1e6:9.1f} us", flush=True)
+        print(f"{what:8s} composition / dynamic_routing = "
+              f"{res[(what, 'composition (ATen)')] / res[(what, 'dynamic_routing (HIP)')]:.2f}x", flush=True)
+    L.DYNAMIC_ROUTING = True
+    x.grad = m.S.grad = None
+    # the two kernels alone, and the noise draw
+    code = value_dtype_code(x)
+    with torch.no_grad():
+        pri = torch.mm(x.reshape(B * N, E).float(), m.S.float()).view(B, N, R)
+    noise = torch.randn(B, K, N, R, dtype=dt, device=dev)
+    out = torch.empty(B, K, R, dtype=dt, device=dev)
+    c = torch.empty(B, K, N, dtype=torch.float32, device=dev)
+    z = torch.empty(B, K, R, dtype=torch.float32, device=dev)
+    dpri = torch.empty(B, N, R, dtype=dt, device=dev)
+
+    def k_fwd():
+        call("trs_dynamic_routing_fwd", ptr(pri), ptr(noise), B, N, R, K, iters, code, ptr(out), ptr(c), ptr(z), stream_ptr())
+
+    def k_bwd():
+        call("trs_dynamic_routing_bwd", ptr(noise), ptr(c), ptr(z), ptr(gout), B, N, R, K, code, ptr(dpri), stream_ptr())
+
+    def draw():
+        torch.randn(B, K, N, R, dtype=dt, device=dev)
+
+    for name, f, alg in (("trs_dynamic_routing_fwd", k_fwd, alg_f), ("trs_dynamic_routing_bwd", k_bwd, alg_b),
+                         ("torch.randn (noise)", draw, B * K * N * R * s)):
+        ts = sorted(timeit(f, iters=launches, warm=2)[0] for _ in range(a.rounds))
+        med = ts[len(ts) // 2]
+        print(f"kernel   {name:24s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
+              f"{alg / 1e6:8.0f} MB (alg) {alg / med / 1e12:5.2f} TB/s = {alg / med / 8e12:.2f} of 8 TB/s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -491,13 +590,18 @@ def main():
     ap.add_argument("--V", type=int, default=1_000_000)
     ap.add_argument("--zipf", action="store_true")
     ap.add_argument("--what", default="all")
-    ap.add_argument("--L", type=int, default=50, help="bag / attn: list length")
+    ap.add_argument("--L", type=int, default=50, help="bag / attn / routing: list length")
     ap.add_argument("--H", type=int, default=1, help="attn: attention heads")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
-    ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe: alternating rounds")
-    ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact / moe: timed launches per round")
+    ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe / routing: alternating rounds")
+    ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact / moe / routing: timed launches per round")
+    ap.add_argument("--routing-iters", type=int, default=3, help="routing: num_iter of the layer")
+    ap.add_argument("--R", type=int, default=64, help="routing: routed size")
+    ap.add_argument("--caps", type=int, default=8, help="routing: max_num_caps")
     ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
     a = ap.parse_args()
+    if a.what == "routing":      # own inputs and module: not part of "all"
+        return bench_routing(a)
     if a.what == "compact":      # own inputs (a 125 M-row table and its Adagrad state): not part of "all"
         return bench_compact(a)
     if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"

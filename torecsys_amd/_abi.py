@@ -125,6 +125,9 @@ SIGNATURES = {
     "trs_moe_gate_last_path": (c_int32, []),
     "trs_moe_gate_fwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_moe_gate_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P]),
+    "trs_dynamic_routing_path": (c_int32, [_I32, _I32, _I32, _I32]),
+    "trs_dynamic_routing_fwd": (c_int32, [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "trs_dynamic_routing_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
     "trs_fm_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_bwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_dot_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

@@ -1928,6 +1928,121 @@ def moe_gate(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]
 
 
 # --------------------------------------------------------------------------------------------
+# Behaviour-to-interest dynamic routing (MIND): out = squash(sum_n softmax_k(noise + c) (x @ S))
+# --------------------------------------------------------------------------------------------
+ROUTING_PATH_VECTOR, ROUTING_PATH_ELEMENT = 1, 2
+
+
+def dynamic_routing_path(N: int, R: int, K: int, dtype: torch.dtype) -> int:
+    """0: no fused kernel for this shape (callers keep the ATen composition), ROUTING_PATH_VECTOR: rows of whole 16-byte
+    vectors, ROUTING_PATH_ELEMENT: element loads (trs_dynamic_routing_path; a pure function, callable without a device).
+    Covered: 1 <= N <= 128, 1 <= R <= 128, 1 <= K <= 8, fp32 / bf16."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return 0
+    code = _abi.TRS_F32 if dtype == torch.float32 else _abi.TRS_BF16
+    return size_query("trs_dynamic_routing_path", int(N), int(R), int(K), code)
+
+
+def _routing_operands(noise, priors=None, c=None, z=None, gout=None):
+    for name, t in (("priors", priors), ("noise", noise), ("c", c), ("z", z), ("gout", gout)):
+        if t is not None and not t.is_contiguous():      # the entries read dense rows: a strided operand would be misread
+            raise ValueError(f"dynamic_routing: {name} must be contiguous, got strides {tuple(t.stride())} for "
+                             f"{tuple(t.shape)}")
+    require_device(noise, priors, c, z, gout)
+    if noise.dim() != 4:
+        raise ValueError(f"dynamic_routing: noise (B, K, N, R) expected, got {tuple(noise.shape)}")
+    B, K, N, R = noise.shape
+    for name, t, shape, dtype in (("priors", priors, (B, N, R), torch.float32), ("c", c, (B, K, N), torch.float32),
+                                  ("z", z, (B, K, R), torch.float32), ("gout", gout, (B, K, R), noise.dtype)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype):
+            raise ValueError(f"dynamic_routing: {name} {shape} of {dtype} expected, got {tuple(t.shape)} {t.dtype}")
+    code = value_dtype_code(noise)
+    if dynamic_routing_path(N, R, K, noise.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: dynamic_routing does not cover N={N}, R={R}, K={K} "
+                                  f"(1 <= N <= 128, 1 <= R <= 128, 1 <= K <= 8)")
+    return B, K, N, R, code
+
+
+def dynamic_routing_forward_raw(priors: torch.Tensor, noise: torch.Tensor, num_iter: int, save: bool = False):
+    """trs_dynamic_routing_fwd as it is (no autograd): fp32 priors (B, N, R), noise (B, K, N, R) of the value dtype ->
+    out (B, K, R) of the value dtype; with ``save`` also the fp32 routing sum c (B, K, N) and z (B, K, R) the backward
+    reads.  A non-contiguous operand raises ValueError."""
+    B, K, N, R, code = _routing_operands(noise, priors=priors)
+    if int(num_iter) < 1:
+        raise ValueError(f"dynamic_routing: num_iter >= 1 expected, got {num_iter}")
+    out = torch.empty(B, K, R, dtype=noise.dtype, device=noise.device)
+    c = torch.empty(B, K, N, dtype=torch.float32, device=noise.device) if save else None
+    z = torch.empty(B, K, R, dtype=torch.float32, device=noise.device) if save else None
+    call("trs_dynamic_routing_fwd", ptr(priors), ptr(noise), B, N, R, K, int(num_iter), code, ptr(out), ptr(c), ptr(z),
+         stream_ptr())
+    return (out, c, z) if save else out
+
+
+def dynamic_routing_backward_raw(noise: torch.Tensor, c: torch.Tensor, z: torch.Tensor, gout: torch.Tensor) -> torch.Tensor:
+    """trs_dynamic_routing_bwd as it is: noise, the forward's c and z, gout (B, K, R) -> dpri (B, N, R) of the value
+    dtype."""
+    B, K, N, R, code = _routing_operands(noise, c=c, z=z, gout=gout)
+    dpri = torch.empty(B, N, R, dtype=noise.dtype, device=noise.device)
+    call("trs_dynamic_routing_bwd", ptr(noise), ptr(c), ptr(z), ptr(gout), B, N, R, K, code, ptr(dpri), stream_ptr())
+    return dpri
+
+
+class _DynamicRouting(Function):
+    """The projection stays inside the node, as the gate GEMM of _MoEGate: the priors are the GEMM's fp32 result (rounded
+    to bf16 they move the output by 1e-2 at 3 iterations and 5e-2 at 5), and the gradient of the priors is of the value
+    dtype for the two gradient GEMMs.  Saved: x, S, the noise, c (B, K, N) and z (B, K, R) -- no priors."""
+
+    @staticmethod
+    def forward(ctx, x, S, noise, num_iter):
+        B, N, E = x.shape
+        x2 = x.reshape(B * N, E)
+        S = S.contiguous()
+        if x.dtype == torch.float32:
+            priors = torch.mm(x2, S)
+        else:
+            priors = torch.mm(x2, S, out_dtype=torch.float32)
+        out, c, z = dynamic_routing_forward_raw(priors.view(B, N, S.shape[1]), noise.contiguous(), num_iter, save=True)
+        ctx.save_for_backward(x, S, noise, c, z)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, S, noise, c, z = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, N, E = x.shape
+        dpri = dynamic_routing_backward_raw(noise.contiguous(), c, z, g.contiguous()).view(B * N, S.shape[1])
+        gx = torch.mm(dpri, S.t()).view(B, N, E) if need[0] else None
+        gS = torch.mm(x.reshape(B * N, E).t(), dpri) if need[1] else None
+        return gx, gS, None, None
+
+
+def dynamic_routing(x: torch.Tensor, S: torch.Tensor, noise: torch.Tensor, num_iter: int) -> torch.Tensor:
+    """(B, N, E) behaviours, projection S (E, R), coupling noise (B, K', N, R) -> (B, K', R) interest capsules after
+    ``num_iter`` rounds of MIND's behaviour-to-interest routing (K' is the noise's; the routing loop runs on detached
+    priors, the noise receives no gradient).  One GEMM with an fp32 result and one kernel; the backward is one kernel and
+    two GEMMs.  All operands of one dtype (fp32 / bf16); raises for shapes ``dynamic_routing_path`` refuses."""
+    x, S, noise = (t.rename(None) if t.has_names() else t for t in (x, S, noise))
+    if x.dim() != 3 or S.dim() != 2 or noise.dim() != 4 or S.shape[0] != x.shape[2]:
+        raise ValueError(f"dynamic_routing: x (B, N, E), S (E, R) and noise (B, K, N, R) expected, got {tuple(x.shape)}, "
+                         f"{tuple(S.shape)} and {tuple(noise.shape)}")
+    B, N, _ = x.shape
+    if noise.shape[0] != B or noise.shape[2] != N or noise.shape[3] != S.shape[1]:
+        raise ValueError(f"dynamic_routing: noise ({B}, K, {N}, {S.shape[1]}) expected, got {tuple(noise.shape)}")
+    if S.dtype != x.dtype or noise.dtype != x.dtype:
+        raise TypeError(f"dynamic_routing: operands of one dtype expected, got x {x.dtype}, S {S.dtype}, noise "
+                        f"{noise.dtype}")
+    if int(num_iter) < 1:
+        raise ValueError(f"dynamic_routing: num_iter >= 1 expected, got {num_iter}")
+    require_device(x, S, noise)
+    value_dtype_code(x)
+    if dynamic_routing_path(N, S.shape[1], noise.shape[1], x.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: dynamic_routing does not cover N={N}, R={S.shape[1]}, "
+                                  f"K={noise.shape[1]} (1 <= N <= 128, 1 <= R <= 128, 1 <= K <= 8)")
+    return _DynamicRouting.apply(x, S, noise, int(num_iter))
+
+
+# --------------------------------------------------------------------------------------------
 # K3: field-aware FM pair products
 # --------------------------------------------------------------------------------------------
 class _FFM(Function):

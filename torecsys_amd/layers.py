@@ -1249,6 +1249,82 @@ class MixtureOfExpertsLayer(BaseLayer):
         return outputs
 
 
+# TRS_DYNAMIC_ROUTING=0: DynamicRoutingLayer keeps the ATen composition (the A/B baseline of functional.dynamic_routing)
+DYNAMIC_ROUTING = os.environ.get("TRS_DYNAMIC_ROUTING", "1") not in ("", "0")
+
+
+class DynamicRoutingLayer(BaseLayer):
+    """Behaviour-to-interest dynamic routing of MIND, (B,N,E) -> (B, K', R) named ('B','N','O') with
+    K' = max(1, min(max_num_caps, log2 N)) interest capsules.  layers/ctr/dynamic_routing.py:11-177.
+    Parameter ``S`` (E, R) = randn, as in the reference.  priors = x @ S are shared by the capsules; the coupling
+    logits start as Gaussian noise (B, K', N, R), ``num_iter - 1`` routing rounds on the detached priors add the
+    agreement sum_r priors v to them, and the output is squash(sum_n softmax_k(logits) priors).  The projection is one
+    GEMM with an fp32 result, everything behind it one kernel per direction that keeps a sample's routing state on chip
+    (functional.dynamic_routing); the (B, K', N, R) tensors of the reference are never built beyond the noise itself.
+    ``forward(emb_inputs, noise=None)``: without ``noise`` the layer draws ``torch.randn(B, K', N, R)`` in the input's
+    dtype on its device, which consumes the generator as the reference's ``randn_like`` does.
+    Outside 1 <= N <= 128, R <= 128, K' <= 8, fp32 / bf16 on the device, and with ``TRS_DYNAMIC_ROUTING=0``, the ATen
+    composition runs.  The fused path has not been timed against it yet (profiles/dynamic_routing_kernels.md).  Deviations: the caller's tensor keeps its names (the reference renames it in place); a sample of
+    all-zero rows gets a zero gradient from the kernel where the reference's autograd gives NaN."""
+
+    @property
+    def inputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'inputs': ('B', 'N', 'E',)}
+
+    @property
+    def outputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'inputs': ('B', 'Number of Caps', 'Routed Size',)}
+
+    def __init__(self, embed_size: int, routed_size: int, max_num_caps: int, num_iter: int):
+        super().__init__()
+        self.max_num_caps = max_num_caps
+        self.num_caps = None
+        self.num_iter = num_iter
+        self.S = nn.Parameter(torch.randn(embed_size, routed_size))
+
+    def _dynamic_interest_number(self, i: int) -> int:
+        return int(max(1, min(self.max_num_caps, math.log2(i))))
+
+    @staticmethod
+    def _squash(z: torch.Tensor) -> torch.Tensor:
+        n2 = torch.sum(torch.pow(z, 2), dim=-1, keepdim=True)
+        return (n2 / (1 + n2)) * (z / (torch.sqrt(n2) + 1e-8))
+
+    def _forward_aten(self, x: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+        """dynamic_routing.py:113-172 on un-named tensors, with the noise handed in"""
+        priors = torch.matmul(x, self.S).unsqueeze(1).repeat(1, noise.shape[1], 1, 1)
+        priors_temp = priors.detach()
+        coup = noise.detach()
+        for _ in range(self.num_iter - 1):
+            weights = torch.softmax(coup, dim=1)
+            v = self._squash((weights * priors_temp).sum(dim=2))
+            coup = coup + torch.matmul(priors_temp, v.unsqueeze(-1))
+        weights = torch.softmax(coup, dim=1)
+        return self._squash((weights * priors).sum(dim=2))
+
+    def forward(self, emb_inputs: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = _strip(emb_inputs)
+        if x.dim() != 3:
+            raise ValueError(f'expected (B, N, E), got {tuple(x.shape)}')
+        B, N, _ = x.shape
+        R = self.S.shape[1]
+        self.num_caps = self._dynamic_interest_number(N)
+        if noise is None:
+            noise = torch.randn(B, self.num_caps, N, R, dtype=x.dtype, device=x.device)
+        else:
+            noise = _strip(noise)
+            if tuple(noise.shape) != (B, self.num_caps, N, R):
+                raise ValueError(f'noise ({B}, {self.num_caps}, {N}, {R}) expected, got {tuple(noise.shape)}')
+        S = _strip(self.S)
+        if (DYNAMIC_ROUTING and x.is_cuda and S.dtype == x.dtype and noise.dtype == x.dtype and self.num_iter >= 1
+                and F_.dynamic_routing_path(N, R, self.num_caps, x.dtype) != 0):
+            outputs = F_.dynamic_routing(x, S, noise, self.num_iter)
+        else:
+            outputs = self._forward_aten(x, noise)
+        outputs.names = ('B', 'N', 'O',)
+        return outputs
+
+
 # aliases, layers/ctr/__init__.py:23-35
 MOELayer = MixtureOfExpertsLayer
 AFMLayer = AttentionalFactorizationMachineLayer

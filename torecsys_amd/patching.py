@@ -7,7 +7,8 @@ What is rebound: the interaction layers of SURVEY §8a/§8f-N3, the SENET / comp
 layers/ctr/__init__.py:24,34,35; the first layer of the FiBiNET and FAT-DeepFFM models, whose ``forward``s run as they are
 over the drop-ins), the mixture-of-experts layer (``MixtureOfExpertsLayer`` and its alias ``MOELayer`` --
 layers/ctr/__init__.py:16,32; ``MultiGateMixtureOfExpertsModel`` and ``DeepMixtureOfExpertsModel`` construct on it unchanged,
-models/ctr/multigate_moe.py:56, deep_moe.py:55, and need no head wrapper), the per-field / deep MLP
+models/ctr/multigate_moe.py:56, deep_moe.py:55, and need no head wrapper), the capsule routing of MIND
+(``DynamicRoutingLayer`` -- layers/ctr/__init__.py:12; the reference ships no model on it), the per-field / deep MLP
 (``MultilayerPerceptionLayer`` and its aliases ``DNNLayer``, ``DenseLayer``, ``FullyConnectLayer``,
 ``FeedForwardLayer`` -- layers/ctr/__init__.py:23-35; this is what ``DeepAndCrossNetworkModel.deep``,
 ``DeepFactorizationMachineModel.deep`` and ``XDeepFactorizationMachineModel.deep`` are built from,
@@ -49,6 +50,7 @@ _MLP_NAMES = ["MultilayerPerceptionLayer", "DNNLayer", "DenseLayer", "FullyConne
 _INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFieldAwareEmbedding", "ListIndicesEmbedding"]
 _ROUTER_NAMES = ["Inputs"]
 _MOE_NAMES = ["MixtureOfExpertsLayer", "MOELayer"]
+_ROUTING_NAMES = ["DynamicRoutingLayer"]
 _saved = {}
 _saved_defaults = {}
 
@@ -169,7 +171,7 @@ def patch(torecsys_pkg=None, fuse_fm: bool = True, mlp: bool = True, router: boo
     ``heads``: wrap the three first-order models' ``forward`` with the one-kernel head (module docstring)."""
     if torecsys_pkg is None:
         torecsys_pkg = importlib.import_module("torecsys")
-    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs), (_MOE_NAMES, _layers)]
+    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs), (_MOE_NAMES, _layers), (_ROUTING_NAMES, _layers)]
     if mlp:
         groups.append((_MLP_NAMES, _layers))
     if router:
