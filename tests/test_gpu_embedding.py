@@ -6,6 +6,7 @@ import torch
 
 from conftest import LAYER_SHAPES, rel_err
 from oracle import cpu_ref as O
+from scatter_ref import _check_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -448,22 +449,6 @@ def test_fused_sparse_adam_equals_torch_sparse_adam(dev, dtype, E):
     tol = 1e-5 if dtype == torch.float32 else 1e-2          # north_star's bounds (measured: 5e-7 / 5.4e-3)
     assert rel_err(fused.embedding.weight.detach().float().cpu(), master.detach().cpu()) <= tol
     assert not torch.equal(master.detach().cpu(), w.float())
-
-
-def _check_csr(rb, rows_flat, V):
-    """row_start = exclusive prefix sum of the per-row lookup counts; perm lists, row by row, exactly the flat
-    lookup positions that hit the row (any order inside a row)."""
-    valid = (rows_flat >= 0) & (rows_flat < V)
-    counts = torch.bincount(rows_flat[valid], minlength=V)
-    expect_start = torch.zeros(V + 1, dtype=torch.int64, device=rows_flat.device)
-    expect_start[1:] = counts.cumsum(0)
-    assert torch.equal(rb.row_start.long(), expect_start)
-    total = int(expect_start[-1])
-    perm = rb.perm[:total].long()
-    assert torch.equal(perm.sort().values, valid.nonzero().flatten())       # a permutation of the valid lookups
-    got_rows = rows_flat[perm]
-    assert torch.equal(got_rows, got_rows.sort().values)                    # grouped by destination row
-    assert torch.equal(torch.bincount(got_rows, minlength=V), counts)
 
 
 @pytest.mark.parametrize("case", ["criteo", "tiny_fields", "spill", "unsorted_offsets", "int32", "huge_field", "zipf",

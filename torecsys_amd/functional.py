@@ -333,6 +333,17 @@ def _fm_grad_operand(g_fm: torch.Tensor) -> torch.Tensor:
     return g_fm.contiguous()
 
 
+def _walk_takes_vectors(table: torch.Tensor, *operands: Optional[torch.Tensor]) -> bool:
+    """trs_scatter_rows' choice of walk, restated: rows of 1, 2, 4 ... 64 whole 16-byte vectors behind 16-byte aligned
+    pointers are reduced by lane groups; every other width or alignment (E = 12 fp32: three vectors; a table that is a
+    misaligned view) takes the element walk -- which has no companion-table form (trs_scatter_rows_first rejects it)."""
+    row_bytes = table.shape[1] * table.element_size()
+    vecs = row_bytes // 16
+    if row_bytes % 16 != 0 or vecs & (vecs - 1) != 0 or vecs > 64:
+        return False
+    return all(t is None or t.data_ptr() % 16 == 0 for t in operands)
+
+
 def scatter_rows(rb: RowBuckets, like_table: torch.Tensor, g_rows: Optional[torch.Tensor] = None,
                  g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
                  padding_row: int = -1, g_rows_batch_stride: int = 0) -> torch.Tensor:
@@ -830,12 +841,15 @@ class _EmbedFM(Function):
         has_fm = g_fm is not None
         pad = ctx.padding_idx      # nn.Embedding(padding_idx=): that row of the E-wide table receives no gradient
         if (ctx.fields and ctx.opt is None and g_first is not None and (has_emb or has_fm) and pad < 0
-                and ctx.needs_input_grad[0] and ctx.needs_input_grad[3] and (E * weight.element_size()) % 16 == 0):
-            gw, gfw = scatter_rows_first(rb, weight, first_weight, g_first.contiguous(),
-                                         g_rows=g_emb.contiguous() if has_emb else None,
-                                         g_bcast=_fm_grad_operand(g_fm) if has_fm else None,
-                                         fm_sum=fm_sum if has_fm else None)
-            return gw, None, None, gfw, None, None, None, None
+                and ctx.needs_input_grad[0] and ctx.needs_input_grad[3]):
+            g_rows = g_emb.contiguous() if has_emb else None
+            g_bcast = _fm_grad_operand(g_fm) if has_fm else None
+            # (a per-sample FM gradient is read as scalars: its own alignment does not matter)
+            if _walk_takes_vectors(weight, g_rows, weight if has_fm else None,
+                                   g_bcast if has_fm and _bcast_cols(g_bcast, E) == E else None):
+                gw, gfw = scatter_rows_first(rb, weight, first_weight, g_first.contiguous(), g_rows=g_rows,
+                                             g_bcast=g_bcast, fm_sum=fm_sum if has_fm else None)
+                return gw, None, None, gfw, None, None, None, None
         if ctx.needs_input_grad[0]:
             if has_emb or has_fm:
                 gw = _apply_or_grad(rb, weight, ctx.opt, g_rows=g_emb.contiguous() if has_emb else None,
