@@ -141,61 +141,46 @@ int trs_scatter_rows_first(const void* g_rows, int64_t g_rows_batch_stride, cons
                            const void* g_first, void* grad_first, void* workspace, size_t ws_bytes,
                            trs_stream_t stream);
 
-/* Same walk, but the finished row sum is APPLIED to the table row in place by a fused sparse optimizer
- *  instead of being written out: optimizer 1 = SGD  w -= lr*g;
- * 2 = Adagrad  state += g*g, w -= lr*g/(sqrt(state)+eps)  (state: V x E fp32).  Exactly equivalent to the
- * dense torch.optim.SGD / Adagrad step (no momentum / weight decay): rows nobody looked up have zero gradient
- * and are not touched -- neither the dense V x E gradient nor a dense optimizer pass over the table exists.  */
+/* Same walk, but the finished row sum g is APPLIED to the table row in place by a fused sparse optimizer (SURVEY.md
+ * section 8f N1) instead of being written out.  Rows nobody looked up have zero gradient and are not touched -- neither
+ * the dense V x E gradient nor a dense optimizer pass over the table exists.  Both update entries end in the same
+ * optimizer tail:
+ *   optimizer  1 = SGD      w -= lr*g
+ *              2 = Adagrad  state += g*g;  w -= lr*g/(sqrt(state)+eps)
+ *              3 = lazy Adam (torch.optim.SparseAdam semantics: moments and weights of looked-up rows only; the reference
+ *                  trains with dense Adam, trainer/torecsys_pipeline.py:562-578, which cannot exist at 1 B rows)
+ *                  m = m + (g - m)(1 - beta1);  v = v + (g*g - v)(1 - beta2);  w -= lr * m / (sqrt(v) + eps)
+ *                  where the step size passed as lr is already bias-corrected by the caller:
+ *                  lr * sqrt(1 - beta2^t) / (1 - beta1^t); state = exp_avg (m), state2 = exp_avg_sq (v)
+ *              1 and 2 are exactly the dense torch.optim.SGD / Adagrad step (no momentum / weight decay).
+ *   lr, lr_dev lr_dev == NULL: the step size is lr, by value.  lr_dev != NULL: it is ONE fp32 in device memory, read by
+ *              the kernels when they apply a row, and lr is ignored: a launch captured into a hipGraph then follows a
+ *              learning rate written between replays (FusedSparse*.set_lr) and Adam's per-step bias correction
+ *              (trs_adam_step_size below) instead of repeating the capture-time value.
+ *   beta1, beta2   Adam only, each in [0, 1).
+ *   state, state2  V x E fp32; state is needed by optimizers 2 and 3, state2 by 3; NULL otherwise.
+ * The tail is validated before anything is launched (TRS_EINVAL).                                                    */
 int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
                             const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
                             int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                            int32_t optimizer, float lr, float eps, float* state, void* workspace,
-                            size_t ws_bytes, trs_stream_t stream);
-
-/* Same pass with a lazy Adam step (torch.optim.SparseAdam semantics: moments and weights of looked-up rows only;
- * the reference trains with dense Adam, trainer/torecsys_pipeline.py:562-578, which cannot exist at 1 B rows):
- *   m = m + (g - m)(1 - beta1);  v = v + (g*g - v)(1 - beta2);  w -= step_size * m / (sqrt(v) + eps)
- * with step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller; exp_avg / exp_avg_sq: V x E fp32. */
-int trs_scatter_rows_update_adam(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
-                                 const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
-                                 int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                                 float step_size, float beta1, float beta2, float eps, float* exp_avg,
-                                 float* exp_avg_sq, void* workspace, size_t ws_bytes, trs_stream_t stream);
+                            int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1, float beta2,
+                            float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
 /* The same fused optimizer step when the bucketed rows are a COMPACT list of U distinct table rows (the owner side of
  * a row-sharded table: a 125 M-row shard cannot afford a V-sized bucket index per step):  row_start (U+1) / perm (K)
  * bucket the K gradient rows g_rows (K,E) by compact row u, row_map[u] is the table row that compact row u updates
- * (distinct values).  optimizer 1 = SGD, 2 = Adagrad (state), 3 = lazy Adam (lr = bias-corrected step size, state =
- * exp_avg, state2 = exp_avg_sq); state buffers are V x E fp32.  Workspace: trs_scatter_workspace_bytes(K, 1, E, dtype). */
+ * (distinct values; an entry outside [0, V) updates nothing).  The optimizer tail is the one described above; state
+ * buffers are V x E fp32.  U == 0 or K == 0: nothing to do, TRS_OK.  Workspace: trs_scatter_workspace_bytes(K, 1, E,
+ * dtype). */
 int trs_scatter_rows_update_mapped(const void* g_rows, void* table, const int32_t* row_map, const int32_t* row_start,
                                    const int32_t* perm, int64_t K, int64_t U, int64_t V, int32_t E, int32_t dtype,
-                                   int32_t optimizer, float lr, float eps, float beta1, float beta2, float* state,
-                                   float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
-
-/* ---- fused optimizer steps whose step size lives on the DEVICE (hipGraph-capturable optimizers) ------------------
- * trs_scatter_rows_update / _adam / _mapped with the by-value step size replaced by a pointer to ONE fp32 in device
- * memory, read by the kernels when they apply a row: a launch captured into a hipGraph follows a learning rate written
- * between replays (FusedSparse*.set_lr) and Adam's per-step bias correction (trs_adam_step_size below) instead of
- * repeating the capture-time value.  Everything else -- arguments, arithmetic, workspace -- is that of the sibling. */
-int trs_scatter_rows_update_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
-                                const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
-                                int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                                int32_t optimizer, const float* lr_dev, float eps, float* state, void* workspace,
-                                size_t ws_bytes, trs_stream_t stream);
-int trs_scatter_rows_update_adam_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
-                                     const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
-                                     int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                                     const float* step_size_dev, float beta1, float beta2, float eps, float* exp_avg,
-                                     float* exp_avg_sq, void* workspace, size_t ws_bytes, trs_stream_t stream);
-/* optimizer 3 (lazy Adam): lr_dev points at the bias-corrected step size */
-int trs_scatter_rows_update_mapped_dev(const void* g_rows, void* table, const int32_t* row_map, const int32_t* row_start,
-                                       const int32_t* perm, int64_t K, int64_t U, int64_t V, int32_t E, int32_t dtype,
-                                       int32_t optimizer, const float* lr_dev, float eps, float beta1, float beta2,
-                                       float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
+                                   int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1, float beta2,
+                                   float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
 /* Adam's per-step scalars, on the device (one thread):  *step += 1;  *step_size_dev = *lr_dev * sqrt(1 - beta2^t) /
- * (1 - beta1^t) with t the new *step -- computed in double, rounded once to fp32 (what the host computes for
- * trs_scatter_rows_update_adam).  Enqueued once per table per backward in front of the *_dev update. */
+ * (1 - beta1^t) with t the new *step -- computed in double, rounded once to fp32 (what the host computes when it
+ * passes the step size by value).  Enqueued once per table per backward in front of the update that reads it through
+ * lr_dev. */
 int trs_adam_step_size(int64_t* step, const float* lr_dev, double beta1, double beta2, float* step_size_dev,
                        trs_stream_t stream);
 

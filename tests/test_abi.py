@@ -51,6 +51,44 @@ def test_argument_errors_without_gpu(lib):
         _abi.call("trs_pair_dot_fwd", null, 1, 2, 4, 0, null, null)
 
 
+def test_fused_update_tail_is_validated_without_gpu(lib):
+    """The optimizer tail both fused-update entries share (optimizer, lr, lr_dev, eps, beta1, beta2, state, state2) is
+    rejected with TRS_EINVAL and a message naming the entry before anything is launched; a mapped update of no rows is
+    TRS_OK.  No call here carries a fully valid argument set with non-zero sizes."""
+    from torecsys_amd import _abi
+    null, p = ctypes.c_void_p(0), ctypes.c_void_p(16)
+    EINVAL = -1
+    good = dict(optimizer=3, beta1=0.9, beta2=0.999, state=p, state2=p, table=p, row_map=p, U=5)
+
+    def tail(a):
+        return (a["optimizer"], 0.1, null, 1e-8, a["beta1"], a["beta2"], a["state"], a["state2"], p, 1 << 20, null)
+
+    def plain(**kw):
+        a = {**good, **kw}
+        return lib.trs_scatter_rows_update(p, 0, null, 0, null, a["table"], p, p, 40, 10, 16, 4, 0, -1, *tail(a))
+
+    def mapped(**kw):
+        a = {**good, **kw}
+        return lib.trs_scatter_rows_update_mapped(p, a["table"], a["row_map"], p, p, 40, a["U"], 10, 16, 0, *tail(a))
+
+    bad_tails = [dict(optimizer=0), dict(optimizer=4), dict(optimizer=2, state=null), dict(optimizer=3, state2=null),
+                 dict(beta1=1.0), dict(beta2=-0.1), dict(table=null)]
+    for name, entry in (("scatter_rows_update", plain), ("scatter_rows_update_mapped", mapped)):
+        for kw in bad_tails:
+            assert entry(**kw) == EINVAL, (name, kw)
+            assert _abi.last_error().startswith(name + ":"), (name, kw, _abi.last_error())
+    assert mapped(row_map=null) == EINVAL and _abi.last_error().startswith("scatter_rows_update_mapped:")
+    for opt_kw in (dict(optimizer=1, state=null, state2=null), dict(optimizer=2, state2=null), dict()):
+        assert mapped(U=0, **opt_kw) == 0
+    # a bad tail is refused even where there is nothing to update
+    assert mapped(U=0, optimizer=4) == EINVAL
+    retired = ["trs_scatter_rows_update_adam", "trs_scatter_rows_update_dev", "trs_scatter_rows_update_adam_dev",
+               "trs_scatter_rows_update_mapped_dev"]
+    for n in retired:
+        assert not hasattr(lib, n), f"{n} is still exported"
+        assert n not in _abi.SIGNATURES
+
+
 def test_no_oracle_import_in_product():
     pkg = os.path.join(ROOT, "torecsys_amd")
     for f in os.listdir(pkg):

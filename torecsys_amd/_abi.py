@@ -21,6 +21,9 @@ TRS_I64, TRS_I32 = 0, 1
 
 _P, _I32, _I64, _SZ, _F32 = c_void_p, c_int32, c_int64, c_size_t, ctypes.c_float
 
+# what both fused-update entries end in: optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream
+_OPTIMIZER_TAIL = [_I32, _F32, _P, _F32, _F32, _F32, _P, _P, _P, _SZ, _P]
+
 # name -> (restype, argtypes); must list every symbol of include/trs_abi.h (tests/test_abi.py checks)
 SIGNATURES = {
     "trs_version": (c_int32, []),
@@ -84,20 +87,9 @@ SIGNATURES = {
     "trs_scatter_rows": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P]),
     "trs_scatter_rows_first": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _P, _P, _P, _P,
                                          _SZ, _P]),
-    "trs_scatter_rows_update": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _I32,
-                                          ctypes.c_float, ctypes.c_float, _P, _P, _SZ, _P]),
-    "trs_scatter_rows_update_adam": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64,
-                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P,
-                                               _P, _SZ, _P]),
-    "trs_scatter_rows_update_mapped": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_float,
-                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ, _P]),
-    "trs_scatter_rows_update_dev": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64, _I32,
-                                              _P, ctypes.c_float, _P, _P, _SZ, _P]),
-    "trs_scatter_rows_update_adam_dev": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64,
-                                                   _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ,
-                                                   _P]),
-    "trs_scatter_rows_update_mapped_dev": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I32, _P,
-                                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _SZ, _P]),
+    "trs_scatter_rows_update": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64,
+                                          *_OPTIMIZER_TAIL]),
+    "trs_scatter_rows_update_mapped": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, *_OPTIMIZER_TAIL]),
     "trs_adam_step_size": (c_int32, [_P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
     "trs_compact_rows_slots": (_I64, [_I64]),
     "trs_compact_rows": (c_int32, [_P, _I64, _P, _I64, _P, _P]),

@@ -468,7 +468,7 @@ struct RowSink {
   // the owner side of a row-sharded table, whose 125 M-row shard cannot afford a V-sized bucket index per step.
   const int32_t* row_map = nullptr;
   int64_t map_rows = 0;     // rows of the table row_map points into: an entry outside [0, map_rows) is skipped
-  // Optional: the step size lives on the DEVICE (one fp32, the *_dev entries): a launch captured into a hipGraph then
+  // Optional: the step size lives on the DEVICE (one fp32, the entries' lr_dev): a launch captured into a hipGraph then
   // follows set_lr() / Adam's per-step bias correction from replay to replay; `lr` is ignored when this is set
   const float* lr_dev = nullptr;
 };
@@ -1144,72 +1144,103 @@ static int log2_lanes_sc(int row_bytes) {
   return l;
 }
 
+// the sink of the two gradient-writing entries: every finished row sum is written out
+static const RowSink GRAD_SINK{0, 0.f, 0.f, nullptr};
+
+// Host side of one bucket walk: what an entry hands to scatter_rows_impl (operands, bucket index, sizes, destination,
+// sink, stream) and what scatter_rows_impl derives from it (gbs, B, the three regions carved from the workspace).
+// Host only: never a kernel argument.
+struct WalkJob {
+  // gradient operands
+  const void* g_rows = nullptr;
+  int64_t gbs = 0;                 // rows between the samples of g_rows; entries pass g_rows_batch_stride (0 = N)
+  const void* g_fm = nullptr;
+  int g_fm_cols = 0;
+  const float* fm_sum = nullptr;
+  const void* table = nullptr;
+  // bucket index
+  const int32_t* row_start = nullptr;
+  const int32_t* perm = nullptr;
+  // sizes
+  int64_t B = 0, V = 0;
+  int E = 0, N = 0;
+  int64_t padding_row = -1;
+  // destination (the gradient table, or the table itself under a fused optimizer) and the E = 1 companion pair
+  void* out = nullptr;
+  const void* g_first = nullptr;
+  void* grad_first = nullptr;
+  // workspace regions: queue(s) of hot rows, staged FM rows, chunk partials
+  int32_t* long_rows = nullptr;
+  void* tg = nullptr;
+  float* scratch = nullptr;
+  RowSink sink = GRAD_SINK;
+  hipStream_t s = nullptr;
+};
+
 template <typename T, int LOG2L>
-static void scatter_group_launch(const void* g_rows, const void* g_fm, const float* fm_sum, const void* table,
-                                 const int32_t* row_start, const int32_t* perm, int64_t V, int N, int64_t gbs,
-                                 int64_t padding_row, void* grad, int32_t* long_rows, void* tg, float* scratch,
-                                 int64_t B, RowSink sink, hipStream_t s, int gcols, const void* g_first = nullptr,
-                                 void* grad_first = nullptr) {
+static void scatter_group_launch(const WalkJob& j) {
   const int L = 1 << LOG2L;
+  hipStream_t s = j.s;
   FmSrc fs{nullptr, nullptr, 0, 0};
   bool scal = false;
-  if (g_fm != nullptr && fm_sum != nullptr) {
-    if (gcols == 1) {      // (L == 1 too: a (B,1) buffer must never be read as B 16-byte rows)
-      uint4* gvec = (uint4*)tg + B * L;
-      hipLaunchKernelGGL((build_tg1_kernel<T>), dim3(stream_grid(B * L, 256, 4096)), dim3(256), 0, s, (const T*)g_fm,
-                         fm_sum, (uint4*)tg, gvec, B, L);
-      fs = FmSrc{(const uint4*)tg, gvec, L, 1};
-      fs.g1 = g_fm;
-      scal = g_first == nullptr;
+  const void* fm = j.g_fm;       // the FM operand the walk reads: the staged [g*S | g] rows when the FM term is folded in
+  if (j.g_fm != nullptr && j.fm_sum != nullptr) {
+    if (j.g_fm_cols == 1) {      // (L == 1 too: a (B,1) buffer must never be read as B 16-byte rows)
+      uint4* gvec = (uint4*)j.tg + j.B * L;
+      hipLaunchKernelGGL((build_tg1_kernel<T>), dim3(stream_grid(j.B * L, 256, 4096)), dim3(256), 0, s,
+                         (const T*)j.g_fm, j.fm_sum, (uint4*)j.tg, gvec, j.B, L);
+      fs = FmSrc{(const uint4*)j.tg, gvec, L, 1};
+      fs.g1 = j.g_fm;
+      scal = j.g_first == nullptr;
     } else {
-      hipLaunchKernelGGL((build_tg_kernel<T>), dim3(stream_grid(B * L, 256, 4096)), dim3(256), 0, s, (const uint4*)g_fm,
-                         fm_sum, (uint4*)tg, B, L);
-      fs = FmSrc{(const uint4*)tg, (const uint4*)tg + L, 2 * L, 2 * L};
+      hipLaunchKernelGGL((build_tg_kernel<T>), dim3(stream_grid(j.B * L, 256, 4096)), dim3(256), 0, s,
+                         (const uint4*)j.g_fm, j.fm_sum, (uint4*)j.tg, j.B, L);
+      fs = FmSrc{(const uint4*)j.tg, (const uint4*)j.tg + L, 2 * L, 2 * L};
     }
-    g_fm = tg;
+    fm = j.tg;
   }
-  const int grid = stream_grid(V * L, 256, 256 * 32);
-  const bool hg = g_rows != nullptr, hf = g_fm != nullptr;
+  const int grid = stream_grid(j.V * L, 256, 256 * 32);
+  const bool hg = j.g_rows != nullptr, hf = fm != nullptr;
 #define TRS_SC_TAIL(HG, HF, SC)                                                                                 \
   do {                                                                                                          \
     hipLaunchKernelGGL((scatter_long_rows_kernel<T, LOG2L, HG, HF, SC>), dim3(2048), dim3(256), 0, s,            \
-                       (const uint4*)g_rows, (const uint4*)g_fm, fm_sum, (const uint4*)table, row_start, perm, N, \
-                       gbs, (uint4*)grad, long_rows, scratch, sink, fs);                                              \
-    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF>), dim3(64), dim3(256), 0, s, fm_sum,           \
-                       (const uint4*)table, row_start, (uint4*)grad, long_rows, scratch, sink);                       \
+                       (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
+                       j.perm, j.N, j.gbs, (uint4*)j.out, j.long_rows, j.scratch, j.sink, fs);                  \
+    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF>), dim3(64), dim3(256), 0, s, j.fm_sum,    \
+                       (const uint4*)j.table, j.row_start, (uint4*)j.out, j.long_rows, j.scratch, j.sink);      \
   } while (0)
 #define TRS_SC(HG, HF)                                                                                          \
   do {                                                                                                          \
-    if (g_first != nullptr)                                                                                     \
+    if (j.g_first != nullptr)                                                                                   \
       hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF, true>), dim3(grid), dim3(256), 0, s,       \
-                         (const uint4*)g_rows, (const uint4*)g_fm, fm_sum, (const uint4*)table, row_start, perm, \
-                         V, N, gbs, padding_row, (uint4*)grad, long_rows, sink, fs, (const T*)g_first,           \
-                         (T*)grad_first);                                                                        \
+                         (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start, \
+                         j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs,        \
+                         (const T*)j.g_first, (T*)j.grad_first);                                                \
     else                                                                                                        \
       hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF>), dim3(grid), dim3(256), 0, s,             \
-                         (const uint4*)g_rows, (const uint4*)g_fm, fm_sum, (const uint4*)table, row_start, perm, \
-                         V, N, gbs, padding_row, (uint4*)grad, long_rows, sink, fs);                             \
+                         (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start, \
+                         j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);       \
     TRS_SC_TAIL(HG, HF, false);                                                                                 \
   } while (0)
 #define TRS_SCS(HG, CHF_)                                                                                       \
   do {                                                                                                          \
     hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, true, false, true, CHF_>), dim3(grid), dim3(256), 0, s, \
-                       (const uint4*)g_rows, (const uint4*)g_fm, fm_sum, (const uint4*)table, row_start, perm,   \
-                       V, N, gbs, padding_row, (uint4*)grad, long_rows, sink, fs);                               \
+                       (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
+                       j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);         \
     TRS_SC_TAIL(HG, true, true);                                                                                \
   } while (0)
-  const bool lean = scal && (B * N) * (int64_t)L < ((int64_t)1 << 31) && V * (int64_t)L < ((int64_t)1 << 31) &&
-                    N >= 2 && (B * N) * (int64_t)N < ((int64_t)1 << 32) && gbs == N;   // (mulhi by ceil(2^32/N) is exact)
+  const bool lean = scal && (j.B * j.N) * (int64_t)L < ((int64_t)1 << 31) && j.V * (int64_t)L < ((int64_t)1 << 31) &&
+                    j.N >= 2 && (j.B * j.N) * (int64_t)j.N < ((int64_t)1 << 32) && j.gbs == j.N;   // (mulhi by ceil(2^32/N) is exact)
   if (lean) {
-    const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + (unsigned)N - 1) / (unsigned)N);
+    const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + (unsigned)j.N - 1) / (unsigned)j.N);
     if (hg)
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true>), dim3(grid), dim3(256), 0, s, (const uint4*)g_rows,
-                         (const uint4*)tg, (const T*)fs.g1, (const uint4*)table, row_start, perm, (int)V, (unsigned)N,
-                         rcpN, (int)padding_row, (uint4*)grad, long_rows, sink);
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+                         (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
+                         (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     else
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false>), dim3(grid), dim3(256), 0, s, (const uint4*)g_rows,
-                         (const uint4*)tg, (const T*)fs.g1, (const uint4*)table, row_start, perm, (int)V, (unsigned)N,
-                         rcpN, (int)padding_row, (uint4*)grad, long_rows, sink);
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+                         (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
+                         (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     if (hg) TRS_SC_TAIL(true, true, true);
     else TRS_SC_TAIL(false, true, true);
   } else if (scal) {
@@ -1221,45 +1252,46 @@ static void scatter_group_launch(const void* g_rows, const void* g_fm, const flo
 #undef TRS_SC
 #undef TRS_SCS
 #undef TRS_SC_TAIL
-  if (g_first != nullptr)
-    hipLaunchKernelGGL((scatter_first_long_kernel<T>), dim3(64), dim3(256), 0, s, (const T*)g_first, row_start, perm,
-                       long_rows, (T*)grad_first);
+  if (j.g_first != nullptr)
+    hipLaunchKernelGGL((scatter_first_long_kernel<T>), dim3(64), dim3(256), 0, s, (const T*)j.g_first, j.row_start,
+                       j.perm, j.long_rows, (T*)j.grad_first);
 }
 
 template <typename T>
-static int scatter_launch(const void* g_rows, const void* g_fm, const float* fm_sum, const void* table,
-                          const int32_t* row_start, const int32_t* perm, int64_t V, int E, int N, int64_t gbs,
-                          int64_t padding_row, void* grad, int32_t* long_rows, void* tg, float* scratch, int64_t B,
-                          RowSink sink, hipStream_t s, int gcols, const void* g_first = nullptr,
-                          void* grad_first = nullptr) {
-  const int lg = log2_lanes_sc(E * (int)sizeof(T));
-  const bool scal = gcols == 1 && E > 1 && fm_sum != nullptr;      // g_fm read as scalars: no alignment requirement
-  const bool al = aligned16(g_rows) && (scal || aligned16(g_fm)) && aligned16(table) && aligned16(grad) && aligned16(fm_sum);
+static int scatter_launch(const WalkJob& j) {
+  const int lg = log2_lanes_sc(j.E * (int)sizeof(T));
+  const bool scal = j.g_fm_cols == 1 && j.E > 1 && j.fm_sum != nullptr;      // g_fm read as scalars: no alignment requirement
+  const bool al = aligned16(j.g_rows) && (scal || aligned16(j.g_fm)) && aligned16(j.table) && aligned16(j.out) &&
+                  aligned16(j.fm_sum);
   if (lg >= 0 && al) {
     switch (lg) {
-      case 0: scatter_group_launch<T, 0>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      case 1: scatter_group_launch<T, 1>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      case 2: scatter_group_launch<T, 2>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      case 3: scatter_group_launch<T, 3>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      case 4: scatter_group_launch<T, 4>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      case 5: scatter_group_launch<T, 5>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
-      default: scatter_group_launch<T, 6>(g_rows, g_fm, fm_sum, table, row_start, perm, V, N, gbs, padding_row, grad, long_rows, tg, scratch, B, sink, s, gcols, g_first, grad_first); break;
+      case 0: scatter_group_launch<T, 0>(j); break;
+      case 1: scatter_group_launch<T, 1>(j); break;
+      case 2: scatter_group_launch<T, 2>(j); break;
+      case 3: scatter_group_launch<T, 3>(j); break;
+      case 4: scatter_group_launch<T, 4>(j); break;
+      case 5: scatter_group_launch<T, 5>(j); break;
+      default: scatter_group_launch<T, 6>(j); break;
     }
   } else {
-    if (g_first != nullptr) return 1;   // the companion table rides only in the 16-byte-vector walk
+    // the companion table rides only in the 16-byte-vector walk
+    TRS_REQUIRE(j.g_first == nullptr, TRS_ESHAPE,
+                "scatter_rows_first: rows must be whole 16-byte vectors (E*sizeof %% 16 == 0)");
+    hipStream_t s = j.s;
     // queue of the split rows: behind the plain queue of long rows (long_row_queue_bytes); its counter was zeroed with
     // the other one (scatter_rows_impl)
-    int32_t* split_rows = long_rows + 1 + (B * N / LONG_ROW_ELEM + 2);
-    hipLaunchKernelGGL((scatter_rows_elem_kernel<T>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
-                       (const T*)g_rows, (const T*)g_fm, fm_sum, (const T*)table, row_start, perm, V, E, N, gbs,
-                       padding_row, (T*)grad, long_rows, sink, gcols, split_rows, scratch);
-    hipLaunchKernelGGL((scatter_long_rows_elem_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)g_rows,
-                       (const T*)g_fm, fm_sum, (const T*)table, row_start, perm, E, N, gbs, (T*)grad, long_rows, sink,
-                       gcols);
-    hipLaunchKernelGGL((scatter_split_rows_elem_kernel<T>), dim3(512), dim3(256), 0, s, (const T*)g_rows,
-                       (const T*)g_fm, fm_sum, row_start, perm, E, N, gbs, split_rows, scratch, gcols);
-    hipLaunchKernelGGL((scatter_split_rows_finish_elem_kernel<T>), dim3(16), dim3(256), 0, s, (const T*)g_fm, fm_sum,
-                       (const T*)table, E, (T*)grad, split_rows, scratch, sink);
+    int32_t* split_rows = j.long_rows + 1 + (j.B * j.N / LONG_ROW_ELEM + 2);
+    hipLaunchKernelGGL((scatter_rows_elem_kernel<T>), dim3(stream_grid(j.V * j.E, 256, 256 * 32)), dim3(256), 0, s,
+                       (const T*)j.g_rows, (const T*)j.g_fm, j.fm_sum, (const T*)j.table, j.row_start, j.perm, j.V, j.E,
+                       j.N, j.gbs, j.padding_row, (T*)j.out, j.long_rows, j.sink, j.g_fm_cols, split_rows, j.scratch);
+    hipLaunchKernelGGL((scatter_long_rows_elem_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)j.g_rows,
+                       (const T*)j.g_fm, j.fm_sum, (const T*)j.table, j.row_start, j.perm, j.E, j.N, j.gbs, (T*)j.out,
+                       j.long_rows, j.sink, j.g_fm_cols);
+    hipLaunchKernelGGL((scatter_split_rows_elem_kernel<T>), dim3(512), dim3(256), 0, s, (const T*)j.g_rows,
+                       (const T*)j.g_fm, j.fm_sum, j.row_start, j.perm, j.E, j.N, j.gbs, split_rows, j.scratch,
+                       j.g_fm_cols);
+    hipLaunchKernelGGL((scatter_split_rows_finish_elem_kernel<T>), dim3(16), dim3(256), 0, s, (const T*)j.g_fm, j.fm_sum,
+                       (const T*)j.table, j.E, (T*)j.out, split_rows, j.scratch, j.sink);
   }
   return check_launch("scatter_rows");
 }
@@ -1431,39 +1463,28 @@ extern "C" size_t trs_scatter_workspace_bytes(int64_t BN, int32_t N, int32_t E, 
          align_up(long_row_entries(BN) * 2 * E * 4, 256);
 }
 
-static int scatter_rows_impl(RowSink sink, const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
-                                int32_t g_fm_cols, const float* fm_sum, const void* table, const int32_t* row_start,
-                                const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
-                                int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
-                                trs_stream_t stream, const void* g_first = nullptr, void* grad_first = nullptr) {
-  TRS_REQUIRE(row_start && perm && grad_table && workspace, TRS_EINVAL, "scatter_rows: NULL pointer");
-  TRS_REQUIRE(g_rows || g_fm, TRS_EINVAL, "scatter_rows: need g_rows and/or g_fm");
-  TRS_REQUIRE((fm_sum == nullptr) || (g_fm && table), TRS_EINVAL, "scatter_rows: fm_sum needs g_fm and table");
-  TRS_REQUIRE(g_fm == nullptr || g_fm_cols == E || (g_fm_cols == 1 && fm_sum != nullptr), TRS_EINVAL,
-              "scatter_rows: g_fm_cols %d (E = %d full rows, or 1 = constant along E with fm_sum)", g_fm_cols, E);
-  const int64_t gbs = g_rows_batch_stride > 0 ? g_rows_batch_stride : N;
-  TRS_REQUIRE(gbs >= N, TRS_EINVAL, "scatter_rows: g_rows_batch_stride %lld < N", (long long)gbs);
-  TRS_REQUIRE(V > 0 && E > 0 && N > 0 && BN >= 0, TRS_EINVAL, "scatter_rows: bad size");
+// validates what the entry filled in, carves the workspace and derives the rest of the job
+static int scatter_rows_impl(WalkJob j, int64_t BN, int32_t dtype, void* workspace, size_t ws_bytes) {
+  TRS_REQUIRE(j.row_start && j.perm && j.out && workspace, TRS_EINVAL, "scatter_rows: NULL pointer");
+  TRS_REQUIRE(j.g_rows || j.g_fm, TRS_EINVAL, "scatter_rows: need g_rows and/or g_fm");
+  TRS_REQUIRE((j.fm_sum == nullptr) || (j.g_fm && j.table), TRS_EINVAL, "scatter_rows: fm_sum needs g_fm and table");
+  TRS_REQUIRE(j.g_fm == nullptr || j.g_fm_cols == j.E || (j.g_fm_cols == 1 && j.fm_sum != nullptr), TRS_EINVAL,
+              "scatter_rows: g_fm_cols %d (E = %d full rows, or 1 = constant along E with fm_sum)", j.g_fm_cols, j.E);
+  if (j.gbs <= 0) j.gbs = j.N;
+  TRS_REQUIRE(j.gbs >= j.N, TRS_EINVAL, "scatter_rows: g_rows_batch_stride %lld < N", (long long)j.gbs);
+  TRS_REQUIRE(j.V > 0 && j.E > 0 && j.N > 0 && BN >= 0, TRS_EINVAL, "scatter_rows: bad size");
   TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows: dtype %d", dtype);
-  TRS_REQUIRE(ws_bytes >= trs_scatter_workspace_bytes(BN, N, E, dtype), TRS_EWORKSPACE,
-              "scatter_rows: workspace %zu < %zu", ws_bytes, trs_scatter_workspace_bytes(BN, N, E, dtype));
-  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "scatter_rows: B*N=%lld not a multiple of N=%d", (long long)BN, N);
-  void* tg = (char*)workspace + long_row_queue_bytes(BN);
-  const int64_t B = BN / N;
-  float* scratch = (float*)((char*)tg + align_up((size_t)B * 2 * E * dtype_size(dtype), 256));
-  hipStream_t s = (hipStream_t)stream;
-  int32_t* long_rows = (int32_t*)workspace;
+  TRS_REQUIRE(ws_bytes >= trs_scatter_workspace_bytes(BN, j.N, j.E, dtype), TRS_EWORKSPACE,
+              "scatter_rows: workspace %zu < %zu", ws_bytes, trs_scatter_workspace_bytes(BN, j.N, j.E, dtype));
+  TRS_REQUIRE(BN % j.N == 0, TRS_EINVAL, "scatter_rows: B*N=%lld not a multiple of N=%d", (long long)BN, j.N);
+  j.B = BN / j.N;
+  j.long_rows = (int32_t*)workspace;
+  j.tg = (char*)workspace + long_row_queue_bytes(BN);
+  j.scratch = (float*)((char*)j.tg + align_up((size_t)j.B * 2 * j.E * dtype_size(dtype), 256));
   // the counters of the hot-row queue and (element path) of the split-row queue behind it
-  hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, s, long_rows, long_rows + 1 + (BN / LONG_ROW_ELEM + 2));
-  int rc;
-  if (dtype == TRS_F32)
-    rc = scatter_launch<float>(g_rows, g_fm, fm_sum, table, row_start, perm, V, E, N, gbs, padding_row, grad_table,
-                               long_rows, tg, scratch, B, sink, s, g_fm_cols, g_first, grad_first);
-  else
-    rc = scatter_launch<bf16_t>(g_rows, g_fm, fm_sum, table, row_start, perm, V, E, N, gbs, padding_row, grad_table,
-                                long_rows, tg, scratch, B, sink, s, g_fm_cols, g_first, grad_first);
-  if (rc == 1) return fail(TRS_ESHAPE, "scatter_rows_first: rows must be whole 16-byte vectors (E*sizeof %% 16 == 0)");
-  return rc;
+  hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, j.s, j.long_rows,
+                     j.long_rows + 1 + (BN / LONG_ROW_ELEM + 2));
+  return dtype == TRS_F32 ? scatter_launch<float>(j) : scatter_launch<bf16_t>(j);
 }
 
 /* see include/trs_abi.h: the dense gradients of an embedding table AND of its first-order (E = 1) companion in one walk */
@@ -1473,9 +1494,11 @@ extern "C" int trs_scatter_rows_first(const void* g_rows, int64_t g_rows_batch_s
                                       int64_t padding_row, void* grad_table, const void* g_first, void* grad_first,
                                       void* workspace, size_t ws_bytes, trs_stream_t stream) {
   TRS_REQUIRE(g_first && grad_first, TRS_EINVAL, "scatter_rows_first: NULL first-order pointer");
-  return scatter_rows_impl(RowSink{0, 0.f, 0.f, nullptr}, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start,
-                           perm, BN, V, E, N, dtype, padding_row, grad_table, workspace, ws_bytes, stream, g_first,
-                           grad_first);
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
+                                   .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
+                                   .N = N, .padding_row = padding_row, .out = grad_table, .g_first = g_first,
+                                   .grad_first = grad_first, .sink = GRAD_SINK, .s = (hipStream_t)stream},
+                           BN, dtype, workspace, ws_bytes);
 }
 
 extern "C" int trs_scatter_rows(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
@@ -1483,125 +1506,63 @@ extern "C" int trs_scatter_rows(const void* g_rows, int64_t g_rows_batch_stride,
                                 const void* table, const int32_t* row_start, const int32_t* perm, int64_t BN, int64_t V,
                                 int32_t E, int32_t N, int32_t dtype, int64_t padding_row, void* grad_table,
                                 void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  return scatter_rows_impl(RowSink{0, 0.f, 0.f, nullptr}, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start,
-                           perm, BN, V, E, N, dtype, padding_row, grad_table, workspace, ws_bytes, stream);
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
+                                   .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
+                                   .N = N, .padding_row = padding_row, .out = grad_table, .sink = GRAD_SINK,
+                                   .s = (hipStream_t)stream},
+                           BN, dtype, workspace, ws_bytes);
 }
 
-// the three fused-optimizer entries and their *_dev twins share these: ``lr_dev`` (device fp32, may be NULL) replaces ``lr``
-static int update_impl(const char* who, float lr, const float* lr_dev, const void* g_rows, int64_t g_rows_batch_stride,
-                       const void* g_fm, int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start,
-                       const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
-                       int64_t padding_row, int32_t optimizer, float eps, float* state, void* workspace, size_t ws_bytes,
-                       trs_stream_t stream) {
+// The row sink of a fused optimizer step: the optimizer tail of both update entries (include/trs_abi.h) is validated
+// here, before anything is launched.  ``row_map`` / ``map_rows``: the mapped entry's indirection (NULL / 0: none).
+static int make_sink(const char* who, const void* table, int32_t optimizer, float lr, const float* lr_dev, float eps,
+                     float beta1, float beta2, float* state, float* state2, const int32_t* row_map, int64_t map_rows,
+                     RowSink* sink) {
   TRS_REQUIRE(table, TRS_EINVAL, "%s: NULL table", who);
-  TRS_REQUIRE(optimizer == 1 || optimizer == 2, TRS_EINVAL, "%s: optimizer %d (1 = SGD, 2 = Adagrad)", who, optimizer);
-  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: Adagrad needs the state buffer", who);
-  RowSink sink{optimizer, lr, eps, state};
-  sink.lr_dev = lr_dev;
-  return scatter_rows_impl(sink, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN, V, E, N,
-                           dtype, padding_row, table, workspace, ws_bytes, stream);
-}
-
-static int update_adam_impl(const char* who, float step_size, const float* step_size_dev, const void* g_rows,
-                            int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols, const float* fm_sum,
-                            void* table, const int32_t* row_start, const int32_t* perm, int64_t BN, int64_t V, int32_t E,
-                            int32_t N, int32_t dtype, int64_t padding_row, float beta1, float beta2, float eps,
-                            float* exp_avg, float* exp_avg_sq, void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(table && exp_avg && exp_avg_sq, TRS_EINVAL, "%s: NULL table / moment buffer", who);
-  TRS_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, TRS_EINVAL, "%s: betas (%g, %g) must be in [0, 1)",
-              who, (double)beta1, (double)beta2);
-  RowSink sink{3, step_size, eps, exp_avg};
-  sink.beta1 = beta1;
-  sink.beta2 = beta2;
-  sink.state2 = exp_avg_sq;
-  sink.lr_dev = step_size_dev;
-  return scatter_rows_impl(sink, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN, V, E, N, dtype,
-                           padding_row, table, workspace, ws_bytes, stream);
-}
-
-static int update_mapped_impl(const char* who, float lr, const float* lr_dev, const void* g_rows, void* table,
-                              const int32_t* row_map, const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
-                              int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float eps, float beta1, float beta2,
-                              float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(g_rows && table && row_map, TRS_EINVAL, "%s: NULL pointer", who);
-  TRS_REQUIRE(optimizer >= 1 && optimizer <= 3, TRS_EINVAL, "%s: optimizer %d", who, optimizer);
-  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: missing optimizer state", who);
+  TRS_REQUIRE(optimizer >= 1 && optimizer <= 3, TRS_EINVAL, "%s: optimizer %d (1 = SGD, 2 = Adagrad, 3 = Adam)", who,
+              optimizer);
+  TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: optimizer %d needs the state buffer", who, optimizer);
   TRS_REQUIRE(optimizer != 3 || state2 != nullptr, TRS_EINVAL, "%s: Adam needs both moments", who);
-  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
-  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
-  RowSink sink{optimizer, lr, eps, state};
-  sink.map_rows = V;
-  sink.beta1 = beta1;
-  sink.beta2 = beta2;
-  sink.state2 = state2;
-  sink.row_map = row_map;
-  sink.lr_dev = lr_dev;
-  return scatter_rows_impl(sink, g_rows, 0, nullptr, 0, nullptr, table, row_start, perm, K, U, E, 1, dtype, -1, table,
-                           workspace, ws_bytes, stream);
+  TRS_REQUIRE(optimizer != 3 || (beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f), TRS_EINVAL,
+              "%s: betas (%g, %g) must be in [0, 1)", who, (double)beta1, (double)beta2);
+  *sink = RowSink{.mode = optimizer, .lr = lr, .eps = eps, .state = state, .beta1 = beta1, .beta2 = beta2,
+                  .state2 = state2, .row_map = row_map, .map_rows = map_rows, .lr_dev = lr_dev};
+  return TRS_OK;
 }
 
+/* see include/trs_abi.h: the walk with a fused sparse optimizer step as its sink */
 extern "C" int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
                                        const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
                                        int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                                       int32_t optimizer, float lr, float eps, float* state, void* workspace,
-                                       size_t ws_bytes, trs_stream_t stream) {
-  return update_impl("scatter_rows_update", lr, nullptr, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table,
-                     row_start, perm, BN, V, E, N, dtype, padding_row, optimizer, eps, state, workspace, ws_bytes, stream);
-}
-
-extern "C" int trs_scatter_rows_update_adam(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
-                                            const float* fm_sum, void* table, const int32_t* row_start,
-                                            const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N,
-                                            int32_t dtype, int64_t padding_row, float step_size, float beta1,
-                                            float beta2, float eps, float* exp_avg, float* exp_avg_sq, void* workspace,
-                                            size_t ws_bytes, trs_stream_t stream) {
-  return update_adam_impl("scatter_rows_update_adam", step_size, nullptr, g_rows, g_rows_batch_stride, g_fm, g_fm_cols,
-                          fm_sum, table, row_start, perm, BN, V, E, N, dtype, padding_row, beta1, beta2, eps, exp_avg,
-                          exp_avg_sq, workspace, ws_bytes, stream);
+                                       int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1,
+                                       float beta2, float* state, float* state2, void* workspace, size_t ws_bytes,
+                                       trs_stream_t stream) {
+  RowSink sink;
+  if (int rc = make_sink("scatter_rows_update", table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, nullptr, 0,
+                         &sink))
+    return rc;
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
+                                   .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
+                                   .N = N, .padding_row = padding_row, .out = table, .sink = sink,
+                                   .s = (hipStream_t)stream},
+                           BN, dtype, workspace, ws_bytes);
 }
 
 /* see include/trs_abi.h: the fused sparse optimizer step on a COMPACT list of distinct rows */
 extern "C" int trs_scatter_rows_update_mapped(const void* g_rows, void* table, const int32_t* row_map,
                                               const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
-                                              int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float lr, float eps,
-                                              float beta1, float beta2, float* state, float* state2, void* workspace,
-                                              size_t ws_bytes, trs_stream_t stream) {
-  return update_mapped_impl("scatter_rows_update_mapped", lr, nullptr, g_rows, table, row_map, row_start, perm, K, U, V, E,
-                            dtype, optimizer, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream);
-}
-
-/* ---- the same three entries with the step size read from DEVICE memory (see include/trs_abi.h) ---- */
-extern "C" int trs_scatter_rows_update_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
-                                           int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start,
-                                           const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
-                                           int64_t padding_row, int32_t optimizer, const float* lr_dev, float eps,
-                                           float* state, void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(lr_dev, TRS_EINVAL, "scatter_rows_update_dev: NULL lr_dev");
-  return update_impl("scatter_rows_update_dev", 0.f, lr_dev, g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table,
-                     row_start, perm, BN, V, E, N, dtype, padding_row, optimizer, eps, state, workspace, ws_bytes, stream);
-}
-
-extern "C" int trs_scatter_rows_update_adam_dev(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
-                                                int32_t g_fm_cols, const float* fm_sum, void* table,
-                                                const int32_t* row_start, const int32_t* perm, int64_t BN, int64_t V,
-                                                int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
-                                                const float* step_size_dev, float beta1, float beta2, float eps,
-                                                float* exp_avg, float* exp_avg_sq, void* workspace, size_t ws_bytes,
-                                                trs_stream_t stream) {
-  TRS_REQUIRE(step_size_dev, TRS_EINVAL, "scatter_rows_update_adam_dev: NULL step_size_dev");
-  return update_adam_impl("scatter_rows_update_adam_dev", 0.f, step_size_dev, g_rows, g_rows_batch_stride, g_fm, g_fm_cols,
-                          fm_sum, table, row_start, perm, BN, V, E, N, dtype, padding_row, beta1, beta2, eps, exp_avg,
-                          exp_avg_sq, workspace, ws_bytes, stream);
-}
-
-extern "C" int trs_scatter_rows_update_mapped_dev(const void* g_rows, void* table, const int32_t* row_map,
-                                                  const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
-                                                  int64_t V, int32_t E, int32_t dtype, int32_t optimizer,
-                                                  const float* lr_dev, float eps, float beta1, float beta2, float* state,
-                                                  float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  TRS_REQUIRE(lr_dev, TRS_EINVAL, "scatter_rows_update_mapped_dev: NULL lr_dev");
-  return update_mapped_impl("scatter_rows_update_mapped_dev", 0.f, lr_dev, g_rows, table, row_map, row_start, perm, K, U, V,
-                            E, dtype, optimizer, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream);
+                                              int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float lr,
+                                              const float* lr_dev, float eps, float beta1, float beta2, float* state,
+                                              float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  const char* who = "scatter_rows_update_mapped";
+  RowSink sink;
+  if (int rc = make_sink(who, table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, row_map, V, &sink)) return rc;
+  TRS_REQUIRE(g_rows && row_map, TRS_EINVAL, "%s: NULL pointer", who);
+  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
+  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .table = table, .row_start = row_start, .perm = perm, .V = U, .E = E,
+                                   .N = 1, .out = table, .sink = sink, .s = (hipStream_t)stream},
+                           K, dtype, workspace, ws_bytes);
 }
 
 namespace trs {

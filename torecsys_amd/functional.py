@@ -384,49 +384,46 @@ def _adam_step_dev(opt, table: torch.Tensor, key) -> torch.Tensor:
     return step_size
 
 
-def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
-                        g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
-                        padding_row: int = -1, key=None) -> None:
-    """Fused sparse optimizer step: the bucketed gradient of every looked-up row is applied to ``table`` in
-    place (see trs_scatter_rows_update); no gradient tensor is produced.  A ``capturable`` optimizer goes through the
-    ``_dev`` entries, which read the step size from device memory (eagerly and under capture alike)."""
-    V, E = table.shape
-    if not table.is_contiguous():
-        raise ValueError("fused optimizer needs a contiguous table")
+def _sink_args(opt, table: torch.Tensor, key):
+    """The optimizer tail of trs_scatter_rows_update[_mapped] up to ``state2``: (kind, lr, lr_dev, eps, beta1, beta2,
+    state, state2).  A ``capturable`` optimizer hands its step size over in device memory (lr_dev; eagerly and under
+    capture alike), any other by value.  For Adam this advances the table's step."""
     capturable = getattr(opt, "capturable", False)
-    ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, rb.N, E, value_dtype_code(table))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
+    lr, lr_dev = float(opt.lr), opt.lr_tensor(table.device) if capturable else None
+    beta1 = beta2 = 0.0
+    state = state2 = None
     if opt.kind == 3:
-        if capturable:
-            m1, m2 = opt.state_for(table, key)
-            step_size = _adam_step_dev(opt, table, key)
-            call("trs_scatter_rows_update_adam_dev", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum),
-                 ptr(table), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
-                 ptr(step_size), float(opt.beta1), float(opt.beta2), float(opt.eps), ptr(m1), ptr(m2), ptr(ws), ws_bytes,
-                 stream_ptr())
-            return
-        if torch.cuda.is_current_stream_capturing():
+        if not capturable and torch.cuda.is_current_stream_capturing():
             # the bias-corrected step size lr*sqrt(1-b2^t)/(1-b1^t) is computed on the host per step and passed by
             # value: a captured launch would replay the capture-time t for ever (~0.18*lr with default betas)
             raise RuntimeError("torecsys_amd: FusedSparseAdam cannot be captured into a hipGraph (its per-step bias "
                                "correction is a host-side scalar); use FusedSparseSGD / FusedSparseAdagrad under "
                                "GraphedStep, or run the Adam step eagerly")
-        m1, m2 = opt.state_for(table, key)
-        call("trs_scatter_rows_update_adam", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
-             ptr(rb.row_start),
-             ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row, float(opt.next_step_size(table, key)),
-             float(opt.beta1), float(opt.beta2), float(opt.eps), ptr(m1), ptr(m2), ptr(ws), ws_bytes, stream_ptr())
-        return
-    state = opt.state_for(table, key)
-    if capturable:
-        call("trs_scatter_rows_update_dev", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
-             ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row, opt.kind,
-             ptr(opt.lr_tensor(table.device)), float(opt.eps), ptr(state), ptr(ws), ws_bytes, stream_ptr())
-        return
+        state, state2 = opt.state_for(table, key)
+        beta1, beta2 = float(opt.beta1), float(opt.beta2)
+        if capturable:
+            lr_dev = _adam_step_dev(opt, table, key)
+        else:
+            lr = float(opt.next_step_size(table, key))
+    elif opt.kind == 2:
+        state = opt.state_for(table, key)
+    return opt.kind, lr, ptr(lr_dev), float(opt.eps), beta1, beta2, ptr(state), ptr(state2)
+
+
+def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
+                        g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
+                        padding_row: int = -1, key=None) -> None:
+    """Fused sparse optimizer step: the bucketed gradient of every looked-up row is applied to ``table`` in
+    place (see trs_scatter_rows_update); no gradient tensor is produced.  A ``capturable`` optimizer's step size is read
+    from device memory (eagerly and under capture alike)."""
+    V, E = table.shape
+    if not table.is_contiguous():
+        raise ValueError("fused optimizer needs a contiguous table")
+    ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, rb.N, E, value_dtype_code(table))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
     call("trs_scatter_rows_update", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
-         ptr(rb.row_start),
-         ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row, opt.kind, float(opt.lr), float(opt.eps),
-         ptr(state), ptr(ws), ws_bytes, stream_ptr())
+         ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
+         *_sink_args(opt, table, key), ptr(ws), ws_bytes, stream_ptr())
 
 
 def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows: torch.Tensor, row_map: torch.Tensor,
@@ -434,36 +431,17 @@ def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows:
     """Fused sparse optimizer step where the bucketed rows are a compact list of distinct table rows:
     ``rb`` buckets the K rows of ``g_rows`` by compact row u (rb.V = U), ``row_map[u]`` (int32, distinct) is the table
     row that u updates; entries outside [0, V) -- the empty slots of ``compact_rows`` -- update nothing.  See
-    trs_scatter_rows_update_mapped (``capturable`` optimizers: trs_scatter_rows_update_mapped_dev)."""
+    trs_scatter_rows_update_mapped."""
     V, E = table.shape
     if not table.is_contiguous():
         raise ValueError("fused optimizer needs a contiguous table")
     if row_map.dtype != torch.int32 or row_map.numel() != rb.V:
         raise ValueError("row_map must be int32 with one entry per bucketed row")
-    capturable = getattr(opt, "capturable", False)
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, 1, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
-    lr, st1, st2, b1, b2 = float(opt.lr), None, None, 0.0, 0.0
-    lr_dev = opt.lr_tensor(table.device) if capturable else None
-    if opt.kind == 3:
-        if not capturable and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("torecsys_amd: FusedSparseAdam cannot be captured into a hipGraph")
-        st1, st2 = opt.state_for(table, key)
-        b1, b2 = float(opt.beta1), float(opt.beta2)
-        if capturable:
-            lr_dev = _adam_step_dev(opt, table, key)
-        else:
-            lr = float(opt.next_step_size(table, key))
-    elif opt.kind == 2:
-        st1 = opt.state_for(table, key)
-    if capturable:
-        call("trs_scatter_rows_update_mapped_dev", ptr(g_rows.contiguous()), ptr(table), ptr(row_map), ptr(rb.row_start),
-             ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), opt.kind, ptr(lr_dev), float(opt.eps), b1, b2,
-             ptr(st1), ptr(st2), ptr(ws), ws_bytes, stream_ptr())
-        return
     call("trs_scatter_rows_update_mapped", ptr(g_rows.contiguous()), ptr(table), ptr(row_map), ptr(rb.row_start),
-         ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), opt.kind, lr, float(opt.eps), b1, b2, ptr(st1), ptr(st2),
-         ptr(ws), ws_bytes, stream_ptr())
+         ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), *_sink_args(opt, table, key), ptr(ws), ws_bytes,
+         stream_ptr())
 
 
 def compact_rows(ids: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
