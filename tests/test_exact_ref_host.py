@@ -1,0 +1,250 @@
+"""Host checks of tests/exact_ref.py: the float64 references against the oracle / dense autograd, the guard that makes
+``torch.equal`` a fair demand over EVERY case tests/test_gpu_exact_mfma.py runs, that the max-norm the existing tests use
+does not see the defect the exact tests are for, and the kernel-source thresholds the case lists were built around."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import exact_ref as X
+from conftest import rel_err
+from oracle import cpu_ref as O
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the references compute what the project's oracle computes
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("detach", [True, False])
+def test_cross_reference_is_the_oracle(detach):
+    c = X.cross_case(64, 6, 193)
+    r = c.ref[detach]
+    x = c.x.clone().requires_grad_()
+    W = [c.W[l].clone().requires_grad_() for l in range(6)]
+    b = [c.b[l].clone().requires_grad_() for l in range(6)]
+    out = O.cross_network(x, W, b, detach_first_input=detach)
+    out.backward(c.gout)
+    assert torch.equal(out.detach(), r.out) and torch.equal(x.grad, r.dx)
+    assert torch.equal(torch.stack([w.grad for w in W]), r.dW) and torch.equal(torch.stack([v.grad for v in b]), r.db)
+    assert not torch.equal(r.dx, c.ref[not detach].dx)            # the two forms are different gradients
+
+
+def test_mlp_reference_is_the_oracle_and_its_structured_layer_is_linear():
+    c = X.mlp_case((32, 104, 200, 40), 4, 257)
+    x = c.x.clone().requires_grad_()
+    W = [w.clone().requires_grad_() for w in c.Ws]
+    b = [v.clone().requires_grad_() for v in c.bs]
+    y = O.mlp(x, W, b)
+    y.backward(c.gout)
+    assert torch.equal(y.detach(), c.ref.y) and torch.equal(x.grad, c.ref.gx)
+    for l in range(3):
+        assert torch.equal(W[l].grad, c.ref.dW[l]) and torch.equal(b[l].grad, c.ref.db[l])
+    m = X.mlp_mask_in_case((16, 72, 8), 4, 257)
+    z = torch.where(m.x > 0, m.x, -torch.ones_like(m.x)).requires_grad_()      # any z with relu(z) = x
+    O.mlp(torch.relu(z), m.Ws, m.bs).backward(m.gout)
+    assert torch.equal(z.grad, m.ref.gx) and torch.equal(z.grad.sum(0), m.ref.gb_in)
+    assert float((m.ref.gx[m.x == 0]).abs().max()) == 0.0 and float(m.ref.gx.abs().max()) > 0
+
+
+@pytest.mark.parametrize("mode,has_bias", X.PAIR_FORMS)
+def test_pair_reference_written_out_pair_by_pair(mode, has_bias):
+    c = X.pair_case(5, 32, 17)
+    r = c.ref[(mode, has_bias)]
+    I, J = X.pair_index(5)
+    assert list(zip(I.tolist(), J.tolist())) == list(zip(*[t.tolist() for t in O.pair_indices(5)]))
+    for p in (0, 4, 9):
+        T = c.x[:, I[p]] @ c.W[p]
+        want = (T * c.x[:, J[p]]).sum(-1) if mode == 0 else T * c.x[:, J[p]] + (c.bias[p] if has_bias else 0)
+        assert torch.equal(r.out[:, p], want)
+    if mode == 0:       # 'mat' outer product of the oracle: kernel (E_h, P, E_e) = W[p][e][h] transposed
+        assert torch.equal(r.out, O.outer_product_layer(c.x, c.W.permute(2, 0, 1).contiguous(), "mat"))
+    ti, tj = X.pair_tasks(5)
+    assert ti == [(0, 1, 3), (0, 4, 1), (1, 2, 3), (2, 3, 2), (3, 4, 1)] and len(tj) == 5
+    assert [t for t in X.pair_tasks(39)[0] if t[0] == 0][-1] == (0, 37, 2)      # N = 39: the last task of a field short
+    assert X.pair_tasks(4)[0][0] == (0, 1, 3) and X.pair_tasks(2)[0] == [(0, 1, 1)]
+
+
+def test_cin_reference_is_the_oracle_in_both_forms():
+    for form, N, H, C, E, B in (("plain", 10, 10, 64, 32, 9), ("fold", 33, 33, 128, 64, 9)):
+        c = X.cin_case(form, N, H, C, E, B, 2)
+        a = c.x0.permute(0, 2, 1).contiguous().requires_grad_()
+        k = a if c.same else c.xk.permute(0, 2, 1).contiguous().requires_grad_()
+        Wo = c.W.reshape(C, N * H, 1).clone().requires_grad_()
+        bo = c.bias.clone().requires_grad_()
+        y = O.cin_contraction(a, k, Wo, bo)
+        y.backward(c.gy)
+        assert torch.equal(y.detach(), c.ref.y) and torch.equal(a.grad.permute(0, 2, 1), c.ref.dx0)
+        assert torch.equal(Wo.grad.reshape(C, N * H), c.ref.dW) and torch.equal(bo.grad, c.ref.db)
+        if not c.same:
+            assert torch.equal(k.grad.permute(0, 2, 1), c.ref.dxk)
+
+
+def test_generators():
+    g = X.gen(9)
+    v = X.ints((1000, 7), g)
+    assert set(v.unique().tolist()) == {-1.0, 0.0, 1.0}
+    P = X.signed_rows(64, 64, 1, g)
+    assert torch.equal(P.abs().sum(0), torch.ones(64, dtype=X.F64)) and torch.equal(P.abs().sum(1), torch.ones(64, dtype=X.F64))
+    W = X.signed_rows(72, 16, 4, g)
+    assert torch.equal(W.abs().sum(1), torch.full((72,), 4.0, dtype=X.F64)) and set(W.unique().tolist()) == {-1.0, 0.0, 1.0}
+    S = X.pair_stack(3, 32, g)
+    assert S.shape == (3, 32, 32) and torch.equal(S.abs().sum(1), torch.ones(3, 32, dtype=X.F64))
+    assert not torch.equal(S[0], S[1])
+    assert torch.equal(X.ints(5, X.gen(1, 2)), X.ints(5, X.gen(1, 2))) and not torch.equal(X.ints(50, X.gen(1, 2)), X.ints(50, X.gen(2, 1)))
+    big = torch.tensor([257.0])
+    with pytest.raises(AssertionError):
+        X.assert_exact_domain({"v": big}, {})
+    with pytest.raises(AssertionError):
+        X.assert_exact_domain({}, {"v": torch.tensor([2.0 ** 24])})
+    with pytest.raises(AssertionError):
+        X.assert_exact_domain({}, {"v": torch.tensor([0.5])})
+    X.assert_exact_domain({"v": torch.tensor([256.0, -3.0])}, {"w": torch.tensor([2.0 ** 24 - 1])})
+    assert torch.equal(X.expect(torch.tensor([257.0, 258.0, 259.0]), torch.bfloat16).double(), torch.tensor([256.0, 258.0, 260.0]).double())
+    assert X.mismatch("t", torch.zeros(2, 3), torch.zeros(2, 3)) is None
+    msg = X.mismatch("t", torch.tensor([[0.0, 1.0], [2.0, 3.0]]), torch.tensor([[0.0, 1.0], [2.0, 4.0]]))
+    assert "1 of 4" in msg and "(1, 1)" in msg
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the guard over every case the GPU file runs
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("E,L", sorted({(E, L) for E, L, _ in X.CROSS_CASES}))
+def test_cross_cases_are_in_the_exact_domain(E, L):
+    for rows in [r for (e, l, r) in X.CROSS_CASES if (e, l) == (E, L)]:
+        c = X.cross_case(E, L, rows)
+        for d in (True, False):
+            r = c.ref[d]
+            X.assert_exact_domain({**r.inter, "out": r.out, "dx": r.dx}, {"dW": r.dW, "db": r.db})
+
+
+def test_pair_cases_are_in_the_exact_domain():
+    for case in X.PAIR_CASES:
+        c = X.pair_case(*case)
+        for form in X.PAIR_FORMS:
+            r = c.ref[form]
+            sums = {"gW": r.gW} if r.gbias is None else {"gW": r.gW, "gbias": r.gbias}
+            X.assert_exact_domain(r.inter, sums, r.term_sums)
+
+
+def test_cin_cases_are_in_the_exact_domain():
+    for case in X.CIN_CASES:
+        c = X.cin_case(*case)
+        X.assert_exact_domain(c.ref.inter, {"dW": c.ref.dW, "db": c.ref.db})
+        if c.live:
+            assert float(c.ref.dW[c.live:].abs().max()) == 0.0 and float(c.ref.dW[:c.live].abs().max()) > 0
+    # every plain shape sits in the matrix-core sets of _CINContractCL.backward but the one listed as generic
+    for (N, H, C, E) in X.CIN_SHAPES:
+        assert (C in (64, 128, 256) and E in (32, 64, 128)) == ((N, H, C, E) not in X.CIN_GENERIC_DW)
+    assert all(N > 32 for N, _, _ in X.CIN_FOLD_SHAPES)
+
+
+@pytest.mark.parametrize("widths,k", [(tuple(w), k) for w, k in X.MLP_STACKS], ids=str)
+def test_mlp_cases_are_in_the_exact_domain(widths, k):
+    cases = [X.mlp_case(*c) for c in X.MLP_CASES if c[:2] == (widths, k)]
+    cases += [X.mlp_mask_in_case(*c) for c in X.MLP_MASK_IN_CASES if c[:2] == (widths, k)]
+    assert len(cases) >= len(X.MLP_ROWS)
+    for c in cases:
+        r = c.ref
+        X.assert_exact_domain({**r.inter, "gx": r.gx, **{f"h{l}": h for l, h in enumerate(r.hidden)}},
+                              {**{f"dW{l}": w for l, w in enumerate(r.dW)}, **{f"db{l}": v for l, v in enumerate(r.db)},
+                               "gb_in": r.gb_in})
+        if c.x.shape[0] >= 127:
+            # the ReLU masks are not degenerate: a fifth to two thirds of every hidden layer alive
+            assert all(0.2 <= a <= 0.67 for a in r.alive), r.alive
+
+
+def test_wgrad_and_rows_gemm_cases_are_in_the_exact_domain():
+    for case in X.WGRAD_CASES:
+        c = X.wgrad_case(*case)
+        X.assert_exact_domain({"g": c.g, "inp": c.inp}, {"dW": c.dW, "db": c.db})
+        assert float(c.g[:, case[0]:].abs().max() if c.g.shape[1] > case[0] else 1.0) == 1.0      # other values in the padding
+    for case in X.ROWS_GEMM_CASES:
+        c = X.rows_gemm_case(*case)
+        X.assert_exact_domain({"x": c.x, "W": c.W, "y": c.y}, {})
+    c = X.rows_gemm_case(64, 1024, 4097, 4)
+    assert torch.equal(c.y, X.rows_gemm_ref(c.x, c.W, 64)) and c.W.shape == (64, 1024)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what the exact comparison sees and the max-norm of the existing tests does not
+# ---------------------------------------------------------------------------------------------------------------------
+def test_one_dropped_tile_of_sixteen_rows_is_invisible_to_the_max_norm():
+    """The defect the exact tests are for: the contribution of the last 16 samples missing from a batch reduction.
+    ``torch.equal`` sees it at any row count; conftest.rel_err, the norm every existing bf16 test asserts at 1e-2, sees a
+    change of about sqrt(16 / rows) of the largest value: 5e-2 at the 6 240 rows of a mid-sized GPU case (asserted below:
+    there the norm still notices), under 1e-2 from a few hundred thousand rows on -- the batch x fields row counts of the
+    models.  Hence the row count here, on narrow shapes that keep the float64 references cheap."""
+    TOL, R = 1e-2, 600_000
+    g = X.gen(8)
+    seen = {}
+
+    def cross(rows):
+        x, go, b = X.ints((rows, 32), g), X.ints((rows, 32), g), X.ints((1, 32), g)
+        W = X.signed_rows(32, 32, 1, g).unsqueeze(0)
+        return X.cross_ref(x[:-16], W, b, go[:-16], True).dW, X.cross_ref(x, W, b, go, True).dW
+    seen["cross dW"] = cross(R)
+    mid = cross(6240)
+    assert not torch.equal(*mid) and rel_err(*mid) > TOL
+
+    _, Ws, bs = X._mlp_operands((16, 72, 8), 4, R, 8)
+    x, go = X.ints((R, 16), g), X.ints((R, 8), g)
+    seen["mlp dW"] = (X.mlp_ref(x[:-16], Ws, bs, go[:-16]).dW[1], X.mlp_ref(x, Ws, bs, go).dW[1])
+
+    x, W, go = X.ints((R, 2, 32), g), X.pair_stack(1, 32, g), X.ints((R, 1), g)
+    seen["pair gW"] = (X.pair_ref(x[:-16], W, None, go[:-16], 0).gW, X.pair_ref(x, W, None, go, 0).gW)
+
+    x0, xk, W, b, gy = X.ints((R, 2, 16), g), X.ints((R, 2, 16), g), X.signed_rows(8, 4, 1, g), X.ints(8, g), X.ints((R, 8, 16), g)
+    seen["cin dW"] = (X.cin_ref(x0[:-16], xk[:-16], W, b, gy[:-16], chunk=1 << 16).dW, X.cin_ref(x0, xk, W, b, gy, chunk=1 << 16).dW)
+
+    for name, (cut_, full) in seen.items():
+        assert not torch.equal(cut_, full), name
+        assert float(full.abs().max()) < 2 ** 24
+        assert rel_err(cut_, full) < TOL, (name, rel_err(cut_, full))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the thresholds in the sources
+# ---------------------------------------------------------------------------------------------------------------------
+def test_case_lists_sit_on_the_thresholds_in_the_source():
+    """Whoever retunes one of these constants must move the case lists of tests/exact_ref.py with it."""
+    c = X.source_constants()
+    assert c["B3_ROWS"] == X.B3_ROWS == 96 and c["BW_MAX_BLOCKS"] == X.BW_MAX_BLOCKS == 256
+    assert c["MF_ROWS"] == X.MF_ROWS == 128 and c["MF_GRID"] == X.MF_GRID == 256 and c["RO_ROWS"] == X.RO_ROWS == 256
+    assert c["WG_KS"] == X.WG_KS == 32 and c["WG_KR"] == X.WG_KR == 64 and c["WG_TC"] == X.WG_TC == 7
+    assert c["PB_PPT"] == X.PB_PPT == 3 and c["DW_NG"] == 8 and X.TILE == 16
+    with open(X.os.path.join(X.CSRC, "cross_mfma.hip")) as f:
+        src = f.read()
+    # the formulas restated in exact_ref: the forward's grid and residency, the unrolling of the partial reduction
+    assert "std::min<int64_t>((ntiles + 7) / 8, resident ? 256 * 3 : 256 * 8)" in src
+    assert "const bool resident = lds <= 64 * 1024;" in src and "for (; p + 48 < nparts; p += 64)" in src
+    assert "E % 32 == 0 && E >= 32 && E <= 128 && L >= 1" in src and "!(E == 32 || E == 64) || L < 1 || L > 6" in src
+
+    rows = {(E, L): {r for (e, l, r) in X.CROSS_CASES if (e, l) == (E, L)} for E, L, _ in X.CROSS_CASES}
+    for E in (32, 64):
+        for L in (1, 2, 6):
+            have = rows[(E, L)]
+            for edge in (X.TILE, X.CROSS_FWD_UNIT, X.B3_ROWS):
+                assert {edge - 1, edge, edge + 1} <= have
+            assert {2 * X.B3_ROWS - 1, 2 * X.B3_ROWS + 1} <= have and 1 in have
+    for EL in ((64, 6), (32, 2)):
+        assert {X.cross_nparts(r) for r in rows[EL]} >= {1, 16, 17, 49, 64, 65, 256}
+        assert {X.BW_MAX_BLOCKS * X.B3_ROWS - 1, X.BW_MAX_BLOCKS * X.B3_ROWS + 1} <= rows[EL]
+    assert X.cross_fwd_resident(128, 1) and not X.cross_fwd_resident(128, 2) and X.cross_fwd_resident(64, 6)
+    assert {(E, L) for E, L, _ in X.CROSS_CASES} >= {(E, L) for E in (96, 128) for L in (1, 2, 4)}
+    top = max(r for (e, l, r) in X.CROSS_CASES if (e, l) == (64, 2))
+    assert X.cross_fwd_resident(64, 2) and (top + X.TILE - 1) // X.TILE > 8 * X.CROSS_FWD_GRID_RESIDENT
+
+    assert X.MF_GRID * X.MF_ROWS + 1 in X.MLP_ROWS and X.MF_GRID * X.RO_ROWS + 1 in X.MLP_ROWS
+    assert {X.MF_ROWS - 1, X.MF_ROWS, X.MF_ROWS + 1, X.RO_ROWS - 1, X.RO_ROWS, X.RO_ROWS + 1} <= set(X.MLP_ROWS)
+
+    # wgrad_rows: not taken below four 64-row stages; the row counts one either side of 4 * WG_KR * S keep S, and one
+    # count gives more than 8 ranges
+    for (M, N) in X.WGRAD_SHAPES:
+        assert X.wgrad_splits(M, N, 4 * X.WG_KR - 1) == 0 and X.wgrad_splits(M, N, 4 * X.WG_KR) == 8
+        for S in (8, 16):
+            assert X.wgrad_splits(M, N, 4 * X.WG_KR * S - 1) == S and X.wgrad_splits(M, N, 4 * X.WG_KR * S + 1) == S
+        assert {4 * X.WG_KR * S + d for S in (8, 16) for d in (-1, 1)} <= set(X.WGRAD_ROWS)
+    assert {X.WG_KS - 1, X.WG_KS, X.WG_KS + 1, 4 * X.WG_KS - 1, 4 * X.WG_KS, 4 * X.WG_KS + 1} <= set(X.WGRAD_ROWS)
+
+    # pair kernels: a task of exactly PB_PPT pairs, PB_PPT + 1, a short last task; 2049 samples = 65 steps of 32: with
+    # at least 8 steps per split, 8 splits
+    assert {N for N, _, _ in X.PAIR_CASES} == {2, X.PB_PPT + 1, X.PB_PPT + 2, 39}
+    assert ((2049 + 31) // 32) // 8 == 8
