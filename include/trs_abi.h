@@ -548,6 +548,16 @@ int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int3
 int32_t trs_wgrad_rows_splits(int32_t M, int32_t N, int64_t rows);
 int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t ldx, int64_t rows, int32_t M, int32_t N,
                    int32_t dtype, int32_t S, float* part, trs_stream_t stream);
+/* the same product for a WIDE input, transposed: part (S, M_x, N_g) fp32, slice s = x[rows_s, :M_x]^T g[rows_s, :N_g] -- what
+ * trs_wgrad_finish_t folds -- with no work spent on the padding columns of g.  Taken (trs_wgrad_wide_splits > 0) when M_x
+ * is a multiple of 208 (at least two blocks of 13 tiles of 16), N_g a multiple of 16 that cuts into two blocks of 12 | 13
+ * tiles whose 208-column images lie inside ld_g (384, 400 or 416 columns; ld_g >= 16 * (N_g / 32) + 208), ld_g a
+ * multiple of 8, rows a multiple of 128 and at least 128 * S, and 32 rows of either operand span less than 2^31 bytes.
+ * trs_wgrad_wide takes exactly that S, bf16 operands that are 16-byte aligned, ldx >= M_x a multiple of 8; it
+ * allocates nothing and does not synchronise.                                                                         */
+int32_t trs_wgrad_wide_splits(int32_t M_x, int32_t N_g, int32_t ld_g, int64_t rows);
+int trs_wgrad_wide(const void* x, int32_t ldx, const void* g, int32_t ldg, int64_t rows, int32_t M_x, int32_t N_g,
+                   int32_t S, float* part, trs_stream_t stream);
 /* n strided 2-D copies in one launch: desc (device, n x 6 int64) = {src address, dst address, rows, cols, src_ld,
  * dst_ld} (sizes in elements of elem_size bytes); max_elems = the largest rows*cols (sizes the grid).  Refreshes the
  * zero-padded copies of an MLP stack's nn.Linear parameters (multilayer_perceptron.py:55-61) before a forward.     */

@@ -50,6 +50,7 @@ struct WgradArgs {
   int M, N;                  // columns of g / x that count (multiples of 8)
   int MB, NB;                // output blocks along M / N
   int slots_per_xcd;         // row ranges per XCD (S = 8 * slots_per_xcd)
+  int S;                     // wgrad_dma2_kernel only: row ranges, >= 8 * slots_per_xcd (see wd2_place)
 };
 
 __host__ __device__ __forceinline__ int split_start(int total, int parts, int k) { return (int)(((int64_t)total * k) / parts); }
@@ -426,6 +427,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradArgs a) {
 // perfectly; here it is 80 KB per 338-tile step.  The g block is also fetched once instead of twice.  Three images per
 // step (g, x block 0, x block 1: 39 pieces), ring of four slots, copies three steps ahead.  For long row ranges
 // (rows >= WD2_MIN_ROWS: twice as many fp32 partials as the eight-wave form for the same number of workgroups).
+// trs_wgrad_wide (end of file) runs the same kernel on a wide input with the operands' roles swapped.
 constexpr int WD2_SLOT = 3 * WD_IMG;
 constexpr int WD2_NSLOT = 4;
 constexpr int WD2_AHEAD = 3;
@@ -437,16 +439,34 @@ __device__ __forceinline__ void wd_mfma(wg_f32x4& acc, const wg_bf16x8& A, const
   else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(A), "v"(B));
 }
 
+// workgroup b -> (row range ``slot`` of a.S, g block ``mb`` of a.MB), for any a.MB and a.S.  Blocks b and b + 8 share an
+// XCD (dealt round-robin), one workgroup fills a CU.  The first 8 * slots_per_xcd ranges are XCD-local: the MB workgroups
+// of a range sit on one XCD, so the x rows all of them read come out of that XCD's L2.  Where MB does not divide the 32
+// CUs of an XCD (12 blocks: 2 ranges on 24 CUs), the ranges behind those are dealt over the CUs left over, MB
+// consecutive ones of them to a range (2496 columns: 5 more ranges, 252 of 256 CUs at work).  Measured at 65 536 rows of
+// 2496 x 400 (profiles/wgrad_wide.md): 16 local ranges on 192 CUs 177-188 us; 21 ranges, all dealt in dispatch order
+// (range-major or block-major) 149-154 us; this map 143-146 us.
+__device__ __forceinline__ void wd2_place(const WgradArgs& a, int b, int& slot, int& mb) {
+  const int xcd = b & 7, j = b >> 3, local = a.slots_per_xcd * a.MB;
+  if (j < local) {
+    slot = xcd * a.slots_per_xcd + j / a.MB;
+    mb = j % a.MB;
+  } else {
+    const int r = (j - local) * 8 + xcd;
+    slot = 8 * a.slots_per_xcd + r / a.MB;      // (>= a.S: the grid is rounded up to whole rounds of 8)
+    mb = r % a.MB;
+  }
+}
+
 __global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char wg_lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane >> 4, i = lane & 15;
   const bool odd = q & 1;
-  const int TB = a.MB;                                   // (a.NB == 2: both x blocks belong to the workgroup)
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int slot = xcd * a.slots_per_xcd + j / TB;
-  const int S = 8 * a.slots_per_xcd;
-  const int mb = j % TB;
+  const int S = a.S;
+  int slot, mb;
+  wd2_place(a, blockIdx.x, slot, mb);
+  if (slot >= S) return;
   const int Mt = (a.M + 15) >> 4, Nt = (a.N + 15) >> 4;
   const int bm0 = split_start(Mt, a.MB, mb), PM = split_start(Mt, a.MB, mb + 1) - bm0;
   const int xb = wave >> 1;                              // this wave's x block
@@ -631,6 +651,17 @@ static int wgrad_launch(const WgradArgs& a, int grid, size_t lds, hipStream_t s)
                           : wgrad_launch_c<WM, WN, MC, NC, false>(a, grid, lds, s);
 }
 
+static int wgrad_dma2_launch(const WgradArgs& a, int grid, hipStream_t s, const char* what) {
+  static bool attr2 = false;
+  if (!attr2) {
+    if (hipFuncSetAttribute((const void*)wgrad_dma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      return check_launch("wgrad_dma2: LDS attribute");
+    attr2 = true;
+  }
+  hipLaunchKernelGGL(wgrad_dma2_kernel, dim3(grid), dim3(256), (size_t)WD2_NSLOT * WD2_SLOT, s, a);
+  return check_launch(what);
+}
+
 extern "C" int32_t trs_wgrad_rows_splits(int32_t M, int32_t N, int64_t rows) {
   const WgradPlan p = wgrad_plan(M, N, rows);
   return 8 * p.slots_per_xcd;
@@ -648,21 +679,15 @@ extern "C" int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t
               "wgrad_rows: row strides must be multiples of 8 elements and cover M / N, operands 16-byte aligned");
   if (!g || !x || !part) return fail(TRS_EINVAL, "wgrad_rows: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  WgradArgs a{(const uint16_t*)g, (const uint16_t*)x, part, rows, ldg, ldx, M, N, p.MB, p.NB, p.slots_per_xcd};
+  WgradArgs a{(const uint16_t*)g, (const uint16_t*)x, part, rows, ldg, ldx, M, N, p.MB, p.NB, p.slots_per_xcd, 0};
   const int Mt = (M + 15) / 16, Nt = (N + 15) / 16;
   const int PM = (Mt + p.MB - 1) / p.MB, PN = (Nt + p.NB - 1) / p.NB;
   const size_t lds = (size_t)(4 * (PM + PN) + WG_TC) * WG_PANEL;      // + the panels a short wave runs on into
   const int grid = 8 * p.slots_per_xcd * p.MB * p.NB;
   TRS_REQUIRE(p.dma == 0 || (int64_t)WG_KS * std::max(ldg, ldx) * 2 < ((int64_t)1 << 31), TRS_ESHAPE, "wgrad_rows: row stride too large");
   if (p.dma == 2) {
-    static bool attr2 = false;
-    if (!attr2) {
-      if (hipFuncSetAttribute((const void*)wgrad_dma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return check_launch("wgrad_rows(dma2): LDS attribute");
-      attr2 = true;
-    }
-    hipLaunchKernelGGL(wgrad_dma2_kernel, dim3(8 * p.slots_per_xcd * p.MB), dim3(256), (size_t)WD2_NSLOT * WD2_SLOT, s, a);
-    return check_launch("wgrad_rows(dma2)");
+    a.S = 8 * p.slots_per_xcd;
+    return wgrad_dma2_launch(a, a.S * p.MB, s, "wgrad_rows(dma2)");
   }
   if (p.dma == 1) {
     static bool attr = false;
@@ -682,4 +707,45 @@ extern "C" int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t
   if (p.mc == 1) return wgrad_launch<1, 4, 1, WG_TC>(a, grid, lds, s);
   if (p.mc == 4) return wgrad_launch<1, 4, 4, WG_TC>(a, grid, lds, s);
   return wgrad_launch<1, 4, WG_TC, WG_TC>(a, grid, lds, s);
+}
+
+// ---- a wide input against a two-block g (the 2496-wide first layer of the deep branch: dW^T = x^T g1, x (rows, 12 x 208)
+// and g1 (rows, 400 live columns in 512-wide rows)) on wgrad_dma2_kernel, x in the role the kernel calls g: a workgroup owns
+// one 13-tile block of x against both blocks of g1, so neither the padding columns of g1 nor a macro tile's round-up are
+// multiplied.  part (S, M_x, N_g) fp32 is what trs_wgrad_finish_t folds.
+struct WidePlan {
+  int spx, S, grid;      // XCD-local row ranges per XCD, row ranges in all, workgroups
+};
+
+// at most 4 local ranges per XCD (32 in all: every range costs M_x * N_g fp32 partials); an XCD that its local ranges
+// leave CUs on (32 % MB) gives those to further ranges
+static WidePlan wide_plan(int MB) {
+  WidePlan w{std::min(32 / MB, 4), 0, 0};
+  const int extra = w.spx == 32 / MB ? 8 * (32 - w.spx * MB) / MB : 0;
+  w.S = 8 * w.spx + extra;
+  w.grid = 8 * (w.spx * MB + (extra * MB + 7) / 8);
+  return w;
+}
+
+extern "C" int32_t trs_wgrad_wide_splits(int32_t M_x, int32_t N_g, int32_t ld_g, int64_t rows) {
+  if (M_x < 2 * 208 || M_x % 208 || N_g < 8 || (N_g & 15) || (ld_g & 7) || rows <= 0 || rows % (4 * WG_KS)) return 0;
+  const int Nt = N_g / 16, MB = M_x / 208;
+  if (Nt < 24 || Nt > 26 || 16 * split_start(Nt, 2, 1) + 208 > ld_g || MB > 32) return 0;      // blocks of 12 | 13 tiles, images inside the rows
+  if ((int64_t)WG_KS * std::max(M_x, ld_g) * 2 >= ((int64_t)1 << 31)) return 0;
+  const int S = wide_plan(MB).S;
+  return rows >= (int64_t)4 * WG_KS * S ? S : 0;
+}
+
+extern "C" int trs_wgrad_wide(const void* x, int32_t ldx, const void* g, int32_t ldg, int64_t rows, int32_t M_x, int32_t N_g,
+                              int32_t S, float* part, trs_stream_t stream) {
+  if (!g || !x || !part) return fail(TRS_EINVAL, "wgrad_wide: null pointer");
+  TRS_REQUIRE(ldx >= M_x && (ldx & 7) == 0 && aligned16(g) && aligned16(x) && (int64_t)WG_KS * ldx * 2 < ((int64_t)1 << 31),
+              TRS_ESHAPE, "wgrad_wide: operands 16-byte aligned, ldx a multiple of 8 elements that covers M_x, under 2^31 bytes per 32 rows");
+  const int S0 = trs_wgrad_wide_splits(M_x, N_g, ldg, rows);
+  TRS_REQUIRE(S0 > 0 && S == S0, TRS_ESHAPE, "wgrad_wide: (M_x=%d, N_g=%d, ldg=%d, rows=%lld) takes %d row ranges, caller passed %d",
+              M_x, N_g, ldg, (long long)rows, S0, S);
+  const int MB = M_x / 208;
+  const WidePlan w = wide_plan(MB);
+  WgradArgs a{(const uint16_t*)x, (const uint16_t*)g, part, rows, ldx, ldg, M_x, N_g, MB, 2, w.spx, S};
+  return wgrad_dma2_launch(a, w.grid, (hipStream_t)stream, "wgrad_wide");
 }

@@ -775,6 +775,24 @@ class _LinearSplitK(torch.autograd.Function):
         return gx, gw, gb, None, None, None
 
 
+# trs_wgrad_wide writes (and its finish reads back) one fp32 partial of the whole gradient per row slice, 84 MB at
+# 2496 x 400, whatever the row count.  Measured against the library GEMM (profiles/wgrad_wide.md, weight gradient +
+# finish), in us:
+# 2688 rows 56 against 47, 4096 rows 59 against 55, 6144 rows 62 against 68, 8192 rows 66 against 79, 16 384 rows
+# 78 against 108, 65 536 rows 171 against 220 -- so the layer takes the kernel from 6144 rows on.
+WIDE_WGRAD_MIN_ROWS = 6144
+
+
+def _wide_wgrad_splits(g2, xin, out_f, in_f) -> int:
+    """Row slices trs_wgrad_wide takes for dW^T = xin^T g2 (0: not its shape -- the caller keeps the library GEMM)."""
+    if not (xin.shape[0] >= WIDE_WGRAD_MIN_ROWS and g2.dtype == xin.dtype == torch.bfloat16
+            and xin.shape[1] == in_f and g2.shape[1] >= out_f
+            and g2.stride(1) == 1 and xin.stride(1) == 1 and xin.stride(0) % 8 == 0
+            and g2.data_ptr() % 16 == 0 and xin.data_ptr() % 16 == 0):
+        return 0
+    return F_.size_query("trs_wgrad_wide_splits", in_f, out_f, g2.stride(0), xin.shape[0])
+
+
 def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b):
     """Gradients of y = xin @ W^T + b from g2 = dL/dy (rows, padded width; ``gbf``: its fp32 column sums when a fused
     ReLU-backward already produced them): (dL/dxin, dL/dW, dL/db), None where not needed."""
@@ -782,7 +800,21 @@ def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b
     gw_out = gb_out = None
     S = _split_count(rows, _LinearSplitK.SPLIT_ROWS)
     if need_w or (need_b and gbf is not None):
-        if need_w and S >= 4 and rows % S == 0 and 32 <= g2.shape[1] <= 1024 and 32 <= xin.shape[1] <= 4096 \
+        Sw = _wide_wgrad_splits(g2, xin, out_f, in_f) if need_w else 0
+        if Sw:
+            # wide input on the project's own kernel: x^T g over Sw row slices, the live columns of g only
+            gw = torch.empty(out_f, in_f, dtype=wdt, device=xin.device)
+            part = torch.empty(Sw, in_f, out_f, dtype=torch.float32, device=xin.device)
+            F_.call("trs_wgrad_wide", F_.ptr(xin), xin.stride(0), F_.ptr(g2), g2.stride(0), rows, in_f, out_f, Sw,
+                    F_.ptr(part), F_.stream_ptr())
+            with_b = need_b and gbf is not None
+            gb = torch.empty(out_f, dtype=wdt, device=xin.device) if with_b else None
+            F_.call("trs_wgrad_finish_t", F_.ptr(part), Sw, in_f, out_f, out_f, in_f, F_.value_dtype_code(gw),
+                    F_.ptr(gw), F_.ptr(gbf) if with_b else F_.ptr(None), F_.ptr(gb), F_.stream_ptr())
+            gw_out = gw
+            if with_b:
+                gb_out = gb
+        elif need_w and S >= 4 and rows % S == 0 and 32 <= g2.shape[1] <= 1024 and 32 <= xin.shape[1] <= 4096 \
                 and xin.is_contiguous():
             gw = torch.empty(out_f, in_f, dtype=wdt, device=xin.device)
             St = _split_count(rows, _MLPStack.SPLIT_ROWS_WIDE)
