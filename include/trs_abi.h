@@ -823,6 +823,64 @@ int trs_dynamic_routing_fwd(const float* priors, const void* noise, int64_t B, i
 int trs_dynamic_routing_bwd(const void* noise, const float* c, const float* z, const void* gout, int64_t B, int32_t N,
                             int32_t R, int32_t K, int32_t dtype, void* dpri, trs_stream_t stream);
 
+/* ---- an ordered list of ids through a one-layer RNN, then pooled (csrc/seq_rnn.hip) --------------------------------
+ * table (V, E), idx (B, L) and lengths (B,) int32 or int64, w_ih / w_hh (G E, E), b_ih / b_hh (G E) of the table's dtype,
+ * hidden size == E, PyTorch's gate order.  cell: 0 rnn (tanh, G = 1), 1 lstm (G = 4), 2 gru (G = 3).  Per sample, with
+ * len = clamp(lengths[b], 0, L), x_t = table[idx[b, t]], h_{-1} = c_{-1} = 0 and t < len:
+ *   rnn:  h_t = tanh(W_ih x_t + b_ih + W_hh h_{t-1} + b_hh)
+ *   lstm: [i f g o] = W_ih x_t + b_ih + W_hh h_{t-1} + b_hh;  c_t = s(f) c_{t-1} + s(i) tanh(g);  h_t = s(o) tanh(c_t)
+ *   gru:  r, z = s(W_i* x_t + b_i* + W_h* h_{t-1} + b_h*);  n = tanh(W_in x_t + b_in + r (W_hn h_{t-1} + b_hn));
+ *         h_t = (1 - z) n + z h_{t-1}
+ *   mode 0: out (B, E) = *scale * sum_{t < len} h_t;      mode 1: out (B, L, E) = h_t, zeros from t = len on.
+ * replaces the sort / aten::embedding / pack_padded_sequence (a host read of the lengths) / nn.LSTM | nn.GRU | nn.RNN /
+ * pad_packed_sequence / un-sort / pooling chain of inputs/base/sequence_indices_emb.py:128-171; the (B, L, E) block of
+ * looked-up rows is never formed.  scale: ONE float in device memory that the forward writes before its main kernel --
+ * 1 / max_b len (the reference's divisor: pad_packed_sequence pads to the batch maximum; 0 when every length is 0) with
+ * average != 0, else 1 -- and the backward reads.  No host synchronisation.
+ * h_save (B, L, E) of the value dtype (h_t, zeros from t = len on) and c_save (B, L, E) fp32 (the lstm's c_t, written for
+ * t < len only) are what the backward needs; either may be NULL in a forward that no backward follows.  fp32 FMA between
+ * loads and stores; h_t is rounded to the value dtype once per step (the next step's operand and the saved state are the
+ * same number).
+ * Index rules: an id outside [0, V) at a live step reads as a zero row and raises *err_flag; ids at t >= len are never
+ * read.  A length outside [1, L] is clamped to [0, L] and raises the same flag; length 0 gives a zero output row.
+ * trs_seq_rnn_path (a pure function): 0 not covered; 1 the vector path (fp32 FMA; fp32 or bf16 operands, 1 <= E <= 128,
+ *   any L >= 1, all three cells); 2 the matrix-core path (mfma_f32_16x16x32_bf16): bf16, E in {16, 32, 64} for all three
+ *   cells, any L >= 1.  There a wave keeps its B fragments of [W_ih | W_hh] (and, in the backward, of W_hh by rows) in
+ *   REGISTERS for its whole tile of samples, not in LDS: 16 (forward) + 8 (backward) fragments of four registers at the
+ *   lstm's E = 64, which is what bounds E -- E = 128 would need four times that, and E = 48 is three 16-unit tiles that
+ *   four waves do not divide; both take path 1.  The A operands are x_t (bf16 rows of the table: exact) and h_{t-1}
+ *   (rounded once per step on both paths); in the backward's dh_{t-1} = dgates_h W_hh the A operand is dgates_h as it is
+ *   stored, i.e. rounded to bf16.  fp32 accumulators.  Weight pointers that are not 16-byte aligned take the path-1
+ *   kernels (same results to rounding; the path function, being pure, still says 2).
+ * workspace: trs_seq_rnn_workspace_bytes(cell, E) = 2 G E E floats, a transposed fp32 image of the two weight matrices
+ *   that each entry writes for itself (contents need not survive between calls).
+ * Backward, t from len - 1 down to 0 with dh (and dc) on chip, the gates recomputed from x_t and the saved state; gout is
+ * (B, E) for mode 0 and (B, L, E) for mode 1, of the value dtype:
+ *   dgates (B, L, G E) of the value dtype: the gradient of the pre-activations on the INPUT side, zeros from t = len on;
+ *   dgates_h (B, L, G E), gru only (NULL for the other cells, whose two sides are equal): the whole block on the HIDDEN
+ *   side -- blocks r and z repeat dgates, block n is r * dn.  dh_{t-1} = dgates_h W_hh (+ z dh_t for the gru) on chip.
+ *   The caller's GEMMs finish: dX = dgates W_ih -> trs_scatter_rows*, dW_ih = dgates^T X, dW_hh = dgates_h^T H_prev (the
+ *   saved h shifted by one step), the biases as column sums.  No atomics, a static deal of samples to workgroups (which
+ *   needs no count from the caller), fixed summation order: out, h_save, c_save, dgates and dgates_h have reproducible
+ *   bits, and so has dX.  The TABLE gradient is not these entries' result: dX reaches the table through the row buckets
+ *   (trs_csr_build*), where the order of a bucket's entries comes from int32 atomics, so for a row that more than two
+ *   live positions look up its last bit may differ between two bucket builds, as for every lookup of this library.
+ * B == 0 returns TRS_OK and touches nothing.  Errors: NULL pointer, B < 0, bad cell / mode / index dtype, an lstm without
+ * c_save or a gru without dgates_h in the backward TRS_EINVAL; dtype TRS_EDTYPE; a shape the path function refuses
+ * TRS_ESHAPE; a workspace that is too small TRS_EWORKSPACE -- all before any launch.                                 */
+int trs_seq_rnn_path(int32_t cell, int32_t L, int32_t E, int32_t dtype);
+size_t trs_seq_rnn_workspace_bytes(int32_t cell, int32_t E);
+int trs_seq_rnn_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                    const void* lengths, int32_t len_dtype, int64_t B, int32_t L, const void* w_ih, const void* w_hh,
+                    const void* b_ih, const void* b_hh, int32_t cell, int32_t mode, int32_t average, float* scale,
+                    void* out, void* h_save, float* c_save, void* workspace, size_t ws_bytes, int32_t* err_flag,
+                    trs_stream_t stream);
+int trs_seq_rnn_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                    const void* lengths, int32_t len_dtype, int64_t B, int32_t L, const void* w_ih, const void* w_hh,
+                    const void* b_ih, const void* b_hh, int32_t cell, int32_t mode, const float* scale,
+                    const void* h_save, const float* c_save, const void* gout, void* dgates, void* dgates_h,
+                    void* workspace, size_t ws_bytes, trs_stream_t stream);
+
 /* ---- index staging: pack per-field columns into the (B,N) index matrix --------
  * out[b, c] = src_j[b * width_j + t]  for the c-th output column = column t of source j.
  * replaces the per-field unsqueeze + torch.cat of inputs/inputs.py:75-80 by one pass.

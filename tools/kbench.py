@@ -12,7 +12,10 @@ of a large shard through either (own inputs, see bench_compact).
 alone, and the experts' share of the whole layer (own inputs, see bench_moe).
 --what routing [--L 50] [--R 64] [--caps 8] [--routing-iters 3]: DynamicRoutingLayer over lists of L behaviours, the fused
 path against the same module with the switch off, the two kernels alone, the noise draw and the peak allocations (own
-inputs, see bench_routing)."""
+inputs, see bench_routing).
+--what seq [--L 50] [--cell lstm|gru|rnn]: SequenceIndicesEmbedding(output_method='avg_pooling') over ordered lists of L ids
+with lengths uniform in [1, L], the fused path against the same module with the switch off, and the two kernels alone (own
+inputs, see bench_seq)."""
 import argparse
 import os
 import sys
@@ -581,6 +584,118 @@ def bench_routing(a):
               f"{alg / 1e6:8.0f} MB (alg) {alg / med / 1e12:5.2f} TB/s = {alg / med / 8e12:.2f} of 8 TB/s", flush=True)
 
 
+def bench_seq(a):
+    """Sequence embedding (csrc/seq_rnn.hip) at (B, L, E, V, cell): forward and forward+backward of
+    SequenceIndicesEmbedding(output_method='avg_pooling') with lengths uniform in [1, L], the fused path against the SAME
+    module with the switch off (inputs.SEQ_RNN_FUSED = False: HIP gather, the module's own nn.LSTM / nn.GRU / nn.RNN on a
+    packed sequence with its host read of the lengths, ATen mean), taking turns inside every round; the forward's peak
+    allocation of either; then the two kernels alone with their FMA rate.  Every figure is the median of ``--rounds``
+    per-round medians with their min..max."""
+    from torecsys_amd import inputs as I
+    from torecsys_amd._abi import call, index_dtype_code, ptr, size_query, stream_ptr, value_dtype_code
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, L, E, V, cell = a.B, a.L, a.E, a.V, a.cell
+    G = F_.SEQ_RNN_GATES[F_.SEQ_RNN_CELLS[cell]]
+    g = torch.Generator(device=dev).manual_seed(1234)
+    lengths = torch.randint(1, L + 1, (B,), generator=g, device=dev)
+    idx = torch.randint(1, V, (B, L), generator=g, device=dev)
+    idx = torch.where(torch.arange(L, device=dev).view(1, L) < lengths.view(B, 1), idx, torch.zeros_like(idx))
+    m = I.SequenceIndicesEmbedding(embed_size=E, field_size=V, rnn_method=cell, output_method="avg_pooling").to(dev).to(dt)
+    gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+    steps = int(lengths.sum())
+    flops = 2.0 * steps * 2 * G * E * E                     # the two matrix-vector products of every live step
+    alg = steps * (8 + E * s) + B * (8 + E * s) + 2 * G * E * E * s
+    print(f"sequence embedding B={B} L={L} E={E} V={V} {cell} {a.dtype} path {F_.seq_rnn_path(cell, L, E, dt)}, live steps "
+          f"{steps / (B * L):.2f} of B*L, {a.rounds} rounds x {a.iters} launches; forward: {alg / 1e6:.0f} MB (alg), "
+          f"{flops / 1e9:.1f} GFLOP", flush=True)
+
+    def module(fused):
+        def f():
+            I.SEQ_RNN_FUSED = fused
+            return m(idx, lengths).rename(None)
+        return f
+
+    def fwd_bwd(f):
+        def run():
+            F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+            for p in m.parameters():
+                p.grad = None
+            f().backward(gout)
+        return run
+
+    cands = []
+    for name, f in (("seq_rnn (HIP)", module(True)), ("composition (ATen)", module(False))):
+        try:
+            fwd_bwd(f)()
+            torch.cuda.synchronize()
+            cands.append((name, f))
+        except Exception as e:      # noqa: BLE001 -- a cell / dtype this torch build does not serve
+            print(f"{name:22s} not supported on this torch build ({type(e).__name__}: {str(e)[:120]})", flush=True)
+    for name, f in cands:
+        with torch.no_grad():
+            f()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        y = f()
+        torch.cuda.synchronize()
+        print(f"{name:22s} forward peak allocation {(torch.cuda.max_memory_allocated() - base) / 2**20:9.1f} MiB "
+              f"((B, L, E) block: {B * L * E * s / 2**20:.1f} MiB)", flush=True)
+        del y
+    res = {}
+    for what in ("fwd", "fwd+bwd"):
+        per = {name: [] for name, _ in cands}
+        for _ in range(a.rounds):
+            for name, f in cands:
+                if what == "fwd":
+                    with torch.no_grad():
+                        per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                else:
+                    per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+        for name, ts in per.items():
+            ts = sorted(ts)
+            res[(what, name)] = ts[len(ts) // 2]
+            print(f"{what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                  f"{ts[-1] * 1e6:9.1f} us", flush=True)
+        if len(cands) == 2:
+            print(f"{what:8s} composition / seq_rnn = "
+                  f"{res[(what, 'composition (ATen)')] / res[(what, 'seq_rnn (HIP)')]:.2f}x", flush=True)
+    I.SEQ_RNN_FUSED = True
+    for p in m.parameters():
+        p.grad = None
+    # the two kernels alone (the backward without its GEMMs and the bucket walk behind it)
+    w = m.embedding.weight.detach()
+    wi, wh, bi, bh = (p.detach().contiguous() for p in m._rnn_params())
+    code, ccode = value_dtype_code(w), F_.SEQ_RNN_CELLS[cell]
+    out = torch.empty(B, E, dtype=dt, device=dev)
+    scale = torch.empty(1, dtype=torch.float32, device=dev)
+    h = torch.empty(B, L, E, dtype=dt, device=dev)
+    c = torch.empty(B, L, E, dtype=torch.float32, device=dev) if cell == "lstm" else None
+    dg = torch.empty(B, L, G * E, dtype=dt, device=dev)
+    dgh = torch.empty(B, L, G * E, dtype=dt, device=dev) if cell == "gru" else None
+    ws_bytes = size_query("trs_seq_rnn_workspace_bytes", ccode, E)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    g2 = gout.view(B, E)
+
+    def k_fwd():
+        call("trs_seq_rnn_fwd", ptr(w), V, E, code, ptr(idx), index_dtype_code(idx), ptr(lengths), index_dtype_code(lengths),
+             B, L, ptr(wi), ptr(wh), ptr(bi), ptr(bh), ccode, 0, 1, ptr(scale), ptr(out), ptr(h), ptr(c), ptr(ws), ws_bytes,
+             None, stream_ptr())
+
+    def k_bwd():
+        call("trs_seq_rnn_bwd", ptr(w), V, E, code, ptr(idx), index_dtype_code(idx), ptr(lengths), index_dtype_code(lengths),
+             B, L, ptr(wi), ptr(wh), ptr(bi), ptr(bh), ccode, 0, ptr(scale), ptr(h), ptr(c), ptr(g2), ptr(dg), ptr(dgh),
+             ptr(ws), ws_bytes, stream_ptr())
+
+    for name, f, fl in (("trs_seq_rnn_fwd (saving h, c)", k_fwd, flops), ("trs_seq_rnn_bwd", k_bwd, 1.5 * flops)):
+        ts = sorted(timeit(f, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+        med = ts[len(ts) // 2]
+        print(f"kernel   {name:30s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
+              f"{fl / med / 1e12:6.1f} TFLOP/s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -590,7 +705,7 @@ def main():
     ap.add_argument("--V", type=int, default=1_000_000)
     ap.add_argument("--zipf", action="store_true")
     ap.add_argument("--what", default="all")
-    ap.add_argument("--L", type=int, default=50, help="bag / attn / routing: list length")
+    ap.add_argument("--L", type=int, default=50, help="bag / attn / routing / seq: list length")
     ap.add_argument("--H", type=int, default=1, help="attn: attention heads")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
     ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe / routing: alternating rounds")
@@ -599,7 +714,10 @@ def main():
     ap.add_argument("--R", type=int, default=64, help="routing: routed size")
     ap.add_argument("--caps", type=int, default=8, help="routing: max_num_caps")
     ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
+    ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"], help="seq: the recurrent cell")
     a = ap.parse_args()
+    if a.what == "seq":          # own inputs and module: not part of "all"
+        return bench_seq(a)
     if a.what == "routing":      # own inputs and module: not part of "all"
         return bench_routing(a)
     if a.what == "compact":      # own inputs (a 125 M-row table and its Adagrad state): not part of "all"

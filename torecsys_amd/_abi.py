@@ -122,6 +122,12 @@ SIGNATURES = {
     "trs_dynamic_routing_path": (c_int32, [_I32, _I32, _I32, _I32]),
     "trs_dynamic_routing_fwd": (c_int32, [_P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "trs_dynamic_routing_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
+    "trs_seq_rnn_path": (c_int32, [_I32, _I32, _I32, _I32]),
+    "trs_seq_rnn_workspace_bytes": (_SZ, [_I32, _I32]),
+    "trs_seq_rnn_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _P,
+                                  _P, _P, _P, _P, _SZ, _P, _P]),
+    "trs_seq_rnn_bwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P,
+                                  _P, _P, _P, _P, _P, _SZ, _P]),
     "trs_fm_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P]),
     "trs_fm_bwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_pair_dot_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),

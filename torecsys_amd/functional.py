@@ -2035,6 +2035,221 @@ def dynamic_routing(x: torch.Tensor, S: torch.Tensor, noise: torch.Tensor, num_i
 
 
 # --------------------------------------------------------------------------------------------
+# An ordered (B, L) list of ids through a one-layer RNN / LSTM / GRU, pooled over the live steps
+# --------------------------------------------------------------------------------------------
+SEQ_RNN_CELLS = {"rnn": 0, "lstm": 1, "gru": 2}
+SEQ_RNN_GATES = {0: 1, 1: 4, 2: 3}
+SEQ_RNN_MODES = {"avg": (0, 1), "sum": (0, 0), "none": (1, 0)}      # name -> (kernel mode, average)
+SEQ_RNN_PATH_VECTOR, SEQ_RNN_PATH_MATRIX = 1, 2
+
+
+def _seq_cell_code(cell) -> int:
+    if isinstance(cell, str):
+        if cell not in SEQ_RNN_CELLS:
+            raise ValueError(f'seq_rnn: cell must be one of {sorted(SEQ_RNN_CELLS)}, got {cell!r}')
+        return SEQ_RNN_CELLS[cell]
+    return int(cell)
+
+
+def seq_rnn_path(cell, L: int, E: int, dtype: torch.dtype) -> int:
+    """0: no fused kernel for this cell / shape / dtype (callers keep the composition); SEQ_RNN_PATH_VECTOR: the fp32-FMA
+    kernels (fp32 or bf16 operands, 1 <= E <= 128, any L >= 1); SEQ_RNN_PATH_MATRIX: the matrix-core kernels (bf16, E in
+    {16, 32, 64}, any L >= 1).  trs_seq_rnn_path; a pure function, callable without a device.  ``cell``: 'rnn' | 'lstm' |
+    'gru' or its code."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return 0
+    code = _abi.TRS_F32 if dtype == torch.float32 else _abi.TRS_BF16
+    return size_query("trs_seq_rnn_path", _seq_cell_code(cell), int(L), int(E), code)
+
+
+def _seq_operands(weight, idx, lengths, w_ih, w_hh, b_ih, b_hh, cell, **more):
+    named = dict(weight=weight, idx=idx, lengths=lengths, w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh, **more)
+    for name, t in named.items():
+        if t is not None and not t.is_contiguous():      # the entries read dense rows: a strided operand would be misread
+            raise ValueError(f"seq_rnn: {name} must be contiguous, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+    require_device(*named.values())
+    if weight.dim() != 2 or idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError(f"seq_rnn: weight (V, E) and idx (B, L >= 1) expected, got {tuple(weight.shape)} and "
+                         f"{tuple(idx.shape)}")
+    (V, E), (B, L) = weight.shape, idx.shape
+    cell = _seq_cell_code(cell)
+    if cell not in SEQ_RNN_GATES:
+        raise ValueError(f"seq_rnn: bad cell code {cell}")
+    GE = SEQ_RNN_GATES[cell] * E
+    if tuple(lengths.shape) != (B,):
+        raise ValueError(f"seq_rnn: lengths ({B},) expected, got {tuple(lengths.shape)}")
+    for name, t, shape in (("w_ih", w_ih, (GE, E)), ("w_hh", w_hh, (GE, E)), ("b_ih", b_ih, (GE,)), ("b_hh", b_hh, (GE,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"seq_rnn: {name} {shape} expected, got {tuple(t.shape)}")
+        if t.dtype != weight.dtype:
+            raise TypeError(f"seq_rnn: {name} must have the table's dtype {weight.dtype}, got {t.dtype}")
+    code = value_dtype_code(weight)
+    if seq_rnn_path(cell, L, E, weight.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: seq_rnn does not cover L={L}, E={E}, {weight.dtype} (L >= 1, 1 <= E <= 128, "
+                                  f"fp32 / bf16)")
+    return V, E, B, L, GE, cell, code
+
+
+def _seq_workspace(cell: int, E: int, dev) -> Tuple[torch.Tensor, int]:
+    ws_bytes = size_query("trs_seq_rnn_workspace_bytes", cell, E)
+    return torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes
+
+
+def seq_rnn_forward_raw(weight: torch.Tensor, idx: torch.Tensor, lengths: torch.Tensor, w_ih: torch.Tensor,
+                        w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor, cell, mode: int, average: bool = True,
+                        save: bool = False, flag: Optional[_ErrFlag] = None):
+    """trs_seq_rnn_fwd as it is (no autograd).  ``mode`` 0: (B, E) = scale * sum of the live h_t, 1: (B, L, E) every h_t.
+    Returns ``(out, scale, h_save, c_save)``: the one-float device scale (1 / max(lengths) with ``average``, else 1) and,
+    with ``save``, what the backward reads -- h (B, L, E) of the value dtype (``out`` itself in mode 1) and the LSTM's fp32
+    c (B, L, E), else None.  A non-contiguous operand raises ValueError."""
+    V, E, B, L, GE, cell, code = _seq_operands(weight, idx, lengths, w_ih, w_hh, b_ih, b_hh, cell)
+    if mode not in (0, 1):
+        raise ValueError(f"seq_rnn: mode 0 or 1 expected, got {mode}")
+    dev = weight.device
+    out = torch.empty((B, E) if mode == 0 else (B, L, E), dtype=weight.dtype, device=dev)
+    scale = torch.empty(1, dtype=torch.float32, device=dev)
+    h = torch.empty(B, L, E, dtype=weight.dtype, device=dev) if save and mode == 0 else None
+    c = torch.empty(B, L, E, dtype=torch.float32, device=dev) if save and cell == SEQ_RNN_CELLS["lstm"] else None
+    ws, ws_bytes = _seq_workspace(cell, E, dev)
+    call("trs_seq_rnn_fwd", ptr(weight), V, E, code, ptr(idx), index_dtype_code(idx), ptr(lengths),
+         index_dtype_code(lengths), B, L, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), cell, mode, int(bool(average)),
+         ptr(scale), ptr(out), ptr(h), ptr(c), ptr(ws), ws_bytes, ptr(flag.t if flag is not None else None), stream_ptr())
+    return out, scale, (out if save and mode == 1 else h), c
+
+
+def seq_rnn_backward_raw(weight: torch.Tensor, idx: torch.Tensor, lengths: torch.Tensor, w_ih: torch.Tensor,
+                         w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor, cell, mode: int, scale: torch.Tensor,
+                         h: torch.Tensor, c: Optional[torch.Tensor], gout: torch.Tensor):
+    """trs_seq_rnn_bwd as it is: the forward's operands, scale and saved state, gout (B, E) for mode 0 / (B, L, E) for
+    mode 1 -> ``(dgates, dgates_h)``, both (B, L, G E) of the value dtype; ``dgates_h`` is ``dgates`` itself except for the
+    GRU (whose n block differs on the hidden side)."""
+    V, E, B, L, GE, cell, code = _seq_operands(weight, idx, lengths, w_ih, w_hh, b_ih, b_hh, cell, scale=scale, h=h, c=c,
+                                               gout=gout)
+    if mode not in (0, 1):
+        raise ValueError(f"seq_rnn: mode 0 or 1 expected, got {mode}")
+    lstm, gru = cell == SEQ_RNN_CELLS["lstm"], cell == SEQ_RNN_CELLS["gru"]
+    for name, t, shape, dtype in (("scale", scale, (1,), torch.float32), ("h", h, (B, L, E), weight.dtype),
+                                  ("c", c, (B, L, E), torch.float32),
+                                  ("gout", gout, (B, E) if mode == 0 else (B, L, E), weight.dtype)):
+        if t is None and (name != "c" or lstm):
+            raise ValueError(f"seq_rnn: {name} is required")
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype):
+            raise ValueError(f"seq_rnn: {name} {shape} of {dtype} expected, got {tuple(t.shape)} {t.dtype}")
+    dev = weight.device
+    dgates = torch.empty(B, L, GE, dtype=weight.dtype, device=dev)
+    dgates_h = torch.empty(B, L, GE, dtype=weight.dtype, device=dev) if gru else None
+    ws, ws_bytes = _seq_workspace(cell, E, dev)
+    call("trs_seq_rnn_bwd", ptr(weight), V, E, code, ptr(idx), index_dtype_code(idx), ptr(lengths),
+         index_dtype_code(lengths), B, L, ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), cell, mode, ptr(scale), ptr(h),
+         ptr(c if lstm else None), ptr(gout), ptr(dgates), ptr(dgates_h), ptr(ws), ws_bytes, stream_ptr())
+    return dgates, (dgates_h if gru else dgates)
+
+
+class _SeqRNN(Function):
+    """One kernel per direction for the chain; the sums over the batch are GEMMs here, as in _DynamicRouting and _MoEGate:
+    dX = dgates W_ih (-> the row-bucket walk), dW_ih = dgates^T X with X gathered again (the forward never formed it),
+    dW_hh = dgates_h^T H_prev with H_prev the saved h shifted by one step, the biases as column sums.  The list positions
+    from a sample's length on are masked to the padding id for the gather and the walk: their dgates rows are zero, and
+    whatever ids sit there are never looked up."""
+
+    @staticmethod
+    def forward(ctx, weight, idx, lengths, w_ih, w_hh, b_ih, b_hh, cell, mode, average, padding_idx):
+        w, wi, wh, bi, bh = (t.contiguous() for t in (weight, w_ih, w_hh, b_ih, b_hh))
+        V, E = w.shape
+        L = idx.shape[1]
+        need = ctx.needs_input_grad
+        ctx.empty = idx.shape[0] == 0
+        save = any(need) and not ctx.empty
+        flag = _ErrFlag(w.device)
+        out, scale, h, c = seq_rnn_forward_raw(w, idx, lengths, wi, wh, bi, bh, cell, mode, average, save=save, flag=flag)
+        flag.check("seq_rnn")
+        ctx.cell, ctx.mode = cell, mode
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None      # as _BagPool: no walk reads that bucket
+        if save:
+            idx_m = None
+            if need[0] or need[3]:
+                live = torch.arange(L, device=idx.device).unsqueeze(0) < lengths.unsqueeze(1)
+                idx_m = torch.where(live, idx, torch.full_like(idx, ctx.skip if ctx.skip is not None else 0))
+                if need[0] and not torch.cuda.is_current_stream_capturing():
+                    # (a capture stays one chain on one stream: the backward then builds the buckets in line)
+                    prefetch_row_buckets(idx_m, None, V, skip_row=ctx.skip)
+            ctx.has_idx_m, ctx.has_c = idx_m is not None, c is not None
+            extra = [t for t in (idx_m, c) if t is not None]
+            ctx.save_for_backward(idx, lengths, weight, w_ih, w_hh, b_ih, b_hh, scale, h, *extra)
+        elif ctx.empty:
+            ctx.save_for_backward(weight, w_ih, w_hh, b_ih, b_hh)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if ctx.empty:      # no sample: zero gradients
+            zeros = [torch.zeros_like(t) if n else None
+                     for t, n in zip(ctx.saved_tensors, (ctx.needs_input_grad[0],) + tuple(ctx.needs_input_grad[3:7]))]
+            return (zeros[0], None, None, *zeros[1:], None, None, None, None)
+        idx, lengths, weight, w_ih, w_hh, b_ih, b_hh, scale, h = ctx.saved_tensors[:9]
+        extra = list(ctx.saved_tensors[9:])
+        idx_m = extra.pop(0) if ctx.has_idx_m else None
+        c = extra.pop(0) if ctx.has_c else None
+        _adopt_grads(g)
+        need = ctx.needs_input_grad
+        V, E = weight.shape
+        B, L = idx.shape
+        w, wi, wh, bi, bh = (t.contiguous() for t in (weight, w_ih, w_hh, b_ih, b_hh))
+        dgates, dgates_h = seq_rnn_backward_raw(w, idx, lengths, wi, wh, bi, bh, ctx.cell, ctx.mode, scale, h, c,
+                                                g.contiguous())
+        GE = dgates.shape[2]
+        dg, dgh = dgates.view(B * L, GE), dgates_h.view(B * L, GE)
+        g_w = g_wih = g_whh = g_bih = g_bhh = None
+        if need[3]:
+            x = torch.empty(B, L, E, dtype=w.dtype, device=w.device)
+            # the gather range-checks only when it is handed a flag (rows out of range then read as zeros, as in the
+            # forward, which has reported them already: this one is not read back)
+            call("trs_gather_rows", ptr(w), V, E, value_dtype_code(w), ptr(idx_m), index_dtype_code(idx_m), None, B, L,
+                 ptr(x), ptr(_ErrFlag(w.device).t), stream_ptr())
+            g_wih = torch.mm(dg.t(), x.view(B * L, E))
+        if need[4]:
+            h_prev = torch.cat([h.new_zeros(B, 1, E), h[:, :-1]], dim=1)
+            g_whh = torch.mm(dgh.t(), h_prev.view(B * L, E))
+        if need[5]:
+            g_bih = dg.sum(0)
+        if need[6]:
+            g_bhh = dgh.sum(0)
+        if need[0]:
+            dx = torch.mm(dg, wi).view(B, L, E)
+            rb = row_buckets(idx_m, None, V, skip_row=ctx.skip)
+            g_w = scatter_rows(rb, weight, g_rows=dx, padding_row=ctx.padding_idx)
+        return g_w, None, None, g_wih, g_whh, g_bih, g_bhh, None, None, None, None
+
+
+def seq_rnn(weight: torch.Tensor, idx: torch.Tensor, lengths: torch.Tensor, w_ih: torch.Tensor, w_hh: torch.Tensor,
+            b_ih: torch.Tensor, b_hh: torch.Tensor, cell: str = "lstm", mode: str = "avg",
+            padding_idx: Optional[int] = None) -> torch.Tensor:
+    """The looked-up rows of an ordered, padded (B, L) list of ids through a one-layer ``cell`` ('rnn' | 'lstm' | 'gru',
+    hidden size E, PyTorch's parameter layout) over the first ``lengths[b]`` steps of every sample, in one HIP pass per
+    direction (csrc/seq_rnn.hip).  ``mode``: 'avg' -> (B, 1, E), the sum of the live h_t over ``max(lengths)`` (the
+    divisor pad_packed_sequence leaves the reference's pooling with; read on the device); 'sum' -> (B, 1, E) unscaled;
+    'none' -> (B, L, E), zeros from each sample's length on.  No sort, no packing and no host read of the lengths: the
+    call can be captured in a graph.  ``padding_idx``: the table row that receives no gradient.  All parameters of the
+    table's dtype (fp32 / bf16); raises NotImplementedError for what ``seq_rnn_path`` refuses."""
+    if mode not in SEQ_RNN_MODES:
+        raise ValueError(f'seq_rnn: mode must be one of {sorted(SEQ_RNN_MODES)}, got {mode!r}')
+    code = _seq_cell_code(cell)
+    idx = _as_index(idx)
+    lengths = _as_index(lengths)
+    w_ih, w_hh, b_ih, b_hh = (t.rename(None) if t.has_names() else t for t in (w_ih, w_hh, b_ih, b_hh))
+    # shapes and dtypes are checked before the node is built (contiguity is the node's own business)
+    _seq_operands(weight.contiguous(), idx, lengths, w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(),
+                  b_hh.contiguous(), code)
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = weight.shape[0] + padding_idx
+    kmode, average = SEQ_RNN_MODES[mode]
+    out = _SeqRNN.apply(weight, idx, lengths, w_ih, w_hh, b_ih, b_hh, code, kmode, bool(average), padding_idx)
+    return out.unsqueeze(1) if kmode == 0 else out
+
+
+# --------------------------------------------------------------------------------------------
 # K3: field-aware FM pair products
 # --------------------------------------------------------------------------------------------
 class _FFM(Function):

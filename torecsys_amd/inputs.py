@@ -287,6 +287,122 @@ class ListIndicesEmbedding(BaseInput):
         raise NotImplementedError('torecsys_amd: show_attention (a plotting helper) is not provided')
 
 
+# TRS_SEQ_RNN=0: SequenceIndicesEmbedding runs the composition (HIP row gather, the module's own nn.LSTM / nn.GRU / nn.RNN
+# on a packed sequence, ATen pooling) instead of the fused kernels, which are the default on the strength of the timing in
+# profiles/seq_rnn_kernels.md (forward + backward 4.4x to 5.5x faster at the workload shape)
+SEQ_RNN_FUSED = os.environ.get("TRS_SEQ_RNN", "1") not in ("", "0")
+
+
+class SequenceIndicesEmbedding(BaseInput):
+    """sequence_indices_emb.py:11-171: an ordered, padded (B, L) list of ids and its (B,) lengths -> embedding rows ->
+    one-layer LSTM / GRU / RNN over the first ``lengths[b]`` steps -> pooling, named ('B','N','E').  Constructor
+    signature, attributes (``length``, ``embedding``, ``rnn_layers``, ``output_method``) and ``state_dict`` keys
+    (``embedding.weight``, ``rnn_layers.{weight,bias}_{ih,hh}_l0``) are the reference's: the module holds a real
+    ``nn.LSTM`` / ``nn.GRU`` / ``nn.RNN``, so a reference checkpoint loads.  The reference hands ``num_layers``, ``bias``,
+    ``bidirectional`` and ``dropout`` on to ``nn.Embedding``, which raises TypeError for each of them; so do they here --
+    every instance is one layer, one direction, with biases and hidden size ``embed_size``.
+
+    ``output_method``:
+      'avg_pooling'  (B, 1, E): the sum of h_t over t < lengths[b], divided by max(lengths) of the BATCH (what the
+                     reference's pooling over the pad_packed_sequence output computes; not L, not the sample's own length).
+                     The fused path: one kernel, no sort, no packing, no host read of the lengths -- capturable in a graph.
+      'mean', 'sum'  raise RuntimeError in the reference (dim='N' on an un-named tensor); here 'mean' is 'avg_pooling' and
+                     'sum' the unscaled sum -- a deliberate difference, the same one ListIndicesEmbedding documents.
+      'none'         (B, max(lengths), E), zeros from each sample's length on; one host read of max(lengths), as in the
+                     reference.
+      'max_pooling'  the reference tests ``in ['avg_pooling' or 'max_pooling']``, i.e. ``in ['avg_pooling']``, so this
+                     method falls into the other branch and AdaptiveMaxPool1d(1) runs over the LAST dim of (B, L', E):
+                     the result is (B, max(lengths), 1), the maximum over E.  Kept as it is (every h_t from the kernel,
+                     then an ATen amax), since that is what a model built on the reference was trained with.
+    ``TRS_SEQ_RNN=0`` and every cell / shape / dtype ``functional.seq_rnn_path`` refuses run the composition: HIP row
+    gather, ``rnn_layers`` on a packed sequence, ATen pooling (the fused path is the default by the timing in
+    profiles/seq_rnn_kernels.md).  A length <= 0 raises
+    there (pack_padded_sequence), as in the reference; the fused path treats it as an empty sequence (zero row) and
+    raises the index flag.  A fused sparse optimizer is not implemented for this class: the walk would have to tell the
+    positions past a sample's length, which touch no row, from real lookups."""
+
+    _CELLS = {'rnn': nn.RNN, 'lstm': nn.LSTM, 'gru': nn.GRU}
+    _RNN_KWARGS = ('num_layers', 'bias', 'bidirectional', 'dropout')
+
+    def __init__(self, embed_size: int, field_size: int, padding_idx: Optional[int] = 0,
+                 rnn_method: Optional[str] = 'lstm', output_method: Optional[str] = 'avg_pooling',
+                 nn_embedding: Optional[nn.Parameter] = None, **kwargs):
+        super().__init__()
+        for k in self._RNN_KWARGS:
+            if k in kwargs:
+                raise TypeError(f"Embedding.__init__() got an unexpected keyword argument '{k}' (the reference passes its "
+                                f"RNN kwargs on to nn.Embedding: one layer, one direction, with biases is all there is)")
+        _check_embedding_kwargs(kwargs)
+        if nn_embedding is not None:
+            embed_size = nn_embedding.size('E') if nn_embedding.has_names() else nn_embedding.size(-1)
+            self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
+        else:
+            self.embedding = nn.Embedding(field_size, embed_size, padding_idx=padding_idx, **kwargs)
+        self.length = embed_size
+        self.padding_idx = self.embedding.padding_idx
+        if rnn_method not in self._CELLS:
+            raise ValueError('rnn_method only allows ["rnn", "lstm", "gru"].')
+        self.rnn_method = rnn_method
+        self.rnn_layers = self._CELLS[rnn_method](input_size=embed_size, hidden_size=embed_size, num_layers=1, bias=True,
+                                                  batch_first=True, dropout=0.0, bidirectional=False)
+        if output_method not in ('avg_pooling', 'max_pooling', 'mean', 'none', 'sum'):
+            raise ValueError('output_method only allows ["avg_pooling", "max_pooling", "mean", "none", "sum"].')
+        self.output_method = output_method
+
+    def set_fused_optimizer(self, opt):
+        if opt is not None:
+            raise NotImplementedError('torecsys_amd: a fused sparse optimizer is not implemented for '
+                                      'SequenceIndicesEmbedding (positions past a sample\'s length would count as touched '
+                                      'rows); use a dense optimizer')
+        return super().set_fused_optimizer(opt)
+
+    def set_schema(self, inputs: str, **kwargs):
+        lengths = kwargs.get('lengths', None)
+        if lengths is None:
+            raise ValueError('')
+        schema = namedtuple('Schema', ['inputs', 'lengths'])
+        self.schema = schema(inputs=[inputs], lengths=lengths)
+
+    def _rnn_params(self):
+        r = self.rnn_layers
+        return r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0
+
+    def _fused(self, idx: torch.Tensor) -> bool:
+        w = self.embedding.weight
+        if not (SEQ_RNN_FUSED and w.is_cuda and idx.shape[1] >= 1):
+            return False
+        if any(p.dtype != w.dtype or p.device != w.device for p in self._rnn_params()):
+            return False
+        return F_.seq_rnn_path(self.rnn_method, idx.shape[1], w.shape[1], w.dtype) != 0
+
+    def forward(self, inputs: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        idx, lens = _strip(inputs), _strip(lengths)
+        if idx.dim() != 2:
+            raise ValueError(f'inputs must be (B, L), got {tuple(idx.shape)}')
+        if lens.dim() != 1 or lens.shape[0] != idx.shape[0]:
+            raise ValueError(f'lengths must be ({idx.shape[0]},), got {tuple(lens.shape)}')
+        w, method = self.embedding.weight, self.output_method
+        if self._fused(idx):
+            mode = {'avg_pooling': 'avg', 'mean': 'avg', 'sum': 'sum'}.get(method, 'none')
+            out = F_.seq_rnn(w, idx, lens, *self._rnn_params(), cell=self.rnn_method, mode=mode,
+                             padding_idx=self.padding_idx)
+            if mode == 'none':
+                longest = min(max(int(lens.max()), 0), idx.shape[1]) if lens.numel() else 0      # the one host read
+                out = out[:, :longest]
+        else:
+            rows = F_.gather_rows(w, idx, None, self.padding_idx)                                 # (B, L, E)
+            packed = nn.utils.rnn.pack_padded_sequence(rows, lens.cpu(), batch_first=True, enforce_sorted=False)
+            seq, _ = self.rnn_layers(packed)
+            out, _ = nn.utils.rnn.pad_packed_sequence(seq, batch_first=True)                      # (B, max(lengths), E)
+            if method in ('avg_pooling', 'mean'):
+                out = out.mean(dim=1, keepdim=True)
+            elif method == 'sum':
+                out = out.sum(dim=1, keepdim=True)
+        if method == 'max_pooling':
+            out = out.amax(dim=2, keepdim=True)
+        return out.refine_names('B', 'N', 'E')
+
+
 class ValueInput(BaseInput):
     """inputs/base/value_inp.py:26-44 (pass-through; no kernel)."""
 
@@ -448,6 +564,10 @@ class Inputs(BaseInput):
                     inp = cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
                 packed[names] = inp
             args[k] = [inp]
+            # inputs.py:84 asks for 'SequenceIndexEmbedding', a class the reference does not have (its class is
+            # SequenceIndicesEmbedding, which therefore never receives its lengths there); both names are routed here
+            if emb_fn.__class__.__name__ in ('SequenceIndicesEmbedding', 'SequenceIndexEmbedding'):
+                args[k].append(inputs[emb_fn.schema.lengths])
         # The lookups of a batch are independent of each other: every plain lookup after the first goes onto the "lookup"
         # side stream.  What pays is the BACKWARD: autograd runs a node's backward on the stream of its forward, so the
         # bucket walk of the E = 1 first-order table of an FM-family model (one walk and four small launches, ~45 us at the

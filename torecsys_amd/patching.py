@@ -13,7 +13,8 @@ models/ctr/multigate_moe.py:56, deep_moe.py:55, and need no head wrapper), the c
 ``FeedForwardLayer`` -- layers/ctr/__init__.py:23-35; this is what ``DeepAndCrossNetworkModel.deep``,
 ``DeepFactorizationMachineModel.deep`` and ``XDeepFactorizationMachineModel.deep`` are built from,
 models/ctr/deep_and_cross_network.py:44, deep_fm.py:47, xdeep_fm.py:71), the three index-embedding
-inputs, the list-of-ids embedding ``ListIndicesEmbedding`` and the ``Inputs`` router (inputs/inputs.py:56-89).  ``patch(pkg, mlp=False)`` /
+inputs, the list-of-ids embedding ``ListIndicesEmbedding``, the ordered-sequence embedding ``SequenceIndicesEmbedding``
+(inputs/base/sequence_indices_emb.py) and the ``Inputs`` router (inputs/inputs.py:56-89).  ``patch(pkg, mlp=False)`` /
 ``patch(pkg, router=False)`` leave the MLP / the router with the reference.
 
 ``heads`` (default on): the scalar heads of ``FactorizationMachineModel``, ``DeepFactorizationMachineModel`` and
@@ -51,6 +52,7 @@ _INPUT_NAMES = ["SingleIndexEmbedding", "MultiIndicesEmbedding", "MultiIndicesFi
 _ROUTER_NAMES = ["Inputs"]
 _MOE_NAMES = ["MixtureOfExpertsLayer", "MOELayer"]
 _ROUTING_NAMES = ["DynamicRoutingLayer"]
+_SEQUENCE_NAMES = ["SequenceIndicesEmbedding"]
 _saved = {}
 _saved_defaults = {}
 
@@ -171,7 +173,8 @@ def patch(torecsys_pkg=None, fuse_fm: bool = True, mlp: bool = True, router: boo
     ``heads``: wrap the three first-order models' ``forward`` with the one-kernel head (module docstring)."""
     if torecsys_pkg is None:
         torecsys_pkg = importlib.import_module("torecsys")
-    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs), (_MOE_NAMES, _layers), (_ROUTING_NAMES, _layers)]
+    groups = [(_LAYER_NAMES, _layers), (_INPUT_NAMES, _inputs), (_MOE_NAMES, _layers), (_ROUTING_NAMES, _layers),
+              (_SEQUENCE_NAMES, _inputs)]
     if mlp:
         groups.append((_MLP_NAMES, _layers))
     if router:
