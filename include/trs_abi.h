@@ -548,6 +548,28 @@ int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int3
 int32_t trs_wgrad_rows_splits(int32_t M, int32_t N, int64_t rows);
 int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t ldx, int64_t rows, int32_t M, int32_t N,
                    int32_t dtype, int32_t S, float* part, trs_stream_t stream);
+/* 1 .. 8 such products over the SAME rows in one launch of the eight-wave LDS-DMA kernel (the tail layers of a deep
+ * branch): job k is g[k] (rows, ldg[k]) against x[k] (rows, ldx[k]) into part[k] (S, M[k], N[k]).  The arrays are HOST
+ * arrays; the job table travels in the kernel arguments, so nothing is uploaded or allocated and the launch can be
+ * captured.  trs_wgrad_rows_many_splits answers S > 0 when every job on its own takes that kernel (blocks of 12 | 13
+ * tiles, rows a multiple of 128 below 2^20) with the same block counts, every 208-column image lies inside its
+ * operand's row stride, strides are multiples of 8 that cover M / N and keep 32 rows under 2^31 bytes, the batch is
+ * resident in one round (blocks * jobs <= 32 per row range) and rows >= 256 * S (two 400 x 400 jobs: S = 32 from 8192
+ * rows on); 0 otherwise -- the caller keeps the per-layer calls.  trs_wgrad_rows_many takes exactly that S and 16-byte
+ * aligned operands and partials; every job is checked before anything is launched.  trs_wgrad_rows_many_map (host
+ * only) tells where workgroup ``block`` works: out = {job, row range, output block, first row, end row}, returns the
+ * grid size (0: not taken / no such block).  trs_wgrad_finish_many = trs_wgrad_finish for every job (one S, one dtype;
+ * gb[k] / gb_f32[k] both or neither) in one launch.                                                                  */
+int32_t trs_wgrad_rows_many_splits(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
+                                   const int32_t* ldx, int64_t rows);
+int32_t trs_wgrad_rows_many_map(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
+                                const int32_t* ldx, int64_t rows, int32_t block, int64_t* out);
+int trs_wgrad_rows_many(int32_t n_jobs, const void* const* g, const int32_t* ldg, const void* const* x,
+                        const int32_t* ldx, int64_t rows, const int32_t* M, const int32_t* N, int32_t S,
+                        float* const* part, trs_stream_t stream);
+int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
+                          const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                          const float* const* gb_f32, void* const* gb, trs_stream_t stream);
 /* the same product for a WIDE input, transposed: part (S, M_x, N_g) fp32, slice s = x[rows_s, :M_x]^T g[rows_s, :N_g] -- what
  * trs_wgrad_finish_t folds -- with no work spent on the padding columns of g.  Taken (trs_wgrad_wide_splits > 0) when M_x
  * is a multiple of 208 (at least two blocks of 13 tiles of 16), N_g a multiple of 16 that cuts into two blocks of 12 | 13

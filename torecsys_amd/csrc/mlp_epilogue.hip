@@ -257,15 +257,15 @@ static bool rowdot_shape_ok(int C, int dtype) {
 // the (S, R, Cc) fp32 partial products, cast to the parameter dtype; blockIdx.y == gridDim.y-1 also casts the fp32
 // bias gradient.  One launch instead of ATen's sum(0) + strided slice copy + cast (+ slice + cast for the bias).
 template <typename T>
-__global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restrict__ part, int S, int R, int Cc,
-                                                          int out_rows, int out_cols, T* __restrict__ gw,
-                                                          const float* __restrict__ gbf, T* __restrict__ gb) {
+__device__ __forceinline__ void wgrad_finish_body(const float* __restrict__ part, int S, int R, int Cc, int out_rows,
+                                                  int out_cols, T* __restrict__ gw, const float* __restrict__ gbf,
+                                                  T* __restrict__ gb) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if ((int)blockIdx.y == out_rows) {           // the extra row of workgroups: bias gradient
     if (gb != nullptr && c < out_rows) gb[c] = from_f32<T>(gbf[c]);
     return;
   }
-  if (c >= out_cols) return;
+  if ((int)blockIdx.y > out_rows || c >= out_cols) return;      // (a batched grid is sized by its largest job)
   const int r = blockIdx.y;
   const float* p = part + (size_t)r * Cc + c;
   const size_t stride = (size_t)R * Cc;
@@ -279,6 +279,33 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restri
   }
   for (; s < S; ++s) a0 += p[(size_t)s * stride];
   gw[(size_t)r * out_cols + c] = from_f32<T>((a0 + a1) + (a2 + a3));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restrict__ part, int S, int R, int Cc,
+                                                          int out_rows, int out_cols, T* __restrict__ gw,
+                                                          const float* __restrict__ gbf, T* __restrict__ gb) {
+  wgrad_finish_body<T>(part, S, R, Cc, out_rows, out_cols, gw, gbf, gb);
+}
+
+// The same finish for several weight gradients in one launch (the partials of trs_wgrad_rows_many): blockIdx.z is the
+// job, the table travels in the kernel arguments.
+constexpr int WF_MAXJ = 8;
+struct WgradFinishJob {
+  const float* part;
+  void* gw;
+  const float* gbf;
+  void* gb;
+  int R, Cc, out_rows, out_cols;
+};
+struct WgradFinishArgs {
+  WgradFinishJob job[WF_MAXJ];
+  int S;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad_finish_many_kernel(WgradFinishArgs a) {
+  const WgradFinishJob& j = a.job[blockIdx.z];
+  wgrad_finish_body<T>(j.part, a.S, j.R, j.Cc, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb);
 }
 
 // The finish of a layer with FEW output rows and MANY splits (the 400 -> 1 head at 65 536 rows: 256 partial products of
@@ -730,6 +757,35 @@ extern "C" int trs_wgrad_finish(const float* part, int32_t S, int32_t R, int32_t
     hipLaunchKernelGGL((wgrad_finish_kernel<bf16_t>), grid, dim3(256), 0, s, part, S, R, Cc, out_rows, out_cols,
                        (bf16_t*)gw, gb_f32, (bf16_t*)gb);
   return check_launch("wgrad_finish");
+}
+
+extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
+                                     const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                     void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
+  TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_many: NULL array");
+  TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_many: bad size");
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish_many: dtype %d", dtype);
+  WgradFinishArgs a{};
+  a.S = S;
+  int max_rows = 0, max_cols = 0;
+  for (int k = 0; k < n_jobs; ++k) {
+    TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
+                TRS_EINVAL, "wgrad_finish_many: bad size (job %d)", k);
+    TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_many: NULL pointer (job %d)", k);
+    TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_many: gb and gb_f32 go together (job %d)", k);
+    TRS_REQUIRE(gb[k] == nullptr || out_rows[k] <= ((out_cols[k] + 255) / 256) * 256, TRS_ESHAPE,
+                "wgrad_finish_many: out_rows %d exceeds the bias row of workgroups", out_rows[k]);
+    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k]};
+    max_rows = std::max(max_rows, out_rows[k]);
+    max_cols = std::max(max_cols, out_cols[k]);
+  }
+  dim3 grid((max_cols + 255) / 256, max_rows + 1, n_jobs);
+  if (dtype == TRS_F32)
+    hipLaunchKernelGGL((wgrad_finish_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((wgrad_finish_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("wgrad_finish_many");
 }
 
 extern "C" int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int32_t out_rows, int32_t out_cols,

@@ -55,6 +55,34 @@ struct WgradArgs {
 
 __host__ __device__ __forceinline__ int split_start(int total, int parts, int k) { return (int)(((int64_t)total * k) / parts); }
 
+// wgrad_dma_kernel's arguments: 1 .. WG_MAXJ products over the same rows in ONE launch (the tail layers of a deep branch:
+// two 400 x 400 products at 65 536 rows fill the chip once with 32 row ranges each instead of twice with 64, with half
+// the fp32 partials and one ramp).  The table travels by value in the kernel arguments: nothing is uploaded, so the
+// launch can be captured.  Every job is cut into the same MB x NB blocks and the same 8 * slots_per_xcd row ranges.
+constexpr int WG_MAXJ = 8;                 // = MF_MAXL (mlp_fused.hip): a fused stack has no more layers than that
+struct WgradJob {
+  const uint16_t* g;
+  const uint16_t* x;
+  float* part;               // (S, M, N) fp32
+  int ldg, ldx, M, N;
+};
+struct WgradManyArgs {
+  WgradJob job[WG_MAXJ];
+  int64_t rows;
+  int J, MB, NB, slots_per_xcd;
+};
+
+// workgroup b -> (job, row range ``slot`` of 8 * spx, output block ``tile`` of TB = MB * NB).  Blocks b and b + 8 share an
+// XCD (dealt round-robin), and the TB workgroups of one (job, range) are consecutive there: the second reader of a g / x
+// piece finds it in that XCD's L2.  Job-major inside an XCD; with one job this is the map the kernel always had.
+__host__ __device__ __forceinline__ void wdm_place(int TB, int spx, int b, int& job, int& slot, int& tile) {
+  const int xcd = b & 7, j = b >> 3, per_job = spx * TB;
+  job = j / per_job;
+  const int r = j - job * per_job;
+  slot = xcd * spx + r / TB;
+  tile = r % TB;
+}
+
 // 8 k-values x this lane's column: two transpose reads (``lo`` / ``hi``: the lane's addresses of rows +0..3 / +4..7 -- swapped
 // on odd lane groups --, ``off`` a compile-time byte offset that lands in the instruction's offset field)
 __device__ __forceinline__ wg_bf16x8 tr_frag(const char* lo_p, const char* hi_p, int off) {
@@ -296,16 +324,16 @@ __device__ __forceinline__ void wd_dma(const char* src, unsigned voff, unsigned 
 }
 
 template <int MC, int NC>
-__global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradArgs a) {
+__global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradManyArgs am) {
   extern __shared__ __attribute__((aligned(16))) char wg_lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane >> 4, i = lane & 15;
   const bool odd = q & 1;
-  const int TB = a.MB * a.NB;
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int slot = xcd * a.slots_per_xcd + j / TB;
+  int jb, slot, tile;
+  wdm_place(am.MB * am.NB, am.slots_per_xcd, blockIdx.x, jb, slot, tile);
+  const WgradJob& jd = am.job[jb];      // (uniform: scalar loads from the kernel arguments)
+  const WgradArgs a{jd.g, jd.x, jd.part, am.rows, jd.ldg, jd.ldx, jd.M, jd.N, am.MB, am.NB, am.slots_per_xcd, 0};
   const int S = 8 * a.slots_per_xcd;
-  const int tile = j % TB;
   const int mb = tile / a.NB, nb = tile % a.NB;
   const int Mt = (a.M + 15) >> 4, Nt = (a.N + 15) >> 4;
   const int bm0 = split_start(Mt, a.MB, mb), bm1 = split_start(Mt, a.MB, mb + 1);
@@ -628,6 +656,38 @@ static WgradPlan wgrad_plan(int M, int N, int64_t rows) {
   return p;
 }
 
+// Several products over the same rows in one launch of wgrad_dma_kernel.  Taken (S > 0) when every job on its own plans
+// to that kernel with the same MB x NB blocks, every 208-column image lies inside its operand's rows (h1 arrives 512
+// wide, gz 416: the row STRIDE bounds what a DMA may fetch, and M / N <= stride), the whole batch is resident at once
+// (MB * NB * J workgroups per range fit the 32 CUs of an XCD) and the rows give every one of the 8 * slots_per_xcd
+// ranges its four stages -- with fewer rows the batch would not fill the chip, and the per-layer launches stay.
+// Measured at 65 536 rows, two 400 x 400 jobs, product + finish (profiles/wgrad_many.md): one round of 256 workgroups,
+// 32 ranges per job, 66.5 us; two rounds of 256, 64 ranges per job, 89.5 us; the per-layer launches 89.0 us.
+struct ManyPlan {
+  int S = 0, MB = 0, NB = 0, slots_per_xcd = 0, grid = 0;
+};
+
+static ManyPlan wgrad_many_plan(int J, const int32_t* M, const int32_t* N, const int32_t* ldg, const int32_t* ldx, int64_t rows) {
+  ManyPlan mp;
+  if (J < 1 || J > WG_MAXJ || !M || !N || !ldg || !ldx || rows <= 0) return mp;
+  int MB = 0, NB = 0;
+  for (int k = 0; k < J; ++k) {
+    if (ldg[k] < M[k] || ldx[k] < N[k] || (ldg[k] & 7) || (ldx[k] & 7)) return mp;
+    if ((int64_t)WG_KS * std::max(ldg[k], ldx[k]) * 2 >= ((int64_t)1 << 31)) return mp;
+    const WgradPlan p = wgrad_plan(M[k], N[k], rows);
+    if (p.slots_per_xcd == 0 || p.dma != 1) return mp;
+    if (k > 0 && (p.MB != MB || p.NB != NB)) return mp;
+    MB = p.MB, NB = p.NB;
+    // the last block's image against the row stride (wgrad_plan checked it against M / N)
+    const int Mt = (M[k] + 15) / 16, Nt = (N[k] + 15) / 16;
+    if (16 * split_start(Mt, MB, MB - 1) + 208 > ldg[k] || 16 * split_start(Nt, NB, NB - 1) + 208 > ldx[k]) return mp;
+  }
+  const int spx = 32 / (MB * NB * J);
+  if (spx < 1 || rows / WG_KR / (8 * spx) < 4) return mp;
+  mp.S = 8 * spx, mp.MB = MB, mp.NB = NB, mp.slots_per_xcd = spx, mp.grid = 8 * spx * MB * NB * J;
+  return mp;
+}
+
 template <int WM, int WN, int MC, int NC, bool CHECK>
 int wgrad_launch_c(const WgradArgs& a, int grid, size_t lds, hipStream_t s) {
   static bool attr = false;
@@ -662,6 +722,17 @@ static int wgrad_dma2_launch(const WgradArgs& a, int grid, hipStream_t s, const 
   return check_launch(what);
 }
 
+static int wgrad_dma_launch(const WgradManyArgs& am, int grid, hipStream_t s, const char* what) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)wgrad_dma_kernel<7, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      return check_launch("wgrad_rows(dma): LDS attribute");
+    attr = true;
+  }
+  hipLaunchKernelGGL((wgrad_dma_kernel<7, 4>), dim3(grid), dim3(512), (size_t)WD_NSLOT * WD_SLOT, s, am);
+  return check_launch(what);
+}
+
 extern "C" int32_t trs_wgrad_rows_splits(int32_t M, int32_t N, int64_t rows) {
   const WgradPlan p = wgrad_plan(M, N, rows);
   return 8 * p.slots_per_xcd;
@@ -689,15 +760,11 @@ extern "C" int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t
     a.S = 8 * p.slots_per_xcd;
     return wgrad_dma2_launch(a, a.S * p.MB, s, "wgrad_rows(dma2)");
   }
-  if (p.dma == 1) {
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)wgrad_dma_kernel<7, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return check_launch("wgrad_rows(dma): LDS attribute");
-      attr = true;
-    }
-    hipLaunchKernelGGL((wgrad_dma_kernel<7, 4>), dim3(grid), dim3(512), (size_t)WD_NSLOT * WD_SLOT, s, a);
-    return check_launch("wgrad_rows(dma)");
+  if (p.dma == 1) {      // a job table of one: the same grid and the same map as ever
+    WgradManyArgs am{};
+    am.job[0] = WgradJob{a.g, a.x, part, ldg, ldx, M, N};
+    am.rows = rows, am.J = 1, am.MB = p.MB, am.NB = p.NB, am.slots_per_xcd = p.slots_per_xcd;
+    return wgrad_dma_launch(am, grid, s, "wgrad_rows(dma)");
   }
   if (p.wm == 2 && p.wn == 4)
     return p.nc == 4 ? wgrad_launch<2, 4, 7, 4>(a, grid, lds, s) : wgrad_launch<2, 4, 7, 3>(a, grid, lds, s);
@@ -707,6 +774,46 @@ extern "C" int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t
   if (p.mc == 1) return wgrad_launch<1, 4, 1, WG_TC>(a, grid, lds, s);
   if (p.mc == 4) return wgrad_launch<1, 4, 4, WG_TC>(a, grid, lds, s);
   return wgrad_launch<1, 4, WG_TC, WG_TC>(a, grid, lds, s);
+}
+
+// ---- several products over the same rows in one launch (wgrad_many_plan above)
+extern "C" int32_t trs_wgrad_rows_many_splits(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
+                                              const int32_t* ldx, int64_t rows) {
+  return wgrad_many_plan(n_jobs, M, N, ldg, ldx, rows).S;
+}
+
+// where workgroup ``block`` of the batched launch works: out = {job, row range, output block, first row, row behind the
+// last}; returns the grid (0: the batch is not taken, or no such block).  Host only -- what the tests walk.
+extern "C" int32_t trs_wgrad_rows_many_map(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
+                                           const int32_t* ldx, int64_t rows, int32_t block, int64_t* out) {
+  const ManyPlan mp = wgrad_many_plan(n_jobs, M, N, ldg, ldx, rows);
+  if (mp.S == 0 || !out || block < 0 || block >= mp.grid) return 0;
+  int job, slot, tile;
+  wdm_place(mp.MB * mp.NB, mp.slots_per_xcd, block, job, slot, tile);
+  const int64_t quads = rows / (4 * WG_KS);
+  out[0] = job, out[1] = slot, out[2] = tile;
+  out[3] = 4 * WG_KS * (quads * slot / mp.S), out[4] = 4 * WG_KS * (quads * (slot + 1) / mp.S);
+  return mp.grid;
+}
+
+extern "C" int trs_wgrad_rows_many(int32_t n_jobs, const void* const* g, const int32_t* ldg, const void* const* x,
+                                   const int32_t* ldx, int64_t rows, const int32_t* M, const int32_t* N, int32_t S,
+                                   float* const* part, trs_stream_t stream) {
+  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WG_MAXJ, TRS_EINVAL, "wgrad_rows_many: %d jobs (1 .. %d)", n_jobs, WG_MAXJ);
+  if (!g || !x || !part || !ldg || !ldx || !M || !N) return fail(TRS_EINVAL, "wgrad_rows_many: null pointer");
+  const ManyPlan mp = wgrad_many_plan(n_jobs, M, N, ldg, ldx, rows);
+  // S = what trs_wgrad_rows_many_splits returned
+  TRS_REQUIRE(mp.S > 0 && S == mp.S, TRS_ESHAPE, "wgrad_rows_many: %d jobs over %lld rows take %d row ranges each, caller passed %d",
+              n_jobs, (long long)rows, mp.S, S);
+  WgradManyArgs am{};
+  for (int k = 0; k < n_jobs; ++k) {      // every job before any launch
+    if (!g[k] || !x[k] || !part[k]) return fail(TRS_EINVAL, "wgrad_rows_many: null pointer (job %d)", k);
+    TRS_REQUIRE(aligned16(g[k]) && aligned16(x[k]) && aligned16(part[k]), TRS_ESHAPE,
+                "wgrad_rows_many: operands of job %d not 16-byte aligned", k);
+    am.job[k] = WgradJob{(const uint16_t*)g[k], (const uint16_t*)x[k], part[k], ldg[k], ldx[k], M[k], N[k]};
+  }
+  am.rows = rows, am.J = n_jobs, am.MB = mp.MB, am.NB = mp.NB, am.slots_per_xcd = mp.slots_per_xcd;
+  return wgrad_dma_launch(am, mp.grid, (hipStream_t)stream, "wgrad_rows_many");
 }
 
 // ---- a wide input against a two-block g (the 2496-wide first layer of the deep branch: dW^T = x^T g1, x (rows, 12 x 208)

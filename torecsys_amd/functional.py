@@ -2942,6 +2942,12 @@ class _FusedMLP(Function):
         gy2 = gy.reshape(rows, widths[L]).contiguous()
         gx, gz, gb, _ = fused_mlp_backward_raw(gy2, widths, Ws, masks, family=fam)
         grads = []
+        if all(pdt[2 * l] == pdt[2 * l + 1] for l in range(L)):
+            for gw, gbias in _tail_grads([(gy2 if l == L - 1 else gz[l], x2 if l == 0 else hidden[l - 1], widths[l + 1],
+                                           widths[l], pdt[2 * l], gb[l], ctx.needs_input_grad[1 + 2 * l],
+                                           ctx.needs_input_grad[2 + 2 * l]) for l in range(L)]):
+                grads += [gw, gbias]
+            return (gx.reshape(xshape) if ctx.needs_input_grad[0] else None, *grads)
         for l in range(L):
             inp = x2 if l == 0 else hidden[l - 1]               # (rows, widths[l] | pad32)
             g = gy2 if l == L - 1 else gz[l]                    # (rows, widths[l+1] | pad32)
@@ -2990,6 +2996,58 @@ def _tail_layer_grads(g, inp, out_f, in_f, dtype, gb_f32, need_w, need_b):
         return _wgrad_rows(g, inp, out_f, in_f, dtype, gb_f32)
     gw = _wgrad_rows(g, inp, out_f, in_f, dtype) if need_w else None
     return gw, (gb_f32[:out_f].to(dtype) if need_b else None)
+
+
+def _wgrad_many_splits(jobs) -> int:
+    """Row ranges per job when the products ``jobs`` = [(g, inp, M, N)] over the same rows go out as ONE launch of the
+    LDS-DMA kernel (trs_wgrad_rows_many_splits; 0: the caller keeps the per-layer calls)."""
+    if not WGRAD_ROWS or len(jobs) < 2:
+        return 0
+    for g, inp, _, _ in jobs:
+        if not (g.is_cuda and g.dtype == torch.bfloat16 and inp.dtype == torch.bfloat16 and g.is_contiguous()
+                and inp.is_contiguous() and g.shape[0] == jobs[0][0].shape[0]):
+            return 0
+    return size_query("trs_wgrad_rows_many_splits", len(jobs), _i32_array([j[2] for j in jobs]),
+                      _i32_array([j[3] for j in jobs]), _i32_array([j[0].shape[1] for j in jobs]),
+                      _i32_array([j[1].shape[1] for j in jobs]), int(jobs[0][0].shape[0]))
+
+
+def _tail_grads(layers):
+    """(dW, db) of every layer behind the fused kernels, ``layers`` = [(g, inp, out_f, in_f, dtype, gb_f32, need_w,
+    need_b)] in stack order with the output layer last.  The hidden layers whose weight gradient is needed go out as one
+    batched product and one batched finish where trs_wgrad_rows_many_splits takes them (two 400 x 400 layers from 8192
+    rows on); the output layer's few columns stay on their own kernel, and so does everything the query declines."""
+    out = [None] * len(layers)
+    batch = [k for k, t in enumerate(layers[:-1]) if t[6]]
+    jobs = [(layers[k][0], layers[k][1], min(layers[k][0].shape[1], (layers[k][2] + 7) // 8 * 8),
+             min(layers[k][1].shape[1], (layers[k][3] + 7) // 8 * 8)) for k in batch]
+    S = _wgrad_many_splits(jobs) if len({layers[k][4] for k in batch}) == 1 else 0
+    if S > 0:
+        dev, dtype, rows = jobs[0][0].device, layers[batch[0]][4], jobs[0][0].shape[0]
+        parts = [torch.empty(S, M, N, dtype=torch.float32, device=dev) for _, _, M, N in jobs]
+        call("trs_wgrad_rows_many", len(jobs), _ptr_array([j[0] for j in jobs]), _i32_array([j[0].shape[1] for j in jobs]),
+             _ptr_array([j[1] for j in jobs]), _i32_array([j[1].shape[1] for j in jobs]), rows,
+             _i32_array([j[2] for j in jobs]), _i32_array([j[3] for j in jobs]), S, _ptr_array(parts), stream_ptr())
+        gws, gbs, gbfs = [], [], []
+        for k in batch:
+            _, _, out_f, in_f, _, gb_f32, _, need_b = layers[k]
+            gws.append(torch.empty(out_f, in_f, dtype=dtype, device=dev))
+            ride = need_b and out_f <= (in_f + 255) // 256 * 256      # the bias cast rides in the finish (see _wgrad_rows)
+            gbs.append(torch.empty(out_f, dtype=dtype, device=dev) if ride else None)
+            gbfs.append(gb_f32 if ride else None)
+        call("trs_wgrad_finish_many", len(jobs), _ptr_array(parts), S, _i32_array([j[2] for j in jobs]),
+             _i32_array([j[3] for j in jobs]), _i32_array([layers[k][2] for k in batch]),
+             _i32_array([layers[k][3] for k in batch]), value_dtype_code(gws[0]), _ptr_array(gws), _ptr_array(gbfs),
+             _ptr_array(gbs), stream_ptr())
+        for n, k in enumerate(batch):
+            gb = gbs[n]
+            if gb is None and layers[k][7]:
+                gb = layers[k][5][:layers[k][2]].to(dtype)
+            out[k] = (gws[n], gb)
+    for k, t in enumerate(layers):
+        if out[k] is None:
+            out[k] = _tail_layer_grads(*t)
+    return out
 
 
 WGRAD_ROWS = os.environ.get("TRS_WGRAD_ROWS", "1") not in ("", "0")

@@ -902,12 +902,9 @@ class _HybridMLP(torch.autograd.Function):
         gy2 = F_.pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
         g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam)
         grads = []
-        for l in range(L):
-            inp = h1 if l == 0 else hidden[l - 1]
-            g = gy2 if l == L - 1 else gz[l]
-            out_f, in_f = wshapes[l]
-            grads += [*F_._tail_layer_grads(g, inp, out_f, in_f, wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]),
-                      None, None]
+        for gw, gbias in F_._tail_grads([(gy2 if l == L - 1 else gz[l], h1 if l == 0 else hidden[l - 1], *wshapes[l],
+                                          wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]) for l in range(L)]):
+            grads += [gw, gbias, None, None]
         gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3])
         return (gx.reshape(xshape) if needs[0] else None, None, gw1, gbias1, None, None, *grads)
 
