@@ -933,6 +933,65 @@ int trs_bce_logits_fwd(const void* logits, int32_t dtype, const void* labels, in
 int trs_bce_logits_bwd(const void* logits, int32_t dtype, const void* labels, int32_t label_dtype, const float* gout,
                        int64_t B, void* glogits, trs_stream_t stream);
 
+/* ---- pair scores of the embedding models (csrc/rank.hip) ----------------------------------------------------------
+ * models/emb/matrix_factorization.py:21-36 + layers/emb/generalized_matrix_factorization.py:44-57 (inner product) and
+ * models/emb/starspace.py:38-124 + layers/emb/starspace.py:62-90 (any similarity; here inner product and cosine) behind the
+ * negative sampler miners/uniform_batch_miner.py:17-44, which repeats the anchor id K times and lets the input layer
+ * gather a (B (1+K), 2, E) block.  Here:
+ *   scores[b, j] = sim(A[a_idx[b] + a_offset], T[t_idx[b, j] + t_offset]),  j = 0 .. K  (column 0: the positive)
+ * a_table (Va, E) and t_table (Vt, E) of one value dtype (the two pointers may be equal), a_idx (B) and t_idx (B, 1+K) of
+ * one index dtype, the offsets plain row numbers added to every id of their side.  sim: 0 = inner product, 1 = cosine as
+ * ATen's cosine_similarity, dot / (max(|a|, eps) max(|t|, eps)) with eps = 1e-8.  scores (B, 1+K) of out_dtype: the
+ * table's or TRS_F32; fp32 accumulation, one rounding on store.  The anchor row is read once per sample; no (B (1+K), 2, E)
+ * and no (B, 1+K, E) block exists.  An id outside its table reads as a zero row and raises *err_flag.
+ * Backward from g_scores (B, 1+K) of g_dtype (the table's or TRS_F32): the rows are gathered again, norms and cosines
+ * recomputed, and the gradient ROWS written to g_block (B, 2+K, E) of the table's dtype, ordered [anchor, positive,
+ * negatives]:  g_block[b, 0] = sum_j g_bj dsim/da (j in order),  g_block[b, 1+j] = g_bj dsim/dt;  the row of an id outside
+ * its table is zeros.  No atomics: reproducible bits.  The TABLE gradient is trs_csr_build* + trs_scatter_rows* over the
+ * (B, 2+K) id matrix (one walk for a shared table, two walks over the column ranges 0 and 1 .. 1+K for two tables).
+ * trs_pair_score_path (pure): 1 = lane-group kernels (rows of 1, 2, 4 .. 64 whole 16-byte vectors; one group per sample,
+ * 16-byte loads, shuffles), 0 = one thread per (b, j) (any other E; the forward also when a table pointer is not 16-byte
+ * aligned), -1 = bad E / dtype.  The backward of path 0 needs trs_pair_score_bwd_workspace_bytes (0 for path 1), and
+ * path 1 needs 16-byte aligned tables and g_block (TRS_EALIGN).
+ * K >= 0; B == 0 returns TRS_OK and touches nothing.  Errors, all before any launch: NULL pointer, bad sim, bad index dtype,
+ * bad size TRS_EINVAL; value / out / gradient dtype TRS_EDTYPE; workspace TRS_EWORKSPACE.                             */
+int trs_pair_score_path(int32_t E, int32_t dtype);
+int trs_embed_pair_score_fwd(const void* a_table, int64_t Va, const void* a_idx, int64_t a_offset, const void* t_table,
+                             int64_t Vt, const void* t_idx, int64_t t_offset, int32_t E, int32_t dtype, int32_t idx_dtype,
+                             int64_t B, int32_t K, int32_t sim, void* scores, int32_t out_dtype, int32_t* err_flag,
+                             trs_stream_t stream);
+size_t trs_pair_score_bwd_workspace_bytes(int64_t B, int32_t K, int32_t E, int32_t dtype);
+int trs_embed_pair_score_bwd(const void* a_table, int64_t Va, const void* a_idx, int64_t a_offset, const void* t_table,
+                             int64_t Vt, const void* t_idx, int64_t t_offset, int32_t E, int32_t dtype, int32_t idx_dtype,
+                             int64_t B, int32_t K, int32_t sim, const void* g_scores, int32_t g_dtype, void* g_block,
+                             void* workspace, size_t ws_bytes, trs_stream_t stream);
+
+/* ---- ranking losses over (positive, negatives) scores (csrc/rank.hip; losses/ltr/functional.py) ---------------------
+ * pos: one value per sample at pos[b * pos_stride]; neg: K values per sample at neg[b * neg_stride + k] (columns 0 and
+ * 1 .. K of one (B, 1+K) score matrix: pos = S, neg = S + 1, both strides 1 + K); dtype TRS_F32 | TRS_BF16; mask (B) one
+ * byte per sample (torch.bool), 0 = the sample is dropped, or NULL.  Terms, per kept sample b and negative k:
+ *   kind 0  (1 - sigmoid(p)) + sigmoid(n)      pointwise_logistic_ranking_loss
+ *   kind 1  softplus(-(p - n))                 bayesian_personalized_ranking_loss (= -log sigmoid(p - n), finite for every
+ *                                              argument); TripletLoss(margin = 0) -> nn.SoftMarginLoss
+ *   kind 2  max(0, margin - p + n)             hinge_loss; TripletLoss(margin) -> nn.MarginRankingLoss
+ *   kind 3  max(0, margin - p + max_k n)       ONE term per sample: adaptive_hinge_loss as documented
+ * *loss (fp32, device) = the sum of the terms divided by: reduction 0 nothing (sum), 1 the number of kept terms (mean),
+ * 2 the number of kept SAMPLES (the reference's apply_mask rule: loss[mask].sum() / mask.sum()).  No kept sample under
+ * reduction 1 / 2 gives NaN (0 / 0), as the reference's.  *denom (fp32, device, may be NULL) receives the divisor.
+ * Two launches: per-workgroup partial sums in a fixed order, then one wave (reproducible bits).
+ * bwd: g_pos[b * g_pos_stride] = sum_k dterm/dp, g_neg[b * g_neg_stride + k] = dterm/dn, times gout[0] (fp32 device
+ * scalar, NULL = 1) over the divisor (denom: the forward's, required for a masked mean; NULL = computed from B and K);
+ * zeros for a dropped sample.  kind 3: the first of equal maximal negatives takes the gradient.  K >= 1.  B == 0 returns
+ * TRS_OK.  Errors before any launch: dtype TRS_EDTYPE; kind, reduction, sizes, strides, NULL TRS_EINVAL.            */
+size_t trs_rank_loss_workspace_bytes(int64_t B);
+int trs_rank_loss_fwd(const void* pos, int64_t pos_stride, const void* neg, int64_t neg_stride, int32_t dtype,
+                      const void* mask, int64_t B, int32_t K, int32_t kind, float margin, int32_t reduction, float* loss,
+                      float* denom, void* workspace, size_t ws_bytes, trs_stream_t stream);
+int trs_rank_loss_bwd(const void* pos, int64_t pos_stride, const void* neg, int64_t neg_stride, int32_t dtype,
+                      const void* mask, int64_t B, int32_t K, int32_t kind, float margin, int32_t reduction,
+                      const float* gout, const float* denom, void* g_pos, int64_t g_pos_stride, void* g_neg,
+                      int64_t g_neg_stride, trs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

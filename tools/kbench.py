@@ -15,7 +15,10 @@ path against the same module with the switch off, the two kernels alone, the noi
 inputs, see bench_routing).
 --what seq [--L 50] [--cell lstm|gru|rnn]: SequenceIndicesEmbedding(output_method='avg_pooling') over ordered lists of L ids
 with lengths uniform in [1, L], the fused path against the same module with the switch off, and the two kernels alone (own
-inputs, see bench_seq)."""
+inputs, see bench_seq).
+--what rank [--neg 10] [--sim dot|cosine]: pair scores + ranking loss of the embedding models, the fused path against the
+same module with the switch off and against the reference-shaped composition, and the four kernels alone (own inputs, see
+bench_rank)."""
 import argparse
 import os
 import sys
@@ -696,6 +699,105 @@ def bench_seq(a):
               f"{fl / med / 1e12:6.1f} TFLOP/s", flush=True)
 
 
+def bench_rank(a):
+    """Pair scores + ranking loss (csrc/rank.hip) at (B, K, E, V): one shared table, Zipf(1.05) anchor and target ids,
+    hinge loss (mean).  Forward + backward of (1) fused.EmbeddingPairScorer + losses.HingeLoss, (2) the same module with
+    the switch off (functional.PAIR_SCORE = False: HIP gathers + ATen multiply / cosine, the HIP loss), (3) the
+    reference-shaped composition -- the miner's (B (1+K), 2) id pairs, an aten::embedding gather of the (B (1+K), 2, E)
+    block, the GMF / cosine on its halves, the hinge as ATen elementwise ops and the dense index_add gradient -- taking
+    turns inside every round; then the score and loss kernels alone.  Every figure is the median of ``--rounds``
+    per-round medians with their min..max."""
+    import torch.nn.functional as TF
+    from torecsys_amd.fused import EmbeddingPairScorer
+    from torecsys_amd.losses import HingeLoss
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, K, E, V, sim = a.B, a.neg, a.E, a.V, a.sim
+    g = torch.Generator(device=dev).manual_seed(1234)
+    cdf = torch.arange(1, V + 1, device=dev, dtype=torch.float64).pow(-1.05).cumsum(0)
+    cdf /= cdf[-1].clone()
+
+    def zipf(*shape):
+        return torch.searchsorted(cdf, torch.rand(*shape, generator=g, device=dev, dtype=torch.float64)).clamp_(max=V - 1)
+
+    a_idx, t_idx = zipf(B), zipf(B, 1 + K)
+    m = EmbeddingPairScorer(E, V, None, sim).to(dev).to(dt)
+    w = m.anchor.weight
+    loss_fn = HingeLoss(margin=1.0, reduction="mean")
+    alg = B * (2 + K) * (8 + E * s) + B * (1 + K) * s
+    print(f"pair scores + ranking loss B={B} K={K} E={E} V={V} {sim} {a.dtype} path {F_.pair_score_path(E, dt)}, "
+          f"{a.rounds} rounds x {a.iters} launches; forward: {alg / 1e6:.0f} MB (alg), reference block "
+          f"{B * (1 + K) * 2 * E * s / 1e6:.0f} MB", flush=True)
+
+    def module(fused):
+        def f():
+            F_.PAIR_SCORE = fused
+            return loss_fn(m(a_idx, t_idx), None)
+        return f
+
+    pair_ids = torch.stack([a_idx.repeat_interleave(1 + K), t_idx.reshape(-1)], dim=1)      # what the miner hands over
+
+    def reference_shaped():
+        block = TF.embedding(pair_ids, w)                                                    # (B (1+K), 2, E)
+        if sim == "dot":
+            sc = (block[:, 0, :] * block[:, 1, :]).sum(dim=1)
+        else:
+            sc = TF.cosine_similarity(block[:, 0:1, :], block[:, 1:2, :], dim=2)
+        sc = sc.view(B, 1 + K).float()
+        return torch.clamp(1.0 - sc[:, :1] + sc[:, 1:], min=0.0).mean()
+
+    def fwd_bwd(f):
+        def run():
+            F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+            w.grad = None
+            f().backward()
+        return run
+
+    cands = [("pair_scores (HIP)", module(True)), ("switch off (gather+ATen)", module(False)),
+             ("reference-shaped (ATen)", reference_shaped)]
+    for name, f in cands:
+        fwd_bwd(f)()
+    torch.cuda.synchronize()
+    res = {}
+    for what in ("fwd", "fwd+bwd"):
+        per = {name: [] for name, _ in cands}
+        for _ in range(a.rounds):
+            for name, f in cands:
+                if what == "fwd":
+                    with torch.no_grad():
+                        per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                else:
+                    per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+        for name, ts in per.items():
+            ts = sorted(ts)
+            res[(what, name)] = ts[len(ts) // 2]
+            print(f"{what:8s} {name:26s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                  f"{ts[-1] * 1e6:9.1f} us", flush=True)
+        for name in ("switch off (gather+ATen)", "reference-shaped (ATen)"):
+            print(f"{what:8s} {name} / pair_scores = {res[(what, name)] / res[(what, 'pair_scores (HIP)')]:.2f}x", flush=True)
+    F_.PAIR_SCORE = True
+    w.grad = None
+    # the kernels alone
+    wd = w.detach()
+    scores = F_.pair_scores_forward_raw(wd, a_idx, wd, t_idx, sim=sim)
+    gs = torch.randn(B, 1 + K, generator=g, device=dev, dtype=dt)
+    _, denom = F_.rank_loss_forward_raw(scores, None, "hinge", 1.0, None, "mean")
+    kernels = [("trs_embed_pair_score_fwd", lambda: F_.pair_scores_forward_raw(wd, a_idx, wd, t_idx, sim=sim), alg),
+               ("trs_embed_pair_score_bwd", lambda: F_.pair_scores_backward_raw(wd, a_idx, wd, t_idx, gs, sim=sim),
+                B * (2 + K) * (8 + 2 * E * s) + B * (1 + K) * s),
+               ("trs_rank_loss_fwd", lambda: F_.rank_loss_forward_raw(scores, None, "hinge", 1.0, None, "mean"),
+                B * (1 + K) * s),
+               ("trs_rank_loss_bwd", lambda: F_.rank_loss_backward_raw(scores, None, "hinge", 1.0, None, "mean", None, denom),
+                2 * B * (1 + K) * s)]
+    for name, f, nbytes in kernels:
+        ts = sorted(timeit(f, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+        med = ts[len(ts) // 2]
+        print(f"kernel   {name:26s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
+              f"{nbytes / med / 1e9:7.0f} GB/s = {nbytes / med / 8e12 * 100:5.1f}% of 8 TB/s on {nbytes / 1e6:.0f} MB (alg)",
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -715,7 +817,11 @@ def main():
     ap.add_argument("--caps", type=int, default=8, help="routing: max_num_caps")
     ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
     ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"], help="seq: the recurrent cell")
+    ap.add_argument("--neg", type=int, default=10, help="rank: sampled negatives per sample")
+    ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
     a = ap.parse_args()
+    if a.what == "rank":         # own inputs and modules: not part of "all"
+        return bench_rank(a)
     if a.what == "seq":          # own inputs and module: not part of "all"
         return bench_seq(a)
     if a.what == "routing":      # own inputs and module: not part of "all"

@@ -168,6 +168,16 @@ SIGNATURES = {
     "trs_bce_logits_workspace_bytes": (_SZ, [_I64]),
     "trs_bce_logits_fwd": (c_int32, [_P, _I32, _P, _I32, _I64, _P, _P, _SZ, _P]),
     "trs_bce_logits_bwd": (c_int32, [_P, _I32, _P, _I32, _P, _I64, _P, _P]),
+    "trs_pair_score_path": (c_int32, [_I32, _I32]),
+    "trs_embed_pair_score_fwd": (c_int32, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P,
+                                           _I32, _P, _P]),
+    "trs_pair_score_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "trs_embed_pair_score_bwd": (c_int32, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P,
+                                           _I32, _P, _P, _SZ, _P]),
+    "trs_rank_loss_workspace_bytes": (_SZ, [_I64]),
+    "trs_rank_loss_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _SZ, _P]),
+    "trs_rank_loss_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _I64, _P, _I64,
+                                    _P]),
     "trs_bucket_workspace_bytes": (_SZ, [_I64, _I32]),
     "trs_bucket_by_owner": (c_int32, [_P, _I32, _P, _I64, _I32, _I64, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "trs_embed_fm_sharded": (c_int32, [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _I32, _I32, _I64, _I32, _P, _P, _P, _P,

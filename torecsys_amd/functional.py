@@ -412,16 +412,16 @@ def _sink_args(opt, table: torch.Tensor, key):
 
 def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
                         g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
-                        padding_row: int = -1, key=None) -> None:
+                        padding_row: int = -1, key=None, g_rows_batch_stride: int = 0) -> None:
     """Fused sparse optimizer step: the bucketed gradient of every looked-up row is applied to ``table`` in
     place (see trs_scatter_rows_update); no gradient tensor is produced.  A ``capturable`` optimizer's step size is read
-    from device memory (eagerly and under capture alike)."""
+    from device memory (eagerly and under capture alike).  ``g_rows_batch_stride`` as in ``scatter_rows``."""
     V, E = table.shape
     if not table.is_contiguous():
         raise ValueError("fused optimizer needs a contiguous table")
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, rb.N, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
-    call("trs_scatter_rows_update", ptr(g_rows), 0, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
+    call("trs_scatter_rows_update", ptr(g_rows), g_rows_batch_stride, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
          ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
          *_sink_args(opt, table, key), ptr(ws), ws_bytes, stream_ptr())
 
@@ -3208,3 +3208,355 @@ def bce_with_logits(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     elements): an fp32 scalar.  ``F.binary_cross_entropy_with_logits(logits.float(), labels)`` in three launches
     (forward 2, backward 1) instead of ATen's cast + log-sigmoid chain + mean and their backwards."""
     return _BCEWithLogits.apply(logits, labels)
+
+
+# --------------------------------------------------------------------------------------------
+# Pair scores of the embedding models (MF / StarSpace) and the ranking losses over them (csrc/rank.hip)
+# --------------------------------------------------------------------------------------------
+PAIR_SIMS = {"dot": 0, "cosine": 1}
+RANK_KINDS = {"pointwise": 0, "bpr": 1, "hinge": 2, "adaptive_hinge": 3}
+RANK_REDUCTIONS = {"sum": 0, "mean": 1, "sample": 2}
+# TRS_PAIR_SCORE=0: pair_scores keeps the composition (gather_rows + ATen multiply / cosine_similarity), for A/B runs
+PAIR_SCORE = os.environ.get("TRS_PAIR_SCORE", "1") not in ("", "0")
+
+
+def pair_score_path(E: int, dtype: torch.dtype) -> int:
+    """1: the lane-group kernels (rows of 1, 2, 4 .. 64 whole 16-byte vectors), 0: one thread per (b, j) (any other E),
+    -1: a dtype or E the kernels do not take.  trs_pair_score_path; a pure function, callable without a device."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return -1
+    return size_query("trs_pair_score_path", int(E), _abi.TRS_F32 if dtype == torch.float32 else _abi.TRS_BF16)
+
+
+def _sim_code(sim) -> int:
+    if isinstance(sim, str):
+        if sim not in PAIR_SIMS:
+            raise ValueError(f"pair_scores: sim must be one of {sorted(PAIR_SIMS)}, got {sim!r}")
+        return PAIR_SIMS[sim]
+    if sim not in (0, 1):
+        raise ValueError(f"pair_scores: bad sim code {sim!r}")
+    return int(sim)
+
+
+def _pair_operands(aw, a_idx, tw, t_idx, **more):
+    named = dict(anchor_weight=aw, anchor_idx=a_idx, target_weight=tw, target_idx=t_idx, **more)
+    for name, t in named.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"pair_scores: {name} must be contiguous, got strides {tuple(t.stride())}")
+    require_device(*named.values())
+    if aw.dim() != 2 or tw.dim() != 2 or aw.shape[1] != tw.shape[1] or aw.dtype != tw.dtype:
+        raise ValueError(f"pair_scores: two (V, E) tables of one dtype and width expected, got {tuple(aw.shape)} {aw.dtype} "
+                         f"and {tuple(tw.shape)} {tw.dtype}")
+    if a_idx.dim() != 1 or t_idx.dim() != 2 or t_idx.shape[0] != a_idx.shape[0] or t_idx.shape[1] < 1:
+        raise ValueError(f"pair_scores: anchor ids (B,) and target ids (B, 1 + K) expected, got {tuple(a_idx.shape)} and "
+                         f"{tuple(t_idx.shape)}")
+    if a_idx.dtype != t_idx.dtype:
+        raise TypeError(f"pair_scores: one index dtype expected, got {a_idx.dtype} and {t_idx.dtype}")
+    return aw.shape[0], tw.shape[0], aw.shape[1], a_idx.shape[0], t_idx.shape[1] - 1, value_dtype_code(aw)
+
+
+def pair_scores_forward_raw(anchor_weight: torch.Tensor, anchor_idx: torch.Tensor, target_weight: torch.Tensor,
+                            target_idx: torch.Tensor, anchor_offset: int = 0, target_offset: int = 0, sim=0,
+                            out_dtype: Optional[torch.dtype] = None, flag: Optional[_ErrFlag] = None) -> torch.Tensor:
+    """trs_embed_pair_score_fwd as it is (no autograd): (B, 1 + K) scores of ``out_dtype`` (the tables' or fp32)."""
+    Va, Vt, E, B, K, code = _pair_operands(anchor_weight, anchor_idx, target_weight, target_idx)
+    out_dtype = out_dtype or anchor_weight.dtype
+    if out_dtype not in (anchor_weight.dtype, torch.float32):
+        raise TypeError(f"pair_scores: out_dtype must be the tables' dtype or float32, got {out_dtype}")
+    out = torch.empty(B, 1 + K, dtype=out_dtype, device=anchor_weight.device)
+    call("trs_embed_pair_score_fwd", ptr(anchor_weight), Va, ptr(anchor_idx), int(anchor_offset), ptr(target_weight), Vt,
+         ptr(target_idx), int(target_offset), E, code, index_dtype_code(anchor_idx), B, K, _sim_code(sim), ptr(out),
+         value_dtype_code(out), ptr(flag.t if flag is not None else None), stream_ptr())
+    return out
+
+
+def pair_scores_backward_raw(anchor_weight: torch.Tensor, anchor_idx: torch.Tensor, target_weight: torch.Tensor,
+                             target_idx: torch.Tensor, g_scores: torch.Tensor, anchor_offset: int = 0,
+                             target_offset: int = 0, sim=0) -> torch.Tensor:
+    """trs_embed_pair_score_bwd as it is: the gradient rows (B, 2 + K, E) of the tables' dtype, ordered [anchor,
+    positive, negatives], from ``g_scores`` (B, 1 + K) of the tables' dtype or fp32."""
+    Va, Vt, E, B, K, code = _pair_operands(anchor_weight, anchor_idx, target_weight, target_idx, g_scores=g_scores)
+    if tuple(g_scores.shape) != (B, 1 + K) or g_scores.dtype not in (anchor_weight.dtype, torch.float32):
+        raise ValueError(f"pair_scores: g_scores ({B}, {1 + K}) of {anchor_weight.dtype} or float32 expected, got "
+                         f"{tuple(g_scores.shape)} {g_scores.dtype}")
+    dev = anchor_weight.device
+    block = torch.empty(B, 2 + K, E, dtype=anchor_weight.dtype, device=dev)
+    ws_bytes = size_query("trs_pair_score_bwd_workspace_bytes", B, K, E, code)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    call("trs_embed_pair_score_bwd", ptr(anchor_weight), Va, ptr(anchor_idx), int(anchor_offset), ptr(target_weight), Vt,
+         ptr(target_idx), int(target_offset), E, code, index_dtype_code(anchor_idx), B, K, _sim_code(sim), ptr(g_scores),
+         value_dtype_code(g_scores), ptr(block), ptr(ws), ws_bytes, stream_ptr())
+    return block
+
+
+_pair_offsets = {}        # (device, anchor offset, target offset, columns) -> the per-column offsets of the id matrix
+
+
+def _pair_offset_columns(dev, a_off: int, t_off: int, na: int, nt: int) -> Optional[torch.Tensor]:
+    if a_off == 0 and t_off == 0:
+        return None
+    key = (dev, a_off, t_off, na, nt)
+    t = _pair_offsets.get(key)
+    if t is None:
+        t = _pair_offsets[key] = torch.tensor([a_off] * na + [t_off] * nt, dtype=torch.int64, device=dev)
+    return t
+
+
+class _PairScores(Function):
+    """ids -> (B, 1 + K) scores in one kernel; nothing but the ids is saved.  The backward writes the gradient rows
+    (B, 2 + K, E) and walks the row buckets of the (B, 2 + K) id matrix: ONE walk for a shared table (one gradient, or one
+    fused optimizer step), two walks over its two column ranges for two tables."""
+
+    @staticmethod
+    def forward(ctx, aw, a_idx, tw, t_idx, a_off, t_off, sim, out_dtype, opt, track):
+        shared = tw is None
+        wa = aw.contiguous()
+        wt = wa if shared else tw.contiguous()
+        flag = _ErrFlag(wa.device)
+        out = pair_scores_forward_raw(wa, a_idx, wt, t_idx, a_off, t_off, sim, out_dtype, flag)
+        flag.check("pair_scores")
+        ctx.args = (a_off, t_off, sim, opt, shared)
+        K1 = t_idx.shape[1]
+        dev = wa.device
+        # ``track``: the caller's grad mode (needs_input_grad says True under torch.no_grad() too, and the forward itself
+        # always runs with grad mode off): no backward, no id matrix, no buckets
+        need = track and (ctx.needs_input_grad[0] or (not shared and ctx.needs_input_grad[2]))
+        ids = ()
+        if need and a_idx.shape[0] > 0:
+            prefetch = not torch.cuda.is_current_stream_capturing()      # a capture stays one chain on one stream
+            if shared:
+                ids = (torch.cat([a_idx.unsqueeze(1), t_idx], dim=1),)
+                if prefetch:
+                    prefetch_row_buckets(ids[0], _pair_offset_columns(dev, a_off, t_off, 1, K1), wa.shape[0])
+            else:
+                ids = (a_idx.unsqueeze(1),)
+                if prefetch and ctx.needs_input_grad[0]:
+                    prefetch_row_buckets(ids[0], _pair_offset_columns(dev, a_off, 0, 1, 0), wa.shape[0])
+                if prefetch and ctx.needs_input_grad[2]:
+                    prefetch_row_buckets(t_idx, _pair_offset_columns(dev, 0, t_off, 0, K1), wt.shape[0])
+        ctx.save_for_backward(aw, a_idx, tw, t_idx, *ids)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        aw, a_idx, tw, t_idx = ctx.saved_tensors[:4]
+        a_off, t_off, sim, opt, shared = ctx.args
+        need_a, need_t = ctx.needs_input_grad[0], (not shared and ctx.needs_input_grad[2])
+        tail = (None,) * 6
+        if not (need_a or need_t):
+            return (None, None, None, None, *tail)
+        if a_idx.shape[0] == 0:      # no sample: zero gradients
+            za = torch.zeros_like(aw) if need_a and opt is None else None
+            zt = torch.zeros_like(tw) if need_t and opt is None else None
+            return (za, None, zt, None, *tail)
+        _adopt_grads(g)
+        ids = ctx.saved_tensors[4]
+        wa = aw.contiguous()
+        wt = wa if shared else tw.contiguous()
+        K1 = t_idx.shape[1]
+        dev = wa.device
+        block = pair_scores_backward_raw(wa, a_idx, wt, t_idx, g.contiguous(), a_off, t_off, sim)
+        if shared:
+            rb = row_buckets(ids, _pair_offset_columns(dev, a_off, t_off, 1, K1), wa.shape[0])
+            return (_apply_or_grad(rb, aw, opt, g_rows=block), None, None, None, *tail)
+        g_a = g_t = None
+        if need_a:
+            rb = row_buckets(ids, _pair_offset_columns(dev, a_off, 0, 1, 0), wa.shape[0])
+            g_a = _apply_or_grad(rb, aw, opt, g_rows=block, g_rows_batch_stride=K1 + 1)
+        if need_t:
+            rb = row_buckets(t_idx, _pair_offset_columns(dev, 0, t_off, 0, K1), wt.shape[0])
+            g_t = _apply_or_grad(rb, tw, opt, g_rows=block[:, 1:], g_rows_batch_stride=K1 + 1)
+        return (g_a, None, g_t, None, *tail)
+
+
+def _pair_scores_composition(aw, a_idx, tw, t_idx, a_off, t_off, sim, out_dtype, opt):
+    """gather_rows + ATen: the A/B baseline of pair_scores (TRS_PAIR_SCORE=0); forms the (B, 1 + K, E) block"""
+    dev = aw.device
+    a = gather_rows(aw, a_idx.unsqueeze(1), _pair_offset_columns(dev, a_off, 0, 1, 0), opt=opt)              # (B, 1, E)
+    t = gather_rows(aw if tw is None else tw, t_idx, _pair_offset_columns(dev, 0, t_off, 0, t_idx.shape[1]), opt=opt)
+    if out_dtype is not None and out_dtype != a.dtype:
+        a, t = a.to(out_dtype), t.to(out_dtype)
+    if sim == 0:
+        return (a * t).sum(dim=2)
+    return torch.nn.functional.cosine_similarity(a, t, dim=2)
+
+
+def pair_scores(anchor_weight: torch.Tensor, anchor_idx: torch.Tensor, target_weight: Optional[torch.Tensor],
+                target_idx: torch.Tensor, anchor_offset: Optional[int] = None, target_offset: Optional[int] = None,
+                sim="dot", out_dtype: Optional[torch.dtype] = None, opt=None) -> torch.Tensor:
+    """scores[b, j] = sim(anchor_weight[anchor_idx[b] + anchor_offset], target_weight[target_idx[b, j] + target_offset]):
+    (B,) anchor ids and (B, 1 + K) target ids (column 0 the positive, the others sampled negatives; K >= 0) -> (B, 1 + K)
+    in one HIP pass per direction (csrc/rank.hip).  ``sim``: 'dot' | 'cosine' (ATen's cosine_similarity, eps 1e-8).
+    ``target_weight`` None or ``anchor_weight`` itself: ONE shared table, which then gets one gradient from one bucket walk
+    (or one fused step with ``opt``).  ``out_dtype``: the tables' dtype (default) or float32.  The anchor row is read once
+    per sample, no (B, 1 + K, E) block is formed, nothing but the ids is kept for the backward.  An id outside its table
+    scores as a zero row, receives no gradient and raises the index flag."""
+    sim = _sim_code(sim)
+    a_idx, t_idx = _as_index(anchor_idx), _as_index(target_idx)
+    if a_idx.dim() == 2 and a_idx.shape[1] == 1:
+        a_idx = a_idx.reshape(-1)
+    if t_idx.dim() == 1:
+        t_idx = t_idx.unsqueeze(1)
+    if a_idx.dtype != t_idx.dtype:
+        a_idx, t_idx = a_idx.long(), t_idx.long()
+    tw = None if target_weight is None or target_weight is anchor_weight else target_weight
+    a_off, t_off = int(anchor_offset or 0), int(target_offset or 0)
+    _pair_operands(anchor_weight.contiguous(), a_idx, (anchor_weight if tw is None else tw).contiguous(), t_idx)
+    if pair_score_path(anchor_weight.shape[1], anchor_weight.dtype) < 0:
+        raise TypeError(f"pair_scores: unsupported table dtype {anchor_weight.dtype}")
+    if not PAIR_SCORE:
+        return _pair_scores_composition(anchor_weight, a_idx, tw, t_idx, a_off, t_off, sim, out_dtype, opt)
+    return _PairScores.apply(anchor_weight, a_idx, tw, t_idx, a_off, t_off, sim, out_dtype, opt, torch.is_grad_enabled())
+
+
+_row_ids = {}       # (device, B) -> (2 b, 2 b + 1): the rows of a (B, 2, E) block seen as a (2 B, E) table
+
+
+class _BlockPairScore(Function):
+    """sim of the two rows of every sample of a (B, 2, E) block already in memory (the layers' input): the pair-score
+    kernels over the block as a (2 B, E) table with ids (2 b, 2 b + 1); the (B, 2, E) gradient rows ARE the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, sim):
+        B = x.shape[0]
+        key = (x.device, B)
+        ids = _row_ids.get(key)
+        if ids is None:
+            if len(_row_ids) > 16:
+                _row_ids.clear()
+            even = torch.arange(0, 2 * B, 2, dtype=torch.int32, device=x.device)
+            ids = _row_ids[key] = (even, (even + 1).unsqueeze(1).contiguous())
+        xc = x.contiguous()
+        ctx.save_for_backward(xc, *ids)
+        ctx.sim = sim
+        rows = xc.view(2 * B, xc.shape[2])
+        return pair_scores_forward_raw(rows, ids[0], rows, ids[1], 0, 0, sim)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        xc, a_idx, t_idx = ctx.saved_tensors
+        rows = xc.view(-1, xc.shape[2])
+        return pair_scores_backward_raw(rows, a_idx, rows, t_idx, g.contiguous(), 0, 0, ctx.sim), None
+
+
+def block_pair_score(x: torch.Tensor, sim="dot") -> torch.Tensor:
+    """(B, 2, E) -> (B, 1): sim(x[:, 0], x[:, 1]) in one kernel per direction (GeneralizedMatrixFactorizationLayer,
+    StarSpaceLayer); 'dot' | 'cosine'."""
+    x = x.rename(None) if x.has_names() else x
+    if x.dim() != 3 or x.shape[1] != 2:
+        raise ValueError(f"block_pair_score: (B, 2, E) expected, got {tuple(x.shape)}")
+    require_device(x)
+    if pair_score_path(x.shape[2], x.dtype) < 0:
+        raise TypeError(f"block_pair_score: unsupported dtype {x.dtype}")
+    return _BlockPairScore.apply(x, _sim_code(sim))
+
+
+def _rank_kind_code(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in RANK_KINDS:
+            raise ValueError(f"rank_loss: kind must be one of {sorted(RANK_KINDS)}, got {kind!r}")
+        return RANK_KINDS[kind]
+    if kind not in (0, 1, 2, 3):
+        raise ValueError(f"rank_loss: bad kind code {kind!r}")
+    return int(kind)
+
+
+def rank_reduction_code(reduction) -> int:
+    """'sum' | torch.sum -> 0, 'mean' | torch.mean -> 1, 'sample' -> 2 (the sum over the kept samples' terms divided by the
+    number of kept samples: the reference's apply_mask rule); anything else raises.  Callable without a device."""
+    if isinstance(reduction, int) and not isinstance(reduction, bool) and reduction in (0, 1, 2):
+        return reduction
+    if reduction is torch.sum:
+        return 0
+    if reduction is torch.mean:
+        return 1
+    if isinstance(reduction, str) and reduction in RANK_REDUCTIONS:
+        return RANK_REDUCTIONS[reduction]
+    raise ValueError(f"rank_loss: reduction must be 'sum', 'mean', 'sample', torch.sum or torch.mean, got {reduction!r}")
+
+
+def _rank_views(pos, neg):
+    """(pos, pos row stride, neg, neg row stride, B, K) of a (B, 1 + K) score matrix (``neg`` None) or a (B[, 1]) /
+    (B, K) pair"""
+    if neg is None:
+        if pos.dim() != 2 or pos.shape[1] < 2:
+            raise ValueError(f"rank_loss: a (B, 1 + K) score matrix with K >= 1 expected, got {tuple(pos.shape)}")
+        s = pos.contiguous()
+        return s, s.shape[1], s[:, 1:], s.shape[1], s.shape[0], s.shape[1] - 1
+    p = pos.reshape(-1).contiguous()
+    if neg.dim() != 2 or neg.shape[0] != p.shape[0] or neg.shape[1] < 1 or neg.dtype != p.dtype:
+        raise ValueError(f"rank_loss: pos (B,) | (B, 1) and neg (B, K >= 1) of one dtype expected, got {tuple(pos.shape)} "
+                         f"{pos.dtype} and {tuple(neg.shape)} {neg.dtype}")
+    n = neg.contiguous()
+    return p, 1, n, n.shape[1], n.shape[0], n.shape[1]
+
+
+def rank_loss_forward_raw(pos: torch.Tensor, neg: Optional[torch.Tensor], kind, margin: float = 1.0,
+                          mask: Optional[torch.Tensor] = None, reduction="sum"):
+    """trs_rank_loss_fwd as it is (no autograd): ``(loss, denom)``, two fp32 device scalars."""
+    require_device(pos, neg, mask)
+    p, ps, n, ns, B, K = _rank_views(pos, neg)
+    if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (B,)):
+        raise ValueError(f"rank_loss: mask ({B},) of torch.bool expected, got {tuple(mask.shape)} {mask.dtype}")
+    mask = None if mask is None else mask.contiguous()
+    loss = torch.zeros((), dtype=torch.float32, device=p.device) if B == 0 else \
+        torch.empty((), dtype=torch.float32, device=p.device)
+    denom = torch.empty((), dtype=torch.float32, device=p.device)
+    ws_bytes = size_query("trs_rank_loss_workspace_bytes", B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    call("trs_rank_loss_fwd", ptr(p), ps, ptr(n), ns, value_dtype_code(p), ptr(mask), B, K, _rank_kind_code(kind),
+         float(margin), rank_reduction_code(reduction), ptr(loss), ptr(denom), ptr(ws), ws_bytes, stream_ptr())
+    return loss, denom
+
+
+def rank_loss_backward_raw(pos: torch.Tensor, neg: Optional[torch.Tensor], kind, margin: float = 1.0,
+                           mask: Optional[torch.Tensor] = None, reduction="sum", gout: Optional[torch.Tensor] = None,
+                           denom: Optional[torch.Tensor] = None):
+    """trs_rank_loss_bwd as it is: ``(g_pos, g_neg)`` shaped like the operands -- for a (B, 1 + K) score matrix
+    (``neg`` None) ``g_pos`` is the whole (B, 1 + K) gradient and ``g_neg`` None."""
+    require_device(pos, neg, mask, gout, denom)
+    p, ps, n, ns, B, K = _rank_views(pos, neg)
+    mask = None if mask is None else mask.contiguous()
+    if neg is None:
+        g = torch.empty_like(p)
+        gp, gps, gn, gns = g, K + 1, g[:, 1:], K + 1
+    else:
+        gp, gn = torch.empty_like(p), torch.empty_like(n)
+        gps, gns = 1, K
+    call("trs_rank_loss_bwd", ptr(p), ps, ptr(n), ns, value_dtype_code(p), ptr(mask), B, K, _rank_kind_code(kind),
+         float(margin), rank_reduction_code(reduction), ptr(gout), ptr(denom), ptr(gp), gps, ptr(gn), gns, stream_ptr())
+    return (gp, None) if neg is None else (gp.reshape(pos.shape), gn)
+
+
+class _RankLoss(Function):
+    @staticmethod
+    def forward(ctx, pos, neg, kind, margin, mask, reduction):
+        loss, denom = rank_loss_forward_raw(pos, neg, kind, margin, mask, reduction)
+        ctx.save_for_backward(pos, neg, mask, denom)
+        ctx.args = (kind, margin, reduction)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        pos, neg, mask, denom = ctx.saved_tensors
+        kind, margin, reduction = ctx.args
+        gp, gn = rank_loss_backward_raw(pos, neg, kind, margin, mask, reduction, g.float().contiguous(), denom)
+        return gp, gn, None, None, None, None
+
+
+def rank_loss(pos: torch.Tensor, neg: Optional[torch.Tensor], kind, margin: float = 1.0,
+              mask: Optional[torch.Tensor] = None, reduction="sum") -> torch.Tensor:
+    """Ranking loss of positive scores ``pos`` (B,) | (B, 1) against negative scores ``neg`` (B, K), fp32 or bf16 -> an
+    fp32 scalar, forward two launches, backward one.  ``neg=None``: ``pos`` is the (B, 1 + K) score matrix of
+    ``pair_scores`` (column 0 the positive), read in place, and its gradient is written as one matrix.
+    ``kind``: 'pointwise' (1 - sigmoid(p)) + sigmoid(n) | 'bpr' softplus(-(p - n)) | 'hinge' max(0, margin - p + n) |
+    'adaptive_hinge' max(0, margin - p + max_k n), one term per sample.  ``mask`` (B,) bool drops samples.
+    ``reduction``: 'sum' | 'mean' (over the kept terms) | 'sample' (the sum over the number of kept SAMPLES: the
+    reference's masked rule); torch.sum / torch.mean are accepted for the first two."""
+    strip = lambda t: None if t is None else (t.rename(None) if t.has_names() else t)
+    pos, neg, mask = strip(pos), strip(neg), strip(mask)
+    value_dtype_code(pos)
+    return _RankLoss.apply(pos, neg, _rank_kind_code(kind), float(margin), mask, rank_reduction_code(reduction))

@@ -8,7 +8,7 @@ straight from the N tables.  ``EmbeddingFM`` = ``MultiIndicesEmbedding`` + ``Fac
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -58,6 +58,49 @@ class EmbeddingFM(nn.Module):
             emb.names = ('B', 'N', 'E',)
         fm.names = ('B', 'O',)
         return emb, fm, first
+
+
+class EmbeddingPairScorer(nn.Module):
+    """ids -> (B, 1 + K) similarity scores of the embedding models (MatrixFactorizationModel, StarSpaceModel) in one kernel
+    per direction (functional.pair_scores): ``forward(anchor_idx (B,), target_idx (B, 1 + K))``, column 0 of the target
+    ids the positive, the others sampled negatives; K = 0 is the plain GMF score.  Replaces the reference's miner
+    (anchor id repeated K times) + input layer ((B (1+K), 2, E) gather) + model (slice and multiply).
+    Tables: ``anchor_size`` / ``target_size`` rows in two ``nn.Embedding``s (``anchor.weight``, ``target.weight``);
+    ``target_size=None``: one shared table, ``target_offset`` then places the targets' rows behind the anchors' (as the
+    field offsets of ``MultiIndicesEmbedding`` do); ``anchor=`` / ``target=`` borrow existing ``nn.Embedding``s.
+    ``similarity``: 'dot' | 'cosine'.  ``set_fused_optimizer(opt)``: the backward applies the fused sparse SGD / Adagrad /
+    Adam step to the looked-up rows instead of returning a dense gradient."""
+
+    def __init__(self, embed_size: int, anchor_size: Optional[int] = None, target_size: Optional[int] = None,
+                 similarity: str = 'dot', anchor_offset: int = 0, target_offset: int = 0, out_dtype=None,
+                 anchor: Optional[nn.Embedding] = None, target: Optional[nn.Embedding] = None):
+        super().__init__()
+        if similarity not in F_.PAIR_SIMS:
+            raise ValueError(f"similarity must be one of {sorted(F_.PAIR_SIMS)}, got {similarity!r}")
+        if anchor is None:
+            if anchor_size is None:
+                raise ValueError("EmbeddingPairScorer: anchor_size or an anchor nn.Embedding is needed")
+            anchor = nn.Embedding(anchor_size, embed_size)
+            nn.init.xavier_uniform_(anchor.weight.data)
+        if target is None and target_size is not None:
+            target = nn.Embedding(target_size, embed_size)
+            nn.init.xavier_uniform_(target.weight.data)
+        if anchor.weight.shape[1] != embed_size or (target is not None and target.weight.shape[1] != embed_size):
+            raise ValueError("EmbeddingPairScorer: the tables' rows must have embed_size columns")
+        self.anchor = anchor
+        self.target = None if target is anchor else target
+        self.similarity = similarity
+        self.anchor_offset, self.target_offset = int(anchor_offset), int(target_offset)
+        self.out_dtype = out_dtype
+        self._fused_opt = None
+
+    def set_fused_optimizer(self, opt) -> None:
+        self._fused_opt = opt
+
+    def forward(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor) -> torch.Tensor:
+        tw = None if self.target is None else self.target.weight
+        return F_.pair_scores(self.anchor.weight, anchor_idx, tw, target_idx, self.anchor_offset, self.target_offset,
+                              self.similarity, self.out_dtype, self._fused_opt)
 
 
 class BCEWithLogitsLoss(nn.Module):

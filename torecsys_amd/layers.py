@@ -1354,6 +1354,84 @@ class DynamicRoutingLayer(BaseLayer):
         return outputs
 
 
+def inner_product_similarity(a: torch.Tensor, b: torch.Tensor, dim: int = 1) -> torch.Tensor:
+    """utils/operations.py: (a * b).sum(dim) -- the default similarity of the reference's StarSpaceModel"""
+    return (a * b).sum(dim=dim)
+
+
+class GeneralizedMatrixFactorizationLayer(BaseLayer):
+    """(B, 2, E) -> (B, 1) named ('B','O'): the inner product of a sample's two rows, one kernel per direction
+    (functional.block_pair_score).  layers/emb/generalized_matrix_factorization.py:44-57.  Deviation: the caller's
+    tensor keeps its names (the reference renames it in place)."""
+
+    @property
+    def inputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'inputs': ('B', '2', 'E',)}
+
+    @property
+    def outputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'outputs': ('B', '1',)}
+
+    def __init__(self):
+        super().__init__()
+
+    @staticmethod
+    def forward(emb_inputs: torch.Tensor) -> torch.Tensor:
+        outputs = F_.block_pair_score(_strip(emb_inputs), "dot")
+        outputs.names = ('B', 'O',)
+        return outputs
+
+
+def _fused_similarity(similarity) -> Optional[str]:
+    """'dot' | 'cosine' for the similarities the pair-score kernel computes on (B, 1, E) operands, else None"""
+    import functools
+    if similarity is inner_product_similarity:
+        return None          # its default dim = 1 sums over the singleton axis: not a row similarity
+    if isinstance(similarity, functools.partial) and not similarity.args and similarity.keywords == {'dim': 2}:
+        if similarity.func is inner_product_similarity:
+            return 'dot'
+        if similarity.func is torch.nn.functional.cosine_similarity:
+            return 'cosine'
+    return None
+
+
+class StarSpaceLayer(BaseLayer):
+    """(B, 2, E) -> ``similarity(context (B, 1, E), target (B, 1, E))`` named ('B','O').  layers/emb/starspace.py:62-90.
+    ``functools.partial(inner_product_similarity, dim=2)`` (this module's function: the reference model's default) and
+    ``functools.partial(torch.nn.functional.cosine_similarity, dim=2)`` give (B, 1) in one kernel per direction
+    (functional.block_pair_score); any other callable is simply called on the two (B, 1, E) views, as in the reference --
+    the bare ``inner_product_similarity`` included, whose default ``dim=1`` sums over the singleton axis and returns the
+    (B, E) product."""
+
+    @property
+    def inputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'inputs': ('B', '2', 'E',)}
+
+    @property
+    def outputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'outputs': ('B', 'E',)}
+
+    def __init__(self, similarity):
+        super().__init__()
+        self.similarity = similarity
+        self._fused = _fused_similarity(similarity)
+
+    def extra_repr(self) -> str:
+        name = getattr(self.similarity, '__qualname__', None) or getattr(getattr(self.similarity, 'func', None),
+                                                                         '__qualname__', type(self.similarity).__name__)
+        return f'similarity={name.split(".")[-1].lower()}'
+
+    def forward(self, samples_inputs: torch.Tensor) -> torch.Tensor:
+        x = _strip(samples_inputs)
+        if self._fused is not None and x.is_cuda and x.dim() == 3 and x.shape[1] == 2 \
+                and x.dtype in (torch.float32, torch.bfloat16):
+            outputs = F_.block_pair_score(x, self._fused)
+        else:
+            outputs = self.similarity(x[:, 0:1, :], x[:, 1:2, :])
+        outputs.names = ('B', 'O',)
+        return outputs
+
+
 # aliases, layers/ctr/__init__.py:23-35
 MOELayer = MixtureOfExpertsLayer
 AFMLayer = AttentionalFactorizationMachineLayer
