@@ -821,6 +821,34 @@ int trs_attn_pool_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, co
                       const void* gout, void* dx, float* dw_part, float* db_part, int32_t blocks, void* workspace,
                       size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
 
+/* ---- residual multi-head self-attention over a short list (csrc/self_attn.hip) -------------------------------------
+ * y = x + nn.MultiheadAttention(x, x, x) for x (B, L, E) contiguous, no masks, no dropout.  Per sample (d = E / H):
+ *   [Q | K | V] = X w_in^T + b_in;   P_h = softmax_rows(Q_h K_h^T / sqrt(d));   O = concat_h(P_h V_h)
+ *   y = X + O w_out^T + b_out                                                                  (B, L, E) of x's dtype
+ * replaces the in_proj GEMM, two batched GEMMs, the softmax over (B H, L, L), the out_proj GEMM and the residual add of
+ * models/ltr/personalized_reranking.py; nothing but y is written.  w_in (3E, E), w_out (E, E), b_in (3E) and b_out (E)
+ * of x's dtype; the biases are both given or both NULL.
+ * trs_self_attn_path (a pure function): 0 unsupported, 1 vector path (fp32 FMA; 1 <= L <= 64, E <= 128, E % H == 0 and a
+ *   backward working set of 6 L E + 2 L^2 + 6 L floats within 160 KB of LDS: every L at E <= 64, L <= 47 at E = 128),
+ *   2 MFMA path (bf16 with E % 16 == 0 and d % 16 == 0 in the same envelope; operands bf16, fp32 accumulation).
+ * trs_self_attn_blocks: the workgroups a launch uses (persistent: min(B, resident workgroups)); the backward is launched
+ *   with the count the caller passes (1 <= blocks <= B), which sizes its workspace.
+ * Backward, gout (B, L, E); Q, K, V, P and O are recomputed from x:
+ *   dx (B, L, E) of x's dtype, or NULL when the input needs no gradient;
+ *   workspace (trs_self_attn_bwd_workspace_bytes): `blocks` fp32 slabs [dw_in (3E, E) | dw_out (E, E) | db_in (3E) |
+ *   db_out (E)], fully written; the caller adds them over `blocks`.  No atomics, samples are dealt to workgroups
+ *   statically: reproducible bits.
+ * Errors: NULL pointer, one bias without the other, blocks outside [1, B] TRS_EINVAL; bad dtype and a shape
+ * trs_self_attn_path refuses TRS_EDTYPE (-2); short workspace TRS_EWORKSPACE.                                          */
+int trs_self_attn_path(int32_t L, int32_t E, int32_t H, int32_t dtype);
+int trs_self_attn_blocks(int64_t B, int32_t L, int32_t E, int32_t H, int32_t dtype, int32_t backward);
+size_t trs_self_attn_bwd_workspace_bytes(int32_t blocks, int32_t E);
+int trs_self_attn_fwd(const void* x, int64_t B, int32_t L, int32_t E, int32_t H, int32_t dtype, const void* w_in,
+                      const void* b_in, const void* w_out, const void* b_out, void* y, trs_stream_t stream);
+int trs_self_attn_bwd(const void* x, int64_t B, int32_t L, int32_t E, int32_t H, int32_t dtype, const void* w_in,
+                      const void* b_in, const void* w_out, const void* b_out, const void* gout, void* dx,
+                      void* workspace, size_t ws_bytes, int32_t blocks, trs_stream_t stream);
+
 /* ---- behaviour-to-interest dynamic routing, MIND (csrc/dynamic_routing.hip) ----------------------------------------
  * priors (B, N, R) fp32 = x @ S (the caller's GEMM, fp32 result), noise (B, K, N, R) of the value dtype, c[b,k,n] = 0:
  *   num_iter - 1 times:  w = softmax_k(noise[b,k,n,r] + c[b,k,n]);  z[b,k,r] = sum_n w priors[b,n,r];  v = squash(z)

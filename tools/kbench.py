@@ -18,7 +18,9 @@ with lengths uniform in [1, L], the fused path against the same module with the 
 inputs, see bench_seq).
 --what rank [--neg 10] [--sim dot|cosine]: pair scores + ranking loss of the embedding models, the fused path against the
 same module with the switch off and against the reference-shaped composition, and the four kernels alone (own inputs, see
-bench_rank)."""
+bench_rank).
+--what prm [--L 30] [--H 4] [--layers 2]: the residual self-attention block and PersonalizedReRankingModel over it, fp32 and
+bf16, the fused path against the same modules with the switch off, and the two kernels alone (own inputs, see bench_prm)."""
 import argparse
 import os
 import sys
@@ -242,6 +244,109 @@ def bench_attn(a):
         med = ts[len(ts) // 2]
         print(f"kernel   {name:22s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
               f"{fl / med / 1e12:6.1f} TFLOP/s ({blocks} workgroups in the backward)", flush=True)
+
+
+def bench_prm(a):
+    """Residual self-attention (csrc/self_attn.hip) at (B, L, E, H) and PersonalizedReRankingModel with ``--layers``
+    encoder layers over it, fp32 and bf16: the block ``x + MHA(x)`` forward and forward + backward, and the whole harness
+    model forward + backward, the fused default against the SAME modules with the switch off (fused.SELF_ATTN = False: the
+    nn.MultiheadAttention composition a user of the reference runs today), taking turns inside every round; then the two
+    kernels alone with algorithmic GB/s.  Every figure is the median of ``--rounds`` per-round medians with their min..max."""
+    import torch.nn as nn
+    from harness.ltr_models import PersonalizedReRankingModel
+    from torecsys_amd import fused as FU
+    from torecsys_amd._abi import call, ptr, size_query, stream_ptr, value_dtype_code
+    dev = torch.device("cuda:0")
+    B, L, E, H, layers = a.B, a.L, a.E, a.H, a.layers
+    flops = B * (8 * L * E * E + 4 * L * L * E)
+    switch = FU.SELF_ATTN
+    for dt, s in ((torch.float32, 4), (torch.bfloat16, 2)):
+        g = torch.Generator(device=dev).manual_seed(1234)
+        mha = nn.MultiheadAttention(E, H)
+        with torch.no_grad():
+            mha.in_proj_bias.normal_(0, 0.1)
+            mha.out_proj.bias.normal_(0, 0.1)
+        mha = mha.to(dev).to(dt)
+        x = torch.randn(B, L, E, generator=g, device=dev, dtype=dt).requires_grad_()
+        gout = torch.randn(B, L, E, generator=g, device=dev, dtype=dt)
+        torch.manual_seed(7)
+        model = PersonalizedReRankingModel(embed_size=E, max_num_position=L, encoding_size=E, num_heads=H,
+                                           num_layers=layers).to(dev).to(dt).train()
+        gm = torch.randn(B, L, generator=g, device=dev, dtype=dt)
+        alg_f = 2 * B * L * E * s + (4 * E * E + 4 * E) * s
+        alg_b = 3 * B * L * E * s + (4 * E * E + 4 * E) * s
+        print(f"self-attention B={B} L={L} E={E} H={H} layers={layers} {dt} path {F_.self_attn_path(L, E, H, dt)}, "
+              f"{a.rounds} rounds x {a.iters} launches; block forward {alg_f / 1e6:.0f} MB (alg), {flops / 1e9:.1f} GFLOP",
+              flush=True)
+
+        def block(fused):
+            def f():
+                FU.SELF_ATTN = fused
+                return FU.residual_self_attention(mha, x)
+            return f
+
+        def block_fb(fused):
+            def run():
+                FU.SELF_ATTN = fused
+                x.grad = None
+                for p in mha.parameters():
+                    p.grad = None
+                FU.residual_self_attention(mha, x).backward(gout)
+            return run
+
+        def model_fb(fused):
+            def run():
+                FU.SELF_ATTN = fused
+                for p in model.parameters():
+                    p.grad = None
+                model(x.detach()).rename(None).backward(gm)
+            return run
+
+        names = ("self_attn (HIP)", "composition (ATen)")
+        for what, mk in (("block fwd", block), ("block fwd+bwd", block_fb), ("model fwd+bwd", model_fb)):
+            cands = list(zip(names, (mk(True), mk(False))))
+            per = {n: [] for n in names}
+            for _ in range(a.rounds):
+                for n, f in cands:
+                    if what == "block fwd":
+                        with torch.no_grad():
+                            per[n].append(timeit(f, iters=a.iters, warm=2)[0])
+                    else:
+                        per[n].append(timeit(f, iters=a.iters, warm=2)[0])
+            med = {}
+            for n, ts in per.items():
+                ts = sorted(ts)
+                med[n] = ts[len(ts) // 2]
+                print(f"{what:14s} {n:20s} med {med[n] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us",
+                      flush=True)
+            print(f"{what:14s} composition / self_attn = {med[names[1]] / med[names[0]]:.2f}x", flush=True)
+        FU.SELF_ATTN = switch
+        # the two kernels alone
+        xd = x.detach()
+        w_in, b_in = mha.in_proj_weight.detach(), mha.in_proj_bias.detach()
+        w_out, b_out = mha.out_proj.weight.detach(), mha.out_proj.bias.detach()
+        code = value_dtype_code(xd)
+        y = torch.empty_like(xd)
+        dx = torch.empty_like(xd)
+        blocks = size_query("trs_self_attn_blocks", B, L, E, H, code, 1)
+        ws_bytes = size_query("trs_self_attn_bwd_workspace_bytes", blocks, E)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+
+        def k_fwd():
+            call("trs_self_attn_fwd", ptr(xd), B, L, E, H, code, ptr(w_in), ptr(b_in), ptr(w_out), ptr(b_out), ptr(y),
+                 stream_ptr())
+
+        def k_bwd():
+            call("trs_self_attn_bwd", ptr(xd), B, L, E, H, code, ptr(w_in), ptr(b_in), ptr(w_out), ptr(b_out), ptr(gout),
+                 ptr(dx), ptr(ws), ws_bytes, blocks, stream_ptr())
+
+        for name, f, alg, fl in (("trs_self_attn_fwd", k_fwd, alg_f, flops), ("trs_self_attn_bwd", k_bwd, alg_b, 3 * flops)):
+            ts = sorted(timeit(f, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+            med = ts[len(ts) // 2]
+            print(f"kernel         {name:20s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
+                  f"{alg / med / 1e9:7.1f} GB/s (alg)  {fl / med / 1e12:5.1f} TFLOP/s ({blocks} workgroups in the backward)",
+                  flush=True)
+        del model, mha, x, gout, y, dx, ws
 
 
 def bench_senet(a):
@@ -819,6 +924,7 @@ def main():
     ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"], help="seq: the recurrent cell")
     ap.add_argument("--neg", type=int, default=10, help="rank: sampled negatives per sample")
     ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
+    ap.add_argument("--layers", type=int, default=2, help="prm: encoder layers of the model")
     a = ap.parse_args()
     if a.what == "rank":         # own inputs and modules: not part of "all"
         return bench_rank(a)
@@ -832,6 +938,10 @@ def main():
         return bench_bag(a)
     if a.what == "attn":         # own inputs and module: not part of "all"
         return bench_attn(a)
+    if a.what == "prm":          # own inputs and modules: not part of "all"; the list and head defaults of the paper
+        a.L = a.L if any(v.startswith("--L") for v in sys.argv) else 30
+        a.H = a.H if any(v.startswith("--H") for v in sys.argv) else 4
+        return bench_prm(a)
     if a.what == "senet":        # own inputs and modules: not part of "all"
         return bench_senet(a)
     if a.what == "moe":          # own inputs and modules: not part of "all"

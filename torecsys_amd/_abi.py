@@ -112,6 +112,11 @@ SIGNATURES = {
     "trs_attn_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
     "trs_attn_pool_bwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32,
                                     _P, _SZ, _P, _P]),
+    "trs_self_attn_path": (c_int32, [_I32, _I32, _I32, _I32]),
+    "trs_self_attn_blocks": (c_int32, [_I64, _I32, _I32, _I32, _I32, _I32]),
+    "trs_self_attn_bwd_workspace_bytes": (_SZ, [_I32, _I32]),
+    "trs_self_attn_fwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "trs_self_attn_bwd": (c_int32, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _I32, _P]),
     "trs_senet_fused_supported": (c_int32, [_I32, _I32, _I32, _I32]),
     "trs_senet_fwd": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "trs_senet_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32]),

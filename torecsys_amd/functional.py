@@ -759,6 +759,87 @@ def attn_pool_layer(weight: torch.Tensor, idx: torch.Tensor, in_proj_weight: tor
 
 
 # --------------------------------------------------------------------------------------------
+# residual self-attention over a short list: x + nn.MultiheadAttention(x, x, x), un-pooled
+# --------------------------------------------------------------------------------------------
+def self_attn_path(L: int, E: int, H: int, dtype: torch.dtype) -> int:
+    """0: no fused kernel for this shape (callers keep the ATen composition), 1: vector path, 2: MFMA path
+    (trs_self_attn_path; a pure function, callable without a device)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return 0
+    code = _abi.TRS_F32 if dtype == torch.float32 else _abi.TRS_BF16
+    return size_query("trs_self_attn_path", int(L), int(E), int(H), code)
+
+
+class _SelfAttnResidual(Function):
+    @staticmethod
+    def forward(ctx, x, w_in, b_in, w_out, b_out, num_heads):
+        require_device(x, w_in, b_in, w_out, b_out)
+        B, L, E = x.shape
+        H = int(num_heads)
+        xc = x.contiguous()
+        y = torch.empty(B, L, E, dtype=x.dtype, device=x.device)
+        call("trs_self_attn_fwd", ptr(xc), B, L, E, H, value_dtype_code(xc), ptr(w_in.contiguous()),
+             ptr(None if b_in is None else b_in.contiguous()), ptr(w_out.contiguous()),
+             ptr(None if b_out is None else b_out.contiguous()), ptr(y), stream_ptr())
+        # nothing but the inputs is kept: the backward recomputes Q, K, V, the probabilities and O from x
+        ctx.save_for_backward(x, w_in, b_in, w_out, b_out)
+        ctx.H = H
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w_in, b_in, w_out, b_out = ctx.saved_tensors
+        B, L, E = x.shape
+        need = ctx.needs_input_grad
+        if B == 0:
+            return tuple(torch.zeros_like(t) if t is not None and n else None
+                         for t, n in zip((x, w_in, b_in, w_out, b_out), need)) + (None,)
+        dev = x.device
+        xc = x.contiguous()
+        code = value_dtype_code(xc)
+        blocks = size_query("trs_self_attn_blocks", B, L, E, ctx.H, code, 1)
+        ws_bytes = size_query("trs_self_attn_bwd_workspace_bytes", blocks, E)
+        slabs = torch.empty(blocks, 4 * E * E + 4 * E, dtype=torch.float32, device=dev)
+        dx = torch.empty(B, L, E, dtype=x.dtype, device=dev) if need[0] else None
+        call("trs_self_attn_bwd", ptr(xc), B, L, E, ctx.H, code, ptr(w_in.contiguous()),
+             ptr(None if b_in is None else b_in.contiguous()), ptr(w_out.contiguous()),
+             ptr(None if b_out is None else b_out.contiguous()), ptr(g.contiguous()), ptr(dx), ptr(slabs), ws_bytes,
+             blocks, stream_ptr())
+        tot = slabs.sum(0)          # fixed order: reproducible
+        o1, o2, o3 = 3 * E * E, 4 * E * E, 4 * E * E + 3 * E
+        g_win = tot[:o1].view(3 * E, E).to(w_in.dtype) if need[1] else None
+        g_bin = tot[o2:o3].to(b_in.dtype) if b_in is not None and need[2] else None
+        g_wout = tot[o1:o2].view(E, E).to(w_out.dtype) if need[3] else None
+        g_bout = tot[o3:].to(b_out.dtype) if b_out is not None and need[4] else None
+        return dx, g_win, g_bin, g_wout, g_bout, None
+
+
+def self_attn_residual(x: torch.Tensor, in_proj_weight: torch.Tensor, in_proj_bias: Optional[torch.Tensor],
+                       out_w: torch.Tensor, out_b: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+    """(B, L, E) in ``x``'s dtype: ``x + nn.MultiheadAttention(E, num_heads)(x, x, x)`` over the list dimension of a
+    batch-first (B, L, E) block, without masks or dropout, in one HIP pass per direction (csrc/self_attn.hip).
+    ``in_proj_weight`` (3E, E), ``out_w`` (E, E); ``in_proj_bias`` (3E) and ``out_b`` (E) are both given or both None.
+    The backward recomputes everything from ``x``; the weight gradients are reduced in a fixed order (same bits on every
+    call).  Raises for shapes ``self_attn_path`` refuses."""
+    if x.dim() != 3:
+        raise ValueError(f"self_attn_residual: x must be (B, L, E), got shape {tuple(x.shape)}")
+    B, L, E = x.shape
+    if tuple(in_proj_weight.shape) != (3 * E, E) or tuple(out_w.shape) != (E, E):
+        raise ValueError(f"self_attn_residual: in_proj_weight must be ({3 * E}, {E}) and out_w ({E}, {E})")
+    if (in_proj_bias is None) != (out_b is None):
+        raise ValueError("self_attn_residual: in_proj_bias and out_b are both given or both None")
+    if in_proj_bias is not None and (tuple(in_proj_bias.shape) != (3 * E,) or tuple(out_b.shape) != (E,)):
+        raise ValueError(f"self_attn_residual: in_proj_bias must be ({3 * E},) and out_b ({E},)")
+    if any(t is not None and t.dtype != x.dtype for t in (in_proj_weight, in_proj_bias, out_w, out_b)):
+        raise TypeError("self_attn_residual: the parameters must have x's dtype")
+    if self_attn_path(L, E, num_heads, x.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: self_attn_residual does not cover L={L}, E={E}, H={num_heads}, {x.dtype} "
+                                  f"(1 <= L <= 64, E <= 128, E % H == 0, fp32 / bf16)")
+    return _SelfAttnResidual.apply(x, in_proj_weight, in_proj_bias, out_w, out_b, num_heads)
+
+
+# --------------------------------------------------------------------------------------------
 # K1+K2(+K8): fused lookup + FM (+ first-order sum)
 # --------------------------------------------------------------------------------------------
 class _EmbedFM(Function):

@@ -8,6 +8,7 @@ straight from the N tables.  ``EmbeddingFM`` = ``MultiIndicesEmbedding`` + ``Fac
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional
 
 import torch
@@ -15,6 +16,35 @@ import torch.nn as nn
 
 from . import functional as F_
 from .inputs import BaseInput, MultiIndicesEmbedding, field_offsets
+
+# TRS_SELF_ATTN: 1 / 0 send every dtype residual_self_attention covers through functional.self_attn_residual / keep the
+# nn.MultiheadAttention composition (the A/B baseline).  Unset (None): per dtype by what was measured at B = 65 536, L = 30,
+# E = 64, H = 4 (profiles/self_attn_kernels.md) -- bf16 (MFMA path) on: 3.3x forward, 2.0x forward + backward; fp32 (vector
+# path) off: 0.86x / 0.73x of the composition
+_env = os.environ.get("TRS_SELF_ATTN")
+SELF_ATTN = None if _env is None else _env not in ("", "0")
+
+
+def self_attn_enabled(dtype: torch.dtype) -> bool:
+    return dtype == torch.bfloat16 if SELF_ATTN is None else SELF_ATTN
+
+
+def residual_self_attention(mha: nn.MultiheadAttention, x: torch.Tensor) -> torch.Tensor:
+    """``x + mha(x, x, x)`` over the list dimension of an un-named batch-first (B, L, E) block: the attention half of an
+    encoder layer of ``PersonalizedReRankingModel`` (models/ltr/personalized_reranking.py:126-146).  One HIP pass per
+    direction (``functional.self_attn_residual``, csrc/self_attn.hip) for a HIP tensor in fp32 / bf16, an ``mha`` with one
+    embedding size, no ``bias_k`` / ``add_zero_attn``, attention dropout 0 or eval mode, a shape ``self_attn_path`` takes
+    and the switch ``TRS_SELF_ATTN`` (default: on for bf16, off for fp32, where the kernel was measured slower than the
+    composition); every other case runs the reference's composition on the transposed block."""
+    if (x.is_cuda and self_attn_enabled(x.dtype) and x.dim() == 3 and x.dtype in (torch.float32, torch.bfloat16)
+            and mha._qkv_same_embed_dim and mha.bias_k is None and mha.bias_v is None and not mha.add_zero_attn
+            and not getattr(mha, "batch_first", False) and (mha.dropout == 0 or not mha.training)
+            and x.shape[2] == mha.embed_dim and mha.in_proj_weight.dtype == x.dtype
+            and F_.self_attn_path(x.shape[1], x.shape[2], mha.num_heads, x.dtype) != 0):
+        return F_.self_attn_residual(x, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                                     mha.num_heads)
+    xt = x.transpose(0, 1)
+    return x + mha(xt, xt, xt)[0].transpose(0, 1)
 
 
 class FusedFieldAwareFM(BaseInput):

@@ -1432,6 +1432,28 @@ class StarSpaceLayer(BaseLayer):
         return outputs
 
 
+class PositionEmbeddingLayer(BaseLayer):
+    """(B, L, E) + ``bias`` (1, L, 1): one trainable offset per list position, the input layer of the reference's
+    PersonalizedReRankingModel.  layers/ctr/position_embedding.py:34-60.  A broadcast add (no kernel of its own);
+    ``patch()`` does not rebind it."""
+
+    @property
+    def inputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'inputs': ('B', 'L', 'E',)}
+
+    @property
+    def outputs_size(self) -> Dict[str, Tuple[str, ...]]:
+        return {'outputs': ('B', 'L', 'E',)}
+
+    def __init__(self, max_num_position: int):
+        super().__init__()
+        self.bias = nn.Parameter(torch.Tensor(1, max_num_position, 1))
+        nn.init.normal_(self.bias)
+
+    def forward(self, session_embed_inputs: torch.Tensor) -> torch.Tensor:
+        return session_embed_inputs + self.bias
+
+
 # aliases, layers/ctr/__init__.py:23-35
 MOELayer = MixtureOfExpertsLayer
 AFMLayer = AttentionalFactorizationMachineLayer

@@ -24,7 +24,11 @@ one kernel, ``functional.ctr_logit``, and the one-output ``fc`` of ``DeepAndCros
 (deep_and_cross_network.py:82-92: ``cat`` of the cross and deep blocks -> flatten -> Linear) reads the two blocks where
 they lie, ``functional.cat_head`` (no 0.65 GB concatenation at the bench size): the classes keep their constructors, parameters and ``state_dict``; only ``forward``
 is wrapped, and the wrapper hands anything it does not cover (CPU tensors, dtypes other than fp32 / bf16, models whose
-layers are not the drop-ins) to the reference's own ``forward``."""
+layers are not the drop-ins) to the reference's own ``forward``.  With them, ``PersonalizedReRankingModel``
+(models/ltr/personalized_reranking.py): its encoder loop runs ``fused.residual_self_attention`` for the attention and its
+residual add (one HIP pass per direction, csrc/self_attn.hip) and the model's own BatchNorm1d, feed-forward and output
+modules for the rest, returning the ('B', 'O')-named softmax; CPU tensors, other dtypes, a list shorter than 2 or a named
+input (which raises in the reference) go to the reference's own ``forward``.  ``PositionEmbeddingLayer`` is not rebound."""
 from __future__ import annotations
 
 import importlib
@@ -34,6 +38,7 @@ import torch
 
 from . import functional as _F
 from . import inputs as _inputs
+from .fused import residual_self_attention
 from . import layers as _layers
 
 _LAYER_NAMES = [
@@ -145,21 +150,44 @@ def _dcn_forward(orig):
     return forward
 
 
+def _prm_forward(orig):
+    def forward(self, feat_inputs):
+        layers = getattr(self, "layers", None)
+        if not (torch.is_tensor(feat_inputs) and feat_inputs.is_cuda and not feat_inputs.has_names()
+                and feat_inputs.dim() == 3 and feat_inputs.shape[1] >= 2
+                and feat_inputs.dtype in (torch.float32, torch.bfloat16) and isinstance(layers, torch.nn.ModuleDict)
+                and layers['InputLayer']['PositionEmbedding'] is not None):
+            return orig(self, feat_inputs)
+        output = layers['InputLayer']['FeedForward'](layers['InputLayer']['PositionEmbedding'](feat_inputs))
+        for i in range(len(layers['EncodingLayer'])):          # personalized_reranking.py:122-162, un-named
+            layer = layers['EncodingLayer'][f'Transformer_{i}']
+            output = layer['AttentionBatchNorm'](residual_self_attention(layer['MultiHeadAttention'], output))
+            output = layer['FNNBatchNorm'](layer['FeedForward'](output) + output)
+        output = layers['OutputLayer']['Softmax'](layers['OutputLayer']['FeedForward'](output).flatten(1))
+        output.names = ('B', 'O',)
+        return output
+    forward._trs_head = True
+    return forward
+
+
 _HEADS = {"FactorizationMachineModel": _fm_forward, "DeepFactorizationMachineModel": _deepfm_forward,
           "XDeepFactorizationMachineModel": _xdeepfm_forward, "DeepAndCrossNetworkModel": _dcn_forward}
+# forward wrappers beyond the CTR heads: the learning-to-rank model, whose encoder layers run the fused residual self-attention
+_MODEL_FORWARDS = {"PersonalizedReRankingModel": _prm_forward}
 _saved_forwards = {}
 
 
 def _patch_heads(pkg):
     seen = set()
-    for mod, n in _targets(pkg, list(_HEADS)):
+    wrappers = {**_HEADS, **_MODEL_FORWARDS}
+    for mod, n in _targets(pkg, list(wrappers)):
         cls = getattr(mod, n)
         if id(cls) in seen or not isinstance(cls, type) or getattr(cls.__dict__.get("forward"), "_trs_head", False):
             continue
         seen.add(id(cls))
         orig = cls.forward
         _saved_forwards[cls] = orig
-        cls.forward = _HEADS[n](orig)
+        cls.forward = wrappers[n](orig)
 
 
 def patch(torecsys_pkg=None, fuse_fm: bool = True, mlp: bool = True, router: bool = True, heads: bool = True):
