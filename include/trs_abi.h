@@ -501,6 +501,48 @@ int trs_permute_grad(const void* g_block, const void* g_fm, const float* fm_sum,
                      const int32_t* pos, int64_t K, int32_t N, int32_t E, int32_t dtype, void* out,
                      trs_stream_t stream);
 
+/* ---- bag pooling over a row-sharded table (dist.RowShardedListIndicesEmbedding; csrc/bag_shard.hip) ---------------
+ * Sum / mean pooling is linear: every owner pools the rows it holds for each (source rank, sample) into one fp32 partial
+ * row and only those rows travel.  New: the reference has no distributed code.
+ *
+ * Route, on the sender.  idx (B, L) global row ids, owner = id / rows_per_rank (rows_per_rank * world >= V):
+ *   counts (world, B) int32    counts[w, b] = lookups of sample b that rank w owns
+ *   send_ids (n_send int32)    LOCAL ids (id - owner * rows_per_rank) grouped by owner, then by sample, then in list order:
+ *                              segment (w, b) = send_ids[seg_start[w*B + b] .. seg_start[w*B + b + 1]), seg_start
+ *                              (world*B + 1 int32) the exclusive scan of counts in that (owner-major) order, n_send its
+ *                              last entry.  The layout is a pure function of idx: no atomics place a value.
+ * An id outside [0, V) is not sent (no count, no slot) and raises *err_flag (trs_bag_route_count only; may be NULL).
+ * A slot at or past the end of its segment or past n_send is never written (a seg_start that is not the scan of the counts).
+ * One wave per sample, 64 list positions at a time; the place of a lookup in its segment is ballot + popcount per owner.
+ * Limits: 1 <= world <= 64, 1 <= L <= 65535, B*L < 2^31, else TRS_ESHAPE.  B == 0 (and, for place, n_send == 0) returns
+ * TRS_OK and touches nothing.  NULL pointer TRS_EINVAL, bad idx dtype TRS_EDTYPE, all before any launch.               */
+int trs_bag_route_count(const void* idx, int32_t idx_dtype, int64_t B, int32_t L, int64_t V, int64_t rows_per_rank,
+                        int32_t world, int32_t* counts, int32_t* err_flag, trs_stream_t stream);
+int trs_bag_route_place(const void* idx, int32_t idx_dtype, int64_t B, int32_t L, int64_t V, int64_t rows_per_rank,
+                        int32_t world, const int32_t* seg_start, int32_t* send_ids, int64_t n_send, trs_stream_t stream);
+/* Owner: out[s, :] (S, E) fp32 = the sum, in list order and in fp32, of the shard rows ids[seg_start[s] .. seg_start[s+1])
+ * (ids: n int32 local row ids; seg_start: S + 1 int32, clipped to [0, n]).  An empty segment gives a zero row; an id
+ * outside [0, n_valid) reads as a zero row and raises *err_flag (may be NULL).  shard (rows, E) fp32 or bf16.  Rows that
+ * are a power-of-two number (<= 64) of whole 16-byte vectors take the lane-group path of trs_bag_pool_fwd; any other E
+ * one thread per (s, e).  S == 0 returns TRS_OK and touches nothing (n == 0 with S > 0 writes S zero rows).
+ * NULL pointer TRS_EINVAL, bad dtype TRS_EDTYPE, n >= 2^31 TRS_ESHAPE, all before any launch.                            */
+int trs_bag_pool_segments(const void* shard, int64_t n_valid, int32_t E, int32_t dtype, const int32_t* ids, int64_t n,
+                          const int32_t* seg_start, int64_t S, float* out, int32_t* err_flag, trs_stream_t stream);
+/* out[b, e] = round_to_dtype( (parts[0, b, e] + parts[1, b, e] + ... + parts[P-1, b, e]) * scale ), parts (P, B, E) fp32,
+ * p ascending, fp32 sum, exactly one rounding; scale = 1.f / (float)L for the mean (the expression of trs_bag_pool_fwd).
+ * B == 0 returns TRS_OK and touches nothing.  NULL pointer / P < 1 TRS_EINVAL, bad dtype TRS_EDTYPE.                     */
+int trs_bag_combine(const float* parts, int32_t P, int64_t B, int32_t E, float scale, int32_t dtype, void* out,
+                    trs_stream_t stream);
+/* Backward on the owner: g_all (S, E) of `dtype`, one output-gradient row per segment (same ids / seg_start as
+ * trs_bag_pool_segments).  For every lookup q of segment s: grad_rows[q, :] (n, E) = g_all[s, :] and ids_bwd[q] = ids[q];
+ * a lookup of pad_local_row (-1: none) or of an id outside [0, n_valid) -- which read as a zero row in the forward -- gets
+ * a zero row and ids_bwd[q] = -1 (trs_csr_build_skip / the unchecked bucket build leave -1 out of the index), and so do
+ * the slots q in [seg_start[S], n) behind the last segment (the room a one-rank sender keeps for ids it did not send).
+ * S == 0 or n == 0 returns TRS_OK and touches nothing.  NULL pointer TRS_EINVAL, bad dtype TRS_EDTYPE.                  */
+int trs_bag_expand_grad(const void* g_all, int32_t dtype, int32_t E, const int32_t* ids, int64_t n,
+                        const int32_t* seg_start, int64_t S, int64_t n_valid, int64_t pad_local_row, void* grad_rows,
+                        int32_t* ids_bwd, trs_stream_t stream);
+
 /* ---- Linear with one output unit (the logit layer of the DeepFM / xDeepFM MLP, multilayer_perceptron.py:51) -------
  * out[r] = h[r,:] . w + bias[0]: a row-wise dot product, not a GEMM.  h (rows, C), w (C); C * sizeof(T) / 16 must be
  * a power of two <= 64.  bwd: gh (rows, C) = g[r] * w (may be NULL); gw (C), gb (1) fp32, written (both or neither). */

@@ -20,7 +20,10 @@ inputs, see bench_seq).
 same module with the switch off and against the reference-shaped composition, and the four kernels alone (own inputs, see
 bench_rank).
 --what prm [--L 30] [--H 4] [--layers 2]: the residual self-attention block and PersonalizedReRankingModel over it, fp32 and
-bf16, the fused path against the same modules with the switch off, and the two kernels alone (own inputs, see bench_prm)."""
+bf16, the fused path against the same modules with the switch off, and the two kernels alone (own inputs, see bench_prm).
+--what bagshard [--L 50] [--world 8]: the four kernels of the sharded bag pooling alone with this process as rank 0 of
+--world, the world-1 module against the unsharded ListIndicesEmbedding, fp32 and bf16, and the wire bytes per rank of the
+partial-sum path against the rows path (own inputs, see bench_bagshard)."""
 import argparse
 import os
 import sys
@@ -903,6 +906,79 @@ def bench_rank(a):
               flush=True)
 
 
+def bench_bagshard(a):
+    """Sharded bag pooling (csrc/bag_shard.hip) on ONE GPU at (B, L, E, V), fp32 and bf16: the four kernels alone with this
+    process playing rank 0 of ``--world`` (it routes its batch over W owners, pools the segments W senders with batches like
+    its own would send to it, combines W slabs, expands W*B output gradients); the world-1 module forward + backward
+    against the unsharded ListIndicesEmbedding (needs an nccl group of one rank, started here); and the wire bytes per
+    rank of the partial-sum path against the rows path, from the formulas (byte counts, not measurements)."""
+    import torch.distributed as dist
+    from torecsys_amd.dist import HipOps, RowShardedListIndicesEmbedding, segment_starts, shard_ranges
+    from torecsys_amd.inputs import ListIndicesEmbedding
+    dev = torch.device("cuda:0")
+    B, L, E, V, W = a.B, a.L, a.E, a.V, a.world
+    ops = HipOps()
+    g = torch.Generator(device=dev).manual_seed(1234)
+    idx = torch.randint(0, V, (B, L), generator=g, device=dev)
+    per, ranges = shard_ranges(V, W)
+    lo, hi = ranges[0]
+    print(f"sharded bag pooling B={B} L={L} E={E} V={V} world={W} (this process: rank 0, rows [{lo}, {hi})), "
+          f"{a.rounds} rounds x {a.iters} launches", flush=True)
+    for s in (4, 2):
+        rows, parts, gback = (W - 1) / W * B * L * E * s, (W - 1) * B * E * 4, (W - 1) * B * E * s
+        print(f"wire bytes per rank ({'fp32' if s == 4 else 'bf16'} table): forward rows {rows / 1e6:.1f} MB -> fp32 partials "
+              f"{parts / 1e6:.1f} MB (x{rows / max(parts, 1):.2f}); backward rows {rows / 1e6:.1f} MB -> output gradient "
+              f"{gback / 1e6:.1f} MB (x{rows / max(gback, 1):.2f})", flush=True)
+
+    def report(name, fns):
+        per_ = {n: [] for n, _ in fns}
+        for _ in range(a.rounds):
+            for n, f in fns:
+                per_[n].append(timeit(f, iters=a.iters, warm=2)[0])
+        for n, ts in per_.items():
+            ts = sorted(ts)
+            print(f"{name:5s} {n:44s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us",
+                  flush=True)
+
+    counts, seg_start, send_ids = ops.bag_route(idx, V, per, W)
+    # what rank 0 receives: its own segment from each of W senders with batches like its own
+    n0 = int(seg_start[B])
+    ids = send_ids[:n0].repeat(W)
+    rseg = segment_starts(counts[0].unsqueeze(0).expand(W, B).contiguous())
+    for dt in (torch.float32, torch.bfloat16):
+        name = "fp32" if dt == torch.float32 else "bf16"
+        shard = torch.randn(hi - lo, E, generator=g, device=dev, dtype=dt)
+        slabs = torch.randn(W, B, E, generator=g, device=dev)
+        g_all = torch.randn(W * B, E, generator=g, device=dev, dtype=dt)
+        report(name, [
+            ("route (count + scan + place)", lambda: ops.bag_route(idx, V, per, W)),
+            (f"pool_segments ({W * B} segments, {ids.numel()} ids)", lambda: ops.bag_pool_segments(shard, hi - lo, ids, rseg)),
+            (f"combine ({W} slabs)", lambda: ops.bag_combine(slabs, 1.0 / L, dt)),
+            ("expand_grad", lambda: ops.bag_expand_grad(g_all, ids, rseg, hi - lo, 0)),
+        ])
+    if not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29533")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    try:
+        for dt in (torch.float32, torch.bfloat16):
+            name = "fp32" if dt == torch.float32 else "bf16"
+            gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+            plain = ListIndicesEmbedding(E, V, padding_idx=0, output_method="avg_pooling").to(dev).to(dt)
+            shd = RowShardedListIndicesEmbedding(E, V, padding_idx=0, output_method="avg_pooling", dtype=dt, device=dev)
+
+            def step(m):
+                def run():
+                    F_.clear_caches()
+                    m.embedding.weight.grad = None
+                    m(idx).rename(None).backward(gout)
+                return run
+            report(name, [("fwd+bwd ListIndicesEmbedding (unsharded)", step(plain)),
+                          ("fwd+bwd RowShardedListIndicesEmbedding (world 1)", step(shd))])
+    finally:
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -925,8 +1001,11 @@ def main():
     ap.add_argument("--neg", type=int, default=10, help="rank: sampled negatives per sample")
     ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
     ap.add_argument("--layers", type=int, default=2, help="prm: encoder layers of the model")
+    ap.add_argument("--world", type=int, default=8, help="bagshard: the world size whose rank 0 this process plays")
     a = ap.parse_args()
-    if a.what == "rank":         # own inputs and modules: not part of "all"
+    if a.what == "bagshard":     # own inputs and modules: not part of "all"
+        return bench_bagshard(a)
+    if a.what == "rank":        # own inputs and modules: not part of "all"
         return bench_rank(a)
     if a.what == "seq":          # own inputs and module: not part of "all"
         return bench_seq(a)

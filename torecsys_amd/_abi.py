@@ -188,6 +188,11 @@ SIGNATURES = {
     "trs_embed_fm_sharded": (c_int32, [_P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _I32, _I32, _I64, _I32, _P, _P, _P, _P,
                                        _P]),
     "trs_permute_grad": (c_int32, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P]),
+    "trs_bag_route_count": (c_int32, [_P, _I32, _I64, _I32, _I64, _I64, _I32, _P, _P, _P]),
+    "trs_bag_route_place": (c_int32, [_P, _I32, _I64, _I32, _I64, _I64, _I32, _P, _P, _I64, _P]),
+    "trs_bag_pool_segments": (c_int32, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P]),
+    "trs_bag_combine": (c_int32, [_P, _I32, _I64, _I32, _F32, _I32, _P, _P]),
+    "trs_bag_expand_grad": (c_int32, [_P, _I32, _I32, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
 }
 
 _lib = None

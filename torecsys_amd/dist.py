@@ -44,6 +44,12 @@ all-to-all and the owner-side reduction of a batch onto the same stream, where t
 With a fused optimizer on the owner an early lookup reads rows that are one update behind (asynchronous-SGD semantics):
 refused unless ``prefetch_lookup(..., stale_ok=True)``.
 
+Multi-valued fields (``RowShardedListIndicesEmbedding``): a padded (B, L) list of ids pooled by sum / mean.  Pooling is
+linear, so the rows stay where they are: the sender routes its ids by owner (HIP: trs_bag_route_count / _place), every owner
+pools the rows it holds per (source rank, sample) into one fp32 partial row (trs_bag_pool_segments), the partial rows are
+exchanged and added up in rank order with one rounding (trs_bag_combine); backward all-gathers the (B, E) output gradient and
+expands it on the owner along the saved segments (trs_bag_expand_grad) into the owner-side reduction above.
+
 ``backend='nccl'`` is RCCL on ROCm (xGMI links); the same code runs on ``gloo`` with CPU tensors when a
 CPU ``ops`` object is injected (tests only -- the default ops are the HIP kernels and refuse CPU tensors).
 """
@@ -264,6 +270,67 @@ class HipOps:
                          padded: bool = False) -> torch.Tensor:
         rb = F_.row_buckets(ids.view(-1, 1), None, weight.shape[0], check=not padded)
         return F_.scatter_rows(rb, weight, g_rows=grad_rows.contiguous())
+
+    # ---- bag pooling over a row-sharded table (RowShardedListIndicesEmbedding; csrc/bag_shard.hip) ----
+    def bag_route(self, idx: torch.Tensor, num_rows: int, rows_per_rank: int, world: int):
+        """(B, L) global ids -> (counts (W, B) int32, seg_start (W*B + 1) int32, send_ids (B*L) int32): the LOCAL ids
+        grouped by owner, then sample, then list order; segment (w, b) = send_ids[seg_start[w*B + b] : seg_start[w*B + b + 1]].
+        ``send_ids`` has room for every lookup; the entries from seg_start[-1] on (ids outside [0, num_rows) are not sent and
+        raise the index flag) are unwritten."""
+        require_device(idx)
+        B, L = idx.shape
+        dev = idx.device
+        counts = torch.empty(world, B, dtype=torch.int32, device=dev)
+        send_ids = torch.empty(B * L, dtype=torch.int32, device=dev)
+        flag = F_._ErrFlag(dev)
+        call("trs_bag_route_count", ptr(idx), index_dtype_code(idx), B, L, num_rows, rows_per_rank, world, ptr(counts),
+             ptr(flag.t), stream_ptr())
+        seg_start = segment_starts(counts)
+        call("trs_bag_route_place", ptr(idx), index_dtype_code(idx), B, L, num_rows, rows_per_rank, world, ptr(seg_start),
+             ptr(send_ids), B * L, stream_ptr())
+        flag.check("sharded bag lookup")
+        return counts, seg_start, send_ids
+
+    def bag_pool_segments(self, weight: torch.Tensor, n_valid: int, ids: torch.Tensor, seg_start: torch.Tensor) -> torch.Tensor:
+        """(S, E) fp32: the rows ``ids[seg_start[s] : seg_start[s + 1]]`` of this rank's shard summed in list order; ids
+        outside [0, n_valid) read as zero rows and raise the index flag"""
+        require_device(weight, ids, seg_start)
+        S = seg_start.numel() - 1
+        V, E = weight.shape
+        out = torch.empty(S, E, dtype=torch.float32, device=weight.device)
+        flag = F_._ErrFlag(weight.device)
+        call("trs_bag_pool_segments", ptr(weight), min(V, n_valid), E, value_dtype_code(weight),
+             ptr(ids if ids.numel() else None), ids.numel(), ptr(seg_start), S, ptr(out), ptr(flag.t), stream_ptr())
+        flag.check("sharded bag lookup")
+        return out
+
+    def bag_combine(self, parts: torch.Tensor, scale: float, dtype: torch.dtype) -> torch.Tensor:
+        """(P, B, E) fp32 partial rows -> (B, E) of ``dtype``: summed over P in order, times ``scale``, rounded once"""
+        require_device(parts)
+        P, B, E = parts.shape
+        out = torch.empty(B, E, dtype=dtype, device=parts.device)
+        call("trs_bag_combine", ptr(parts), P, B, E, float(scale), value_dtype_code(out), ptr(out), stream_ptr())
+        return out
+
+    def bag_expand_grad(self, g_all: torch.Tensor, ids: torch.Tensor, seg_start: torch.Tensor, n_valid: int,
+                        pad_local_row: int):
+        """(S, E) output gradients -> one gradient row per lookup (n, E) and the ids of the owner-side reduction (n int32):
+        lookups of ``pad_local_row`` (-1: none) and of ids outside the shard carry a zero row and the id -1"""
+        require_device(g_all, ids, seg_start)
+        S, E = g_all.shape
+        n = ids.numel()
+        rows = torch.empty(n, E, dtype=g_all.dtype, device=g_all.device)
+        ids_bwd = torch.empty(n, dtype=torch.int32, device=g_all.device)
+        call("trs_bag_expand_grad", ptr(g_all), value_dtype_code(g_all), E, ptr(ids), n, ptr(seg_start), S, n_valid,
+             pad_local_row, ptr(rows), ptr(ids_bwd), stream_ptr())
+        return rows, ids_bwd
+
+
+def segment_starts(counts: torch.Tensor) -> torch.Tensor:
+    """exclusive scan of the flattened per-segment counts, one more entry than segments (int32)"""
+    out = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=counts.device)
+    torch.cumsum(counts.reshape(-1), 0, dtype=torch.int32, out=out[1:])
+    return out
 
 
 class _Accumulate:
@@ -1075,6 +1142,223 @@ class RowShardedMultiIndicesEmbedding(BaseInput):
         mine[: hi - lo] = self.embedding.weight[: hi - lo]
         dist.all_gather(parts, mine, group=self.group)
         return torch.cat(parts, 0)[: self.num_rows]
+
+    def full_state_dict(self):
+        return {'embedding.weight': self.full_weight()}
+
+
+# ---- bag pooling over a row-sharded table -------------------------------------------------------------------------------
+# bytes this rank SENT to other ranks in RowShardedListIndicesEmbedding steps: the (W, B) counts, the int32 local ids, the
+# fp32 partial rows (forward) and the all-gathered (B, E) output gradient (backward)
+bag_wire_bytes = {"counts": 0, "ids": 0, "partials": 0, "g": 0, "steps": 0}
+
+
+class _ShardedBagPool(Function):
+    """(local shard, local (B, L) batch of ids) -> (B, E) pooled rows.  Sum and mean are linear, so every owner pools the
+    rows it holds for each (source rank, sample) into one fp32 partial row and only those rows travel; the backward sends
+    the (B, E) output gradient to every owner once and expands it there along the saved segments."""
+
+    @staticmethod
+    def forward(ctx, weight, idx, mod):
+        ops, W, rank = mod.ops, mod.world, mod.rank
+        B, L = idx.shape
+        E = weight.shape[1]
+        dev = weight.device
+        n_valid = mod.row_range[1] - mod.row_range[0]
+        with _phase("bag route", dev):
+            counts, seg_start, send_ids = ops.bag_route(idx, mod.field_size, mod.rows_per_rank, W)
+        if W == 1:
+            ids, rseg = send_ids, seg_start        # no collective, nothing read on the host
+        else:
+            mod.check_equal_batch(B)
+            recv_counts = torch.empty_like(counts)
+            with _phase("bag count all-to-all", dev):
+                dist.all_to_all_single(recv_counts, counts, group=mod.group)
+            # the W per-owner totals, read once on the host: the split sizes of the id exchange
+            both = torch.stack([counts.sum(1), recv_counts.sum(1)])
+            if both.is_cuda:
+                host = torch.empty(both.shape, dtype=both.dtype, pin_memory=True)
+                host.copy_(both, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                ev.synchronize()
+            else:
+                host = both
+            send_splits, recv_splits = host[0].tolist(), host[1].tolist()
+            ids = torch.empty(sum(recv_splits), dtype=torch.int32, device=dev)
+            with _phase("bag id all-to-all", dev):
+                _all_to_all(ids, send_ids[:sum(send_splits)], recv_splits, send_splits, mod.group)
+            rseg = segment_starts(recv_counts)          # source-major: segment (p, b) of the ids rank p sent
+            bag_wire_bytes["counts"] += (W - 1) * B * 4
+            bag_wire_bytes["ids"] += (sum(send_splits) - send_splits[rank]) * 4
+            bag_wire_bytes["partials"] += (W - 1) * B * E * 4
+        with _phase("bag owner pool", dev):
+            parts = ops.bag_pool_segments(weight.detach(), n_valid, ids, rseg)          # (W*B, E) fp32
+        if W > 1:
+            got = torch.empty_like(parts)
+            with _phase("bag partial all-to-all", dev):
+                dist.all_to_all_single(got, parts, group=mod.group)      # slab p: what owner p pooled for this rank
+            parts = got
+        with _phase("bag combine", dev):
+            out = ops.bag_combine(parts.view(W, B, E), mod.scale(L), weight.dtype)
+        ctx.mod, ctx.L = mod, L
+        ctx.save_for_backward(weight, ids, rseg)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        mod = ctx.mod
+        ops, W = mod.ops, mod.world
+        weight, ids, rseg = ctx.saved_tensors
+        dev = weight.device
+        E = weight.shape[1]
+        lo, hi = mod.row_range
+        g = g.reshape(-1, E).to(weight.dtype)
+        g = g * (1.0 / ctx.L) if mod.pool == 'mean' else g.contiguous()      # as functional._BagPool.backward, on (B, E)
+        if W > 1:
+            g_all = torch.empty(W * g.shape[0], E, dtype=g.dtype, device=dev)
+            with _phase("bag gradient all-gather", dev):
+                if g.is_cuda:
+                    dist.all_gather_into_tensor(g_all, g, group=mod.group)
+                else:
+                    dist.all_gather(list(g_all.chunk(W)), g, group=mod.group)
+            bag_wire_bytes["g"] += (W - 1) * g.numel() * g.element_size()
+        else:
+            g_all = g
+        bag_wire_bytes["steps"] += 1
+        pad = mod.padding_idx
+        pad_local = pad - lo if pad is not None and lo <= pad < hi else -1
+        if ids.numel() == 0:                   # this rank received no lookups: nothing to reduce
+            if mod.fused_optimizer is not None:
+                return None, None, None
+            if weight.shape[0] <= mod.dense_grad_max_rows:
+                return torch.zeros_like(weight), None, None
+            return torch.sparse_coo_tensor(torch.empty(1, 0, dtype=torch.long, device=dev),
+                                           torch.empty(0, E, dtype=weight.dtype, device=dev), size=weight.shape), None, None
+        with _phase("bag expand gradient", dev):
+            rows, ids_bwd = ops.bag_expand_grad(g_all, ids, rseg, hi - lo, pad_local)
+        with _phase("owner reduce / update", dev):
+            # padding lookups arrive as -1: the bucket build leaves them out (filed under one row they would serialise it)
+            gw = _ShardedLookup._owner_reduce(mod, weight, ids_bwd, rows, True)
+        return gw, None, None
+
+
+class RowShardedListIndicesEmbedding(BaseInput):
+    """``inputs.ListIndicesEmbedding`` (``use_attn=False``, sum / mean pooling) with the table row-sharded over the process
+    group: a padded (B, L) list of global ids -> (B, 1, E) named ('B','N','E').  Every list position counts, the padding row
+    is read like any other; ``padding_idx`` names the GLOBAL row that receives no gradient.  ``embedding.weight`` holds this
+    rank's rows of ``shard_ranges(field_size, world)``.
+
+    The rows never travel: each owner pools the rows it holds for every (source rank, sample) into one fp32 partial row
+    (csrc/bag_shard.hip) and only those cross the links -- ``7/8*B*L*E*s`` bytes of rows per rank become ``7*B*E*4`` of
+    partials at world 8, a ratio of ``L*s / (W*4)``; the backward all-gathers the (B, E) output gradient (``L / W``).  The
+    partials are summed in rank order and rounded once, so the result differs from the unsharded lookup only by the order
+    of an fp32 sum.  The gradient ends in the owner-side reduction of the sharded one-id lookup: a dense shard gradient, a
+    sparse COO gradient above ``dense_grad_max_rows``, or a fused optimizer step (``set_fused_optimizer``).
+
+    Limits: ``max_pooling`` (not linear) and ``none`` / attention (they need the rows) are refused; every rank passes the
+    same local batch size (checked once per distinct size); the partials are fp32 on the wire; the id exchange reads its W
+    split sizes on the host once per step (a group of one rank takes no collective and no host read)."""
+
+    _POOL = {'avg_pooling': 'mean', 'mean': 'mean', 'sum': 'sum'}
+
+    def __init__(self, embed_size: int, field_size: int, padding_idx: Optional[int] = 0,
+                 output_method: str = 'avg_pooling', dtype: torch.dtype = torch.float32, device='cpu',
+                 process_group=None, ops=None, dense_grad_max_rows: int = DENSE_GRAD_MAX_ROWS, use_attn: bool = False):
+        super().__init__()
+        if use_attn:
+            raise NotImplementedError('RowShardedListIndicesEmbedding: attention pooling needs the looked-up rows of a '
+                                      'sample on one rank; only their pooled partial sums travel here')
+        if output_method == 'max_pooling':
+            raise NotImplementedError('RowShardedListIndicesEmbedding: max_pooling is not linear, so per-owner partial '
+                                      'results cannot be added up; use avg_pooling / mean / sum')
+        if output_method == 'none':
+            raise NotImplementedError("RowShardedListIndicesEmbedding: output_method='none' needs every looked-up row on "
+                                      "the requesting rank; use RowShardedMultiIndicesEmbedding for un-pooled lookups")
+        if output_method not in self._POOL:
+            raise ValueError('output_method only allows ["avg_pooling", "mean", "sum"].')
+        if not dist.is_initialized():
+            raise RuntimeError("RowShardedListIndicesEmbedding needs torch.distributed to be initialised")
+        self.group = process_group
+        self.world = dist.get_world_size(process_group)
+        self.rank = dist.get_rank(process_group)
+        if self.world > 64:
+            raise ValueError("RowShardedListIndicesEmbedding: at most 64 ranks (one wave lane per owner in the route kernel)")
+        self.ops = ops if ops is not None else HipOps()
+        self.field_size = int(field_size)
+        self.embed_size = int(embed_size)
+        self.length = self.embed_size
+        self.rows_per_rank, ranges = shard_ranges(self.field_size, self.world)
+        self.row_range = ranges[self.rank]
+        lo, hi = self.row_range
+        self.embedding = nn.Embedding(max(hi - lo, 1), embed_size, device=device, dtype=dtype)
+        if padding_idx is not None:
+            if not -self.field_size <= padding_idx < self.field_size:
+                raise ValueError('padding_idx must be within the table')
+            padding_idx = padding_idx % self.field_size
+            if lo <= padding_idx < hi:
+                with torch.no_grad():
+                    self.embedding.weight[padding_idx - lo].zero_()       # as nn.Embedding(padding_idx=...) starts out
+        self.padding_idx = padding_idx
+        self.output_method = output_method
+        self.pool = self._POOL[output_method]
+        # what _ShardedLookup._owner_reduce reads
+        self.dense_grad_max_rows = int(dense_grad_max_rows)
+        self.dense_index_max_rows = int(dense_grad_max_rows)
+        self._batch_sizes = set()
+        self._scales = {}
+
+    def scale(self, L: int) -> float:
+        """1.f / (float)L in fp32 arithmetic, the expression of csrc/bag.hip (mean), or 1"""
+        if self.pool != 'mean':
+            return 1.0
+        s_ = self._scales.get(L)
+        if s_ is None:
+            s_ = self._scales[L] = float(torch.ones((), dtype=torch.float32) / torch.tensor(float(L), dtype=torch.float32))
+        return s_
+
+    def check_equal_batch(self, B: int) -> None:
+        """The count and partial exchanges have equal splits of B per peer: every rank must pass the same local batch size.
+        Checked ONCE per distinct size (one small all-reduce the first time a size is seen), never per step."""
+        if B in self._batch_sizes:
+            return
+        t = torch.tensor([B, -B], dtype=torch.int64, device=self.embedding.weight.device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        hi, lo = int(t[0]), -int(t[1])
+        if hi != lo:
+            raise RuntimeError(f"RowShardedListIndicesEmbedding: every rank must pass the same local batch size "
+                               f"(this step: between {lo} and {hi})")
+        self._batch_sizes.add(B)
+
+    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+        idx = inputs.rename(None) if inputs.has_names() else inputs
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError(f'inputs must be (B, L) with L >= 1, got {tuple(idx.shape)}')
+        if idx.shape[1] > 65535:
+            raise ValueError(f'list length {idx.shape[1]} exceeds 65535')
+        if idx.dtype not in (torch.int64, torch.int32):
+            idx = idx.long()
+        out = _ShardedBagPool.apply(self.embedding.weight, idx.contiguous(), self)
+        return out.unsqueeze(1).refine_names('B', 'N', 'E')
+
+    @torch.no_grad()
+    def load_full_weight(self, full: torch.Tensor):
+        lo, hi = self.row_range
+        self.embedding.weight[: hi - lo].copy_(full[lo:hi])
+
+    @torch.no_grad()
+    def full_weight(self) -> torch.Tensor:
+        lo, hi = self.row_range
+        w = self.embedding.weight
+        parts = [torch.empty(self.rows_per_rank, self.embed_size, dtype=w.dtype, device=w.device) for _ in range(self.world)]
+        mine = torch.zeros_like(parts[0])
+        mine[: hi - lo] = w[: hi - lo]
+        dist.all_gather(parts, mine, group=self.group)
+        return torch.cat(parts, 0)[: self.field_size]
 
     def full_state_dict(self):
         return {'embedding.weight': self.full_weight()}
