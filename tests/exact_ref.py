@@ -9,6 +9,9 @@ is then ``expect(ref, dtype)`` -- the float64 value rounded once -- and a missin
 
 ``assert_exact_domain`` is the guard that makes that a fair demand; tests/test_exact_ref_host.py runs it over every case
 list below, and tests/test_gpu_exact_mfma.py takes its cases from the same lists.  Nothing here imports torecsys_amd.
+
+tests/exact_ipn_ref.py builds on ``gen``, ``ints``, ``expect``, ``assert_exact_domain``, ``mismatch`` and ``pair_index``
+from here for the inner-product network kernels of csrc/pair.hip (tests/test_exact_ipn_host.py, tests/test_gpu_exact_ipn.py).
 """
 import functools
 import os
