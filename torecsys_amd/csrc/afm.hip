@@ -971,8 +971,11 @@ extern "C" int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const 
   if (dtype == TRS_BF16 && (E == 32 || E == 64 || E == 128) && A % 32 == 0 && A <= 128 &&
       (A / 16) * (E / 32) <= 12 &&
       afm_bwd_mfma_lds(N, E, A) <= 160 * 1024 && aligned16(x) && aligned16(W1)) {
+    // the packer keeps the fields of a tile in a 64-bit mask: N > 64 goes to the rounds without asking it (the shape is
+    // admitted -- N = 65, E = 32, A = 32 needs 109 KB -- and its tiles would not fit AFM_TILE_MAX anyway)
+    static const AfmTiles no_tiles = {};
     int T = 0;
-    const AfmTiles* packed = afm_packed_tiles(N, &T);
+    const AfmTiles* packed = N <= 64 ? afm_packed_tiles(N, &T) : &no_tiles;
     if (N <= 32) T = 0;  // a round IS a maximal tile there
     // (four waves = one per SIMD: A = 64, E = 64 already holds 388 registers per wave -- W1 / W1^T fragments, the dW1
     // accumulators, both x rows of the tile -- so a second wave per SIMD would spill; measured with six: 536 B of scratch)
