@@ -455,6 +455,30 @@ int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_layers, con
                            const void* const* weights, const void* const* masks, void* const* gz, float* const* gbias,
                            void* gx, const void* mask_in, float* gbias_in, int32_t dtype, int32_t family,
                            void* workspace, size_t ws_bytes, trs_stream_t stream);
+/* The same backward carrying the OUTPUT layer's weight gradient (a deep branch's 400 -> 1 logit layer: a product of its
+ * own is two dependent launches for one read of the last hidden activation, which this kernel can stream beside its
+ * GEMMs while the gy tile it needs lies in LDS).  Tile kernel only (family TILE or MIXED), bf16, num_layers >= 2.
+ *   live: the real output columns, 1 <= live <= 3 and <= widths[num_layers] (the layer may run padded to 8 columns);
+ *   gy_stride: widths[num_layers] -- gy as trs_mlp_fused_bwd_data takes it -- or, for live < 8, live: gy is then the
+ *     contiguous (rows, live) gradient of the live columns alone, read by elements where it lies (no padded copy);
+ *   h_last: (rows, h_stride) the last hidden activation (hidden[num_layers-2] of the forward), h_stride % 8 == 0 and
+ *     >= pad32(widths[num_layers-1]), 16-byte aligned;
+ *   wl_part: caller-owned fp32 scratch of trs_mlp_fused_bwd_wlast_part_bytes bytes, [workgroup][live][pad32(widths[
+ *     num_layers-1])] partial rows, written; gw_last: (live, pad32(widths[num_layers-1])) fp32, written: row j =
+ *     sum over rows of gy[row][j] * h_last[row], summed in a fixed order (no atomics) by the entry's own reduce launch.
+ * Everything else as trs_mlp_fused_bwd_data, bit for bit.  trs_mlp_fused_bwd_wlast_part_bytes returns 0 where the
+ * kernel does not carry it (fp32, the row-owner family, num_layers < 2, live outside 1..3, num_layers + 1 + live > 8
+ * reduce entries, or 128 * act_stride + 16 KB + (num_layers + 1 + live) * 2 KB of LDS above 160 KB): the caller keeps
+ * trs_mlp_fused_bwd_data and trs_wgrad_rows.  The entry returns TRS_ESHAPE for such a call, TRS_EWORKSPACE for a
+ * wl_part_bytes below the query's answer, before anything is launched.                                                */
+size_t trs_mlp_fused_bwd_wlast_part_bytes(int32_t num_layers, const int32_t* widths, int64_t rows, int32_t dtype,
+                                          int32_t family, int32_t live);
+int trs_mlp_fused_bwd_data_wlast(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
+                                 const int32_t* widths, const void* const* weights, const void* const* masks,
+                                 void* const* gz, float* const* gbias, void* gx, const void* mask_in, float* gbias_in,
+                                 const void* h_last, int32_t h_stride, int32_t live, float* wl_part,
+                                 size_t wl_part_bytes, float* gw_last, int32_t dtype, int32_t family, void* workspace,
+                                 size_t ws_bytes, trs_stream_t stream);
 
 /* dst (rows, c_out) = [src (rows, c_in) | zeros], bf16: the gradient of the first c_in columns of a padded output (the
  * logit column of a deep branch whose last layer runs at 8 columns) in one launch.                                   */
@@ -601,7 +625,9 @@ int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t ldx, int64
  * aligned operands and partials; every job is checked before anything is launched.  trs_wgrad_rows_many_map (host
  * only) tells where workgroup ``block`` works: out = {job, row range, output block, first row, end row}, returns the
  * grid size (0: not taken / no such block).  trs_wgrad_finish_many = trs_wgrad_finish for every job (one S, one dtype;
- * gb[k] / gb_f32[k] both or neither) in one launch.                                                                  */
+ * gb[k] / gb_f32[k] both or neither) in one launch.  A job WITHOUT a product, part[k] = gw[k] = NULL, only casts:
+ * gb[k][c] = gb_f32[k][c] for c < out_cols[k] (R, Cc, out_rows of the job are not read) -- a gradient that arrives
+ * summed in fp32, such as a row of trs_mlp_fused_bwd_data_wlast's gw_last, rides in the finish of the other layers.  */
 int32_t trs_wgrad_rows_many_splits(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
                                    const int32_t* ldx, int64_t rows);
 int32_t trs_wgrad_rows_many_map(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,

@@ -305,6 +305,11 @@ struct WgradFinishArgs {
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_finish_many_kernel(WgradFinishArgs a) {
   const WgradFinishJob& j = a.job[blockIdx.z];
+  if (j.part == nullptr) {      // a job without a product: out_cols fp32 values cast (a gradient that arrives summed)
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.y == 0 && c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
+    return;
+  }
   wgrad_finish_body<T>(j.part, a.S, j.R, j.Cc, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb);
 }
 
@@ -770,6 +775,13 @@ extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, i
   a.S = S;
   int max_rows = 0, max_cols = 0;
   for (int k = 0; k < n_jobs; ++k) {
+    if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
+      TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
+                  "wgrad_finish_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
+      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k]};
+      max_cols = std::max(max_cols, out_cols[k]);
+      continue;
+    }
     TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
                 TRS_EINVAL, "wgrad_finish_many: bad size (job %d)", k);
     TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_many: NULL pointer (job %d)", k);

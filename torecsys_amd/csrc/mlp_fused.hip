@@ -32,6 +32,7 @@ constexpr int MF_WAVES = 8;
 constexpr int MF_MINW = 2;            // waves per SIMD the kernels are compiled for (2 = one 8-wave workgroup per CU)
 constexpr int MF_MAXP = 2;            // 32-column pairs per wave: widths up to 8 * 2 * 32 = 512
 constexpr int MF_MAXL = 8;
+constexpr int MF_MAXLIVE = 3;         // output columns whose weight-gradient rows the backward can carry (2 KB of LDS each)
 constexpr int MF_MASK_TILE = 64 * MF_WAVES * 16;   // mask bytes per 128-row pass and layer: 16 per lane (see mlp_fused_fwd_kernel)
 
 // column of D-row slot m (= 4*q + i) of 16-column tile mt: the two tiles of a pair interleave 4-column groups, so that
@@ -142,6 +143,12 @@ struct MlpArgs {
                       // the backward's last step: written by the forward, applied by the backward; may be null
   float* colsum_in;   // backward, with mask_in: partial column sums of the masked input gradient, [gridDim.x][step N]
   int ro_masks;       // backward: the sign bits are in the ROW-OWNER kernels' layout (mlp_ro.hpp), see mlp_fused_bwd_kernel
+  // backward, the output layer's weight gradient riding along (trs_mlp_fused_bwd_data_wlast; live = 0: not asked for)
+  const void* h_last; // (rows x h_stride) bf16: the last hidden activation, step[0].N columns of it are read
+  int h_stride;
+  int live;           // real output columns (<= MF_MAXLIVE): row j of the gradient = sum over rows of gy[row][j] * h_last[row]
+  float* wl_part;     // [gridDim.x][live][step[0].N] per-workgroup sums
+  int in_narrow;      // > 0: ``in`` is a contiguous (rows x in_narrow) tensor with in_narrow < 8 columns, read by elements
 };
 
 // tiles of the step owned by this wave: wide outputs split the 32-column pairs over the 8 waves (all 8 row tiles
@@ -369,6 +376,28 @@ __device__ __forceinline__ void mlp_load_in(char* act, int act_str, const void* 
   }
 }
 
+// the same for a contiguous (rows x cin) input with cin < 8 columns (the logit column's gradient where it lies): element
+// loads into the first 16-byte chunk of a row, zeros behind it
+__device__ __forceinline__ void mlp_load_in_narrow(char* act, int act_str, const void* in, int cin, int ncols, int64_t row0,
+                                                   int64_t rows) {
+  const int cpr = ncols >> 3;
+  const uint16_t* src = reinterpret_cast<const uint16_t*>(in);
+  for (int t = threadIdx.x; t < MF_ROWS * cpr; t += blockDim.x) {
+    const int r = t / cpr, c = t - r * cpr;
+    // every load is issued, on a clamped index, and the ones not wanted are dropped afterwards: a branch per element puts a
+    // wait behind every load
+    const bool ok = c == 0 && row0 + r < rows;
+    const uint16_t* p = src + (ok ? (row0 + r) * cin : 0);
+    unsigned e[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) e[j] = p[j < cin ? j : cin - 1];
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 7; ++j) w[j >> 1] |= (ok && j < cin ? e[j] : 0u) << (16 * (j & 1));
+    *reinterpret_cast<uint4*>(act + r * act_str + c * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 // workgroup barrier for the LDS hand-offs inside a pass: __syncthreads() also waits vmcnt(0), i.e. for the global stores
 // in flight, which nothing here depends on
@@ -576,8 +605,10 @@ __global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_rows_gemm_kernel(R
 // ------------------------------------------------------------------------------------------------ backward (data)
 // step s works on layer l = L-1-s: input = d(pre-activation of layer l) (rows x N_l) in LDS, output = d(input of layer l)
 // = d(output of layer l-1), masked by layer l-1's ReLU mask into d(pre-activation of layer l-1).
-template <bool RO_MASKS>
-__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(MlpArgs a) {
+// WLAST: the output layer's weight gradient rides along (MlpArgs::h_last ...); kernels of their own
+// (mlp_fused_bwd_wlast_kernel), so that the kernels of every other caller stay what they were.
+template <bool RO_MASKS, bool WLAST>
+__device__ __forceinline__ void mlp_fused_bwd_body(const MlpArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act = smem;
   float* scratch = reinterpret_cast<float*>(act + MF_ROWS * a.act_str);              // [8 row slices][512]
@@ -592,23 +623,95 @@ __global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(M
   // sums have been folded, between two extra barriers.
   unsigned short* mstage = reinterpret_cast<unsigned short*>(scratch);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, r = lane & 15;
-  for (int i = threadIdx.x; i < (a.nsteps + 1) * 512; i += blockDim.x) csum[i] = 0.f;
+  float* wsum = csum + (a.nsteps + 1) * 512;                                          // WLAST: [live][512] the output layer's dW rows
+  const int live = WLAST ? a.live : 0;
+  for (int i = threadIdx.x; i < (a.nsteps + 1 + live) * 512; i += blockDim.x) csum[i] = 0.f;
   const int64_t ntiles = (a.rows + MF_ROWS - 1) / MF_ROWS;
+  const int Kh = a.step[0].N;                                                         // padded width of the last hidden layer
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t row0 = tile * MF_ROWS;
-    mlp_load_in(act, a.act_str, a.in, a.in_stride, a.step[0].K, row0, a.rows);
+    // The output layer's weight gradient: row j = sum over the rows of gy[row][j] * h_last[row].  Wave w takes the 16 rows
+    // from 16 w of the tile, a lane 8 columns of them (the lanes past the last chunk repeat it and are dropped at the
+    // fold).  The rows of h_last are requested here, while no accumulator is alive, and multiplied once the gy tile lies in
+    // LDS; the 8 slices meet in ``scratch`` as the column sums do.  Rows past the end are read as the last row (no branch
+    // per load) and meet the zeros that the tile load puts behind the last row of gy.
+    uint4 hv[WLAST ? MF_ROWS / 8 : 1];
+    // (this part's addresses are worked out per tile from opaque copies of the lane / wave numbers: as kernel invariants
+    // they would be held in registers across the GEMMs, which have none to spare)
+    int hl = lane, hw = wave;
+    if constexpr (WLAST) {
+      asm volatile("" : "+v"(hl));
+      hw = __builtin_amdgcn_readfirstlane(hl ^ lane ^ wave);
+      const int64_t hr0 = row0 + hw * (MF_ROWS / 8);
+      const int hleft = (int)std::min<int64_t>(a.rows - hr0, MF_ROWS / 8);      // rows of this slice inside the tensor (may be <= 0)
+      const bf16_t* hp = reinterpret_cast<const bf16_t*>(a.h_last) + std::min<int64_t>(hr0, a.rows - 1) * a.h_stride +
+                         std::min(hl, (Kh >> 3) - 1) * 8;
+      // (one pointer walked down the rows: sixteen row addresses written out are loop invariants that the compiler keeps
+      // in registers across the GEMMs)
+#pragma unroll
+      for (int rr = 0; rr < MF_ROWS / 8; ++rr) {
+        hv[rr] = *reinterpret_cast<const uint4*>(hp);
+        if (rr + 1 < hleft) hp += a.h_stride;
+      }
+    }
+    if (WLAST && a.in_narrow > 0) mlp_load_in_narrow(act, a.act_str, a.in, a.in_narrow, a.step[0].K, row0, a.rows);
+    else mlp_load_in(act, a.act_str, a.in, a.in_stride, a.step[0].K, row0, a.rows);
     MF_BAR();
+    if constexpr (WLAST) {
+      // lane r of the wave fetches gy[16 w + r][j]; the multiply reads it from there as a scalar
+      unsigned gbits[MF_MAXLIVE];
+#pragma unroll
+      for (int j = 0; j < MF_MAXLIVE; ++j)
+        gbits[j] = j < live ? *reinterpret_cast<const uint16_t*>(act + (hw * (MF_ROWS / 8) + (hl & 15)) * a.act_str + 2 * j) : 0u;
+      float wacc[MF_MAXLIVE][8];
+#pragma unroll
+      for (int j = 0; j < MF_MAXLIVE; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) wacc[j][e] = 0.f;
+#pragma unroll
+      for (int rr = 0; rr < MF_ROWS / 8; ++rr) {
+        float f[8];
+        Vec16<bf16_t>::unpack(hv[rr], f);
+#pragma unroll
+        for (int j = 0; j < MF_MAXLIVE; ++j)
+          if (j < live) {
+            const float g = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)gbits[j], rr) << 16);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) wacc[j][e] = __builtin_fmaf(g, f[e], wacc[j][e]);
+          }
+      }
+      const bool hon = hl < (Kh >> 3);
+#pragma unroll
+      for (int j = 0; j < MF_MAXLIVE; ++j)
+        if (j < live) {
+          if (j > 0) MF_BAR();                       // the previous row's slices have been read
+          if (hon) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) scratch[hw * 512 + hl * 8 + e] = wacc[j][e];
+          }
+          MF_BAR();
+          if (hw * 64 + hl < Kh) {
+            float t = 0.f;
+#pragma unroll
+            for (int sl = 0; sl < 8; ++sl) t += scratch[sl * 512 + hw * 64 + hl];
+            wsum[j * 512 + hw * 64 + hl] += t;
+          }
+        }
+      MF_BAR();                                      // step 0 writes its column-sum slices to ``scratch``
+    }
     for (int s = 0; s < a.nsteps; ++s) {
       const MlpStep st = a.step[s];
       const MlpShare sh = mlp_share(st.N, wave);
       // the ReLU sign bits of this lane's outputs (the forward's vector for this pass and thread), in flight during the GEMM
       uint4 mraw = make_uint4(0, 0, 0, 0);
+      int tid = threadIdx.x;
+      if constexpr (WLAST) asm volatile("" : "+v"(tid));      // (as above: no thread offsets kept across the GEMMs)
       if (st.mask != nullptr) {
         if constexpr (RO_MASKS)      // piece threadIdx.x / 128 (= chunk group), 16 bytes of this tile's 2 KB of it
-          mraw = *reinterpret_cast<const uint4*>(st.mask + (tile >> 1) * 16384 + (threadIdx.x >> 7) * 4096 + (tile & 1) * 2048 +
-                                                 (threadIdx.x & 127) * 16);
+          mraw = *reinterpret_cast<const uint4*>(st.mask + (tile >> 1) * 16384 + (tid >> 7) * 4096 + (tile & 1) * 2048 +
+                                                 (tid & 127) * 16);
         else
-          mraw = *(reinterpret_cast<const uint4*>(st.mask + tile * MF_MASK_TILE) + threadIdx.x);
+          mraw = *(reinterpret_cast<const uint4*>(st.mask + tile * MF_MASK_TILE) + tid);
       }
       const unsigned mword[4] = {mraw.x, mraw.y, mraw.z, mraw.w};
       mf_f32x4 acc[MF_MT][2 * MF_MAXP];
@@ -650,7 +753,7 @@ __global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(M
       }
       if (RO_MASKS && st.mask != nullptr) {
         MF_BAR();                                                        // the partial sums have been read
-        reinterpret_cast<uint4*>(mstage)[threadIdx.x] = mraw;
+        reinterpret_cast<uint4*>(mstage)[tid] = mraw;
         MF_BAR();
       }
       const int lrow = sh.mt0 * 16 + r;          // item addresses as in the forward
@@ -731,6 +834,16 @@ __global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(M
       a.step[s].colsum[(size_t)blockIdx.x * a.step[s].K + threadIdx.x] = csum[s * 512 + threadIdx.x];
   if (a.colsum_in != nullptr && threadIdx.x < a.step[a.nsteps - 1].N)
     a.colsum_in[(size_t)blockIdx.x * a.step[a.nsteps - 1].N + threadIdx.x] = csum[a.nsteps * 512 + threadIdx.x];
+  for (int j = 0; j < live; ++j)
+    if (threadIdx.x < Kh) a.wl_part[((size_t)blockIdx.x * live + j) * Kh + threadIdx.x] = wsum[j * 512 + threadIdx.x];
+}
+template <bool RO_MASKS>
+__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_kernel(MlpArgs a) {
+  mlp_fused_bwd_body<RO_MASKS, false>(a);
+}
+template <bool RO_MASKS>
+__global__ __launch_bounds__(64 * MF_WAVES, MF_MINW) void mlp_fused_bwd_wlast_kernel(MlpArgs a) {
+  mlp_fused_bwd_body<RO_MASKS, true>(a);
 }
 
 // out[i] = sum_p part[p][i]
@@ -739,17 +852,18 @@ struct MlpColsumArgs {
   const float* part[MF_MAXL];
   float* out[MF_MAXL];
   int n[MF_MAXL];
+  int stride[MF_MAXL];      // floats between a column's partials (n, or live * n for a row of the output layer's dW)
   int nparts;
 };
 __global__ __launch_bounds__(1024) void mlp_colsum_reduce_many_kernel(MlpColsumArgs a) {
   __shared__ float red[16][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int n = a.n[blockIdx.y];
+  const int n = a.n[blockIdx.y], stride = a.stride[blockIdx.y];
   const float* part = a.part[blockIdx.y];
   const int i = blockIdx.x * 64 + tx;
   float s = 0.f;
   if (i < n)
-    for (int p = ty; p < a.nparts; p += 16) s += part[(size_t)p * n + i];
+    for (int p = ty; p < a.nparts; p += 16) s += part[(size_t)p * stride + i];
   red[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && i < n) {
@@ -942,10 +1056,24 @@ extern "C" int trs_mlp_fused_fwd(const void* x, int64_t rows, int32_t num_layers
 
 /* gz[l] (l = 0..L-2): d(pre-activation of layer l), (rows x pad32(widths[l+1])) bf16 -- d(pre-activation) of the last
  * layer is gy itself.  gbias[l] (l = 0..L-1): pad32(widths[l+1]) fp32 each, written.  gx: (rows x widths[0]). */
-extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
-                                      const void* const* weights, const void* const* masks, void* const* gz,
-                                      float* const* gbias, void* gx, const void* mask_in, float* gbias_in, int32_t dtype,
-                                      int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+namespace trs {
+// the output layer's weight gradient carried by the tile backward (trs_mlp_fused_bwd_data_wlast), null: not asked for
+struct MlpWlast {
+  const void* h_last;
+  int h_stride, live, gy_stride;
+  float* part;      // [grid][live][pad32(widths[L-1])]
+  float* gw;        // [live][pad32(widths[L-1])] fp32, written
+};
+static size_t mlp_bwd_lds(int L, const int32_t* widths, int live) {
+  return (size_t)MF_ROWS * mlp_act_str(L, widths) + 8 * 512 * 4 + (size_t)(L + 1 + live) * 512 * 4;
+}
+static int mlp_bwd_grid(int64_t rows) { return (int)std::min<int64_t>((rows + MF_ROWS - 1) / MF_ROWS, MF_GRID); }
+}  // namespace trs
+
+static int mlp_fused_bwd_impl(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
+                              const void* const* weights, const void* const* masks, void* const* gz,
+                              float* const* gbias, void* gx, const void* mask_in, float* gbias_in, int32_t dtype,
+                              int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream, const MlpWlast* wl) {
   hipStream_t s = (hipStream_t)stream;
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "mlp_fused_bwd_data: bf16 only");
   TRS_REQUIRE(trs_mlp_fused_supported(num_layers, widths), TRS_ESHAPE, "mlp_fused_bwd_data: unsupported layer widths");
@@ -974,6 +1102,8 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
   if (rows == 0) {
     for (int l = 0; l < L; ++l)
       if (int rc = zero_bytes(gbias[l], (size_t)pad32(widths[l + 1]) * 4, s)) return rc;
+    if (wl)
+      if (int rc = zero_bytes(wl->gw, (size_t)wl->live * pad32(widths[L - 1]) * 4, s)) return rc;
     if (gbias_in) return zero_bytes(gbias_in, (size_t)pad32(widths[0]) * 4, s);
     return TRS_OK;
   }
@@ -987,7 +1117,7 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
     for (int i = 0; i < rc.count; ++i) {
       cs.part[i] = rc.part[i];
       cs.out[i] = rc.out[i];
-      cs.n[i] = rc.n[i];
+      cs.n[i] = cs.stride[i] = rc.n[i];
       kmax = std::max(kmax, rc.n[i]);
     }
     hipLaunchKernelGGL(mlp_colsum_reduce_many_kernel, dim3((kmax + 63) / 64, rc.count), dim3(1024), 0, s, cs);
@@ -1000,8 +1130,12 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
   a.rows = rows;
   a.nbias = 0;
   a.act_str = mlp_act_str(L, widths);
-  const int64_t ntiles = (rows + MF_ROWS - 1) / MF_ROWS;
-  const int grid = (int)std::min<int64_t>(ntiles, MF_GRID);
+  const int grid = mlp_bwd_grid(rows);
+  a.h_last = wl ? wl->h_last : nullptr;
+  a.h_stride = wl ? wl->h_stride : 0;
+  a.live = wl ? wl->live : 0;
+  a.wl_part = wl ? wl->part : nullptr;
+  a.in_narrow = wl && wl->gy_stride != widths[L] ? wl->gy_stride : 0;
   char* wsp = (char*)workspace;
   float* part_base = (float*)(wsp + mlp_frag_bytes(L, widths));
   size_t woff = 0, poff = 0;
@@ -1027,19 +1161,19 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
   a.mask_in = nullptr;
   a.colsum_in = mask_in != nullptr ? part_base + poff : nullptr;      // (the workspace counts widths[0] as well)
   a.ro_masks = family == TRS_MLP_FAMILY_MIXED ? 1 : 0;
-  const size_t lds = (size_t)MF_ROWS * a.act_str + 8 * 512 * 4 + (size_t)(L + 1) * 512 * 4;
+  const size_t lds = mlp_bwd_lds(L, widths, a.live);
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)mlp_fused_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)mlp_fused_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-      return check_launch("mlp_fused_bwd_data: LDS attribute");
+    for (const void* k : {(const void*)mlp_fused_bwd_kernel<false>, (const void*)mlp_fused_bwd_kernel<true>,
+                          (const void*)mlp_fused_bwd_wlast_kernel<false>, (const void*)mlp_fused_bwd_wlast_kernel<true>})
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        return check_launch("mlp_fused_bwd_data: LDS attribute");
     attr = true;
   }
   hipLaunchKernelGGL(mlp_prepack_many_kernel, dim3(pk_blocks, L), dim3(256), 0, s, pk);
-  if (a.ro_masks) hipLaunchKernelGGL(mlp_fused_bwd_kernel<true>, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
-  else hipLaunchKernelGGL(mlp_fused_bwd_kernel<false>, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
+  auto* kern = a.ro_masks ? (wl ? mlp_fused_bwd_wlast_kernel<true> : mlp_fused_bwd_kernel<true>)
+                          : (wl ? mlp_fused_bwd_wlast_kernel<false> : mlp_fused_bwd_kernel<false>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
   MlpColsumArgs cs;
   cs.nparts = grid;
   int kmax = 0;
@@ -1047,19 +1181,74 @@ extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_
     const int l = L - 1 - sidx;
     cs.part[sidx] = a.step[sidx].colsum;
     cs.out[sidx] = gbias[l];
-    cs.n[sidx] = a.step[sidx].K;
+    cs.n[sidx] = cs.stride[sidx] = a.step[sidx].K;
     kmax = std::max(kmax, a.step[sidx].K);
   }
   int nsum = L;
   if (a.colsum_in != nullptr) {
     cs.part[L] = a.colsum_in;
     cs.out[L] = gbias_in;
-    cs.n[L] = pad32(widths[0]);
+    cs.n[L] = cs.stride[L] = pad32(widths[0]);
     kmax = std::max(kmax, cs.n[L]);
     nsum = L + 1;
   }
+  for (int j = 0; j < a.live; ++j, ++nsum) {      // the rows of the output layer's dW: the same fold over the workgroups
+    const int Kh = pad32(widths[L - 1]);
+    cs.part[nsum] = wl->part + (size_t)j * Kh;
+    cs.out[nsum] = wl->gw + (size_t)j * Kh;
+    cs.n[nsum] = Kh;
+    cs.stride[nsum] = a.live * Kh;
+    kmax = std::max(kmax, Kh);
+  }
   hipLaunchKernelGGL(mlp_colsum_reduce_many_kernel, dim3((kmax + 63) / 64, nsum), dim3(1024), 0, s, cs);
   return check_launch("mlp_fused_bwd_data");
+}
+
+extern "C" int trs_mlp_fused_bwd_data(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
+                                      const void* const* weights, const void* const* masks, void* const* gz,
+                                      float* const* gbias, void* gx, const void* mask_in, float* gbias_in, int32_t dtype,
+                                      int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  return mlp_fused_bwd_impl(gy, rows, num_layers, widths, weights, masks, gz, gbias, gx, mask_in, gbias_in, dtype, family,
+                            workspace, ws_bytes, stream, nullptr);
+}
+
+/* bytes of the per-workgroup partial buffer when the tile backward can carry the output layer's weight gradient, 0 when it
+ * cannot (the caller keeps trs_mlp_fused_bwd_data and the product of its own) */
+extern "C" size_t trs_mlp_fused_bwd_wlast_part_bytes(int32_t num_layers, const int32_t* widths, int64_t rows, int32_t dtype,
+                                                     int32_t family, int32_t live) {
+  const int L = num_layers;
+  if (dtype != TRS_BF16 || rows <= 0 || L < 2 || !mlp_fused_covers(L, widths)) return 0;
+  if (family != TRS_MLP_FAMILY_TILE && family != TRS_MLP_FAMILY_MIXED) return 0;      // the row-owner backward does not carry it
+  if (live < 1 || live > MF_MAXLIVE || live > widths[L]) return 0;
+  if (L + 1 + live > MF_MAXL) return 0;                                               // entries of the one reduce launch
+  if (mlp_bwd_lds(L, widths, live) > 160 * 1024) return 0;
+  return (size_t)mlp_bwd_grid(rows) * live * pad32(widths[L - 1]) * 4;
+}
+
+extern "C" int trs_mlp_fused_bwd_data_wlast(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
+                                            const int32_t* widths, const void* const* weights, const void* const* masks,
+                                            void* const* gz, float* const* gbias, void* gx, const void* mask_in,
+                                            float* gbias_in, const void* h_last, int32_t h_stride, int32_t live,
+                                            float* wl_part, size_t wl_part_bytes, float* gw_last, int32_t dtype,
+                                            int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "mlp_fused_bwd_data_wlast: bf16 only");
+  TRS_REQUIRE(widths && num_layers >= 1 && num_layers <= MF_MAXL, TRS_EINVAL, "mlp_fused_bwd_data_wlast: bad stack");
+  TRS_REQUIRE(h_last && wl_part && gw_last, TRS_EINVAL, "mlp_fused_bwd_data_wlast: NULL pointer");
+  const size_t need = trs_mlp_fused_bwd_wlast_part_bytes(num_layers, widths, rows > 0 ? rows : 1, dtype, family, live);
+  TRS_REQUIRE(need > 0, TRS_ESHAPE,
+              "mlp_fused_bwd_data_wlast: not carried for this stack / family %d / %d live columns (trs_mlp_fused_bwd_wlast_part_bytes)",
+              family, live);
+  TRS_REQUIRE(wl_part_bytes >= need, TRS_EWORKSPACE, "mlp_fused_bwd_data_wlast: partial buffer too small");
+  TRS_REQUIRE(gy_stride == widths[num_layers] || (gy_stride == live && live < 8), TRS_ESHAPE,
+              "mlp_fused_bwd_data_wlast: gy_stride %d (widths[L] = %d, or the %d live columns alone)", gy_stride,
+              widths[num_layers], live);
+  TRS_REQUIRE(h_stride >= pad32(widths[num_layers - 1]) && h_stride % 8 == 0, TRS_ESHAPE,
+              "mlp_fused_bwd_data_wlast: h_stride %d", h_stride);
+  TRS_REQUIRE(aligned16(h_last) && aligned16(wl_part) && aligned16(gw_last), TRS_EALIGN,
+              "mlp_fused_bwd_data_wlast: 16-byte alignment");
+  const MlpWlast wl{h_last, h_stride, live, gy_stride, wl_part, gw_last};
+  return mlp_fused_bwd_impl(gy, rows, num_layers, widths, weights, masks, gz, gbias, gx, mask_in, gbias_in, dtype, family,
+                            workspace, ws_bytes, stream, &wl);
 }
 
 /* y (rows x in_f) = x[:, :out_f] (rows x x_stride) @ W (out_f x in_f, row stride in_f), bf16 -- the input gradient of an

@@ -2973,11 +2973,22 @@ def fused_mlp_forward_raw(x2: torch.Tensor, Ws: Sequence[torch.Tensor], bs: Sequ
     return y, hidden, masks, fam
 
 
+def mlp_bwd_wlast_bytes(widths: Sequence[int], rows: int, family: int, live: int) -> int:
+    """Bytes of the partial buffer when the fused backward of this stack carries the output layer's weight gradient
+    (trs_mlp_fused_bwd_wlast_part_bytes); 0: it does not -- the caller keeps the product of its own."""
+    return size_query("trs_mlp_fused_bwd_wlast_part_bytes", len(widths) - 1, _i32_array(widths), int(rows), _abi.TRS_BF16,
+                      int(family), int(live))
+
+
 def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequence[torch.Tensor],
-                           masks: Sequence[torch.Tensor], mask_in: Optional[torch.Tensor] = None, *, family: int):
+                           masks: Sequence[torch.Tensor], mask_in: Optional[torch.Tensor] = None, *, family: int,
+                           h_last: Optional[torch.Tensor] = None, live: int = 0):
     """trs_mlp_fused_bwd_data: (gx, gz [d(pre-activation) of the hidden layers], gb [fp32 bias gradients, padded]) and,
     with ``mask_in``, gb_in: gx is then masked by the upstream ReLU and gb_in holds its column sums.  ``family``: what
-    fused_mlp_forward_raw returned with these masks."""
+    fused_mlp_forward_raw returned with these masks.
+    With ``h_last`` (the last hidden activation) and ``live`` (the output layer's real columns) the kernel also sums the
+    output layer's weight gradient (trs_mlp_fused_bwd_data_wlast; the caller asked mlp_bwd_wlast_bytes first): a fifth
+    result, (live, pad32(widths[L-1])) fp32.  gy2 is then (rows, widths[L]) or the contiguous (rows, live) gradient."""
     if family not in (MLP_FAMILY_TILE, MLP_FAMILY_ROW_OWNER, MLP_FAMILY_MIXED):
         raise ValueError("fused_mlp_backward_raw: family must be the value the forward returned with these masks")
     L = len(Ws)
@@ -2989,6 +3000,16 @@ def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequenc
     wl = _i32_array(widths)
     ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if h_last is not None:
+        if not (gy2.is_contiguous() and h_last.is_contiguous() and h_last.shape[0] == rows):
+            raise ValueError("fused_mlp_backward_raw: gy2 / h_last must be contiguous over the same rows")
+        part_bytes = mlp_bwd_wlast_bytes(widths, max(rows, 1), family, live)
+        part = torch.empty(max(part_bytes, 16), dtype=torch.uint8, device=dev)
+        gw_last = torch.empty(live, _pad32(widths[L - 1]), dtype=torch.float32, device=dev)
+        call("trs_mlp_fused_bwd_data_wlast", ptr(gy2), gy2.shape[1], rows, L, wl, _ptr_array(Ws), _ptr_array(masks),
+             _ptr_array(gz), _ptr_array(gb), ptr(gx), ptr(mask_in), ptr(gb_in), ptr(h_last), h_last.shape[1], int(live),
+             ptr(part), part_bytes, ptr(gw_last), _abi.TRS_BF16, int(family), ptr(ws), ws_bytes, stream_ptr())
+        return gx, gz, gb, gb_in, gw_last
     call("trs_mlp_fused_bwd_data", ptr(gy2), rows, L, wl, _ptr_array(Ws), _ptr_array(masks), _ptr_array(gz),
          _ptr_array(gb), ptr(gx), ptr(mask_in), ptr(gb_in), _abi.TRS_BF16, int(family), ptr(ws), ws_bytes, stream_ptr())
     return gx, gz, gb, gb_in
@@ -3021,12 +3042,19 @@ class _FusedMLP(Function):
         hidden, masks = saved[1 + L:L + L], saved[L + L:]
         rows, dev = x2.shape[0], x2.device
         gy2 = gy.reshape(rows, widths[L]).contiguous()
-        gx, gz, gb, _ = fused_mlp_backward_raw(gy2, widths, Ws, masks, family=fam)
+        same_dt = all(pdt[2 * l] == pdt[2 * l + 1] for l in range(L))
+        gw_last = None
+        if (same_dt and ctx.needs_input_grad[2 * L - 1] and gy2.dtype == torch.bfloat16
+                and mlp_bwd_wlast_bytes(widths, rows, fam, widths[L]) > 0):
+            gx, gz, gb, _, gw_last = fused_mlp_backward_raw(gy2, widths, Ws, masks, family=fam, h_last=hidden[L - 2],
+                                                            live=widths[L])
+        else:
+            gx, gz, gb, _ = fused_mlp_backward_raw(gy2, widths, Ws, masks, family=fam)
         grads = []
-        if all(pdt[2 * l] == pdt[2 * l + 1] for l in range(L)):
+        if same_dt:
             for gw, gbias in _tail_grads([(gy2 if l == L - 1 else gz[l], x2 if l == 0 else hidden[l - 1], widths[l + 1],
                                            widths[l], pdt[2 * l], gb[l], ctx.needs_input_grad[1 + 2 * l],
-                                           ctx.needs_input_grad[2 + 2 * l]) for l in range(L)]):
+                                           ctx.needs_input_grad[2 + 2 * l]) for l in range(L)], gw_last):
                 grads += [gw, gbias]
             return (gx.reshape(xshape) if ctx.needs_input_grad[0] else None, *grads)
         for l in range(L):
@@ -3093,16 +3121,35 @@ def _wgrad_many_splits(jobs) -> int:
                       _i32_array([j[1].shape[1] for j in jobs]), int(jobs[0][0].shape[0]))
 
 
-def _tail_grads(layers):
+def _tail_grads(layers, gw_last=None):
     """(dW, db) of every layer behind the fused kernels, ``layers`` = [(g, inp, out_f, in_f, dtype, gb_f32, need_w,
     need_b)] in stack order with the output layer last.  The hidden layers whose weight gradient is needed go out as one
     batched product and one batched finish where trs_wgrad_rows_many_splits takes them (two 400 x 400 layers from 8192
-    rows on); the output layer's few columns stay on their own kernel, and so does everything the query declines."""
+    rows on); the output layer's few columns stay on their own kernel, and so does everything the query declines.
+    ``gw_last``: the output layer's weight gradient as the fused backward summed it ((out_f, padded in_f) fp32, see
+    fused_mlp_backward_raw): no product for that layer, the cast of its rows and of its bias gradient ride in the batched
+    finish as jobs without a product (a finish launch of their own where there is no batch)."""
     out = [None] * len(layers)
     batch = [k for k, t in enumerate(layers[:-1]) if t[6]]
     jobs = [(layers[k][0], layers[k][1], min(layers[k][0].shape[1], (layers[k][2] + 7) // 8 * 8),
              min(layers[k][1].shape[1], (layers[k][3] + 7) // 8 * 8)) for k in batch]
     S = _wgrad_many_splits(jobs) if len({layers[k][4] for k in batch}) == 1 else 0
+    # the output layer as cast-only jobs of the finish (part = gw = None): (out_cols, fp32 source, destination) per row
+    casts = []
+    if gw_last is not None:
+        _, _, out_f, in_f, dt, gb_f32, _, need_b = layers[-1]
+        gw = torch.empty(out_f, in_f, dtype=dt, device=gw_last.device)
+        gbias = torch.empty(out_f, dtype=dt, device=gw_last.device) if need_b else None
+        casts = [(in_f, gw_last[r], gw[r]) for r in range(out_f)] + ([(out_f, gb_f32, gbias)] if need_b else [])
+        out[-1] = (gw, gbias)
+
+    def finish(parts, S, R, Cc, orows, ocols, gws, gbfs, gbs, dtype_code, extra):
+        n = len(extra)
+        call("trs_wgrad_finish_many", len(parts) + n, _ptr_array(parts + [None] * n), S, _i32_array(R + [0] * n),
+             _i32_array(Cc + [0] * n), _i32_array(orows + [0] * n), _i32_array(ocols + [c[0] for c in extra]), dtype_code,
+             _ptr_array(gws + [None] * n), _ptr_array(gbfs + [c[1] for c in extra]), _ptr_array(gbs + [c[2] for c in extra]),
+             stream_ptr())
+
     if S > 0:
         dev, dtype, rows = jobs[0][0].device, layers[batch[0]][4], jobs[0][0].shape[0]
         parts = [torch.empty(S, M, N, dtype=torch.float32, device=dev) for _, _, M, N in jobs]
@@ -3116,15 +3163,18 @@ def _tail_grads(layers):
             ride = need_b and out_f <= (in_f + 255) // 256 * 256      # the bias cast rides in the finish (see _wgrad_rows)
             gbs.append(torch.empty(out_f, dtype=dtype, device=dev) if ride else None)
             gbfs.append(gb_f32 if ride else None)
-        call("trs_wgrad_finish_many", len(jobs), _ptr_array(parts), S, _i32_array([j[2] for j in jobs]),
-             _i32_array([j[3] for j in jobs]), _i32_array([layers[k][2] for k in batch]),
-             _i32_array([layers[k][3] for k in batch]), value_dtype_code(gws[0]), _ptr_array(gws), _ptr_array(gbfs),
-             _ptr_array(gbs), stream_ptr())
+        ride_casts = casts if casts and layers[-1][4] == dtype and len(jobs) + len(casts) <= 8 else []
+        finish(parts, S, [j[2] for j in jobs], [j[3] for j in jobs], [layers[k][2] for k in batch],
+               [layers[k][3] for k in batch], gws, gbfs, gbs, value_dtype_code(gws[0]), ride_casts)
+        if ride_casts:
+            casts = []
         for n, k in enumerate(batch):
             gb = gbs[n]
             if gb is None and layers[k][7]:
                 gb = layers[k][5][:layers[k][2]].to(dtype)
             out[k] = (gws[n], gb)
+    if casts:      # no batched finish to ride in: a launch of their own
+        finish([], 1, [], [], [], [], [], [], [], value_dtype_code(casts[0][2]), casts)
     for k, t in enumerate(layers):
         if out[k] is None:
             out[k] = _tail_layer_grads(*t)

@@ -899,11 +899,19 @@ class _HybridMLP(torch.autograd.Function):
         hidden, masks = saved[4 + L:3 + L + L], saved[3 + L + L:]
         needs = ctx.needs_input_grad
         gy = gy.reshape(h1.shape[0], -1)
-        gy2 = F_.pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
-        g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam)
+        live, gw_last = wshapes[L - 1][0], None
+        if (needs[6 + 4 * (L - 1)] and gy.dtype == torch.bfloat16 and gy.shape[1] == live
+                and F_.mlp_bwd_wlast_bytes(widths, h1.shape[0], fam, live) > 0):
+            # the fused backward sums the output layer's weight gradient itself and reads the logit gradient where it lies
+            gy2 = gy.contiguous()
+            g1, gz, gb, gb1, gw_last = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam,
+                                                                 h_last=hidden[L - 2], live=live)
+        else:
+            gy2 = F_.pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
+            g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam)
         grads = []
         for gw, gbias in F_._tail_grads([(gy2 if l == L - 1 else gz[l], h1 if l == 0 else hidden[l - 1], *wshapes[l],
-                                          wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]) for l in range(L)]):
+                                          wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]) for l in range(L)], gw_last):
             grads += [gw, gbias, None, None]
         gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3])
         return (gx.reshape(xshape) if needs[0] else None, None, gw1, gbias1, None, None, *grads)
