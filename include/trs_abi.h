@@ -259,6 +259,49 @@ int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, const int32_t
                             int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
                             void* grad_table, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
+/* Bag pooling that leaves one row id out and / or weights every id (nn.EmbeddingBag's padding_idx and
+ * per_sample_weights).  live(b,l) := idx[b,l] != exclude_row (every position when exclude_row = -1), cnt[b] = the number
+ * of live positions, w = weights (B, L) of the table's dtype or NULL (= 1):
+ *   mode 0 (sum):  out[b,:] = sum_live w[b,l] * table[idx[b,l], :]
+ *   mode 1 (mean): out[b,:] = (sum_live table[idx[b,l], :]) * inv_cnt[b],  inv_cnt[b] = 1/cnt[b], 0 when cnt[b] == 0
+ *                  (an empty bag is a zero row); inv_cnt (B,) fp32 is written for the backward and required when
+ *                  exclude_row >= 0; with exclude_row = -1 it is not touched and the scale is 1/L
+ *   mode 2 (max):  the maximum over the live positions, the first live position winning a tie; an empty bag gives a zero
+ *                  row and argmax[b,:] = 0xFFFF, which no position equals: L <= 65534 when exclude_row >= 0
+ * An excluded position issues no table load and its weight is not read.  A live id outside [0, V) reads as a zero row,
+ * raises *err_flag and counts in cnt.  Arithmetic, paths and outputs as trs_bag_pool_fwd.
+ * TRS_EINVAL: NULL table / idx / out, exclude_row outside [-1, V), neither exclude_row >= 0 nor weights (that call is
+ * trs_bag_pool_fwd), weights with mode != 0, mode 2 without argmax, mode 1 with exclude_row >= 0 without inv_cnt, L out
+ * of range; TRS_EDTYPE: dtype / idx_dtype.  All before any launch.
+ * Backward: trs_csr_build_skip(skip_row = exclude_row) + trs_scatter_rows with g_fm = g (mean: g * inv_cnt[b]) or
+ * trs_scatter_rows_argmax; with weights trs_scatter_rows_weighted and, for the weights' own gradient, trs_bag_weight_grad.
+ * replaces F.embedding_bag(idx, table, mode=..., padding_idx=..., per_sample_weights=...) on 2-D idx.                 */
+int trs_bag_pool_masked_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx, int32_t idx_dtype,
+                            int64_t B, int32_t L, int32_t mode, int64_t exclude_row, const void* weights, void* out,
+                            uint16_t* argmax, float* inv_cnt, int32_t* err_flag, trs_stream_t stream);
+
+/* Table gradient of the weighted sum on the row buckets of the same ids (trs_csr_build / trs_csr_build_skip, N = L):
+ *   grad_table[r,:] = sum over the lookups p = (b,l) of row r of  weights[p] * g[b,:]
+ * for EVERY r in [0,V) (rows without lookups and padding_row are written as zeros; -1: no padding row).  g (B, E) and
+ * weights (B, L) of the table's dtype; positions that the bucket build left out contribute nothing.  The walk of
+ * trs_scatter_rows_argmax with another term: fp32 products and sums, no atomics on values, fixed summation order, rows
+ * with more than 64 lookups (32 on the any-E path) queued in `workspace` and reduced by whole waves, 256 lookups at a
+ * time; the (B, L, E) block is never formed.
+ * TRS_EINVAL: NULL pointer, bad size, L outside [1, 65535], B*L not a multiple of L; TRS_ESHAPE: B*L >= 2^31 - 1;
+ * TRS_EDTYPE: dtype; TRS_EWORKSPACE: ws_bytes below the query.                                                         */
+size_t trs_scatter_weighted_workspace_bytes(int64_t BN, int32_t E);
+int trs_scatter_rows_weighted(const void* g, const void* weights, const int32_t* row_start, const int32_t* perm,
+                              int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                              void* grad_table, void* workspace, size_t ws_bytes, trs_stream_t stream);
+
+/* Gradient of the weights of the weighted sum:
+ *   dw[b,l] = sum_e g[b,e] * table[idx[b,l], e]      (fp32, columns in order, one rounding to the table's dtype)
+ * and exactly 0 where idx[b,l] == exclude_row (-1: no row is excluded) or lies outside [0, V).  g (B, E), dw (B, L) of
+ * the table's dtype; one lane group (any E: one thread) per position re-reads the row, no (B, L, E) block.
+ * TRS_EINVAL: NULL pointer, bad size, L outside [1, 65535], exclude_row outside [-1, V); TRS_EDTYPE: dtype / idx_dtype. */
+int trs_bag_weight_grad(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx,
+                        int32_t idx_dtype, int64_t B, int32_t L, int64_t exclude_row, void* dw, trs_stream_t stream);
+
 /* ---- K2: FM layer on a materialised block -------------------------------------------------
  * fwd: fm[b,:] = 0.5*((sum_n x)^2 - sum_n x^2), fm_sum[b,:] = sum_n x (fp32, optional)
  * bwd: dx[b,n,:] = g[b,:] * (fm_sum[b,:] - x[b,n,:])

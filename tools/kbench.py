@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks (developer tool): time each C-ABI kernel at the BASELINE shape with HIP events
 on the launch stream and print algorithmic GB/s.  python tools/kbench.py [--dtype bf16] [--what a,b]
---what bag [--L 50] [--pad 0.3]: the bag-pooling kernels against their two ATen baselines (own inputs, see bench_bag).
+--what bag [--L 50] [--pad 0.3] [--exclude-padding] [--weighted]: the bag-pooling kernels against their two ATen baselines
+(own inputs, see bench_bag); the two switches add the masked / weighted kernels as further candidates of the same rounds.
 --what attn [--L 50] [--H 1] [--pad 0.3]: attention pooling of ListIndicesEmbedding, the fused path against the same module
 with the switch off, and the two kernels alone (own inputs, see bench_attn).
 --what senet: the SENET / compose-excitation layer, both kernel families, against the ATen composition of the same module
@@ -53,7 +54,10 @@ def bench_bag(a):
     process with two baselines on the same inputs -- the reference's composition (F.embedding -> transpose -> adaptive
     pooling; the sum has no pooling module: block.sum(1)) and torch.nn.functional.embedding_bag without padding_idx.
     Every figure is the median of ``--rounds`` per-round medians with their min..max; the candidates take turns inside a
-    round.  Then the row-bucket build on a batch with 60 % padding against one without."""
+    round.  ``--exclude-padding`` adds bag_pool(exclude_padding=True) to the candidates of every mode, ``--weighted`` the
+    weighted sum (per_sample_weights requiring grad, so its backward includes dw; with both switches also the two
+    together) to those of the sum -- they alternate with the unmasked kernel in the same rounds, so its spread is the
+    yardstick.  Then the row-bucket build on a batch with 60 % padding against one without."""
     import torch.nn.functional as TF
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     s = 2 if dt == torch.bfloat16 else 4
@@ -75,8 +79,10 @@ def bench_bag(a):
           f"{float((idx == 0).float().mean()):.2f}, {a.rounds} rounds x {a.iters} launches", flush=True)
     alg = B * L * (8 + E * s) + B * E * s
 
-    def ours(mode):
-        return lambda: F_.bag_pool(w, idx, mode, padding_idx=0)
+    def ours(mode, **kw):
+        return lambda: F_.bag_pool(w, idx, mode, padding_idx=0, **kw)
+
+    psw = (torch.rand(B, L, generator=g, device=dev) * 2).to(dt).requires_grad_() if a.weighted else None
 
     def comp(mode):
         def f():
@@ -94,11 +100,19 @@ def bench_bag(a):
         def run():
             F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
             w.grad = None
+            if psw is not None:
+                psw.grad = None
             f().backward(gout)
         return run
 
     for mode in ("sum", "mean", "max"):
         cands = [("bag_pool (HIP)", ours(mode)), ("composition (ATen)", comp(mode)), ("embedding_bag (ATen)", bag(mode))]
+        if a.exclude_padding:
+            cands.insert(1, ("bag_pool masked (HIP)", ours(mode, exclude_padding=True)))
+        if a.weighted and mode == "sum":
+            cands.insert(1, ("bag_pool wgt (HIP)", ours(mode, per_sample_weights=psw)))
+            if a.exclude_padding:
+                cands.insert(1, ("masked + wgt (HIP)", ours(mode, exclude_padding=True, per_sample_weights=psw)))
         live = []
         for name, f in cands:
             try:
@@ -991,6 +1005,8 @@ def main():
     ap.add_argument("--L", type=int, default=50, help="bag / attn / routing / seq: list length")
     ap.add_argument("--H", type=int, default=1, help="attn: attention heads")
     ap.add_argument("--pad", type=float, default=0.3, help="bag: share of padded positions")
+    ap.add_argument("--exclude-padding", action="store_true", help="bag: also time bag_pool(exclude_padding=True)")
+    ap.add_argument("--weighted", action="store_true", help="bag: also time the weighted sum (per_sample_weights)")
     ap.add_argument("--rounds", type=int, default=5, help="bag / senet / compact / moe / routing: alternating rounds")
     ap.add_argument("--iters", type=int, default=10, help="bag / senet / compact / moe / routing: timed launches per round")
     ap.add_argument("--routing-iters", type=int, default=3, help="routing: num_iter of the layer")

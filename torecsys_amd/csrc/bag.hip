@@ -14,6 +14,16 @@
 // elsewhere.  It reads g (B, E) and amax (B, E), never a (B, Lb, E) block; every table row is written (padding row: zeros);
 // no atomics on values, fixed summation order.  Rows with more than BAG_LONG_ROW lookups are queued and reduced by whole
 // waves in chunks of BAG_LONG_CHUNK, as scatter.hip's hot rows are.
+//
+// Masked / weighted variants (trs_bag_pool_masked_fwd): the same two forward kernels with the compile-time flags MASK (a
+// position that holds the excluded row id issues no table load and takes no part: sum over the live positions, mean over
+// their count -- written as inv_cnt[b] = 1/cnt for the backward, 0 for an empty bag --, max over them with the sentinel
+// 0xFFFF in argmax for an empty bag) and WGT (sum only: every term times w[b, l], the weight read once per position).  With
+// both flags off the instantiations are the ones above: no branch is added to them.  Algorithmic bytes per sample =
+// Lb * idx bytes + cnt * E*s (+ Lb * s of weights) read, E*s (+ 4 for inv_cnt, + 2*E for the max positions) written.
+// Weighted backward: the walk of the max backward with the term of lookup p = (b, l) being w[p] * g[b, e] (flag WGT of the
+// same kernels, same queue thresholds BAG_LONG_ROW / BAG_LONG_CHUNK / BAG_LONG_ROW_ELEM), and bag_weight_grad_*_kernel:
+// dw[b, l] = sum_e g[b, e] * table[idx[b, l], e], one lane group (or one thread) per position, 0 at excluded positions.
 #include <algorithm>
 #include <cmath>
 
@@ -30,11 +40,13 @@ constexpr size_t BAG_STREAM_BYTES = (size_t)512 << 20;      // twice the Infinit
 // ATen's rule (adaptive_max_pool): a later value replaces the running maximum when it is greater or NaN
 __device__ __forceinline__ bool bag_takes(float v, float m) { return v > m || v != v; }
 
-template <typename T, typename IdxT, int LOG2L, bool MAXP, int CH, bool STREAM>
+template <typename T, typename IdxT, int LOG2L, bool MAXP, int CH, bool STREAM, bool MASK, bool WGT>
 __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __restrict__ table,
                                                              const IdxT* __restrict__ idx, int64_t B, int Lb, int64_t V,
                                                              float scale, uint4* __restrict__ out,
-                                                             uint16_t* __restrict__ amax, int32_t* __restrict__ err_flag) {
+                                                             uint16_t* __restrict__ amax, int32_t* __restrict__ err_flag,
+                                                             int64_t pad, const T* __restrict__ wts,
+                                                             float* __restrict__ inv_cnt) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   const int lane_v = threadIdx.x & (L - 1);
@@ -44,17 +56,28 @@ __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __rest
     int am[VE];
 #pragma unroll
     for (int k = 0; k < VE; ++k) { s[k] = MAXP ? -INFINITY : 0.f; am[k] = 0; }
+    int cnt = 0;                            // MASK: live positions of the bag
     for (int l0 = 0; l0 < Lb; l0 += CH) {
       int64_t r[CH];
       uint4 v[CH];
+      bool live[CH];                        // MASK only
+      float wv[CH];                         // WGT only
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         r[c] = -1;
+        live[c] = false;
+        wv[c] = 1.f;
         if (l0 + c < Lb) {
           r[c] = (int64_t)idx[b * Lb + l0 + c];
-          if (r[c] < 0 || r[c] >= V) {      // reads as a zero row
-            if (err_flag != nullptr) *err_flag = 1;
+          if (MASK && r[c] == pad) {        // excluded: no load, no term, no count
             r[c] = -1;
+          } else {
+            live[c] = true;
+            if (WGT) wv[c] = to_f32(wts[b * Lb + l0 + c]);
+            if (r[c] < 0 || r[c] >= V) {    // reads as a zero row
+              if (err_flag != nullptr) *err_flag = 1;
+              r[c] = -1;
+            }
           }
         }
       }
@@ -65,13 +88,19 @@ __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __rest
       }
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
-        if (l0 + c < Lb) {
+        // MASK: a branch per lane (the bags of a wave end at different positions).  Taking an excluded position as a term of
+        // zero / a select instead measured slower: 67.0 against 60.2 us (35 % padding), 76.6 against 74.5 us (none),
+        // profiles/bag_kernels.md
+        if (MASK ? live[c] : (l0 + c < Lb)) {
+          if (MASK) ++cnt;
           float x[VE];
           Vec16<T>::unpack(v[c], x);
 #pragma unroll
           for (int k = 0; k < VE; ++k) {
             if (MAXP) {
               if (bag_takes(x[k], s[k])) { s[k] = x[k]; am[k] = l0 + c; }
+            } else if (WGT) {
+              s[k] += wv[c] * x[k];
             } else {
               s[k] += x[k];
             }
@@ -80,8 +109,16 @@ __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __rest
       }
     }
     if (!MAXP) {
+      float sc = scale;
+      if (MASK && inv_cnt != nullptr) {     // mean over the live positions; an empty bag is a zero row
+        sc = cnt > 0 ? 1.f / (float)cnt : 0.f;
+        if (lane_v == 0) inv_cnt[b] = sc;
+      }
 #pragma unroll
-      for (int k = 0; k < VE; ++k) s[k] *= scale;
+      for (int k = 0; k < VE; ++k) s[k] *= sc;
+    } else if (MASK && cnt == 0) {          // empty bag: zero row, no position holds the maximum
+#pragma unroll
+      for (int k = 0; k < VE; ++k) { s[k] = 0.f; am[k] = 0xFFFF; }
     }
     out[b * L + lane_v] = Vec16<T>::pack(s);
     if (MAXP) {
@@ -96,11 +133,12 @@ __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __rest
 }
 
 // generic path: any E; one thread per (b, e)
-template <typename T, typename IdxT, bool MAXP>
+template <typename T, typename IdxT, bool MAXP, bool MASK, bool WGT>
 __global__ __launch_bounds__(256) void bag_pool_elem_kernel(const T* __restrict__ table, const IdxT* __restrict__ idx,
                                                             int64_t B, int Lb, int E, int64_t V, float scale,
                                                             T* __restrict__ out, uint16_t* __restrict__ amax,
-                                                            int32_t* __restrict__ err_flag) {
+                                                            int32_t* __restrict__ err_flag, int64_t pad,
+                                                            const T* __restrict__ wts, float* __restrict__ inv_cnt) {
   const int64_t total = B * E;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const bool f32 = total < ((int64_t)1 << 32);
@@ -109,8 +147,13 @@ __global__ __launch_bounds__(256) void bag_pool_elem_kernel(const T* __restrict_
     const int e = (int)(t - b * E);
     float s = MAXP ? -INFINITY : 0.f;
     int am = 0;
+    int cnt = 0;
     for (int l = 0; l < Lb; ++l) {
       const int64_t r = (int64_t)idx[b * Lb + l];
+      if (MASK) {
+        if (r == pad) continue;
+        ++cnt;
+      }
       T raw = T{};
       if (r < 0 || r >= V) {
         if (err_flag != nullptr) *err_flag = 1;
@@ -120,11 +163,19 @@ __global__ __launch_bounds__(256) void bag_pool_elem_kernel(const T* __restrict_
       const float x = to_f32(raw);
       if (MAXP) {
         if (bag_takes(x, s)) { s = x; am = l; }
+      } else if (WGT) {
+        s += to_f32(wts[b * Lb + l]) * x;
       } else {
         s += x;
       }
     }
-    out[t] = from_f32<T>(MAXP ? s : s * scale);
+    float sc = scale;
+    if (MASK && !MAXP && inv_cnt != nullptr) {
+      sc = cnt > 0 ? 1.f / (float)cnt : 0.f;
+      if (e == 0) inv_cnt[b] = sc;
+    }
+    if (MASK && MAXP && cnt == 0) { s = 0.f; am = 0xFFFF; }
+    out[t] = from_f32<T>(MAXP ? s : s * sc);
     if (MAXP) amax[t] = (uint16_t)am;
   }
 }
@@ -138,21 +189,25 @@ static int bag_log2_lanes(int row_bytes) {
   return l;
 }
 
-template <typename T, typename IdxT>
+template <typename T, typename IdxT, bool MASK, bool WGT>
 static int bag_pool_launch(const void* table, const IdxT* idx, int64_t B, int Lb, int E, int64_t V, int mode, void* out,
-                           uint16_t* amax, int32_t* err_flag, hipStream_t s) {
+                           uint16_t* amax, int32_t* err_flag, int64_t pad, const void* wts_, float* inv_cnt,
+                           hipStream_t s) {
+  const T* wts = (const T*)wts_;
   const int lg = bag_log2_lanes(E * (int)sizeof(T));
   const float scale = mode == BAG_MEAN ? 1.f / (float)Lb : 1.f;
   if (lg >= 0 && aligned16(table) && aligned16(out) && aligned16(amax)) {
     const int grid = stream_grid(B << lg, 256, 256 * 16);
     const bool stream = (size_t)V * E * sizeof(T) > BAG_STREAM_BYTES;
 #define TRS_BAG2(LG, MX, CH_, ST)                                                                              \
-  hipLaunchKernelGGL((bag_pool_group_kernel<T, IdxT, LG, MX, CH_, ST>), dim3(grid), dim3(256), 0, s,             \
-                     (const uint4*)table, idx, B, Lb, V, scale, (uint4*)out, amax, err_flag)
+  hipLaunchKernelGGL((bag_pool_group_kernel<T, IdxT, LG, MX, CH_, ST, MASK, WGT>), dim3(grid), dim3(256), 0, s,  \
+                     (const uint4*)table, idx, B, Lb, V, scale, (uint4*)out, amax, err_flag, pad, wts, inv_cnt)
 #define TRS_BAG(LG)                                      \
   if (mode == BAG_MAX) {                                 \
-    if (stream) TRS_BAG2(LG, true, 4, true);             \
-    else TRS_BAG2(LG, true, 4, false);                   \
+    if constexpr (!WGT) {      /* weights: sum only */   \
+      if (stream) TRS_BAG2(LG, true, 4, true);           \
+      else TRS_BAG2(LG, true, 4, false);                 \
+    }                                                    \
   } else {                                               \
     if (stream) TRS_BAG2(LG, false, 8, true);            \
     else TRS_BAG2(LG, false, 8, false);                  \
@@ -170,44 +225,54 @@ static int bag_pool_launch(const void* table, const IdxT* idx, int64_t B, int Lb
 #undef TRS_BAG2
   } else {
     const int grid = stream_grid(B * E, 256, 256 * 16);
-    if (mode == BAG_MAX)
-      hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, true>), dim3(grid), dim3(256), 0, s, (const T*)table, idx, B, Lb,
-                         E, V, scale, (T*)out, amax, err_flag);
-    else
-      hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, false>), dim3(grid), dim3(256), 0, s, (const T*)table, idx, B,
-                         Lb, E, V, scale, (T*)out, amax, err_flag);
+    if (mode == BAG_MAX) {
+      if constexpr (!WGT)
+        hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, true, MASK, false>), dim3(grid), dim3(256), 0, s,
+                           (const T*)table, idx, B, Lb, E, V, scale, (T*)out, amax, err_flag, pad, wts, inv_cnt);
+    } else {
+      hipLaunchKernelGGL((bag_pool_elem_kernel<T, IdxT, false, MASK, WGT>), dim3(grid), dim3(256), 0, s, (const T*)table,
+                         idx, B, Lb, E, V, scale, (T*)out, amax, err_flag, pad, wts, inv_cnt);
+    }
   }
-  return check_launch("bag_pool_fwd");
+  return check_launch(MASK || WGT ? "bag_pool_masked_fwd" : "bag_pool_fwd");
 }
 
 // ---------------------------------------------------------------------------------------------
 // max backward: bucket walk with the winner mask
 
 // the lookups q = beg, beg + step, ... < end of one bucket, CH in flight per lane: acc[k] += g[b, k] where amax[b, k] == l
-template <typename T, int LOG2L, int CH>
+// (WGT: acc[k] += wts[p] * g[b, k] instead, p = b * N + l the flat position; amax is not read)
+template <typename T, int LOG2L, int CH, bool WGT>
 __device__ __forceinline__ void bag_argmax_bucket(float* acc, const uint4* __restrict__ g,
-                                                  const uint16_t* __restrict__ amax, const int32_t* __restrict__ perm,
-                                                  int beg, int end, int step, unsigned N, int lane_v) {
+                                                  const uint16_t* __restrict__ amax, const T* __restrict__ wts,
+                                                  const int32_t* __restrict__ perm, int beg, int end, int step,
+                                                  unsigned N, int lane_v) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   for (int q = beg; q < end; q += CH * step) {
     int p[CH];
     uint4 gv[CH], av[CH];
+    float wv[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) p[c] = (q + c * step) < end ? perm[q + c * step] : -1;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       gv[c] = make_uint4(0, 0, 0, 0);
       av[c] = make_uint4(0, 0, 0, 0);
+      wv[c] = 0.f;
       if (p[c] >= 0) {
         const int64_t b = (int64_t)((unsigned)p[c] / N);
         gv[c] = g[b * L + lane_v];
-        const uint16_t* ap = amax + (b * L + lane_v) * VE;
-        if (VE == 8) {
-          av[c] = *reinterpret_cast<const uint4*>(ap);
+        if (WGT) {
+          wv[c] = to_f32(wts[p[c]]);
         } else {
-          const uint2 a2 = *reinterpret_cast<const uint2*>(ap);
-          av[c] = make_uint4(a2.x, a2.y, 0, 0);
+          const uint16_t* ap = amax + (b * L + lane_v) * VE;
+          if (VE == 8) {
+            av[c] = *reinterpret_cast<const uint4*>(ap);
+          } else {
+            const uint2 a2 = *reinterpret_cast<const uint2*>(ap);
+            av[c] = make_uint4(a2.x, a2.y, 0, 0);
+          }
         }
       }
     }
@@ -221,17 +286,22 @@ __device__ __forceinline__ void bag_argmax_bucket(float* acc, const uint4* __res
         const uint32_t w[4] = {av[c].x, av[c].y, av[c].z, av[c].w};
 #pragma unroll
         for (int k = 0; k < VE; ++k) {
-          const unsigned a = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
-          acc[k] += a == l ? x[k] : 0.f;
+          if (WGT) {
+            acc[k] += wv[c] * x[k];
+          } else {
+            const unsigned a = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
+            acc[k] += a == l ? x[k] : 0.f;
+          }
         }
       }
     }
   }
 }
 
-template <typename T, int LOG2L>
+template <typename T, int LOG2L, bool WGT>
 __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __restrict__ g,
                                                               const uint16_t* __restrict__ amax,
+                                                              const T* __restrict__ wts,
                                                               const int32_t* __restrict__ row_start,
                                                               const int32_t* __restrict__ perm, int64_t V, unsigned N,
                                                               int64_t padding_row, uint4* __restrict__ grad,
@@ -257,7 +327,7 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
         }
         continue;
       }
-      bag_argmax_bucket<T, LOG2L, 4>(acc, g, amax, perm, beg, end, 1, N, lane_v);
+      bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg, end, 1, N, lane_v);
     }
     store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
   }
@@ -265,9 +335,10 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
 
 // hot rows: one wave per (row, chunk) entry, its 64 / L lane groups stride the chunk, partial sums folded by shuffles.
 // Rows of a single chunk are finished here; otherwise the partial goes to scratch[entry][E] (fp32) for the finish kernel.
-template <typename T, int LOG2L>
+template <typename T, int LOG2L, bool WGT>
 __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __restrict__ g,
                                                               const uint16_t* __restrict__ amax,
+                                                              const T* __restrict__ wts,
                                                               const int32_t* __restrict__ row_start,
                                                               const int32_t* __restrict__ perm, unsigned N,
                                                               uint4* __restrict__ grad,
@@ -289,7 +360,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __res
     float acc[VE];
 #pragma unroll
     for (int k = 0; k < VE; ++k) acc[k] = 0.f;
-    bag_argmax_bucket<T, LOG2L, 4>(acc, g, amax, perm, beg + grp, end, G, N, lane_v);
+    bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg + grp, end, G, N, lane_v);
 #pragma unroll
     for (int m = L; m < 64; m <<= 1) {
 #pragma unroll
@@ -338,18 +409,20 @@ __global__ __launch_bounds__(256) void bag_argmax_finish_kernel(const int32_t* _
 
 // generic path (any E): one thread per (row, e); rows with more than BAG_LONG_ROW_ELEM lookups are queued (one id each)
 // and reduced by one wave per row
-template <typename T>
-__device__ __forceinline__ float bag_argmax_term(const T* __restrict__ g, const uint16_t* __restrict__ amax, int p,
-                                                 unsigned N, int E, int e) {
+template <typename T, bool WGT>
+__device__ __forceinline__ float bag_argmax_term(const T* __restrict__ g, const uint16_t* __restrict__ amax,
+                                                 const T* __restrict__ wts, int p, unsigned N, int E, int e) {
   const unsigned b = (unsigned)p / N;
   const unsigned l = (unsigned)p - b * N;
   const int64_t o = (int64_t)b * E + e;
+  if (WGT) return to_f32(wts[p]) * to_f32(g[o]);
   return (unsigned)amax[o] == l ? to_f32(g[o]) : 0.f;
 }
 
-template <typename T>
+template <typename T, bool WGT>
 __global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __restrict__ g,
                                                                    const uint16_t* __restrict__ amax,
+                                                                   const T* __restrict__ wts,
                                                                    const int32_t* __restrict__ row_start,
                                                                    const int32_t* __restrict__ perm, int64_t V, int E,
                                                                    unsigned N, int64_t padding_row, T* __restrict__ grad,
@@ -367,15 +440,16 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __re
         if (e == 0) long_rows[1 + atomicAdd(&long_rows[0], 1)] = (int32_t)r;
         continue;
       }
-      for (int q = beg; q < end; ++q) acc += bag_argmax_term<T>(g, amax, perm[q], N, E, e);
+      for (int q = beg; q < end; ++q) acc += bag_argmax_term<T, WGT>(g, amax, wts, perm[q], N, E, e);
     }
     grad[t] = from_f32<T>(acc);
   }
 }
 
-template <typename T>
+template <typename T, bool WGT>
 __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __restrict__ g,
                                                                    const uint16_t* __restrict__ amax,
+                                                                   const T* __restrict__ wts,
                                                                    const int32_t* __restrict__ row_start,
                                                                    const int32_t* __restrict__ perm, int E, unsigned N,
                                                                    T* __restrict__ grad,
@@ -395,7 +469,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __re
         for (int u = 0; u < U; ++u) pp[u] = (q + 64 * u) < end ? perm[q + 64 * u] : -1;
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (pp[u] >= 0) acc += bag_argmax_term<T>(g, amax, pp[u], N, E, e);
+          if (pp[u] >= 0) acc += bag_argmax_term<T, WGT>(g, amax, wts, pp[u], N, E, e);
       }
 #pragma unroll
       for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
@@ -415,20 +489,21 @@ static size_t bag_queue_bytes(int64_t BN) {
   return bag_align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
 }
 
-template <typename T>
-static int bag_argmax_launch(const void* g, const uint16_t* amax, const int32_t* row_start, const int32_t* perm,
-                             int64_t V, int E, int N, int64_t padding_row, void* grad, int32_t* long_rows,
-                             float* scratch, hipStream_t s) {
+template <typename T, bool WGT>
+static int bag_argmax_launch(const void* g, const uint16_t* amax, const void* wts_, const int32_t* row_start,
+                             const int32_t* perm, int64_t V, int E, int N, int64_t padding_row, void* grad,
+                             int32_t* long_rows, float* scratch, hipStream_t s) {
+  const T* wts = (const T*)wts_;
   const int lg = bag_log2_lanes(E * (int)sizeof(T));
   hipLaunchKernelGGL(bag_zero_counter_kernel, dim3(1), dim3(64), 0, s, long_rows);
   if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(grad)) {
     const int grid = stream_grid(V << lg, 256, 256 * 32);
 #define TRS_BAGB(LG)                                                                                                  \
   do {                                                                                                                \
-    hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, row_start, \
-                       perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);                                    \
-    hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, row_start, \
-                       perm, (unsigned)N, (uint4*)grad, long_rows, scratch);                                           \
+    hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, wts,  \
+                       row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);                         \
+    hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, wts,  \
+                       row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch);                                \
     hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,          \
                        long_rows, scratch);                                                                            \
   } while (0)
@@ -443,12 +518,94 @@ static int bag_argmax_launch(const void* g, const uint16_t* amax, const int32_t*
     }
 #undef TRS_BAGB
   } else {
-    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
-                       (const T*)g, amax, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows);
-    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, row_start,
-                       perm, E, (unsigned)N, (T*)grad, long_rows);
+    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T, WGT>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
+                       (const T*)g, amax, wts, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows);
+    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T, WGT>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, wts,
+                       row_start, perm, E, (unsigned)N, (T*)grad, long_rows);
   }
-  return check_launch("scatter_rows_argmax");
+  return check_launch(WGT ? "scatter_rows_weighted" : "scatter_rows_argmax");
+}
+
+// ---------------------------------------------------------------------------------------------
+// weight gradient: dw[b, l] = sum_e g[b, e] * table[idx[b, l], e]; 0 where the position is excluded or out of range
+
+// a group of L lanes per position p = b * Lb + l: one 16-byte vector of the row and of g[b] per lane, fp32 products summed
+// in column order inside the lane, then folded over the group by shuffles (fixed order)
+template <typename T, typename IdxT, int LOG2L>
+__global__ __launch_bounds__(256) void bag_weight_grad_group_kernel(const uint4* __restrict__ table,
+                                                                    const uint4* __restrict__ g,
+                                                                    const IdxT* __restrict__ idx, int64_t BN, int Lb,
+                                                                    int64_t V, int64_t pad, T* __restrict__ dw) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  const int lane_v = threadIdx.x & (L - 1);
+  const int64_t groups = ((int64_t)gridDim.x * blockDim.x) >> LOG2L;
+  const int64_t first = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> LOG2L;
+  const int64_t trips = (BN + groups - 1) / groups;      // the same for every lane: the shuffles need the whole wave
+  const bool f32 = BN < ((int64_t)1 << 32);
+  for (int64_t it = 0; it < trips; ++it) {
+    const int64_t p = first + it * groups;
+    float d = 0.f;
+    if (p < BN) {
+      const int64_t r = (int64_t)idx[p];
+      if (r != pad && r >= 0 && r < V) {
+        const int64_t b = udiv_fast(p, Lb, f32);
+        float x[VE], y[VE];
+        Vec16<T>::unpack(table[r * L + lane_v], x);
+        Vec16<T>::unpack(g[b * L + lane_v], y);
+#pragma unroll
+        for (int k = 0; k < VE; ++k) d += x[k] * y[k];
+      }
+    }
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) d += __shfl_xor(d, m, 64);
+    if (p < BN && lane_v == 0) dw[p] = from_f32<T>(d);
+  }
+}
+
+// generic path (any E): one thread per position
+template <typename T, typename IdxT>
+__global__ __launch_bounds__(256) void bag_weight_grad_elem_kernel(const T* __restrict__ table, const T* __restrict__ g,
+                                                                   const IdxT* __restrict__ idx, int64_t BN, int Lb,
+                                                                   int E, int64_t V, int64_t pad, T* __restrict__ dw) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const bool f32 = BN < ((int64_t)1 << 32);
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < BN; p += stride) {
+    const int64_t r = (int64_t)idx[p];
+    float d = 0.f;
+    if (r != pad && r >= 0 && r < V) {
+      const int64_t b = udiv_fast(p, Lb, f32);
+      for (int e = 0; e < E; ++e) d += to_f32(table[r * E + e]) * to_f32(g[b * E + e]);
+    }
+    dw[p] = from_f32<T>(d);
+  }
+}
+
+template <typename T, typename IdxT>
+static int bag_weight_grad_launch(const void* table, const void* g, const IdxT* idx, int64_t B, int Lb, int E, int64_t V,
+                                  int64_t pad, void* dw, hipStream_t s) {
+  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  const int64_t BN = B * Lb;
+  if (lg >= 0 && aligned16(table) && aligned16(g)) {
+    const int grid = stream_grid(BN << lg, 256, 256 * 32);
+#define TRS_BAGW(LG)                                                                                                  \
+  hipLaunchKernelGGL((bag_weight_grad_group_kernel<T, IdxT, LG>), dim3(grid), dim3(256), 0, s, (const uint4*)table,   \
+                     (const uint4*)g, idx, BN, Lb, V, pad, (T*)dw)
+    switch (lg) {
+      case 0: TRS_BAGW(0); break;
+      case 1: TRS_BAGW(1); break;
+      case 2: TRS_BAGW(2); break;
+      case 3: TRS_BAGW(3); break;
+      case 4: TRS_BAGW(4); break;
+      case 5: TRS_BAGW(5); break;
+      default: TRS_BAGW(6); break;
+    }
+#undef TRS_BAGW
+  } else {
+    hipLaunchKernelGGL((bag_weight_grad_elem_kernel<T, IdxT>), dim3(stream_grid(BN, 256, 256 * 32)), dim3(256), 0, s,
+                       (const T*)table, (const T*)g, idx, BN, Lb, E, V, pad, (T*)dw);
+  }
+  return check_launch("bag_weight_grad");
 }
 
 }  // namespace trs
@@ -469,7 +626,9 @@ extern "C" int trs_bag_pool_fwd(const void* table, int64_t V, int32_t E, int32_t
   TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "bag_pool_fwd: dtype %d", dtype);
   TRS_REQUIRE(idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EDTYPE, "bag_pool_fwd: idx dtype %d", idx_dtype);
   hipStream_t s = (hipStream_t)stream;
-#define TRS_CALL(T, I) return bag_pool_launch<T, I>(table, (const I*)idx, B, L, E, V, mode, out, argmax, err_flag, s)
+#define TRS_CALL(T, I)                                                                                            \
+  return bag_pool_launch<T, I, false, false>(table, (const I*)idx, B, L, E, V, mode, out, argmax, err_flag, -1, nullptr, \
+                                             nullptr, s)
   if (dtype == TRS_F32) {
     if (idx_dtype == TRS_I64) TRS_CALL(float, int64_t);
     TRS_CALL(float, int32_t);
@@ -502,6 +661,106 @@ extern "C" int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, co
   float* scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
   hipStream_t s = (hipStream_t)stream;
   if (dtype == TRS_F32)
-    return bag_argmax_launch<float>(g, argmax, row_start, perm, V, E, N, padding_row, grad_table, long_rows, scratch, s);
-  return bag_argmax_launch<bf16_t>(g, argmax, row_start, perm, V, E, N, padding_row, grad_table, long_rows, scratch, s);
+    return bag_argmax_launch<float, false>(g, argmax, nullptr, row_start, perm, V, E, N, padding_row, grad_table,
+                                           long_rows, scratch, s);
+  return bag_argmax_launch<bf16_t, false>(g, argmax, nullptr, row_start, perm, V, E, N, padding_row, grad_table,
+                                          long_rows, scratch, s);
+}
+
+extern "C" int trs_bag_pool_masked_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx,
+                                       int32_t idx_dtype, int64_t B, int32_t L, int32_t mode, int64_t exclude_row,
+                                       const void* weights, void* out, uint16_t* argmax, float* inv_cnt,
+                                       int32_t* err_flag, trs_stream_t stream) {
+  if (B == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
+  TRS_REQUIRE(table && idx && out, TRS_EINVAL, "bag_pool_masked_fwd: NULL pointer");
+  TRS_REQUIRE(mode == BAG_SUM || mode == BAG_MEAN || mode == BAG_MAX, TRS_EINVAL,
+              "bag_pool_masked_fwd: mode %d (0 = sum, 1 = mean, 2 = max)", mode);
+  TRS_REQUIRE(V > 0 && E > 0 && B >= 0, TRS_EINVAL, "bag_pool_masked_fwd: bad size V=%lld E=%d B=%lld", (long long)V, E,
+              (long long)B);
+  TRS_REQUIRE(exclude_row >= -1 && exclude_row < V, TRS_EINVAL, "bag_pool_masked_fwd: exclude_row %lld outside [-1, V)",
+              (long long)exclude_row);
+  TRS_REQUIRE(exclude_row >= 0 || weights != nullptr, TRS_EINVAL,
+              "bag_pool_masked_fwd: neither an excluded row nor weights (that case is trs_bag_pool_fwd)");
+  TRS_REQUIRE(weights == nullptr || mode == BAG_SUM, TRS_EINVAL, "bag_pool_masked_fwd: weights need mode 0 (sum), got %d",
+              mode);
+  TRS_REQUIRE(mode != BAG_MAX || argmax != nullptr, TRS_EINVAL,
+              "bag_pool_masked_fwd: max pooling needs the argmax output");
+  TRS_REQUIRE(mode != BAG_MEAN || exclude_row < 0 || inv_cnt != nullptr, TRS_EINVAL,
+              "bag_pool_masked_fwd: the mean over the live positions needs the inv_cnt output");
+  TRS_REQUIRE(L >= 1 && L <= (mode == BAG_MAX && exclude_row >= 0 ? 65534 : 65535), TRS_EINVAL,
+              "bag_pool_masked_fwd: list length L=%d outside [1, %d]", L,
+              mode == BAG_MAX && exclude_row >= 0 ? 65534 : 65535);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "bag_pool_masked_fwd: dtype %d", dtype);
+  TRS_REQUIRE(idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EDTYPE, "bag_pool_masked_fwd: idx dtype %d", idx_dtype);
+  hipStream_t s = (hipStream_t)stream;
+  float* ic = mode == BAG_MEAN ? inv_cnt : nullptr;
+#define TRS_CALL3(T, I, M, W)                                                                                       \
+  return bag_pool_launch<T, I, M, W>(table, (const I*)idx, B, L, E, V, mode, out, argmax, err_flag, exclude_row, weights, \
+                                     ic, s)
+#define TRS_CALL(T, I)                            \
+  do {                                            \
+    if (exclude_row >= 0) {                       \
+      if (weights != nullptr) TRS_CALL3(T, I, true, true); \
+      TRS_CALL3(T, I, true, false);               \
+    }                                             \
+    TRS_CALL3(T, I, false, true);                 \
+  } while (0)
+  if (dtype == TRS_F32) {
+    if (idx_dtype == TRS_I64) TRS_CALL(float, int64_t);
+    TRS_CALL(float, int32_t);
+  }
+  if (idx_dtype == TRS_I64) TRS_CALL(bf16_t, int64_t);
+  TRS_CALL(bf16_t, int32_t);
+#undef TRS_CALL
+#undef TRS_CALL3
+}
+
+extern "C" size_t trs_scatter_weighted_workspace_bytes(int64_t BN, int32_t E) {
+  return trs_scatter_argmax_workspace_bytes(BN, E);      // the same queue and chunk partials
+}
+
+extern "C" int trs_scatter_rows_weighted(const void* g, const void* weights, const int32_t* row_start,
+                                         const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                                         int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
+                                         trs_stream_t stream) {
+  TRS_REQUIRE(g && weights && row_start && perm && grad_table && workspace, TRS_EINVAL,
+              "scatter_rows_weighted: NULL pointer");
+  TRS_REQUIRE(V > 0 && E > 0 && BN >= 0, TRS_EINVAL, "scatter_rows_weighted: bad size");
+  TRS_REQUIRE(N >= 1 && N <= 65535, TRS_EINVAL, "scatter_rows_weighted: list length L=%d outside [1, 65535]", N);
+  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "scatter_rows_weighted: B*L=%lld not a multiple of L=%d", (long long)BN, N);
+  TRS_REQUIRE(BN < (int64_t)0x7fffffff, TRS_ESHAPE, "scatter_rows_weighted: B*L=%lld must fit int32", (long long)BN);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_weighted: dtype %d", dtype);
+  TRS_REQUIRE(ws_bytes >= trs_scatter_weighted_workspace_bytes(BN, E), TRS_EWORKSPACE,
+              "scatter_rows_weighted: workspace %zu < %zu", ws_bytes, trs_scatter_weighted_workspace_bytes(BN, E));
+  int32_t* long_rows = (int32_t*)workspace;
+  float* scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TRS_F32)
+    return bag_argmax_launch<float, true>(g, nullptr, weights, row_start, perm, V, E, N, padding_row, grad_table,
+                                          long_rows, scratch, s);
+  return bag_argmax_launch<bf16_t, true>(g, nullptr, weights, row_start, perm, V, E, N, padding_row, grad_table,
+                                         long_rows, scratch, s);
+}
+
+extern "C" int trs_bag_weight_grad(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype,
+                                   const void* idx, int32_t idx_dtype, int64_t B, int32_t L, int64_t exclude_row,
+                                   void* dw, trs_stream_t stream) {
+  if (B == 0) return TRS_OK;
+  TRS_REQUIRE(g && table && idx && dw, TRS_EINVAL, "bag_weight_grad: NULL pointer");
+  TRS_REQUIRE(V > 0 && E > 0 && B >= 0, TRS_EINVAL, "bag_weight_grad: bad size V=%lld E=%d B=%lld", (long long)V, E,
+              (long long)B);
+  TRS_REQUIRE(L >= 1 && L <= 65535, TRS_EINVAL, "bag_weight_grad: list length L=%d outside [1, 65535]", L);
+  TRS_REQUIRE(exclude_row >= -1 && exclude_row < V, TRS_EINVAL, "bag_weight_grad: exclude_row %lld outside [-1, V)",
+              (long long)exclude_row);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "bag_weight_grad: dtype %d", dtype);
+  TRS_REQUIRE(idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EDTYPE, "bag_weight_grad: idx dtype %d", idx_dtype);
+  hipStream_t s = (hipStream_t)stream;
+#define TRS_CALL(T, I) return bag_weight_grad_launch<T, I>(table, g, (const I*)idx, B, L, E, V, exclude_row, dw, s)
+  if (dtype == TRS_F32) {
+    if (idx_dtype == TRS_I64) TRS_CALL(float, int64_t);
+    TRS_CALL(float, int32_t);
+  }
+  if (idx_dtype == TRS_I64) TRS_CALL(bf16_t, int64_t);
+  TRS_CALL(bf16_t, int32_t);
+#undef TRS_CALL
 }

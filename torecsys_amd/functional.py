@@ -609,12 +609,84 @@ class _BagPool(Function):
         return grad, None, None, None, None
 
 
+class _BagPoolMasked(Function):
+    """bag_pool with ``exclude_padding`` and / or ``per_sample_weights`` (trs_bag_pool_masked_fwd).  The row buckets are
+    the ones _BagPool builds (padding id skipped), so the sum / mean / max backward are its walks on another gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, idx, psw, mode, padding_idx, exclude, opt=None):
+        require_device(weight, idx, psw)
+        B, L = idx.shape
+        V, E = weight.shape
+        w = weight.contiguous()
+        wts = psw.contiguous() if psw is not None else None
+        out = torch.empty(B, E, dtype=w.dtype, device=w.device)
+        amax = torch.empty(B, E, dtype=torch.int16, device=w.device) if mode == 2 else None
+        # 1 / (live positions of the bag), 0 for an empty one: written by the kernel, never read back here
+        inv_cnt = torch.empty(B, dtype=torch.float32, device=w.device) if mode == 1 else None
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        ctx.exclude_row = ctx.padding_idx if exclude else -1
+        flag = _ErrFlag(w.device)
+        call("trs_bag_pool_masked_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, mode,
+             ctx.exclude_row, ptr(wts), ptr(out), ptr(amax), ptr(inv_cnt), ptr(flag.t), stream_ptr())
+        flag.check("bag_pool")
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        if ctx.needs_input_grad[0]:
+            prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
+        ctx.has = (wts is not None, amax is not None, inv_cnt is not None)
+        ctx.save_for_backward(idx, weight, *[t for t in (wts, amax, inv_cnt) if t is not None])
+        ctx.mode = mode
+        ctx.opt = opt
+        return out.unsqueeze(1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        idx, weight = ctx.saved_tensors[:2]
+        rest = list(ctx.saved_tensors[2:])
+        wts, amax, inv_cnt = (rest.pop(0) if h else None for h in ctx.has)
+        _adopt_grads(g)
+        V, E = weight.shape
+        B, L = idx.shape
+        g2 = g.reshape(B, E)
+        grad = dw = None
+        if wts is not None and ctx.needs_input_grad[2]:
+            g2 = g2.contiguous()
+            dw = torch.empty(B, L, dtype=wts.dtype, device=wts.device)
+            call("trs_bag_weight_grad", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(idx),
+                 index_dtype_code(idx), B, L, ctx.exclude_row, ptr(dw), stream_ptr())
+        if ctx.needs_input_grad[0]:
+            rb = row_buckets(idx, None, V, skip_row=ctx.skip)
+            if ctx.mode == 2 or wts is not None:
+                g2 = g2.contiguous()
+                grad = torch.empty(V, E, dtype=weight.dtype, device=weight.device)
+                entry = "argmax" if ctx.mode == 2 else "weighted"
+                ws_bytes = size_query(f"trs_scatter_{entry}_workspace_bytes", rb.BN, E)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
+                call(f"trs_scatter_rows_{entry}", ptr(g2), ptr(amax if ctx.mode == 2 else wts), ptr(rb.row_start),
+                     ptr(rb.perm), rb.BN, V, E, L, value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws),
+                     ws_bytes, stream_ptr())
+            else:
+                # sum / mean over the live positions: the per-sample gradient (mean: times 1 / cnt[b] in fp32, rounded
+                # once to the table's dtype, on (B,E)) broadcast over the bucketed -- live -- positions
+                g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
+                grad = _apply_or_grad(rb, weight, ctx.opt, g_bcast=g2, padding_row=ctx.padding_idx)
+        return grad, None, dw, None, None, None, None
+
+
 def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", padding_idx: Optional[int] = None,
-             opt=None) -> torch.Tensor:
-    """(B,1,E) pooled rows of a padded (B,L) list of ids: ``sum`` / ``mean`` (= sum / L: every position counts, the
-    padding row is read like any other, as F.embedding does) / ``max`` (first position wins a tie) in one pass over the
-    looked-up rows -- the (B,L,E) block of list_indices_emb.py:124-152 is never formed.  ``padding_idx``: the table row
-    that receives no gradient.  ``opt``: fused sparse optimizer (sum / mean only)."""
+             opt=None, *, exclude_padding: bool = False, per_sample_weights: Optional[torch.Tensor] = None
+             ) -> torch.Tensor:
+    """(B,1,E) pooled rows of a padded (B,L) list of ids: ``sum`` / ``mean`` / ``max`` (first position wins a tie) in one
+    pass over the looked-up rows -- the (B,L,E) block of list_indices_emb.py:124-152 is never formed.  ``padding_idx``:
+    the table row that receives no gradient.  ``opt``: fused sparse optimizer (sum / mean only, not with weights).
+
+    By default every position counts (``mean`` = sum / L) and the padding row is read like any other, as F.embedding
+    does.  ``exclude_padding=True`` (needs ``padding_idx``) is nn.EmbeddingBag's ``padding_idx``: positions holding the
+    padding id are not read and take no part -- sum and max over the live positions, mean over their count, an empty bag
+    a zero row (max: L <= 65534).  ``per_sample_weights`` (B,L), of the table's dtype and device, ``sum`` only:
+    out[b] = sum_l w[b,l] * table[idx[b,l]] over all positions, or over the live ones with ``exclude_padding``; it may
+    require grad (dw[b,l] = <g[b], table[idx[b,l]]>, 0 at excluded positions)."""
     if mode not in BAG_MODES:
         raise ValueError(f'bag_pool: mode must be one of {sorted(BAG_MODES)}, got {mode!r}')
     idx = _as_index(idx)
@@ -629,7 +701,33 @@ def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", paddin
                                   "(use sum / mean pooling, or a dense optimizer)")
     if padding_idx is not None and padding_idx < 0:
         padding_idx = weight.shape[0] + padding_idx
-    return _BagPool.apply(weight, idx, BAG_MODES[mode], padding_idx, opt)
+    if not exclude_padding and per_sample_weights is None:
+        return _BagPool.apply(weight, idx, BAG_MODES[mode], padding_idx, opt)
+    if exclude_padding:
+        if padding_idx is None:
+            raise ValueError("bag_pool: exclude_padding=True needs a padding_idx")
+        if not 0 <= padding_idx < weight.shape[0]:
+            raise ValueError(f"bag_pool: exclude_padding=True needs a padding row inside the table, got {padding_idx} "
+                             f"for {weight.shape[0]} rows")
+        if mode == "max" and idx.shape[1] > 65534:
+            raise ValueError(f"bag_pool: max pooling with exclude_padding=True: list length {idx.shape[1]} exceeds "
+                             "65534 (0xFFFF marks an empty bag)")
+    psw = per_sample_weights
+    if psw is not None:
+        if mode != "sum":
+            raise ValueError(f"bag_pool: per_sample_weights is only supported for mode='sum', got {mode!r}")
+        psw = psw.rename(None) if psw.has_names() else psw
+        if tuple(psw.shape) != tuple(idx.shape):
+            raise ValueError(f"bag_pool: per_sample_weights must be (B, L) = {tuple(idx.shape)}, got {tuple(psw.shape)}")
+        if psw.dtype != weight.dtype:
+            raise ValueError(f"bag_pool: per_sample_weights must have the table's dtype {weight.dtype}, got {psw.dtype}")
+        if psw.device != weight.device:
+            raise ValueError(f"bag_pool: per_sample_weights must be on the table's device {weight.device}, "
+                             f"got {psw.device}")
+        if opt is not None:
+            raise NotImplementedError("torecsys_amd: per_sample_weights with a fused sparse optimizer is not "
+                                      "implemented (use a dense optimizer)")
+    return _BagPoolMasked.apply(weight, idx, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), opt)
 
 
 # --------------------------------------------------------------------------------------------

@@ -188,8 +188,16 @@ class ListIndicesEmbedding(BaseInput):
     attributes and ``state_dict`` keys as the reference.
 
     ``avg_pooling`` / ``max_pooling`` run as one HIP pass over the looked-up rows (``functional.bag_pool``): the
-    (B,L,E) block of the reference is never formed, forward or backward.  Every list position counts, padding included
-    (the padding row is read like any other row, as the reference does).
+    (B,L,E) block of the reference is never formed, forward or backward.  By default every list position counts, padding
+    included (the padding row is read like any other row, as the reference does).
+
+    ``exclude_padding=True`` (not in the reference; needs a ``padding_idx``) pools like ``nn.EmbeddingBag(padding_idx=)``:
+    positions that hold the padding id are not read and take no part -- the mean is over the live positions of the
+    sample, the maximum cannot be the padding row's, a list of nothing but padding gives a zero row.
+    ``forward(inputs, per_sample_weights)`` with ``output_method='sum'`` weights every id of the list (a (B,L) tensor of the
+    table's dtype, which may require grad); ``set_schema(inputs, weights='column')`` lets ``Inputs`` hand that column
+    over.  Neither option changes names, shape or ``state_dict`` keys; neither is served together with ``use_attn=True``
+    (NotImplementedError) or ``output_method='none'`` (ValueError).
 
     Deliberate difference: ``output_method='mean'`` and ``'sum'`` RAISE in the reference (it strips the tensor names and
     then reduces over ``dim='N'``); here they do what its docstring promises -- ``mean`` equals ``avg_pooling``, ``sum``
@@ -222,7 +230,8 @@ class ListIndicesEmbedding(BaseInput):
 
     def __init__(self, embed_size: Optional[int] = None, field_size: Optional[int] = None,
                  padding_idx: Optional[int] = 0, nn_embedding: Optional[nn.Parameter] = None,
-                 use_attn: Optional[bool] = False, output_method: Optional[str] = 'avg_pooling', **kwargs):
+                 use_attn: Optional[bool] = False, output_method: Optional[str] = 'avg_pooling',
+                 exclude_padding: bool = False, **kwargs):
         super().__init__()
         if nn_embedding is not None:
             self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
@@ -250,17 +259,47 @@ class ListIndicesEmbedding(BaseInput):
         if output_method not in ('avg_pooling', 'max_pooling', 'mean', 'none', 'sum'):
             raise ValueError('output_method only allows ["avg_pooling", "max_pooling", "mean", "none", "sum"].')
         self.output_method = output_method
+        self.exclude_padding = bool(exclude_padding)
+        if self.exclude_padding:
+            if self.padding_idx is None:
+                raise ValueError('exclude_padding=True needs a padding_idx (nn_embedding= tables have none)')
+            self._check_masked_options('exclude_padding=True')
+
+    def _check_masked_options(self, what: str):
+        if self.use_attn:
+            raise NotImplementedError(f'torecsys_amd: {what} with use_attn=True is not implemented (the attention '
+                                      f'kernels take no key-padding mask)')
+        if self.output_method == 'none':
+            raise ValueError(f"{what} needs a pooling output_method, not 'none'")
+
+    def set_schema(self, inputs: Union[str, List[str]], **kwargs):
+        """``weights='column'``: ``Inputs.forward`` hands that column to ``forward`` as ``per_sample_weights``."""
+        weights = kwargs.get('weights', None)
+        if weights is None:
+            return super().set_schema(inputs)
+        if not isinstance(weights, str):
+            raise TypeError(f'weights must be a column name, got {type(weights).__name__}')
+        schema = namedtuple('Schema', ['inputs', 'weights'])
+        self.schema = schema(inputs=[inputs] if isinstance(inputs, str) else inputs, weights=weights)
 
     def set_fused_optimizer(self, opt):
         if opt is not None and self.output_method == 'max_pooling' and not self.use_attn:
             raise NotImplementedError('torecsys_amd: max_pooling with a fused sparse optimizer is not implemented')
+        if opt is not None and getattr(self.schema, 'weights', None) is not None:
+            raise NotImplementedError('torecsys_amd: per_sample_weights with a fused sparse optimizer is not implemented')
         return super().set_fused_optimizer(opt)
 
-    def forward(self, inputs: torch.Tensor) -> torch.Tensor:
+    def forward(self, inputs: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         idx = _strip(inputs)
         if idx.dim() != 2:
             raise ValueError(f'inputs must be (B, L), got {tuple(idx.shape)}')
         w = self.embedding.weight
+        if self.exclude_padding or per_sample_weights is not None:
+            if per_sample_weights is not None:
+                self._check_masked_options('per_sample_weights')
+            out = F_.bag_pool(w, idx, self._POOL[self.output_method], self.padding_idx, self.fused_optimizer,
+                              exclude_padding=self.exclude_padding, per_sample_weights=per_sample_weights)
+            return out.refine_names('B', 'N', 'E')
         mode = self._attn_pool_mode(idx)
         if mode is not None:
             a = self.attention
@@ -568,6 +607,8 @@ class Inputs(BaseInput):
             # SequenceIndicesEmbedding, which therefore never receives its lengths there); both names are routed here
             if emb_fn.__class__.__name__ in ('SequenceIndicesEmbedding', 'SequenceIndexEmbedding'):
                 args[k].append(inputs[emb_fn.schema.lengths])
+            elif getattr(emb_fn.schema, 'weights', None) is not None:      # ListIndicesEmbedding: per_sample_weights
+                args[k].append(inputs[emb_fn.schema.weights])
         # The lookups of a batch are independent of each other: every plain lookup after the first goes onto the "lookup"
         # side stream.  What pays is the BACKWARD: autograd runs a node's backward on the stream of its forward, so the
         # bucket walk of the E = 1 first-order table of an FM-family model (one walk and four small launches, ~45 us at the
