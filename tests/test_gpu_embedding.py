@@ -592,6 +592,26 @@ def test_gather_backward_of_a_field_constant_gradient(dev, dtype, tol, E):
     assert rel_err(wd.grad.float().cpu(), wd2.grad.float().cpu()) <= (1e-6 if dtype == torch.float32 else 8e-3)
 
 
+@pytest.mark.parametrize("dtype,E", [(torch.float32, 4 << k) for k in range(7)] +
+                         [(torch.bfloat16, 8 << k) for k in range(7)] + [(torch.float32, 12)])
+def test_gather_rows_every_lane_group_width(dev, dtype, E):
+    """Rows of 16 * 2^k bytes, k = 0..6, take the lane-group kernels (2^k lanes of a wave per row); any other width
+    (fp32 E = 12) takes the element path.  Every width goes through the lookup and its backward: the forward is a copy,
+    and the gradient is integer-valued, so the sum over the repeated id is exact in any order (|sum| <= 8 in bf16)."""
+    from torecsys_amd import functional as F_
+    B, N, V = 3, 2, 5
+    g = torch.Generator().manual_seed(E)
+    w = torch.randn(V, E, generator=g).to(dtype)
+    idx = torch.tensor([[0, 3], [4, 1], [3, 2]])                     # id 3 twice, once per field
+    gy = torch.randint(-4, 5, (B, N, E), generator=g).to(dtype)
+    wd = w.to(dev).requires_grad_()
+    out = F_.gather_rows(wd, idx.to(dev))
+    assert torch.equal(out.detach().cpu(), w[idx])
+    out.backward(gy.to(dev))
+    ref = torch.zeros(V, E, dtype=dtype).index_add_(0, idx.reshape(-1), gy.reshape(-1, E))
+    assert torch.equal(wd.grad.cpu(), ref)
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 1e-2)])
 @pytest.mark.parametrize("B,N,E,Vf,hot", [(1024, 10, 16, 100, False), (4096, 39, 64, 7, True), (300, 5, 10, 9, False),
                                            (512, 6, 4, 50, False), (512, 6, 8, 50, True)])     # rows of ONE 16-byte vector

@@ -19,25 +19,16 @@
 
 namespace trs {
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // block-wide reductions over 256 threads through 4 LDS slots (+ broadcast)
 __device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
+  v = group_sum_down<64>(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
 __device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
+  v = group_max_down<64>(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -136,7 +127,7 @@ __global__ __launch_bounds__(256) void afm_fwd_kernel(const T* __restrict__ x, c
       float part = 0.f;
       if (lane < A) part = fmaf(fmaxf(acc[0], 0.f), l.w2[lane], part);
       if (64 + lane < A) part = fmaf(fmaxf(acc[1], 0.f), l.w2[64 + lane], part);
-      part = wave_sum(part);
+      part = group_sum_down<64>(part);
       if (lane == 0) l.lg[p] = part + bias2;
     }
     __syncthreads();
@@ -332,10 +323,6 @@ static size_t afm_fwd_mfma_lds(int N, int E) {
 // the per-field LDS gradient block with plain read-modify-writes inside a round.
 __host__ __device__ inline int afm_rounds(int N) { return sched_rounds(N); }
 __host__ __device__ inline int afm_width(int N) { return sched_width(N); }
-__device__ __forceinline__ void afm_build_schedule(int* sched, int N) {
-  const int R = sched_rounds(N), H = sched_width(N);
-  for (int t = threadIdx.x; t < R * H; t += blockDim.x) sched[t] = sched_entry(t / H, t % H, N);
-}
 
 // Backward.  Per sample: d(score)_p = g_attn_p + g_out . prod_p;  softmax backward;  then per pair
 //   dh_a = d(logit)_p w2_a [h_a > 0];   dprod = score_p g_out + W1^T dh;   dx_i += dprod * x_j, dx_j += dprod * x_i
@@ -357,7 +344,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const T* __restrict__ g_ou
   int* sched = reinterpret_cast<int*>(dw1 + A * E);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   afm_stage_weights(l, W1, b1, w2, E, A, true);
-  afm_build_schedule(sched, N);
+  build_pair_schedule(sched, N);
   for (int k = threadIdx.x; k < A * E; k += 256) dw1[k] = 0.f;
   float dw1r[ES][AMAX];
 #pragma unroll
@@ -385,7 +372,7 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const T* __restrict__ g_ou
       float d = 0.f;
       if (lane < E) d = l.vec[lane] * l.xs[i * E + lane] * l.xs[j * E + lane];
       if (64 + lane < E) d = fmaf(l.vec[64 + lane], l.xs[i * E + 64 + lane] * l.xs[j * E + 64 + lane], d);
-      d = wave_sum(d);
+      d = group_sum_down<64>(d);
       if (lane == 0) l.aux[p] = (d + (g_attn != nullptr ? to_f32(g_attn[b * P + p]) : 0.f)) * l.msk[p];
     }
     __syncthreads();
@@ -651,7 +638,7 @@ __global__ __launch_bounds__(64 * WAVES) void afm_bwd_mfma_kernel(const bf16_t* 
     __syncthreads();
     float s = 0.f;
     for (int p = threadIdx.x; p < P; p += NTHR) s += lg[p] * aux[p];
-    s = wave_sum(s);
+    s = group_sum_down<64>(s);
     if (lane == 0) red[wave] = s;
     __syncthreads();
     s = 0.f;
@@ -831,7 +818,7 @@ __global__ __launch_bounds__(64 * WAVES) void afm_bwd_mfma_kernel(const bf16_t* 
         atomicAdd(&dw1[A * E + A + a], v2);
       }
     }
-  db2r = wave_sum(db2r);
+  db2r = group_sum_down<64>(db2r);
   if (lane == 0) atomicAdd(&dw1[A * E + 2 * A], db2r);
   __syncthreads();
   float* mine = partial + (size_t)blockIdx.x * (A * E + 2 * A + 1);
@@ -887,35 +874,19 @@ extern "C" int trs_afm_fwd_dropout(const void* x, const void* W1, const void* b1
     const size_t lds = afm_fwd_mfma_lds(N, E);
     // one round of workgroups, each walking its share of the samples (A = E = 64: 162 registers = 3 workgroups per CU;
     // the fixed 1024 this replaces ran as a round of 768 and one of 256)
-#define TRS_AFM_M(AT_, KS_)                                                                                       \
-  do {                                                                                                            \
-    auto kern = afm_fwd_mfma_kernel<AT_, KS_>;                                                                    \
-    static size_t cap_lds = ~(size_t)0;                                                                           \
-    static int cap = 0;                                                                                           \
-    if (cap_lds != lds) { cap = resident_blocks((const void*)kern, 256, lds); cap_lds = lds; }                    \
-    const int grid = (int)std::min<int64_t>(B, cap);                                                              \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)W1, (const bf16_t*)b1, \
-                       (const bf16_t*)w2, (const bf16_t*)b2, B, N, (bf16_t*)out, (bf16_t*)attn, keep, keep_scale,  \
-                       (bf16_t*)attn_drop);                                                                       \
-  } while (0)
-#define TRS_AFM_MK(AT_)                                 \
-  do {                                                  \
-    if (E == 32) TRS_AFM_M(AT_, 1);                     \
-    else if (E == 64) TRS_AFM_M(AT_, 2);                \
-    else TRS_AFM_M(AT_, 4);                             \
-  } while (0)
-    switch (A / 16) {
-      case 1: TRS_AFM_MK(1); break;
-      case 2: TRS_AFM_MK(2); break;
-      case 3: TRS_AFM_MK(3); break;
-      case 4: TRS_AFM_MK(4); break;
-      case 5: TRS_AFM_MK(5); break;
-      case 6: TRS_AFM_MK(6); break;
-      case 7: TRS_AFM_MK(7); break;
-      default: TRS_AFM_MK(8); break;
-    }
-#undef TRS_AFM_MK
-#undef TRS_AFM_M
+    // A = 16 .. 128 in steps of 16 and E = 32, 64 or 128 by the test above
+    dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(A / 16, [&](auto at_c) {
+      dispatch_int<1, 2, 4>(E / 32, [&](auto ks_c) {
+        auto kern = afm_fwd_mfma_kernel<decltype(at_c)::value, decltype(ks_c)::value>;
+        static size_t cap_lds = ~(size_t)0;
+        static int cap = 0;
+        if (cap_lds != lds) { cap = resident_blocks((const void*)kern, 256, lds); cap_lds = lds; }
+        const int grid = (int)std::min<int64_t>(B, cap);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)W1, (const bf16_t*)b1,
+                           (const bf16_t*)w2, (const bf16_t*)b2, B, N, (bf16_t*)out, (bf16_t*)attn, keep, keep_scale,
+                           (bf16_t*)attn_drop);
+      });
+    });
     return check_launch("afm_fwd(mfma)");
   }
   const size_t lds = afm_lds_floats(N, E, A, P, false) * 4;
@@ -999,17 +970,9 @@ extern "C" int trs_afm_bwd_dropout(const void* g_out, const void* g_attn, const 
                            B, N, (bf16_t*)gx, part, keep, keep_scale, T, *packed);
       }
     };
-    auto launch_at = [&](auto at_c) {
-      if (E == 32) launch(at_c, std::integral_constant<int, 1>{});
-      else if (E == 64) launch(at_c, std::integral_constant<int, 2>{});
-      else launch(at_c, std::integral_constant<int, 4>{});
-    };
-    switch (A / 32) {
-      case 1: launch_at(std::integral_constant<int, 2>{}); break;
-      case 2: launch_at(std::integral_constant<int, 4>{}); break;
-      case 3: launch_at(std::integral_constant<int, 6>{}); break;
-      default: launch_at(std::integral_constant<int, 8>{}); break;
-    }
+    dispatch_int<2, 4, 6, 8>(A / 16, [&](auto at_c) {
+      dispatch_int<1, 2, 4>(E / 32, [&](auto ks_c) { launch(at_c, ks_c); });
+    });
     if (rc_launch != 0) return rc_launch;
     const int n = A * E + 2 * A + 1;
     hipLaunchKernelGGL(afm_reduce_partials_kernel, dim3((n + 255) / 256), dim3(256), 0, s, part, mgrid, n, A, E, gW1,

@@ -109,11 +109,6 @@ __device__ __forceinline__ void ap_gemm(float* C, int scm, int scn, bool acc, co
 }
 
 // S <- P = softmax_rows(S): 4 adjacent lanes per row (rows >= L idle but keep the shuffles whole)
-__device__ __forceinline__ float ap_quad_sum(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  return v;
-}
 __device__ __forceinline__ void ap_softmax_rows(float* S, int ss, int L) {
   const int row = threadIdx.x >> 2, sub = threadIdx.x & 3;
   const bool live = row < L;
@@ -130,7 +125,7 @@ __device__ __forceinline__ void ap_softmax_rows(float* S, int ss, int L) {
       p[c] = e;
       sum += e;
     }
-  sum = ap_quad_sum(sum);
+  sum = group_sum_up<4>(sum);
   if (live) {
     const float inv = 1.f / sum;
     for (int c = sub; c < L; c += 4) p[c] *= inv;

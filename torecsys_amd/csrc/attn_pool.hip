@@ -159,7 +159,7 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(
         float s = 0.f;
         if (row < L)
           for (int e = sub; e < E; e += 4) s = fmaf(X[row * sx + e], to_f32(g[h * E + e]), s);
-        s = ap_quad_sum(s);
+        s = group_sum_up<4>(s);
         if (row < L && sub == 0) rv[row] = s;
       }
       ap_head_probs<MF>(S, ss, QK, sqk, L, E, d, h, alpha, cscale, pbar + h * L);
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(AP_THREADS) void attn_pool_bwd_kernel(
         float t = 0.f;
         if (row < L)
           for (int c = sub; c < L; c += 4) t = fmaf(p[c], rv[c], t);
-        t = ap_quad_sum(t);
+        t = group_sum_up<4>(t);
         if (row < L)
           for (int c = sub; c < L; c += 4) p[c] = cscale * p[c] * (rv[c] - t);
       }

@@ -180,49 +180,35 @@ __global__ __launch_bounds__(256) void bag_pool_elem_kernel(const T* __restrict_
   }
 }
 
-static int bag_log2_lanes(int row_bytes) {
-  if (row_bytes % 16 != 0) return -1;
-  const int L = row_bytes / 16;
-  if (!is_pow2(L) || L > 64) return -1;
-  int l = 0;
-  while ((1 << l) < L) ++l;
-  return l;
-}
-
 template <typename T, typename IdxT, bool MASK, bool WGT>
 static int bag_pool_launch(const void* table, const IdxT* idx, int64_t B, int Lb, int E, int64_t V, int mode, void* out,
                            uint16_t* amax, int32_t* err_flag, int64_t pad, const void* wts_, float* inv_cnt,
                            hipStream_t s) {
   const T* wts = (const T*)wts_;
-  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  const int lg = log2_lanes(E * (int)sizeof(T));
   const float scale = mode == BAG_MEAN ? 1.f / (float)Lb : 1.f;
   if (lg >= 0 && aligned16(table) && aligned16(out) && aligned16(amax)) {
     const int grid = stream_grid(B << lg, 256, 256 * 16);
     const bool stream = (size_t)V * E * sizeof(T) > BAG_STREAM_BYTES;
-#define TRS_BAG2(LG, MX, CH_, ST)                                                                              \
-  hipLaunchKernelGGL((bag_pool_group_kernel<T, IdxT, LG, MX, CH_, ST, MASK, WGT>), dim3(grid), dim3(256), 0, s,  \
-                     (const uint4*)table, idx, B, Lb, V, scale, (uint4*)out, amax, err_flag, pad, wts, inv_cnt)
-#define TRS_BAG(LG)                                      \
-  if (mode == BAG_MAX) {                                 \
-    if constexpr (!WGT) {      /* weights: sum only */   \
-      if (stream) TRS_BAG2(LG, true, 4, true);           \
-      else TRS_BAG2(LG, true, 4, false);                 \
-    }                                                    \
-  } else {                                               \
-    if (stream) TRS_BAG2(LG, false, 8, true);            \
-    else TRS_BAG2(LG, false, 8, false);                  \
-  }
-    switch (lg) {
-      case 0: TRS_BAG(0); break;
-      case 1: TRS_BAG(1); break;
-      case 2: TRS_BAG(2); break;
-      case 3: TRS_BAG(3); break;
-      case 4: TRS_BAG(4); break;
-      case 5: TRS_BAG(5); break;
-      default: TRS_BAG(6); break;
-    }
-#undef TRS_BAG
-#undef TRS_BAG2
+    dispatch_lanes(lg, [&](auto lg_c) {
+      auto launch = [&](auto mx_c, auto ch_c, auto st_c) {
+        hipLaunchKernelGGL((bag_pool_group_kernel<T, IdxT, decltype(lg_c)::value, decltype(mx_c)::value,
+                                                  decltype(ch_c)::value, decltype(st_c)::value, MASK, WGT>),
+                           dim3(grid), dim3(256), 0, s, (const uint4*)table, idx, B, Lb, V, scale, (uint4*)out, amax,
+                           err_flag, pad, wts, inv_cnt);
+      };
+      constexpr std::integral_constant<int, 4> ch4{};
+      constexpr std::integral_constant<int, 8> ch8{};
+      if (mode == BAG_MAX) {
+        if constexpr (!WGT) {      /* weights: sum only */
+          if (stream) launch(std::true_type{}, ch4, std::true_type{});
+          else launch(std::true_type{}, ch4, std::false_type{});
+        }
+      } else {
+        if (stream) launch(std::false_type{}, ch8, std::true_type{});
+        else launch(std::false_type{}, ch8, std::false_type{});
+      }
+    });
   } else {
     const int grid = stream_grid(B * E, 256, 256 * 16);
     if (mode == BAG_MAX) {
@@ -471,8 +457,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __re
         for (int u = 0; u < U; ++u)
           if (pp[u] >= 0) acc += bag_argmax_term<T, WGT>(g, amax, wts, pp[u], N, E, e);
       }
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+      acc = group_sum_down<64>(acc);
       if (lane == 0) grad[r * E + e] = from_f32<T>(acc);
     }
   }
@@ -482,11 +467,10 @@ __global__ void bag_zero_counter_kernel(int32_t* __restrict__ p) {
   if (threadIdx.x == 0) *p = 0;
 }
 
-static size_t bag_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // queue entries: a row is queued with more than 32 (element path; one id) or 64 lookups (one (row, chunk) pair per chunk)
 static size_t bag_queue_entries(int64_t BN) { return (size_t)(BN / BAG_LONG_ROW + BN / BAG_LONG_CHUNK + 2); }
 static size_t bag_queue_bytes(int64_t BN) {
-  return bag_align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
+  return align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
 }
 
 template <typename T, bool WGT>
@@ -494,29 +478,19 @@ static int bag_argmax_launch(const void* g, const uint16_t* amax, const void* wt
                              const int32_t* perm, int64_t V, int E, int N, int64_t padding_row, void* grad,
                              int32_t* long_rows, float* scratch, hipStream_t s) {
   const T* wts = (const T*)wts_;
-  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  const int lg = log2_lanes(E * (int)sizeof(T));
   hipLaunchKernelGGL(bag_zero_counter_kernel, dim3(1), dim3(64), 0, s, long_rows);
   if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(grad)) {
     const int grid = stream_grid(V << lg, 256, 256 * 32);
-#define TRS_BAGB(LG)                                                                                                  \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, wts,  \
-                       row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);                         \
-    hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, wts,  \
-                       row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch);                                \
-    hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,          \
-                       long_rows, scratch);                                                                            \
-  } while (0)
-    switch (lg) {
-      case 0: TRS_BAGB(0); break;
-      case 1: TRS_BAGB(1); break;
-      case 2: TRS_BAGB(2); break;
-      case 3: TRS_BAGB(3); break;
-      case 4: TRS_BAGB(4); break;
-      case 5: TRS_BAGB(5); break;
-      default: TRS_BAGB(6); break;
-    }
-#undef TRS_BAGB
+    dispatch_lanes(lg, [&](auto lg_c) {
+      constexpr int LG = decltype(lg_c)::value;
+      hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, wts,
+                         row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);
+      hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, wts,
+                         row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch);
+      hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,
+                         long_rows, scratch);
+    });
   } else {
     hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T, WGT>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
                        (const T*)g, amax, wts, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows);
@@ -557,8 +531,7 @@ __global__ __launch_bounds__(256) void bag_weight_grad_group_kernel(const uint4*
         for (int k = 0; k < VE; ++k) d += x[k] * y[k];
       }
     }
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) d += __shfl_xor(d, m, 64);
+    d = group_sum_up<L>(d);
     if (p < BN && lane_v == 0) dw[p] = from_f32<T>(d);
   }
 }
@@ -584,23 +557,14 @@ __global__ __launch_bounds__(256) void bag_weight_grad_elem_kernel(const T* __re
 template <typename T, typename IdxT>
 static int bag_weight_grad_launch(const void* table, const void* g, const IdxT* idx, int64_t B, int Lb, int E, int64_t V,
                                   int64_t pad, void* dw, hipStream_t s) {
-  const int lg = bag_log2_lanes(E * (int)sizeof(T));
+  const int lg = log2_lanes(E * (int)sizeof(T));
   const int64_t BN = B * Lb;
   if (lg >= 0 && aligned16(table) && aligned16(g)) {
     const int grid = stream_grid(BN << lg, 256, 256 * 32);
-#define TRS_BAGW(LG)                                                                                                  \
-  hipLaunchKernelGGL((bag_weight_grad_group_kernel<T, IdxT, LG>), dim3(grid), dim3(256), 0, s, (const uint4*)table,   \
-                     (const uint4*)g, idx, BN, Lb, V, pad, (T*)dw)
-    switch (lg) {
-      case 0: TRS_BAGW(0); break;
-      case 1: TRS_BAGW(1); break;
-      case 2: TRS_BAGW(2); break;
-      case 3: TRS_BAGW(3); break;
-      case 4: TRS_BAGW(4); break;
-      case 5: TRS_BAGW(5); break;
-      default: TRS_BAGW(6); break;
-    }
-#undef TRS_BAGW
+    dispatch_lanes(lg, [&](auto lg_c) {
+      hipLaunchKernelGGL((bag_weight_grad_group_kernel<T, IdxT, decltype(lg_c)::value>), dim3(grid), dim3(256), 0, s,
+                         (const uint4*)table, (const uint4*)g, idx, BN, Lb, V, pad, (T*)dw);
+    });
   } else {
     hipLaunchKernelGGL((bag_weight_grad_elem_kernel<T, IdxT>), dim3(stream_grid(BN, 256, 256 * 32)), dim3(256), 0, s,
                        (const T*)table, (const T*)g, idx, BN, Lb, E, V, pad, (T*)dw);
@@ -641,7 +605,7 @@ extern "C" int trs_bag_pool_fwd(const void* table, int64_t V, int32_t E, int32_t
 extern "C" size_t trs_scatter_argmax_workspace_bytes(int64_t BN, int32_t E) {
   // [queue of hot rows + its counter][chunk partials of the rows of several chunks: entries x E fp32]
   if (BN < 0 || E < 0) return 0;
-  return bag_queue_bytes(BN) + bag_align_up(bag_queue_entries(BN) * (size_t)E * 4, 256);
+  return bag_queue_bytes(BN) + align_up(bag_queue_entries(BN) * (size_t)E * 4, 256);
 }
 
 extern "C" int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, const int32_t* row_start,

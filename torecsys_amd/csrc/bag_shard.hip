@@ -147,41 +147,22 @@ __global__ __launch_bounds__(256) void bag_seg_pool_elem_kernel(const T* __restr
   }
 }
 
-static int bags_log2_lanes(int row_bytes) {
-  if (row_bytes % 16 != 0) return -1;
-  const int L = row_bytes / 16;
-  if (!is_pow2(L) || L > 64) return -1;
-  int l = 0;
-  while ((1 << l) < L) ++l;
-  return l;
-}
-
 template <typename T>
 static int bag_seg_pool_launch(const void* shard, int64_t n_valid, int E, const int32_t* ids, int64_t n,
                                const int32_t* seg_start, int64_t S, float* out, int32_t* err_flag, hipStream_t s) {
-  const int lg = bags_log2_lanes(E * (int)sizeof(T));
+  const int lg = log2_lanes(E * (int)sizeof(T));
   if (lg >= 0 && aligned16(shard) && aligned16(out)) {
     const int grid = stream_grid(S << lg, 256, 256 * 16);
     const bool stream = (size_t)n_valid * E * sizeof(T) > BAGS_STREAM_BYTES;
-#define TRS_BAGS(LG)                                                                                              \
-  do {                                                                                                            \
-    if (stream)                                                                                                   \
-      hipLaunchKernelGGL((bag_seg_pool_group_kernel<T, LG, 8, true>), dim3(grid), dim3(256), 0, s,                 \
-                         (const uint4*)shard, n_valid, ids, n, seg_start, S, (uint4*)out, err_flag);               \
-    else                                                                                                          \
-      hipLaunchKernelGGL((bag_seg_pool_group_kernel<T, LG, 8, false>), dim3(grid), dim3(256), 0, s,                \
-                         (const uint4*)shard, n_valid, ids, n, seg_start, S, (uint4*)out, err_flag);               \
-  } while (0)
-    switch (lg) {
-      case 0: TRS_BAGS(0); break;
-      case 1: TRS_BAGS(1); break;
-      case 2: TRS_BAGS(2); break;
-      case 3: TRS_BAGS(3); break;
-      case 4: TRS_BAGS(4); break;
-      case 5: TRS_BAGS(5); break;
-      default: TRS_BAGS(6); break;
-    }
-#undef TRS_BAGS
+    dispatch_lanes(lg, [&](auto lg_c) {
+      constexpr int LG = decltype(lg_c)::value;
+      if (stream)
+        hipLaunchKernelGGL((bag_seg_pool_group_kernel<T, LG, 8, true>), dim3(grid), dim3(256), 0, s,
+                           (const uint4*)shard, n_valid, ids, n, seg_start, S, (uint4*)out, err_flag);
+      else
+        hipLaunchKernelGGL((bag_seg_pool_group_kernel<T, LG, 8, false>), dim3(grid), dim3(256), 0, s,
+                           (const uint4*)shard, n_valid, ids, n, seg_start, S, (uint4*)out, err_flag);
+    });
   } else {
     hipLaunchKernelGGL((bag_seg_pool_elem_kernel<T>), dim3(stream_grid(S * E, 256, 256 * 16)), dim3(256), 0, s,
                        (const T*)shard, n_valid, ids, n, seg_start, S, E, out, err_flag);
@@ -315,22 +296,13 @@ __global__ __launch_bounds__(256) void bag_expand_elem_kernel(const T* __restric
 template <typename T>
 static int bag_expand_launch(const void* g_all, int E, const int32_t* ids, int64_t n, const int32_t* seg_start, int64_t S,
                              int64_t n_valid, int64_t pad_row, void* grad_rows, int32_t* ids_bwd, hipStream_t s) {
-  const int lg = bags_log2_lanes(E * (int)sizeof(T));
+  const int lg = log2_lanes(E * (int)sizeof(T));
   if (lg >= 0 && aligned16(g_all) && aligned16(grad_rows)) {
     const int grid = stream_grid(S << lg, 256, 256 * 16);
-#define TRS_BAGX(LG)                                                                                                 \
-  hipLaunchKernelGGL((bag_expand_group_kernel<LG>), dim3(grid), dim3(256), 0, s, (const uint4*)g_all, ids, n, seg_start, \
-                     S, n_valid, pad_row, (uint4*)grad_rows, ids_bwd)
-    switch (lg) {
-      case 0: TRS_BAGX(0); break;
-      case 1: TRS_BAGX(1); break;
-      case 2: TRS_BAGX(2); break;
-      case 3: TRS_BAGX(3); break;
-      case 4: TRS_BAGX(4); break;
-      case 5: TRS_BAGX(5); break;
-      default: TRS_BAGX(6); break;
-    }
-#undef TRS_BAGX
+    dispatch_lanes(lg, [&](auto lg_c) {
+      hipLaunchKernelGGL((bag_expand_group_kernel<decltype(lg_c)::value>), dim3(grid), dim3(256), 0, s,
+                         (const uint4*)g_all, ids, n, seg_start, S, n_valid, pad_row, (uint4*)grad_rows, ids_bwd);
+    });
   } else {
     hipLaunchKernelGGL((bag_expand_elem_kernel<T>), dim3(stream_grid(S * E, 256, 256 * 16)), dim3(256), 0, s,
                        (const T*)g_all, ids, n, seg_start, S, E, n_valid, pad_row, (T*)grad_rows, ids_bwd);

@@ -654,22 +654,15 @@ int cross_mfma_fwd(const void* x, const void* W, const void* b, int64_t rows, in
   const bool resident = lds <= 64 * 1024;
   const int64_t ntiles = (rows + 15) / 16;
   const int grid = (int)std::min<int64_t>((ntiles + 7) / 8, resident ? 256 * 3 : 256 * 8);
-#define TRS_CF(NT_)                                                                                              \
-  do {                                                                                                           \
-    if (resident)                                                                                                \
-      hipLaunchKernelGGL((cross_mfma_fwd_kernel<NT_, true>), dim3(grid), dim3(256), lds, s, (const uint4*)x,     \
-                         (const uint4*)Wp, bp, rows, L, (uint4*)out);                                            \
-    else                                                                                                         \
-      hipLaunchKernelGGL((cross_mfma_fwd_kernel<NT_, false>), dim3(grid), dim3(256), 0, s, (const uint4*)x,      \
-                         (const uint4*)Wp, bp, rows, L, (uint4*)out);                                            \
-  } while (0)
-  switch (E / 16) {
-    case 2: TRS_CF(2); break;
-    case 4: TRS_CF(4); break;
-    case 6: TRS_CF(6); break;
-    default: TRS_CF(8); break;
-  }
-#undef TRS_CF
+  dispatch_int<2, 4, 6, 8>(E / 16, [&](auto nt_c) {      // cross_mfma_covers: E = 32, 64, 96 or 128
+    constexpr int NT = decltype(nt_c)::value;
+    if (resident)
+      hipLaunchKernelGGL((cross_mfma_fwd_kernel<NT, true>), dim3(grid), dim3(256), lds, s, (const uint4*)x,
+                         (const uint4*)Wp, bp, rows, L, (uint4*)out);
+    else
+      hipLaunchKernelGGL((cross_mfma_fwd_kernel<NT, false>), dim3(grid), dim3(256), 0, s, (const uint4*)x,
+                         (const uint4*)Wp, bp, rows, L, (uint4*)out);
+  });
   return check_launch("cross_fwd(mfma)");
 }
 
@@ -716,28 +709,14 @@ int cross_mfma_bwd(const void* x, const void* W, const void* b, const void* g, i
   const int pgrid = std::min(64, (L * E * E / 8 + 255) / 256);
   hipLaunchKernelGGL((cross_prepack_kernel), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)W, (const bf16_t*)b, Wp, bp, E,
                      L, Wtp);
-#define TRS_CB(NT_, L_)                                                                                              \
-  return cross_bwd_launch<NT_, L_>(x, g, (const uint4*)Wp, (const uint4*)Wtp, bp, rows, dx, dWpart, dbpart, dW, db, \
-                                   detach_first, s)
-  if (E == 32) {
-    switch (L) {
-      case 1: TRS_CB(2, 1);
-      case 2: TRS_CB(2, 2);
-      case 3: TRS_CB(2, 3);
-      case 4: TRS_CB(2, 4);
-      case 5: TRS_CB(2, 5);
-      default: TRS_CB(2, 6);
-    }
-  }
-  switch (L) {
-    case 1: TRS_CB(4, 1);
-    case 2: TRS_CB(4, 2);
-    case 3: TRS_CB(4, 3);
-    case 4: TRS_CB(4, 4);
-    case 5: TRS_CB(4, 5);
-    default: TRS_CB(4, 6);
-  }
-#undef TRS_CB
+  int rc = TRS_OK;      // E = 32 or 64 and 1 <= L <= 6 by the test above
+  dispatch_int<2, 4>(E / 16, [&](auto nt_c) {
+    dispatch_int<1, 2, 3, 4, 5, 6>(L, [&](auto l_c) {
+      rc = cross_bwd_launch<decltype(nt_c)::value, decltype(l_c)::value>(x, g, (const uint4*)Wp, (const uint4*)Wtp, bp, rows,
+                                                                         dx, dWpart, dbpart, dW, db, detach_first, s);
+    });
+  });
+  return rc;
 }
 
 }  // namespace trs

@@ -48,12 +48,6 @@ __host__ __device__ inline size_t dr_fixed_bytes(int N, int R, int K) {
   return (floats * sizeof(float) + 15) & ~(size_t)15;
 }
 
-__device__ __forceinline__ float dr_wave_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 template <typename T, int K, bool VEC>
 __global__ __launch_bounds__(DR_THREADS) void dr_fwd_kernel(const float* __restrict__ pri, const T* __restrict__ noise,
                                                             int64_t B, int N, int R, int iters, int NC,
@@ -154,7 +148,7 @@ __global__ __launch_bounds__(DR_THREADS) void dr_fwd_kernel(const float* __restr
       if (wave < K) {
         float s = 0.f;
         for (int rr = lane; rr < R; rr += 64) s = fmaf(z_s[wave * R + rr], z_s[wave * R + rr], s);
-        s = dr_wave_sum(s);
+        s = group_sum_up<64>(s);
         if (lane == 0) n2_s[wave] = s;
       }
       __syncthreads();
@@ -214,8 +208,8 @@ __global__ __launch_bounds__(DR_BWD_THREADS) void dr_bwd_kernel(const T* __restr
         n2 = fmaf(zr[rr], zr[rr], n2);
         gz = fmaf(to_f32(gr[rr]), zr[rr], gz);
       }
-      n2 = dr_wave_sum(n2);
-      gz = dr_wave_sum(gz);
+      n2 = group_sum_up<64>(n2);
+      gz = group_sum_up<64>(gz);
       const float s = sqrtf(n2), den = (1.f + n2) * (s + 1e-8f);
       const float f = n2 > 0.f ? n2 / den : 0.f;
       const float f2 = n2 > 0.f ? 2.f * gz * ((s + 1e-8f) - 0.5f * s * (1.f + n2)) / den / den : 0.f;
@@ -279,16 +273,9 @@ static size_t dr_fwd_lds(int N, int R, int K, int dtype, int NC) {
 
 template <typename T, bool VEC>
 static const void* dr_fwd_kernel_of(int K) {
-  switch (K) {
-    case 1: return (const void*)dr_fwd_kernel<T, 1, VEC>;
-    case 2: return (const void*)dr_fwd_kernel<T, 2, VEC>;
-    case 3: return (const void*)dr_fwd_kernel<T, 3, VEC>;
-    case 4: return (const void*)dr_fwd_kernel<T, 4, VEC>;
-    case 5: return (const void*)dr_fwd_kernel<T, 5, VEC>;
-    case 6: return (const void*)dr_fwd_kernel<T, 6, VEC>;
-    case 7: return (const void*)dr_fwd_kernel<T, 7, VEC>;
-    default: return (const void*)dr_fwd_kernel<T, 8, VEC>;
-  }
+  const void* kern = nullptr;      // dr_check admitted 1 <= K <= DR_MAX_K
+  dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto k_c) { kern = (const void*)dr_fwd_kernel<T, decltype(k_c)::value, VEC>; });
+  return kern;
 }
 
 // persistent grid of the forward: the workgroups resident at once on the current device (asked of the runtime once per
@@ -335,20 +322,10 @@ template <typename T, int VE>
 static int dr_bwd_launch(const void* noise, const float* c, const float* z, const void* gout, int64_t B, int N, int R,
                          int K, void* dpri, hipStream_t s) {
   const int grid = stream_grid(B * DR_BWD_THREADS, DR_BWD_THREADS, 256 * 16);
-#define TRS_DR(K_)                                                                                                   \
-  hipLaunchKernelGGL((dr_bwd_kernel<T, K_, VE>), dim3(grid), dim3(DR_BWD_THREADS), 0, s, (const T*)noise, c, z,       \
-                     (const T*)gout, B, N, R, (T*)dpri)
-  switch (K) {
-    case 1: TRS_DR(1); break;
-    case 2: TRS_DR(2); break;
-    case 3: TRS_DR(3); break;
-    case 4: TRS_DR(4); break;
-    case 5: TRS_DR(5); break;
-    case 6: TRS_DR(6); break;
-    case 7: TRS_DR(7); break;
-    default: TRS_DR(8); break;
-  }
-#undef TRS_DR
+  dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(K, [&](auto k_c) {
+    hipLaunchKernelGGL((dr_bwd_kernel<T, decltype(k_c)::value, VE>), dim3(grid), dim3(DR_BWD_THREADS), 0, s,
+                       (const T*)noise, c, z, (const T*)gout, B, N, R, (T*)dpri);
+  });
   return check_launch("dynamic_routing_bwd");
 }
 

@@ -101,8 +101,7 @@ __global__ __launch_bounds__(256) void embed_fm_group_kernel(
       for (int k = 0; k < VE; k += 4) dst[k / 4] = make_float4(s[k], s[k + 1], s[k + 2], s[k + 3]);
     }
     if (GATHER && first_table != nullptr) {
-#pragma unroll
-      for (int m = L >> 1; m >= 1; m >>= 1) f1 += __shfl_xor(f1, m, 64);
+      f1 = group_sum_down<L>(f1);
       if (lane_v == 0 && first != nullptr) first[b] = from_f32<T>(f1);
     }
   }
@@ -149,15 +148,6 @@ __global__ __launch_bounds__(256) void embed_fm_elem_kernel(
 
 constexpr size_t EMBED_STREAM_BYTES = (size_t)512 << 20;      // twice the Infinity Cache
 
-static int log2_lanes(int row_bytes) {
-  if (row_bytes % 16 != 0) return -1;
-  const int L = row_bytes / 16;
-  if (!is_pow2(L) || L > 64) return -1;
-  int l = 0;
-  while ((1 << l) < L) ++l;
-  return l;
-}
-
 template <typename T, typename IdxT, bool GATHER>
 static int embed_fm_launch(const void* src, const IdxT* idx, const int64_t* offsets, int64_t B, int N, int E,
                            int64_t V, void* emb, void* fm, float* fm_sum, const void* first_table, void* first,
@@ -168,27 +158,15 @@ static int embed_fm_launch(const void* src, const IdxT* idx, const int64_t* offs
     const int L = 1 << lg;
     const int grid = stream_grid(B * L, 256, 256 * 16);
     const bool stream = GATHER && (size_t)V * E * sizeof(T) > EMBED_STREAM_BYTES;
-#define TRS_EF2(LG, ST)                                                                                   \
-  hipLaunchKernelGGL((embed_fm_group_kernel<T, IdxT, LG, GATHER, ST>), dim3(grid), dim3(256), 0, s,        \
-                     (const uint4*)src, idx, offsets, B, N, V, (uint4*)emb, (uint4*)fm, fm_sum,            \
-                     (const T*)first_table, (T*)first, err_flag, (T*)first_vals)
-#define TRS_EF(LG)                 \
-  if (GATHER && stream) {          \
-    TRS_EF2(LG, GATHER);           \
-  } else {                         \
-    TRS_EF2(LG, false);            \
-  }
-    switch (lg) {
-      case 0: TRS_EF(0); break;
-      case 1: TRS_EF(1); break;
-      case 2: TRS_EF(2); break;
-      case 3: TRS_EF(3); break;
-      case 4: TRS_EF(4); break;
-      case 5: TRS_EF(5); break;
-      default: TRS_EF(6); break;
-    }
-#undef TRS_EF
-#undef TRS_EF2
+    dispatch_lanes(lg, [&](auto lg_c) {
+      auto launch = [&](auto st_c) {
+        hipLaunchKernelGGL((embed_fm_group_kernel<T, IdxT, decltype(lg_c)::value, GATHER, decltype(st_c)::value>),
+                           dim3(grid), dim3(256), 0, s, (const uint4*)src, idx, offsets, B, N, V, (uint4*)emb, (uint4*)fm,
+                           fm_sum, (const T*)first_table, (T*)first, err_flag, (T*)first_vals);
+      };
+      if (GATHER && stream) launch(std::bool_constant<GATHER>{});
+      else launch(std::false_type{});
+    });
   } else {
     const int grid = stream_grid(B * E, 256, 256 * 16);
     hipLaunchKernelGGL((embed_fm_elem_kernel<T, IdxT, GATHER>), dim3(grid), dim3(256), 0, s, (const T*)src, idx,

@@ -121,21 +121,12 @@ static int launch_gather_vec(const void* table, const IdxT* idx, const int64_t* 
   const int64_t total = rows * vpr;
   constexpr int UNROLL = 4;
   const int grid = stream_grid((total + UNROLL - 1) / UNROLL, 256, 256 * 32);
-#define TRS_GV(SH)                                                                                  \
-  hipLaunchKernelGGL((gather_rows_vec_kernel<IdxT, SH, UNROLL>), dim3(grid), dim3(256), 0, s,       \
-                     (const uint4*)table, idx, offsets, (uint4*)out, total, vpr, N, V, err_flag,  \
-                     (size_t)V * vpr * 16 > ((size_t)512 << 20))
-  switch (vpr) {
-    case 1: TRS_GV(0); break;
-    case 2: TRS_GV(1); break;
-    case 4: TRS_GV(2); break;
-    case 8: TRS_GV(3); break;
-    case 16: TRS_GV(4); break;
-    case 32: TRS_GV(5); break;
-    case 64: TRS_GV(6); break;
-    default: TRS_GV(-1); break;
-  }
-#undef TRS_GV
+  // SH = log2(vpr) for a row of 1..64 vectors that is a power of two, else -1 (the kernel divides by vpr)
+  dispatch_int<-1, 0, 1, 2, 3, 4, 5, 6>(log2_lanes(vpr * 16), [&](auto sh_c) {
+    hipLaunchKernelGGL((gather_rows_vec_kernel<IdxT, decltype(sh_c)::value, UNROLL>), dim3(grid), dim3(256), 0, s,
+                       (const uint4*)table, idx, offsets, (uint4*)out, total, vpr, N, V, err_flag,
+                       (size_t)V * vpr * 16 > ((size_t)512 << 20));
+  });
   return check_launch("gather_rows");
 }
 
@@ -475,29 +466,20 @@ static int fa_dispatch(const void* const* tables, int64_t V, int E, int dtype, c
   if (row_bytes % 16 == 0 && aligned16(out)) {
     const int vpr = row_bytes / 16;
     const int64_t total = B * N * N * vpr;
-    if (is_pow2(vpr) && vpr <= 64 && N <= 4096) {
-      int lg = 0;
-      while ((1 << lg) < vpr) ++lg;
+    const int lg = log2_lanes(row_bytes);
+    if (lg >= 0 && N <= 4096) {
       const bool stream = (size_t)N * V * row_bytes > ((size_t)512 << 20);
       const int grid = (int)std::min<int64_t>(B, 256 * 8);
       const size_t lds = (size_t)N * 8;
-#define TRS_FAG(LG)                                                                                                     \
-  if (stream)                                                                                                           \
-    hipLaunchKernelGGL((fa_gather_rows_kernel<IdxT, LG, true>), dim3(grid), dim3(256), lds, s,                           \
-                       (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);                      \
-  else                                                                                                                  \
-    hipLaunchKernelGGL((fa_gather_rows_kernel<IdxT, LG, false>), dim3(grid), dim3(256), lds, s,                          \
-                       (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag)
-      switch (lg) {
-        case 0: TRS_FAG(0); break;
-        case 1: TRS_FAG(1); break;
-        case 2: TRS_FAG(2); break;
-        case 3: TRS_FAG(3); break;
-        case 4: TRS_FAG(4); break;
-        case 5: TRS_FAG(5); break;
-        default: TRS_FAG(6); break;
-      }
-#undef TRS_FAG
+      dispatch_lanes(lg, [&](auto lg_c) {
+        constexpr int LG = decltype(lg_c)::value;
+        if (stream)
+          hipLaunchKernelGGL((fa_gather_rows_kernel<IdxT, LG, true>), dim3(grid), dim3(256), lds, s,
+                             (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);
+        else
+          hipLaunchKernelGGL((fa_gather_rows_kernel<IdxT, LG, false>), dim3(grid), dim3(256), lds, s,
+                             (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);
+      });
       return check_launch("fa_gather_rows");
     }
     hipLaunchKernelGGL((fa_gather_vec_kernel<IdxT>), dim3(stream_grid(total, 256, 256 * 32)), dim3(256), 0, s,

@@ -81,8 +81,7 @@ __global__ __launch_bounds__(BCE_BLOCK) void bce_partial_kernel(const T* __restr
   const int64_t stride = (int64_t)gridDim.x * BCE_BLOCK;
   for (int64_t i = (int64_t)blockIdx.x * BCE_BLOCK + threadIdx.x; i < B; i += stride)
     acc += bce_term(to_f32(x[i]), to_f32(y[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = group_sum_down<64>(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -98,8 +97,7 @@ __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict_
                                                         float* __restrict__ loss) {
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 64) acc += partial[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = group_sum_down<64>(acc);
   if (threadIdx.x == 0) *loss = acc * inv_B;
 }
 
@@ -114,8 +112,7 @@ __global__ __launch_bounds__(1024) void bce_one_kernel(const T* __restrict__ x, 
   __shared__ float red[16];
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < B; i += 1024) acc += bce_term(to_f32(x[i]), to_f32(y[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = group_sum_down<64>(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {

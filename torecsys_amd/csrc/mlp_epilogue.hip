@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void rowdot_fwd_kernel(const uint4* __restrict
       for (int u = 0; u < U; ++u) {
         const int64_t r = r0 + u * step;
         float a = acc[u];
-        for (int o = lpr >> 1; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        a = group_sum_down(a, lpr);
         if (v == 0 && r < rows) out[r] = from_f32<T>(a + b0);
       }
     }

@@ -887,7 +887,6 @@ __global__ __launch_bounds__(256) void mlp_colsum_reduce_kernel(const float* __r
   if (ty == 0 && i < n) out[i] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
 }
 
-static inline int pad32(int v) { return (v + 31) / 32 * 32; }
 constexpr int MF_GRID = 256;
 
 static bool mlp_fused_covers(int L, const int32_t* w) {

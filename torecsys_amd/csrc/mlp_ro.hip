@@ -38,8 +38,6 @@ __global__ __launch_bounds__(256) void mlp_ro_prepack_kernel(RoPackArgs a) {
       j.bf[t] = (j.b != nullptr && t < j.out_f) ? to_f32(j.b[t]) : 0.f;
 }
 
-static inline int ro_pad32(int x) { return (x + 31) / 32 * 32; }
-
 template <class Cfg>
 static bool ro_matches(int L, const int32_t* w, bool reversed) {
   if (L != Cfg::L) return false;
@@ -95,7 +93,7 @@ int mlp_ro_fwd(const void* x, int64_t rows, int L, const int32_t* widths, const 
   a.colsum_in = nullptr;
   char* wsp = (char*)workspace;
   size_t wbytes = 0;
-  for (int l = 0; l < L; ++l) wbytes += (size_t)ro_pad32(widths[l]) * ro_pad32(widths[l + 1]) * 2;
+  for (int l = 0; l < L; ++l) wbytes += (size_t)pad32(widths[l]) * pad32(widths[l + 1]) * 2;
   wbytes = (wbytes + 255) / 256 * 256;
   float* bias_base = (float*)(wsp + wbytes);
   a.bias = bias_base;
@@ -104,7 +102,7 @@ int mlp_ro_fwd(const void* x, int64_t rows, int L, const int32_t* widths, const 
   int pk_blocks = 1;
   size_t woff = 0, boff = 0;
   for (int l = 0; l < L; ++l) {
-    const int KS = ro_ks(widths[l]), N = ro_pad32(widths[l + 1]);
+    const int KS = ro_ks(widths[l]), N = pad32(widths[l + 1]);
     pk.job[l] = RoPackJob{(const bf16_t*)weights[l], (const bf16_t*)biases[l], (bf16_t*)(wsp + woff), bias_base + boff,
                           widths[l + 1], widths[l], N / 32, KS, N};
     pk_blocks = std::max(pk_blocks, std::min(256, (N / 32 * KS * 64 + 255) / 256));
@@ -139,7 +137,7 @@ int mlp_ro_bwd(const void* gy, int64_t rows, int L, const int32_t* widths, const
   const int nparts = grid * (8 / RO_BWD_RT);
   char* wsp = (char*)workspace;
   size_t wbytes = 0;
-  for (int l = 0; l < L; ++l) wbytes += (size_t)ro_pad32(widths[l]) * ro_pad32(widths[l + 1]) * 2;
+  for (int l = 0; l < L; ++l) wbytes += (size_t)pad32(widths[l]) * pad32(widths[l + 1]) * 2;
   wbytes = (wbytes + 255) / 256 * 256;
   float* part_base = (float*)(wsp + wbytes);
   RoPackArgs pk;
@@ -152,11 +150,11 @@ int mlp_ro_bwd(const void* gy, int64_t rows, int L, const int32_t* widths, const
   a.colsum_in = part_base + poff;
   cs->part[cs->count] = a.colsum_in;
   cs->out[cs->count] = gbias[L - 1];
-  cs->n[cs->count++] = ro_pad32(widths[L]);
-  poff += (size_t)nparts * ro_pad32(widths[L]);
+  cs->n[cs->count++] = pad32(widths[L]);
+  poff += (size_t)nparts * pad32(widths[L]);
   for (int sidx = 0; sidx < L; ++sidx) {
     const int l = L - 1 - sidx;
-    const int KS = ro_ks(widths[l + 1]), N = ro_pad32(widths[l]);      // contraction over layer l's outputs, output = its inputs
+    const int KS = ro_ks(widths[l + 1]), N = pad32(widths[l]);      // contraction over layer l's outputs, output = its inputs
     pk.job[sidx] = RoPackJob{(const bf16_t*)weights[l], nullptr, (bf16_t*)(wsp + woff), nullptr, widths[l + 1], widths[l], N / 32, KS, 0};
     pk_blocks = std::max(pk_blocks, std::min(256, (N / 32 * KS * 64 + 255) / 256));
     RoLayer& ly = a.layer[sidx];

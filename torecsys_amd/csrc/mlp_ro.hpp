@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "lds_dma.hpp"
 #include "trs_common.hpp"
 
 namespace trs {
@@ -138,27 +139,6 @@ struct RoArgs {
   float* colsum_in;     // backward: [gridDim.x * waves][K0] partial column sums of the input rows, zeroed by the host
 };
 
-__device__ __forceinline__ unsigned ro_lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-}
-
-// one 1 KB piece (16 bytes per lane) from global memory (uniform ``src`` + this lane's ``voff``) straight into LDS at the
-// wave-uniform address ``lds_dst``.  M0 belongs to the compiler: saved and restored inside the statement.
-__device__ __forceinline__ void ro_dma1(const char* src, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(dst), "s"(src) : "memory");
-}
-
-// the same as a buffer operation (offsets past the end read nothing)
-__device__ __forceinline__ void ro_dma1_buf(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(dst), "s"(rs) : "memory");
-}
-
 template <int N>
 __device__ __forceinline__ void ro_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -221,7 +201,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
   // ---- weight stream: chunk q (counted from this workgroup's first pass on) lives in ring slot q % 3.  The ring
   // positions are carried along (one add and a wrap per chunk) instead of computed from q: everything below is one
   // basic block per pass, and 41 chunks' worth of independent address arithmetic is what the scheduler hoists and spills.
-  const unsigned ring = ro_lds_addr(smem);
+  const unsigned ring = lds_addr(smem);
   const unsigned lane16 = lane * 16;
   unsigned dma_at = ring;                               // slot the next copy goes to (wave-uniform)
   unsigned pass_zero = 0;      // 0, redefined per pass behind an asm, like the weight pointers: keeps ~300 loop-invariant
@@ -233,7 +213,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
     constexpr int cq = decltype(cq_)::value, c2 = cq % NC, l2 = Cfg::layer_of(c2), ct2 = Cfg::ct_of(c2), P = Cfg::ks(l2);
     const int p0 = (P * wave) / NW, p1 = (P * (wave + 1)) / NW;      // the chunk's P (= its layer's KS) KB are split over the waves
     if (p0 + i < p1)
-      ro_dma1(wfl[l2] + (unsigned)((ct2 * P + p0 + i) * 1024), lane16, dma_at + (p0 + i) * 1024);
+      lds_dma1(wfl[l2] + (unsigned)((ct2 * P + p0 + i) * 1024), lane16, dma_at + (p0 + i) * 1024);
   };
   constexpr int MAXP = (RO_MAXKS + NW - 1) / NW;      // pieces per wave and chunk, at most
   ro_for<0, RO_AHEAD>([&](auto cq) __attribute__((always_inline)) {
@@ -459,7 +439,7 @@ __global__ __launch_bounds__(512 / RT, 1) void mlp_ro_kernel(RoArgs a) {
     if (mask_has(l_)) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)      // piece q: chunks 4 q .. 4 q + 3, this lane's two slots (16 bytes)
-        if (4 * q < Cfg::ct(l)) ro_dma1_buf(rm, mrec + q * 4096, ring + mstage + q * 1024);
+        if (4 * q < Cfg::ct(l)) lds_dma1_buf(rm, mrec + q * 4096, ring + mstage + q * 1024);
     }
   };
 

@@ -27,19 +27,6 @@ constexpr int MOE_LANE_COLS = 16;                       // columns a lane of the
 constexpr int MOE_GATE_MAX_K = 64 * MOE_LANE_COLS;      // = functional.MOE_GATE_MAX_K
 constexpr int MOE_TILE_COLS = 8;                        // general backward: columns per lane and tile
 
-template <int L>
-__device__ __forceinline__ float moe_group_max(float v) {
-#pragma unroll
-  for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-template <int L>
-__device__ __forceinline__ float moe_group_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // z[0..VE) = logits + bias for vector v of row `row` (NV vectors of T per row); fp32 logits are VE/4 16-byte vectors
 template <typename T>
 __device__ __forceinline__ void moe_load_z(const uint4* __restrict__ logits, const uint4* __restrict__ bias, int64_t row,
@@ -95,7 +82,7 @@ __global__ __launch_bounds__(256) void moe_gate_group_kernel(const uint4* __rest
 #pragma unroll
         for (int k = 0; k < VE; ++k) m = fmaxf(m, p[r][k]);
       }
-      m = moe_group_max<L>(m);
+      m = group_max_up<L>(m);
       float s = 0.f;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(256) void moe_gate_group_kernel(const uint4* __rest
           s += p[r][k];
         }
       }
-      const float inv = 1.f / moe_group_sum<L>(s);
+      const float inv = 1.f / group_sum_up<L>(s);
       if (!BWD) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(256) void moe_gate_group_kernel(const uint4* __rest
             acc[r][k] += go[k] * p[r][k];
           }
         }
-        d = moe_group_sum<L>(d);
+        d = group_sum_up<L>(d);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const int v = r * L + lane_v;
@@ -157,9 +144,6 @@ __global__ __launch_bounds__(256) void moe_gate_group_kernel(const uint4* __rest
 // ---------------------------------------------------------------------------------------------
 // general path: element loads, one wave per row (forward) or per sample (backward)
 
-__device__ __forceinline__ float moe_wave_max(float v) { return moe_group_max<64>(v); }
-__device__ __forceinline__ float moe_wave_sum(float v) { return moe_group_sum<64>(v); }
-
 template <typename T>
 __device__ __forceinline__ float moe_z(const float* __restrict__ zrow, const T* __restrict__ brow, int k) {
   return brow != nullptr ? zrow[k] + to_f32(brow[k]) : zrow[k];
@@ -182,10 +166,10 @@ __global__ __launch_bounds__(256) void moe_gate_fwd_elem_kernel(const float* __r
     T* orow = out + row * K;
     float m = -INFINITY;
     for (int k = lane; k < K; k += 64) m = fmaxf(m, moe_z<T>(zrow, brow, k));
-    m = moe_wave_max(m);
+    m = group_max_up<64>(m);
     float s = 0.f;
     for (int k = lane; k < K; k += 64) s += expf(moe_z<T>(zrow, brow, k) - m);
-    const float inv = 1.f / moe_wave_sum(s);
+    const float inv = 1.f / group_sum_up<64>(s);
     for (int k = lane; k < K; k += 64)
       orow[k] = from_f32<T>(expf(moe_z<T>(zrow, brow, k) - m) * inv * to_f32(erow[k]));
   }
@@ -213,15 +197,15 @@ __global__ __launch_bounds__(256) void moe_gate_bwd_elem_kernel(const float* __r
         const T* grow = gout + row * K;
         float m = -INFINITY;
         for (int k = lane; k < K; k += 64) m = fmaxf(m, moe_z<T>(zrow, brow, k));
-        m = moe_wave_max(m);
+        m = group_max_up<64>(m);
         float s = 0.f, u = 0.f;
         for (int k = lane; k < K; k += 64) {
           const float x = expf(moe_z<T>(zrow, brow, k) - m);
           s += x;
           u += x * (to_f32(grow[k]) * to_f32(erow[k]));
         }
-        const float inv = 1.f / moe_wave_sum(s);
-        const float d = moe_wave_sum(u) * inv;
+        const float inv = 1.f / group_sum_up<64>(s);
+        const float d = group_sum_up<64>(u) * inv;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
           const int k = k0 + lane + 64 * j;
@@ -263,24 +247,15 @@ static int moe_gate_launch(const float* logits, const void* bias, const void* ex
     while ((1 << lg) < NV && lg < 6) ++lg;
     const int per_lane = (NV + (1 << lg) - 1) >> lg;      // 1 below 64 lanes; <= 4 (fp32) or 2 (bf16) by the cap
     const int grid = stream_grid(B << lg, 256, 256 * 16);
-#define TRS_MOE(LG, R_)                                                                                                 \
-  hipLaunchKernelGGL((moe_gate_group_kernel<T, LG, R_, BWD>), dim3(grid), dim3(256), 0, s, (const uint4*)logits,        \
-                     (const uint4*)bias, (const uint4*)experts, (const uint4*)gout, B, G, NV, (uint4*)out,             \
-                     (uint4*)gexperts)
-    switch (lg) {
-      case 0: TRS_MOE(0, 1); break;
-      case 1: TRS_MOE(1, 1); break;
-      case 2: TRS_MOE(2, 1); break;
-      case 3: TRS_MOE(3, 1); break;
-      case 4: TRS_MOE(4, 1); break;
-      case 5: TRS_MOE(5, 1); break;
-      default:
-        if (per_lane == 1) TRS_MOE(6, 1);
-        else if (per_lane == 2) TRS_MOE(6, 2);
-        else if constexpr (sizeof(T) == 4) TRS_MOE(6, 4);      // 3 or 4 vectors of 4 floats
-        break;
-    }
-#undef TRS_MOE
+    auto launch = [&](auto lg_c, auto r_c) {
+      hipLaunchKernelGGL((moe_gate_group_kernel<T, decltype(lg_c)::value, decltype(r_c)::value, BWD>), dim3(grid),
+                         dim3(256), 0, s, (const uint4*)logits, (const uint4*)bias, (const uint4*)experts,
+                         (const uint4*)gout, B, G, NV, (uint4*)out, (uint4*)gexperts);
+    };
+    if (lg < 6) dispatch_int<0, 1, 2, 3, 4, 5>(lg, [&](auto lg_c) { launch(lg_c, int_c<1>{}); });
+    else if (per_lane == 1) launch(int_c<6>{}, int_c<1>{});
+    else if (per_lane == 2) launch(int_c<6>{}, int_c<2>{});
+    else if constexpr (sizeof(T) == 4) launch(int_c<6>{}, int_c<4>{});      // 3 or 4 vectors of 4 floats
   } else if (!BWD) {
     moe_last_path = 2;
     hipLaunchKernelGGL((moe_gate_fwd_elem_kernel<T>), dim3(stream_grid(B * G * 64, 256, 256 * 16)), dim3(256), 0, s,

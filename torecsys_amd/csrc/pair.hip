@@ -462,23 +462,13 @@ static int pair_dot_fwd_mfma(const void* x, void* out, int64_t B, int N, int E, 
   const int NT = (N + 15) / 16, KS = E / 32;
   const int grid = (int)std::min<int64_t>((B + 3) / 4, 256 * 8);
   const size_t lds_f = (size_t)4 * (((N * (N - 1) / 2) + 7) & ~7) * 2;
-#define TRS_PF(NT_, KS_)                                                                                      \
-  hipLaunchKernelGGL((pair_dot_fwd_mfma_kernel<NT_, KS_>), dim3(grid), dim3(256), lds_f, s, (const bf16_t*)x,  \
-                     (bf16_t*)out, B, N, E)
-#define TRS_PF_K(NT_)               \
-  do {                              \
-    if (KS == 1) TRS_PF(NT_, 1);    \
-    else if (KS == 2) TRS_PF(NT_, 2); \
-    else TRS_PF(NT_, 4);            \
-  } while (0)
-  switch (NT) {
-    case 1: TRS_PF_K(1); break;
-    case 2: TRS_PF_K(2); break;
-    case 3: TRS_PF_K(3); break;
-    default: TRS_PF_K(4); break;
-  }
-#undef TRS_PF_K
-#undef TRS_PF
+  // pair_mfma_ok admitted N <= 64 and E = 32, 64 or 128: NT = 1..4, KS = 1, 2 or 4
+  dispatch_int<1, 2, 3, 4>(NT, [&](auto nt_c) {
+    dispatch_int<1, 2, 4>(KS, [&](auto ks_c) {
+      hipLaunchKernelGGL((pair_dot_fwd_mfma_kernel<decltype(nt_c)::value, decltype(ks_c)::value>), dim3(grid), dim3(256),
+                         lds_f, s, (const bf16_t*)x, (bf16_t*)out, B, N, E);
+    });
+  });
   return check_launch("pair_dot_fwd(mfma)");
 }
 
@@ -488,23 +478,13 @@ static int embed_pair_dot_mfma(const void* table, const IdxT* idx, const int64_t
   const int NT = (N + 15) / 16, KS = E / 32;
   const int grid = (int)std::min<int64_t>((B + 3) / 4, 256 * 8);
   const size_t lds_f = (size_t)4 * (((N * (N - 1) / 2) + 7) & ~7) * 2;
-#define TRS_PG(NT_, KS_)                                                                                           \
-  hipLaunchKernelGGL((pair_dot_fwd_mfma_kernel<NT_, KS_, true, IdxT>), dim3(grid), dim3(256), lds_f, s,             \
-                     (const bf16_t*)table, (bf16_t*)out, B, N, E, idx, offsets, V, (bf16_t*)emb, err_flag)
-#define TRS_PG_K(NT_)               \
-  do {                              \
-    if (KS == 1) TRS_PG(NT_, 1);    \
-    else if (KS == 2) TRS_PG(NT_, 2); \
-    else TRS_PG(NT_, 4);            \
-  } while (0)
-  switch (NT) {
-    case 1: TRS_PG_K(1); break;
-    case 2: TRS_PG_K(2); break;
-    case 3: TRS_PG_K(3); break;
-    default: TRS_PG_K(4); break;
-  }
-#undef TRS_PG_K
-#undef TRS_PG
+  dispatch_int<1, 2, 3, 4>(NT, [&](auto nt_c) {
+    dispatch_int<1, 2, 4>(KS, [&](auto ks_c) {
+      hipLaunchKernelGGL((pair_dot_fwd_mfma_kernel<decltype(nt_c)::value, decltype(ks_c)::value, true, IdxT>), dim3(grid),
+                         dim3(256), lds_f, s, (const bf16_t*)table, (bf16_t*)out, B, N, E, idx, offsets, V, (bf16_t*)emb,
+                         err_flag);
+    });
+  });
   return check_launch("embed_pair_dot");
 }
 
@@ -514,33 +494,22 @@ static int pair_dot_bwd_mfma(const void* x, const void* g, void* dx, int64_t B, 
   const int P = N * (N - 1) / 2;
   const size_t lds = (size_t)((P + 7) & ~7) * 2 + (size_t)4 * (NP * (NPK + 8) + E * (NPK + 8)) * 2;
   const int grid = (int)std::min<int64_t>((B + 3) / 4, 256 * 8);
-#define TRS_PB(NT_, KE_)                                                                                      \
-  do {                                                                                                        \
-    auto kern = pair_dot_bwd_mfma_kernel<NT_, KE_>;                                                           \
-    static bool attr_set = false;                                                                             \
-    if (!attr_set && lds > 64 * 1024) {                                                                       \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=     \
-          hipSuccess)                                                                                         \
-        return check_launch("pair_dot_bwd(mfma): LDS attribute");                                             \
-      attr_set = true;                                                                                        \
-    }                                                                                                         \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)g, (bf16_t*)dx,  \
-                       B, N, E);                                                                              \
-  } while (0)
-#define TRS_PB_K(NT_)               \
-  do {                              \
-    if (KE == 2) TRS_PB(NT_, 2);    \
-    else if (KE == 4) TRS_PB(NT_, 4); \
-    else TRS_PB(NT_, 8);            \
-  } while (0)
-  switch (NT) {
-    case 1: TRS_PB_K(1); break;
-    case 2: TRS_PB_K(2); break;
-    case 3: TRS_PB_K(3); break;
-    default: TRS_PB_K(4); break;
-  }
-#undef TRS_PB_K
-#undef TRS_PB
+  int rc = TRS_OK;
+  dispatch_int<1, 2, 3, 4>(NT, [&](auto nt_c) {
+    dispatch_int<2, 4, 8>(KE, [&](auto ke_c) {
+      auto kern = pair_dot_bwd_mfma_kernel<decltype(nt_c)::value, decltype(ke_c)::value>;
+      static bool attr_set = false;
+      if (!attr_set && lds > 64 * 1024) {
+        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+          rc = check_launch("pair_dot_bwd(mfma): LDS attribute");
+          return;
+        }
+        attr_set = true;
+      }
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, (const bf16_t*)x, (const bf16_t*)g, (bf16_t*)dx, B, N, E);
+    });
+  });
+  if (rc != TRS_OK) return rc;
   return check_launch("pair_dot_bwd(mfma)");
 }
 
@@ -985,36 +954,25 @@ static int ffm_fused_dispatch(const void* const* tables, int64_t V, int E, int d
   const bool vec = rb % 16 == 0 && aligned16(out);
   const int upr = vec ? rb / 16 : E;
   if (vec && is_pow2(upr) && upr <= 64 && N <= 255) {      // whole 16-byte units, a power of two of them per row: the sample-wise kernel
-    int lg = 0;
-    while ((1 << lg) < upr) ++lg;
+    const int lg = log2_lanes(rb);
     const int P = N * (N - 1) / 2;
     const size_t lds = (size_t)((2 * P + 15) / 16) * 16 + (size_t)N * 8;
     const bool stream = (size_t)N * V * rb > ((size_t)512 << 20);
     const int grid = (int)std::min<int64_t>(B, 256 * 8);
-#define TRS_FFM_ROWS(TT, LG)                                                                                              \
-  if (stream)                                                                                                             \
-    hipLaunchKernelGGL((ffm_fused_fwd_rows_kernel<TT, IdxT, LG, true>), dim3(grid), dim3(256), lds, s,                     \
-                       (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);                        \
-  else                                                                                                                    \
-    hipLaunchKernelGGL((ffm_fused_fwd_rows_kernel<TT, IdxT, LG, false>), dim3(grid), dim3(256), lds, s,                    \
-                       (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag)
-#define TRS_FFM_ROWS_T(TT)                    \
-  switch (lg) {                               \
-    case 0: TRS_FFM_ROWS(TT, 0); break;       \
-    case 1: TRS_FFM_ROWS(TT, 1); break;       \
-    case 2: TRS_FFM_ROWS(TT, 2); break;       \
-    case 3: TRS_FFM_ROWS(TT, 3); break;       \
-    case 4: TRS_FFM_ROWS(TT, 4); break;       \
-    case 5: TRS_FFM_ROWS(TT, 5); break;       \
-    default: TRS_FFM_ROWS(TT, 6); break;      \
-  }
-    if (dtype == TRS_F32) {
-      TRS_FFM_ROWS_T(float)
-    } else {
-      TRS_FFM_ROWS_T(bf16_t)
-    }
-#undef TRS_FFM_ROWS_T
-#undef TRS_FFM_ROWS
+    auto launch = [&](auto t) {
+      using TT = decltype(t);
+      dispatch_lanes(lg, [&](auto lg_c) {
+        constexpr int LG = decltype(lg_c)::value;
+        if (stream)
+          hipLaunchKernelGGL((ffm_fused_fwd_rows_kernel<TT, IdxT, LG, true>), dim3(grid), dim3(256), lds, s,
+                             (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);
+        else
+          hipLaunchKernelGGL((ffm_fused_fwd_rows_kernel<TT, IdxT, LG, false>), dim3(grid), dim3(256), lds, s,
+                             (const uint4* const*)tables, idx, offsets, (uint4*)out, B, N, V, err_flag);
+      });
+    };
+    if (dtype == TRS_F32) launch(float{});
+    else launch(bf16_t{});
     return check_launch("ffm_fused_fwd");
   }
   const int grid = stream_grid(B * N * N * upr, 256, 256 * 32);
@@ -1052,37 +1010,26 @@ static int ffm_fused_bwd_dispatch(const void* const* tables, int64_t V, int E, i
   const bool vec = rb % 16 == 0 && aligned16(gout);
   const int upr = vec ? rb / 16 : E;
   if (vec && is_pow2(upr) && upr <= 64 && N < 65536 && BN < ((int64_t)1 << 31)) {
-    int lg = 0;
-    while ((1 << lg) < upr) ++lg;
+    const int lg = log2_lanes(rb);
     const bool stream = (size_t)N * V * rb > ((size_t)512 << 20);
     const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + N - 1) / N);
     const dim3 grid((unsigned)stream_grid(V * upr, 256, 256 * 4), (unsigned)N);
-#define TRS_FFMB(TT, LG)                                                                                                 \
-  if (stream)                                                                                                           \
-    hipLaunchKernelGGL((ffm_fused_bwd_rows_kernel<TT, IdxT, LG, true>), grid, dim3(256), 0, s, (const uint4* const*)tables, \
-                       idx, offsets, (const uint4*)gout, row_start, perm, (unsigned)N, rcpN, V, (uint4* const*)grads,    \
-                       rid_t, BN / N);                                                                                  \
-  else                                                                                                                  \
-    hipLaunchKernelGGL((ffm_fused_bwd_rows_kernel<TT, IdxT, LG, false>), grid, dim3(256), 0, s, (const uint4* const*)tables, \
-                       idx, offsets, (const uint4*)gout, row_start, perm, (unsigned)N, rcpN, V, (uint4* const*)grads,    \
-                       rid_t, BN / N)
-#define TRS_FFMB_T(TT)                   \
-  switch (lg) {                          \
-    case 0: TRS_FFMB(TT, 0); break;      \
-    case 1: TRS_FFMB(TT, 1); break;      \
-    case 2: TRS_FFMB(TT, 2); break;      \
-    case 3: TRS_FFMB(TT, 3); break;      \
-    case 4: TRS_FFMB(TT, 4); break;      \
-    case 5: TRS_FFMB(TT, 5); break;      \
-    default: TRS_FFMB(TT, 6); break;     \
-  }
-    if (dtype == TRS_F32) {
-      TRS_FFMB_T(float)
-    } else {
-      TRS_FFMB_T(bf16_t)
-    }
-#undef TRS_FFMB_T
-#undef TRS_FFMB
+    auto launch = [&](auto t) {
+      using TT = decltype(t);
+      dispatch_lanes(lg, [&](auto lg_c) {
+        constexpr int LG = decltype(lg_c)::value;
+        if (stream)
+          hipLaunchKernelGGL((ffm_fused_bwd_rows_kernel<TT, IdxT, LG, true>), grid, dim3(256), 0, s,
+                             (const uint4* const*)tables, idx, offsets, (const uint4*)gout, row_start, perm, (unsigned)N,
+                             rcpN, V, (uint4* const*)grads, rid_t, BN / N);
+        else
+          hipLaunchKernelGGL((ffm_fused_bwd_rows_kernel<TT, IdxT, LG, false>), grid, dim3(256), 0, s,
+                             (const uint4* const*)tables, idx, offsets, (const uint4*)gout, row_start, perm, (unsigned)N,
+                             rcpN, V, (uint4* const*)grads, rid_t, BN / N);
+      });
+    };
+    if (dtype == TRS_F32) launch(float{});
+    else launch(bf16_t{});
     return check_launch("ffm_fused_bwd");
   }
   const int grid = stream_grid((int64_t)N * V * upr, 256, 256 * 32);

@@ -18,12 +18,6 @@
 
 namespace trs {
 
-__device__ __forceinline__ float group_reduce(float v, int EL) {
-  // sum over the EL-lane group (EL a power of two <= 64)
-  for (int o = EL >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <typename T>
 __device__ __forceinline__ void stage_block(const T* __restrict__ src, float* __restrict__ dst, int n) {
   for (int e = threadIdx.x; e < n; e += blockDim.x) dst[e] = to_f32(src[e]);
@@ -46,13 +40,6 @@ __device__ __forceinline__ void build_pair_lut(int* lut, int N) {
     lut[p] = (i << 16) | j;
   }
 }
-
-// Conflict-free pair schedule (see trs_common.hpp): sched[r*H + k] = (i << 16) | j, or -1.
-__device__ __forceinline__ void build_round_schedule(int* sched, int N) {
-  const int R = sched_rounds(N), H = sched_width(N);
-  for (int t = threadIdx.x; t < R * H; t += blockDim.x) sched[t] = sched_entry(t / H, t % H, N);
-}
-__device__ __forceinline__ int pair_index(int i, int j, int N) { return i * (2 * N - i - 1) / 2 + j - i - 1; }
 
 template <typename T>
 __global__ __launch_bounds__(256) void pairw_dot_fwd_kernel(const T* __restrict__ x, const T* __restrict__ kern, int kp,
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(256) void pairw_dot_fwd_kernel(const T* __restrict_
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int p = p0 + u * groups;
-        const float r = group_reduce(acc[u], EL);
+        const float r = group_sum_down(acc[u], EL);
         if (e0 == 0 && p < P) out[b * P + p] = from_f32<T>(r);
       }
     }
@@ -242,7 +229,7 @@ __global__ __launch_bounds__(256) void pairw_dot_bwd_data_kernel(const T* __rest
   const int R = sched_rounds(N), H = sched_width(N);
   int* sched = reinterpret_cast<int*>(smem + 2 * N * E);
   const int groups = blockDim.x / EL, grp = threadIdx.x / EL, e0 = threadIdx.x % EL;
-  build_round_schedule(sched, N);
+  build_pair_schedule(sched, N);
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     stage_block(x + b * N * E, xs, N * E);
@@ -252,7 +239,7 @@ __global__ __launch_bounds__(256) void pairw_dot_bwd_data_kernel(const T* __rest
       for (int k = grp; k < H; k += groups) {
         const int ij = sched[r * H + k];
         if (ij < 0) continue;
-        const int i = ij >> 16, j = ij & 0xffff, p = pair_index(i, j, N);
+        const int i = ij >> 16, j = ij & 0xffff, p = pair_index_of(i, j, N);
         const float gp = to_f32(g[b * P + p]);
         for (int e = e0; e < E; e += EL) {
           const float w = gp * to_f32(kern[(int64_t)p * kp + e * ke]);
@@ -594,7 +581,7 @@ __global__ __launch_bounds__(256) void pair_bil_fwd_kernel(const T* __restrict__
       if (MODE == 0) {
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-          const float r = group_reduce(rsum[s], 64);        // wavefront reduction over h
+          const float r = group_sum_down(rsum[s], 64);        // wavefront reduction over h
           if (lane == 0 && s < ns) out[(b0 + s) * P + p] = from_f32<T>(r);
         }
       }
@@ -619,7 +606,7 @@ __global__ __launch_bounds__(256) void pair_bil_bwd_data_kernel(const T* __restr
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   int* sched = reinterpret_cast<int*>(gts + nwaves * E);
   float* gt = gts + wave * E;
-  build_round_schedule(sched, N);
+  build_pair_schedule(sched, N);
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     stage_block(x + b * N * E, xs, N * E);
@@ -629,7 +616,7 @@ __global__ __launch_bounds__(256) void pair_bil_bwd_data_kernel(const T* __restr
       for (int k = wave; k < H; k += nwaves) {
         const int ij = sched[r * H + k];
         if (ij < 0) continue;
-        const int i = ij >> 16, j = ij & 0xffff, p = pair_index(i, j, N);
+        const int i = ij >> 16, j = ij & 0xffff, p = pair_index_of(i, j, N);
         const T* Wp = W + (int64_t)p * wp * E * E;
         for (int h = lane; h < E; h += 64) {
           float t = 0.f;
@@ -689,7 +676,7 @@ __global__ __launch_bounds__(256) void pair_epi_fwd_kernel(T* __restrict__ Tb, c
         float acc = 0.f;
 #pragma unroll
         for (int k = 0; k < VE; ++k) acc = fmaf(t[k], xs[j * E + v * VE + k], acc);
-        for (int o = vpr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);      // vpr is a power of two (host)
+        acc = group_sum_down(acc, vpr);      // vpr is a power of two (host)
         if (v == 0) out[b * P + p] = from_f32<T>(acc);
       } else {
 #pragma unroll
@@ -718,7 +705,7 @@ __global__ __launch_bounds__(256) void pair_epi_bwd_kernel(const T* __restrict__
   const int vpr = E / VE;
   const int groups = blockDim.x / vpr, grp = threadIdx.x / vpr, v = threadIdx.x % vpr;
   const bool active = grp < groups;
-  build_round_schedule(sched, N);
+  build_pair_schedule(sched, N);
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     __syncthreads();
     stage_block(x + b * N * E, xs, N * E);
@@ -731,7 +718,7 @@ __global__ __launch_bounds__(256) void pair_epi_bwd_kernel(const T* __restrict__
         for (int k = grp; k < H; k += groups) {
           const int ij = sched[r * H + k];
           if (ij < 0) continue;
-          const int i = ij >> 16, j = ij & 0xffff, p = pair_index(i, j, N);
+          const int i = ij >> 16, j = ij & 0xffff, p = pair_index_of(i, j, N);
           float t[VE], gv[VE];
           Vec16<T>::unpack(trow[(int64_t)p * vpr + v], t);
           if (MODE == 0) {

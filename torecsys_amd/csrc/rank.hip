@@ -50,13 +50,6 @@ struct PairArgs {
   bool idx64;
 };
 
-template <int LOG2L>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < (1 << LOG2L); m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 template <typename T, int LOG2L>
 __global__ __launch_bounds__(256) void pair_score_group_kernel(PairArgs p, void* __restrict__ scores, bool out_f32,
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(256) void pair_score_group_kernel(PairArgs p, void*
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < VE; ++k) s += a[k] * a[k];
-      na = fmaxf(sqrtf(group_sum<LOG2L>(s)), COS_EPS);
+      na = fmaxf(sqrtf(group_sum_up<(1 << LOG2L)>(s)), COS_EPS);
     }
     for (int j0 = 0; j0 < p.K1; j0 += CH) {
       int64_t r[CH];
@@ -111,8 +104,8 @@ __global__ __launch_bounds__(256) void pair_score_group_kernel(PairArgs p, void*
             d += a[k] * t[k];
             s += t[k] * t[k];
           }
-          d = group_sum<LOG2L>(d);
-          if (cosine) d = d / (na * fmaxf(sqrtf(group_sum<LOG2L>(s)), COS_EPS));
+          d = group_sum_up<(1 << LOG2L)>(d);
+          if (cosine) d = d / (na * fmaxf(sqrtf(group_sum_up<(1 << LOG2L)>(s)), COS_EPS));
           if (lane_v == 0) rank_store_val(scores, out_f32, b * p.K1 + j0 + c, d);
         }
       }
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(256) void pair_score_bwd_group_kernel(PairArgs p, c
     if (cosine) {
 #pragma unroll
       for (int k = 0; k < VE; ++k) na2 += a[k] * a[k];
-      na2 = group_sum<LOG2L>(na2);
+      na2 = group_sum_up<(1 << LOG2L)>(na2);
       na = sqrtf(na2);
       na_c = fmaxf(na, COS_EPS);
     }
@@ -211,8 +204,8 @@ __global__ __launch_bounds__(256) void pair_score_bwd_group_kernel(PairArgs p, c
               d += a[k] * t[k];
               s += t[k] * t[k];
             }
-            d = group_sum<LOG2L>(d);
-            s = group_sum<LOG2L>(s);
+            d = group_sum_up<(1 << LOG2L)>(d);
+            s = group_sum_up<(1 << LOG2L)>(s);
             const float nt = sqrtf(s);
             const float inv = 1.f / (na_c * fmaxf(nt, COS_EPS));
             const float cs = d * inv;
@@ -322,35 +315,15 @@ __global__ __launch_bounds__(256) void pair_score_bwd_anchor_elem_kernel(PairArg
   }
 }
 
-static int pair_log2_lanes(int row_bytes) {
-  if (row_bytes <= 0 || row_bytes % 16 != 0) return -1;
-  const int L = row_bytes / 16;
-  if (!is_pow2(L) || L > 64) return -1;
-  int l = 0;
-  while ((1 << l) < L) ++l;
-  return l;
-}
-
-#define TRS_RANK_SWITCH(lg, M) \
-  switch (lg) {                \
-    case 0: M(0); break;       \
-    case 1: M(1); break;       \
-    case 2: M(2); break;       \
-    case 3: M(3); break;       \
-    case 4: M(4); break;       \
-    case 5: M(5); break;       \
-    default: M(6); break;      \
-  }
-
 template <typename T>
 static int pair_score_fwd_launch(const PairArgs& p, void* scores, bool out_f32, int32_t* err_flag, hipStream_t s) {
-  const int lg = pair_log2_lanes(p.E * (int)sizeof(T));
+  const int lg = log2_lanes(p.E * (int)sizeof(T));
   if (lg >= 0 && aligned16(p.a_table) && aligned16(p.t_table)) {
     const int grid = stream_grid(p.B << lg, 256, 256 * 16);
-#define TRS_M(LG) \
-  hipLaunchKernelGGL((pair_score_group_kernel<T, LG>), dim3(grid), dim3(256), 0, s, p, scores, out_f32, err_flag)
-    TRS_RANK_SWITCH(lg, TRS_M)
-#undef TRS_M
+    dispatch_lanes(lg, [&](auto lg_c) {
+      hipLaunchKernelGGL((pair_score_group_kernel<T, decltype(lg_c)::value>), dim3(grid), dim3(256), 0, s, p, scores,
+                         out_f32, err_flag);
+    });
   } else {
     hipLaunchKernelGGL((pair_score_elem_kernel<T>), dim3(stream_grid(p.B * p.K1, 256, 256 * 16)), dim3(256), 0, s, p,
                        scores, out_f32, err_flag);
@@ -359,19 +332,19 @@ static int pair_score_fwd_launch(const PairArgs& p, void* scores, bool out_f32, 
 }
 
 static size_t pair_bwd_ws_bytes(int64_t B, int K, int E, int dtype) {
-  if (pair_log2_lanes(E * dtype_size(dtype)) >= 0) return 0;
+  if (log2_lanes(E * dtype_size(dtype)) >= 0) return 0;
   return (size_t)B * (size_t)(K + 1) * sizeof(float2);
 }
 
 template <typename T>
 static int pair_score_bwd_launch(const PairArgs& p, const void* g, bool g_f32, void* gblock, void* ws, hipStream_t s) {
-  const int lg = pair_log2_lanes(p.E * (int)sizeof(T));
+  const int lg = log2_lanes(p.E * (int)sizeof(T));
   if (lg >= 0) {
     const int grid = stream_grid(p.B << lg, 256, 256 * 16);
-#define TRS_M(LG) \
-  hipLaunchKernelGGL((pair_score_bwd_group_kernel<T, LG>), dim3(grid), dim3(256), 0, s, p, g, g_f32, (uint4*)gblock)
-    TRS_RANK_SWITCH(lg, TRS_M)
-#undef TRS_M
+    dispatch_lanes(lg, [&](auto lg_c) {
+      hipLaunchKernelGGL((pair_score_bwd_group_kernel<T, decltype(lg_c)::value>), dim3(grid), dim3(256), 0, s, p, g, g_f32,
+                         (uint4*)gblock);
+    });
   } else {
     hipLaunchKernelGGL((pair_score_bwd_elem_kernel<T>), dim3(stream_grid(p.B * p.K1, 256, 256 * 16)), dim3(256), 0, s, p,
                        g, g_f32, (T*)gblock, (float2*)ws);
@@ -397,7 +370,6 @@ struct RankArgs {
   bool f32;
 };
 
-__device__ __forceinline__ float rank_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 // softplus(-d) = -log(sigmoid(d)), finite for every d
 __device__ __forceinline__ float rank_softplus_neg(float d) { return fmaxf(-d, 0.f) + log1pf(expf(-fabsf(d))); }
 
@@ -416,10 +388,10 @@ __device__ __forceinline__ float rank_sample_terms(const RankArgs& a, int64_t b)
     for (int k = 0; k < a.K; ++k) mx = fmaxf(mx, rank_load_val(a.neg, a.f32, b * a.neg_stride + k));
     return fmaxf(a.margin - p + mx, 0.f);
   }
-  const float sp = 1.f - rank_sigmoid(p);
+  const float sp = 1.f - sigmoid_f(p);
   for (int k = 0; k < a.K; ++k) {
     const float n = rank_load_val(a.neg, a.f32, b * a.neg_stride + k);
-    if (a.kind == RANK_POINTWISE) acc += sp + rank_sigmoid(n);
+    if (a.kind == RANK_POINTWISE) acc += sp + sigmoid_f(n);
     else if (a.kind == RANK_BPR) acc += rank_softplus_neg(p - n);
     else acc += fmaxf(a.margin - p + n, 0.f);
   }
@@ -501,16 +473,16 @@ __global__ __launch_bounds__(256) void rank_loss_bwd_kernel(RankArgs a, const fl
       for (int k = 0; k < a.K; ++k) rank_store_val(g_neg, a.f32, b * g_neg_stride + k, k == at ? on : 0.f);
       gp = -on;
     } else {
-      const float sp = rank_sigmoid(p);
+      const float sp = sigmoid_f(p);
       for (int k = 0; k < a.K; ++k) {
         const float n = rank_load_val(a.neg, a.f32, b * a.neg_stride + k);
         float dp, dn;
         if (a.kind == RANK_POINTWISE) {
-          const float sn = rank_sigmoid(n);
+          const float sn = sigmoid_f(n);
           dp = -sp * (1.f - sp);
           dn = sn * (1.f - sn);
         } else if (a.kind == RANK_BPR) {
-          dn = rank_sigmoid(n - p);
+          dn = sigmoid_f(n - p);
           dp = -dn;
         } else {
           dn = a.margin - p + n > 0.f ? 1.f : 0.f;
@@ -544,7 +516,7 @@ using namespace trs;
 
 extern "C" int trs_pair_score_path(int32_t E, int32_t dtype) {
   if (E <= 0 || (dtype != TRS_F32 && dtype != TRS_BF16)) return -1;
-  return pair_log2_lanes(E * dtype_size(dtype)) >= 0 ? 1 : 0;
+  return log2_lanes(E * dtype_size(dtype)) >= 0 ? 1 : 0;
 }
 
 static int pair_args(const char* what, PairArgs* p, const void* a_table, int64_t Va, const void* a_idx, int64_t a_offset,

@@ -196,8 +196,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_onepass_kernel(int32_t* __r
         const unsigned long long incl = __ballot((w & 0x80000000u) != 0u);
         const int first = incl ? __ffsll((long long)incl) - 1 : 64;      // nearest predecessor with an inclusive prefix
         int c = lane <= first ? (int)(w & 0x3fffffffu) : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        c = group_sum_down<64>(c);
         run += c;
         if (first < 64) break;
       }
@@ -814,8 +813,7 @@ __global__ __launch_bounds__(256) void scatter_first_long_kernel(const T* __rest
       for (int u = 0; u < U; ++u)
         if (pp[u] >= 0) acc += to_f32(g_first[pp[u]]);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    acc = group_sum_down<64>(acc);
     if (lane == 0) grad_first[r] = from_f32<T>(acc);
   }
 }
@@ -1135,15 +1133,6 @@ __global__ __launch_bounds__(256) void scatter_split_rows_finish_elem_kernel(
   }
 }
 
-static int log2_lanes_sc(int row_bytes) {
-  if (row_bytes % 16 != 0) return -1;
-  const int L = row_bytes / 16;
-  if (!is_pow2(L) || L > 64) return -1;
-  int l = 0;
-  while ((1 << l) < L) ++l;
-  return l;
-}
-
 // the sink of the two gradient-writing entries: every finished row sum is written out
 static const RowSink GRAD_SINK{0, 0.f, 0.f, nullptr};
 
@@ -1259,20 +1248,12 @@ static void scatter_group_launch(const WalkJob& j) {
 
 template <typename T>
 static int scatter_launch(const WalkJob& j) {
-  const int lg = log2_lanes_sc(j.E * (int)sizeof(T));
+  const int lg = log2_lanes(j.E * (int)sizeof(T));
   const bool scal = j.g_fm_cols == 1 && j.E > 1 && j.fm_sum != nullptr;      // g_fm read as scalars: no alignment requirement
   const bool al = aligned16(j.g_rows) && (scal || aligned16(j.g_fm)) && aligned16(j.table) && aligned16(j.out) &&
                   aligned16(j.fm_sum);
   if (lg >= 0 && al) {
-    switch (lg) {
-      case 0: scatter_group_launch<T, 0>(j); break;
-      case 1: scatter_group_launch<T, 1>(j); break;
-      case 2: scatter_group_launch<T, 2>(j); break;
-      case 3: scatter_group_launch<T, 3>(j); break;
-      case 4: scatter_group_launch<T, 4>(j); break;
-      case 5: scatter_group_launch<T, 5>(j); break;
-      default: scatter_group_launch<T, 6>(j); break;
-    }
+    dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value>(j); });
   } else {
     // the companion table rides only in the 16-byte-vector walk
     TRS_REQUIRE(j.g_first == nullptr, TRS_ESHAPE,
@@ -1295,8 +1276,6 @@ static int scatter_launch(const WalkJob& j) {
   }
   return check_launch("scatter_rows");
 }
-
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Zero-fill by a kernel, not hipMemsetAsync: a memset captured into a hipGraph becomes a memset NODE, and on this runtime
 // the global-atomic bucket build replayed from a graph faulted (counters incremented on top of the previous replay's

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(AP_THREADS) void self_attn_bwd_kernel(const T* __re
         float t = 0.f;
         if (row < L)
           for (int c = sub; c < L; c += 4) t = fmaf(p[c], dp[c], t);
-        t = ap_quad_sum(t);
+        t = group_sum_up<4>(t);
         if (row < L)
           for (int c = sub; c < L; c += 4) dp[c] = p[c] * (dp[c] - t);
       }

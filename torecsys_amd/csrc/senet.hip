@@ -409,7 +409,7 @@ __global__ __launch_bounds__(256) void senet_rowsum_kernel(const T* __restrict__
         }
       }
     }
-    for (int m = 1; m < G; m <<= 1) s += __shfl_xor(s, m, 64);
+    s = group_sum_up(s, G);
     if (r < rows && gl == 0) dst[r] = s * scale;
   }
 }
@@ -505,16 +505,14 @@ static int senet_check_rows(const char* what, int64_t B, int M, int E, int dtype
 
 using namespace trs;
 
-#define TRS_SENET_K(T, FN, ...)                        \
-  switch (senet_vec_per_lane(M * (E * (int)sizeof(T) / 16))) { \
-    case 1: return FN<T, 1>(__VA_ARGS__);              \
-    case 2: return FN<T, 2>(__VA_ARGS__);              \
-    case 4: return FN<T, 4>(__VA_ARGS__);              \
-    case 5: return FN<T, 5>(__VA_ARGS__);              \
-    case 8: return FN<T, 8>(__VA_ARGS__);              \
-    case 10: return FN<T, 10>(__VA_ARGS__);            \
-    default: return FN<T, 16>(__VA_ARGS__);            \
-  }
+// K = 16-byte vectors of a sample per lane (senet_vec_per_lane): senet_check_fused has bounded the sample by
+// SENET_MAX_VEC per lane, so it is one of the seven steps
+template <typename T, typename F>
+static int senet_dispatch_k(int M, int E, F&& f) {
+  int rc = TRS_OK;
+  dispatch_int<1, 2, 4, 5, 8, 10, 16>(senet_vec_per_lane(M * (E * (int)sizeof(T) / 16)), [&](auto k_c) { rc = f(k_c); });
+  return rc;
+}
 
 extern "C" int trs_senet_fused_supported(int32_t M, int32_t H, int32_t E, int32_t dtype) {
   if (dtype != TRS_F32 && dtype != TRS_BF16) return 0;
@@ -533,8 +531,13 @@ extern "C" int trs_senet_fwd(const void* x, const void* W1, const void* b1, cons
   TRS_REQUIRE(aligned16(x) && aligned16(out), TRS_EALIGN, "senet_fwd: x / out not 16-byte aligned");
   if (B == 0) return TRS_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_F32) { TRS_SENET_K(float, senet_fwd_launch, x, W1, b1, W2, b2, B, M, H, E, out, gates, hidden, s) }
-  TRS_SENET_K(bf16_t, senet_fwd_launch, x, W1, b1, W2, b2, B, M, H, E, out, gates, hidden, s)
+  auto run = [&](auto t) {
+    using T = decltype(t);
+    return senet_dispatch_k<T>(M, E, [&](auto k_c) {
+      return senet_fwd_launch<T, decltype(k_c)::value>(x, W1, b1, W2, b2, B, M, H, E, out, gates, hidden, s);
+    });
+  };
+  return dtype == TRS_F32 ? run(float{}) : run(bf16_t{});
 }
 
 extern "C" size_t trs_senet_bwd_workspace_bytes(int64_t B, int32_t M, int32_t H) {
@@ -556,10 +559,14 @@ extern "C" int trs_senet_bwd(const void* x, const void* g, const float* gates, c
   if (B == 0 && !params) return TRS_OK;
   hipStream_t s = (hipStream_t)stream;
   float* slabs = (float*)workspace;
-  if (dtype == TRS_F32) {
-    TRS_SENET_K(float, senet_bwd_launch, x, g, gates, hidden, W1, W2, B, M, H, E, dx, dW1, db1, dW2, db2, slabs, s)
-  }
-  TRS_SENET_K(bf16_t, senet_bwd_launch, x, g, gates, hidden, W1, W2, B, M, H, E, dx, dW1, db1, dW2, db2, slabs, s)
+  auto run = [&](auto t) {
+    using T = decltype(t);
+    return senet_dispatch_k<T>(M, E, [&](auto k_c) {
+      return senet_bwd_launch<T, decltype(k_c)::value>(x, g, gates, hidden, W1, W2, B, M, H, E, dx, dW1, db1, dW2, db2,
+                                                       slabs, s);
+    });
+  };
+  return dtype == TRS_F32 ? run(float{}) : run(bf16_t{});
 }
 
 extern "C" int trs_senet_squeeze(const void* x, int64_t B, int32_t M, int32_t E, int32_t dtype, float* z,

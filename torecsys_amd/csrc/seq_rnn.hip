@@ -57,7 +57,6 @@ static int sr_pow2_above(int E) {
 __device__ __forceinline__ int64_t sr_load_int(const void* p, int64_t i, bool is32) {
   return is32 ? (int64_t)((const int32_t*)p)[i] : ((const int64_t*)p)[i];
 }
-__device__ __forceinline__ float sr_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // wt[which][k][r] = w_which[r][k] as fp32 (which = 0: w_ih, 1: w_hh; r < G E, k < E)
 template <typename T>
@@ -309,12 +308,12 @@ __global__ __launch_bounds__(SR_THREADS) void sr_fwd_kernel(
           if constexpr (CELL == SR_RNN) {
             h = tanhf(acc[0][s]);
           } else if constexpr (CELL == SR_LSTM) {
-            const float ig = sr_sigmoid(acc[0][s]), fg = sr_sigmoid(acc[1][s]), gg = tanhf(acc[2][s]),
-                        og = sr_sigmoid(acc[3][s]);
+            const float ig = sigmoid_f(acc[0][s]), fg = sigmoid_f(acc[1][s]), gg = tanhf(acc[2][s]),
+                        og = sigmoid_f(acc[3][s]);
             c[s] = fmaf(fg, c[s], ig * gg);
             h = og * tanhf(c[s]);
           } else {
-            const float r = sr_sigmoid(acc[0][s]), z = sr_sigmoid(acc[1][s]);
+            const float r = sigmoid_f(acc[0][s]), z = sigmoid_f(acc[1][s]);
             const float n = tanhf(fmaf(r, acc[3][s], acc[2][s]));
             h = fmaf(z, hcur[s] - n, n);
           }
@@ -428,8 +427,8 @@ __global__ __launch_bounds__(SR_THREADS) void sr_bwd_kernel(
             const float h = tanhf(acc[0][s]);
             di[0] = dhid[0] = dht * (1.f - h * h);
           } else if constexpr (CELL == SR_LSTM) {
-            const float ig = sr_sigmoid(acc[0][s]), fg = sr_sigmoid(acc[1][s]), gg = tanhf(acc[2][s]),
-                        og = sr_sigmoid(acc[3][s]);
+            const float ig = sigmoid_f(acc[0][s]), fg = sigmoid_f(acc[1][s]), gg = tanhf(acc[2][s]),
+                        og = sigmoid_f(acc[3][s]);
             const float cprev = t > 0 ? c_save[(b * L + t - 1) * E + j] : 0.f;
             const float tc = tanhf(fmaf(fg, cprev, ig * gg));
             const float dct = fmaf(dht * og, 1.f - tc * tc, dc[s]);
@@ -441,7 +440,7 @@ __global__ __launch_bounds__(SR_THREADS) void sr_bwd_kernel(
 #pragma unroll
             for (int g = 0; g < G; ++g) dhid[g] = di[g];
           } else {
-            const float r = sr_sigmoid(acc[0][s]), z = sr_sigmoid(acc[1][s]);
+            const float r = sigmoid_f(acc[0][s]), z = sigmoid_f(acc[1][s]);
             const float n = tanhf(fmaf(r, acc[3][s], acc[2][s]));
             const float hprev = hs[(m0 + s) * E + j];
             const float dan = dht * (1.f - z) * (1.f - n * n);

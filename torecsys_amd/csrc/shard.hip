@@ -133,8 +133,6 @@ __global__ void bucket_zero_kernel(unsigned long long* __restrict__ a, unsigned 
   for (int w = threadIdx.x; w < W; w += blockDim.x) { a[w] = 0ull; b[w] = 0ull; }
 }
 
-static size_t align_up_s(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // ---- un-permute of the sharded lookup with the LOCALLY-OWNED lookups read straight from this rank's shard ------------
 // The requester's lookups are numbered in exchange order (slot s = inv_pos[p], grouped by owner).  The slots
 // [self_lo, self_lo + self_n) are the ones this rank owns itself: their rows never travel (no owner-side gather into a send
@@ -260,37 +258,21 @@ static int embed_fm_sharded_launch(const void* back, const void* local, const in
                                    int32_t self_lo, int32_t self_n, int64_t n_valid, int64_t local_rows, int64_t B, int N,
                                    int E, void* emb, void* fm, float* fm_sum, int32_t* err_flag, hipStream_t s) {
   const int rb = E * (int)sizeof(T);
-  int lg = -1;
-  if (rb % 16 == 0 && is_pow2(rb / 16) && rb / 16 <= 64) {
-    lg = 0;
-    while ((1 << lg) < rb / 16) ++lg;
-  }
+  const int lg = log2_lanes(rb);
   const bool al = aligned16(back) && aligned16(local) && aligned16(emb) && aligned16(fm) && aligned16(fm_sum);
   if (lg >= 0 && al) {
     const int L = 1 << lg;
     const int grid = stream_grid(B * L, 256, 256 * 16);
     const bool stream = (size_t)local_rows * rb > ((size_t)512 << 20);      // as embed_fm: a table far beyond the caches
-#define TRS_SH2(LG, ST)                                                                                               \
-  hipLaunchKernelGGL((embed_fm_sharded_group_kernel<T, LG, ST>), dim3(grid), dim3(256), 0, s, (const uint4*)back,     \
-                     (const uint4*)local, inv_pos, send_ids, self_lo, self_n, n_valid, B, N, (uint4*)emb, (uint4*)fm, \
-                     fm_sum, err_flag)
-#define TRS_SH(LG)      \
-  if (stream) {         \
-    TRS_SH2(LG, true);  \
-  } else {              \
-    TRS_SH2(LG, false); \
-  }
-    switch (lg) {
-      case 0: TRS_SH(0); break;
-      case 1: TRS_SH(1); break;
-      case 2: TRS_SH(2); break;
-      case 3: TRS_SH(3); break;
-      case 4: TRS_SH(4); break;
-      case 5: TRS_SH(5); break;
-      default: TRS_SH(6); break;
-    }
-#undef TRS_SH
-#undef TRS_SH2
+    dispatch_lanes(lg, [&](auto lg_c) {
+      auto launch = [&](auto st_c) {
+        hipLaunchKernelGGL((embed_fm_sharded_group_kernel<T, decltype(lg_c)::value, decltype(st_c)::value>), dim3(grid),
+                           dim3(256), 0, s, (const uint4*)back, (const uint4*)local, inv_pos, send_ids, self_lo, self_n,
+                           n_valid, B, N, (uint4*)emb, (uint4*)fm, fm_sum, err_flag);
+      };
+      if (stream) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
   } else {
     if (emb == nullptr) return fail(TRS_EINVAL, "embed_fm_sharded: rows that are not whole 16-byte vectors need the block");
     hipLaunchKernelGGL((gather_sharded_elem_kernel<T>), dim3(stream_grid(B * N * E, 256, 256 * 32)), dim3(256), 0, s,
@@ -309,7 +291,7 @@ using namespace trs;
 
 extern "C" size_t trs_bucket_workspace_bytes(int64_t BN, int32_t world) {
   (void)BN;
-  return align_up_s((size_t)world * 8, 256);
+  return align_up((size_t)world * 8, 256);
 }
 
 extern "C" int trs_bucket_by_owner(const void* idx, int32_t idx_dtype, const int64_t* offsets, int64_t B, int32_t N,

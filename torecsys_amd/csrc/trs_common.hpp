@@ -5,6 +5,9 @@
 #include <stdio.h>
 #include <stdarg.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/trs_abi.h"
 
 namespace trs {
@@ -84,6 +87,47 @@ struct Vec16<bf16_t> {
   }
 };
 
+// ---------------------------------------------------------------- lane-group reductions
+// Sum / maximum over each group of G adjacent lanes of the wave (G a power of two <= 64); every lane of the group gets
+// the result.  Both butterfly orders are kept -- `_up` takes the narrowest step first (1, 2, .., G/2), `_down` the
+// widest (G/2, .., 2, 1) -- since float sums taken in another order differ in the last bits and a caller's order is
+// part of its result.
+template <int G, typename T>
+__device__ __forceinline__ T group_sum_up(T v) {
+#pragma unroll
+  for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+template <int G, typename T>
+__device__ __forceinline__ T group_sum_down(T v) {
+#pragma unroll
+  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+template <int G>
+__device__ __forceinline__ float group_max_up(float v) {
+#pragma unroll
+  for (int m = 1; m < G; m <<= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+template <int G>
+__device__ __forceinline__ float group_max_down(float v) {
+#pragma unroll
+  for (int m = G >> 1; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+// group width known at run time only (a power of two <= 64, uniform over the wave)
+__device__ __forceinline__ float group_sum_up(float v, int G) {
+  for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ float group_sum_down(float v, int G) {
+  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+
 // ---------------------------------------------------------------- (i<j) field pairs
 // pair index p = i*(2N-i-1)/2 + (j-i-1), lexicographic in (i, j) -- the order of the reference's row_idx / col_idx
 // lists (layers/ctr/inner_product_network.py:43-52).
@@ -117,6 +161,11 @@ __device__ __forceinline__ int sched_entry(int r, int k, int N) {
   if (a >= N || b >= N) return -1;
   return ((a < b ? a : b) << 16) | (a < b ? b : a);
 }
+// the whole schedule, built once per workgroup: sched[r * H + k] = sched_entry(r, k, N)
+__device__ __forceinline__ void build_pair_schedule(int* sched, int N) {
+  const int R = sched_rounds(N), H = sched_width(N);
+  for (int t = threadIdx.x; t < R * H; t += blockDim.x) sched[t] = sched_entry(t / H, t % H, N);
+}
 
 // ---------------------------------------------------------------- index loads
 template <typename IdxT>
@@ -129,6 +178,32 @@ __device__ __forceinline__ int64_t load_row_id(const IdxT* __restrict__ idx, con
 
 inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline int pad32(int x) { return (x + 31) / 32 * 32; }
+// A row of `row_bytes` bytes as 2^k 16-byte vectors, k = 0..6 (one lane of a wave per vector): k, or -1 where the row is
+// no such size and the caller takes its element path.
+inline int log2_lanes(int row_bytes) {
+  if (row_bytes % 16 != 0) return -1;
+  const int v = row_bytes / 16;
+  if (!is_pow2(v) || v > 64) return -1;
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return l;
+}
+// Runtime integer -> template argument: calls f(std::integral_constant<int, V>{}) for the one V of Vs... that equals v
+// and returns true, or calls nothing and returns false.  The callee reads the value as decltype(c)::value.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <int... Vs, typename F>
+inline bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(int_c<Vs>{}), true) : false) || ...);
+}
+// The lane-group case, lg = log2_lanes(...).  Every caller sits behind lg >= 0, so the seven values cover every call:
+// no default arm is needed (a `default:` could only ever have stood for 6).
+template <typename F>
+inline bool dispatch_lanes(int lg, F&& f) {
+  return dispatch_int<0, 1, 2, 3, 4, 5, 6>(lg, std::forward<F>(f));
+}
 inline int dtype_size(int dtype) { return dtype == TRS_F32 ? 4 : 2; }
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 

@@ -27,6 +27,7 @@
 // 416 x 64: 0.43 ms = 5.7 TB/s (0.52 ms).
 #include <algorithm>
 
+#include "lds_dma.hpp"
 #include "trs_common.hpp"
 
 namespace trs {
@@ -91,15 +92,6 @@ __device__ __forceinline__ wg_bf16x8 tr_frag(const char* lo_p, const char* hi_p,
   const wg_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(hi_p + off));
   const wg_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(wg_bf16x8, v);
-}
-
-// acc += A B, accumulator pinned to the accumulation registers and updated in place.  Written as an asm statement because
-// with 49 tiles per wave hipcc otherwise gives the result a different register from the addend and moves 196 values
-// back every iteration (3.7 register moves per MFMA).  The compiler still tracks the operands (it waits for the LDS reads
-// that feed A and B); what it cannot know is that the statement is an MFMA: the accumulators are read only after the
-// loop, behind explicit wait states.
-__device__ __forceinline__ void wg_mfma(wg_f32x4& acc, const wg_bf16x8& A, const wg_bf16x8& B) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(A), "v"(B));
 }
 
 // WM x WN waves: 4 (one per SIMD, every wave MC x NC tiles -- short shares run on into the neighbour's panels) or, for the
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_rows_kernel(WgradArgs a
         const char* fb = (m + PD < MCx) ? cb : nb_;                                                                  \
         Ar[(RO + m + PD) % 4] = tr_frag(fb + a_lo, fb + a_hi, t * WG_PANEL);                                        \
         _Pragma("unroll") for (int n = 0; n < NCx; ++n) {                                                            \
-          wg_mfma(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                                              \
+          mfma_inplace(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                                          \
           if (m == MCx - 1) Bf[n] = tr_frag(nb_ + b_lo, nb_ + b_hi, n * WG_PANEL);                                   \
         }                                                                                                           \
         if (m == (MCx > 2 ? 1 : 0)) { MID }                                                                          \
@@ -316,13 +308,6 @@ constexpr int WD_SLOT = 2 * WD_IMG;
 constexpr int WD_NSLOT = 6;
 constexpr int WD_AHEAD = 5;
 
-__device__ __forceinline__ void wd_dma(const char* src, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(dst), "s"(src) : "memory");
-}
-
 template <int MC, int NC>
 __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradManyArgs am) {
   extern __shared__ __attribute__((aligned(16))) char wg_lds[];
@@ -365,7 +350,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradManyArgs am) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int p = wave + 8 * t;
-      if (p < 26) wd_dma(p >= 13 ? xs : gs, voff[t], base + (p >= 13 ? WD_IMG + (p - 13) * 1024 : p * 1024));
+      if (p < 26) lds_dma1(p >= 13 ? xs : gs, voff[t], base + (p >= 13 ? WD_IMG + (p - 13) * 1024 : p * 1024));
     }
   };
   // this wave's pieces of all steps but the three youngest have landed (then: barrier -> visible to every wave)
@@ -399,7 +384,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradManyArgs am) {
         const char* fb = (m + PD < MCx) ? cb : nb_;                                                                  \
         Ar[(RO + m + PD) % 4] = tr_frag(fb + a_lo, fb + a_hi, t * 32);                                              \
         _Pragma("unroll") for (int n = 0; n < NCx; ++n) {                                                            \
-          wg_mfma(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                                              \
+          mfma_inplace(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                                          \
           if (m == MCx - 1) Bf[n] = tr_frag(nb_ + b_lo, nb_ + b_hi, n * 32);                                         \
         }                                                                                                           \
         if (m == (MCx > 2 ? 1 : 0)) {                                                                                \
@@ -461,12 +446,6 @@ constexpr int WD2_NSLOT = 4;
 constexpr int WD2_AHEAD = 3;
 constexpr int64_t WD2_MIN_ROWS = 1 << 20;
 
-template <bool AG>
-__device__ __forceinline__ void wd_mfma(wg_f32x4& acc, const wg_bf16x8& A, const wg_bf16x8& B) {
-  if constexpr (AG) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(A), "v"(B));
-  else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(A), "v"(B));
-}
-
 // workgroup b -> (row range ``slot`` of a.S, g block ``mb`` of a.MB), for any a.MB and a.S.  Blocks b and b + 8 share an
 // XCD (dealt round-robin), one workgroup fills a CU.  The first 8 * slots_per_xcd ranges are XCD-local: the MB workgroups
 // of a range sit on one XCD, so the x rows all of them read come out of that XCD's L2.  Where MB does not divide the 32
@@ -526,7 +505,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(WgradArgs a) {
 #pragma unroll
     for (int t = 0; t < 10; ++t) {
       const int p = wave + 4 * t;
-      if (p < 39) wd_dma(p < 13 ? gs : (p < 26 ? x0s : x1s), voff[t], base + p * 1024);
+      if (p < 39) lds_dma1(p < 13 ? gs : (p < 26 ? x0s : x1s), voff[t], base + p * 1024);
     }
   };
   auto landed = [&]() __attribute__((always_inline)) {      // all but the youngest step's pieces of this wave
@@ -556,8 +535,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(WgradArgs a) {
         const char* fb = (m + PD < MCx) ? cb : nb_;                                                                  \
         Ar[(RO + m + PD) % 4] = tr_frag(fb + a_lo, fb + a_hi, t * 32);                                              \
         _Pragma("unroll") for (int n = 0; n < NCx; ++n) {                                                            \
-          if (m * NCx + n < 64) wd_mfma<true>(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                   \
-          else wd_mfma<false>(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                                   \
+          if (m * NCx + n < 64) mfma_inplace<true>(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                              \
+          else mfma_inplace<false>(acc[m][n], Ar[(RO + m) % 4], Bf[n]);                                              \
           if (m == MCx - 1) Bf[n] = tr_frag(nb_ + b_lo, nb_ + b_hi, n * 32);                                         \
         }                                                                                                           \
         if (m == 1) issue((KEXPR) + WD2_AHEAD, ((c4) + WD2_AHEAD) % WD2_NSLOT);      /* the slot the last barrier freed */ \
