@@ -302,6 +302,77 @@ int trs_scatter_rows_weighted(const void* g, const void* weights, const int32_t*
 int trs_bag_weight_grad(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx,
                         int32_t idx_dtype, int64_t B, int32_t L, int64_t exclude_row, void* dw, trs_stream_t stream);
 
+/* ---- ragged bag pooling: one flat id vector plus offsets (nn.EmbeddingBag's calling form) ------------------------------
+ * ids (n,) int64/int32 RAW row ids; offsets (n_off,) int64/int32 with n_off = B or B + 1.  Bag b is the positions
+ * [offsets[b], end_b), end_b = offsets[b + 1] where that entry exists, else n; ids behind the last bag's end belong to no
+ * bag.  live(p) := ids[p] != exclude_row (every position when exclude_row = -1), cnt[b] = the live positions of bag b,
+ * w = weights (n,) of the table's dtype or NULL (= 1):
+ *   mode 0 (sum):  out[b,:] = sum_live w[p] * table[ids[p], :]
+ *   mode 1 (mean): out[b,:] = (sum_live table[ids[p], :]) * inv_cnt[b],  inv_cnt[b] = 1/cnt[b], 0 when cnt[b] == 0 (an
+ *                  empty bag is a zero row); inv_cnt (B,) fp32 is always written in this mode and required
+ *   mode 2 (max):  the maximum over the live positions, the first live position winning a tie (a later value wins only
+ *                  when it is greater or NaN, the rule of trs_bag_pool_fwd); argmax (B, E) int32 = the FLAT position p of
+ *                  the winner, -1 for an empty bag (a zero row): no limit on a bag's length
+ * out (B, E) of the table's dtype; fp32 accumulation in list order, one rounding on store.  An excluded position issues
+ * no table load and its weight is not read.  A live id outside [0, V) reads as a zero row, raises *err_flag and counts in
+ * cnt.  Offsets are range-checked on the device, nothing on the host reads them: begin and end are clamped to [0, n]; an
+ * offset outside [0, n], or a bag whose end lies before its begin (it is then empty), raises *err_flag; nothing is read
+ * outside ids[0, n).  B == 0: TRS_OK, nothing touched.  n == 0 with B > 0: B zero rows (ids may be NULL).
+ * Paths: rows that are a power-of-two number (<= 64) of whole 16-byte vectors: one lane group per bag; a bag of more than
+ * trs_bag_ragged_long_len() ids is queued in `workspace` (trs_bag_ragged_workspace_bytes(B): a counter + at most B
+ * entries) and reduced by ONE WAVE in a second, fixed-grid kernel whose 64/L lane groups stride the bag and fold their
+ * partials in a fixed order -- the result of a bag depends on its ids and its length alone, not on the queue order.
+ * Tables above 512 MiB are read with streaming loads.  Any other E: one thread per (b, e), no second tier.
+ * TRS_EINVAL: NULL table / offsets / out / workspace (ids: unless n == 0), bad size, n_off not B or B + 1, exclude_row
+ * outside [-1, V), weights with mode != 0, mode 2 without argmax, mode 1 without inv_cnt; TRS_ESHAPE: n or B >= 2^31 - 1;
+ * TRS_EDTYPE: dtype / ids_dtype / off_dtype; TRS_EWORKSPACE: ws_bytes below the query.  All before any launch.
+ * replaces F.embedding_bag(ids, table, offsets, mode=..., padding_idx=..., per_sample_weights=...,
+ * include_last_offset=...) on 1-D ids.                                                                               */
+int32_t trs_bag_ragged_long_len(void);
+size_t trs_bag_ragged_workspace_bytes(int64_t B);
+int trs_bag_pool_ragged_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* ids, int32_t ids_dtype,
+                            int64_t n, const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int32_t mode,
+                            int64_t exclude_row, const void* weights, void* out, int32_t* argmax, float* inv_cnt,
+                            void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
+/* Lookup -> sample map of ragged bags, for the gradients: bag_of[p] (n,) int32 = the last b in [0, B) with
+ * offsets[b] <= p, provided p < end_b (end_b as above); -1 otherwise, which covers a position that no bag holds.  Of
+ * several equal offsets (empty bags) the last, non-empty, bag owns the position.  One thread per position, a binary search
+ * over the offsets; a pure function of the offsets, no atomics.  n == 0: TRS_OK.
+ * Specified for offsets that do not decrease.  Where they do (trs_bag_pool_ragged_fwd raises *err_flag for such a batch)
+ * every entry is still a bag in [0, B) or -1, but it need not be the bag whose clamped range the forward walked.
+ * TRS_EINVAL: NULL pointer, bad size, n_off not B or B + 1; TRS_ESHAPE: n or B >= 2^31 - 1; TRS_EDTYPE: off_dtype.      */
+int trs_bag_owner(const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int64_t n, int32_t* bag_of,
+                  trs_stream_t stream);
+
+/* Table gradient of ragged bags on the row buckets of ids viewed as (n, 1) (trs_csr_build_skip, B = n, N = 1, skip_row =
+ * the excluded or the padding row):
+ *   grad_table[r,:] = sum over the lookups p of row r with b = bag_of[p] >= 0 of term(p)
+ * for EVERY r in [0,V) (rows without lookups and padding_row are written as zeros; -1: no padding row).  term(p):
+ *   weights == NULL, argmax == NULL:  g[b,:]          (the mean passes g * inv_cnt[b], rounded once, on (B, E))
+ *   weights (n,) of the table's dtype: weights[p] * g[b,:]
+ *   argmax (B, E) int32 of trs_bag_pool_ragged_fwd:  argmax[b,e] == p ? g[b,e] : 0
+ * g (B, E) of the table's dtype.  The walk of trs_scatter_rows_argmax / _weighted with the sample read from bag_of: fp32
+ * sums, no atomics on values, fixed summation order, rows with more than 64 lookups (32 on the any-E path) queued in
+ * `workspace` and reduced by whole waves, 256 lookups at a time; the (n, E) block is never formed.
+ * TRS_EINVAL: NULL pointer, both weights and argmax, bad size; TRS_ESHAPE: n or B >= 2^31 - 1; TRS_EDTYPE: dtype;
+ * TRS_EWORKSPACE: ws_bytes below the query.                                                                            */
+size_t trs_scatter_ragged_workspace_bytes(int64_t n, int32_t E);
+int trs_scatter_rows_ragged(const void* g, const int32_t* bag_of, const void* weights, const int32_t* argmax,
+                            const int32_t* row_start, const int32_t* perm, int64_t n, int64_t B, int64_t V, int32_t E,
+                            int32_t dtype, int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
+                            trs_stream_t stream);
+
+/* Gradient of the weights of the ragged weighted sum:
+ *   dw[p] = sum_e g[bag_of[p], e] * table[ids[p], e]      (fp32, columns in order, one rounding to the table's dtype)
+ * and exactly 0 where ids[p] == exclude_row (-1: none), lies outside [0, V), or bag_of[p] < 0.  g (B, E), dw (n,) of the
+ * table's dtype.  n == 0: TRS_OK.
+ * TRS_EINVAL: NULL pointer, bad size, exclude_row outside [-1, V); TRS_ESHAPE: n >= 2^31 - 1; TRS_EDTYPE: dtype /
+ * ids_dtype.                                                                                                          */
+int trs_bag_weight_grad_ragged(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype, const void* ids,
+                               int32_t ids_dtype, int64_t n, const int32_t* bag_of, int64_t exclude_row, void* dw,
+                               trs_stream_t stream);
+
 /* ---- K2: FM layer on a materialised block -------------------------------------------------
  * fwd: fm[b,:] = 0.5*((sum_n x)^2 - sum_n x^2), fm_sum[b,:] = sum_n x (fp32, optional)
  * bwd: dx[b,n,:] = g[b,:] * (fm_sum[b,:] - x[b,n,:])

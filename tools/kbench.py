@@ -24,7 +24,9 @@ bench_rank).
 bf16, the fused path against the same modules with the switch off, and the two kernels alone (own inputs, see bench_prm).
 --what bagshard [--L 50] [--world 8]: the four kernels of the sharded bag pooling alone with this process as rank 0 of
 --world, the world-1 module against the unsharded ListIndicesEmbedding, fp32 and bf16, and the wire bytes per rank of the
-partial-sum path against the rows path (own inputs, see bench_bagshard)."""
+partial-sum path against the rows path (own inputs, see bench_bagshard).
+--what ragged [--shape fixed,uniform,longtail] [--modes sum,mean,max]: ragged bag pooling (ids + offsets) against bag_pool on
+the same bags padded to the longest and against F.embedding_bag with offsets (own inputs, see bench_ragged)."""
 import argparse
 import os
 import sys
@@ -160,6 +162,99 @@ def bench_bag(a):
         ts = sorted(ts)
         print(f"csr_build (B, L) {name:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us",
               flush=True)
+
+
+def bench_ragged(a):
+    """Ragged bag pooling (csrc/bag_ragged.hip) at B bags, E, V: forward and forward+backward (row buckets rebuilt every
+    step) of sum / mean / max, alternating in this process with bag_pool(exclude_padding=True) on the same bags padded with
+    id 0 to the longest one, and with torch.nn.functional.embedding_bag(ids, w, offsets) on the device.  Bag lengths from a
+    seeded generator: ``fixed`` 50; ``uniform`` 0..100; ``longtail`` most bags under 10 ids, 300 bags of 2000..6000.  Every
+    figure is the median of ``--rounds`` per-round medians with their min..max; the candidates take turns inside a round.
+    The forward's share of 8 TB/s is on its algorithmic bytes n * (8 + E*s) + (B + 1) * 8 read, B * E*s written."""
+    import torch.nn.functional as TF
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    s = 2 if dt == torch.bfloat16 else 4
+    dev = torch.device("cuda:0")
+    B, E, V = a.B, a.E, a.V
+    g = torch.Generator(device=dev).manual_seed(4321)
+    w = torch.randn(V, E, generator=g, device=dev, dtype=dt).requires_grad_()
+    gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+    print(f"ragged bag pooling B={B} E={E} V={V} {a.dtype} table {V * E * s / 2**30:.2f} GiB, long-bag threshold "
+          f"T={F_.bag_ragged_long_len()}, {a.rounds} rounds x {a.iters} launches", flush=True)
+
+    def lengths_of(shape):
+        if shape == "fixed":
+            return torch.full((B,), 50, dtype=torch.int64, device=dev)
+        if shape == "uniform":
+            return torch.randint(0, 101, (B,), generator=g, device=dev)
+        ln = torch.randint(0, 10, (B,), generator=g, device=dev)
+        hot = torch.randperm(B, generator=g, device=dev)[:300]
+        ln[hot] = torch.randint(2000, 6001, (300,), generator=g, device=dev)
+        return ln
+
+    for shape in a.shape.split(","):
+        ln = lengths_of(shape)
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), ln.cumsum(0)])
+        n, lmax = int(offsets[-1]), int(ln.max())
+        ids = torch.randint(1, V, (n,), generator=g, device=dev)
+        alg = n * (8 + E * s) + (B + 1) * 8 + B * E * s
+        print(f"{shape}: n={n} ids, longest bag {lmax}, padded form B*L_max={B * lmax} ids "
+              f"({n / max(B * lmax, 1) * 100:.1f} % live)", flush=True)
+        padded = None
+        if B * lmax < 2 ** 31 - 1:
+            col = torch.arange(lmax, device=dev).view(1, lmax)
+            padded = torch.zeros(B, lmax, dtype=torch.int64, device=dev)
+            padded[col < ln.view(B, 1)] = ids                      # row-major: the bags in order
+        else:
+            print(f"{shape}: padded form not run (B*L_max does not fit the bucket build's int32 positions)", flush=True)
+        off_b = offsets[:-1].contiguous()
+
+        def fwd_bwd(f):
+            def run():
+                F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+                w.grad = None
+                f().backward(gout)
+            return run
+
+        for mode in a.modes.split(","):
+            cands = [("bag_pool_ragged (HIP)", lambda: F_.bag_pool_ragged(w, ids, offsets, mode, 0, exclude_padding=True,
+                                                                          include_last_offset=True))]
+            if padded is not None:
+                cands.append(("bag_pool padded (HIP)", lambda: F_.bag_pool(w, padded, mode, 0, exclude_padding=True)))
+            cands.append(("embedding_bag (ATen)", lambda: TF.embedding_bag(ids, w, off_b, mode=mode).unsqueeze(1)))
+            live = {"fwd": [], "fwd+bwd": []}      # probed separately: a missing backward does not drop the forward
+            for name, f in cands:
+                for what in ("fwd", "fwd+bwd"):
+                    try:
+                        if what == "fwd":
+                            with torch.no_grad():
+                                f()
+                        else:
+                            f().backward(gout)
+                            w.grad = None
+                        torch.cuda.synchronize()
+                        live[what].append((name, f))
+                    except Exception as e:      # noqa: BLE001 -- a mode / dtype this torch build does not serve
+                        print(f"{shape:8s} {mode:5s} {what:8s} {name:22s} not run ({type(e).__name__}: {str(e)[:80]})",
+                              flush=True)
+            for what in ("fwd", "fwd+bwd"):
+                per = {name: [] for name, _ in live[what]}
+                for _ in range(a.rounds):
+                    for name, f in live[what]:
+                        if what == "fwd":
+                            with torch.no_grad():
+                                per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                        else:
+                            per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+                for name, ts in per.items():
+                    ts = sorted(ts)
+                    extra = ""
+                    if what == "fwd" and name.startswith("bag_pool_ragged"):
+                        extra = f"  {alg / ts[len(ts) // 2] / 8e12 * 100:5.1f}% of 8 TB/s on {alg / 1e6:.0f} MB (alg)"
+                    print(f"{shape:8s} {mode:5s} {what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread "
+                          f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us{extra}", flush=True)
+            w.grad = None
+        del padded, ids
 
 
 def bench_attn(a):
@@ -1018,7 +1113,11 @@ def main():
     ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
     ap.add_argument("--layers", type=int, default=2, help="prm: encoder layers of the model")
     ap.add_argument("--world", type=int, default=8, help="bagshard: the world size whose rank 0 this process plays")
+    ap.add_argument("--shape", default="fixed,uniform,longtail", help="ragged: bag-length distributions to run")
+    ap.add_argument("--modes", default="sum,mean,max", help="ragged: pooling modes to run")
     a = ap.parse_args()
+    if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"
+        return bench_ragged(a)
     if a.what == "bagshard":     # own inputs and modules: not part of "all"
         return bench_bagshard(a)
     if a.what == "rank":        # own inputs and modules: not part of "all"

@@ -24,21 +24,13 @@
 // Weighted backward: the walk of the max backward with the term of lookup p = (b, l) being w[p] * g[b, e] (flag WGT of the
 // same kernels, same queue thresholds BAG_LONG_ROW / BAG_LONG_CHUNK / BAG_LONG_ROW_ELEM), and bag_weight_grad_*_kernel:
 // dw[b, l] = sum_e g[b, e] * table[idx[b, l], e], one lane group (or one thread) per position, 0 at excluded positions.
-#include <algorithm>
-#include <cmath>
-
-#include "trs_common.hpp"
+//
+// Ragged bags (forward: bag_ragged.hip): the same walks and the same weight-gradient kernels with the compile-time flag RAG
+// -- the sample of lookup p is read from a map (bag_of[p], trs_bag_owner) where the padded layout divides p by the list
+// length, and the winners of the max are flat int32 positions behind a pointer of their own.  RAG_OFF: the code above.
+#include "bag_common.hpp"
 
 namespace trs {
-
-constexpr int BAG_SUM = 0, BAG_MEAN = 1, BAG_MAX = 2;
-constexpr int BAG_LONG_ROW = 64;        // lookups a single lane group walks by itself (scatter.hip: LONG_ROW)
-constexpr int BAG_LONG_CHUNK = 256;     // lookups per queue entry of a hot row (scatter.hip: LONG_CHUNK)
-constexpr int BAG_LONG_ROW_ELEM = 32;   // the same for the one-thread-per-element path
-constexpr size_t BAG_STREAM_BYTES = (size_t)512 << 20;      // twice the Infinity Cache: the STREAM rule of fm.hip
-
-// ATen's rule (adaptive_max_pool): a later value replaces the running maximum when it is greater or NaN
-__device__ __forceinline__ bool bag_takes(float v, float m) { return v > m || v != v; }
 
 template <typename T, typename IdxT, int LOG2L, bool MAXP, int CH, bool STREAM, bool MASK, bool WGT>
 __global__ __launch_bounds__(256) void bag_pool_group_kernel(const uint4* __restrict__ table,
@@ -284,14 +276,73 @@ __device__ __forceinline__ void bag_argmax_bucket(float* acc, const uint4* __res
   }
 }
 
-template <typename T, int LOG2L, bool WGT>
+// Ragged bags (RAG != 0 in the kernels below): the sample of lookup p is bag_of[p] (trs_bag_owner; < 0: no bag holds p,
+// no term) where the padded layout divides, and the winners are FLAT positions: amax32 (B, E) int32, amax32[b, k] == p.
+// RAG names the term at compile time -- RAG_PLAIN: g[b, k]; RAG_WGT: wts[p] * g[b, k]; RAG_MAX: the winner mask.
+constexpr int RAG_OFF = 0, RAG_PLAIN = 1, RAG_WGT = 2, RAG_MAX = 3;
+
+template <typename T, int LOG2L, int CH, int RAG>
+__device__ __forceinline__ void bag_ragged_bucket(float* acc, const uint4* __restrict__ g,
+                                                  const int32_t* __restrict__ amax32, const T* __restrict__ wts,
+                                                  const int32_t* __restrict__ bag_of,
+                                                  const int32_t* __restrict__ perm, int beg, int end, int step,
+                                                  int lane_v) {
+  constexpr int L = 1 << LOG2L;
+  constexpr int VE = Vec16<T>::VE;
+  for (int q = beg; q < end; q += CH * step) {
+    int p[CH], b[CH];
+    uint4 gv[CH];
+    int av[CH][VE];                           // RAG_MAX only
+    float wv[CH];                             // RAG_WGT only
+#pragma unroll
+    for (int c = 0; c < CH; ++c) p[c] = (q + c * step) < end ? perm[q + c * step] : -1;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) b[c] = p[c] >= 0 ? bag_of[p[c]] : -1;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      gv[c] = make_uint4(0, 0, 0, 0);
+      wv[c] = 1.f;
+      if (b[c] >= 0) {
+        gv[c] = g[(int64_t)b[c] * L + lane_v];
+        if constexpr (RAG == RAG_WGT) {
+          wv[c] = to_f32(wts[p[c]]);
+        } else if constexpr (RAG == RAG_MAX) {
+          const uint4* ap = reinterpret_cast<const uint4*>(amax32 + ((int64_t)b[c] * L + lane_v) * VE);
+#pragma unroll
+          for (int h = 0; h < VE / 4; ++h) {
+            const uint4 a4 = ap[h];
+            av[c][4 * h] = (int)a4.x; av[c][4 * h + 1] = (int)a4.y;
+            av[c][4 * h + 2] = (int)a4.z; av[c][4 * h + 3] = (int)a4.w;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      if (b[c] >= 0) {
+        float x[VE];
+        Vec16<T>::unpack(gv[c], x);
+#pragma unroll
+        for (int k = 0; k < VE; ++k) {
+          if constexpr (RAG == RAG_WGT) acc[k] += wv[c] * x[k];
+          else if constexpr (RAG == RAG_MAX) acc[k] += av[c][k] == p[c] ? x[k] : 0.f;
+          else acc[k] += x[k];
+        }
+      }
+    }
+  }
+}
+
+template <typename T, int LOG2L, bool WGT, int RAG>
 __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __restrict__ g,
                                                               const uint16_t* __restrict__ amax,
                                                               const T* __restrict__ wts,
                                                               const int32_t* __restrict__ row_start,
                                                               const int32_t* __restrict__ perm, int64_t V, unsigned N,
                                                               int64_t padding_row, uint4* __restrict__ grad,
-                                                              int32_t* __restrict__ long_rows /* [0] = count */) {
+                                                              int32_t* __restrict__ long_rows /* [0] = count */,
+                                                              const int32_t* __restrict__ bag_of /* RAG only */,
+                                                              const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   const int lane_v = threadIdx.x & (L - 1);
@@ -313,7 +364,10 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
         }
         continue;
       }
-      bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg, end, 1, N, lane_v);
+      if constexpr (RAG != RAG_OFF)
+        bag_ragged_bucket<T, LOG2L, 4, RAG>(acc, g, amax32, wts, bag_of, perm, beg, end, 1, lane_v);
+      else
+        bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg, end, 1, N, lane_v);
     }
     store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
   }
@@ -321,7 +375,7 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
 
 // hot rows: one wave per (row, chunk) entry, its 64 / L lane groups stride the chunk, partial sums folded by shuffles.
 // Rows of a single chunk are finished here; otherwise the partial goes to scratch[entry][E] (fp32) for the finish kernel.
-template <typename T, int LOG2L, bool WGT>
+template <typename T, int LOG2L, bool WGT, int RAG>
 __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __restrict__ g,
                                                               const uint16_t* __restrict__ amax,
                                                               const T* __restrict__ wts,
@@ -329,7 +383,9 @@ __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __res
                                                               const int32_t* __restrict__ perm, unsigned N,
                                                               uint4* __restrict__ grad,
                                                               const int32_t* __restrict__ long_rows,
-                                                              float* __restrict__ scratch) {
+                                                              float* __restrict__ scratch,
+                                                              const int32_t* __restrict__ bag_of /* RAG only */,
+                                                              const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   constexpr int G = 64 / L;
@@ -346,7 +402,10 @@ __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __res
     float acc[VE];
 #pragma unroll
     for (int k = 0; k < VE; ++k) acc[k] = 0.f;
-    bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg + grp, end, G, N, lane_v);
+    if constexpr (RAG != RAG_OFF)
+      bag_ragged_bucket<T, LOG2L, 4, RAG>(acc, g, amax32, wts, bag_of, perm, beg + grp, end, G, lane_v);
+    else
+      bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg + grp, end, G, N, lane_v);
 #pragma unroll
     for (int m = L; m < 64; m <<= 1) {
 #pragma unroll
@@ -405,14 +464,37 @@ __device__ __forceinline__ float bag_argmax_term(const T* __restrict__ g, const 
   return (unsigned)amax[o] == l ? to_f32(g[o]) : 0.f;
 }
 
-template <typename T, bool WGT>
+// ragged bags: the term of bag_ragged_bucket for one element
+template <typename T, int RAG>
+__device__ __forceinline__ float bag_ragged_term(const T* __restrict__ g, const int32_t* __restrict__ amax32,
+                                                 const T* __restrict__ wts, const int32_t* __restrict__ bag_of, int p,
+                                                 int E, int e) {
+  const int b = bag_of[p];
+  if (b < 0) return 0.f;
+  const int64_t o = (int64_t)b * E + e;
+  if constexpr (RAG == RAG_WGT) return to_f32(wts[p]) * to_f32(g[o]);
+  else if constexpr (RAG == RAG_MAX) return amax32[o] == p ? to_f32(g[o]) : 0.f;
+  else return to_f32(g[o]);
+}
+
+template <typename T, bool WGT, int RAG>
+__device__ __forceinline__ float bag_walk_term(const T* __restrict__ g, const uint16_t* __restrict__ amax,
+                                               const T* __restrict__ wts, const int32_t* __restrict__ bag_of,
+                                               const int32_t* __restrict__ amax32, int p, unsigned N, int E, int e) {
+  if constexpr (RAG != RAG_OFF) return bag_ragged_term<T, RAG>(g, amax32, wts, bag_of, p, E, e);
+  else return bag_argmax_term<T, WGT>(g, amax, wts, p, N, E, e);
+}
+
+template <typename T, bool WGT, int RAG>
 __global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __restrict__ g,
                                                                    const uint16_t* __restrict__ amax,
                                                                    const T* __restrict__ wts,
                                                                    const int32_t* __restrict__ row_start,
                                                                    const int32_t* __restrict__ perm, int64_t V, int E,
                                                                    unsigned N, int64_t padding_row, T* __restrict__ grad,
-                                                                   int32_t* __restrict__ long_rows) {
+                                                                   int32_t* __restrict__ long_rows,
+                                                                   const int32_t* __restrict__ bag_of /* RAG only */,
+                                                                   const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
   const int64_t total = V * E;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const bool f32 = total < ((int64_t)1 << 32);
@@ -426,20 +508,22 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __re
         if (e == 0) long_rows[1 + atomicAdd(&long_rows[0], 1)] = (int32_t)r;
         continue;
       }
-      for (int q = beg; q < end; ++q) acc += bag_argmax_term<T, WGT>(g, amax, wts, perm[q], N, E, e);
+      for (int q = beg; q < end; ++q) acc += bag_walk_term<T, WGT, RAG>(g, amax, wts, bag_of, amax32, perm[q], N, E, e);
     }
     grad[t] = from_f32<T>(acc);
   }
 }
 
-template <typename T, bool WGT>
+template <typename T, bool WGT, int RAG>
 __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __restrict__ g,
                                                                    const uint16_t* __restrict__ amax,
                                                                    const T* __restrict__ wts,
                                                                    const int32_t* __restrict__ row_start,
                                                                    const int32_t* __restrict__ perm, int E, unsigned N,
                                                                    T* __restrict__ grad,
-                                                                   const int32_t* __restrict__ long_rows) {
+                                                                   const int32_t* __restrict__ long_rows,
+                                                                   const int32_t* __restrict__ bag_of /* RAG only */,
+                                                                   const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
   const int nlong = long_rows[0];
   const int lane = threadIdx.x & 63;
   const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -455,7 +539,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __re
         for (int u = 0; u < U; ++u) pp[u] = (q + 64 * u) < end ? perm[q + 64 * u] : -1;
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (pp[u] >= 0) acc += bag_argmax_term<T, WGT>(g, amax, wts, pp[u], N, E, e);
+          if (pp[u] >= 0) acc += bag_walk_term<T, WGT, RAG>(g, amax, wts, bag_of, amax32, pp[u], N, E, e);
       }
       acc = group_sum_down<64>(acc);
       if (lane == 0) grad[r * E + e] = from_f32<T>(acc);
@@ -473,31 +557,33 @@ static size_t bag_queue_bytes(int64_t BN) {
   return align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
 }
 
-template <typename T, bool WGT>
+template <typename T, bool WGT, int RAG = RAG_OFF>
 static int bag_argmax_launch(const void* g, const uint16_t* amax, const void* wts_, const int32_t* row_start,
                              const int32_t* perm, int64_t V, int E, int N, int64_t padding_row, void* grad,
-                             int32_t* long_rows, float* scratch, hipStream_t s) {
+                             int32_t* long_rows, float* scratch, hipStream_t s, const int32_t* bag_of = nullptr,
+                             const int32_t* amax32 = nullptr) {
   const T* wts = (const T*)wts_;
   const int lg = log2_lanes(E * (int)sizeof(T));
   hipLaunchKernelGGL(bag_zero_counter_kernel, dim3(1), dim3(64), 0, s, long_rows);
-  if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(grad)) {
+  if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(amax32) && aligned16(grad)) {
     const int grid = stream_grid(V << lg, 256, 256 * 32);
     dispatch_lanes(lg, [&](auto lg_c) {
       constexpr int LG = decltype(lg_c)::value;
-      hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax, wts,
-                         row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows);
-      hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax, wts,
-                         row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch);
+      hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT, RAG>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax,
+                         wts, row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows, bag_of, amax32);
+      hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT, RAG>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax,
+                         wts, row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch, bag_of, amax32);
       hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,
                          long_rows, scratch);
     });
   } else {
-    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T, WGT>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s,
-                       (const T*)g, amax, wts, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows);
-    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T, WGT>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, wts,
-                       row_start, perm, E, (unsigned)N, (T*)grad, long_rows);
+    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T, WGT, RAG>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0,
+                       s, (const T*)g, amax, wts, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows,
+                       bag_of, amax32);
+    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T, WGT, RAG>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, wts,
+                       row_start, perm, E, (unsigned)N, (T*)grad, long_rows, bag_of, amax32);
   }
-  return check_launch(WGT ? "scatter_rows_weighted" : "scatter_rows_argmax");
+  return check_launch(RAG != RAG_OFF ? "scatter_rows_ragged" : WGT ? "scatter_rows_weighted" : "scatter_rows_argmax");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -505,11 +591,13 @@ static int bag_argmax_launch(const void* g, const uint16_t* amax, const void* wt
 
 // a group of L lanes per position p = b * Lb + l: one 16-byte vector of the row and of g[b] per lane, fp32 products summed
 // in column order inside the lane, then folded over the group by shuffles (fixed order)
-template <typename T, typename IdxT, int LOG2L>
+// RAG (ragged bags): the sample of position p is bag_of[p]; < 0 (no bag holds p): dw[p] = 0
+template <typename T, typename IdxT, int LOG2L, bool RAG>
 __global__ __launch_bounds__(256) void bag_weight_grad_group_kernel(const uint4* __restrict__ table,
                                                                     const uint4* __restrict__ g,
                                                                     const IdxT* __restrict__ idx, int64_t BN, int Lb,
-                                                                    int64_t V, int64_t pad, T* __restrict__ dw) {
+                                                                    int64_t V, int64_t pad, T* __restrict__ dw,
+                                                                    const int32_t* __restrict__ bag_of) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   const int lane_v = threadIdx.x & (L - 1);
@@ -522,8 +610,8 @@ __global__ __launch_bounds__(256) void bag_weight_grad_group_kernel(const uint4*
     float d = 0.f;
     if (p < BN) {
       const int64_t r = (int64_t)idx[p];
-      if (r != pad && r >= 0 && r < V) {
-        const int64_t b = udiv_fast(p, Lb, f32);
+      if (r != pad && r >= 0 && r < V && (!RAG || bag_of[p] >= 0)) {
+        const int64_t b = RAG ? (int64_t)bag_of[p] : udiv_fast(p, Lb, f32);
         float x[VE], y[VE];
         Vec16<T>::unpack(table[r * L + lane_v], x);
         Vec16<T>::unpack(g[b * L + lane_v], y);
@@ -537,39 +625,41 @@ __global__ __launch_bounds__(256) void bag_weight_grad_group_kernel(const uint4*
 }
 
 // generic path (any E): one thread per position
-template <typename T, typename IdxT>
+template <typename T, typename IdxT, bool RAG>
 __global__ __launch_bounds__(256) void bag_weight_grad_elem_kernel(const T* __restrict__ table, const T* __restrict__ g,
                                                                    const IdxT* __restrict__ idx, int64_t BN, int Lb,
-                                                                   int E, int64_t V, int64_t pad, T* __restrict__ dw) {
+                                                                   int E, int64_t V, int64_t pad, T* __restrict__ dw,
+                                                                   const int32_t* __restrict__ bag_of) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const bool f32 = BN < ((int64_t)1 << 32);
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < BN; p += stride) {
     const int64_t r = (int64_t)idx[p];
     float d = 0.f;
-    if (r != pad && r >= 0 && r < V) {
-      const int64_t b = udiv_fast(p, Lb, f32);
+    if (r != pad && r >= 0 && r < V && (!RAG || bag_of[p] >= 0)) {
+      const int64_t b = RAG ? (int64_t)bag_of[p] : udiv_fast(p, Lb, f32);
       for (int e = 0; e < E; ++e) d += to_f32(table[r * E + e]) * to_f32(g[b * E + e]);
     }
     dw[p] = from_f32<T>(d);
   }
 }
 
-template <typename T, typename IdxT>
+// RAG: B = the n positions of the flat id vector, Lb = 1
+template <typename T, typename IdxT, bool RAG = false>
 static int bag_weight_grad_launch(const void* table, const void* g, const IdxT* idx, int64_t B, int Lb, int E, int64_t V,
-                                  int64_t pad, void* dw, hipStream_t s) {
+                                  int64_t pad, void* dw, hipStream_t s, const int32_t* bag_of = nullptr) {
   const int lg = log2_lanes(E * (int)sizeof(T));
   const int64_t BN = B * Lb;
   if (lg >= 0 && aligned16(table) && aligned16(g)) {
     const int grid = stream_grid(BN << lg, 256, 256 * 32);
     dispatch_lanes(lg, [&](auto lg_c) {
-      hipLaunchKernelGGL((bag_weight_grad_group_kernel<T, IdxT, decltype(lg_c)::value>), dim3(grid), dim3(256), 0, s,
-                         (const uint4*)table, (const uint4*)g, idx, BN, Lb, V, pad, (T*)dw);
+      hipLaunchKernelGGL((bag_weight_grad_group_kernel<T, IdxT, decltype(lg_c)::value, RAG>), dim3(grid), dim3(256), 0,
+                         s, (const uint4*)table, (const uint4*)g, idx, BN, Lb, V, pad, (T*)dw, bag_of);
     });
   } else {
-    hipLaunchKernelGGL((bag_weight_grad_elem_kernel<T, IdxT>), dim3(stream_grid(BN, 256, 256 * 32)), dim3(256), 0, s,
-                       (const T*)table, (const T*)g, idx, BN, Lb, E, V, pad, (T*)dw);
+    hipLaunchKernelGGL((bag_weight_grad_elem_kernel<T, IdxT, RAG>), dim3(stream_grid(BN, 256, 256 * 32)), dim3(256), 0,
+                       s, (const T*)table, (const T*)g, idx, BN, Lb, E, V, pad, (T*)dw, bag_of);
   }
-  return check_launch("bag_weight_grad");
+  return check_launch(RAG ? "bag_weight_grad_ragged" : "bag_weight_grad");
 }
 
 }  // namespace trs
@@ -725,6 +815,71 @@ extern "C" int trs_bag_weight_grad(const void* g, const void* table, int64_t V, 
     TRS_CALL(float, int32_t);
   }
   if (idx_dtype == TRS_I64) TRS_CALL(bf16_t, int64_t);
+  TRS_CALL(bf16_t, int32_t);
+#undef TRS_CALL
+}
+
+// ---------------------------------------------------------------------------------------------
+// ragged bags (forward: bag_ragged.hip): the walks above with the sample of a lookup read from bag_of
+
+extern "C" size_t trs_scatter_ragged_workspace_bytes(int64_t n, int32_t E) {
+  return trs_scatter_argmax_workspace_bytes(n, E);      // the same queue and chunk partials
+}
+
+extern "C" int trs_scatter_rows_ragged(const void* g, const int32_t* bag_of, const void* weights, const int32_t* argmax,
+                                       const int32_t* row_start, const int32_t* perm, int64_t n, int64_t B, int64_t V,
+                                       int32_t E, int32_t dtype, int64_t padding_row, void* grad_table, void* workspace,
+                                       size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(g && bag_of && row_start && perm && grad_table && workspace, TRS_EINVAL,
+              "scatter_rows_ragged: NULL pointer");
+  TRS_REQUIRE(weights == nullptr || argmax == nullptr, TRS_EINVAL,
+              "scatter_rows_ragged: weights and argmax are two different terms, pass one of them at most");
+  TRS_REQUIRE(V > 0 && E > 0 && n >= 0 && B > 0, TRS_EINVAL, "scatter_rows_ragged: bad size n=%lld B=%lld V=%lld E=%d",
+              (long long)n, (long long)B, (long long)V, E);
+  TRS_REQUIRE(n < (int64_t)0x7fffffff && B < (int64_t)0x7fffffff, TRS_ESHAPE,
+              "scatter_rows_ragged: n=%lld and B=%lld must fit int32", (long long)n, (long long)B);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_ragged: dtype %d", dtype);
+  TRS_REQUIRE(ws_bytes >= trs_scatter_ragged_workspace_bytes(n, E), TRS_EWORKSPACE,
+              "scatter_rows_ragged: workspace %zu < %zu", ws_bytes, trs_scatter_ragged_workspace_bytes(n, E));
+  int32_t* long_rows = (int32_t*)workspace;
+  float* scratch = (float*)((char*)workspace + bag_queue_bytes(n));
+  hipStream_t s = (hipStream_t)stream;
+#define TRS_CALL(T, R)                                                                                                  \
+  return bag_argmax_launch<T, false, R>(g, nullptr, weights, row_start, perm, V, E, 1, padding_row, grad_table, long_rows, \
+                                        scratch, s, bag_of, argmax)
+#define TRS_TERM(T)                               \
+  do {                                            \
+    if (weights != nullptr) TRS_CALL(T, RAG_WGT); \
+    if (argmax != nullptr) TRS_CALL(T, RAG_MAX);  \
+    TRS_CALL(T, RAG_PLAIN);                       \
+  } while (0)
+  if (dtype == TRS_F32) TRS_TERM(float);
+  TRS_TERM(bf16_t);
+#undef TRS_TERM
+#undef TRS_CALL
+}
+
+extern "C" int trs_bag_weight_grad_ragged(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype,
+                                          const void* ids, int32_t ids_dtype, int64_t n, const int32_t* bag_of,
+                                          int64_t exclude_row, void* dw, trs_stream_t stream) {
+  if (n == 0) return TRS_OK;
+  TRS_REQUIRE(g && table && ids && bag_of && dw, TRS_EINVAL, "bag_weight_grad_ragged: NULL pointer");
+  TRS_REQUIRE(V > 0 && E > 0 && n >= 0, TRS_EINVAL, "bag_weight_grad_ragged: bad size V=%lld E=%d n=%lld", (long long)V,
+              E, (long long)n);
+  TRS_REQUIRE(n < (int64_t)0x7fffffff, TRS_ESHAPE, "bag_weight_grad_ragged: n=%lld must fit int32", (long long)n);
+  TRS_REQUIRE(exclude_row >= -1 && exclude_row < V, TRS_EINVAL,
+              "bag_weight_grad_ragged: exclude_row %lld outside [-1, V)", (long long)exclude_row);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "bag_weight_grad_ragged: dtype %d", dtype);
+  TRS_REQUIRE(ids_dtype == TRS_I64 || ids_dtype == TRS_I32, TRS_EDTYPE, "bag_weight_grad_ragged: ids dtype %d",
+              ids_dtype);
+  hipStream_t s = (hipStream_t)stream;
+#define TRS_CALL(T, I) \
+  return bag_weight_grad_launch<T, I, true>(table, g, (const I*)ids, n, 1, E, V, exclude_row, dw, s, bag_of)
+  if (dtype == TRS_F32) {
+    if (ids_dtype == TRS_I64) TRS_CALL(float, int64_t);
+    TRS_CALL(float, int32_t);
+  }
+  if (ids_dtype == TRS_I64) TRS_CALL(bf16_t, int64_t);
   TRS_CALL(bf16_t, int32_t);
 #undef TRS_CALL
 }

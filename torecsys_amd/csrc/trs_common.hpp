@@ -116,6 +116,14 @@ __device__ __forceinline__ float group_max_down(float v) {
   for (int m = G >> 1; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
   return v;
 }
+// Sum ACROSS the 64 / L groups of L adjacent lanes of a wave: lane i of every group gets the sum over lane i of all the
+// groups (steps L, 2L, .., 32; L = 64: nothing to fold).  The groups' partials of one row, column by column.
+template <int L, typename T>
+__device__ __forceinline__ T across_groups_sum(T v) {
+#pragma unroll
+  for (int m = L; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
 // group width known at run time only (a power of two <= 64, uniform over the wave)
 __device__ __forceinline__ float group_sum_up(float v, int G) {
   for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);

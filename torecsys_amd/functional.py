@@ -730,6 +730,145 @@ def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", paddin
     return _BagPoolMasked.apply(weight, idx, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), opt)
 
 
+def bag_ragged_long_len() -> int:
+    """Bags of more ids than this are reduced by a whole wave each (the second tier of trs_bag_pool_ragged_fwd)."""
+    return size_query("trs_bag_ragged_long_len")
+
+
+class _BagPoolRagged(Function):
+    """bag_pool on one flat id vector (n,) plus offsets (trs_bag_pool_ragged_fwd).  Nothing here reads a tensor back:
+    the offsets are range-checked on the device and ``n`` is the shape of ``ids``.  The row buckets are those of the
+    ids seen as an (n, 1) batch; the lookup -> sample map (trs_bag_owner) is built in the backward only."""
+
+    @staticmethod
+    def forward(ctx, weight, ids, offsets, psw, mode, padding_idx, exclude, B):
+        require_device(weight, ids, offsets, psw)
+        n = ids.shape[0]
+        V, E = weight.shape
+        w = weight.contiguous()
+        wts = psw.contiguous() if psw is not None else None
+        dev = w.device
+        out = torch.empty(B, E, dtype=w.dtype, device=dev)
+        amax = torch.empty(B, E, dtype=torch.int32, device=dev) if mode == 2 else None      # flat winner positions
+        inv_cnt = torch.empty(B, dtype=torch.float32, device=dev) if mode == 1 else None
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        ctx.exclude_row = ctx.padding_idx if exclude else -1
+        ws_bytes = size_query("trs_bag_ragged_workspace_bytes", B)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        flag = _ErrFlag(dev)
+        call("trs_bag_pool_ragged_fwd", ptr(w), V, E, value_dtype_code(w), ptr(ids), index_dtype_code(ids), n,
+             ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, mode, ctx.exclude_row, ptr(wts), ptr(out),
+             ptr(amax), ptr(inv_cnt), ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+        flag.check("bag_pool_ragged")
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        if ctx.needs_input_grad[0] and n > 0 and B > 0:
+            prefetch_row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
+        ctx.has = (wts is not None, amax is not None, inv_cnt is not None)
+        ctx.save_for_backward(ids, offsets, weight, *[t for t in (wts, amax, inv_cnt) if t is not None])
+        ctx.mode, ctx.B = mode, B
+        return out.unsqueeze(1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ids, offsets, weight = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[3:])
+        wts, amax, inv_cnt = (rest.pop(0) if h else None for h in ctx.has)
+        _adopt_grads(g)
+        V, E = weight.shape
+        n, B = ids.shape[0], ctx.B
+        dev = weight.device
+        g2 = g.reshape(B, E)
+        # mean: times 1 / cnt[b] in fp32, rounded once to the table's dtype, on (B, E) -- as _BagPoolMasked does
+        g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
+        grad = dw = None
+        need_dw = wts is not None and ctx.needs_input_grad[3]
+        if not (ctx.needs_input_grad[0] or need_dw):      # a frozen table without weights: no map, no walk
+            return None, None, None, None, None, None, None, None
+        if n == 0 or B == 0:      # no lookup belongs to a bag
+            if ctx.needs_input_grad[0]:
+                grad = torch.zeros(V, E, dtype=weight.dtype, device=dev)
+            if need_dw:
+                dw = torch.zeros(n, dtype=wts.dtype, device=dev)
+            return grad, None, None, dw, None, None, None, None
+        bag_of = torch.empty(n, dtype=torch.int32, device=dev)
+        call("trs_bag_owner", ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, n, ptr(bag_of), stream_ptr())
+        if need_dw:
+            dw = torch.empty(n, dtype=wts.dtype, device=dev)
+            call("trs_bag_weight_grad_ragged", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(ids),
+                 index_dtype_code(ids), n, ptr(bag_of), ctx.exclude_row, ptr(dw), stream_ptr())
+        if ctx.needs_input_grad[0]:
+            rb = row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
+            grad = torch.empty(V, E, dtype=weight.dtype, device=dev)
+            ws_bytes = size_query("trs_scatter_ragged_workspace_bytes", n, E)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            call("trs_scatter_rows_ragged", ptr(g2), ptr(bag_of), ptr(wts), ptr(amax), ptr(rb.row_start), ptr(rb.perm),
+                 n, B, V, E, value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+        return grad, None, None, dw, None, None, None, None
+
+
+def bag_pool_ragged(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, mode: str = "mean",
+                    padding_idx: Optional[int] = None, *, exclude_padding: bool = False,
+                    per_sample_weights: Optional[torch.Tensor] = None, include_last_offset: bool = False,
+                    opt=None) -> torch.Tensor:
+    """(B,1,E) pooled rows of RAGGED bags, nn.EmbeddingBag's calling form: ``ids`` (n,) or (n,1) is one flat vector of
+    row ids, ``offsets`` (int64 / int32) says where each sample's bag begins; bag b is ids[offsets[b]:offsets[b+1]], the
+    last one runs to n -- or, with ``include_last_offset=True``, B = len(offsets) - 1 and ids behind offsets[-1] belong to
+    no bag.  ``sum`` / ``mean`` (over the bag's own length; an empty bag is a zero row) / ``max`` (first position wins a
+    tie) in one pass: nothing is padded, no bag length is read on the host, a few very long bags are reduced by a wave
+    each.  ``padding_idx``, ``exclude_padding`` and ``per_sample_weights`` (n,) mean what they mean in ``bag_pool``.
+
+    Offsets are checked on the device: they are clamped to [0, n], and an offset outside it or a decreasing pair (that bag
+    is empty) raises the index flag (``index_errors_seen()``; IndexError with TRS_CHECK_INDICES=1).  A fused sparse
+    optimizer is not served."""
+    if mode not in BAG_MODES:
+        raise ValueError(f'bag_pool_ragged: mode must be one of {sorted(BAG_MODES)}, got {mode!r}')
+    if opt is not None:
+        raise NotImplementedError("torecsys_amd: ragged bags with a fused sparse optimizer are not implemented: the "
+                                  "fused-update walks find the sample of a lookup by dividing its position by the list "
+                                  "length, which ragged bags do not have (use a dense optimizer)")
+    ids = _as_index(ids)
+    if ids.dim() == 2 and ids.shape[1] == 1:
+        ids = ids.reshape(-1)
+    if ids.dim() != 1:
+        raise ValueError(f"ids must be (n,) or (n, 1), got shape {tuple(ids.shape)}")
+    offsets = _as_index(offsets)
+    if offsets.dim() != 1:
+        raise ValueError(f"offsets must be one-dimensional, got shape {tuple(offsets.shape)}")
+    B = offsets.shape[0] - 1 if include_last_offset else offsets.shape[0]
+    if B < 0:
+        raise ValueError("bag_pool_ragged: include_last_offset=True needs at least one offset")
+    if ids.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f"bag_pool_ragged: {ids.shape[0]} ids, must be below 2^31 - 1")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = weight.shape[0] + padding_idx
+    if exclude_padding:
+        if padding_idx is None:
+            raise ValueError("bag_pool_ragged: exclude_padding=True needs a padding_idx")
+        if not 0 <= padding_idx < weight.shape[0]:
+            raise ValueError(f"bag_pool_ragged: exclude_padding=True needs a padding row inside the table, got "
+                             f"{padding_idx} for {weight.shape[0]} rows")
+    psw = per_sample_weights
+    if psw is not None:
+        if mode != "sum":
+            raise ValueError(f"bag_pool_ragged: per_sample_weights is only supported for mode='sum', got {mode!r}")
+        psw = psw.rename(None) if psw.has_names() else psw
+        if psw.dim() == 2 and psw.shape[1] == 1:
+            psw = psw.reshape(-1)
+        if tuple(psw.shape) != tuple(ids.shape):
+            raise ValueError(f"bag_pool_ragged: per_sample_weights must be (n,) = {tuple(ids.shape)}, got "
+                             f"{tuple(psw.shape)}")
+        if psw.dtype != weight.dtype:
+            raise ValueError(f"bag_pool_ragged: per_sample_weights must have the table's dtype {weight.dtype}, got "
+                             f"{psw.dtype}")
+        if psw.device != weight.device:
+            raise ValueError(f"bag_pool_ragged: per_sample_weights must be on the table's device {weight.device}, "
+                             f"got {psw.device}")
+    return _BagPoolRagged.apply(weight, ids, offsets, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), B)
+
+
 # --------------------------------------------------------------------------------------------
 # attention pooling: self-attention over the rows of a (B, L) list of ids, then sum / mean over the list
 # --------------------------------------------------------------------------------------------

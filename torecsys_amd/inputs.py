@@ -326,6 +326,71 @@ class ListIndicesEmbedding(BaseInput):
         raise NotImplementedError('torecsys_amd: show_attention (a plotting helper) is not provided')
 
 
+class RaggedListIndicesEmbedding(BaseInput):
+    """``ListIndicesEmbedding`` for bags that arrive the way ``nn.EmbeddingBag`` takes them (not in the reference): one
+    flat vector of ids (n,) and ``offsets`` that say where each sample's bag begins, instead of a (B,L) list padded to the
+    longest bag.  ``forward(values, offsets, per_sample_weights=None)`` -> (B,1,E) named ('B','N','E'), one HIP pass
+    (``functional.bag_pool_ragged``): bags of any length, empty ones (a zero row) included; no bag length is read on the
+    host.  With ``include_last_offset=True`` the last offset closes the last bag and B = len(offsets) - 1.
+
+    ``output_method``: 'avg_pooling' / 'mean' (over the bag's own length), 'max_pooling', 'sum' (the only one that takes
+    ``per_sample_weights`` (n,)).  ``exclude_padding=True`` leaves the ids equal to ``padding_idx`` out, as
+    ``nn.EmbeddingBag(padding_idx=)`` does.  The table is ``embedding.weight``, so a ``ListIndicesEmbedding`` checkpoint
+    loads.  Not offered: ``output_method='none'``, ``use_attn``, a fused sparse optimizer (NotImplementedError).
+    ``set_schema(inputs, offsets='column', weights=None)`` names the columns ``Inputs`` hands over."""
+
+    _POOL = ListIndicesEmbedding._POOL
+
+    def __init__(self, embed_size: Optional[int] = None, field_size: Optional[int] = None,
+                 padding_idx: Optional[int] = 0, nn_embedding: Optional[nn.Parameter] = None,
+                 output_method: Optional[str] = 'avg_pooling', exclude_padding: bool = False,
+                 include_last_offset: bool = False):
+        super().__init__()
+        if nn_embedding is not None:
+            self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
+        elif field_size is not None and embed_size is not None:
+            self.embedding = nn.Embedding(field_size, embed_size, padding_idx=padding_idx)
+        else:
+            raise ValueError('missing required arguments')
+        self.field_size = self.embedding.num_embeddings
+        self.embed_size = self.embedding.embedding_dim
+        self.padding_idx = self.embedding.padding_idx
+        self.length = self.embed_size
+        if output_method not in self._POOL:
+            raise ValueError(f'output_method only allows {sorted(self._POOL)}.')
+        self.output_method = output_method
+        self.exclude_padding = bool(exclude_padding)
+        if self.exclude_padding and self.padding_idx is None:
+            raise ValueError('exclude_padding=True needs a padding_idx (nn_embedding= tables have none)')
+        self.include_last_offset = bool(include_last_offset)
+
+    def set_schema(self, inputs: Union[str, List[str]], **kwargs):
+        """``offsets='column'`` (required) and ``weights='column'``: ``Inputs.forward`` hands those columns to
+        ``forward`` as ``offsets`` and ``per_sample_weights``."""
+        offsets, weights = kwargs.get('offsets', None), kwargs.get('weights', None)
+        if not isinstance(offsets, str):
+            raise TypeError(f'offsets must be a column name, got {type(offsets).__name__}')
+        if weights is not None and not isinstance(weights, str):
+            raise TypeError(f'weights must be a column name, got {type(weights).__name__}')
+        schema = namedtuple('Schema', ['inputs', 'offsets', 'weights'])
+        self.schema = schema(inputs=[inputs] if isinstance(inputs, str) else inputs, offsets=offsets, weights=weights)
+
+    def set_fused_optimizer(self, opt):
+        if opt is not None:
+            raise NotImplementedError('torecsys_amd: ragged bags with a fused sparse optimizer are not implemented (the '
+                                      'fused-update walks find the sample of a lookup by dividing its position by the '
+                                      'list length)')
+        return super().set_fused_optimizer(opt)
+
+    def forward(self, values: torch.Tensor, offsets: torch.Tensor,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        out = F_.bag_pool_ragged(self.embedding.weight, _strip(values), _strip(offsets), self._POOL[self.output_method],
+                                 self.padding_idx, exclude_padding=self.exclude_padding,
+                                 per_sample_weights=per_sample_weights, include_last_offset=self.include_last_offset,
+                                 opt=self.fused_optimizer)
+        return out.refine_names('B', 'N', 'E')
+
+
 # TRS_SEQ_RNN=0: SequenceIndicesEmbedding runs the composition (HIP row gather, the module's own nn.LSTM / nn.GRU / nn.RNN
 # on a packed sequence, ATen pooling) instead of the fused kernels, which are the default on the strength of the timing in
 # profiles/seq_rnn_kernels.md (forward + backward 4.4x to 5.5x faster at the workload shape)
@@ -607,6 +672,9 @@ class Inputs(BaseInput):
             # SequenceIndicesEmbedding, which therefore never receives its lengths there); both names are routed here
             if emb_fn.__class__.__name__ in ('SequenceIndicesEmbedding', 'SequenceIndexEmbedding'):
                 args[k].append(inputs[emb_fn.schema.lengths])
+            elif emb_fn.__class__.__name__ == 'RaggedListIndicesEmbedding':      # (n,) ids: their offsets, their weights
+                args[k].append(inputs[emb_fn.schema.offsets])
+                args[k].append(None if emb_fn.schema.weights is None else inputs[emb_fn.schema.weights])
             elif getattr(emb_fn.schema, 'weights', None) is not None:      # ListIndicesEmbedding: per_sample_weights
                 args[k].append(inputs[emb_fn.schema.weights])
         # The lookups of a batch are independent of each other: every plain lookup after the first goes onto the "lookup"
