@@ -1003,6 +1003,38 @@ int trs_attn_pool_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, co
                       const void* gout, void* dx, float* dw_part, float* db_part, int32_t blocks, void* workspace,
                       size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
 
+/* Attention pooling of RAGGED bags: the four entries above with (idx, B, L) replaced by one flat vector of ids (n,) plus
+ * offsets, as trs_bag_pool_ragged_fwd takes them: bag b is ids[offsets[b], end_b), end_b = offsets[b + 1] where that entry
+ * exists (n_off = B or B + 1), else n; begin and end are clamped to [0, n] on the device and an offset outside it or a
+ * decreasing pair (that bag is empty) raises *err_flag.  exclude_row >= 0: the ids equal to it are left out of the bag (no
+ * table load); -1: every id is live.  A bag attends to its own live ids only: the sample's L_b is the number of live ids,
+ * capped at max_len (1 <= max_len <= 64) -- the FIRST max_len live ids in list order are taken, the others contribute
+ * nothing in either direction, and a bag with more raises *err_flag.  The algebra is the padded one with L_b for L
+ * (c = 1 / L_b for the mean); no key-padding mask exists, the work is sum_b (L_b E^2 + L_b^2 E).  max_len sizes the LDS
+ * layout (it takes the place of L in the path, blocks and workspace queries); no length is read on the host.
+ *   out (B, H, E) of the table's dtype;  cnt (B,) fp32 = L_b.  L_b = 0: a zero block, cnt 0, no gradient.
+ *   The pooled layer output is concat_h(out_h Wv_h^T + c' bv_h) Wout^T + c' bout with c' = L_b (sum) or [L_b > 0] (mean).
+ * Backward: dx (n, E) of the table's dtype, row p = the gradient of position p.  The kernel writes the rows of the positions
+ * that were taken and no other: THE CALLER ZERO-FILLS dx, which makes the rows of excluded, not taken and unowned
+ * positions exact zeros.  (Bags overlap only behind a decreasing pair of offsets, which is flagged; a shared position's row
+ * then holds the gradient of one of its bags.)  dw_part / db_part / blocks / workspace as in trs_attn_pool_bwd (queries:
+ * trs_attn_pool_ragged_blocks, trs_attn_pool_ragged_bwd_workspace_bytes); static dealing, no atomics: reproducible bits.
+ * Every argument error is reported before any launch: NULL pointer (ids and dx may be NULL when n == 0, b_qk always),
+ * n_off not B or B + 1, exclude_row outside [-1, V), max_len outside [1, 64], a mode other than 0 / 1 TRS_EINVAL; n or
+ * B >= 2^31 - 1 TRS_ESHAPE; a dtype, or a shape trs_attn_pool_path(max_len, E, H, dtype) refuses, TRS_EDTYPE; a workspace
+ * below the query TRS_EWORKSPACE.  B == 0 returns TRS_OK and touches nothing; n == 0 with B > 0 gives B zero blocks.   */
+int trs_attn_pool_ragged_blocks(int64_t B, int32_t max_len, int32_t E, int32_t H, int32_t dtype, int32_t backward);
+size_t trs_attn_pool_ragged_bwd_workspace_bytes(int32_t blocks, int32_t max_len, int32_t E, int32_t H);
+int trs_attn_pool_ragged_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* ids, int32_t ids_dtype,
+                             int64_t n, const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int32_t max_len,
+                             int64_t exclude_row, const void* w_qk, const void* b_qk, int32_t H, int32_t mode, void* out,
+                             float* cnt, int32_t* err_flag, trs_stream_t stream);
+int trs_attn_pool_ragged_bwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* ids, int32_t ids_dtype,
+                             int64_t n, const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int32_t max_len,
+                             int64_t exclude_row, const void* w_qk, const void* b_qk, int32_t H, int32_t mode,
+                             const void* gout, void* dx, float* dw_part, float* db_part, int32_t blocks, void* workspace,
+                             size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
 /* ---- residual multi-head self-attention over a short list (csrc/self_attn.hip) -------------------------------------
  * y = x + nn.MultiheadAttention(x, x, x) for x (B, L, E) contiguous, no masks, no dropout.  Per sample (d = E / H):
  *   [Q | K | V] = X w_in^T + b_in;   P_h = softmax_rows(Q_h K_h^T / sqrt(d));   O = concat_h(P_h V_h)

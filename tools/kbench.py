@@ -26,7 +26,10 @@ bf16, the fused path against the same modules with the switch off, and the two k
 --world, the world-1 module against the unsharded ListIndicesEmbedding, fp32 and bf16, and the wire bytes per rank of the
 partial-sum path against the rows path (own inputs, see bench_bagshard).
 --what ragged [--shape fixed,uniform,longtail] [--modes sum,mean,max]: ragged bag pooling (ids + offsets) against bag_pool on
-the same bags padded to the longest and against F.embedding_bag with offsets (own inputs, see bench_ragged)."""
+the same bags padded to the longest and against F.embedding_bag with offsets (own inputs, see bench_ragged).
+--what raggedattn [--shape fixed,uniform,longtail]: attention pooling of ragged bags (max_length 50, H = 1 and 4) against
+ListIndicesEmbedding(use_attn=True) on the same bags padded to 50 and against the ATen composition with a key_padding_mask;
+then the two ragged kernels alone (own inputs, see bench_raggedattn)."""
 import argparse
 import os
 import sys
@@ -356,6 +359,128 @@ def bench_attn(a):
         med = ts[len(ts) // 2]
         print(f"kernel   {name:22s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us  "
               f"{fl / med / 1e12:6.1f} TFLOP/s ({blocks} workgroups in the backward)", flush=True)
+
+
+def bench_raggedattn(a):
+    """Attention pooling of ragged bags (the ragged kernels of csrc/attn_pool.hip) at B bags, E, V, H = 1 and 4,
+    max_length = 50: forward and forward + backward (row buckets rebuilt every step) of
+    RaggedListIndicesEmbedding(use_attn=True, output_method='avg_pooling'), taking turns inside every round with
+    ListIndicesEmbedding(use_attn=True) on the same bags padded with id 0 to 50 (the path before the ragged kernels; it
+    attends to the padding too) and with the ATen composition on the padded bags (embedding, nn.MultiheadAttention with a
+    key_padding_mask, masked mean); then the two new kernels alone.  Bag lengths are those of --what ragged (``fixed`` 50,
+    ``uniform`` 0..100, ``longtail`` most bags under 10 ids and 300 bags of 2000..6000), clipped to 50.  Every figure is the
+    median of ``--rounds`` per-round medians with their min..max."""
+    from torecsys_amd import inputs as I
+    from torecsys_amd._abi import call, index_dtype_code, ptr, size_query, stream_ptr, value_dtype_code
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    dev = torch.device("cuda:0")
+    B, E, V, ML = a.B, a.E, a.V, 50
+    g = torch.Generator(device=dev).manual_seed(4321)
+    gout = torch.randn(B, 1, E, generator=g, device=dev, dtype=dt)
+
+    def lengths_of(shape):
+        if shape == "fixed":
+            return torch.full((B,), 50, dtype=torch.int64, device=dev)
+        if shape == "uniform":
+            return torch.randint(0, 101, (B,), generator=g, device=dev).clamp_(max=ML)
+        ln = torch.randint(0, 10, (B,), generator=g, device=dev)
+        hot = torch.randperm(B, generator=g, device=dev)[:300]
+        ln[hot] = torch.randint(2000, 6001, (300,), generator=g, device=dev)
+        return ln.clamp_(max=ML)
+
+    for H in (1, 4):
+        rag = I.RaggedListIndicesEmbedding(embed_size=E, field_size=V, use_attn=True, num_heads=H, max_length=ML,
+                                           include_last_offset=True)
+        with torch.no_grad():
+            rag.attention.in_proj_bias.normal_(0, 0.1)
+        rag = rag.to(dev).to(dt)
+        pad = I.ListIndicesEmbedding(embed_size=E, field_size=V, use_attn=True, num_heads=H, output_method="avg_pooling")
+        pad.load_state_dict(rag.state_dict())
+        pad = pad.to(dev).to(dt)
+        params = list(rag.parameters()) + list(pad.parameters())
+        for shape in a.shape.split(","):
+            ln = lengths_of(shape)
+            offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), ln.cumsum(0)])
+            n = int(offsets[-1])
+            ids = torch.randint(1, V, (n,), generator=g, device=dev)
+            col = torch.arange(ML, device=dev).view(1, ML)
+            live = col < ln.view(B, 1)
+            padded = torch.zeros(B, ML, dtype=torch.int64, device=dev)
+            padded[live] = ids                                         # row-major: the bags in order
+            mask = ~live
+            mask[:, 0] = False                                         # an empty bag keeps one key: no NaN rows in ATen
+            cnt = ln.clamp(min=1).view(B, 1).to(dt)
+            flops = int((4 * ln * E * E + 2 * ln * ln * E).sum())
+            print(f"ragged attention pooling B={B} E={E} H={H} V={V} {a.dtype} max_length={ML} {shape}: n={n} ids "
+                  f"({n / (B * ML) * 100:.1f} % of the padded positions), forward {flops / 1e9:.1f} GFLOP against "
+                  f"{B * (4 * ML * E * E + 2 * ML * ML * E) / 1e9:.1f} padded, {a.rounds} rounds x {a.iters} launches", flush=True)
+
+            def aten():
+                seq = torch.nn.functional.embedding(padded, pad.embedding.weight).transpose(0, 1)
+                o, _ = pad.attention(seq, seq, seq, key_padding_mask=mask, need_weights=False)
+                return ((o.transpose(0, 1) * live.unsqueeze(-1)).sum(dim=1, keepdim=True) / cnt.unsqueeze(-1)).to(dt)
+
+            cands = [("ragged module (HIP)", lambda: rag(ids, offsets).rename(None)),
+                     ("padded module (HIP)", lambda: pad(padded).rename(None)), ("composition (ATen)", aten)]
+
+            def fwd_bwd(f):
+                def run():
+                    F_.clear_caches()          # the row buckets of the batch are rebuilt every step, as in training
+                    for p in params:
+                        p.grad = None
+                    f().backward(gout)
+                return run
+
+            res = {}
+            for what in ("fwd", "fwd+bwd"):
+                per = {name: [] for name, _ in cands}
+                for _ in range(a.rounds):
+                    for name, f in cands:
+                        if what == "fwd":
+                            with torch.no_grad():
+                                per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                        else:
+                            per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+                for name, ts in per.items():
+                    ts = sorted(ts)
+                    res[name] = ts[len(ts) // 2]
+                    print(f"H={H} {shape:8s} {what:8s} {name:22s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread "
+                          f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us", flush=True)
+                print(f"H={H} {shape:8s} {what:8s} padded / ragged = "
+                      f"{res['padded module (HIP)'] / res['ragged module (HIP)']:.2f}x, composition / ragged = "
+                      f"{res['composition (ATen)'] / res['ragged module (HIP)']:.2f}x", flush=True)
+            # the two new kernels alone (the backward without the zero-fill and the bucket walk around it)
+            w = rag.embedding.weight.detach()
+            wqk = rag.attention.in_proj_weight.detach()[:2 * E].contiguous()
+            bqk = rag.attention.in_proj_bias.detach()[:2 * E].contiguous()
+            code = value_dtype_code(w)
+            xt = torch.empty(B, H, E, dtype=dt, device=dev)
+            cn = torch.empty(B, dtype=torch.float32, device=dev)
+            gx = torch.randn(B, H, E, generator=g, device=dev, dtype=dt)
+            blocks = size_query("trs_attn_pool_ragged_blocks", B, ML, E, H, code, 1)
+            dx = torch.zeros(n, E, dtype=dt, device=dev)
+            dwp = torch.empty(blocks, 2 * E, E, dtype=torch.float32, device=dev)
+            dbp = torch.empty(blocks, 2 * E, dtype=torch.float32, device=dev)
+            ws_bytes = size_query("trs_attn_pool_ragged_bwd_workspace_bytes", blocks, ML, E, H)
+            ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+            oc = index_dtype_code(offsets)
+
+            def k_fwd():
+                call("trs_attn_pool_ragged_fwd", ptr(w), V, E, code, ptr(ids), index_dtype_code(ids), n, ptr(offsets), oc,
+                     B + 1, B, ML, -1, ptr(wqk), ptr(bqk), H, 1, ptr(xt), ptr(cn), None, stream_ptr())
+
+            def k_bwd():
+                call("trs_attn_pool_ragged_bwd", ptr(w), V, E, code, ptr(ids), index_dtype_code(ids), n, ptr(offsets), oc,
+                     B + 1, B, ML, -1, ptr(wqk), ptr(bqk), H, 1, ptr(gx), ptr(dx), ptr(dwp), ptr(dbp), blocks, ptr(ws),
+                     ws_bytes, None, stream_ptr())
+
+            for name, f, fl in (("trs_attn_pool_ragged_fwd", k_fwd, flops), ("trs_attn_pool_ragged_bwd", k_bwd, 4 * flops)):
+                ts = sorted(timeit(f, iters=a.iters, warm=2)[0] for _ in range(a.rounds))
+                med = ts[len(ts) // 2]
+                print(f"H={H} {shape:8s} kernel   {name:26s} med {med * 1e6:9.1f} us  spread {ts[0] * 1e6:9.1f} .. "
+                      f"{ts[-1] * 1e6:9.1f} us  {fl / med / 1e12:6.1f} TFLOP/s ({blocks} workgroups in the backward)",
+                      flush=True)
+            del ids, padded, dx
 
 
 def bench_prm(a):
@@ -1118,6 +1243,8 @@ def main():
     a = ap.parse_args()
     if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"
         return bench_ragged(a)
+    if a.what == "raggedattn":   # own inputs and modules: not part of "all"
+        return bench_raggedattn(a)
     if a.what == "bagshard":     # own inputs and modules: not part of "all"
         return bench_bagshard(a)
     if a.what == "rank":        # own inputs and modules: not part of "all"

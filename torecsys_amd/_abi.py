@@ -124,6 +124,12 @@ SIGNATURES = {
     "trs_attn_pool_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
     "trs_attn_pool_bwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I32,
                                     _P, _SZ, _P, _P]),
+    "trs_attn_pool_ragged_blocks": (c_int32, [_I64, _I32, _I32, _I32, _I32, _I32]),
+    "trs_attn_pool_ragged_bwd_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "trs_attn_pool_ragged_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _I64, _P, _P,
+                                           _I32, _I32, _P, _P, _P, _P]),
+    "trs_attn_pool_ragged_bwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _I64, _P, _P,
+                                           _I32, _I32, _P, _P, _P, _P, _I32, _P, _SZ, _P, _P]),
     "trs_self_attn_path": (c_int32, [_I32, _I32, _I32, _I32]),
     "trs_self_attn_blocks": (c_int32, [_I64, _I32, _I32, _I32, _I32, _I32]),
     "trs_self_attn_bwd_workspace_bytes": (_SZ, [_I32, _I32]),

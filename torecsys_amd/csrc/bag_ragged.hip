@@ -31,27 +31,6 @@ namespace trs {
 // terms of a lane are still added in list order, so the result does not depend on this.
 constexpr int BAG_RAGGED_LONG_CH = 4;
 
-// [begin, end) of bag b, clamped to [0, n]; end < begin: empty.  Either defect raises the flag.
-__device__ __forceinline__ void bag_ragged_bounds(const void* __restrict__ offsets, bool off64, int64_t n_off, int64_t b,
-                                                  int64_t n, int32_t* __restrict__ err_flag, int64_t* beg, int64_t* end) {
-  int64_t o0, o1 = n;
-  if (off64) {
-    o0 = ((const int64_t*)offsets)[b];
-    if (b + 1 < n_off) o1 = ((const int64_t*)offsets)[b + 1];
-  } else {
-    o0 = (int64_t)((const int32_t*)offsets)[b];
-    if (b + 1 < n_off) o1 = (int64_t)((const int32_t*)offsets)[b + 1];
-  }
-  if (o0 < 0 || o0 > n || o1 < 0 || o1 > n || o1 < o0) {
-    if (err_flag != nullptr) *err_flag = 1;
-    o0 = o0 < 0 ? 0 : (o0 > n ? n : o0);
-    o1 = o1 < 0 ? 0 : (o1 > n ? n : o1);
-    if (o1 < o0) o1 = o0;
-  }
-  *beg = o0;
-  *end = o1;
-}
-
 // The positions q = beg, beg + step, .. < end, CH rows in flight: s[k] (+)= the term of q, am[k] = the winning FLAT
 // position (max; < 0: none yet -- the first live position is always taken), cnt += the live positions.  pad >= 0: a position
 // that holds that id issues no load and takes no part.  WGT (sum only): every term times wts[q].

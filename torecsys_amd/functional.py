@@ -995,6 +995,158 @@ def attn_pool_layer(weight: torch.Tensor, idx: torch.Tensor, in_proj_weight: tor
     return y.unsqueeze(1)
 
 
+class _AttnPoolRagged(Function):
+    """attn_pool on one flat id vector (n,) plus offsets (trs_attn_pool_ragged_fwd): _AttnPool's recompute-in-backward
+    shape with _BagPoolRagged's operands.  Nothing here reads a tensor back: offsets, live counts and the ``max_length``
+    cap are checked on the device.  The row buckets are those of the ids seen as an (n, 1) batch."""
+
+    @staticmethod
+    def forward(ctx, weight, ids, offsets, w_qk, b_qk, num_heads, mode, padding_idx, exclude, B, max_length):
+        require_device(weight, ids, offsets, w_qk, b_qk)
+        n = ids.shape[0]
+        V, E = weight.shape
+        H = int(num_heads)
+        w = weight.contiguous()
+        wq = w_qk.contiguous()
+        bq = b_qk.contiguous() if b_qk is not None else None
+        dev = w.device
+        out = torch.empty(B, H, E, dtype=w.dtype, device=dev)
+        cnt = torch.empty(B, dtype=torch.float32, device=dev)
+        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
+        ctx.exclude_row = ctx.padding_idx if exclude else -1
+        flag = _ErrFlag(dev)
+        call("trs_attn_pool_ragged_fwd", ptr(w), V, E, value_dtype_code(w), ptr(ids), index_dtype_code(ids), n,
+             ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, max_length, ctx.exclude_row, ptr(wq), ptr(bq),
+             H, mode, ptr(out), ptr(cnt), ptr(flag.t), stream_ptr())
+        flag.check("attn_pool_ragged")
+        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        if ctx.needs_input_grad[0] and n > 0 and B > 0:
+            prefetch_row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
+        # nothing but the inputs is kept: the backward finds the live ids again and recomputes Q, K and the probabilities
+        ctx.save_for_backward(ids, offsets, weight, w_qk, b_qk)
+        ctx.H, ctx.mode, ctx.B, ctx.max_length = H, mode, B, max_length
+        ctx.mark_non_differentiable(cnt)
+        return out, cnt
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_cnt):
+        ids, offsets, weight, w_qk, b_qk = ctx.saved_tensors
+        _adopt_grads(g)
+        n, B, H = ids.shape[0], ctx.B, ctx.H
+        V, E = weight.shape
+        dev = weight.device
+        if B == 0:
+            return (torch.zeros_like(weight), None, None, torch.zeros_like(w_qk),
+                    None if b_qk is None else torch.zeros_like(b_qk), None, None, None, None, None, None)
+        w = weight.contiguous()
+        wq = w_qk.contiguous()
+        bq = b_qk.contiguous() if b_qk is not None else None
+        code = value_dtype_code(w)
+        blocks = size_query("trs_attn_pool_ragged_blocks", B, ctx.max_length, E, H, code, 1)
+        # the kernel writes the rows of the positions a bag takes; this zero-fill makes every other row (excluded, beyond
+        # max_length, in an empty range or in no bag) an exact zero
+        dx = torch.zeros(n, E, dtype=w.dtype, device=dev)
+        dw_part = torch.empty(blocks, 2 * E, E, dtype=torch.float32, device=dev)
+        db_part = torch.empty(blocks, 2 * E, dtype=torch.float32, device=dev)
+        ws_bytes = size_query("trs_attn_pool_ragged_bwd_workspace_bytes", blocks, ctx.max_length, E, H)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        # every flag was raised by the forward; the backward checks ranges without a flag of its own
+        call("trs_attn_pool_ragged_bwd", ptr(w), V, E, code, ptr(ids), index_dtype_code(ids), n, ptr(offsets),
+             index_dtype_code(offsets), offsets.shape[0], B, ctx.max_length, ctx.exclude_row, ptr(wq), ptr(bq), H, ctx.mode,
+             ptr(g.contiguous()), ptr(dx), ptr(dw_part), ptr(db_part), blocks, ptr(ws), ws_bytes, None, stream_ptr())
+        g_wqk = dw_part.sum(0).to(w_qk.dtype) if ctx.needs_input_grad[3] else None          # fixed order: reproducible
+        g_bqk = db_part.sum(0).to(b_qk.dtype) if b_qk is not None and ctx.needs_input_grad[4] else None
+        grad = None
+        if ctx.needs_input_grad[0]:
+            if n == 0:
+                grad = torch.zeros_like(weight)
+            else:
+                rb = row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
+                grad = scatter_rows(rb, weight, g_rows=dx, padding_row=ctx.padding_idx)
+        return grad, None, None, g_wqk, g_bqk, None, None, None, None, None, None
+
+
+def attn_pool_ragged(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, w_qk: torch.Tensor,
+                     b_qk: Optional[torch.Tensor], num_heads: int, mode: str = "mean", padding_idx: Optional[int] = None, *,
+                     max_length: int, exclude_padding: bool = False,
+                     include_last_offset: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``attn_pool`` for RAGGED bags (``ids`` (n,) or (n,1) plus ``offsets``, as ``bag_pool_ragged`` takes them): a bag
+    attends to its own ids and nothing else.  Returns ``(xt (B, H, E), cnt (B,) fp32)``: per head
+    ``sum_m pbar_h[m] * weight[ids_b[m]]`` over the L_b ids the bag holds, ``pbar_h`` the column sums (``sum``) or the
+    column sums / L_b (``mean``) of the bag's own (L_b, L_b) softmax, and ``cnt[b] = L_b`` (not differentiable).  With
+    ``exclude_padding=True`` the ids equal to ``padding_idx`` are removed from the bag first (no key-padding mask
+    exists).  ``max_length`` (1..64) sizes the kernels' working set and caps a bag: the first ``max_length`` live ids are
+    taken, the others contribute nothing, and a longer bag raises the index flag (``index_errors_seen()``; IndexError with
+    TRS_CHECK_INDICES=1) -- as an out-of-range id or offset does.  An empty bag gives a zero block and ``cnt = 0``.  No
+    length is read on the host.  Raises for shapes ``attn_pool_path(max_length, E, H, dtype)`` refuses."""
+    if mode not in ATTN_POOL_MODES:
+        raise ValueError(f'attn_pool_ragged: mode must be one of {sorted(ATTN_POOL_MODES)}, got {mode!r}')
+    max_length = int(max_length)
+    if not 1 <= max_length <= 64:
+        raise ValueError(f"attn_pool_ragged: max_length must be in [1, 64], got {max_length}")
+    ids = _as_index(ids)
+    if ids.dim() == 2 and ids.shape[1] == 1:
+        ids = ids.reshape(-1)
+    if ids.dim() != 1:
+        raise ValueError(f"ids must be (n,) or (n, 1), got shape {tuple(ids.shape)}")
+    offsets = _as_index(offsets)
+    if offsets.dim() != 1:
+        raise ValueError(f"offsets must be one-dimensional, got shape {tuple(offsets.shape)}")
+    B = offsets.shape[0] - 1 if include_last_offset else offsets.shape[0]
+    if B < 0:
+        raise ValueError("attn_pool_ragged: include_last_offset=True needs at least one offset")
+    if ids.shape[0] >= 2 ** 31 - 1:
+        raise ValueError(f"attn_pool_ragged: {ids.shape[0]} ids, must be below 2^31 - 1")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
+    V, E = weight.shape
+    if tuple(w_qk.shape) != (2 * E, E) or (b_qk is not None and tuple(b_qk.shape) != (2 * E,)):
+        raise ValueError(f"attn_pool_ragged: w_qk must be ({2 * E}, {E}) and b_qk ({2 * E},)")
+    if w_qk.dtype != weight.dtype or (b_qk is not None and b_qk.dtype != weight.dtype):
+        raise TypeError("attn_pool_ragged: w_qk / b_qk must have the table's dtype")
+    if attn_pool_path(max_length, E, num_heads, weight.dtype) == 0:
+        raise NotImplementedError(f"torecsys_amd: attn_pool_ragged does not cover max_length={max_length}, E={E}, "
+                                  f"H={num_heads}, {weight.dtype} (E <= 128, E % H == 0, fp32 / bf16)")
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = V + padding_idx
+    if exclude_padding:
+        if padding_idx is None:
+            raise ValueError("attn_pool_ragged: exclude_padding=True needs a padding_idx")
+        if not 0 <= padding_idx < V:
+            raise ValueError(f"attn_pool_ragged: exclude_padding=True needs a padding row inside the table, got "
+                             f"{padding_idx} for {V} rows")
+    return _AttnPoolRagged.apply(weight, ids, offsets, w_qk, b_qk, num_heads, ATTN_POOL_MODES[mode], padding_idx,
+                                 bool(exclude_padding), B, max_length)
+
+
+def attn_pool_ragged_layer(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, in_proj_weight: torch.Tensor,
+                           in_proj_bias: Optional[torch.Tensor], out_w: torch.Tensor, out_b: Optional[torch.Tensor],
+                           num_heads: int, mode: str = "mean", padding_idx: Optional[int] = None, *, max_length: int,
+                           exclude_padding: bool = False, include_last_offset: bool = False) -> torch.Tensor:
+    """(B, 1, E): per bag, ``nn.MultiheadAttention`` (no masks, no dropout) over the bag's own rows followed by the sum /
+    mean over them.  ``attn_pool_ragged`` covers what depends on the positions; the value and output projections act on
+    its (B, H, E) result as in ``attn_pool_layer``, with a per-sample bias factor c'[b] = L_b (sum) or [L_b > 0] (mean),
+    so an empty bag is an exact zero row in both modes."""
+    E = weight.shape[1]
+    H = int(num_heads)
+    d = E // H
+    xt, cnt = attn_pool_ragged(weight, ids, offsets, in_proj_weight[:2 * E],
+                               None if in_proj_bias is None else in_proj_bias[:2 * E], H, mode, padding_idx,
+                               max_length=max_length, exclude_padding=exclude_padding,
+                               include_last_offset=include_last_offset)
+    B = xt.shape[0]
+    cb = (cnt if mode == "sum" else (cnt > 0)).to(xt.dtype).unsqueeze(1)                     # (B, 1)
+    wv = in_proj_weight[2 * E:].reshape(H, d, E)
+    o = torch.bmm(xt.transpose(0, 1), wv.transpose(1, 2)).transpose(0, 1).reshape(B, E)      # (H,B,E)x(H,E,d) -> (B, H*d)
+    if in_proj_bias is not None:
+        o = o + cb * in_proj_bias[2 * E:]
+    y = torch.nn.functional.linear(o, out_w)
+    if out_b is not None:
+        y = y + cb * out_b
+    return y.unsqueeze(1)
+
+
 # --------------------------------------------------------------------------------------------
 # residual self-attention over a short list: x + nn.MultiheadAttention(x, x, x), un-pooled
 # --------------------------------------------------------------------------------------------

@@ -336,15 +336,28 @@ class RaggedListIndicesEmbedding(BaseInput):
     ``output_method``: 'avg_pooling' / 'mean' (over the bag's own length), 'max_pooling', 'sum' (the only one that takes
     ``per_sample_weights`` (n,)).  ``exclude_padding=True`` leaves the ids equal to ``padding_idx`` out, as
     ``nn.EmbeddingBag(padding_idx=)`` does.  The table is ``embedding.weight``, so a ``ListIndicesEmbedding`` checkpoint
-    loads.  Not offered: ``output_method='none'``, ``use_attn``, a fused sparse optimizer (NotImplementedError).
-    ``set_schema(inputs, offsets='column', weights=None)`` names the columns ``Inputs`` hands over."""
+    loads.  Not offered: ``output_method='none'``, a fused sparse optimizer (NotImplementedError).
+    ``set_schema(inputs, offsets='column', weights=None)`` names the columns ``Inputs`` hands over.
+
+    ``use_attn=True`` (with ``max_length``, and ``num_heads`` / ``dropout`` / ``bias`` for the module's own
+    ``nn.MultiheadAttention``): self-attention over the bag's OWN ids followed by the mean / sum over them, one HIP pass
+    per direction (``functional.attn_pool_ragged_layer``, csrc/attn_pool.hip).  No padding exists, so nothing but the
+    bag's ids takes part in the softmax -- with ``exclude_padding=True`` the ids equal to ``padding_idx`` are removed
+    first -- and the work is proportional to the bags' own lengths.  ``max_length`` (1..64) sizes the kernels' working set
+    and caps a bag: the first ``max_length`` live ids are taken and a longer bag raises the index flag
+    (``functional.index_errors_seen()``); an empty bag is a zero row.  Parameters and ``state_dict`` keys are those of
+    ``ListIndicesEmbedding(use_attn=True)``, so checkpoints load either way.  There is no composition fallback: E > 128,
+    another dtype than fp32 / bf16, attention parameters of another dtype than the table, or attention dropout in
+    training mode raise NotImplementedError; ``max_pooling`` and ``per_sample_weights`` with attention raise
+    ValueError."""
 
     _POOL = ListIndicesEmbedding._POOL
 
     def __init__(self, embed_size: Optional[int] = None, field_size: Optional[int] = None,
                  padding_idx: Optional[int] = 0, nn_embedding: Optional[nn.Parameter] = None,
                  output_method: Optional[str] = 'avg_pooling', exclude_padding: bool = False,
-                 include_last_offset: bool = False):
+                 include_last_offset: bool = False, use_attn: bool = False, max_length: Optional[int] = None,
+                 num_heads: int = 1, dropout: float = 0.0, bias: bool = True):
         super().__init__()
         if nn_embedding is not None:
             self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
@@ -359,6 +372,16 @@ class RaggedListIndicesEmbedding(BaseInput):
         if output_method not in self._POOL:
             raise ValueError(f'output_method only allows {sorted(self._POOL)}.')
         self.output_method = output_method
+        self.use_attn = bool(use_attn)
+        self.max_length = None
+        if self.use_attn:
+            if max_length is None or not 1 <= int(max_length) <= 64:
+                raise ValueError(f'use_attn=True needs max_length in [1, 64], got {max_length!r}')
+            if self._POOL[output_method] == 'max':
+                raise ValueError("use_attn=True pools with 'avg_pooling' / 'mean' / 'sum', not 'max_pooling'")
+            self.max_length = int(max_length)
+            self.attention = nn.MultiheadAttention(embed_dim=self.embed_size, num_heads=num_heads, dropout=dropout,
+                                                   bias=bias)
         self.exclude_padding = bool(exclude_padding)
         if self.exclude_padding and self.padding_idx is None:
             raise ValueError('exclude_padding=True needs a padding_idx (nn_embedding= tables have none)')
@@ -384,10 +407,32 @@ class RaggedListIndicesEmbedding(BaseInput):
 
     def forward(self, values: torch.Tensor, offsets: torch.Tensor,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.use_attn:
+            return self._forward_attn(values, offsets, per_sample_weights)
         out = F_.bag_pool_ragged(self.embedding.weight, _strip(values), _strip(offsets), self._POOL[self.output_method],
                                  self.padding_idx, exclude_padding=self.exclude_padding,
                                  per_sample_weights=per_sample_weights, include_last_offset=self.include_last_offset,
                                  opt=self.fused_optimizer)
+        return out.refine_names('B', 'N', 'E')
+
+    def _forward_attn(self, values, offsets, per_sample_weights):
+        if per_sample_weights is not None:
+            raise ValueError('per_sample_weights is not served with use_attn=True')
+        a, w = self.attention, self.embedding.weight
+        if a.dropout > 0.0 and self.training:
+            raise NotImplementedError('torecsys_amd: attention dropout in training mode is not implemented for ragged '
+                                      'bags (use dropout=0.0 or eval mode)')
+        if a.in_proj_weight.dtype != w.dtype:
+            raise NotImplementedError(f'torecsys_amd: the attention parameters ({a.in_proj_weight.dtype}) must have the '
+                                      f"table's dtype ({w.dtype})")
+        if F_.attn_pool_path(self.max_length, self.embed_size, a.num_heads, w.dtype) == 0:
+            raise NotImplementedError(f'torecsys_amd: attention pooling of ragged bags does not cover E={self.embed_size}, '
+                                      f'H={a.num_heads}, {w.dtype} (E <= 128, fp32 / bf16)')
+        out = F_.attn_pool_ragged_layer(w, _strip(values), _strip(offsets), a.in_proj_weight, a.in_proj_bias,
+                                        a.out_proj.weight, a.out_proj.bias, a.num_heads, self._POOL[self.output_method],
+                                        self.padding_idx, max_length=self.max_length,
+                                        exclude_padding=self.exclude_padding,
+                                        include_last_offset=self.include_last_offset)
         return out.refine_names('B', 'N', 'E')
 
 
