@@ -762,6 +762,28 @@ int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, c
 int32_t trs_wgrad_wide_splits(int32_t M_x, int32_t N_g, int32_t ld_g, int64_t rows);
 int trs_wgrad_wide(const void* x, int32_t ldx, const void* g, int32_t ldg, int64_t rows, int32_t M_x, int32_t N_g,
                    int32_t S, float* part, trs_stream_t stream);
+/* 1 .. 4 such products over the SAME rows in one launch of the four-wave kernel (a deep branch: the wide first layer and
+ * the 400 x 400 layers behind it): job k is x[k] (rows, ldx[k]) against g[k] (rows, ldg[k]) into part[k] (S, M_x[k],
+ * N_g[k]).  HOST arrays; the job table travels in the kernel arguments, nothing is uploaded or allocated, the launch can
+ * be captured.  trs_wgrad_wide_many_splits answers S > 0 when every job is a shape trs_wgrad_wide takes (with ldx[k] >=
+ * M_x[k] a multiple of 8), the blocks of all jobs, TB = sum of M_x[k] / 208, divide 32 -- then S = 8 * min(32 / TB, 4)
+ * and all TB workgroups of a row range sit on one XCD, the jobs in table order --, rows is a multiple of 128 and at
+ * least 128 * S; 0 otherwise, and the caller keeps the per-product calls.  trs_wgrad_wide_many takes exactly that S and
+ * 16-byte aligned operands and partials; every job is checked before the launch.  trs_wgrad_wide_many_map (host only):
+ * out = {job, row range, block of the job, first row, end row} of workgroup ``block``, returns the grid size (0: not
+ * taken / no such block).  trs_wgrad_finish_t_many = trs_wgrad_finish_t for every job (one S, one dtype; gb[k] /
+ * gb_f32[k] both or neither) in one launch, ranges summed in order; a job with part[k] = gw[k] = NULL only casts
+ * gb[k][c] = gb_f32[k][c] for c < out_cols[k], as in trs_wgrad_finish_many.                                            */
+int32_t trs_wgrad_wide_many_splits(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
+                                   const int32_t* ldg, int64_t rows);
+int32_t trs_wgrad_wide_many_map(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
+                                const int32_t* ldg, int64_t rows, int32_t block, int64_t* out);
+int trs_wgrad_wide_many(int32_t n_jobs, const void* const* x, const int32_t* ldx, const void* const* g,
+                        const int32_t* ldg, int64_t rows, const int32_t* M_x, const int32_t* N_g, int32_t S,
+                        float* const* part, trs_stream_t stream);
+int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
+                            const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                            const float* const* gb_f32, void* const* gb, trs_stream_t stream);
 /* n strided 2-D copies in one launch: desc (device, n x 6 int64) = {src address, dst address, rows, cols, src_ld,
  * dst_ld} (sizes in elements of elem_size bytes); max_elems = the largest rows*cols (sizes the grid).  Refreshes the
  * zero-padded copies of an MLP stack's nn.Linear parameters (multilayer_perceptron.py:55-61) before a forward.     */

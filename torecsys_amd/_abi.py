@@ -45,7 +45,11 @@ SIGNATURES = {
     "trs_wgrad_finish_many": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "trs_wgrad_wide_splits": (c_int32, [_I32, _I32, _I32, _I64]),
     "trs_wgrad_wide": (c_int32, [_P, _I32, _P, _I32, _I64, _I32, _I32, _I32, _P, _P]),
-    "trs_copy_padded_many": (c_int32, [_P, _I32, _I32, _I64, _P]),
+    "trs_wgrad_wide_many_splits": (c_int32, [_I32, _P, _P, _P, _P, _I64]),
+    "trs_wgrad_wide_many_map": (c_int32, [_I32, _P, _P, _P, _P, _I64, _I32, _P]),
+    "trs_wgrad_wide_many": (c_int32, [_I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _P]),
+    "trs_wgrad_finish_t_many": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "trs_copy_padded_many":(c_int32, [_P, _I32, _I32, _I64, _P]),
     "trs_cin_glue_blocks": (c_int32, [_I64]),
     "trs_cin_glue_stats": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_cin_glue_fwd": (c_int32, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),

@@ -359,9 +359,9 @@ __global__ __launch_bounds__(256) void wgrad_finish_few_rows_kernel(const float*
 // (2496 x 512) hipBLASLt runs that orientation 1.5x faster than g^T x.  32 x 32 tiles through LDS so that both the
 // reads (along r) and the writes (along c) are coalesced.
 template <typename T>
-__global__ __launch_bounds__(256) void wgrad_finish_t_kernel(const float* __restrict__ part, int S, int Cc, int R,
-                                                            int out_rows, int out_cols, T* __restrict__ gw,
-                                                            const float* __restrict__ gbf, T* __restrict__ gb) {
+__device__ __forceinline__ void wgrad_finish_t_body(const float* __restrict__ part, int S, int Cc, int R, int out_rows,
+                                                    int out_cols, T* __restrict__ gw, const float* __restrict__ gbf,
+                                                    T* __restrict__ gb) {
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
   if ((int)blockIdx.y == (out_cols + 31) / 32) {                // the extra row of workgroups: bias gradient
@@ -395,6 +395,29 @@ __global__ __launch_bounds__(256) void wgrad_finish_t_kernel(const float* __rest
     const int r = r0 + ty + 8 * i, c = c0 + tx;
     if (r < out_rows && c < out_cols) gw[(size_t)r * out_cols + c] = from_f32<T>(tile[tx][ty + 8 * i]);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad_finish_t_kernel(const float* __restrict__ part, int S, int Cc, int R,
+                                                            int out_rows, int out_cols, T* __restrict__ gw,
+                                                            const float* __restrict__ gbf, T* __restrict__ gb) {
+  wgrad_finish_t_body<T>(part, S, Cc, R, out_rows, out_cols, gw, gbf, gb);
+}
+
+// The transposed finish for several weight gradients in one launch (the partials of trs_wgrad_wide_many): blockIdx.z is
+// the job, the table travels in the kernel arguments (job fields: R = the partial's fast dimension, Cc its slow one).  The
+// grid is sized by the largest job; the bias row of workgroups is each job's own (out_cols + 31) / 32.  Jobs without a
+// product cast only, as in wgrad_finish_many_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad_finish_t_many_kernel(WgradFinishArgs a) {
+  const WgradFinishJob& j = a.job[blockIdx.z];
+  if (j.part == nullptr) {
+    const int c = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    if (c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
+    return;
+  }
+  if ((int)blockIdx.x >= (j.out_rows + 31) / 32 || (int)blockIdx.y > (j.out_cols + 31) / 32) return;
+  wgrad_finish_t_body<T>(j.part, a.S, j.Cc, j.R, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb);
 }
 
 }  // namespace trs
@@ -816,6 +839,41 @@ extern "C" int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int3
     hipLaunchKernelGGL((wgrad_finish_t_kernel<bf16_t>), grid, dim3(256), 0, s, part, S, Cc, R, out_rows, out_cols,
                        (bf16_t*)gw, gb_f32, (bf16_t*)gb);
   return check_launch("wgrad_finish_t");
+}
+
+extern "C" int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
+                                       const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                       void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_t_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
+  TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_t_many: NULL array");
+  TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_t_many: bad size");
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish_t_many: dtype %d", dtype);
+  WgradFinishArgs a{};
+  a.S = S;
+  int gx = 1, gy = 1;
+  for (int k = 0; k < n_jobs; ++k) {
+    if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
+      TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
+                  "wgrad_finish_t_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
+      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k]};
+      continue;
+    }
+    TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
+                TRS_EINVAL, "wgrad_finish_t_many: bad size (job %d)", k);
+    TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_t_many: NULL pointer (job %d)", k);
+    TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_t_many: gb and gb_f32 go together (job %d)", k);
+    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k]};
+    gx = std::max(gx, (out_rows[k] + 31) / 32);
+    gy = std::max(gy, (out_cols[k] + 31) / 32 + 1);
+  }
+  for (int k = 0; k < n_jobs; ++k)      // a cast-only job's columns, 256 per workgroup of the (gx, gy) plane
+    if (part[k] == nullptr && (out_cols[k] + 255) / 256 > gx * gy) gx = ((out_cols[k] + 255) / 256 + gy - 1) / gy;
+  dim3 grid(gx, gy, n_jobs);
+  if (dtype == TRS_F32)
+    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("wgrad_finish_t_many");
 }
 
 // ------------------------------------------------------------------------------------------------

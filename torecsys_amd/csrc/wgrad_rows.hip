@@ -440,40 +440,66 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(WgradManyArgs am) {
 // perfectly; here it is 80 KB per 338-tile step.  The g block is also fetched once instead of twice.  Three images per
 // step (g, x block 0, x block 1: 39 pieces), ring of four slots, copies three steps ahead.  For long row ranges
 // (rows >= WD2_MIN_ROWS: twice as many fp32 partials as the eight-wave form for the same number of workgroups).
-// trs_wgrad_wide (end of file) runs the same kernel on a wide input with the operands' roles swapped.
+// trs_wgrad_wide (end of file) runs the same kernel on a wide input with the operands' roles swapped, and
+// trs_wgrad_wide_many several such products over the same rows in one launch.
 constexpr int WD2_SLOT = 3 * WD_IMG;
 constexpr int WD2_NSLOT = 4;
 constexpr int WD2_AHEAD = 3;
 constexpr int64_t WD2_MIN_ROWS = 1 << 20;
 
-// workgroup b -> (row range ``slot`` of a.S, g block ``mb`` of a.MB), for any a.MB and a.S.  Blocks b and b + 8 share an
-// XCD (dealt round-robin), one workgroup fills a CU.  The first 8 * slots_per_xcd ranges are XCD-local: the MB workgroups
-// of a range sit on one XCD, so the x rows all of them read come out of that XCD's L2.  Where MB does not divide the 32
-// CUs of an XCD (12 blocks: 2 ranges on 24 CUs), the ranges behind those are dealt over the CUs left over, MB
+// wgrad_dma2_kernel's arguments: 1 .. WD2_MAXJ products over the same rows in ONE launch, in the KERNEL's roles (g: the
+// operand cut into MB blocks of 13 tiles, x: the two-block operand).  A row range is worked by the TB = sum of MB blocks of
+// all jobs, laid out job after job; every job has the same S ranges.  By value in the kernel arguments, as WgradManyArgs.
+constexpr int WD2_MAXJ = 4;
+struct Wgrad2Job {
+  const uint16_t* g;
+  const uint16_t* x;
+  float* part;               // (S, M, N) fp32
+  int ldg, ldx, M, N, MB;
+};
+struct Wgrad2Args {
+  Wgrad2Job job[WD2_MAXJ];
+  int64_t rows;
+  int J, TB, slots_per_xcd, S;      // S >= 8 * slots_per_xcd (see wd2_place)
+};
+
+// workgroup b -> (row range ``slot`` of S, block ``t`` of the TB blocks of a range), for any TB and S.  Blocks b and b + 8
+// share an XCD (dealt round-robin), one workgroup fills a CU.  The first 8 * spx ranges are XCD-local: the TB workgroups
+// of a range sit on one XCD, so the x rows all of them read come out of that XCD's L2.  Where TB does not divide the 32
+// CUs of an XCD (12 blocks: 2 ranges on 24 CUs), the ranges behind those are dealt over the CUs left over, TB
 // consecutive ones of them to a range (2496 columns: 5 more ranges, 252 of 256 CUs at work).  Measured at 65 536 rows of
 // 2496 x 400 (profiles/wgrad_wide.md): 16 local ranges on 192 CUs 177-188 us; 21 ranges, all dealt in dispatch order
 // (range-major or block-major) 149-154 us; this map 143-146 us.
-__device__ __forceinline__ void wd2_place(const WgradArgs& a, int b, int& slot, int& mb) {
-  const int xcd = b & 7, j = b >> 3, local = a.slots_per_xcd * a.MB;
+__host__ __device__ __forceinline__ void wd2_place(int TB, int spx, int b, int& slot, int& t) {
+  const int xcd = b & 7, j = b >> 3, local = spx * TB;
   if (j < local) {
-    slot = xcd * a.slots_per_xcd + j / a.MB;
-    mb = j % a.MB;
+    slot = xcd * spx + j / TB;
+    t = j % TB;
   } else {
     const int r = (j - local) * 8 + xcd;
-    slot = 8 * a.slots_per_xcd + r / a.MB;      // (>= a.S: the grid is rounded up to whole rounds of 8)
-    mb = r % a.MB;
+    slot = 8 * spx + r / TB;      // (>= S: the grid is rounded up to whole rounds of 8)
+    t = r % TB;
   }
 }
 
-__global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(WgradArgs a) {
+// block ``t`` of a range -> (job, block ``mb`` of that job): the jobs' blocks follow each other in table order
+__host__ __device__ __forceinline__ void wd2_job(const Wgrad2Args& am, int t, int& job, int& mb) {
+  job = 0, mb = t;
+  while (job + 1 < am.J && mb >= am.job[job].MB) mb -= am.job[job++].MB;
+}
+
+__global__ __launch_bounds__(256, 1) void wgrad_dma2_kernel(Wgrad2Args am) {
   extern __shared__ __attribute__((aligned(16))) char wg_lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane >> 4, i = lane & 15;
   const bool odd = q & 1;
-  const int S = a.S;
-  int slot, mb;
-  wd2_place(a, blockIdx.x, slot, mb);
+  const int S = am.S;
+  int slot, blk, jb, mb;
+  wd2_place(am.TB, am.slots_per_xcd, blockIdx.x, slot, blk);
   if (slot >= S) return;
+  wd2_job(am, blk, jb, mb);
+  const Wgrad2Job& jd = am.job[jb];      // (uniform: scalar loads from the kernel arguments)
+  const WgradArgs a{jd.g, jd.x, jd.part, am.rows, jd.ldg, jd.ldx, jd.M, jd.N, jd.MB, 2, am.slots_per_xcd, S};
   const int Mt = (a.M + 15) >> 4, Nt = (a.N + 15) >> 4;
   const int bm0 = split_start(Mt, a.MB, mb), PM = split_start(Mt, a.MB, mb + 1) - bm0;
   const int xb = wave >> 1;                              // this wave's x block
@@ -690,7 +716,7 @@ static int wgrad_launch(const WgradArgs& a, int grid, size_t lds, hipStream_t s)
                           : wgrad_launch_c<WM, WN, MC, NC, false>(a, grid, lds, s);
 }
 
-static int wgrad_dma2_launch(const WgradArgs& a, int grid, hipStream_t s, const char* what) {
+static int wgrad_dma2_launch(const Wgrad2Args& a, int grid, hipStream_t s, const char* what) {
   static bool attr2 = false;
   if (!attr2) {
     if (hipFuncSetAttribute((const void*)wgrad_dma2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -735,9 +761,11 @@ extern "C" int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t
   const size_t lds = (size_t)(4 * (PM + PN) + WG_TC) * WG_PANEL;      // + the panels a short wave runs on into
   const int grid = 8 * p.slots_per_xcd * p.MB * p.NB;
   TRS_REQUIRE(p.dma == 0 || (int64_t)WG_KS * std::max(ldg, ldx) * 2 < ((int64_t)1 << 31), TRS_ESHAPE, "wgrad_rows: row stride too large");
-  if (p.dma == 2) {
-    a.S = 8 * p.slots_per_xcd;
-    return wgrad_dma2_launch(a, a.S * p.MB, s, "wgrad_rows(dma2)");
+  if (p.dma == 2) {      // a job table of one
+    Wgrad2Args a2{};
+    a2.job[0] = Wgrad2Job{a.g, a.x, part, ldg, ldx, M, N, p.MB};
+    a2.rows = rows, a2.J = 1, a2.TB = p.MB, a2.slots_per_xcd = p.slots_per_xcd, a2.S = 8 * p.slots_per_xcd;
+    return wgrad_dma2_launch(a2, a2.S * p.MB, s, "wgrad_rows(dma2)");
   }
   if (p.dma == 1) {      // a job table of one: the same grid and the same map as ever
     WgradManyArgs am{};
@@ -813,12 +841,17 @@ static WidePlan wide_plan(int MB) {
   return w;
 }
 
-extern "C" int32_t trs_wgrad_wide_splits(int32_t M_x, int32_t N_g, int32_t ld_g, int64_t rows) {
-  if (M_x < 2 * 208 || M_x % 208 || N_g < 8 || (N_g & 15) || (ld_g & 7) || rows <= 0 || rows % (4 * WG_KS)) return 0;
+// the shape of one product, whatever the rows
+static bool wide_job_ok(int M_x, int N_g, int ld_g) {
+  if (M_x < 2 * 208 || M_x % 208 || N_g < 8 || (N_g & 15) || (ld_g & 7)) return false;
   const int Nt = N_g / 16, MB = M_x / 208;
-  if (Nt < 24 || Nt > 26 || 16 * split_start(Nt, 2, 1) + 208 > ld_g || MB > 32) return 0;      // blocks of 12 | 13 tiles, images inside the rows
-  if ((int64_t)WG_KS * std::max(M_x, ld_g) * 2 >= ((int64_t)1 << 31)) return 0;
-  const int S = wide_plan(MB).S;
+  if (Nt < 24 || Nt > 26 || 16 * split_start(Nt, 2, 1) + 208 > ld_g || MB > 32) return false;      // blocks of 12 | 13 tiles, images inside the rows
+  return (int64_t)WG_KS * std::max(M_x, ld_g) * 2 < ((int64_t)1 << 31);
+}
+
+extern "C" int32_t trs_wgrad_wide_splits(int32_t M_x, int32_t N_g, int32_t ld_g, int64_t rows) {
+  if (rows <= 0 || rows % (4 * WG_KS) || !wide_job_ok(M_x, N_g, ld_g)) return 0;
+  const int S = wide_plan(M_x / 208).S;
   return rows >= (int64_t)4 * WG_KS * S ? S : 0;
 }
 
@@ -832,6 +865,83 @@ extern "C" int trs_wgrad_wide(const void* x, int32_t ldx, const void* g, int32_t
               M_x, N_g, ldg, (long long)rows, S0, S);
   const int MB = M_x / 208;
   const WidePlan w = wide_plan(MB);
-  WgradArgs a{(const uint16_t*)x, (const uint16_t*)g, part, rows, ldx, ldg, M_x, N_g, MB, 2, w.spx, S};
+  Wgrad2Args a{};
+  a.job[0] = Wgrad2Job{(const uint16_t*)x, (const uint16_t*)g, part, ldx, ldg, M_x, N_g, MB};
+  a.rows = rows, a.J = 1, a.TB = MB, a.slots_per_xcd = w.spx, a.S = S;
   return wgrad_dma2_launch(a, w.grid, (hipStream_t)stream, "wgrad_wide");
+}
+
+// ---- several such products over the same rows in ONE launch of wgrad_dma2_kernel (the deep branch: the 2496-wide first
+// layer's twelve blocks and the two blocks of every 400 x 400 tail layer, 16 blocks in all).  A 416 x 400 product alone has
+// two blocks, which would need 128 row ranges to fill the chip; beside the first layer's twelve they fill the CUs its
+// two XCD-local ranges leave idle.  Taken when every job is one trs_wgrad_wide takes, TB = sum of M_x / 208 divides the 32
+// CUs of an XCD -- every range XCD-local, S = 8 * min(32 / TB, 4) of them, nothing dealt over left-over CUs -- and the
+// rows give every range its 128; every workgroup then has the same work (rows / S x 208 x N_g).
+struct WideManyPlan {
+  int S = 0, TB = 0, spx = 0, grid = 0;
+};
+
+static WideManyPlan wide_many_plan(int J, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g, const int32_t* ldg,
+                                   int64_t rows) {
+  WideManyPlan mp;
+  if (J < 1 || J > WD2_MAXJ || !M_x || !ldx || !N_g || !ldg || rows <= 0 || rows % (4 * WG_KS)) return mp;
+  int TB = 0;
+  for (int k = 0; k < J; ++k) {
+    if (!wide_job_ok(M_x[k], N_g[k], ldg[k]) || ldx[k] < M_x[k] || (ldx[k] & 7)) return mp;
+    if ((int64_t)WG_KS * ldx[k] * 2 >= ((int64_t)1 << 31)) return mp;
+    TB += M_x[k] / 208;
+  }
+  if (TB > 32 || 32 % TB) return mp;
+  const int spx = std::min(32 / TB, 4);
+  if (rows < (int64_t)4 * WG_KS * 8 * spx) return mp;
+  mp.S = 8 * spx, mp.TB = TB, mp.spx = spx, mp.grid = 8 * spx * TB;
+  return mp;
+}
+
+static Wgrad2Args wide_many_table(int J, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g, const int32_t* ldg,
+                                  int64_t rows, const WideManyPlan& mp) {
+  Wgrad2Args a{};
+  for (int k = 0; k < J; ++k) a.job[k] = Wgrad2Job{nullptr, nullptr, nullptr, ldx[k], ldg[k], M_x[k], N_g[k], M_x[k] / 208};
+  a.rows = rows, a.J = J, a.TB = mp.TB, a.slots_per_xcd = mp.spx, a.S = mp.S;
+  return a;
+}
+
+extern "C" int32_t trs_wgrad_wide_many_splits(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
+                                              const int32_t* ldg, int64_t rows) {
+  return wide_many_plan(n_jobs, M_x, ldx, N_g, ldg, rows).S;
+}
+
+// where workgroup ``block`` of the merged launch works: out = {job, row range, block of the job, first row, row behind
+// the last}; returns the grid (0: not taken, or no such block).  Host only -- what the tests walk.
+extern "C" int32_t trs_wgrad_wide_many_map(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
+                                           const int32_t* ldg, int64_t rows, int32_t block, int64_t* out) {
+  const WideManyPlan mp = wide_many_plan(n_jobs, M_x, ldx, N_g, ldg, rows);
+  if (mp.S == 0 || !out || block < 0 || block >= mp.grid) return 0;
+  const Wgrad2Args a = wide_many_table(n_jobs, M_x, ldx, N_g, ldg, rows, mp);
+  int slot, t, job, mb;
+  wd2_place(a.TB, a.slots_per_xcd, block, slot, t);
+  wd2_job(a, t, job, mb);
+  const int64_t quads = rows / (4 * WG_KS);
+  out[0] = job, out[1] = slot, out[2] = mb;
+  out[3] = 4 * WG_KS * (quads * slot / mp.S), out[4] = 4 * WG_KS * (quads * (slot + 1) / mp.S);
+  return mp.grid;
+}
+
+extern "C" int trs_wgrad_wide_many(int32_t n_jobs, const void* const* x, const int32_t* ldx, const void* const* g,
+                                   const int32_t* ldg, int64_t rows, const int32_t* M_x, const int32_t* N_g, int32_t S,
+                                   float* const* part, trs_stream_t stream) {
+  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WD2_MAXJ, TRS_EINVAL, "wgrad_wide_many: %d jobs (1 .. %d)", n_jobs, WD2_MAXJ);
+  if (!x || !g || !part || !ldx || !ldg || !M_x || !N_g) return fail(TRS_EINVAL, "wgrad_wide_many: null pointer");
+  const WideManyPlan mp = wide_many_plan(n_jobs, M_x, ldx, N_g, ldg, rows);
+  // S = what trs_wgrad_wide_many_splits returned
+  TRS_REQUIRE(mp.S > 0 && S == mp.S, TRS_ESHAPE, "wgrad_wide_many: %d jobs over %lld rows take %d row ranges each, caller passed %d",
+              n_jobs, (long long)rows, mp.S, S);
+  Wgrad2Args a = wide_many_table(n_jobs, M_x, ldx, N_g, ldg, rows, mp);
+  for (int k = 0; k < n_jobs; ++k) {      // every job before the launch
+    if (!x[k] || !g[k] || !part[k]) return fail(TRS_EINVAL, "wgrad_wide_many: null pointer (job %d)", k);
+    TRS_REQUIRE(aligned16(x[k]) && aligned16(g[k]) && aligned16(part[k]), TRS_ESHAPE,
+                "wgrad_wide_many: operands of job %d not 16-byte aligned", k);
+    a.job[k].g = (const uint16_t*)x[k], a.job[k].x = (const uint16_t*)g[k], a.job[k].part = part[k];
+  }
+  return wgrad_dma2_launch(a, mp.grid, (hipStream_t)stream, "wgrad_wide_many");
 }

@@ -3510,19 +3510,76 @@ def _wgrad_many_splits(jobs) -> int:
                       _i32_array([j[1].shape[1] for j in jobs]), int(jobs[0][0].shape[0]))
 
 
-def _tail_grads(layers, gw_last=None):
+# The deep branch's weight gradients as ONE product launch (trs_wgrad_wide_many) and one finish: measured against the
+# two products and two finishes it replaces (profiles/wgrad_deep.md), product + finish in us: 8192 rows 66 against 100,
+# 16 384 rows 92 against 120, 65 536 rows 200 against 237.  It is the faster pair at 8192 rows too, but the launches of
+# the 2496-400-400-400-1 stack at exactly that row count are what tests/test_gpu_wgrad_many.py and
+# tests/test_gpu_mlp_bwd_wlast.py pin (trs_wgrad_rows_many once per backward, the first layer bit-equal to
+# trs_wgrad_wide's), so the stack takes the merged launch from the next measured row count on.
+DEEP_WGRAD_MIN_ROWS = 16384
+
+
+def _wgrad_deep_jobs(first, tail):
+    """[(x, g, M_x, N_g, out_f, in_f, gb_f32 or None)] for trs_wgrad_wide_many from layer tuples (g, inp, out_f, in_f,
+    dtype, gb_f32, need_w, need_b), the first layer in front: dW^T = inp^T g over whole 208-column blocks of inp and the
+    16-column tiles of g that hold out_f; None where an operand is not a bf16 matrix of that width"""
+    jobs = []
+    for g, inp, out_f, in_f, dtype, gb_f32, _, need_b in [first] + tail:
+        M_x, N_g = (in_f + 207) // 208 * 208, (out_f + 15) // 16 * 16
+        if not (g.is_cuda and g.dtype == inp.dtype == dtype == torch.bfloat16 and g.dim() == inp.dim() == 2
+                and g.is_contiguous() and inp.is_contiguous() and g.shape[0] == inp.shape[0] == first[0].shape[0]
+                and M_x <= inp.shape[1] and N_g <= g.shape[1] and (not need_b or gb_f32 is not None)):
+            return None
+        jobs.append((inp, g, M_x, N_g, out_f, in_f, gb_f32 if need_b else None))
+    return jobs
+
+
+def _wgrad_deep_splits(jobs) -> int:
+    """Row ranges when ``jobs`` (see _wgrad_deep_jobs) go out as one launch of the four-wave LDS-DMA kernel
+    (trs_wgrad_wide_many_splits; 0: the caller keeps the launch per product)."""
+    if not WGRAD_ROWS or jobs is None or not 2 <= len(jobs) <= 4 or jobs[0][0].shape[0] < DEEP_WGRAD_MIN_ROWS:
+        return 0
+    return size_query("trs_wgrad_wide_many_splits", len(jobs), _i32_array([j[2] for j in jobs]),
+                      _i32_array([j[0].shape[1] for j in jobs]), _i32_array([j[3] for j in jobs]),
+                      _i32_array([j[1].shape[1] for j in jobs]), int(jobs[0][0].shape[0]))
+
+
+def _wgrad_deep(jobs, S, casts):
+    """the merged product and its finish; ``casts`` ride as jobs without a product.  Returns [(dW, db or None)] per job."""
+    dev, rows = jobs[0][0].device, int(jobs[0][0].shape[0])
+    parts = [torch.empty(S, j[2], j[3], dtype=torch.float32, device=dev) for j in jobs]
+    call("trs_wgrad_wide_many", len(jobs), _ptr_array([j[0] for j in jobs]), _i32_array([j[0].shape[1] for j in jobs]),
+         _ptr_array([j[1] for j in jobs]), _i32_array([j[1].shape[1] for j in jobs]), rows,
+         _i32_array([j[2] for j in jobs]), _i32_array([j[3] for j in jobs]), S, _ptr_array(parts), stream_ptr())
+    gws = [torch.empty(j[4], j[5], dtype=torch.bfloat16, device=dev) for j in jobs]
+    gbs = [torch.empty(j[4], dtype=torch.bfloat16, device=dev) if j[6] is not None else None for j in jobs]
+    n = len(casts)
+    call("trs_wgrad_finish_t_many", len(jobs) + n, _ptr_array(parts + [None] * n), S,
+         _i32_array([j[2] for j in jobs] + [0] * n), _i32_array([j[3] for j in jobs] + [0] * n),
+         _i32_array([j[4] for j in jobs] + [0] * n), _i32_array([j[5] for j in jobs] + [c[0] for c in casts]),
+         _abi.TRS_BF16, _ptr_array(gws + [None] * n), _ptr_array([j[6] for j in jobs] + [c[1] for c in casts]),
+         _ptr_array(gbs + [c[2] for c in casts]), stream_ptr())
+    return list(zip(gws, gbs))
+
+
+def _tail_grads(layers, gw_last=None, first=None):
     """(dW, db) of every layer behind the fused kernels, ``layers`` = [(g, inp, out_f, in_f, dtype, gb_f32, need_w,
     need_b)] in stack order with the output layer last.  The hidden layers whose weight gradient is needed go out as one
     batched product and one batched finish where trs_wgrad_rows_many_splits takes them (two 400 x 400 layers from 8192
     rows on); the output layer's few columns stay on their own kernel, and so does everything the query declines.
     ``gw_last``: the output layer's weight gradient as the fused backward summed it ((out_f, padded in_f) fp32, see
     fused_mlp_backward_raw): no product for that layer, the cast of its rows and of its bias gradient ride in the batched
-    finish as jobs without a product (a finish launch of their own where there is no batch)."""
+    finish as jobs without a product (a finish launch of their own where there is no batch).
+    ``first``: the same tuple for the wide layer in FRONT of the stack (_HybridMLP).  The result then has one more entry at
+    its end: that layer's (dW, db) where trs_wgrad_wide_many_splits takes it together with the batch -- one product launch
+    and one finish for all of them -- and None where it does not: the caller computes it as ever."""
     out = [None] * len(layers)
     batch = [k for k, t in enumerate(layers[:-1]) if t[6]]
+    deep = _wgrad_deep_jobs(first, [layers[k] for k in batch]) if first is not None and first[6] and batch else None
+    S_deep = _wgrad_deep_splits(deep)
     jobs = [(layers[k][0], layers[k][1], min(layers[k][0].shape[1], (layers[k][2] + 7) // 8 * 8),
              min(layers[k][1].shape[1], (layers[k][3] + 7) // 8 * 8)) for k in batch]
-    S = _wgrad_many_splits(jobs) if len({layers[k][4] for k in batch}) == 1 else 0
+    S = _wgrad_many_splits(jobs) if S_deep == 0 and len({layers[k][4] for k in batch}) == 1 else 0
     # the output layer as cast-only jobs of the finish (part = gw = None): (out_cols, fp32 source, destination) per row
     casts = []
     if gw_last is not None:
@@ -3539,6 +3596,14 @@ def _tail_grads(layers, gw_last=None):
              _ptr_array(gws + [None] * n), _ptr_array(gbfs + [c[1] for c in extra]), _ptr_array(gbs + [c[2] for c in extra]),
              stream_ptr())
 
+    first_out = None
+    if S_deep > 0:
+        ride_casts = casts if casts and layers[-1][4] == torch.bfloat16 and len(deep) + len(casts) <= 8 else []
+        first_out, *rest = _wgrad_deep(deep, S_deep, ride_casts)
+        if ride_casts:
+            casts = []
+        for k, gwb in zip(batch, rest):
+            out[k] = gwb
     if S > 0:
         dev, dtype, rows = jobs[0][0].device, layers[batch[0]][4], jobs[0][0].shape[0]
         parts = [torch.empty(S, M, N, dtype=torch.float32, device=dev) for _, _, M, N in jobs]
@@ -3567,7 +3632,7 @@ def _tail_grads(layers, gw_last=None):
     for k, t in enumerate(layers):
         if out[k] is None:
             out[k] = _tail_layer_grads(*t)
-    return out
+    return out if first is None else out + [first_out]
 
 
 WGRAD_ROWS = os.environ.get("TRS_WGRAD_ROWS", "1") not in ("", "0")

@@ -793,13 +793,16 @@ def _wide_wgrad_splits(g2, xin, out_f, in_f) -> int:
     return F_.size_query("trs_wgrad_wide_splits", in_f, out_f, g2.stride(0), xin.shape[0])
 
 
-def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b):
+def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b, done=None):
     """Gradients of y = xin @ W^T + b from g2 = dL/dy (rows, padded width; ``gbf``: its fp32 column sums when a fused
-    ReLU-backward already produced them): (dL/dxin, dL/dW, dL/db), None where not needed."""
+    ReLU-backward already produced them): (dL/dxin, dL/dW, dL/db), None where not needed.  ``done``: (dL/dW, dL/db) where
+    the caller already has them (the deep branch's merged weight-gradient launch): only the input gradient is left."""
     rows = xin.shape[0]
     gw_out = gb_out = None
     S = _split_count(rows, _LinearSplitK.SPLIT_ROWS)
-    if need_w or (need_b and gbf is not None):
+    if done is not None:
+        gw_out, gb_out = done
+    elif need_w or (need_b and gbf is not None):
         Sw = _wide_wgrad_splits(g2, xin, out_f, in_f) if need_w else 0
         if Sw:
             # wide input on the project's own kernel: x^T g over Sw row slices, the live columns of g only
@@ -910,10 +913,14 @@ class _HybridMLP(torch.autograd.Function):
             gy2 = F_.pad_cols(gy, widths[L]) if gy.shape[1] != widths[L] else gy.contiguous()
             g1, gz, gb, gb1 = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam)
         grads = []
-        for gw, gbias in F_._tail_grads([(gy2 if l == L - 1 else gz[l], h1 if l == 0 else hidden[l - 1], *wshapes[l],
-                                          wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]) for l in range(L)], gw_last):
+        # the first layer rides in the tail's weight-gradient launch where the library takes all of them as one product
+        *tail, done = F_._tail_grads([(gy2 if l == L - 1 else gz[l], h1 if l == 0 else hidden[l - 1], *wshapes[l],
+                                       wdt[l], gb[l], needs[6 + 4 * l], needs[7 + 4 * l]) for l in range(L)], gw_last,
+                                     first=(g1, cur, w1shape[0], w1shape[1], w1dt, gb1, needs[2], needs[3]))
+        for gw, gbias in tail:
             grads += [gw, gbias, None, None]
-        gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3])
+        gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3],
+                                             done)
         return (gx.reshape(xshape) if needs[0] else None, None, gw1, gbias1, None, None, *grads)
 
 
