@@ -373,6 +373,53 @@ int trs_bag_weight_grad_ragged(const void* g, const void* table, int64_t V, int3
                                int32_t ids_dtype, int64_t n, const int32_t* bag_of, int64_t exclude_row, void* dw,
                                trs_stream_t stream);
 
+/* ---- ragged bag pooling over F fields of one table (the "keyed jagged" layout) -----------------------------------------
+ * One table of V = sum(field sizes) rows; field_offsets (F + 1,) int64 ON THE DEVICE is the exclusive prefix sum of the
+ * field sizes: field f owns the rows [field_offsets[f], field_offsets[f + 1]).  values (n,) int64/int32 RAW per-field ids;
+ * offsets (n_off,) int64/int32 with n_off = F*B + 1, FIELD-MAJOR: bag j = f*B + b is the positions
+ * [offsets[j], offsets[j + 1]); positions behind offsets[F*B] belong to no bag.  w = weights (n,) of the table's dtype or
+ * NULL (= 1), cnt = the bag's length:
+ *   out[b, f, :] = pool over bag f*B + b of w[p] * table[values[p] + field_offsets[f], :]
+ * out (B, F, E) of the table's dtype, sample-major and contiguous: bag j is OUT ROW b*F + f.  mode 0 (sum), 1 (mean over
+ * the bag's own length, an empty bag a zero row; inv_cnt (B*F,) fp32 = 1/cnt, 0 when empty, always written and required),
+ * 2 (max, the first position winning a tie, the rule of trs_bag_pool_fwd; argmax (B*F, E) int32 = the FLAT position of the
+ * winner, -1 for an empty bag).  argmax and inv_cnt are indexed by OUT ROW, as out is.  fp32 accumulation in list order,
+ * one rounding on store: the walk, the two tiers (a bag of more than trs_bag_ragged_long_len() ids is queued in
+ * `workspace`, trs_bag_fields_workspace_bytes(F*B) bytes, and reduced by one wave), the streaming loads above 512 MiB and
+ * the any-E path of trs_bag_pool_ragged_fwd, so a bag's result is bit-equal to that entry's on the field's table slice.
+ * An id is checked against ITS OWN field: values[p] < 0 or >= the field's size reads as a zero row, raises *err_flag and
+ * counts in cnt; it never reads another field's row.  A field that does not lie inside [0, V) (bad field_offsets) has size
+ * 0.  Offsets are range-checked on the device as trs_bag_pool_ragged_fwd does: clamped to [0, n]; an offset outside it or
+ * a decreasing pair (that bag is empty) raises *err_flag.  There is no padding id and no excluded row.
+ * B == 0: TRS_OK, nothing touched.  n == 0 with B > 0: B*F zero rows (values may be NULL).
+ * TRS_EINVAL: NULL table / offsets / out / workspace / field_offsets (values: unless n == 0), F < 1, bad size, n_off not
+ * F*B + 1, weights with mode != 0, mode 2 without argmax, mode 1 without inv_cnt; TRS_ESHAPE: n or F*B >= 2^31 - 1;
+ * TRS_EDTYPE: dtype / val_dtype / off_dtype; TRS_EWORKSPACE: ws_bytes below the query.  All before any launch.
+ * replaces F calls of F.embedding_bag(values_f, table_f, offsets_f, ..., include_last_offset=True) and the cat.       */
+size_t trs_bag_fields_workspace_bytes(int64_t FB);
+int trs_bag_pool_fields_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* values, int32_t val_dtype,
+                            int64_t n, const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int32_t F,
+                            const int64_t* field_offsets, int32_t mode, const void* weights, void* out, int32_t* argmax,
+                            float* inv_cnt, void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
+/* Lookup -> out row and table row map of the F-field bags, for the gradients.  With j = the owner of position p among the
+ * F*B bags by the rule of trs_bag_owner (the last j with offsets[j] <= p, provided p < offsets[j + 1]), f = j / B,
+ * b = j - f*B:
+ *   out_row_of[p] (n,) int32 = b*F + f,                        -1 where no bag holds p
+ *   rows[p]       (n,) int64 = values[p] + field_offsets[f],   -1 where no bag holds p or the id lies outside its field
+ * (V = the table's rows: a field that does not lie inside [0, V) has size 0, as in the forward)
+ * so that trs_csr_build on rows viewed as (n, 1), trs_scatter_rows_ragged (bag_of = out_row_of, B := B*F, g (B*F, E)) and
+ * trs_bag_weight_grad_ragged (ids = rows, exclude_row = -1) are the gradients of trs_bag_pool_fields_fwd.  One thread per
+ * position, a binary search over the offsets; a pure function of its inputs, no atomics.  n == 0: TRS_OK.
+ * Specified for offsets that do not decrease.  Where they do, every out_row_of entry is still an out row in [0, B*F) or
+ * -1 and every rows entry a row of the owner's field or -1, but the owner need not be the bag whose clamped range the
+ * forward walked.
+ * TRS_EINVAL: NULL pointer, F < 1, bad size, n_off not F*B + 1; TRS_ESHAPE: n or F*B >= 2^31 - 1; TRS_EDTYPE: val_dtype /
+ * off_dtype.                                                                                                            */
+int trs_bag_owner_fields(const void* values, int32_t val_dtype, int64_t n, const void* offsets, int32_t off_dtype,
+                         int64_t n_off, int64_t B, int32_t F, int64_t V, const int64_t* field_offsets,
+                         int32_t* out_row_of, int64_t* rows, trs_stream_t stream);
+
 /* ---- K2: FM layer on a materialised block -------------------------------------------------
  * fwd: fm[b,:] = 0.5*((sum_n x)^2 - sum_n x^2), fm_sum[b,:] = sum_n x (fp32, optional)
  * bwd: dx[b,n,:] = g[b,:] * (fm_sum[b,:] - x[b,n,:])

@@ -29,7 +29,10 @@ partial-sum path against the rows path (own inputs, see bench_bagshard).
 the same bags padded to the longest and against F.embedding_bag with offsets (own inputs, see bench_ragged).
 --what raggedattn [--shape fixed,uniform,longtail]: attention pooling of ragged bags (max_length 50, H = 1 and 4) against
 ListIndicesEmbedding(use_attn=True) on the same bags padded to 50 and against the ATen composition with a key_padding_mask;
-then the two ragged kernels alone (own inputs, see bench_raggedattn)."""
+then the two ragged kernels alone (own inputs, see bench_raggedattn).
+--what raggedfields [--fields 4] [--modes sum,mean,max]: RaggedMultiListIndicesEmbedding -- F ragged fields of one table in
+one pass -- against F RaggedListIndicesEmbedding calls plus the cat, and against bag_pool_ragged on pre-offset ids plus the
+permute to (B, F, E) (own inputs, see bench_raggedfields)."""
 import argparse
 import os
 import sys
@@ -258,6 +261,97 @@ def bench_ragged(a):
                           f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us{extra}", flush=True)
             w.grad = None
         del padded, ids
+
+
+def bench_raggedfields(a):
+    """F multi-valued fields over one table of V rows in all (csrc/bag_fields.hip) at B samples, E: forward and
+    forward+backward (maps and row buckets rebuilt every step, as in training) of RaggedMultiListIndicesEmbedding,
+    alternating in this process with two baselines on the same bags:
+      (a) F RaggedListIndicesEmbedding(include_last_offset=True) modules, one per field on a table of the field's size, their
+          (B, 1, E) results joined by torch.cat -- what a model does without the new module;
+      (b) ONE bag_pool_ragged over all F * B bags on ids that already carry their field's row offset, then the permute of
+          the field-major (F, B, E) result to a contiguous (B, F, E) -- one pass, but the copy stays.
+    (a) against the module shows the launches and the copy together, (b) against the module the copy alone.  Bag lengths
+    per field are the ``longtail`` of --what ragged scaled to the field (most bags under 10 ids, 300 / F bags of
+    2000..6000); field sizes are V / F each.  Every figure is the median of ``--rounds`` per-round medians with their
+    min..max; the candidates take turns inside a round."""
+    from torecsys_amd.inputs import RaggedListIndicesEmbedding, RaggedMultiListIndicesEmbedding
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    dev = torch.device("cuda:0")
+    B, E, NF = a.B, a.E, a.fields
+    size = a.V // NF
+    g = torch.Generator(device=dev).manual_seed(9876)
+    ln = torch.randint(0, 10, (NF, B), generator=g, device=dev)
+    hot_n = max(1, 300 // NF)
+    for f in range(NF):
+        hot = torch.randperm(B, generator=g, device=dev)[:hot_n]
+        ln[f, hot] = torch.randint(2000, 6001, (hot_n,), generator=g, device=dev)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), ln.reshape(-1).cumsum(0)])
+    n = int(offsets[-1])
+    values = torch.randint(0, size, (n,), generator=g, device=dev)
+    gout = torch.randn(B, NF, E, generator=g, device=dev, dtype=dt)
+    print(f"ragged fields F={NF} B={B} E={E} V={size * NF} ({size} rows per field) {a.dtype}: n={n} ids, longest bag "
+          f"{int(ln.max())}, {a.rounds} rounds x {a.iters} launches", flush=True)
+    for mode in a.modes.split(","):
+        method = {"sum": "sum", "mean": "avg_pooling", "max": "max_pooling"}[mode]
+        multi = RaggedMultiListIndicesEmbedding(E, [size] * NF, output_method=method).to(dev).to(dt)
+        w = multi.embedding.weight
+        singles, parts = [], []
+        for f in range(NF):
+            m = RaggedListIndicesEmbedding(embed_size=E, field_size=size, padding_idx=None, output_method=method,
+                                           include_last_offset=True).to(dev).to(dt)
+            with torch.no_grad():
+                m.embedding.weight.copy_(w[f * size:(f + 1) * size])
+            beg, end = int(offsets[f * B]), int(offsets[(f + 1) * B])
+            singles.append(m)
+            parts.append((values[beg:end].contiguous(), (offsets[f * B:(f + 1) * B + 1] - beg).contiguous()))
+        field_of = torch.repeat_interleave(torch.arange(NF, device=dev), ln.sum(1))
+        shifted = values + field_of * size                                    # ids with their field's row offset
+
+        def one_pass():
+            return multi(values, offsets).rename(None)
+
+        def per_field():
+            return torch.cat([m(v, o).rename(None) for m, (v, o) in zip(singles, parts)], dim=1)
+
+        def pre_offset():
+            y = F_.bag_pool_ragged(w, shifted, offsets, mode, include_last_offset=True)      # (F*B, 1, E), field-major
+            return y.view(NF, B, E).permute(1, 0, 2).contiguous()
+
+        with torch.no_grad():
+            ref = one_pass()
+            assert torch.equal(ref, per_field()) and torch.equal(ref, pre_offset()), "the candidates disagree"
+        params = [w] + [m.embedding.weight for m in singles]
+
+        def fwd_bwd(f):
+            def run():
+                F_.clear_caches()          # maps and row buckets are rebuilt every step, as in training
+                for p in params:
+                    p.grad = None
+                f().backward(gout)
+            return run
+
+        cands = [("fields module (HIP, one pass)", one_pass), (f"(a) {NF} ragged modules + cat", per_field),
+                 ("(b) pre-offset ids + permute", pre_offset)]
+        res = {}
+        for what in ("fwd", "fwd+bwd"):
+            per = {name: [] for name, _ in cands}
+            for _ in range(a.rounds):
+                for name, f in cands:
+                    if what == "fwd":
+                        with torch.no_grad():
+                            per[name].append(timeit(f, iters=a.iters, warm=2)[0])
+                    else:
+                        per[name].append(timeit(fwd_bwd(f), iters=a.iters, warm=2)[0])
+            for name, ts in per.items():
+                ts = sorted(ts)
+                res[name] = ts[len(ts) // 2]
+                print(f"F={NF:<3d} {mode:5s} {what:8s} {name:30s} med {ts[len(ts) // 2] * 1e6:9.1f} us  spread "
+                      f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us", flush=True)
+            print(f"F={NF:<3d} {mode:5s} {what:8s} (a) / module = {res[cands[1][0]] / res[cands[0][0]]:.2f}x, "
+                  f"(b) / module = {res[cands[2][0]] / res[cands[0][0]]:.2f}x", flush=True)
+        for p in params:
+            p.grad = None
 
 
 def bench_attn(a):
@@ -1239,10 +1333,13 @@ def main():
     ap.add_argument("--layers", type=int, default=2, help="prm: encoder layers of the model")
     ap.add_argument("--world", type=int, default=8, help="bagshard: the world size whose rank 0 this process plays")
     ap.add_argument("--shape", default="fixed,uniform,longtail", help="ragged: bag-length distributions to run")
-    ap.add_argument("--modes", default="sum,mean,max", help="ragged: pooling modes to run")
+    ap.add_argument("--modes", default="sum,mean,max", help="ragged / raggedfields: pooling modes to run")
+    ap.add_argument("--fields", type=int, default=4, help="raggedfields: the number of multi-valued fields F")
     a = ap.parse_args()
     if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"
         return bench_ragged(a)
+    if a.what == "raggedfields":  # own inputs and modules: not part of "all"
+        return bench_raggedfields(a)
     if a.what == "raggedattn":   # own inputs and modules: not part of "all"
         return bench_raggedattn(a)
     if a.what == "bagshard":     # own inputs and modules: not part of "all"

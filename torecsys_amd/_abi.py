@@ -122,6 +122,10 @@ SIGNATURES = {
     "trs_scatter_ragged_workspace_bytes": (_SZ, [_I64, _I32]),
     "trs_scatter_rows_ragged": (c_int32, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, _I64, _P, _P, _SZ, _P]),
     "trs_bag_weight_grad_ragged": (c_int32, [_P, _P, _I64, _I32, _I32, _P, _I32, _I64, _P, _I64, _P, _P]),
+    "trs_bag_fields_workspace_bytes": (_SZ, [_I64]),
+    "trs_bag_pool_fields_fwd": (c_int32, [_P, _I64, _I32, _I32, _P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _P, _I32, _P, _P,
+                                          _P, _P, _P, _SZ, _P, _P]),
+    "trs_bag_owner_fields": (c_int32, [_P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _I64, _P, _P, _P, _P]),
     "trs_attn_pool_path": (c_int32, [_I32, _I32, _I32, _I32]),
     "trs_attn_pool_blocks": (c_int32, [_I64, _I32, _I32, _I32, _I32, _I32]),
     "trs_attn_pool_bwd_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),

@@ -274,6 +274,7 @@ _clear_hooks: List = []        # other per-batch caches keyed by index-tensor id
 
 def clear_caches():
     _bucket_cache.clear()
+    _fields_map_cache.clear()
     for hook in _clear_hooks:
         hook()
 
@@ -867,6 +868,168 @@ def bag_pool_ragged(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Tens
             raise ValueError(f"bag_pool_ragged: per_sample_weights must be on the table's device {weight.device}, "
                              f"got {psw.device}")
     return _BagPoolRagged.apply(weight, ids, offsets, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), B)
+
+
+_fields_map_cache: List[tuple] = []   # [(key, tensors kept alive, (out_row_of, rows))]
+
+
+def _fields_map(values, offsets, field_offsets, B, F, V):
+    """(out_row_of (n,) int32, rows (n,) int64) of trs_bag_owner_fields.  The last two maps are kept, keyed like the row
+    buckets by the identity and version of their inputs (which the cache keeps alive) and by the stream: the same batch
+    looked up again finds the same ``rows`` tensor and therefore the same row buckets, so its table gradient is summed in
+    the same order -- bit for bit -- and the map is not rebuilt."""
+    stream = _abi.current_stream_of(values.device)
+    key = (values.data_ptr(), values._version, values.shape[0], values.dtype, offsets.data_ptr(), offsets._version,
+           offsets.shape[0], offsets.dtype, field_offsets.data_ptr(), field_offsets._version, B, F, V, stream)
+    for k, _, m in _fields_map_cache:
+        if k == key:
+            return m
+    n = values.shape[0]
+    out_row_of = torch.empty(n, dtype=torch.int32, device=values.device)
+    rows = torch.empty(n, dtype=torch.int64, device=values.device)
+    call("trs_bag_owner_fields", ptr(values), index_dtype_code(values), n, ptr(offsets), index_dtype_code(offsets),
+         offsets.shape[0], B, F, V, ptr(field_offsets), ptr(out_row_of), ptr(rows), stream_ptr())
+    _fields_map_cache.append((key, (values, offsets, field_offsets), (out_row_of, rows)))
+    if len(_fields_map_cache) > _BUCKET_CACHE_SIZE:
+        _fields_map_cache.pop(0)
+    return out_row_of, rows
+
+
+class _BagPoolFields(Function):
+    """bag_pool_ragged over the bags of F fields of one table (trs_bag_pool_fields_fwd): one forward pass writes the
+    (B, F, E) block.  The map of every position to its out row and table row (trs_bag_owner_fields) is built in the
+    FORWARD when a gradient will need it, so the row buckets of the table rows can start on the side stream there; the
+    gradients are the walks of _BagPoolRagged on that map.  Nothing here reads a tensor back."""
+
+    @staticmethod
+    def forward(ctx, weight, values, offsets, field_offsets, psw, mode, B, F):
+        require_device(weight, values, offsets, field_offsets, psw)
+        n = values.shape[0]
+        V, E = weight.shape
+        w = weight.contiguous()
+        wts = psw.contiguous() if psw is not None else None
+        dev = w.device
+        FB = F * B
+        out = torch.empty(FB, E, dtype=w.dtype, device=dev)
+        amax = torch.empty(FB, E, dtype=torch.int32, device=dev) if mode == 2 else None      # flat winner positions
+        inv_cnt = torch.empty(FB, dtype=torch.float32, device=dev) if mode == 1 else None
+        ws_bytes = size_query("trs_bag_fields_workspace_bytes", FB)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        flag = _ErrFlag(dev)
+        call("trs_bag_pool_fields_fwd", ptr(w), V, E, value_dtype_code(w), ptr(values), index_dtype_code(values), n,
+             ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, F, ptr(field_offsets), mode, ptr(wts), ptr(out),
+             ptr(amax), ptr(inv_cnt), ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+        flag.check("bag_pool_fields")
+        need_dw = wts is not None and ctx.needs_input_grad[4]
+        out_row_of = rows = None
+        if (ctx.needs_input_grad[0] or need_dw) and n > 0 and B > 0:      # a frozen table without weights: no map
+            out_row_of, rows = _fields_map(values, offsets, field_offsets, B, F, V)
+            if ctx.needs_input_grad[0]:
+                # rows holds -1 where no bag holds the position or the id lies outside its field (flagged by the forward):
+                # the build leaves them out, and must not flag the positions behind the last bag
+                prefetch_row_buckets(rows.view(n, 1), None, V, check=False)
+        ctx.has = (wts is not None, amax is not None, inv_cnt is not None, rows is not None)
+        ctx.save_for_backward(weight, *[t for t in (wts, amax, inv_cnt) if t is not None],
+                              *([out_row_of, rows] if rows is not None else []))
+        ctx.mode, ctx.B, ctx.F, ctx.n = mode, B, F, n
+        return out.view(B, F, E)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        weight = ctx.saved_tensors[0]
+        rest = list(ctx.saved_tensors[1:])
+        wts, amax, inv_cnt, out_row_of = (rest.pop(0) if h else None for h in ctx.has)
+        rows = rest.pop(0) if ctx.has[3] else None
+        _adopt_grads(g)
+        V, E = weight.shape
+        n, FB = ctx.n, ctx.F * ctx.B
+        dev = weight.device
+        grad = dw = None
+        need_dw = wts is not None and ctx.needs_input_grad[4]
+        if not (ctx.needs_input_grad[0] or need_dw):
+            return None, None, None, None, None, None, None, None
+        if rows is None:      # n == 0 or B == 0: no lookup belongs to a bag
+            if ctx.needs_input_grad[0]:
+                grad = torch.zeros(V, E, dtype=weight.dtype, device=dev)
+            if need_dw:
+                dw = torch.zeros(n, dtype=wts.dtype, device=dev)
+            return grad, None, None, None, dw, None, None, None
+        g2 = g.reshape(FB, E)
+        # mean: times 1 / cnt in fp32, rounded once to the table's dtype, on (B*F, E) -- as _BagPoolRagged does
+        g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
+        if need_dw:
+            dw = torch.empty(n, dtype=wts.dtype, device=dev)
+            call("trs_bag_weight_grad_ragged", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(rows),
+                 index_dtype_code(rows), n, ptr(out_row_of), -1, ptr(dw), stream_ptr())
+        if ctx.needs_input_grad[0]:
+            rb = row_buckets(rows.view(n, 1), None, V, check=False)
+            grad = torch.empty(V, E, dtype=weight.dtype, device=dev)
+            ws_bytes = size_query("trs_scatter_ragged_workspace_bytes", n, E)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            call("trs_scatter_rows_ragged", ptr(g2), ptr(out_row_of), ptr(wts), ptr(amax), ptr(rb.row_start), ptr(rb.perm),
+                 n, FB, V, E, value_dtype_code(weight), -1, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+        return grad, None, None, None, dw, None, None, None
+
+
+def bag_pool_fields(weight: torch.Tensor, values: torch.Tensor, offsets: torch.Tensor, field_offsets: torch.Tensor,
+                    mode: str = "mean", *, per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,F,E) pooled rows of the RAGGED bags of F multi-valued fields that share one table, in one pass: the "keyed
+    jagged" layout of feature pipelines.  ``field_offsets`` (F+1,) int64, on the table's device, is the exclusive prefix
+    sum of the field sizes: field f owns the table rows [field_offsets[f], field_offsets[f+1]).  ``values`` (n,) or (n,1)
+    holds RAW per-field ids; ``offsets`` (F*B + 1,) int64 / int32 is FIELD-MAJOR: bag j = f*B + b is
+    values[offsets[j]:offsets[j+1]], the last entry closes the last bag and values behind it belong to no bag.
+    out[b,f] = ``sum`` / ``mean`` (over the bag's own length; an empty bag is a zero row) / ``max`` (first position wins a
+    tie) of table[values[p] + field_offsets[f]] -- what F calls of ``bag_pool_ragged`` on the fields' table slices and a
+    ``cat`` give, bit for bit, without the F passes and the copy.  ``per_sample_weights`` (n,), of the table's dtype,
+    ``sum`` only; it may require grad.
+
+    An id is checked against its own field: one outside [0, field size) reads as a zero row, raises the index flag
+    (``index_errors_seen()``; IndexError with TRS_CHECK_INDICES=1), counts in the mean's divisor and gets no gradient --
+    it never reads a neighbouring field's row.  Offsets are checked on the device as ``bag_pool_ragged`` checks them.
+    There is no padding id, and a fused sparse optimizer is not served."""
+    if mode not in BAG_MODES:
+        raise ValueError(f'bag_pool_fields: mode must be one of {sorted(BAG_MODES)}, got {mode!r}')
+    values = _as_index(values)
+    if values.dim() == 2 and values.shape[1] == 1:
+        values = values.reshape(-1)
+    if values.dim() != 1:
+        raise ValueError(f"values must be (n,) or (n, 1), got shape {tuple(values.shape)}")
+    offsets = _as_index(offsets)
+    if offsets.dim() != 1:
+        raise ValueError(f"offsets must be one-dimensional, got shape {tuple(offsets.shape)}")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
+    fo = field_offsets.rename(None) if field_offsets.has_names() else field_offsets
+    if fo.dim() != 1 or fo.shape[0] < 2 or fo.dtype != torch.int64:
+        raise ValueError(f"bag_pool_fields: field_offsets must be (F + 1,) int64 with F >= 1, got {tuple(fo.shape)} "
+                         f"{fo.dtype}")
+    if fo.device != weight.device:
+        raise ValueError(f"bag_pool_fields: field_offsets must be on the table's device {weight.device}, got {fo.device}")
+    F = fo.shape[0] - 1
+    if offsets.shape[0] < 1 or (offsets.shape[0] - 1) % F != 0:
+        raise ValueError(f"bag_pool_fields: {offsets.shape[0]} offsets for {F} fields, must be F*B + 1 (field-major, the "
+                         f"last one closes the last bag)")
+    B = (offsets.shape[0] - 1) // F
+    if values.shape[0] >= 2 ** 31 - 1 or F * B >= 2 ** 31 - 1:
+        raise ValueError(f"bag_pool_fields: {values.shape[0]} values and {F * B} bags, both must be below 2^31 - 1")
+    psw = per_sample_weights
+    if psw is not None:
+        if mode != "sum":
+            raise ValueError(f"bag_pool_fields: per_sample_weights is only supported for mode='sum', got {mode!r}")
+        psw = psw.rename(None) if psw.has_names() else psw
+        if psw.dim() == 2 and psw.shape[1] == 1:
+            psw = psw.reshape(-1)
+        if tuple(psw.shape) != tuple(values.shape):
+            raise ValueError(f"bag_pool_fields: per_sample_weights must be (n,) = {tuple(values.shape)}, got "
+                             f"{tuple(psw.shape)}")
+        if psw.dtype != weight.dtype:
+            raise ValueError(f"bag_pool_fields: per_sample_weights must have the table's dtype {weight.dtype}, got "
+                             f"{psw.dtype}")
+        if psw.device != weight.device:
+            raise ValueError(f"bag_pool_fields: per_sample_weights must be on the table's device {weight.device}, "
+                             f"got {psw.device}")
+    return _BagPoolFields.apply(weight, values, offsets, fo.contiguous(), psw, BAG_MODES[mode], B, F)
 
 
 # --------------------------------------------------------------------------------------------

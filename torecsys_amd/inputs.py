@@ -436,6 +436,68 @@ class RaggedListIndicesEmbedding(BaseInput):
         return out.refine_names('B', 'N', 'E')
 
 
+class RaggedMultiListIndicesEmbedding(BaseInput):
+    """F multi-valued fields (tags, categories, recent items, ..) that share one ``sum(field_sizes) x E`` table, pooled to
+    the (B,F,E) block named ('B','N','E') in ONE HIP pass (``functional.bag_pool_fields``, csrc/bag_fields.hip) -- what
+    ``MultiIndicesEmbedding`` is to ``SingleIndexEmbedding``, for ``RaggedListIndicesEmbedding`` (not in the reference).
+    The input is the "keyed jagged" layout of feature pipelines: ``forward(values, offsets, per_sample_weights=None)`` with
+    ``values`` (n,) RAW per-field ids and ``offsets`` (F*B + 1,) FIELD-MAJOR -- bag f*B + b is
+    values[offsets[f*B+b]:offsets[f*B+b+1]], the last entry closes the last bag.  out[b,f] pools field f's bag of sample
+    b over the rows ``values + field offset``; bags of any length, empty ones (a zero row) included; no bag length is read
+    on the host.  An id outside its own field reads as a zero row and raises the index flag
+    (``functional.index_errors_seen()``): it never reads a neighbouring field's row.
+
+    ``output_method``: 'avg_pooling' / 'mean' (over the bag's own length), 'max_pooling', 'sum' (the only one that takes
+    ``per_sample_weights`` (n,)).  ``embedding.weight`` is the only ``state_dict`` key; ``offsets`` -- the (F+1,) prefix
+    sum of the field sizes -- is a non-persistent buffer that follows ``.to()``, as in ``MultiIndicesEmbedding``.
+    ``len(module)`` is F.  Not offered: a padding id, attention, ``output_method='none'``, a fused sparse optimizer
+    (NotImplementedError).  ``set_schema(inputs, offsets='column', weights=None)`` names the columns ``Inputs`` hands
+    over."""
+
+    _POOL = ListIndicesEmbedding._POOL
+
+    def __init__(self, embed_size: Optional[int] = None, field_sizes: Optional[List[int]] = None,
+                 nn_embedding: Optional[nn.Parameter] = None, output_method: Optional[str] = 'avg_pooling'):
+        super().__init__()
+        if field_sizes is None or len(field_sizes) < 1 or any(int(s) < 1 for s in field_sizes):
+            raise ValueError('field_sizes must name at least one field, each of at least one row')
+        if nn_embedding is not None:
+            self.embedding = nn.Embedding.from_pretrained(_strip(nn_embedding))
+            if self.embedding.num_embeddings != sum(field_sizes):
+                raise ValueError(f'nn_embedding has {self.embedding.num_embeddings} rows, field_sizes sum to '
+                                 f'{sum(field_sizes)}')
+        elif embed_size is not None:
+            self.embedding = nn.Embedding(sum(field_sizes), embed_size)
+        else:
+            raise ValueError('missing required arguments')
+        sizes = torch.as_tensor([int(s) for s in field_sizes], dtype=torch.int64)
+        self.register_buffer('offsets', torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(sizes, 0)]),
+                             persistent=False)
+        self.field_sizes = [int(s) for s in field_sizes]
+        self.num_fields = len(self.field_sizes)
+        self.field_size = self.embedding.num_embeddings
+        self.embed_size = self.embedding.embedding_dim
+        self.length = self.num_fields
+        if output_method not in self._POOL:
+            raise ValueError(f'output_method only allows {sorted(self._POOL)}.')
+        self.output_method = output_method
+
+    set_schema = RaggedListIndicesEmbedding.set_schema
+
+    def set_fused_optimizer(self, opt):
+        if opt is not None:
+            raise NotImplementedError('torecsys_amd: ragged bags with a fused sparse optimizer are not implemented (the '
+                                      'fused-update walks find the sample of a lookup by dividing its position by the '
+                                      'list length)')
+        return super().set_fused_optimizer(opt)
+
+    def forward(self, values: torch.Tensor, offsets: torch.Tensor,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        out = F_.bag_pool_fields(self.embedding.weight, _strip(values), _strip(offsets), self.offsets,
+                                 self._POOL[self.output_method], per_sample_weights=per_sample_weights)
+        return out.refine_names('B', 'N', 'E')
+
+
 # TRS_SEQ_RNN=0: SequenceIndicesEmbedding runs the composition (HIP row gather, the module's own nn.LSTM / nn.GRU / nn.RNN
 # on a packed sequence, ATen pooling) instead of the fused kernels, which are the default on the strength of the timing in
 # profiles/seq_rnn_kernels.md (forward + backward 4.4x to 5.5x faster at the workload shape)
@@ -717,7 +779,8 @@ class Inputs(BaseInput):
             # SequenceIndicesEmbedding, which therefore never receives its lengths there); both names are routed here
             if emb_fn.__class__.__name__ in ('SequenceIndicesEmbedding', 'SequenceIndexEmbedding'):
                 args[k].append(inputs[emb_fn.schema.lengths])
-            elif emb_fn.__class__.__name__ == 'RaggedListIndicesEmbedding':      # (n,) ids: their offsets, their weights
+            elif emb_fn.__class__.__name__ in ('RaggedListIndicesEmbedding', 'RaggedMultiListIndicesEmbedding'):
+                # (n,) ids: their offsets, their weights
                 args[k].append(inputs[emb_fn.schema.offsets])
                 args[k].append(None if emb_fn.schema.weights is None else inputs[emb_fn.schema.weights])
             elif getattr(emb_fn.schema, 'weights', None) is not None:      # ListIndicesEmbedding: per_sample_weights
