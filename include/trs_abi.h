@@ -153,13 +153,27 @@ int trs_scatter_rows_first(const void* g_rows, int64_t g_rows_batch_stride, cons
  *                  where the step size passed as lr is already bias-corrected by the caller:
  *                  lr * sqrt(1 - beta2^t) / (1 - beta1^t); state = exp_avg (m), state2 = exp_avg_sq (v)
  *              1 and 2 are exactly the dense torch.optim.SGD / Adagrad step (no momentum / weight decay).
+ *              2 | TRS_OPT_ROWWISE = row-wise Adagrad, ONE accumulator per table row (the flag is valid on 2 only; every
+ *                  other value -- 0, 4, the bare flag, 1 | flag, 3 | flag, any other bit -- is TRS_EINVAL):
+ *                  s[r] += mean_e(g[r,e]^2);  w[r,e] -= lr * g[r,e] / (sqrt(s[r]) + eps)
+ *                  The mean is summed in this order, which is part of the result (fp32, every square and add rounded,
+ *                  no fma): a row is L = E*sizeof/16 lanes of VE = 16/sizeof values (4 fp32, 8 bf16), lane l holding
+ *                  elements l*VE .. l*VE+VE-1; each lane sums its squares left to right; the L partial sums are folded
+ *                  by a butterfly that pairs lanes 1 apart, then 2, .., then L/2 apart; the total is multiplied by 1/E
+ *                  (exact: E is a power of two) and added to s[r].  state is V fp32, indexed by the TABLE row (through
+ *                  row_map in the mapped entry: an entry outside [0, V) moves neither weight nor state); state2 is
+ *                  ignored.  Rows must be 1, 2, 4 .. 64 whole 16-byte vectors behind 16-byte aligned pointers (the walk
+ *                  that puts a row into one lane group); any other width or alignment is TRS_ESHAPE before any launch.
+ *                  For E = 1 the rule is optimizer 2 on a V x 1 state.
  *   lr, lr_dev lr_dev == NULL: the step size is lr, by value.  lr_dev != NULL: it is ONE fp32 in device memory, read by
  *              the kernels when they apply a row, and lr is ignored: a launch captured into a hipGraph then follows a
  *              learning rate written between replays (FusedSparse*.set_lr) and Adam's per-step bias correction
  *              (trs_adam_step_size below) instead of repeating the capture-time value.
  *   beta1, beta2   Adam only, each in [0, 1).
- *   state, state2  V x E fp32; state is needed by optimizers 2 and 3, state2 by 3; NULL otherwise.
+ *   state, state2  V x E fp32 (row-wise Adagrad: state is V fp32); state is needed by optimizers 2 and 3, state2 by 3;
+ *              NULL otherwise.
  * The tail is validated before anything is launched (TRS_EINVAL).                                                    */
+#define TRS_OPT_ROWWISE 16
 int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
                             const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
                             int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,

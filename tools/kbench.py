@@ -32,7 +32,10 @@ ListIndicesEmbedding(use_attn=True) on the same bags padded to 50 and against th
 then the two ragged kernels alone (own inputs, see bench_raggedattn).
 --what raggedfields [--fields 4] [--modes sum,mean,max]: RaggedMultiListIndicesEmbedding -- F ragged fields of one table in
 one pass -- against F RaggedListIndicesEmbedding calls plus the cat, and against bag_pool_ragged on pre-offset ids plus the
-permute to (B, F, E) (own inputs, see bench_raggedfields)."""
+permute to (B, F, E) (own inputs, see bench_raggedfields).
+--what rowwise [--shard-rows N]: the fused optimizer step alone (the update walk) for SGD, Adagrad, row-wise Adagrad and
+Adam through gather_rows and embed_fm, uniform and Zipf indices; with --shard-rows also the mapped owner update (own
+inputs, see bench_rowwise)."""
 import argparse
 import os
 import sys
@@ -765,7 +768,7 @@ def bench_compact(a):
     from torecsys_amd.optim import FusedSparseAdagrad
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     dev = torch.device("cuda:0")
-    K, V, E = a.B * a.N, a.shard_rows, a.E
+    K, V, E = a.B * a.N, a.shard_rows or 125_000_000, a.E
     g = torch.Generator(device=dev).manual_seed(1234)
     u = torch.rand(K, generator=g, device=dev, dtype=torch.float64)
     zipf = ((V ** -0.05 - 1.0) * u + 1.0) ** (1.0 / -0.05)      # Zipf(1.05) ranks: the continuous CDF inverted
@@ -810,6 +813,87 @@ def bench_compact(a):
             ts = sorted(meds[c])
             print(f"    {c:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us   ({ts[0] * 1e6:.1f} .. {ts[-1] * 1e6:.1f})",
                   flush=True)
+
+
+def bench_rowwise(a):
+    """The fused optimizer step alone -- the bucket walk with the step as its sink -- for SGD, Adagrad, row-wise Adagrad
+    and Adam on one (V, E) table: the backward of ``F_.gather_rows(..., opt=)`` (plain walk) and of
+    ``F_.embed_fm(..., opt=)`` with the per-sample FM gradient of the models (the lean fm1 walk).  The forward runs once
+    and the row buckets are built by it, so the timed launch is the update walk.  Uniform and Zipf-like indices; the
+    optimizers take turns inside a round; median of the per-round medians with their min..max.  With ``--shard-rows`` on
+    the command line also the owner side of a row-sharded table of that many rows: compaction, bucket build and the
+    mapped update, as ``--what compact`` times it."""
+    from torecsys_amd.optim import FusedSparseAdagrad, FusedSparseAdam, FusedSparseRowWiseAdagrad, FusedSparseSGD
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    dev = torch.device("cuda:0")
+    B, N, E, V = a.B, a.N, a.E, a.V
+    g = torch.Generator().manual_seed(1234)
+    per = V // N
+    fs = [per] * (N - 1) + [V - per * (N - 1)]
+    off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.tensor(fs), 0)[:-1]]).to(dev)
+    zcols = [((f ** torch.rand(B, 1, generator=g, dtype=torch.float64) - 1).clamp_(0, f - 1)).long() for f in fs]
+    indices = {"uniform": torch.cat([torch.randint(0, f, (B, 1), generator=g) for f in fs], 1).to(dev),
+               "zipf": torch.cat(zcols, 1).to(dev)}
+    ge = (torch.randn(B, N, E, generator=g) * 1e-2).to(dt).to(dev)
+    gf1 = (torch.randn(B, 1, generator=g) * 1e-2).to(dt).to(dev)
+    makers = [("sgd", lambda: FusedSparseSGD(1e-3)), ("adagrad", lambda: FusedSparseAdagrad(1e-3)),
+              ("rowwise adagrad", lambda: FusedSparseRowWiseAdagrad(1e-3)), ("adam", lambda: FusedSparseAdam(1e-3))]
+    print(f"fused optimizer step alone, B={B} N={N} E={E} {a.dtype}, {V} rows; {a.rounds} rounds x {a.iters} launches",
+          flush=True)
+
+    def table():
+        return (torch.randn(V, E, generator=g) * 0.1).to(dt).to(dev).requires_grad_()
+
+    def show(title, cands):
+        meds = {c: [] for c, _ in cands}
+        for _ in range(a.rounds):
+            for c, fn in cands:
+                meds[c].append(timeit(fn, iters=a.iters, warm=2)[0])
+        print(f"  {title}", flush=True)
+        for c, _ in cands:
+            ts = sorted(meds[c])
+            print(f"    {c:34s} med {ts[len(ts) // 2] * 1e6:9.1f} us   ({ts[0] * 1e6:.1f} .. {ts[-1] * 1e6:.1f})", flush=True)
+
+    for name, idx in indices.items():
+        F_.clear_caches()
+        plain, folded, keep = [], [], []
+        for label, mk in makers:
+            w = table()
+            out = F_.gather_rows(w, idx, off, opt=mk())
+            plain.append((label, lambda out=out: out.backward(ge, retain_graph=True)))
+            w2 = table()
+            emb, fm, _ = F_.embed_fm(w2, idx, off, None, True, opt=mk())
+            folded.append((label, lambda emb=emb, fm=fm: torch.autograd.backward([emb, fm], [ge, gf1.expand(B, E)],
+                                                                                 retain_graph=True)))
+            keep += [w, w2]
+        show(f"{name}: gather_rows backward (plain walk)", plain)
+        show(f"{name}: embed_fm backward (per-sample FM gradient folded in)", folded)
+        del plain, folded, keep
+        torch.cuda.empty_cache()
+
+    if a.shard_rows is None:
+        return
+    K, Vs = B * N, a.shard_rows
+    gd = torch.Generator(device=dev).manual_seed(1234)
+    u = torch.rand(K, generator=gd, device=dev, dtype=torch.float64)
+    zipf = ((Vs ** -0.05 - 1.0) * u + 1.0) ** (1.0 / -0.05)      # Zipf(1.05) ranks: the continuous CDF inverted
+    ids = {"uniform": torch.randint(0, Vs, (K,), generator=gd, device=dev).to(torch.int32),
+           "zipf(1.05)": (zipf.long() - 1).clamp_(0, Vs - 1).to(torch.int32)}
+    shard = torch.zeros(Vs, E, dtype=dt, device=dev)
+    grad = (torch.randn(K, E, generator=gd, device=dev) * 1e-2).to(dt)
+    print(f"owner update of a {Vs}-row shard (compaction, bucket build, mapped update), K={K} ids", flush=True)
+    for name, x in ids.items():
+        cands = []
+        for label, mk in makers:
+            opt = mk()
+
+            def run(opt=opt, x=x):
+                F_.clear_caches()          # the buckets are rebuilt every step, as in training
+                row_map, inv = F_.compact_rows_dense(x)
+                rb = F_.row_buckets(inv.view(-1, 1), None, row_map.numel())
+                F_.scatter_rows_update_mapped(rb, shard, opt, grad, row_map, key=shard)
+            cands.append((label, run))
+        show(f"{name}: {int(torch.unique(x).numel())} distinct rows", cands)
 
 
 def bench_moe(a):
@@ -1326,7 +1410,9 @@ def main():
     ap.add_argument("--routing-iters", type=int, default=3, help="routing: num_iter of the layer")
     ap.add_argument("--R", type=int, default=64, help="routing: routed size")
     ap.add_argument("--caps", type=int, default=8, help="routing: max_num_caps")
-    ap.add_argument("--shard-rows", type=int, default=125_000_000, help="compact: rows of the owner's shard")
+    ap.add_argument("--shard-rows", type=int, default=None,
+                    help="rows of the owner's shard; compact: 125 000 000 when not given; rowwise: the mapped update runs "
+                         "only when given")
     ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"], help="seq: the recurrent cell")
     ap.add_argument("--neg", type=int, default=10, help="rank: sampled negatives per sample")
     ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
@@ -1352,6 +1438,8 @@ def main():
         return bench_routing(a)
     if a.what == "compact":      # own inputs (a 125 M-row table and its Adagrad state): not part of "all"
         return bench_compact(a)
+    if a.what == "rowwise":      # own inputs (one table and state per optimizer): not part of "all"
+        return bench_rowwise(a)
     if a.what == "bag":          # own inputs (a 4 GiB table is generated on the device): not part of "all"
         return bench_bag(a)
     if a.what == "attn":         # own inputs and module: not part of "all"

@@ -458,9 +458,10 @@ __global__ __launch_bounds__(CSR2_THREADS) void csr2_pass_kernel(const int32_t* 
 // dense torch.optim counterparts (no momentum / weight decay): rows nobody looked up have a zero gradient
 // and are not touched, so neither the dense V x E gradient nor a dense optimizer pass over the table exists.
 struct RowSink {
-  int mode;      // 0 write gradient, 1 SGD, 2 Adagrad, 3 Adam (lazy / SparseAdam semantics)
+  int mode;      // 0 write gradient, 1 SGD, 2 Adagrad, 3 Adam (lazy / SparseAdam semantics), 4 row-wise Adagrad
+                 // (4 exists in the vector walk only, as the RW instantiations of its kernels: see sink_vec)
   float lr, eps; // Adam: lr = lr * sqrt(1 - beta2^t) / (1 - beta1^t), computed by the caller
-  float* state;  // Adagrad accumulator / Adam exp_avg (V x E fp32) or null
+  float* state;  // Adagrad accumulator / Adam exp_avg (V x E fp32), row-wise Adagrad accumulator (V fp32), or null
   float beta1 = 0.f, beta2 = 0.f;
   float* state2 = nullptr;  // Adam exp_avg_sq
   // Optional: the bucketed rows are a COMPACT list of distinct table rows (row_map[r] = table row of bucket row r):
@@ -480,11 +481,37 @@ __device__ __forceinline__ int64_t sink_row(const RowSink& k, int64_t r) {
   return (m >= 0 && m < k.map_rows) ? m : -1;
 }
 
-template <typename T>
+// RW (compile time, so that every other instantiation of the walk kernels is the code it was): the row-wise Adagrad sink,
+// RowSink mode 4.  The 2^LOG2L lanes of the group hold the row (vec = table row * L + lane, VE sums each); `vec` and
+// `touched` are uniform over the group, so its lanes arrive here together -- whatever the other groups of the wave do:
+// the butterfly takes xor steps < L only and reads no lane outside the group.
+//   order of the sum of squares (part of the result):  q = acc[0]^2, then q += acc[i]^2 for i = 1 .. VE-1 in each lane
+//   (every square and every add rounded: no fma); the lanes' q folded by group_sum_up<L> (xor 1, 2, .., L/2); times 1/E
+//   (E = L*VE, a power of two: exact); s' = s[row] + that.  Every lane reads s[row], lane 0 of the group writes s'.
+template <typename T, bool RW = false, int LOG2L = 0>
 __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ out, int64_t vec, const float* acc,
                                          bool touched) {
   constexpr int VE = Vec16<T>::VE;
   if (vec < 0) return;
+  if constexpr (RW) {
+    constexpr int L = 1 << LOG2L;
+    if (!touched) return;
+    float w[VE];
+    Vec16<T>::unpack(out[vec], w);
+    const float lr = sink_lr(k);
+    float* st = k.state + (vec >> LOG2L);
+    float q = acc[0] * acc[0];
+#pragma unroll
+    for (int i = 1; i < VE; ++i) q += acc[i] * acc[i];
+    q = group_sum_up<L>(q);
+    const float s2 = *st + q * (1.f / (float)(L * VE));
+    if ((threadIdx.x & (L - 1)) == 0) *st = s2;
+    const float den = sqrtf(s2) + k.eps;
+#pragma unroll
+    for (int i = 0; i < VE; ++i) w[i] -= lr * acc[i] / den;
+    out[vec] = Vec16<T>::pack(w);
+    return;
+  }
   if (k.mode == 0) {
     // dense gradient table: written once, read by the optimizer much later -- stream it past L2 (which the [g*S | g]
     // rows of the FM term want to keep)
@@ -653,7 +680,8 @@ __device__ __forceinline__ void accumulate_bucket(float* acc, float* gsum, const
   }
 }
 
-template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool HAS_F1 = false, bool SCAL = false, int CHF = 2>
+template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool HAS_F1 = false, bool SCAL = false, int CHF = 2,
+          bool RW = false>
 __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm,
@@ -699,7 +727,7 @@ __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
         for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[SCAL ? 0 : k], acc[k]);
       }
     }
-    sink_vec<T>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && r != padding_row);
+    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && r != padding_row);
     if (HAS_F1 && lane_v == 0) grad_first[r] = from_f32<T>(f1);      // dense companion gradient: every row written
   }
 }
@@ -710,7 +738,7 @@ __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
 // of rows in flight; the generic FM kernel needs 92 registers = 5 waves per SIMD and ran 193 us where the plain walk,
 // at 8 waves, takes 105): 32-bit element offsets from uniform bases (BN * L < 2^31 is checked by the host), the sample
 // index by a multiply-shift with a host-computed reciprocal, the table row fetched with the bucket bounds.
-template <typename T, int LOG2L, bool HAS_G>
+template <typename T, int LOG2L, bool HAS_G, bool RW = false>
 __global__ __launch_bounds__(256, 8) void scatter_rows_fm1_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ tg, const T* __restrict__ g1,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int V,
@@ -784,7 +812,7 @@ __global__ __launch_bounds__(256, 8) void scatter_rows_fm1_kernel(
         for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum, acc[k]);
       }
     }
-    sink_vec<T>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && live);
+    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && live);
   }
 }
 
@@ -824,7 +852,7 @@ __global__ __launch_bounds__(256) void scatter_first_long_kernel(const T* __rest
 // rows of 65 ... 300 lookups, for which 7 of its 8 lane-group rounds had nothing to do -- 92 us at the end of the step.)
 // Rows of a single chunk are finished here; otherwise the chunk's partial sums go to scratch[entry][2][E] (fp32)
 // and scatter_long_rows_finish_kernel adds the chunks of the row.
-template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool SCAL = false>
+template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool SCAL = false, bool RW = false>
 __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int N,
@@ -868,7 +896,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
 #pragma unroll
           for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[k], acc[k]);
         }
-        sink_vec<T>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
+        sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
       } else {
         float* sa = scratch + ((size_t)i * 2) * (L * VE) + lane_v * VE;
 #pragma unroll
@@ -878,7 +906,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
   }
 }
 
-template <typename T, int LOG2L, bool HAS_FM>
+template <typename T, int LOG2L, bool HAS_FM, bool RW = false>
 __global__ __launch_bounds__(256) void scatter_long_rows_finish_kernel(
     const float* __restrict__ fm_sum, const uint4* __restrict__ table, const int32_t* __restrict__ row_start,
     uint4* __restrict__ grad, const int32_t* __restrict__ long_rows, const float* __restrict__ scratch, RowSink sink) {
@@ -931,7 +959,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_finish_kernel(
 #pragma unroll
       for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[k], acc[k]);
     }
-    sink_vec<T>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
+    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
   }
 }
 
@@ -1164,9 +1192,10 @@ struct WalkJob {
   float* scratch = nullptr;
   RowSink sink = GRAD_SINK;
   hipStream_t s = nullptr;
+  const char* who = "scatter_rows";      // the entry, for the messages that name it
 };
 
-template <typename T, int LOG2L>
+template <typename T, int LOG2L, bool RW>
 static void scatter_group_launch(const WalkJob& j) {
   const int L = 1 << LOG2L;
   hipStream_t s = j.s;
@@ -1192,10 +1221,10 @@ static void scatter_group_launch(const WalkJob& j) {
   const bool hg = j.g_rows != nullptr, hf = fm != nullptr;
 #define TRS_SC_TAIL(HG, HF, SC)                                                                                 \
   do {                                                                                                          \
-    hipLaunchKernelGGL((scatter_long_rows_kernel<T, LOG2L, HG, HF, SC>), dim3(2048), dim3(256), 0, s,            \
+    hipLaunchKernelGGL((scatter_long_rows_kernel<T, LOG2L, HG, HF, SC, RW>), dim3(2048), dim3(256), 0, s,            \
                        (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
                        j.perm, j.N, j.gbs, (uint4*)j.out, j.long_rows, j.scratch, j.sink, fs);                  \
-    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF>), dim3(64), dim3(256), 0, s, j.fm_sum,    \
+    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF, RW>), dim3(64), dim3(256), 0, s, j.fm_sum,    \
                        (const uint4*)j.table, j.row_start, (uint4*)j.out, j.long_rows, j.scratch, j.sink);      \
   } while (0)
 #define TRS_SC(HG, HF)                                                                                          \
@@ -1206,14 +1235,14 @@ static void scatter_group_launch(const WalkJob& j) {
                          j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs,        \
                          (const T*)j.g_first, (T*)j.grad_first);                                                \
     else                                                                                                        \
-      hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF>), dim3(grid), dim3(256), 0, s,             \
+      hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF, false, false, 2, RW>), dim3(grid), dim3(256), 0, s,             \
                          (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start, \
                          j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);       \
     TRS_SC_TAIL(HG, HF, false);                                                                                 \
   } while (0)
 #define TRS_SCS(HG, CHF_)                                                                                       \
   do {                                                                                                          \
-    hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, true, false, true, CHF_>), dim3(grid), dim3(256), 0, s, \
+    hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, true, false, true, CHF_, RW>), dim3(grid), dim3(256), 0, s, \
                        (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
                        j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);         \
     TRS_SC_TAIL(HG, true, true);                                                                                \
@@ -1223,11 +1252,11 @@ static void scatter_group_launch(const WalkJob& j) {
   if (lean) {
     const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + (unsigned)j.N - 1) / (unsigned)j.N);
     if (hg)
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true, RW>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
                          (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
                          (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     else
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false, RW>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
                          (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
                          (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     if (hg) TRS_SC_TAIL(true, true, true);
@@ -1246,16 +1275,24 @@ static void scatter_group_launch(const WalkJob& j) {
                        j.perm, j.long_rows, (T*)j.grad_first);
 }
 
-template <typename T>
-static int scatter_launch(const WalkJob& j) {
-  const int lg = log2_lanes(j.E * (int)sizeof(T));
+// which walk a job takes: lane groups over rows of 1, 2, 4 .. 64 whole 16-byte vectors behind 16-byte aligned pointers
+// (returns log2 of the vectors per row), the element walk for everything else (returns -1)
+static int walk_lanes(const WalkJob& j, int elem_bytes) {
+  const int lg = log2_lanes(j.E * elem_bytes);
   const bool scal = j.g_fm_cols == 1 && j.E > 1 && j.fm_sum != nullptr;      // g_fm read as scalars: no alignment requirement
   const bool al = aligned16(j.g_rows) && (scal || aligned16(j.g_fm)) && aligned16(j.table) && aligned16(j.out) &&
                   aligned16(j.fm_sum);
-  if (lg >= 0 && al) {
-    dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value>(j); });
+  return al ? lg : -1;
+}
+
+template <typename T>
+static int scatter_launch(const WalkJob& j, int lg /* walk_lanes(j, sizeof(T)): decided once, by scatter_rows_impl */) {
+  if (lg >= 0) {
+    if (j.sink.mode == 4) dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, true>(j); });
+    else dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, false>(j); });
   } else {
-    // the companion table rides only in the 16-byte-vector walk
+    // the companion table and the row-wise sink ride only in the 16-byte-vector walk (sink_elem knows no mode 4)
+    TRS_REQUIRE(j.sink.mode != 4, TRS_ESHAPE, "%s: row-wise Adagrad has no element walk", j.who);
     TRS_REQUIRE(j.g_first == nullptr, TRS_ESHAPE,
                 "scatter_rows_first: rows must be whole 16-byte vectors (E*sizeof %% 16 == 0)");
     hipStream_t s = j.s;
@@ -1456,6 +1493,12 @@ static int scatter_rows_impl(WalkJob j, int64_t BN, int32_t dtype, void* workspa
   TRS_REQUIRE(ws_bytes >= trs_scatter_workspace_bytes(BN, j.N, j.E, dtype), TRS_EWORKSPACE,
               "scatter_rows: workspace %zu < %zu", ws_bytes, trs_scatter_workspace_bytes(BN, j.N, j.E, dtype));
   TRS_REQUIRE(BN % j.N == 0, TRS_EINVAL, "scatter_rows: B*N=%lld not a multiple of N=%d", (long long)BN, j.N);
+  // a row-wise accumulator is advanced by the lanes of ONE lane group: the element walk (a thread per element, the
+  // threads of a row in several waves) has no row-wise form
+  const int lg = walk_lanes(j, dtype_size(dtype));
+  TRS_REQUIRE(j.sink.mode != 4 || lg >= 0, TRS_ESHAPE,
+              "%s: row-wise Adagrad needs rows of 1, 2, 4 .. 64 whole 16-byte vectors behind 16-byte aligned pointers "
+              "(E = %d, %d bytes per value)", j.who, j.E, dtype_size(dtype));
   j.B = BN / j.N;
   j.long_rows = (int32_t*)workspace;
   j.tg = (char*)workspace + long_row_queue_bytes(BN);
@@ -1463,7 +1506,7 @@ static int scatter_rows_impl(WalkJob j, int64_t BN, int32_t dtype, void* workspa
   // the counters of the hot-row queue and (element path) of the split-row queue behind it
   hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, j.s, j.long_rows,
                      j.long_rows + 1 + (BN / LONG_ROW_ELEM + 2));
-  return dtype == TRS_F32 ? scatter_launch<float>(j) : scatter_launch<bf16_t>(j);
+  return dtype == TRS_F32 ? scatter_launch<float>(j, lg) : scatter_launch<bf16_t>(j, lg);
 }
 
 /* see include/trs_abi.h: the dense gradients of an embedding table AND of its first-order (E = 1) companion in one walk */
@@ -1498,8 +1541,16 @@ static int make_sink(const char* who, const void* table, int32_t optimizer, floa
                      float beta1, float beta2, float* state, float* state2, const int32_t* row_map, int64_t map_rows,
                      RowSink* sink) {
   TRS_REQUIRE(table, TRS_EINVAL, "%s: NULL table", who);
-  TRS_REQUIRE(optimizer >= 1 && optimizer <= 3, TRS_EINVAL, "%s: optimizer %d (1 = SGD, 2 = Adagrad, 3 = Adam)", who,
-              optimizer);
+  // kind | flags: the one flag, TRS_OPT_ROWWISE, goes with Adagrad only
+  const bool rowwise = optimizer == (2 | TRS_OPT_ROWWISE);
+  TRS_REQUIRE((optimizer >= 1 && optimizer <= 3) || rowwise, TRS_EINVAL,
+              "%s: optimizer %d (1 = SGD, 2 = Adagrad, 3 = Adam, 2 | TRS_OPT_ROWWISE = row-wise Adagrad)", who, optimizer);
+  if (rowwise) {
+    TRS_REQUIRE(state != nullptr, TRS_EINVAL, "%s: row-wise Adagrad needs the state buffer (V fp32)", who);
+    *sink = RowSink{.mode = 4, .lr = lr, .eps = eps, .state = state, .row_map = row_map, .map_rows = map_rows,
+                    .lr_dev = lr_dev};
+    return TRS_OK;
+  }
   TRS_REQUIRE(optimizer == 1 || state != nullptr, TRS_EINVAL, "%s: optimizer %d needs the state buffer", who, optimizer);
   TRS_REQUIRE(optimizer != 3 || state2 != nullptr, TRS_EINVAL, "%s: Adam needs both moments", who);
   TRS_REQUIRE(optimizer != 3 || (beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f), TRS_EINVAL,
@@ -1523,7 +1574,7 @@ extern "C" int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_
   return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
                                    .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
                                    .N = N, .padding_row = padding_row, .out = table, .sink = sink,
-                                   .s = (hipStream_t)stream},
+                                   .s = (hipStream_t)stream, .who = "scatter_rows_update"},
                            BN, dtype, workspace, ws_bytes);
 }
 
@@ -1540,7 +1591,7 @@ extern "C" int trs_scatter_rows_update_mapped(const void* g_rows, void* table, c
   TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
   if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
   return scatter_rows_impl(WalkJob{.g_rows = g_rows, .table = table, .row_start = row_start, .perm = perm, .V = U, .E = E,
-                                   .N = 1, .out = table, .sink = sink, .s = (hipStream_t)stream},
+                                   .N = 1, .out = table, .sink = sink, .s = (hipStream_t)stream, .who = who},
                            K, dtype, workspace, ws_bytes);
 }
 

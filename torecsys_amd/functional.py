@@ -385,14 +385,19 @@ def _adam_step_dev(opt, table: torch.Tensor, key) -> torch.Tensor:
     return step_size
 
 
-def _sink_args(opt, table: torch.Tensor, key):
+TRS_OPT_ROWWISE = 16      # include/trs_abi.h: flag on optimizer 2, the state is one fp32 per table row
+
+
+def _sink_args(opt, table: torch.Tensor, key, operands=()):
     """The optimizer tail of trs_scatter_rows_update[_mapped] up to ``state2``: (kind, lr, lr_dev, eps, beta1, beta2,
     state, state2).  A ``capturable`` optimizer hands its step size over in device memory (lr_dev; eagerly and under
-    capture alike), any other by value.  For Adam this advances the table's step."""
+    capture alike), any other by value.  For Adam this advances the table's step.  ``operands``: the tensors of the call
+    whose alignment enters the library's choice of walk (what ``_walk_takes_vectors`` takes)."""
     capturable = getattr(opt, "capturable", False)
     lr, lr_dev = float(opt.lr), opt.lr_tensor(table.device) if capturable else None
     beta1 = beta2 = 0.0
     state = state2 = None
+    kind = opt.kind
     if opt.kind == 3:
         if not capturable and torch.cuda.is_current_stream_capturing():
             # the bias-corrected step size lr*sqrt(1-b2^t)/(1-b1^t) is computed on the host per step and passed by
@@ -407,8 +412,20 @@ def _sink_args(opt, table: torch.Tensor, key):
         else:
             lr = float(opt.next_step_size(table, key))
     elif opt.kind == 2:
+        if getattr(opt, "rowwise", False) and table.shape[1] != 1:
+            # one accumulator per row: the lanes of a row must sit in one lane group.  (E == 1, DeepFM's first-order
+            # table, always takes the element walk -- and there the rule is element-wise Adagrad on the (V,) state
+            # seen as (V, 1): plain optimizer 2 below.)
+            if not _walk_takes_vectors(table, table, *operands):
+                raise NotImplementedError(
+                    f"FusedSparseRowWiseAdagrad: a table of rows of {table.shape[1]} x {table.dtype} "
+                    f"({table.shape[1] * table.element_size()} bytes; table and gradient operands 16-byte aligned: "
+                    f"{all(t is None or t.data_ptr() % 16 == 0 for t in (table, *operands))}) takes "
+                    "the element walk, which has no row-wise form: rows must be whole 16-byte vectors, 1..64 of them a "
+                    "power of two, behind 16-byte aligned pointers")
+            kind = 2 | TRS_OPT_ROWWISE
         state = opt.state_for(table, key)
-    return opt.kind, lr, ptr(lr_dev), float(opt.eps), beta1, beta2, ptr(state), ptr(state2)
+    return kind, lr, ptr(lr_dev), float(opt.eps), beta1, beta2, ptr(state), ptr(state2)
 
 
 def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
@@ -422,9 +439,11 @@ def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Option
         raise ValueError("fused optimizer needs a contiguous table")
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, rb.N, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
+    # (a per-sample FM gradient is read as scalars: its own alignment does not matter)
+    scal = g_bcast is not None and _bcast_cols(g_bcast, E) == 1 and E > 1 and fm_sum is not None
     call("trs_scatter_rows_update", ptr(g_rows), g_rows_batch_stride, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
          ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
-         *_sink_args(opt, table, key), ptr(ws), ws_bytes, stream_ptr())
+         *_sink_args(opt, table, key, (g_rows, None if scal else g_bcast, fm_sum)), ptr(ws), ws_bytes, stream_ptr())
 
 
 def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows: torch.Tensor, row_map: torch.Tensor,
@@ -440,9 +459,10 @@ def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows:
         raise ValueError("row_map must be int32 with one entry per bucketed row")
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, 1, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
-    call("trs_scatter_rows_update_mapped", ptr(g_rows.contiguous()), ptr(table), ptr(row_map), ptr(rb.row_start),
-         ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), *_sink_args(opt, table, key), ptr(ws), ws_bytes,
-         stream_ptr())
+    g_rows = g_rows.contiguous()
+    call("trs_scatter_rows_update_mapped", ptr(g_rows), ptr(table), ptr(row_map), ptr(rb.row_start),
+         ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), *_sink_args(opt, table, key, (g_rows,)), ptr(ws),
+         ws_bytes, stream_ptr())
 
 
 def compact_rows(ids: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None

@@ -52,7 +52,7 @@ class BaseInput(nn.Module):
         self.fused_optimizer = None
 
     def set_fused_optimizer(self, opt):
-        """Apply ``opt`` (torecsys_amd.optim.FusedSparseSGD / FusedSparseAdagrad) to this module's table rows inside
+        """Apply ``opt`` (torecsys_amd.optim.FusedSparse{SGD,Adagrad,RowWiseAdagrad,Adam}) to this module's table rows inside
         the backward pass: no dense gradient is produced, ``weight.grad`` stays None.  Returns self."""
         self.fused_optimizer = opt
         return self
