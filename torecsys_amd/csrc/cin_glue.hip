@@ -358,12 +358,13 @@ __global__ __launch_bounds__(GLUE_THREADS) void glue_bwd_apply_cf_kernel(
 }
 
 static int glue_grid(int64_t B) { return (int)std::min<int64_t>(B, 1024); }
-static bool glue_cf_ok(int C, int E) { return C % 8 == 0 && C / 8 <= GLUE_THREADS && E == 8 * (GLUE_THREADS / (C / 8)); }
 static bool glue_shape_ok(int C, int D, int Hs) {
   const int vpr = C / 8;
   return C % 8 == 0 && vpr >= 1 && vpr <= GLUE_THREADS && GLUE_THREADS % vpr == 0 && D % 8 == 0 && Hs % 8 == 0 &&
          D >= 0 && D <= C && Hs >= 0 && Hs <= C;
 }
+// only a C the entries take: C = 24 would pair with E = 8 * (256 / 3) = 680, C < 8 would divide by zero
+static bool glue_cf_ok(int C, int E) { return glue_shape_ok(C, 0, 0) && E == 8 * (GLUE_THREADS / (C / 8)); }
 
 }  // namespace trs
 
@@ -383,7 +384,8 @@ extern "C" int trs_cin_glue_stats(const void* y, int64_t B, int32_t E, int32_t C
   const int D = 0, Hs = 0;
   TRS_GLUE_COMMON("cin_glue_stats");
   if (B == 0) return TRS_OK;
-  TRS_REQUIRE(y && partial && aligned16(y), TRS_EINVAL, "cin_glue_stats: NULL or unaligned pointer");
+  TRS_REQUIRE(y && partial, TRS_EINVAL, "cin_glue_stats: NULL pointer");
+  TRS_REQUIRE(aligned16(y), TRS_EALIGN, "cin_glue_stats: 16-byte alignment");
   hipLaunchKernelGGL(glue_stats_kernel, dim3(glue_grid(B)), dim3(GLUE_THREADS), (size_t)GLUE_THREADS * 8 * 4,
                      (hipStream_t)stream, (const bf16_t*)y, B, E, C, partial);
   return check_launch("cin_glue_stats");
