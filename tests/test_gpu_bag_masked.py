@@ -288,6 +288,28 @@ def test_live_out_of_range_id(dev, E):
     assert F_.index_errors_seen()
 
 
+@pytest.mark.parametrize("E", [16, 10])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_no_padding_present_equals_plain_bag_pool(dev, dtype, E):
+    """One autograd node serves both forward entries (trs_bag_pool_fwd, trs_bag_pool_masked_fwd) and both backward routes.
+    Where no position holds the padding id they coincide: the same terms, so sum and max agree bit for bit, outputs and
+    table gradients.  Integer operands as in the exact tests above: each call builds its own row buckets, and the order of
+    the lookups inside a bucket (positions handed out by atomics) is not the same from build to build, so only sums that
+    are exact in fp32 can be compared with torch.equal.  (Not the mean: 1 / L in the table's dtype against 1 / cnt in
+    fp32, by design.)"""
+    B, L, V, pad = 67, 9, 53, 0
+    g = torch.Generator().manual_seed(23)
+    idx = torch.randint(1, V, (B, L), generator=g)
+    w, _, gout = _exact_operands(g, B, L, V, E)
+    assert int(idx.min()) >= 1
+    for mode in ("sum", "max"):
+        y_m, grad_m, _ = _run(dev, dtype, torch.int64, w, idx, mode, pad, True, None, gout)
+        y_p, grad_p, _ = _run(dev, dtype, torch.int64, w, idx, mode, pad, False, None, gout)
+        assert torch.equal(y_m, y_p), mode
+        assert torch.equal(grad_m, grad_p), mode
+        assert float(grad_p.abs().max()) > 0.0 and float(grad_p[pad].abs().max()) == 0.0, mode
+
+
 # ------------------------------------------------------------------------------------------------ 5. fused optimizer
 @pytest.mark.parametrize("kind", ["sgd", "adagrad"])
 def test_fused_optimizer_masked_mean_equals_dense_step(dev, kind):

@@ -24,7 +24,8 @@ for line in out.splitlines():
         continue
     k, v = m.groups()
     if k == "Function Name":
-        cur = subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip().split("(")[0]
+        # -p: no parameter list (cutting at the first "(" would also cut an enum template argument, "(trs::BagTerm)1")
+        cur = subprocess.run(["c++filt", "-p", v], capture_output=True, text=True).stdout.strip()
         rows[cur] = {}
     elif cur:
         rows[cur][k] = v

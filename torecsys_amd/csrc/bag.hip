@@ -10,10 +10,11 @@
 // first-order term, so CH = 8 stays within 64 registers for the sums (compiler resource report) -- the
 // occupancy that made 4 beat 8 in fm.hip is not lost here.  The max walk keeps CH = 4.
 //
-// Max backward: the bucket walk of scatter.hip with the term of lookup p = (b, l) being g[b, e] where amax[b, e] == l and 0
-// elsewhere.  It reads g (B, E) and amax (B, E), never a (B, Lb, E) block; every table row is written (padding row: zeros);
-// no atomics on values, fixed summation order.  Rows with more than BAG_LONG_ROW lookups are queued and reduced by whole
-// waves in chunks of BAG_LONG_CHUNK, as scatter.hip's hot rows are.
+// Gradient walks (bag_walk_*_kernel): the bucket walk of scatter.hip, the term of a lookup and the way its sample is found
+// chosen at compile time by a BagWalk policy passed by value.  Max backward: the term of lookup p = (b, l) is g[b, e]
+// where amax[b, e] == l and 0 elsewhere.  It reads g (B, E) and amax (B, E), never a (B, Lb, E) block; every table row is
+// written (padding row: zeros); no atomics on values, fixed summation order.  Rows with more than BAG_LONG_ROW lookups are
+// queued and reduced by whole waves in chunks of BAG_LONG_CHUNK, as scatter.hip's hot rows are.
 //
 // Masked / weighted variants (trs_bag_pool_masked_fwd): the same two forward kernels with the compile-time flags MASK (a
 // position that holds the excluded row id issues no table load and takes no part: sum over the live positions, mean over
@@ -21,13 +22,13 @@
 // 0xFFFF in argmax for an empty bag) and WGT (sum only: every term times w[b, l], the weight read once per position).  With
 // both flags off the instantiations are the ones above: no branch is added to them.  Algorithmic bytes per sample =
 // Lb * idx bytes + cnt * E*s (+ Lb * s of weights) read, E*s (+ 4 for inv_cnt, + 2*E for the max positions) written.
-// Weighted backward: the walk of the max backward with the term of lookup p = (b, l) being w[p] * g[b, e] (flag WGT of the
-// same kernels, same queue thresholds BAG_LONG_ROW / BAG_LONG_CHUNK / BAG_LONG_ROW_ELEM), and bag_weight_grad_*_kernel:
+// Weighted backward: the same walk with the term of lookup p = (b, l) being w[p] * g[b, e] (BagTerm::Weighted, same queue
+// thresholds BAG_LONG_ROW / BAG_LONG_CHUNK / BAG_LONG_ROW_ELEM), and bag_weight_grad_*_kernel:
 // dw[b, l] = sum_e g[b, e] * table[idx[b, l], e], one lane group (or one thread) per position, 0 at excluded positions.
 //
-// Ragged bags (forward: bag_ragged.hip): the same walks and the same weight-gradient kernels with the compile-time flag RAG
-// -- the sample of lookup p is read from a map (bag_of[p], trs_bag_owner) where the padded layout divides p by the list
-// length, and the winners of the max are flat int32 positions behind a pointer of their own.  RAG_OFF: the code above.
+// Ragged bags (forward: bag_ragged.hip): the same walks with the mapped layout of the policy -- the sample of lookup p is
+// read from a map (bag_of[p], trs_bag_owner) where the padded layout divides p by the list length, and the winners of the
+// max are flat int32 positions -- and the same weight-gradient kernels with the compile-time flag RAG.
 #include "bag_common.hpp"
 
 namespace trs {
@@ -216,133 +217,146 @@ static int bag_pool_launch(const void* table, const IdxT* idx, int64_t B, int Lb
 }
 
 // ---------------------------------------------------------------------------------------------
-// max backward: bucket walk with the winner mask
+// gradient walks: the bucket walk of scatter.hip, the term of a lookup chosen by a policy
 
-// the lookups q = beg, beg + step, ... < end of one bucket, CH in flight per lane: acc[k] += g[b, k] where amax[b, k] == l
-// (WGT: acc[k] += wts[p] * g[b, k] instead, p = b * N + l the flat position; amax is not read)
-template <typename T, int LOG2L, int CH, bool WGT>
-__device__ __forceinline__ void bag_argmax_bucket(float* acc, const uint4* __restrict__ g,
-                                                  const uint16_t* __restrict__ amax, const T* __restrict__ wts,
-                                                  const int32_t* __restrict__ perm, int beg, int end, int step,
-                                                  unsigned N, int lane_v) {
+// What lookup p adds to the gradient of its table row, g (samples, E) being the gradient of the pooled rows:
+//   Plain     g[b, k]
+//   Weighted  wts[p] * g[b, k]
+//   Winner    g[b, k] where the stored winner of (b, k) is this lookup, else 0
+// and how its sample b is found.  Padded: b = p / N, the winners are the list positions p - b * N, uint16 (B, E).
+// Mapped (ragged bags): b = owner[p] (trs_bag_owner; below zero: no bag holds p, no term), the winners are the flat
+// positions p, int32 (B, E).  Padded x Plain is the walk of scatter.hip and is not offered here.
+enum class BagTerm { Plain, Weighted, Winner };
+struct BagNoOperand {};
+
+template <typename T, BagTerm TERM, bool MAPPED>
+struct BagWalk {
+  static_assert(MAPPED || TERM != BagTerm::Plain, "padded bags with the plain term are served by scatter.hip");
+  using value_type = T;
+  using WinnerT = std::conditional_t<MAPPED, int32_t, uint16_t>;
+  using Operand = std::conditional_t<TERM == BagTerm::Plain, BagNoOperand,
+                                     const std::conditional_t<TERM == BagTerm::Weighted, T, WinnerT>*>;
+  static constexpr int VE = Vec16<T>::VE;
+  // the operand of one lookup in registers (vector path): its weight, or the winners of this lane's VE columns
+  struct Held {
+    float wv;
+    uint4 av[MAPPED ? VE / 4 : 1];
+  };
+
+  const T* g;
+  std::conditional_t<MAPPED, const int32_t*, unsigned> where;      // mapped: owner (n); padded: the list length N
+  [[no_unique_address]] Operand op;                                 // wts (n), or the winners (B, E)
+
+  // of what the vector path loads as 16-byte (padded winners in fp32: 8-byte) vectors
+  bool aligned() const {
+    if constexpr (TERM == BagTerm::Winner) return aligned16(g) && aligned16(op);
+    else return aligned16(g);
+  }
+
+  // p >= 0.  Padded: p < B * N < 2^31, one 32-bit unsigned division, never below zero.  Typed per layout -- the int the map
+  // holds, the zero-extended quotient -- which keeps every kernel's occupancy (profiles/bag_walk_policy.md)
+  using Sample = std::conditional_t<MAPPED, int, int64_t>;
+  __device__ __forceinline__ Sample sample(int p) const {
+    if constexpr (MAPPED) return where[p];
+    else return (int64_t)((unsigned)p / where);
+  }
+
+  // vector path: o = b * L + lane_v is the 16-byte vector of g[b] that this lane owns
+  __device__ __forceinline__ uint4 g_vec(int64_t o) const { return reinterpret_cast<const uint4*>(g)[o]; }
+
+  __device__ __forceinline__ void hold(Held& h, int p, int64_t o) const {
+    if constexpr (TERM == BagTerm::Weighted) {
+      h.wv = to_f32(op[p]);
+    } else if constexpr (TERM == BagTerm::Winner) {
+      if constexpr (MAPPED) {
+        const uint4* ap = reinterpret_cast<const uint4*>(op + o * VE);
+#pragma unroll
+        for (int i = 0; i < VE / 4; ++i) h.av[i] = ap[i];
+      } else if constexpr (VE == 8) {
+        h.av[0] = *reinterpret_cast<const uint4*>(op + o * VE);
+      } else {
+        const uint2 a2 = *reinterpret_cast<const uint2*>(op + o * VE);
+        h.av[0] = make_uint4(a2.x, a2.y, 0, 0);
+      }
+    }
+  }
+
+  // acc[k] += the term of lookup p of sample b, for this lane's VE columns
+  __device__ __forceinline__ void add(float* acc, int p, Sample b, const uint4& gv, const Held& h) const {
+    float x[VE];
+    Vec16<T>::unpack(gv, x);
+    if constexpr (TERM == BagTerm::Plain) {
+#pragma unroll
+      for (int k = 0; k < VE; ++k) acc[k] += x[k];
+    } else if constexpr (TERM == BagTerm::Weighted) {
+#pragma unroll
+      for (int k = 0; k < VE; ++k) acc[k] += h.wv * x[k];
+    } else if constexpr (MAPPED) {
+#pragma unroll
+      for (int i = 0; i < VE / 4; ++i) {
+        const int a[4] = {(int)h.av[i].x, (int)h.av[i].y, (int)h.av[i].z, (int)h.av[i].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[4 * i + j] += a[j] == p ? x[4 * i + j] : 0.f;
+      }
+    } else {
+      const unsigned l = (unsigned)p - (unsigned)b * where;
+      const uint32_t w[4] = {h.av[0].x, h.av[0].y, h.av[0].z, h.av[0].w};
+#pragma unroll
+      for (int k = 0; k < VE; ++k) {
+        const unsigned a = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
+        acc[k] += a == l ? x[k] : 0.f;
+      }
+    }
+  }
+
+  // element path (any E): the term of lookup p for column e
+  __device__ __forceinline__ float term(int p, int E, int e) const {
+    const Sample b = sample(p);
+    if (MAPPED && b < 0) return 0.f;
+    const int64_t o = (int64_t)b * E + e;
+    if constexpr (TERM == BagTerm::Plain) return to_f32(g[o]);
+    else if constexpr (TERM == BagTerm::Weighted) return to_f32(op[p]) * to_f32(g[o]);
+    else if constexpr (MAPPED) return op[o] == p ? to_f32(g[o]) : 0.f;
+    else return (unsigned)op[o] == (unsigned)p - (unsigned)b * where ? to_f32(g[o]) : 0.f;
+  }
+};
+
+// the lookups q = beg, beg + step, ... < end of one bucket, CH in flight per lane: perm, then the sample (mapped: a load),
+// then g and the term's operand, then the sum in bucket order
+template <typename W, int LOG2L, int CH>
+__device__ __forceinline__ void bag_walk_bucket(float* acc, const W& w, const int32_t* __restrict__ perm, int beg,
+                                                int end, int step, int lane_v) {
   constexpr int L = 1 << LOG2L;
-  constexpr int VE = Vec16<T>::VE;
   for (int q = beg; q < end; q += CH * step) {
     int p[CH];
-    uint4 gv[CH], av[CH];
-    float wv[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) p[c] = (q + c * step) < end ? perm[q + c * step] : -1;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      gv[c] = make_uint4(0, 0, 0, 0);
-      av[c] = make_uint4(0, 0, 0, 0);
-      wv[c] = 0.f;
-      if (p[c] >= 0) {
-        const int64_t b = (int64_t)((unsigned)p[c] / N);
-        gv[c] = g[b * L + lane_v];
-        if (WGT) {
-          wv[c] = to_f32(wts[p[c]]);
-        } else {
-          const uint16_t* ap = amax + (b * L + lane_v) * VE;
-          if (VE == 8) {
-            av[c] = *reinterpret_cast<const uint4*>(ap);
-          } else {
-            const uint2 a2 = *reinterpret_cast<const uint2*>(ap);
-            av[c] = make_uint4(a2.x, a2.y, 0, 0);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      if (p[c] >= 0) {
-        const unsigned b = (unsigned)p[c] / N;
-        const unsigned l = (unsigned)p[c] - b * N;
-        float x[VE];
-        Vec16<T>::unpack(gv[c], x);
-        const uint32_t w[4] = {av[c].x, av[c].y, av[c].z, av[c].w};
-#pragma unroll
-        for (int k = 0; k < VE; ++k) {
-          if (WGT) {
-            acc[k] += wv[c] * x[k];
-          } else {
-            const unsigned a = (k & 1) ? (w[k >> 1] >> 16) : (w[k >> 1] & 0xffffu);
-            acc[k] += a == l ? x[k] : 0.f;
-          }
-        }
-      }
-    }
-  }
-}
-
-// Ragged bags (RAG != 0 in the kernels below): the sample of lookup p is bag_of[p] (trs_bag_owner; < 0: no bag holds p,
-// no term) where the padded layout divides, and the winners are FLAT positions: amax32 (B, E) int32, amax32[b, k] == p.
-// RAG names the term at compile time -- RAG_PLAIN: g[b, k]; RAG_WGT: wts[p] * g[b, k]; RAG_MAX: the winner mask.
-constexpr int RAG_OFF = 0, RAG_PLAIN = 1, RAG_WGT = 2, RAG_MAX = 3;
-
-template <typename T, int LOG2L, int CH, int RAG>
-__device__ __forceinline__ void bag_ragged_bucket(float* acc, const uint4* __restrict__ g,
-                                                  const int32_t* __restrict__ amax32, const T* __restrict__ wts,
-                                                  const int32_t* __restrict__ bag_of,
-                                                  const int32_t* __restrict__ perm, int beg, int end, int step,
-                                                  int lane_v) {
-  constexpr int L = 1 << LOG2L;
-  constexpr int VE = Vec16<T>::VE;
-  for (int q = beg; q < end; q += CH * step) {
-    int p[CH], b[CH];
+    typename W::Sample b[CH];
     uint4 gv[CH];
-    int av[CH][VE];                           // RAG_MAX only
-    float wv[CH];                             // RAG_WGT only
+    typename W::Held h[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) p[c] = (q + c * step) < end ? perm[q + c * step] : -1;
 #pragma unroll
-    for (int c = 0; c < CH; ++c) b[c] = p[c] >= 0 ? bag_of[p[c]] : -1;
+    for (int c = 0; c < CH; ++c) b[c] = p[c] >= 0 ? w.sample(p[c]) : -1;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       gv[c] = make_uint4(0, 0, 0, 0);
-      wv[c] = 1.f;
       if (b[c] >= 0) {
-        gv[c] = g[(int64_t)b[c] * L + lane_v];
-        if constexpr (RAG == RAG_WGT) {
-          wv[c] = to_f32(wts[p[c]]);
-        } else if constexpr (RAG == RAG_MAX) {
-          const uint4* ap = reinterpret_cast<const uint4*>(amax32 + ((int64_t)b[c] * L + lane_v) * VE);
-#pragma unroll
-          for (int h = 0; h < VE / 4; ++h) {
-            const uint4 a4 = ap[h];
-            av[c][4 * h] = (int)a4.x; av[c][4 * h + 1] = (int)a4.y;
-            av[c][4 * h + 2] = (int)a4.z; av[c][4 * h + 3] = (int)a4.w;
-          }
-        }
+        gv[c] = w.g_vec((int64_t)b[c] * L + lane_v);
+        w.hold(h[c], p[c], (int64_t)b[c] * L + lane_v);
       }
     }
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      if (b[c] >= 0) {
-        float x[VE];
-        Vec16<T>::unpack(gv[c], x);
-#pragma unroll
-        for (int k = 0; k < VE; ++k) {
-          if constexpr (RAG == RAG_WGT) acc[k] += wv[c] * x[k];
-          else if constexpr (RAG == RAG_MAX) acc[k] += av[c][k] == p[c] ? x[k] : 0.f;
-          else acc[k] += x[k];
-        }
-      }
+      if (b[c] >= 0) w.add(acc, p[c], b[c], gv[c], h[c]);
     }
   }
 }
 
-template <typename T, int LOG2L, bool WGT, int RAG>
-__global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __restrict__ g,
-                                                              const uint16_t* __restrict__ amax,
-                                                              const T* __restrict__ wts,
-                                                              const int32_t* __restrict__ row_start,
-                                                              const int32_t* __restrict__ perm, int64_t V, unsigned N,
-                                                              int64_t padding_row, uint4* __restrict__ grad,
-                                                              int32_t* __restrict__ long_rows /* [0] = count */,
-                                                              const int32_t* __restrict__ bag_of /* RAG only */,
-                                                              const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
+template <typename W, int LOG2L>
+__global__ __launch_bounds__(256) void bag_walk_rows_kernel(W w, const int32_t* __restrict__ row_start,
+                                                            const int32_t* __restrict__ perm, int64_t V,
+                                                            int64_t padding_row, uint4* __restrict__ grad,
+                                                            int32_t* __restrict__ long_rows /* [0] = count */) {
+  using T = typename W::value_type;
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   const int lane_v = threadIdx.x & (L - 1);
@@ -364,10 +378,7 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
         }
         continue;
       }
-      if constexpr (RAG != RAG_OFF)
-        bag_ragged_bucket<T, LOG2L, 4, RAG>(acc, g, amax32, wts, bag_of, perm, beg, end, 1, lane_v);
-      else
-        bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg, end, 1, N, lane_v);
+      bag_walk_bucket<W, LOG2L, 4>(acc, w, perm, beg, end, 1, lane_v);
     }
     store_stream(&grad[r * L + lane_v], Vec16<T>::pack(acc));
   }
@@ -375,17 +386,12 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_kernel(const uint4* __res
 
 // hot rows: one wave per (row, chunk) entry, its 64 / L lane groups stride the chunk, partial sums folded by shuffles.
 // Rows of a single chunk are finished here; otherwise the partial goes to scratch[entry][E] (fp32) for the finish kernel.
-template <typename T, int LOG2L, bool WGT, int RAG>
-__global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __restrict__ g,
-                                                              const uint16_t* __restrict__ amax,
-                                                              const T* __restrict__ wts,
-                                                              const int32_t* __restrict__ row_start,
-                                                              const int32_t* __restrict__ perm, unsigned N,
-                                                              uint4* __restrict__ grad,
-                                                              const int32_t* __restrict__ long_rows,
-                                                              float* __restrict__ scratch,
-                                                              const int32_t* __restrict__ bag_of /* RAG only */,
-                                                              const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
+template <typename W, int LOG2L>
+__global__ __launch_bounds__(256) void bag_walk_long_kernel(W w, const int32_t* __restrict__ row_start,
+                                                            const int32_t* __restrict__ perm, uint4* __restrict__ grad,
+                                                            const int32_t* __restrict__ long_rows,
+                                                            float* __restrict__ scratch) {
+  using T = typename W::value_type;
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   constexpr int G = 64 / L;
@@ -402,10 +408,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __res
     float acc[VE];
 #pragma unroll
     for (int k = 0; k < VE; ++k) acc[k] = 0.f;
-    if constexpr (RAG != RAG_OFF)
-      bag_ragged_bucket<T, LOG2L, 4, RAG>(acc, g, amax32, wts, bag_of, perm, beg + grp, end, G, lane_v);
-    else
-      bag_argmax_bucket<T, LOG2L, 4, WGT>(acc, g, amax, wts, perm, beg + grp, end, G, N, lane_v);
+    bag_walk_bucket<W, LOG2L, 4>(acc, w, perm, beg + grp, end, G, lane_v);
 #pragma unroll
     for (int m = L; m < 64; m <<= 1) {
 #pragma unroll
@@ -425,10 +428,10 @@ __global__ __launch_bounds__(256) void bag_argmax_long_kernel(const uint4* __res
 
 // rows of several chunks: the first chunk's entry adds the row's partials in chunk order
 template <typename T, int LOG2L>
-__global__ __launch_bounds__(256) void bag_argmax_finish_kernel(const int32_t* __restrict__ row_start,
-                                                                uint4* __restrict__ grad,
-                                                                const int32_t* __restrict__ long_rows,
-                                                                const float* __restrict__ scratch) {
+__global__ __launch_bounds__(256) void bag_walk_finish_kernel(const int32_t* __restrict__ row_start,
+                                                              uint4* __restrict__ grad,
+                                                              const int32_t* __restrict__ long_rows,
+                                                              const float* __restrict__ scratch) {
   constexpr int L = 1 << LOG2L;
   constexpr int VE = Vec16<T>::VE;
   const int lane_v = threadIdx.x & (L - 1);
@@ -454,47 +457,13 @@ __global__ __launch_bounds__(256) void bag_argmax_finish_kernel(const int32_t* _
 
 // generic path (any E): one thread per (row, e); rows with more than BAG_LONG_ROW_ELEM lookups are queued (one id each)
 // and reduced by one wave per row
-template <typename T, bool WGT>
-__device__ __forceinline__ float bag_argmax_term(const T* __restrict__ g, const uint16_t* __restrict__ amax,
-                                                 const T* __restrict__ wts, int p, unsigned N, int E, int e) {
-  const unsigned b = (unsigned)p / N;
-  const unsigned l = (unsigned)p - b * N;
-  const int64_t o = (int64_t)b * E + e;
-  if (WGT) return to_f32(wts[p]) * to_f32(g[o]);
-  return (unsigned)amax[o] == l ? to_f32(g[o]) : 0.f;
-}
-
-// ragged bags: the term of bag_ragged_bucket for one element
-template <typename T, int RAG>
-__device__ __forceinline__ float bag_ragged_term(const T* __restrict__ g, const int32_t* __restrict__ amax32,
-                                                 const T* __restrict__ wts, const int32_t* __restrict__ bag_of, int p,
-                                                 int E, int e) {
-  const int b = bag_of[p];
-  if (b < 0) return 0.f;
-  const int64_t o = (int64_t)b * E + e;
-  if constexpr (RAG == RAG_WGT) return to_f32(wts[p]) * to_f32(g[o]);
-  else if constexpr (RAG == RAG_MAX) return amax32[o] == p ? to_f32(g[o]) : 0.f;
-  else return to_f32(g[o]);
-}
-
-template <typename T, bool WGT, int RAG>
-__device__ __forceinline__ float bag_walk_term(const T* __restrict__ g, const uint16_t* __restrict__ amax,
-                                               const T* __restrict__ wts, const int32_t* __restrict__ bag_of,
-                                               const int32_t* __restrict__ amax32, int p, unsigned N, int E, int e) {
-  if constexpr (RAG != RAG_OFF) return bag_ragged_term<T, RAG>(g, amax32, wts, bag_of, p, E, e);
-  else return bag_argmax_term<T, WGT>(g, amax, wts, p, N, E, e);
-}
-
-template <typename T, bool WGT, int RAG>
-__global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __restrict__ g,
-                                                                   const uint16_t* __restrict__ amax,
-                                                                   const T* __restrict__ wts,
-                                                                   const int32_t* __restrict__ row_start,
-                                                                   const int32_t* __restrict__ perm, int64_t V, int E,
-                                                                   unsigned N, int64_t padding_row, T* __restrict__ grad,
-                                                                   int32_t* __restrict__ long_rows,
-                                                                   const int32_t* __restrict__ bag_of /* RAG only */,
-                                                                   const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
+template <typename W>
+__global__ __launch_bounds__(256) void bag_walk_rows_elem_kernel(W w, const int32_t* __restrict__ row_start,
+                                                                 const int32_t* __restrict__ perm, int64_t V, int E,
+                                                                 int64_t padding_row,
+                                                                 typename W::value_type* __restrict__ grad,
+                                                                 int32_t* __restrict__ long_rows) {
+  using T = typename W::value_type;
   const int64_t total = V * E;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const bool f32 = total < ((int64_t)1 << 32);
@@ -508,22 +477,18 @@ __global__ __launch_bounds__(256) void bag_argmax_rows_elem_kernel(const T* __re
         if (e == 0) long_rows[1 + atomicAdd(&long_rows[0], 1)] = (int32_t)r;
         continue;
       }
-      for (int q = beg; q < end; ++q) acc += bag_walk_term<T, WGT, RAG>(g, amax, wts, bag_of, amax32, perm[q], N, E, e);
+      for (int q = beg; q < end; ++q) acc += w.term(perm[q], E, e);
     }
     grad[t] = from_f32<T>(acc);
   }
 }
 
-template <typename T, bool WGT, int RAG>
-__global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __restrict__ g,
-                                                                   const uint16_t* __restrict__ amax,
-                                                                   const T* __restrict__ wts,
-                                                                   const int32_t* __restrict__ row_start,
-                                                                   const int32_t* __restrict__ perm, int E, unsigned N,
-                                                                   T* __restrict__ grad,
-                                                                   const int32_t* __restrict__ long_rows,
-                                                                   const int32_t* __restrict__ bag_of /* RAG only */,
-                                                                   const int32_t* __restrict__ amax32 /* RAG_MAX only */) {
+template <typename W>
+__global__ __launch_bounds__(256) void bag_walk_long_elem_kernel(W w, const int32_t* __restrict__ row_start,
+                                                                 const int32_t* __restrict__ perm, int E,
+                                                                 typename W::value_type* __restrict__ grad,
+                                                                 const int32_t* __restrict__ long_rows) {
+  using T = typename W::value_type;
   const int nlong = long_rows[0];
   const int lane = threadIdx.x & 63;
   const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -539,7 +504,7 @@ __global__ __launch_bounds__(256) void bag_argmax_long_elem_kernel(const T* __re
         for (int u = 0; u < U; ++u) pp[u] = (q + 64 * u) < end ? perm[q + 64 * u] : -1;
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (pp[u] >= 0) acc += bag_walk_term<T, WGT, RAG>(g, amax, wts, bag_of, amax32, pp[u], N, E, e);
+          if (pp[u] >= 0) acc += w.term(pp[u], E, e);
       }
       acc = group_sum_down<64>(acc);
       if (lane == 0) grad[r * E + e] = from_f32<T>(acc);
@@ -557,33 +522,31 @@ static size_t bag_queue_bytes(int64_t BN) {
   return align_up(std::max(bag_queue_entries(BN) * 8 + 8, (size_t)(BN / BAG_LONG_ROW_ELEM + 3) * 4), 256);
 }
 
-template <typename T, bool WGT, int RAG = RAG_OFF>
-static int bag_argmax_launch(const void* g, const uint16_t* amax, const void* wts_, const int32_t* row_start,
-                             const int32_t* perm, int64_t V, int E, int N, int64_t padding_row, void* grad,
-                             int32_t* long_rows, float* scratch, hipStream_t s, const int32_t* bag_of = nullptr,
-                             const int32_t* amax32 = nullptr) {
-  const T* wts = (const T*)wts_;
+// entry: the C entry that check_launch reports
+template <typename W>
+static int bag_walk_launch(const W& w, const char* entry, const int32_t* row_start, const int32_t* perm, int64_t V, int E,
+                           int64_t padding_row, void* grad, int32_t* long_rows, float* scratch, hipStream_t s) {
+  using T = typename W::value_type;
   const int lg = log2_lanes(E * (int)sizeof(T));
   hipLaunchKernelGGL(bag_zero_counter_kernel, dim3(1), dim3(64), 0, s, long_rows);
-  if (lg >= 0 && aligned16(g) && aligned16(amax) && aligned16(amax32) && aligned16(grad)) {
+  if (lg >= 0 && w.aligned() && aligned16(grad)) {
     const int grid = stream_grid(V << lg, 256, 256 * 32);
     dispatch_lanes(lg, [&](auto lg_c) {
       constexpr int LG = decltype(lg_c)::value;
-      hipLaunchKernelGGL((bag_argmax_rows_kernel<T, LG, WGT, RAG>), dim3(grid), dim3(256), 0, s, (const uint4*)g, amax,
-                         wts, row_start, perm, V, (unsigned)N, padding_row, (uint4*)grad, long_rows, bag_of, amax32);
-      hipLaunchKernelGGL((bag_argmax_long_kernel<T, LG, WGT, RAG>), dim3(2048), dim3(256), 0, s, (const uint4*)g, amax,
-                         wts, row_start, perm, (unsigned)N, (uint4*)grad, long_rows, scratch, bag_of, amax32);
-      hipLaunchKernelGGL((bag_argmax_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,
+      hipLaunchKernelGGL((bag_walk_rows_kernel<W, LG>), dim3(grid), dim3(256), 0, s, w, row_start, perm, V, padding_row,
+                         (uint4*)grad, long_rows);
+      hipLaunchKernelGGL((bag_walk_long_kernel<W, LG>), dim3(2048), dim3(256), 0, s, w, row_start, perm, (uint4*)grad,
+                         long_rows, scratch);
+      hipLaunchKernelGGL((bag_walk_finish_kernel<T, LG>), dim3(64), dim3(256), 0, s, row_start, (uint4*)grad,
                          long_rows, scratch);
     });
   } else {
-    hipLaunchKernelGGL((bag_argmax_rows_elem_kernel<T, WGT, RAG>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0,
-                       s, (const T*)g, amax, wts, row_start, perm, V, E, (unsigned)N, padding_row, (T*)grad, long_rows,
-                       bag_of, amax32);
-    hipLaunchKernelGGL((bag_argmax_long_elem_kernel<T, WGT, RAG>), dim3(2048), dim3(256), 0, s, (const T*)g, amax, wts,
-                       row_start, perm, E, (unsigned)N, (T*)grad, long_rows, bag_of, amax32);
+    hipLaunchKernelGGL((bag_walk_rows_elem_kernel<W>), dim3(stream_grid(V * E, 256, 256 * 32)), dim3(256), 0, s, w,
+                       row_start, perm, V, E, padding_row, (T*)grad, long_rows);
+    hipLaunchKernelGGL((bag_walk_long_elem_kernel<W>), dim3(2048), dim3(256), 0, s, w, row_start, perm, E, (T*)grad,
+                       long_rows);
   }
-  return check_launch(RAG != RAG_OFF ? "scatter_rows_ragged" : WGT ? "scatter_rows_weighted" : "scatter_rows_argmax");
+  return check_launch(entry);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -698,27 +661,49 @@ extern "C" size_t trs_scatter_argmax_workspace_bytes(int64_t BN, int32_t E) {
   return bag_queue_bytes(BN) + align_up(bag_queue_entries(BN) * (size_t)E * 4, 256);
 }
 
+// What the walk entries share once their sizes are known to be sound: the dtype and workspace checks, under the entry's
+// name, and the workspace carved into the queue and the chunk partials.
+struct BagWalkSpace {
+  int32_t* long_rows;
+  float* scratch;
+};
+
+static int bag_walk_space(const char* name, int64_t BN, int32_t E, int32_t dtype, void* workspace, size_t ws_bytes,
+                          BagWalkSpace* sp) {
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "%s: dtype %d", name, dtype);
+  const size_t need = trs_scatter_argmax_workspace_bytes(BN, E);
+  TRS_REQUIRE(ws_bytes >= need, TRS_EWORKSPACE, "%s: workspace %zu < %zu", name, ws_bytes, need);
+  sp->long_rows = (int32_t*)workspace;
+  sp->scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
+  return TRS_OK;
+}
+
+// the two padded walks: operand = the winners (B, E) uint16, or the weights (B, N) of the table's dtype
+template <BagTerm TERM>
+static int bag_walk_padded(const char* name, const void* g, const void* operand, const int32_t* row_start,
+                           const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                           int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes, trs_stream_t stream) {
+  TRS_REQUIRE(g && operand && row_start && perm && grad_table && workspace, TRS_EINVAL, "%s: NULL pointer", name);
+  TRS_REQUIRE(V > 0 && E > 0 && BN >= 0, TRS_EINVAL, "%s: bad size", name);
+  TRS_REQUIRE(N >= 1 && N <= 65535, TRS_EINVAL, "%s: list length L=%d outside [1, 65535]", name, N);
+  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "%s: B*L=%lld not a multiple of L=%d", name, (long long)BN, N);
+  TRS_REQUIRE(BN < (int64_t)0x7fffffff, TRS_ESHAPE, "%s: B*L=%lld must fit int32", name, (long long)BN);
+  BagWalkSpace sp;
+  if (const int rc = bag_walk_space(name, BN, E, dtype, workspace, ws_bytes, &sp); rc != TRS_OK) return rc;
+  auto launch = [&](auto t) {
+    using W = BagWalk<decltype(t), TERM, false>;
+    return bag_walk_launch(W{(const decltype(t)*)g, (unsigned)N, (typename W::Operand)operand}, name, row_start, perm, V,
+                           E, padding_row, grad_table, sp.long_rows, sp.scratch, (hipStream_t)stream);
+  };
+  return dtype == TRS_F32 ? launch(float{}) : launch(bf16_t{});
+}
+
 extern "C" int trs_scatter_rows_argmax(const void* g, const uint16_t* argmax, const int32_t* row_start,
                                        const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
                                        int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
                                        trs_stream_t stream) {
-  TRS_REQUIRE(g && argmax && row_start && perm && grad_table && workspace, TRS_EINVAL,
-              "scatter_rows_argmax: NULL pointer");
-  TRS_REQUIRE(V > 0 && E > 0 && BN >= 0, TRS_EINVAL, "scatter_rows_argmax: bad size");
-  TRS_REQUIRE(N >= 1 && N <= 65535, TRS_EINVAL, "scatter_rows_argmax: list length L=%d outside [1, 65535]", N);
-  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "scatter_rows_argmax: B*L=%lld not a multiple of L=%d", (long long)BN, N);
-  TRS_REQUIRE(BN < (int64_t)0x7fffffff, TRS_ESHAPE, "scatter_rows_argmax: B*L=%lld must fit int32", (long long)BN);
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_argmax: dtype %d", dtype);
-  TRS_REQUIRE(ws_bytes >= trs_scatter_argmax_workspace_bytes(BN, E), TRS_EWORKSPACE,
-              "scatter_rows_argmax: workspace %zu < %zu", ws_bytes, trs_scatter_argmax_workspace_bytes(BN, E));
-  int32_t* long_rows = (int32_t*)workspace;
-  float* scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_F32)
-    return bag_argmax_launch<float, false>(g, argmax, nullptr, row_start, perm, V, E, N, padding_row, grad_table,
-                                           long_rows, scratch, s);
-  return bag_argmax_launch<bf16_t, false>(g, argmax, nullptr, row_start, perm, V, E, N, padding_row, grad_table,
-                                          long_rows, scratch, s);
+  return bag_walk_padded<BagTerm::Winner>("scatter_rows_argmax", g, argmax, row_start, perm, BN, V, E, N, dtype,
+                                          padding_row, grad_table, workspace, ws_bytes, stream);
 }
 
 extern "C" int trs_bag_pool_masked_fwd(const void* table, int64_t V, int32_t E, int32_t dtype, const void* idx,
@@ -777,23 +762,8 @@ extern "C" int trs_scatter_rows_weighted(const void* g, const void* weights, con
                                          const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
                                          int64_t padding_row, void* grad_table, void* workspace, size_t ws_bytes,
                                          trs_stream_t stream) {
-  TRS_REQUIRE(g && weights && row_start && perm && grad_table && workspace, TRS_EINVAL,
-              "scatter_rows_weighted: NULL pointer");
-  TRS_REQUIRE(V > 0 && E > 0 && BN >= 0, TRS_EINVAL, "scatter_rows_weighted: bad size");
-  TRS_REQUIRE(N >= 1 && N <= 65535, TRS_EINVAL, "scatter_rows_weighted: list length L=%d outside [1, 65535]", N);
-  TRS_REQUIRE(BN % N == 0, TRS_EINVAL, "scatter_rows_weighted: B*L=%lld not a multiple of L=%d", (long long)BN, N);
-  TRS_REQUIRE(BN < (int64_t)0x7fffffff, TRS_ESHAPE, "scatter_rows_weighted: B*L=%lld must fit int32", (long long)BN);
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_weighted: dtype %d", dtype);
-  TRS_REQUIRE(ws_bytes >= trs_scatter_weighted_workspace_bytes(BN, E), TRS_EWORKSPACE,
-              "scatter_rows_weighted: workspace %zu < %zu", ws_bytes, trs_scatter_weighted_workspace_bytes(BN, E));
-  int32_t* long_rows = (int32_t*)workspace;
-  float* scratch = (float*)((char*)workspace + bag_queue_bytes(BN));
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_F32)
-    return bag_argmax_launch<float, true>(g, nullptr, weights, row_start, perm, V, E, N, padding_row, grad_table,
-                                          long_rows, scratch, s);
-  return bag_argmax_launch<bf16_t, true>(g, nullptr, weights, row_start, perm, V, E, N, padding_row, grad_table,
-                                         long_rows, scratch, s);
+  return bag_walk_padded<BagTerm::Weighted>("scatter_rows_weighted", g, weights, row_start, perm, BN, V, E, N, dtype,
+                                            padding_row, grad_table, workspace, ws_bytes, stream);
 }
 
 extern "C" int trs_bag_weight_grad(const void* g, const void* table, int64_t V, int32_t E, int32_t dtype,
@@ -838,20 +808,16 @@ extern "C" int trs_scatter_rows_ragged(const void* g, const int32_t* bag_of, con
               (long long)n, (long long)B, (long long)V, E);
   TRS_REQUIRE(n < (int64_t)0x7fffffff && B < (int64_t)0x7fffffff, TRS_ESHAPE,
               "scatter_rows_ragged: n=%lld and B=%lld must fit int32", (long long)n, (long long)B);
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "scatter_rows_ragged: dtype %d", dtype);
-  TRS_REQUIRE(ws_bytes >= trs_scatter_ragged_workspace_bytes(n, E), TRS_EWORKSPACE,
-              "scatter_rows_ragged: workspace %zu < %zu", ws_bytes, trs_scatter_ragged_workspace_bytes(n, E));
-  int32_t* long_rows = (int32_t*)workspace;
-  float* scratch = (float*)((char*)workspace + bag_queue_bytes(n));
-  hipStream_t s = (hipStream_t)stream;
-#define TRS_CALL(T, R)                                                                                                  \
-  return bag_argmax_launch<T, false, R>(g, nullptr, weights, row_start, perm, V, E, 1, padding_row, grad_table, long_rows, \
-                                        scratch, s, bag_of, argmax)
-#define TRS_TERM(T)                               \
-  do {                                            \
-    if (weights != nullptr) TRS_CALL(T, RAG_WGT); \
-    if (argmax != nullptr) TRS_CALL(T, RAG_MAX);  \
-    TRS_CALL(T, RAG_PLAIN);                       \
+  BagWalkSpace sp;
+  if (const int rc = bag_walk_space("scatter_rows_ragged", n, E, dtype, workspace, ws_bytes, &sp); rc != TRS_OK) return rc;
+#define TRS_CALL(T, TERM, ...)                                                                                        \
+  return bag_walk_launch(BagWalk<T, BagTerm::TERM, true>{(const T*)g, bag_of, __VA_ARGS__}, "scatter_rows_ragged",   \
+                         row_start, perm, V, E, padding_row, grad_table, sp.long_rows, sp.scratch, (hipStream_t)stream)
+#define TRS_TERM(T)                                                    \
+  do {                                                                 \
+    if (weights != nullptr) TRS_CALL(T, Weighted, (const T*)weights);  \
+    if (argmax != nullptr) TRS_CALL(T, Winner, argmax);                \
+    TRS_CALL(T, Plain, {});                                            \
   } while (0)
   if (dtype == TRS_F32) TRS_TERM(float);
   TRS_TERM(bf16_t);

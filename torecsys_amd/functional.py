@@ -567,9 +567,7 @@ def gather_rows(weight: torch.Tensor, idx: torch.Tensor, offsets: Optional[torch
         idx = idx.unsqueeze(-1)
     if idx.dim() != 2:
         raise ValueError(f"indices must be (B, N), got shape {tuple(idx.shape)}")
-    if padding_idx is not None and padding_idx < 0:
-        padding_idx = weight.shape[0] + padding_idx
-    return _GatherRows.apply(weight, idx, offsets, padding_idx, opt)
+    return _GatherRows.apply(weight, idx, offsets, _norm_padding("gather_rows", padding_idx, weight.shape[0]), opt)
 
 
 # --------------------------------------------------------------------------------------------
@@ -578,61 +576,68 @@ def gather_rows(weight: torch.Tensor, idx: torch.Tensor, offsets: Optional[torch
 BAG_MODES = {"sum": 0, "mean": 1, "max": 2}
 
 
+def _norm_padding(op, padding_idx, V, exclude_padding=False):
+    """``padding_idx`` counted from the front; ``exclude_padding`` needs it to name a row of the table."""
+    if padding_idx is not None and padding_idx < 0:
+        padding_idx = V + padding_idx
+    if exclude_padding:
+        if padding_idx is None:
+            raise ValueError(f"{op}: exclude_padding=True needs a padding_idx")
+        if not 0 <= padding_idx < V:
+            raise ValueError(f"{op}: exclude_padding=True needs a padding row inside the table, got {padding_idx} "
+                             f"for {V} rows")
+    return padding_idx
+
+
+def _skip_row(padding_idx, V):
+    """The padding id is left out of the row buckets: no walk reads that bucket, and filing a third or more of all
+    positions under one row serialises the build (22 ms against 0.2 ms, profiles/bag_kernels.md)."""
+    return padding_idx if 0 <= padding_idx < V else None
+
+
+def _check_psw(op, psw, mode, weight, shape, flatten):
+    """``per_sample_weights`` as the kernels read them: ``shape`` -- (B, L), or (n,) with ``flatten`` (an (n, 1) column
+    is taken as (n,)) --, the table's dtype and device, ``sum`` only."""
+    if psw is None:
+        return None
+    if mode != "sum":
+        raise ValueError(f"{op}: per_sample_weights is only supported for mode='sum', got {mode!r}")
+    psw = psw.rename(None) if psw.has_names() else psw
+    if flatten and psw.dim() == 2 and psw.shape[1] == 1:
+        psw = psw.reshape(-1)
+    if tuple(psw.shape) != tuple(shape):
+        raise ValueError(f"{op}: per_sample_weights must be {'(n,)' if flatten else '(B, L)'} = {tuple(shape)}, got "
+                         f"{tuple(psw.shape)}")
+    if psw.dtype != weight.dtype:
+        raise ValueError(f"{op}: per_sample_weights must have the table's dtype {weight.dtype}, got {psw.dtype}")
+    if psw.device != weight.device:
+        raise ValueError(f"{op}: per_sample_weights must be on the table's device {weight.device}, got {psw.device}")
+    return psw
+
+
+def _save_optional(ctx, fixed, optional):
+    """save_for_backward of ``fixed`` tensors and of those of ``optional`` that exist; _load_optional gives all back."""
+    ctx.has = tuple(t is not None for t in optional)
+    ctx.save_for_backward(*fixed, *[t for t in optional if t is not None])
+
+
+def _load_optional(ctx):
+    saved = list(ctx.saved_tensors)
+    fixed = saved[:len(saved) - sum(ctx.has)]
+    rest = saved[len(fixed):]
+    return (*fixed, *[rest.pop(0) if h else None for h in ctx.has])
+
+
+def _live_mean_grad(g2, inv_cnt):
+    """The (bags, E) gradient as the walks read it.  Mean over the live positions (``inv_cnt`` given): times 1 / cnt[b]
+    in fp32, rounded once to the table's dtype."""
+    return (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if inv_cnt is not None else g2.contiguous()
+
+
 class _BagPool(Function):
-    @staticmethod
-    def forward(ctx, weight, idx, mode, padding_idx, opt=None):
-        require_device(weight, idx)
-        B, L = idx.shape
-        V, E = weight.shape
-        w = weight.contiguous()
-        out = torch.empty(B, E, dtype=w.dtype, device=w.device)
-        # the winning list positions, uint16 bit patterns (L <= 65535) in an int16 tensor
-        amax = torch.empty(B, E, dtype=torch.int16, device=w.device) if mode == 2 else None
-        flag = _ErrFlag(w.device)
-        call("trs_bag_pool_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, mode,
-             ptr(out), ptr(amax), ptr(flag.t), stream_ptr())
-        flag.check("bag_pool")
-        ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
-        # the padding id is left out of the row buckets: no walk reads that bucket, and filing a third or more of all
-        # B*L positions under one row serialises the build (22 ms against 0.2 ms, profiles/bag_kernels.md)
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
-        if ctx.needs_input_grad[0]:
-            prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
-            if amax is None:
-                ctx.save_for_backward(idx, weight)
-            else:
-                ctx.save_for_backward(idx, weight, amax)
-        ctx.mode = mode
-        ctx.opt = opt
-        return out.unsqueeze(1)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        idx, weight = ctx.saved_tensors[:2]
-        _adopt_grads(g)
-        V, E = weight.shape
-        L = idx.shape[1]
-        rb = row_buckets(idx, None, V, skip_row=ctx.skip)
-        g2 = g.reshape(g.shape[0], E)
-        if ctx.mode == 2:
-            amax = ctx.saved_tensors[2]
-            g2 = g2.contiguous()
-            grad = torch.empty(V, E, dtype=weight.dtype, device=weight.device)
-            ws_bytes = size_query("trs_scatter_argmax_workspace_bytes", rb.BN, E)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
-            call("trs_scatter_rows_argmax", ptr(g2), ptr(amax), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, L,
-                 value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
-            return grad, None, None, None, None
-        # sum / mean: the per-sample gradient broadcast over the L positions (mean: times 1/L first, on (B,E))
-        g2 = g2 * (1.0 / L) if ctx.mode == 1 else g2.contiguous()
-        grad = _apply_or_grad(rb, weight, ctx.opt, g_bcast=g2, padding_row=ctx.padding_idx)
-        return grad, None, None, None, None
-
-
-class _BagPoolMasked(Function):
-    """bag_pool with ``exclude_padding`` and / or ``per_sample_weights`` (trs_bag_pool_masked_fwd).  The row buckets are
-    the ones _BagPool builds (padding id skipped), so the sum / mean / max backward are its walks on another gradient."""
+    """bag_pool. Neither exclusion nor weights: trs_bag_pool_fwd, every position counts.  ``exclude_padding`` and / or
+    ``per_sample_weights``: trs_bag_pool_masked_fwd.  Both build the same row buckets (padding id skipped), so the
+    sum / mean / max backward are the same walks; only the scale of the mean differs (1 / L, or 1 / live count)."""
 
     @staticmethod
     def forward(ctx, weight, idx, psw, mode, padding_idx, exclude, opt=None):
@@ -641,21 +646,27 @@ class _BagPoolMasked(Function):
         V, E = weight.shape
         w = weight.contiguous()
         wts = psw.contiguous() if psw is not None else None
+        masked = exclude or wts is not None
         out = torch.empty(B, E, dtype=w.dtype, device=w.device)
+        # the winning list positions, uint16 bit patterns (L <= 65535) in an int16 tensor
         amax = torch.empty(B, E, dtype=torch.int16, device=w.device) if mode == 2 else None
         # 1 / (live positions of the bag), 0 for an empty one: written by the kernel, never read back here
-        inv_cnt = torch.empty(B, dtype=torch.float32, device=w.device) if mode == 1 else None
+        inv_cnt = torch.empty(B, dtype=torch.float32, device=w.device) if masked and mode == 1 else None
         ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
         ctx.exclude_row = ctx.padding_idx if exclude else -1
         flag = _ErrFlag(w.device)
-        call("trs_bag_pool_masked_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, mode,
-             ctx.exclude_row, ptr(wts), ptr(out), ptr(amax), ptr(inv_cnt), ptr(flag.t), stream_ptr())
+        if masked:
+            call("trs_bag_pool_masked_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L,
+                 mode, ctx.exclude_row, ptr(wts), ptr(out), ptr(amax), ptr(inv_cnt), ptr(flag.t), stream_ptr())
+        else:
+            call("trs_bag_pool_fwd", ptr(w), V, E, value_dtype_code(w), ptr(idx), index_dtype_code(idx), B, L, mode,
+                 ptr(out), ptr(amax), ptr(flag.t), stream_ptr())
         flag.check("bag_pool")
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        ctx.skip = _skip_row(ctx.padding_idx, V)
         if ctx.needs_input_grad[0]:
             prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
-        ctx.has = (wts is not None, amax is not None, inv_cnt is not None)
-        ctx.save_for_backward(idx, weight, *[t for t in (wts, amax, inv_cnt) if t is not None])
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:      # else there is no backward: nothing is kept
+            _save_optional(ctx, (idx, weight), (wts, amax, inv_cnt))
         ctx.mode = mode
         ctx.opt = opt
         return out.unsqueeze(1)
@@ -663,9 +674,7 @@ class _BagPoolMasked(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        idx, weight = ctx.saved_tensors[:2]
-        rest = list(ctx.saved_tensors[2:])
-        wts, amax, inv_cnt = (rest.pop(0) if h else None for h in ctx.has)
+        idx, weight, wts, amax, inv_cnt = _load_optional(ctx)
         _adopt_grads(g)
         V, E = weight.shape
         B, L = idx.shape
@@ -678,19 +687,19 @@ class _BagPoolMasked(Function):
                  index_dtype_code(idx), B, L, ctx.exclude_row, ptr(dw), stream_ptr())
         if ctx.needs_input_grad[0]:
             rb = row_buckets(idx, None, V, skip_row=ctx.skip)
-            if ctx.mode == 2 or wts is not None:
+            if amax is not None or wts is not None:
+                # max: the winner's position takes g; weighted sum: every bucketed position takes w * g
+                entry, operand = ("argmax", amax) if amax is not None else ("weighted", wts)
                 g2 = g2.contiguous()
                 grad = torch.empty(V, E, dtype=weight.dtype, device=weight.device)
-                entry = "argmax" if ctx.mode == 2 else "weighted"
                 ws_bytes = size_query(f"trs_scatter_{entry}_workspace_bytes", rb.BN, E)
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=weight.device)
-                call(f"trs_scatter_rows_{entry}", ptr(g2), ptr(amax if ctx.mode == 2 else wts), ptr(rb.row_start),
-                     ptr(rb.perm), rb.BN, V, E, L, value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws),
-                     ws_bytes, stream_ptr())
+                call(f"trs_scatter_rows_{entry}", ptr(g2), ptr(operand), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, L,
+                     value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
             else:
-                # sum / mean over the live positions: the per-sample gradient (mean: times 1 / cnt[b] in fp32, rounded
-                # once to the table's dtype, on (B,E)) broadcast over the bucketed -- live -- positions
-                g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
+                # sum / mean: the per-sample gradient broadcast over the bucketed positions (mean over all L positions:
+                # times 1 / L first, on (B,E))
+                g2 = g2 * (1.0 / L) if ctx.mode == 1 and inv_cnt is None else _live_mean_grad(g2, inv_cnt)
                 grad = _apply_or_grad(rb, weight, ctx.opt, g_bcast=g2, padding_row=ctx.padding_idx)
         return grad, None, dw, None, None, None, None
 
@@ -720,40 +729,49 @@ def bag_pool(weight: torch.Tensor, idx: torch.Tensor, mode: str = "mean", paddin
     if opt is not None and mode == "max":
         raise NotImplementedError("torecsys_amd: max pooling with a fused sparse optimizer is not implemented "
                                   "(use sum / mean pooling, or a dense optimizer)")
-    if padding_idx is not None and padding_idx < 0:
-        padding_idx = weight.shape[0] + padding_idx
-    if not exclude_padding and per_sample_weights is None:
-        return _BagPool.apply(weight, idx, BAG_MODES[mode], padding_idx, opt)
-    if exclude_padding:
-        if padding_idx is None:
-            raise ValueError("bag_pool: exclude_padding=True needs a padding_idx")
-        if not 0 <= padding_idx < weight.shape[0]:
-            raise ValueError(f"bag_pool: exclude_padding=True needs a padding row inside the table, got {padding_idx} "
-                             f"for {weight.shape[0]} rows")
-        if mode == "max" and idx.shape[1] > 65534:
-            raise ValueError(f"bag_pool: max pooling with exclude_padding=True: list length {idx.shape[1]} exceeds "
-                             "65534 (0xFFFF marks an empty bag)")
-    psw = per_sample_weights
-    if psw is not None:
-        if mode != "sum":
-            raise ValueError(f"bag_pool: per_sample_weights is only supported for mode='sum', got {mode!r}")
-        psw = psw.rename(None) if psw.has_names() else psw
-        if tuple(psw.shape) != tuple(idx.shape):
-            raise ValueError(f"bag_pool: per_sample_weights must be (B, L) = {tuple(idx.shape)}, got {tuple(psw.shape)}")
-        if psw.dtype != weight.dtype:
-            raise ValueError(f"bag_pool: per_sample_weights must have the table's dtype {weight.dtype}, got {psw.dtype}")
-        if psw.device != weight.device:
-            raise ValueError(f"bag_pool: per_sample_weights must be on the table's device {weight.device}, "
-                             f"got {psw.device}")
-        if opt is not None:
-            raise NotImplementedError("torecsys_amd: per_sample_weights with a fused sparse optimizer is not "
-                                      "implemented (use a dense optimizer)")
-    return _BagPoolMasked.apply(weight, idx, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), opt)
+    padding_idx = _norm_padding("bag_pool", padding_idx, weight.shape[0], exclude_padding)
+    if exclude_padding and mode == "max" and idx.shape[1] > 65534:
+        raise ValueError(f"bag_pool: max pooling with exclude_padding=True: list length {idx.shape[1]} exceeds "
+                         "65534 (0xFFFF marks an empty bag)")
+    psw = _check_psw("bag_pool", per_sample_weights, mode, weight, idx.shape, flatten=False)
+    if psw is not None and opt is not None:
+        raise NotImplementedError("torecsys_amd: per_sample_weights with a fused sparse optimizer is not "
+                                  "implemented (use a dense optimizer)")
+    return _BagPool.apply(weight, idx, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), opt)
 
 
 def bag_ragged_long_len() -> int:
     """Bags of more ids than this are reduced by a whole wave each (the second tier of trs_bag_pool_ragged_fwd)."""
     return size_query("trs_bag_ragged_long_len")
+
+
+def _bag_mapped_grads(g2, weight, ids, owner, wts, amax, n, nbags, padding_row, exclude_row, check, need):
+    """(table gradient, weight gradient) of bags whose lookups find their bag in a map: ``ids`` (n,) are the table rows
+    looked up, ``owner`` (n,) int32 the bag of each (below zero: none; None: no lookup belongs to a bag), ``g2``
+    (nbags, E) the bags' gradients (_live_mean_grad).  ``need``: which of the two is wanted; ``check``: whether the
+    bucket build flags ids outside the table."""
+    need_grad, need_dw = need
+    V, E = weight.shape
+    dev = weight.device
+    grad = dw = None
+    if owner is None:
+        if need_grad:
+            grad = torch.zeros(V, E, dtype=weight.dtype, device=dev)
+        if need_dw:
+            dw = torch.zeros(n, dtype=wts.dtype, device=dev)
+        return grad, dw
+    if need_dw:
+        dw = torch.empty(n, dtype=wts.dtype, device=dev)
+        call("trs_bag_weight_grad_ragged", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(ids),
+             index_dtype_code(ids), n, ptr(owner), exclude_row, ptr(dw), stream_ptr())
+    if need_grad:
+        rb = row_buckets(ids.view(n, 1), None, V, check=check, skip_row=_skip_row(padding_row, V))
+        grad = torch.empty(V, E, dtype=weight.dtype, device=dev)
+        ws_bytes = size_query("trs_scatter_ragged_workspace_bytes", n, E)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        call("trs_scatter_rows_ragged", ptr(g2), ptr(owner), ptr(wts), ptr(amax), ptr(rb.row_start), ptr(rb.perm), n,
+             nbags, V, E, value_dtype_code(weight), padding_row, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+    return grad, dw
 
 
 class _BagPoolRagged(Function):
@@ -781,50 +799,27 @@ class _BagPoolRagged(Function):
              ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, mode, ctx.exclude_row, ptr(wts), ptr(out),
              ptr(amax), ptr(inv_cnt), ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
         flag.check("bag_pool_ragged")
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
         if ctx.needs_input_grad[0] and n > 0 and B > 0:
-            prefetch_row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
-        ctx.has = (wts is not None, amax is not None, inv_cnt is not None)
-        ctx.save_for_backward(ids, offsets, weight, *[t for t in (wts, amax, inv_cnt) if t is not None])
-        ctx.mode, ctx.B = mode, B
+            prefetch_row_buckets(ids.view(n, 1), None, V, skip_row=_skip_row(ctx.padding_idx, V))
+        _save_optional(ctx, (ids, offsets, weight), (wts, amax, inv_cnt))
+        ctx.B = B
         return out.unsqueeze(1)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        ids, offsets, weight = ctx.saved_tensors[:3]
-        rest = list(ctx.saved_tensors[3:])
-        wts, amax, inv_cnt = (rest.pop(0) if h else None for h in ctx.has)
+        ids, offsets, weight, wts, amax, inv_cnt = _load_optional(ctx)
         _adopt_grads(g)
-        V, E = weight.shape
         n, B = ids.shape[0], ctx.B
-        dev = weight.device
-        g2 = g.reshape(B, E)
-        # mean: times 1 / cnt[b] in fp32, rounded once to the table's dtype, on (B, E) -- as _BagPoolMasked does
-        g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
-        grad = dw = None
-        need_dw = wts is not None and ctx.needs_input_grad[3]
-        if not (ctx.needs_input_grad[0] or need_dw):      # a frozen table without weights: no map, no walk
-            return None, None, None, None, None, None, None, None
-        if n == 0 or B == 0:      # no lookup belongs to a bag
-            if ctx.needs_input_grad[0]:
-                grad = torch.zeros(V, E, dtype=weight.dtype, device=dev)
-            if need_dw:
-                dw = torch.zeros(n, dtype=wts.dtype, device=dev)
-            return grad, None, None, dw, None, None, None, None
-        bag_of = torch.empty(n, dtype=torch.int32, device=dev)
-        call("trs_bag_owner", ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, n, ptr(bag_of), stream_ptr())
-        if need_dw:
-            dw = torch.empty(n, dtype=wts.dtype, device=dev)
-            call("trs_bag_weight_grad_ragged", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(ids),
-                 index_dtype_code(ids), n, ptr(bag_of), ctx.exclude_row, ptr(dw), stream_ptr())
-        if ctx.needs_input_grad[0]:
-            rb = row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
-            grad = torch.empty(V, E, dtype=weight.dtype, device=dev)
-            ws_bytes = size_query("trs_scatter_ragged_workspace_bytes", n, E)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            call("trs_scatter_rows_ragged", ptr(g2), ptr(bag_of), ptr(wts), ptr(amax), ptr(rb.row_start), ptr(rb.perm),
-                 n, B, V, E, value_dtype_code(weight), ctx.padding_idx, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+        need = (ctx.needs_input_grad[0], wts is not None and ctx.needs_input_grad[3])
+        g2 = _live_mean_grad(g.reshape(B, weight.shape[1]), inv_cnt)
+        bag_of = None
+        if any(need) and n > 0 and B > 0:
+            bag_of = torch.empty(n, dtype=torch.int32, device=weight.device)
+            call("trs_bag_owner", ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, n, ptr(bag_of),
+                 stream_ptr())
+        grad, dw = _bag_mapped_grads(g2, weight, ids, bag_of, wts, amax, n, B, ctx.padding_idx, ctx.exclude_row, True,
+                                     need)
         return grad, None, None, dw, None, None, None, None
 
 
@@ -863,30 +858,8 @@ def bag_pool_ragged(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Tens
         raise ValueError(f"bag_pool_ragged: {ids.shape[0]} ids, must be below 2^31 - 1")
     if weight.dim() != 2:
         raise ValueError(f"weight must be (V, E), got shape {tuple(weight.shape)}")
-    if padding_idx is not None and padding_idx < 0:
-        padding_idx = weight.shape[0] + padding_idx
-    if exclude_padding:
-        if padding_idx is None:
-            raise ValueError("bag_pool_ragged: exclude_padding=True needs a padding_idx")
-        if not 0 <= padding_idx < weight.shape[0]:
-            raise ValueError(f"bag_pool_ragged: exclude_padding=True needs a padding row inside the table, got "
-                             f"{padding_idx} for {weight.shape[0]} rows")
-    psw = per_sample_weights
-    if psw is not None:
-        if mode != "sum":
-            raise ValueError(f"bag_pool_ragged: per_sample_weights is only supported for mode='sum', got {mode!r}")
-        psw = psw.rename(None) if psw.has_names() else psw
-        if psw.dim() == 2 and psw.shape[1] == 1:
-            psw = psw.reshape(-1)
-        if tuple(psw.shape) != tuple(ids.shape):
-            raise ValueError(f"bag_pool_ragged: per_sample_weights must be (n,) = {tuple(ids.shape)}, got "
-                             f"{tuple(psw.shape)}")
-        if psw.dtype != weight.dtype:
-            raise ValueError(f"bag_pool_ragged: per_sample_weights must have the table's dtype {weight.dtype}, got "
-                             f"{psw.dtype}")
-        if psw.device != weight.device:
-            raise ValueError(f"bag_pool_ragged: per_sample_weights must be on the table's device {weight.device}, "
-                             f"got {psw.device}")
+    padding_idx = _norm_padding("bag_pool_ragged", padding_idx, weight.shape[0], exclude_padding)
+    psw = _check_psw("bag_pool_ragged", per_sample_weights, mode, weight, ids.shape, flatten=True)
     return _BagPoolRagged.apply(weight, ids, offsets, psw, BAG_MODES[mode], padding_idx, bool(exclude_padding), B)
 
 
@@ -948,47 +921,19 @@ class _BagPoolFields(Function):
                 # rows holds -1 where no bag holds the position or the id lies outside its field (flagged by the forward):
                 # the build leaves them out, and must not flag the positions behind the last bag
                 prefetch_row_buckets(rows.view(n, 1), None, V, check=False)
-        ctx.has = (wts is not None, amax is not None, inv_cnt is not None, rows is not None)
-        ctx.save_for_backward(weight, *[t for t in (wts, amax, inv_cnt) if t is not None],
-                              *([out_row_of, rows] if rows is not None else []))
-        ctx.mode, ctx.B, ctx.F, ctx.n = mode, B, F, n
+        _save_optional(ctx, (weight,), (wts, amax, inv_cnt, out_row_of, rows))
+        ctx.FB, ctx.n = FB, n
         return out.view(B, F, E)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        weight = ctx.saved_tensors[0]
-        rest = list(ctx.saved_tensors[1:])
-        wts, amax, inv_cnt, out_row_of = (rest.pop(0) if h else None for h in ctx.has)
-        rows = rest.pop(0) if ctx.has[3] else None
+        weight, wts, amax, inv_cnt, out_row_of, rows = _load_optional(ctx)
         _adopt_grads(g)
-        V, E = weight.shape
-        n, FB = ctx.n, ctx.F * ctx.B
-        dev = weight.device
-        grad = dw = None
-        need_dw = wts is not None and ctx.needs_input_grad[4]
-        if not (ctx.needs_input_grad[0] or need_dw):
-            return None, None, None, None, None, None, None, None
-        if rows is None:      # n == 0 or B == 0: no lookup belongs to a bag
-            if ctx.needs_input_grad[0]:
-                grad = torch.zeros(V, E, dtype=weight.dtype, device=dev)
-            if need_dw:
-                dw = torch.zeros(n, dtype=wts.dtype, device=dev)
-            return grad, None, None, None, dw, None, None, None
-        g2 = g.reshape(FB, E)
-        # mean: times 1 / cnt in fp32, rounded once to the table's dtype, on (B*F, E) -- as _BagPoolRagged does
-        g2 = (g2 * inv_cnt.unsqueeze(1)).to(g2.dtype) if ctx.mode == 1 else g2.contiguous()
-        if need_dw:
-            dw = torch.empty(n, dtype=wts.dtype, device=dev)
-            call("trs_bag_weight_grad_ragged", ptr(g2), ptr(weight.contiguous()), V, E, value_dtype_code(weight), ptr(rows),
-                 index_dtype_code(rows), n, ptr(out_row_of), -1, ptr(dw), stream_ptr())
-        if ctx.needs_input_grad[0]:
-            rb = row_buckets(rows.view(n, 1), None, V, check=False)
-            grad = torch.empty(V, E, dtype=weight.dtype, device=dev)
-            ws_bytes = size_query("trs_scatter_ragged_workspace_bytes", n, E)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            call("trs_scatter_rows_ragged", ptr(g2), ptr(out_row_of), ptr(wts), ptr(amax), ptr(rb.row_start), ptr(rb.perm),
-                 n, FB, V, E, value_dtype_code(weight), -1, ptr(grad), ptr(ws), ws_bytes, stream_ptr())
+        need = (ctx.needs_input_grad[0], wts is not None and ctx.needs_input_grad[4])
+        # the table rows are the lookup ids; there is no padding row, and the forward has flagged what the build leaves out
+        g2 = _live_mean_grad(g.reshape(ctx.FB, weight.shape[1]), inv_cnt)
+        grad, dw = _bag_mapped_grads(g2, weight, rows, out_row_of, wts, amax, ctx.n, ctx.FB, -1, -1, False, need)
         return grad, None, None, None, dw, None, None, None
 
 
@@ -1033,22 +978,7 @@ def bag_pool_fields(weight: torch.Tensor, values: torch.Tensor, offsets: torch.T
     B = (offsets.shape[0] - 1) // F
     if values.shape[0] >= 2 ** 31 - 1 or F * B >= 2 ** 31 - 1:
         raise ValueError(f"bag_pool_fields: {values.shape[0]} values and {F * B} bags, both must be below 2^31 - 1")
-    psw = per_sample_weights
-    if psw is not None:
-        if mode != "sum":
-            raise ValueError(f"bag_pool_fields: per_sample_weights is only supported for mode='sum', got {mode!r}")
-        psw = psw.rename(None) if psw.has_names() else psw
-        if psw.dim() == 2 and psw.shape[1] == 1:
-            psw = psw.reshape(-1)
-        if tuple(psw.shape) != tuple(values.shape):
-            raise ValueError(f"bag_pool_fields: per_sample_weights must be (n,) = {tuple(values.shape)}, got "
-                             f"{tuple(psw.shape)}")
-        if psw.dtype != weight.dtype:
-            raise ValueError(f"bag_pool_fields: per_sample_weights must have the table's dtype {weight.dtype}, got "
-                             f"{psw.dtype}")
-        if psw.device != weight.device:
-            raise ValueError(f"bag_pool_fields: per_sample_weights must be on the table's device {weight.device}, "
-                             f"got {psw.device}")
+    psw = _check_psw("bag_pool_fields", per_sample_weights, mode, weight, values.shape, flatten=True)
     return _BagPoolFields.apply(weight, values, offsets, fo.contiguous(), psw, BAG_MODES[mode], B, F)
 
 
@@ -1083,7 +1013,7 @@ class _AttnPool(Function):
              ptr(bq), H, mode, ptr(out), ptr(flag.t), stream_ptr())
         flag.check("attn_pool")
         ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None      # as _BagPool: no walk reads that bucket
+        ctx.skip = _skip_row(ctx.padding_idx, V)
         if ctx.needs_input_grad[0]:
             prefetch_row_buckets(idx, None, V, skip_row=ctx.skip)
         # nothing but the inputs is kept: the backward recomputes Q, K and the probabilities from the table rows
@@ -1202,7 +1132,7 @@ class _AttnPoolRagged(Function):
              ptr(offsets), index_dtype_code(offsets), offsets.shape[0], B, max_length, ctx.exclude_row, ptr(wq), ptr(bq),
              H, mode, ptr(out), ptr(cnt), ptr(flag.t), stream_ptr())
         flag.check("attn_pool_ragged")
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None
+        ctx.skip = _skip_row(ctx.padding_idx, V)
         if ctx.needs_input_grad[0] and n > 0 and B > 0:
             prefetch_row_buckets(ids.view(n, 1), None, V, skip_row=ctx.skip)
         # nothing but the inputs is kept: the backward finds the live ids again and recomputes Q, K and the probabilities
@@ -1291,14 +1221,7 @@ def attn_pool_ragged(weight: torch.Tensor, ids: torch.Tensor, offsets: torch.Ten
     if attn_pool_path(max_length, E, num_heads, weight.dtype) == 0:
         raise NotImplementedError(f"torecsys_amd: attn_pool_ragged does not cover max_length={max_length}, E={E}, "
                                   f"H={num_heads}, {weight.dtype} (E <= 128, E % H == 0, fp32 / bf16)")
-    if padding_idx is not None and padding_idx < 0:
-        padding_idx = V + padding_idx
-    if exclude_padding:
-        if padding_idx is None:
-            raise ValueError("attn_pool_ragged: exclude_padding=True needs a padding_idx")
-        if not 0 <= padding_idx < V:
-            raise ValueError(f"attn_pool_ragged: exclude_padding=True needs a padding row inside the table, got "
-                             f"{padding_idx} for {V} rows")
+    padding_idx = _norm_padding("attn_pool_ragged", padding_idx, V, exclude_padding)
     return _AttnPoolRagged.apply(weight, ids, offsets, w_qk, b_qk, num_heads, ATTN_POOL_MODES[mode], padding_idx,
                                  bool(exclude_padding), B, max_length)
 
@@ -2818,7 +2741,7 @@ class _SeqRNN(Function):
         flag.check("seq_rnn")
         ctx.cell, ctx.mode = cell, mode
         ctx.padding_idx = -1 if padding_idx is None else int(padding_idx)
-        ctx.skip = ctx.padding_idx if 0 <= ctx.padding_idx < V else None      # as _BagPool: no walk reads that bucket
+        ctx.skip = _skip_row(ctx.padding_idx, V)
         if save:
             idx_m = None
             if need[0] or need[3]:
