@@ -1306,8 +1306,10 @@ int trs_embed_pair_score_bwd(const void* a_table, int64_t Va, const void* a_idx,
  * Two launches: per-workgroup partial sums in a fixed order, then one wave (reproducible bits).
  * bwd: g_pos[b * g_pos_stride] = sum_k dterm/dp, g_neg[b * g_neg_stride + k] = dterm/dn, times gout[0] (fp32 device
  * scalar, NULL = 1) over the divisor (denom: the forward's, required for a masked mean; NULL = computed from B and K);
- * zeros for a dropped sample.  kind 3: the first of equal maximal negatives takes the gradient.  K >= 1.  B == 0 returns
- * TRS_OK.  Errors before any launch: dtype TRS_EDTYPE; kind, reduction, sizes, strides, NULL TRS_EINVAL.            */
+ * zeros for a dropped sample.  kind 3: the first of equal maximal negatives takes the gradient.  kinds 2 and 3: a hinge
+ * argument of exactly 0 passes the gradient (margin - p + n >= 0), as ATen's clamp(min=0) and margin_ranking_loss do; the
+ * forward's term is 0 either way.  K >= 1.  B == 0 returns TRS_OK.  Errors before any launch: dtype TRS_EDTYPE; kind,
+ * reduction, sizes, strides, NULL TRS_EINVAL.                                                                         */
 size_t trs_rank_loss_workspace_bytes(int64_t B);
 int trs_rank_loss_fwd(const void* pos, int64_t pos_stride, const void* neg, int64_t neg_stride, int32_t dtype,
                       const void* mask, int64_t B, int32_t K, int32_t kind, float margin, int32_t reduction, float* loss,

@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void rank_loss_bwd_kernel(RankArgs a, const fl
         const float n = rank_load_val(a.neg, a.f32, b * a.neg_stride + k);
         if (n > mx) { mx = n; at = k; }
       }
-      const float on = keep && (a.margin - p + mx > 0.f) ? g : 0.f;
+      const float on = keep && (a.margin - p + mx >= 0.f) ? g : 0.f;      // clamp's derivative at 0 is 1
       for (int k = 0; k < a.K; ++k) rank_store_val(g_neg, a.f32, b * g_neg_stride + k, k == at ? on : 0.f);
       gp = -on;
     } else {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void rank_loss_bwd_kernel(RankArgs a, const fl
           dn = sigmoid_f(n - p);
           dp = -dn;
         } else {
-          dn = a.margin - p + n > 0.f ? 1.f : 0.f;
+          dn = a.margin - p + n >= 0.f ? 1.f : 0.f;      // as ATen's clamp(min=0) and margin_ranking_loss: 1 at the kink
           dp = -dn;
         }
         gp += dp;
