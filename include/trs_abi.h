@@ -654,6 +654,23 @@ int trs_mlp_fused_bwd_data_wlast(const void* gy, int32_t gy_stride, int64_t rows
                                  const void* h_last, int32_t h_stride, int32_t live, float* wl_part,
                                  size_t wl_part_bytes, float* gw_last, int32_t dtype, int32_t family, void* workspace,
                                  size_t ws_bytes, trs_stream_t stream);
+/* The tile backward WITHOUT its reduce launch (TILE and MIXED families, rows > 0).  Operands as the entry above; h_last =
+ * NULL: the output layer's dW is not carried (live / wl_part unused, gy_stride = widths[L]).  Instead of gbias, gbias_in
+ * and gw_last the call reports where the per-workgroup partial rows lie, in ``workspace`` and ``wl_part``:
+ * part_out / stride_out [num_layers + 4] and *nparts_out -- set l < L: layer l's bias gradient (pad32(widths[l+1])
+ * columns); set L: the input's column sums (with mask_in, else NULL); set L + 1 + j: row j of the output layer's dW
+ * (pad32(widths[L-1]) columns, NULL from ``live`` on).  Column c of a set is the sum over p < nparts of
+ * part[p * stride + c]; trs_wgrad_finish_many_parts / trs_wgrad_finish_t_many_parts (or trs_colsum_parts_reduce) take that
+ * sum in the reduce launch's order.  Both buffers must stay allocated until that consumer is enqueued on the stream. */
+int trs_mlp_fused_bwd_data_parts(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
+                                 const int32_t* widths, const void* const* weights, const void* const* masks,
+                                 void* const* gz, void* gx, const void* mask_in, const void* h_last, int32_t h_stride,
+                                 int32_t live, float* wl_part, size_t wl_part_bytes, const float** part_out, int32_t* stride_out, int32_t* nparts_out, int32_t dtype,
+                                 int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream);
+/* out[k][c] = sum of set k's partials for c < n[k] (1 .. 8 sets of ``nparts`` rows): the reduce launch on its own, for a
+ * caller of the entry above that has no batched finish to fold the sets in                                            */
+int trs_colsum_parts_reduce(int32_t n_sets, const float* const* part, const int32_t* stride, const int32_t* n,
+                            int32_t nparts, float* const* out, trs_stream_t stream);
 
 /* dst (rows, c_out) = [src (rows, c_in) | zeros], bf16: the gradient of the first c_in columns of a padded output (the
  * logit column of a deep branch whose last layer runs at 8 columns) in one launch.                                   */
@@ -845,6 +862,20 @@ int trs_wgrad_wide_many(int32_t n_jobs, const void* const* x, const int32_t* ldx
 int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
                             const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
                             const float* const* gb_f32, void* const* gb, trs_stream_t stream);
+/* Both batched finishes with PARTIAL-ROW sources: where gb_nparts[k] > 0, gb_f32[k] is not a summed vector but gb_nparts[k]
+ * rows of per-workgroup partial sums, gb_stride[k] floats apart (>= the job's columns) -- what trs_mlp_fused_bwd_data_parts
+ * reports.  Value c is the sum over p of gb_f32[k][p * gb_stride[k] + c], taken in the order of the tile backward's own
+ * reduce launch (sixteen running sums over p = w, w + 16, ..., then w = 0 .. 15), so the cast value has the bits that
+ * trs_mlp_fused_bwd_data + the plain finish give.  gb_nparts[k] = 0: job k as in the plain entry.  Applies to the bias
+ * row of a product job and to a job without a product alike.                                                         */
+int trs_wgrad_finish_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
+                                const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                                const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                const int32_t* gb_stride, trs_stream_t stream);
+int trs_wgrad_finish_t_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
+                                  const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                                  const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                  const int32_t* gb_stride, trs_stream_t stream);
 /* n strided 2-D copies in one launch: desc (device, n x 6 int64) = {src address, dst address, rows, cols, src_ld,
  * dst_ld} (sizes in elements of elem_size bytes); max_elems = the largest rows*cols (sizes the grid).  Refreshes the
  * zero-padded copies of an MLP stack's nn.Linear parameters (multilayer_perceptron.py:55-61) before a forward.     */

@@ -256,13 +256,46 @@ static bool rowdot_shape_ok(int C, int dtype) {
 // Finish of the split-K weight gradient: gw[r,c] = sum_s part[s,r,c] for the un-padded (out_rows x out_cols) corner of
 // the (S, R, Cc) fp32 partial products, cast to the parameter dtype; blockIdx.y == gridDim.y-1 also casts the fp32
 // bias gradient.  One launch instead of ATen's sum(0) + strided slice copy + cast (+ slice + cast for the bias).
+// The fp32 source of a cast: a value that arrives summed (nparts == 0), or column c of ``nparts`` partial rows ``pstride``
+// floats apart -- what the tile backward leaves per workgroup (trs_mlp_fused_bwd_data_parts).  The partials are added in
+// the order of mlp_colsum_reduce_many_kernel (mlp_fused.hip): sixteen running sums over p = w, w + 16, ..., then
+// w = 0 .. 15 onto 0.f, so that the value has the bits that launch would have stored.
+// wf_fold: ALL 256 threads of the workgroup cast the columns [c0, c0 + count) of a set, sixteen at a time -- thread
+// (column tid & 15, running sum tid >> 4), the sixteen sums of a column meet in LDS as they do in that kernel.  (One thread
+// per column, 256 dependent loads each, made the finish launch 112 us instead of 21: profiles/deep_bwd_launches.md.)
+template <typename T>
+__device__ __forceinline__ void wf_fold(const float* __restrict__ gbf, int nparts, int pstride, int c0, int count, int limit,
+                                        T* __restrict__ out) {
+  __shared__ float red[16][17];
+  const int cl = threadIdx.x & 15, w = threadIdx.x >> 4;
+  for (int base = c0; base < c0 + count && base < limit; base += 16) {
+    const int c = base + cl;
+    const bool live = c < c0 + count && c < limit;
+    float s = 0.f;
+    if (live) {
+#pragma unroll 4
+      for (int p = w; p < nparts; p += 16) s += gbf[(size_t)p * pstride + c];
+    }
+    red[w][cl] = s;
+    __syncthreads();
+    if (w == 0 && live) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) t += red[k][cl];
+      out[c] = from_f32<T>(t);
+    }
+    __syncthreads();
+  }
+}
+
 template <typename T>
 __device__ __forceinline__ void wgrad_finish_body(const float* __restrict__ part, int S, int R, int Cc, int out_rows,
                                                   int out_cols, T* __restrict__ gw, const float* __restrict__ gbf,
-                                                  T* __restrict__ gb) {
+                                                  T* __restrict__ gb, int nparts = 0, int pstride = 0) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if ((int)blockIdx.y == out_rows) {           // the extra row of workgroups: bias gradient
-    if (gb != nullptr && c < out_rows) gb[c] = from_f32<T>(gbf[c]);
+    if (gb != nullptr && nparts > 0) wf_fold<T>(gbf, nparts, pstride, blockIdx.x * 256, 256, out_rows, gb);
+    else if (gb != nullptr && c < out_rows) gb[c] = from_f32<T>(gbf[c]);
     return;
   }
   if ((int)blockIdx.y > out_rows || c >= out_cols) return;      // (a batched grid is sized by its largest job)
@@ -297,6 +330,7 @@ struct WgradFinishJob {
   const float* gbf;
   void* gb;
   int R, Cc, out_rows, out_cols;
+  int nparts, pstride;      // gbf is a set of partial rows (wf_src); 0, 0: a plain vector
 };
 struct WgradFinishArgs {
   WgradFinishJob job[WF_MAXJ];
@@ -307,10 +341,12 @@ __global__ __launch_bounds__(256) void wgrad_finish_many_kernel(WgradFinishArgs 
   const WgradFinishJob& j = a.job[blockIdx.z];
   if (j.part == nullptr) {      // a job without a product: out_cols fp32 values cast (a gradient that arrives summed)
     const int c = blockIdx.x * 256 + threadIdx.x;
-    if (blockIdx.y == 0 && c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
+    if (j.nparts > 0)      // partial rows: sixteen columns per workgroup of the job's (x, y) plane (the entry sized it)
+      wf_fold<T>(j.gbf, j.nparts, j.pstride, (blockIdx.y * gridDim.x + blockIdx.x) * 16, 16, j.out_cols, (T*)j.gb);
+    else if (blockIdx.y == 0 && c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
     return;
   }
-  wgrad_finish_body<T>(j.part, a.S, j.R, j.Cc, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb);
+  wgrad_finish_body<T>(j.part, a.S, j.R, j.Cc, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb, j.nparts, j.pstride);
 }
 
 // The finish of a layer with FEW output rows and MANY splits (the 400 -> 1 head at 65 536 rows: 256 partial products of
@@ -361,12 +397,13 @@ __global__ __launch_bounds__(256) void wgrad_finish_few_rows_kernel(const float*
 template <typename T>
 __device__ __forceinline__ void wgrad_finish_t_body(const float* __restrict__ part, int S, int Cc, int R, int out_rows,
                                                     int out_cols, T* __restrict__ gw, const float* __restrict__ gbf,
-                                                    T* __restrict__ gb) {
+                                                    T* __restrict__ gb, int nparts = 0, int pstride = 0) {
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
   if ((int)blockIdx.y == (out_cols + 31) / 32) {                // the extra row of workgroups: bias gradient
     const int r = blockIdx.x * 32 + tx;
-    if (gb != nullptr && ty == 0 && r < out_rows) gb[r] = from_f32<T>(gbf[r]);
+    if (gb != nullptr && nparts > 0) wf_fold<T>(gbf, nparts, pstride, blockIdx.x * 32, 32, out_rows, gb);
+    else if (gb != nullptr && ty == 0 && r < out_rows) gb[r] = from_f32<T>(gbf[r]);
     return;
   }
   const int r0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
@@ -413,11 +450,13 @@ __global__ __launch_bounds__(256) void wgrad_finish_t_many_kernel(WgradFinishArg
   const WgradFinishJob& j = a.job[blockIdx.z];
   if (j.part == nullptr) {
     const int c = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
-    if (c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
+    if (j.nparts > 0)      // partial rows: sixteen columns per workgroup of the plane
+      wf_fold<T>(j.gbf, j.nparts, j.pstride, (blockIdx.y * gridDim.x + blockIdx.x) * 16, 16, j.out_cols, (T*)j.gb);
+    else if (c < j.out_cols) ((T*)j.gb)[c] = from_f32<T>(j.gbf[c]);
     return;
   }
   if ((int)blockIdx.x >= (j.out_rows + 31) / 32 || (int)blockIdx.y > (j.out_cols + 31) / 32) return;
-  wgrad_finish_t_body<T>(j.part, a.S, j.Cc, j.R, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb);
+  wgrad_finish_t_body<T>(j.part, a.S, j.Cc, j.R, j.out_rows, j.out_cols, (T*)j.gw, j.gbf, (T*)j.gb, j.nparts, j.pstride);
 }
 
 }  // namespace trs
@@ -787,9 +826,20 @@ extern "C" int trs_wgrad_finish(const float* part, int32_t S, int32_t R, int32_t
   return check_launch("wgrad_finish");
 }
 
-extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
-                                     const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                     void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+// gb_nparts / gb_stride (both NULL in the plain entries): per job, gb_f32[k] is gb_nparts[k] > 0 partial rows gb_stride[k]
+// floats apart instead of a summed vector (wf_src)
+static int wgrad_finish_parts_ok(const char* who, int k, const float* gbf, int cols, const int32_t* gb_nparts,
+                                 const int32_t* gb_stride) {
+  if (gb_nparts == nullptr || gb_nparts[k] == 0) return TRS_OK;
+  TRS_REQUIRE(gbf != nullptr && gb_nparts[k] > 0 && gb_stride[k] >= cols, TRS_EINVAL,
+              "%s: job %d: %d partial rows, %d floats apart, for %d columns", who, k, gb_nparts[k], gb_stride[k], cols);
+  return TRS_OK;
+}
+
+static int wgrad_finish_many_impl(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
+                                  const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                  void* const* gw, const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                  const int32_t* gb_stride, trs_stream_t stream) {
   TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
   TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_many: NULL array");
   TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_many: bad size");
@@ -801,7 +851,9 @@ extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, i
     if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
       TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
                   "wgrad_finish_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
-      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k]};
+      if (int rc = wgrad_finish_parts_ok("wgrad_finish_many", k, gb_f32[k], out_cols[k], gb_nparts, gb_stride)) return rc;
+      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k], gb_nparts ? gb_nparts[k] : 0,
+                                gb_nparts ? gb_stride[k] : 0};
       max_cols = std::max(max_cols, out_cols[k]);
       continue;
     }
@@ -811,16 +863,41 @@ extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, i
     TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_many: gb and gb_f32 go together (job %d)", k);
     TRS_REQUIRE(gb[k] == nullptr || out_rows[k] <= ((out_cols[k] + 255) / 256) * 256, TRS_ESHAPE,
                 "wgrad_finish_many: out_rows %d exceeds the bias row of workgroups", out_rows[k]);
-    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k]};
+    if (int rc = wgrad_finish_parts_ok("wgrad_finish_many", k, gb_f32[k], out_rows[k], gb_nparts, gb_stride)) return rc;
+    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k],
+                              gb_nparts ? gb_nparts[k] : 0, gb_nparts ? gb_stride[k] : 0};
     max_rows = std::max(max_rows, out_rows[k]);
     max_cols = std::max(max_cols, out_cols[k]);
   }
+  for (int k = 0; k < n_jobs; ++k)      // a cast-only job on partial rows: 16 columns per workgroup of the (x, y) plane
+    if (part[k] == nullptr && a.job[k].nparts > 0) {
+      const int gx = (max_cols + 255) / 256, need = (out_cols[k] + 15) / 16;
+      if (gx * (max_rows + 1) < need) max_rows = (need + gx - 1) / gx - 1;
+    }
   dim3 grid((max_cols + 255) / 256, max_rows + 1, n_jobs);
   if (dtype == TRS_F32)
     hipLaunchKernelGGL((wgrad_finish_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((wgrad_finish_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("wgrad_finish_many");
+}
+
+extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
+                                     const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                     void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+  return wgrad_finish_many_impl(n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32, gb, nullptr, nullptr, stream);
+}
+
+/* trs_wgrad_finish_many whose fp32 source per job may be a set of per-workgroup partial rows (gb_nparts[k] > 0 rows,
+ * gb_stride[k] floats apart; 0: a summed vector as ever): the partials trs_mlp_fused_bwd_data_parts reports, added in the
+ * order of that backward's own reduce launch, so that every cast value keeps its bits */
+extern "C" int trs_wgrad_finish_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
+                                           const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols,
+                                           int32_t dtype, void* const* gw, const float* const* gb_f32, void* const* gb,
+                                           const int32_t* gb_nparts, const int32_t* gb_stride, trs_stream_t stream) {
+  TRS_REQUIRE(gb_nparts && gb_stride, TRS_EINVAL, "wgrad_finish_many_parts: NULL array");
+  return wgrad_finish_many_impl(n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32, gb, gb_nparts, gb_stride,
+                                stream);
 }
 
 extern "C" int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int32_t out_rows, int32_t out_cols,
@@ -841,9 +918,10 @@ extern "C" int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int3
   return check_launch("wgrad_finish_t");
 }
 
-extern "C" int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
-                                       const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                       void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+static int wgrad_finish_t_many_impl(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
+                                    const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                    void* const* gw, const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                    const int32_t* gb_stride, trs_stream_t stream) {
   TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_t_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
   TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_t_many: NULL array");
   TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_t_many: bad size");
@@ -855,25 +933,49 @@ extern "C" int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part,
     if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
       TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
                   "wgrad_finish_t_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
-      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k]};
+      if (int rc = wgrad_finish_parts_ok("wgrad_finish_t_many", k, gb_f32[k], out_cols[k], gb_nparts, gb_stride)) return rc;
+      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k], gb_nparts ? gb_nparts[k] : 0,
+                                gb_nparts ? gb_stride[k] : 0};
       continue;
     }
     TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
                 TRS_EINVAL, "wgrad_finish_t_many: bad size (job %d)", k);
     TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_t_many: NULL pointer (job %d)", k);
     TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_t_many: gb and gb_f32 go together (job %d)", k);
-    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k]};
+    if (int rc = wgrad_finish_parts_ok("wgrad_finish_t_many", k, gb_f32[k], out_rows[k], gb_nparts, gb_stride)) return rc;
+    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k],
+                              gb_nparts ? gb_nparts[k] : 0, gb_nparts ? gb_stride[k] : 0};
     gx = std::max(gx, (out_rows[k] + 31) / 32);
     gy = std::max(gy, (out_cols[k] + 31) / 32 + 1);
   }
   for (int k = 0; k < n_jobs; ++k)      // a cast-only job's columns, 256 per workgroup of the (gx, gy) plane
-    if (part[k] == nullptr && (out_cols[k] + 255) / 256 > gx * gy) gx = ((out_cols[k] + 255) / 256 + gy - 1) / gy;
+    if (part[k] == nullptr) {         // (on partial rows: 16 per workgroup)
+      const int need = a.job[k].nparts > 0 ? (out_cols[k] + 15) / 16 : (out_cols[k] + 255) / 256;
+      if (need > gx * gy) gx = (need + gy - 1) / gy;
+    }
   dim3 grid(gx, gy, n_jobs);
   if (dtype == TRS_F32)
     hipLaunchKernelGGL((wgrad_finish_t_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL((wgrad_finish_t_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("wgrad_finish_t_many");
+}
+
+extern "C" int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
+                                       const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
+                                       void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
+  return wgrad_finish_t_many_impl(n_jobs, part, S, Cc, R, out_rows, out_cols, dtype, gw, gb_f32, gb, nullptr, nullptr,
+                                  stream);
+}
+
+/* trs_wgrad_finish_t_many with partial-row sources, as trs_wgrad_finish_many_parts */
+extern "C" int trs_wgrad_finish_t_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
+                                             const int32_t* R, const int32_t* out_rows, const int32_t* out_cols,
+                                             int32_t dtype, void* const* gw, const float* const* gb_f32, void* const* gb,
+                                             const int32_t* gb_nparts, const int32_t* gb_stride, trs_stream_t stream) {
+  TRS_REQUIRE(gb_nparts && gb_stride, TRS_EINVAL, "wgrad_finish_t_many_parts: NULL array");
+  return wgrad_finish_t_many_impl(n_jobs, part, S, Cc, R, out_rows, out_cols, dtype, gw, gb_f32, gb, gb_nparts, gb_stride,
+                                  stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1063,6 +1063,12 @@ struct MlpWlast {
   float* part;      // [grid][live][pad32(widths[L-1])]
   float* gw;        // [live][pad32(widths[L-1])] fp32, written
 };
+// the form of the backward that leaves the reduce launch out (trs_mlp_fused_bwd_data_parts), null: today's
+struct MlpBwdForm {
+  const float** part;      // out, [L + 1 + MF_MAXLIVE]: layer l's bias partials at [l], the input's at [L], dW row j at [L+1+j]
+  int32_t* stride;         // out, same order: floats between the partials of one set
+  int32_t* nparts;         // out: partials per set (the backward's grid)
+};
 static size_t mlp_bwd_lds(int L, const int32_t* widths, int live) {
   return (size_t)MF_ROWS * mlp_act_str(L, widths) + 8 * 512 * 4 + (size_t)(L + 1 + live) * 512 * 4;
 }
@@ -1072,11 +1078,12 @@ static int mlp_bwd_grid(int64_t rows) { return (int)std::min<int64_t>((rows + MF
 static int mlp_fused_bwd_impl(const void* gy, int64_t rows, int32_t num_layers, const int32_t* widths,
                               const void* const* weights, const void* const* masks, void* const* gz,
                               float* const* gbias, void* gx, const void* mask_in, float* gbias_in, int32_t dtype,
-                              int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream, const MlpWlast* wl) {
+                              int32_t family, void* workspace, size_t ws_bytes, trs_stream_t stream, const MlpWlast* wl,
+                              const MlpBwdForm* form = nullptr) {
   hipStream_t s = (hipStream_t)stream;
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "mlp_fused_bwd_data: bf16 only");
   TRS_REQUIRE(trs_mlp_fused_supported(num_layers, widths), TRS_ESHAPE, "mlp_fused_bwd_data: unsupported layer widths");
-  TRS_REQUIRE(weights && workspace && gy && masks && gz && gbias, TRS_EINVAL, "mlp_fused_bwd_data: NULL pointer");
+  TRS_REQUIRE(weights && workspace && gy && masks && gz && (gbias || form), TRS_EINVAL, "mlp_fused_bwd_data: NULL pointer");
   TRS_REQUIRE(ws_bytes >= trs_mlp_fused_workspace_bytes(num_layers, widths), TRS_EWORKSPACE,
               "mlp_fused_bwd_data: workspace too small");
   const int L = num_layers;
@@ -1096,7 +1103,11 @@ static int mlp_fused_bwd_impl(const void* gy, int64_t rows, int32_t num_layers, 
   TRS_REQUIRE(fam_ok, TRS_EINVAL,
               "mlp_fused_bwd_data: family must be the TILE / ROW_OWNER / MIXED value the forward ran under (got %d)", family);
   TRS_REQUIRE(family != TRS_MLP_FAMILY_ROW_OWNER || gx != nullptr, TRS_EINVAL, "mlp_fused_bwd_data: the row-owner kernels need gx");
-  TRS_REQUIRE((mask_in == nullptr) == (gbias_in == nullptr) && (mask_in == nullptr || (L + 1 <= MF_MAXL && gx != nullptr)),
+  TRS_REQUIRE(form == nullptr || (rows > 0 && family != TRS_MLP_FAMILY_ROW_OWNER), TRS_EINVAL,
+              "mlp_fused_bwd_data_parts: the tile backward on at least one row only (family %d, %lld rows)", family, (long long)rows);
+  // (the partial form has no gbias_in: mask_in alone asks for the input's column sums)
+  TRS_REQUIRE((form != nullptr || (mask_in == nullptr) == (gbias_in == nullptr)) &&
+                  (mask_in == nullptr || (L + 1 <= MF_MAXL && gx != nullptr)),
               TRS_EINVAL, "mlp_fused_bwd_data: mask_in and gbias_in come together (and with gx, at most %d layers)", MF_MAXL - 1);
   if (rows == 0) {
     for (int l = 0; l < L; ++l)
@@ -1173,6 +1184,22 @@ static int mlp_fused_bwd_impl(const void* gy, int64_t rows, int32_t num_layers, 
   auto* kern = a.ro_masks ? (wl ? mlp_fused_bwd_wlast_kernel<true> : mlp_fused_bwd_kernel<true>)
                           : (wl ? mlp_fused_bwd_wlast_kernel<false> : mlp_fused_bwd_kernel<false>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * MF_WAVES), lds, s, a);
+  if (form != nullptr) {      // no reduce launch: the caller's finish folds the partials (same sets, same strides)
+    for (int sidx = 0; sidx < L; ++sidx) {
+      const int l = L - 1 - sidx;
+      form->part[l] = a.step[sidx].colsum;
+      form->stride[l] = a.step[sidx].K;
+    }
+    form->part[L] = a.colsum_in;
+    form->stride[L] = a.colsum_in != nullptr ? pad32(widths[0]) : 0;
+    for (int j = 0; j < MF_MAXLIVE; ++j) {
+      const int Kh = pad32(widths[L - 1]);
+      form->part[L + 1 + j] = j < a.live ? wl->part + (size_t)j * Kh : nullptr;
+      form->stride[L + 1 + j] = j < a.live ? a.live * Kh : 0;
+    }
+    *form->nparts = grid;
+    return check_launch("mlp_fused_bwd_data_parts");
+  }
   MlpColsumArgs cs;
   cs.nparts = grid;
   int kmax = 0;
@@ -1299,4 +1326,68 @@ extern "C" int trs_rows_gemm(const void* x, int64_t rows, int32_t x_stride, cons
   const int64_t ntiles = (rows + MF_ROWS - 1) / MF_ROWS;
   hipLaunchKernelGGL(mlp_rows_gemm_kernel, dim3((int)std::min<int64_t>(ntiles, MF_GRID)), dim3(64 * MF_WAVES), lds, s, a);
   return check_launch("rows_gemm");
+}
+
+/* The tile backward without its reduce launch.  Operands as trs_mlp_fused_bwd_data_wlast (h_last == NULL: the output
+ * layer's weight gradient is not carried; live, wl_part are then unused and gy_stride is widths[L]); no gbias, gbias_in,
+ * gw_last: instead part_out / stride_out [num_layers + 4] and *nparts_out say where the per-workgroup partial rows lie in
+ * ``workspace`` / ``wl_part`` -- set l (0 .. L-1): layer l's bias gradient, pad32(widths[l+1]) columns; set L: the input's
+ * (with mask_in, else NULL); set L+1+j: row j of the output layer's dW, pad32(widths[L-1]) columns (NULL from ``live`` on).
+ * Value c of a set is the sum over p < nparts of part[p * stride + c], taken as mlp_colsum_reduce_many_kernel takes it
+ * (trs_wgrad_finish_many_parts / trs_wgrad_finish_t_many_parts do): the buffers must stay allocated until that launch is
+ * enqueued.  TILE and MIXED families, rows > 0. */
+extern "C" int trs_mlp_fused_bwd_data_parts(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
+                                            const int32_t* widths, const void* const* weights, const void* const* masks,
+                                            void* const* gz, void* gx, const void* mask_in, const void* h_last,
+                                            int32_t h_stride, int32_t live, float* wl_part, size_t wl_part_bytes,
+                                            const float** part_out, int32_t* stride_out, int32_t* nparts_out,
+                                            int32_t dtype, int32_t family, void* workspace, size_t ws_bytes,
+                                            trs_stream_t stream) {
+  const char* who = "mlp_fused_bwd_data_parts";
+  TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "%s: bf16 only", who);
+  TRS_REQUIRE(widths && num_layers >= 1 && num_layers <= MF_MAXL, TRS_EINVAL, "%s: bad stack", who);
+  TRS_REQUIRE(part_out && stride_out && nparts_out, TRS_EINVAL, "%s: NULL result array", who);
+  TRS_REQUIRE(rows > 0, TRS_EINVAL, "%s: no rows, no partials (trs_mlp_fused_bwd_data zero-fills)", who);
+  TRS_REQUIRE(family == TRS_MLP_FAMILY_TILE || family == TRS_MLP_FAMILY_MIXED, TRS_EINVAL,
+              "%s: the tile backward only (family %d)", who, family);
+  MlpWlast wl{nullptr, 0, 0, 0, nullptr, nullptr};
+  if (h_last != nullptr) {
+    TRS_REQUIRE(wl_part, TRS_EINVAL, "%s: NULL pointer", who);
+    const size_t need = trs_mlp_fused_bwd_wlast_part_bytes(num_layers, widths, rows, dtype, family, live);
+    TRS_REQUIRE(need > 0, TRS_ESHAPE, "%s: the output layer's dW is not carried for this stack / family %d / %d live columns",
+                who, family, live);
+    TRS_REQUIRE(wl_part_bytes >= need, TRS_EWORKSPACE, "%s: partial buffer too small", who);
+    TRS_REQUIRE(gy_stride == widths[num_layers] || (gy_stride == live && live < 8), TRS_ESHAPE,
+                "%s: gy_stride %d (widths[L] = %d, or the %d live columns alone)", who, gy_stride, widths[num_layers], live);
+    TRS_REQUIRE(h_stride >= pad32(widths[num_layers - 1]) && h_stride % 8 == 0, TRS_ESHAPE, "%s: h_stride %d", who, h_stride);
+    TRS_REQUIRE(aligned16(h_last) && aligned16(wl_part), TRS_EALIGN, "%s: 16-byte alignment", who);
+    wl = MlpWlast{h_last, h_stride, live, gy_stride, wl_part, nullptr};
+  } else {
+    TRS_REQUIRE(gy_stride == widths[num_layers], TRS_ESHAPE, "%s: gy_stride %d (widths[L] = %d)", who, gy_stride,
+                widths[num_layers]);
+  }
+  const MlpBwdForm form{part_out, stride_out, nparts_out};
+  return mlp_fused_bwd_impl(gy, rows, num_layers, widths, weights, masks, gz, nullptr, gx, mask_in, nullptr, dtype, family,
+                            workspace, ws_bytes, stream, h_last != nullptr ? &wl : nullptr, &form);
+}
+
+/* out[k][c] = sum over the nparts partials of set k, c < n[k]: the reduce launch of trs_mlp_fused_bwd_data on the sets
+ * trs_mlp_fused_bwd_data_parts reported, for a caller that has no finish launch to fold them in */
+extern "C" int trs_colsum_parts_reduce(int32_t n_sets, const float* const* part, const int32_t* stride, const int32_t* n,
+                                       int32_t nparts, float* const* out, trs_stream_t stream) {
+  TRS_REQUIRE(n_sets >= 1 && n_sets <= MF_MAXL && part && stride && n && out && nparts > 0, TRS_EINVAL,
+              "colsum_parts_reduce: %d sets (1 .. %d) of %d partials", n_sets, MF_MAXL, nparts);
+  MlpColsumArgs cs;
+  cs.nparts = nparts;
+  int kmax = 0;
+  for (int k = 0; k < n_sets; ++k) {
+    TRS_REQUIRE(part[k] && out[k] && n[k] > 0 && stride[k] >= n[k], TRS_EINVAL, "colsum_parts_reduce: bad set %d", k);
+    cs.part[k] = part[k];
+    cs.out[k] = out[k];
+    cs.n[k] = n[k];
+    cs.stride[k] = stride[k];
+    kmax = std::max(kmax, n[k]);
+  }
+  hipLaunchKernelGGL(mlp_colsum_reduce_many_kernel, dim3((kmax + 63) / 64, n_sets), dim3(1024), 0, (hipStream_t)stream, cs);
+  return check_launch("colsum_parts_reduce");
 }

@@ -968,8 +968,10 @@ __global__ __launch_bounds__(256) void scatter_long_rows_finish_kernel(
 // 4*E-byte fp32 fm_sum row at two random addresses).
 template <typename T>
 __global__ __launch_bounds__(256) void build_tg_kernel(const uint4* __restrict__ g_fm, const float* __restrict__ fm_sum,
-                                                       uint4* __restrict__ tg, int64_t B, int L) {
+                                                       uint4* __restrict__ tg, int64_t B, int L,
+                                                       int32_t* __restrict__ zero_a, int32_t* __restrict__ zero_b) {
   constexpr int VE = Vec16<T>::VE;
+  if (zero_a != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { *zero_a = 0; *zero_b = 0; }      // see WalkJob::zero_in_build
   const int64_t total = B * L, stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
     const int64_t b = t / L;
@@ -988,8 +990,10 @@ __global__ __launch_bounds__(256) void build_tg_kernel(const uint4* __restrict__
 // g_fm constant along E: T[b] = g[b] * fm_sum[b,:] (L vectors per sample) and gvec[b] = g[b] in every element of one vector
 template <typename T>
 __global__ __launch_bounds__(256) void build_tg1_kernel(const T* __restrict__ g1, const float* __restrict__ fm_sum,
-                                                        uint4* __restrict__ tg, uint4* __restrict__ gvec, int64_t B, int L) {
+                                                        uint4* __restrict__ tg, uint4* __restrict__ gvec, int64_t B, int L,
+                                                        int32_t* __restrict__ zero_a, int32_t* __restrict__ zero_b) {
   constexpr int VE = Vec16<T>::VE;
+  if (zero_a != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { *zero_a = 0; *zero_b = 0; }      // see WalkJob::zero_in_build
   const int64_t total = B * L, stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
     const int64_t b = t / L;
@@ -1188,6 +1192,14 @@ struct WalkJob {
   void* grad_first = nullptr;
   // workspace regions: queue(s) of hot rows, staged FM rows, chunk partials
   int32_t* long_rows = nullptr;
+  // The two queue counters (long_rows[0] and the element path's split-row counter) are zeroed in front of the walk.  Where
+  // the walk stages its FM rows first (build_tg1_kernel / build_tg_kernel), one thread of THAT launch writes the zeros and
+  // zero_two_i32_kernel is not launched: the build is the first launch of the walk on ``s``, and every kernel that adds to
+  // long_rows[0] (scatter_rows_group_kernel, scatter_rows_fm1_kernel) or reads it (scatter_long_rows_kernel, its finish,
+  // scatter_first_long_kernel) is enqueued behind it on the same stream, whatever the sink -- the sink is an argument of
+  // those kernels, not another stream or launch order.
+  bool zero_in_build = false;
+  int32_t* split_count = nullptr;      // the second counter (scatter_rows_impl)
   void* tg = nullptr;
   float* scratch = nullptr;
   RowSink sink = GRAD_SINK;
@@ -1203,16 +1215,17 @@ static void scatter_group_launch(const WalkJob& j) {
   bool scal = false;
   const void* fm = j.g_fm;       // the FM operand the walk reads: the staged [g*S | g] rows when the FM term is folded in
   if (j.g_fm != nullptr && j.fm_sum != nullptr) {
+    int32_t* zero_a = j.zero_in_build ? j.long_rows : nullptr;
     if (j.g_fm_cols == 1) {      // (L == 1 too: a (B,1) buffer must never be read as B 16-byte rows)
       uint4* gvec = (uint4*)j.tg + j.B * L;
       hipLaunchKernelGGL((build_tg1_kernel<T>), dim3(stream_grid(j.B * L, 256, 4096)), dim3(256), 0, s,
-                         (const T*)j.g_fm, j.fm_sum, (uint4*)j.tg, gvec, j.B, L);
+                         (const T*)j.g_fm, j.fm_sum, (uint4*)j.tg, gvec, j.B, L, zero_a, j.split_count);
       fs = FmSrc{(const uint4*)j.tg, gvec, L, 1};
       fs.g1 = j.g_fm;
       scal = j.g_first == nullptr;
     } else {
       hipLaunchKernelGGL((build_tg_kernel<T>), dim3(stream_grid(j.B * L, 256, 4096)), dim3(256), 0, s,
-                         (const uint4*)j.g_fm, j.fm_sum, (uint4*)j.tg, j.B, L);
+                         (const uint4*)j.g_fm, j.fm_sum, (uint4*)j.tg, j.B, L, zero_a, j.split_count);
       fs = FmSrc{(const uint4*)j.tg, (const uint4*)j.tg + L, 2 * L, 2 * L};
     }
     fm = j.tg;
@@ -1503,9 +1516,11 @@ static int scatter_rows_impl(WalkJob j, int64_t BN, int32_t dtype, void* workspa
   j.long_rows = (int32_t*)workspace;
   j.tg = (char*)workspace + long_row_queue_bytes(BN);
   j.scratch = (float*)((char*)j.tg + align_up((size_t)j.B * 2 * j.E * dtype_size(dtype), 256));
-  // the counters of the hot-row queue and (element path) of the split-row queue behind it
-  hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, j.s, j.long_rows,
-                     j.long_rows + 1 + (BN / LONG_ROW_ELEM + 2));
+  // the counters of the hot-row queue and (element path) of the split-row queue behind it: by the launch that stages
+  // the FM rows where the vector walk has one in front (scatter_group_launch), by a launch of their own everywhere else
+  j.split_count = j.long_rows + 1 + (BN / LONG_ROW_ELEM + 2);
+  j.zero_in_build = lg >= 0 && j.g_fm != nullptr && j.fm_sum != nullptr;
+  if (!j.zero_in_build) hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, j.s, j.long_rows, j.split_count);
   return dtype == TRS_F32 ? scatter_launch<float>(j, lg) : scatter_launch<bf16_t>(j, lg);
 }
 

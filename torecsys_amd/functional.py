@@ -3477,24 +3477,30 @@ def mlp_bwd_wlast_bytes(widths: Sequence[int], rows: int, family: int, live: int
 
 def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequence[torch.Tensor],
                            masks: Sequence[torch.Tensor], mask_in: Optional[torch.Tensor] = None, *, family: int,
-                           h_last: Optional[torch.Tensor] = None, live: int = 0):
+                           h_last: Optional[torch.Tensor] = None, live: int = 0, parts: bool = False):
     """trs_mlp_fused_bwd_data: (gx, gz [d(pre-activation) of the hidden layers], gb [fp32 bias gradients, padded]) and,
     with ``mask_in``, gb_in: gx is then masked by the upstream ReLU and gb_in holds its column sums.  ``family``: what
     fused_mlp_forward_raw returned with these masks.
     With ``h_last`` (the last hidden activation) and ``live`` (the output layer's real columns) the kernel also sums the
     output layer's weight gradient (trs_mlp_fused_bwd_data_wlast; the caller asked mlp_bwd_wlast_bytes first): a fifth
-    result, (live, pad32(widths[L-1])) fp32.  gy2 is then (rows, widths[L]) or the contiguous (rows, live) gradient."""
+    result, (live, pad32(widths[L-1])) fp32.  gy2 is then (rows, widths[L]) or the contiguous (rows, live) gradient.
+    With ``parts`` (trs_mlp_fused_bwd_data_parts: tile and mixed family, rows > 0) the reduce launch behind the kernel is
+    left out and every fp32 result is the set of per-workgroup partial rows instead, a strided view of the call's
+    workspace that keeps it alive: gb[l] and gb_in (nparts, padded width), gw_last (nparts, live, padded width).
+    _tail_grads folds such sets in its batched finish; colsum_parts_reduce sums them on its own."""
     if family not in (MLP_FAMILY_TILE, MLP_FAMILY_ROW_OWNER, MLP_FAMILY_MIXED):
         raise ValueError("fused_mlp_backward_raw: family must be the value the forward returned with these masks")
     L = len(Ws)
     rows, dev = gy2.shape[0], gy2.device
     gz = [torch.empty(rows, _pad32(widths[l + 1]), dtype=torch.bfloat16, device=dev) for l in range(L - 1)]
-    gb = [torch.empty(_pad32(widths[l + 1]), dtype=torch.float32, device=dev) for l in range(L)]
     gx = torch.empty(rows, widths[0], dtype=torch.bfloat16, device=dev)   # the kernel always writes dL/dx (its last GEMM)
-    gb_in = torch.empty(_pad32(widths[0]), dtype=torch.float32, device=dev) if mask_in is not None else None
     wl = _i32_array(widths)
     ws_bytes = size_query("trs_mlp_fused_workspace_bytes", L, wl)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if parts:
+        return _fused_mlp_backward_parts(gy2, widths, Ws, masks, mask_in, family, h_last, live, gz, gx, wl, ws)
+    gb = [torch.empty(_pad32(widths[l + 1]), dtype=torch.float32, device=dev) for l in range(L)]
+    gb_in = torch.empty(_pad32(widths[0]), dtype=torch.float32, device=dev) if mask_in is not None else None
     if h_last is not None:
         if not (gy2.is_contiguous() and h_last.is_contiguous() and h_last.shape[0] == rows):
             raise ValueError("fused_mlp_backward_raw: gy2 / h_last must be contiguous over the same rows")
@@ -3508,6 +3514,64 @@ def fused_mlp_backward_raw(gy2: torch.Tensor, widths: Sequence[int], Ws: Sequenc
     call("trs_mlp_fused_bwd_data", ptr(gy2), rows, L, wl, _ptr_array(Ws), _ptr_array(masks), _ptr_array(gz),
          _ptr_array(gb), ptr(gx), ptr(mask_in), ptr(gb_in), _abi.TRS_BF16, int(family), ptr(ws), ws_bytes, stream_ptr())
     return gx, gz, gb, gb_in
+
+
+def _fused_mlp_backward_parts(gy2, widths, Ws, masks, mask_in, family, h_last, live, gz, gx, wl, ws):
+    """the ``parts`` form of fused_mlp_backward_raw: the entry reports addresses, the results are views of the buffers"""
+    L, rows, dev = len(Ws), gy2.shape[0], gy2.device
+    part, part_bytes = None, 0
+    if h_last is not None:
+        if not (gy2.is_contiguous() and h_last.is_contiguous() and h_last.shape[0] == rows):
+            raise ValueError("fused_mlp_backward_raw: gy2 / h_last must be contiguous over the same rows")
+        part_bytes = mlp_bwd_wlast_bytes(widths, max(rows, 1), family, live)
+        part = torch.empty(max(part_bytes, 16), dtype=torch.uint8, device=dev)
+    n = L + 4
+    where, stride, nparts = (ctypes.c_void_p * n)(), (ctypes.c_int32 * n)(), ctypes.c_int32(0)
+    call("trs_mlp_fused_bwd_data_parts", ptr(gy2), gy2.shape[1], rows, L, wl, _ptr_array(Ws), _ptr_array(masks),
+         _ptr_array(gz), ptr(gx), ptr(mask_in), ptr(h_last), h_last.shape[1] if h_last is not None else 0, int(live),
+         ptr(part), part_bytes, where, stride, ctypes.byref(nparts),
+         _abi.TRS_BF16, int(family), ptr(ws), ws.numel(), stream_ptr())
+    P = int(nparts.value)
+
+    def view(base, k, shape, strides):
+        f32 = base.view(torch.float32)
+        off = (int(where[k] or 0) - base.data_ptr()) // 4
+        last = off + sum((s - 1) * st for s, st in zip(shape, strides))
+        if not (where[k] and 0 <= off and last < f32.numel()):
+            raise RuntimeError("fused_mlp_backward_raw: a partial set lies outside its buffer")
+        return torch.as_strided(f32, shape, strides, off)
+
+    gb = [view(ws, l, (P, _pad32(widths[l + 1])), (int(stride[l]), 1)) for l in range(L)]
+    gb_in = view(ws, L, (P, _pad32(widths[0])), (int(stride[L]), 1)) if mask_in is not None else None
+    out = [gx, gz, gb, gb_in]
+    if h_last is not None:
+        Kh = _pad32(widths[L - 1])
+        out.append(view(part, L + 1, (P, live, Kh), (int(stride[L + 1]), Kh, 1)))
+    return tuple(out)
+
+
+def colsum_parts_reduce(sets: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """The sums of 1 .. 8 partial sets (fp32 (nparts, n), rows a stride apart: fused_mlp_backward_raw with ``parts``) in
+    one launch of the tile backward's own reduce kernel: the vectors trs_mlp_fused_bwd_data would have written."""
+    outs = [torch.empty(t.shape[1], dtype=torch.float32, device=t.device) for t in sets]
+    if len({t.shape[0] for t in sets}) != 1 or any(t.dim() != 2 or t.stride(1) != 1 for t in sets):
+        raise ValueError("colsum_parts_reduce: sets of one launch share their partial count")
+    call("trs_colsum_parts_reduce", len(sets), _ptr_array(sets), _i32_array([t.stride(0) for t in sets]),
+         _i32_array([t.shape[1] for t in sets]), int(sets[0].shape[0]), _ptr_array(outs), stream_ptr())
+    return outs
+
+
+def _plain_sum(t):
+    """a bias gradient as a summed vector: itself, or the sum of its partial rows"""
+    return colsum_parts_reduce([t])[0] if t is not None and t.dim() == 2 else t
+
+
+def _parts_arrays(srcs):
+    """(gb_nparts, gb_stride) of the ``*_parts`` finishes for fp32 sources that are vectors or partial sets; None: all plain"""
+    if not any(t is not None and t.dim() == 2 for t in srcs):
+        return None
+    return (_i32_array([t.shape[0] if t is not None and t.dim() == 2 else 0 for t in srcs]),
+            _i32_array([t.stride(0) if t is not None and t.dim() == 2 else 0 for t in srcs]))
 
 
 class _FusedMLP(Function):
@@ -3650,6 +3714,18 @@ def _wgrad_deep_splits(jobs) -> int:
                       _i32_array([j[1].shape[1] for j in jobs]), int(jobs[0][0].shape[0]))
 
 
+def wgrad_deep_splits_for(rows: int, dims) -> int:
+    """_wgrad_deep_splits from shapes alone, for a backward that chooses its form before the gradients exist: ``dims`` =
+    [(in_f, ldx, out_f, ldg)] of contiguous bf16 operands over ``rows`` rows, the wide first layer in front"""
+    if not WGRAD_ROWS or not 2 <= len(dims) <= 4 or rows < DEEP_WGRAD_MIN_ROWS:
+        return 0
+    M_x, N_g = [(d[0] + 207) // 208 * 208 for d in dims], [(d[2] + 15) // 16 * 16 for d in dims]
+    if any(m > d[1] or n > d[3] for m, n, d in zip(M_x, N_g, dims)):
+        return 0
+    return size_query("trs_wgrad_wide_many_splits", len(dims), _i32_array(M_x), _i32_array([d[1] for d in dims]),
+                      _i32_array(N_g), _i32_array([d[3] for d in dims]), int(rows))
+
+
 def _wgrad_deep(jobs, S, casts):
     """the merged product and its finish; ``casts`` ride as jobs without a product.  Returns [(dW, db or None)] per job."""
     dev, rows = jobs[0][0].device, int(jobs[0][0].shape[0])
@@ -3660,11 +3736,14 @@ def _wgrad_deep(jobs, S, casts):
     gws = [torch.empty(j[4], j[5], dtype=torch.bfloat16, device=dev) for j in jobs]
     gbs = [torch.empty(j[4], dtype=torch.bfloat16, device=dev) if j[6] is not None else None for j in jobs]
     n = len(casts)
-    call("trs_wgrad_finish_t_many", len(jobs) + n, _ptr_array(parts + [None] * n), S,
+    srcs = [j[6] for j in jobs] + [c[1] for c in casts]
+    sets = _parts_arrays(srcs)      # fp32 sources that are partial rows of the fused backward: the finish folds them
+    call("trs_wgrad_finish_t_many" if sets is None else "trs_wgrad_finish_t_many_parts", len(jobs) + n,
+         _ptr_array(parts + [None] * n), S,
          _i32_array([j[2] for j in jobs] + [0] * n), _i32_array([j[3] for j in jobs] + [0] * n),
          _i32_array([j[4] for j in jobs] + [0] * n), _i32_array([j[5] for j in jobs] + [c[0] for c in casts]),
-         _abi.TRS_BF16, _ptr_array(gws + [None] * n), _ptr_array([j[6] for j in jobs] + [c[1] for c in casts]),
-         _ptr_array(gbs + [c[2] for c in casts]), stream_ptr())
+         _abi.TRS_BF16, _ptr_array(gws + [None] * n), _ptr_array(srcs),
+         _ptr_array(gbs + [c[2] for c in casts]), *(sets or ()), stream_ptr())
     return list(zip(gws, gbs))
 
 
@@ -3692,14 +3771,21 @@ def _tail_grads(layers, gw_last=None, first=None):
         _, _, out_f, in_f, dt, gb_f32, _, need_b = layers[-1]
         gw = torch.empty(out_f, in_f, dtype=dt, device=gw_last.device)
         gbias = torch.empty(out_f, dtype=dt, device=gw_last.device) if need_b else None
-        casts = [(in_f, gw_last[r], gw[r]) for r in range(out_f)] + ([(out_f, gb_f32, gbias)] if need_b else [])
+        # (gw_last as partial rows, (nparts, out_f, padded in_f): row r's set is gw_last[:, r])
+        casts = [(in_f, gw_last[r] if gw_last.dim() == 2 else gw_last[:, r], gw[r]) for r in range(out_f)] + \
+                ([(out_f, gb_f32, gbias)] if need_b else [])
         out[-1] = (gw, gbias)
 
+    # Any fp32 bias gradient (and gw_last) may be a set of partial rows (fused_mlp_backward_raw with ``parts``): the
+    # batched finishes fold such a set themselves; whatever does not end in one is summed by colsum_parts_reduce first.
     def finish(parts, S, R, Cc, orows, ocols, gws, gbfs, gbs, dtype_code, extra):
         n = len(extra)
-        call("trs_wgrad_finish_many", len(parts) + n, _ptr_array(parts + [None] * n), S, _i32_array(R + [0] * n),
+        srcs = gbfs + [c[1] for c in extra]
+        sets = _parts_arrays(srcs)
+        call("trs_wgrad_finish_many" if sets is None else "trs_wgrad_finish_many_parts", len(parts) + n,
+             _ptr_array(parts + [None] * n), S, _i32_array(R + [0] * n),
              _i32_array(Cc + [0] * n), _i32_array(orows + [0] * n), _i32_array(ocols + [c[0] for c in extra]), dtype_code,
-             _ptr_array(gws + [None] * n), _ptr_array(gbfs + [c[1] for c in extra]), _ptr_array(gbs + [c[2] for c in extra]),
+             _ptr_array(gws + [None] * n), _ptr_array(srcs), _ptr_array(gbs + [c[2] for c in extra]), *(sets or ()),
              stream_ptr())
 
     first_out = None
@@ -3731,13 +3817,13 @@ def _tail_grads(layers, gw_last=None, first=None):
         for n, k in enumerate(batch):
             gb = gbs[n]
             if gb is None and layers[k][7]:
-                gb = layers[k][5][:layers[k][2]].to(dtype)
+                gb = _plain_sum(layers[k][5])[:layers[k][2]].to(dtype)
             out[k] = (gws[n], gb)
     if casts:      # no batched finish to ride in: a launch of their own
         finish([], 1, [], [], [], [], [], [], [], value_dtype_code(casts[0][2]), casts)
     for k, t in enumerate(layers):
         if out[k] is None:
-            out[k] = _tail_layer_grads(*t)
+            out[k] = _tail_layer_grads(*t[:5], _plain_sum(t[5]) if t[7] else None, *t[6:])
     return out if first is None else out + [first_out]
 
 

@@ -855,7 +855,8 @@ def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b
         # wide input, short contraction (2496 <- 400): our own kernel, K not padded to the library's tile
         gx = F_.rows_gemm(g2, W, out_f, xin.shape[1])
     elif need_x:
-        gx = g2 @ W
+        # (a gradient narrower than the padded weight: its live columns against the weight's live rows)
+        gx = g2 @ W if g2.shape[1] == W.shape[0] else g2[:, :out_f] @ W[:out_f]
     return gx, gw_out, gb_out
 
 
@@ -886,8 +887,12 @@ class _HybridMLP(torch.autograd.Function):
         else:
             y, hidden, masks, mask_in, fam = F_.fused_mlp_forward_raw(h1, Ws, bs, input_mask=True)
         out_f = tail[4 * (L - 1)].shape[0]
+        if w_narrow is not None:
+            # the backward runs at the forward's width too: its input gradient g1 and the bias sums come out h_n wide, and
+            # every reader takes g1's live columns by stride (the columns it drops met zero weights and were zeros)
+            Ws = [w_narrow] + Ws[1:]
         ctx.save_for_backward(cur, W1, h1, mask_in, *Ws, *hidden, *masks)
-        ctx.meta = (L, [h1.shape[1]] + [w.shape[0] for w in Ws], [tuple(tail[4 * l].shape) for l in range(L)],
+        ctx.meta = (L, [Ws[0].shape[1]] + [w.shape[0] for w in Ws], [tuple(tail[4 * l].shape) for l in range(L)],
                     [tail[4 * l].dtype for l in range(L)], tuple(w1.shape), w1.dtype, tuple(x.shape), fam)
         y = y[:, :out_f] if out_f != y.shape[1] else y      # a view of the padded output (the head reads it strided)
         return y.reshape(*x.shape[:-1], out_f)
@@ -903,8 +908,23 @@ class _HybridMLP(torch.autograd.Function):
         needs = ctx.needs_input_grad
         gy = gy.reshape(h1.shape[0], -1)
         live, gw_last = wshapes[L - 1][0], None
-        if (needs[6 + 4 * (L - 1)] and gy.dtype == torch.bfloat16 and gy.shape[1] == live
-                and F_.mlp_bwd_wlast_bytes(widths, h1.shape[0], fam, live) > 0):
+        rows = h1.shape[0]
+        carried = (needs[6 + 4 * (L - 1)] and gy.dtype == torch.bfloat16 and gy.shape[1] == live
+                   and F_.mlp_bwd_wlast_bytes(widths, rows, fam, live) > 0)
+        # Where the weight gradients of the first layer and the tail go out as ONE product and one finish (_tail_grads),
+        # that finish folds the backward's per-workgroup partial sums itself: no reduce launch in between.  The query is the
+        # one _tail_grads asks, on the shapes the gradients will have.
+        tail_w = [l for l in range(L - 1) if needs[6 + 4 * l]]
+        merged = (carried and needs[2] and tail_w and w1dt == torch.bfloat16 and all(d == torch.bfloat16 for d in wdt)
+                  and fam in (F_.MLP_FAMILY_TILE, F_.MLP_FAMILY_MIXED) and cur.dtype == h1.dtype == torch.bfloat16
+                  and F_.wgrad_deep_splits_for(rows, [(w1shape[1], cur.shape[1], w1shape[0], widths[0])] + [
+                      (wshapes[l][1], (h1 if l == 0 else hidden[l - 1]).shape[1], wshapes[l][0], F_._pad32(widths[l + 1]))
+                      for l in tail_w]) > 0)
+        if merged:
+            gy2 = gy.contiguous()
+            g1, gz, gb, gb1, gw_last = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam,
+                                                                 h_last=hidden[L - 2], live=live, parts=True)
+        elif carried:
             # the fused backward sums the output layer's weight gradient itself and reads the logit gradient where it lies
             gy2 = gy.contiguous()
             g1, gz, gb, gb1, gw_last = F_.fused_mlp_backward_raw(gy2, widths, Ws, masks, mask_in, family=fam,
@@ -919,6 +939,8 @@ class _HybridMLP(torch.autograd.Function):
                                      first=(g1, cur, w1shape[0], w1shape[1], w1dt, gb1, needs[2], needs[3]))
         for gw, gbias in tail:
             grads += [gw, gbias, None, None]
+        if done is None or (needs[3] and done[1] is None):
+            gb1 = F_._plain_sum(gb1)      # (partial rows that no batched finish took after all)
         gx, gw1, gbias1 = _dense_layer_grads(g1, gb1, cur, W1, w1shape[0], w1shape[1], w1dt, needs[0], needs[2], needs[3],
                                              done)
         return (gx.reshape(xshape) if needs[0] else None, None, gw1, gbias1, None, None, *grads)
@@ -1143,8 +1165,9 @@ class MultilayerPerceptionLayer(BaseLayer):
         # The library GEMMs of the first layer want its output 512 wide (PAD_MULTIPLE), the fused tail wants 416 (13 chunks
         # of 32: 19 % fewer MFMAs in its first layer, and the shape the row-owner forward is built for).  Both: the tail's
         # FORWARD reads the first 416 columns of the 512-wide rows (x_stride) against a 416-wide copy of its first weight
-        # when the library resolves that stack to the mixed family; the backward keeps the 512-wide form, whose extra
-        # columns meet zero weights (the gradient the first layer's weight-gradient GEMM reads stays 512 wide).
+        # when the library resolves that stack to the mixed family, and the backward runs at that width as well: the
+        # columns it no longer computes met zero weights, and the first layer's weight gradient and input gradient read
+        # the 400 live columns of the 416-wide gradient by stride (profiles/deep_bwd_launches.md).
         narrow = None
         h_n = (first.out_features + 31) // 32 * 32
         if (len(tail) >= 2 and h_n < h_pad
