@@ -198,6 +198,58 @@ int trs_scatter_rows_update_mapped(const void* g_rows, void* table, const int32_
 int trs_adam_step_size(int64_t* step, const float* lr_dev, double beta1, double beta2, float* step_size_dev,
                        trs_stream_t stream);
 
+/* ---- stochastic rounding of bf16 tables under the fused optimizers ---------------------------------------------------
+ * The update entries above compute the new weight of a touched row in fp32 and store it round-to-nearest-even; on a bf16
+ * table (no fp32 master copy) an update below half an ulp of the weight -- 2^-9 at w = 1.0 -- is dropped at every step.
+ * The _sr entries store it with stochastic rounding instead, by a rule in integer arithmetic that the host reproduces
+ * bit for bit (csrc/stochastic_round.hpp, one __host__ __device__ function):
+ *
+ *   sr_bf16(x, i, seed, t): the fp32 value x, destined for table element i = table_row * E + column (int64), in update
+ *   number t (uint64) of that table.  u = bits(x).
+ *     exponent field of u all ones (inf, NaN):  result = u >> 16
+ *     otherwise:                                result = (u + r) >> 16,  r a uniform 16-bit integer
+ *   An fp32 value that already is a bf16 value is never changed; any other is rounded away from zero with probability
+ *   (u & 0xffff) / 65536 and towards zero otherwise, so the expectation of the stored value is x.  (The largest finite
+ *   values can round to infinity, as they do under round-to-nearest.)
+ *
+ *   r is a pure function of (seed, t, i): no launch geometry, lane-group width, vector or element walk, hot-row queue,
+ *   chunk, or mapped / unmapped entry enters it.  Philox4x32-10 (Salmon et al., SC'11; multipliers D2511F53 and CD9E8D57,
+ *   key increments 9E3779B9 and BB67AE85, ten rounds) with
+ *     counter = (lo32(q), hi32(q), lo32(t), hi32(t)),  q = i >> 3
+ *     key     = (lo32(seed), hi32(seed))
+ *   gives four 32-bit words; element i takes 16 bits of word (i & 7) >> 1: the low half for even i, the high half for
+ *   odd i.  One call therefore serves the 8 bf16 elements of one 16-byte vector of the table (q = row * L + lane in the
+ *   lane-group walk).  In the mapped entry table_row is the table row row_map points at.
+ *
+ * trs_scatter_rows_update_sr / trs_scatter_rows_update_mapped_sr take the argument lists of their plain counterparts, the
+ * same validated optimizer tail (every optimizer value, row-wise included) and the same walk, plus
+ *   seed    of the optimizer
+ *   t       the update number of this table, by value (the first update of a table is 1; every update call on a table
+ *           takes the next value, so two walks over one table in one backward draw different bits)
+ *   t_dev   NULL, or ONE int64 in device memory that overrides t (as lr_dev overrides lr): a launch captured into a
+ *           hipGraph then draws fresh bits at every replay, with trs_sr_advance enqueued in front of it.
+ * dtype TRS_BF16 takes the stochastic-rounding instantiations of the kernels; dtype TRS_F32 has nothing to round and runs
+ * exactly what the plain entry runs.  The optimizer state (fp32) is what the plain entry leaves.                        */
+int trs_scatter_rows_update_sr(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
+                               const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
+                               int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row,
+                               int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1, float beta2,
+                               float* state, float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream,
+                               uint64_t seed, uint64_t t, const int64_t* t_dev);
+int trs_scatter_rows_update_mapped_sr(const void* g_rows, void* table, const int32_t* row_map, const int32_t* row_start,
+                                      const int32_t* perm, int64_t K, int64_t U, int64_t V, int32_t E, int32_t dtype,
+                                      int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1,
+                                      float beta2, float* state, float* state2, void* workspace, size_t ws_bytes,
+                                      trs_stream_t stream, uint64_t seed, uint64_t t, const int64_t* t_dev);
+
+/* *t_dev += 1 on the device (one thread): enqueued once per update call in front of the _sr entry that reads t_dev. */
+int trs_sr_advance(int64_t* t_dev, trs_stream_t stream);
+
+/* Host only, no device needed: out[k] = sr_bf16(x[k], first + k, seed, t) for k in [0, n) -- the rule itself, and
+ * out[0..3] = Philox4x32-10(counter[0..3]; key[0..1]) -- the generator under it. */
+int trs_sr_bf16_host(const float* x, int64_t n, int64_t first, uint64_t seed, uint64_t t, uint16_t* out);
+int trs_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+
 /* ---- device-side row compaction (owner side of a large row-sharded table) ---------------------------------------
  * ids (K int32, local row ids with repeats) -> row_map (T + 1 int32) and inv (K int32), T = trs_compact_rows_slots(K) =
  * the smallest power of two >= max(2K, 2): fixed shapes, no read-back, no allocation -- replaces torch.unique(ids,

@@ -34,8 +34,8 @@ then the two ragged kernels alone (own inputs, see bench_raggedattn).
 one pass -- against F RaggedListIndicesEmbedding calls plus the cat, and against bag_pool_ragged on pre-offset ids plus the
 permute to (B, F, E) (own inputs, see bench_raggedfields).
 --what rowwise [--shard-rows N]: the fused optimizer step alone (the update walk) for SGD, Adagrad, row-wise Adagrad and
-Adam through gather_rows and embed_fm, uniform and Zipf indices; with --shard-rows also the mapped owner update (own
-inputs, see bench_rowwise)."""
+Adam through gather_rows and embed_fm, uniform and Zipf indices, on a bf16 table plain and with stochastic rounding; with
+--shard-rows also the mapped owner update (own inputs, see bench_rowwise)."""
 import argparse
 import os
 import sys
@@ -822,7 +822,8 @@ def bench_rowwise(a):
     and the row buckets are built by it, so the timed launch is the update walk.  Uniform and Zipf-like indices; the
     optimizers take turns inside a round; median of the per-round medians with their min..max.  With ``--shard-rows`` on
     the command line also the owner side of a row-sharded table of that many rows: compaction, bucket build and the
-    mapped update, as ``--what compact`` times it."""
+    mapped update, as ``--what compact`` times it.  On a bf16 table every optimizer runs a second time with
+    ``stochastic_rounding=True``."""
     from torecsys_amd.optim import FusedSparseAdagrad, FusedSparseAdam, FusedSparseRowWiseAdagrad, FusedSparseSGD
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     dev = torch.device("cuda:0")
@@ -838,6 +839,14 @@ def bench_rowwise(a):
     gf1 = (torch.randn(B, 1, generator=g) * 1e-2).to(dt).to(dev)
     makers = [("sgd", lambda: FusedSparseSGD(1e-3)), ("adagrad", lambda: FusedSparseAdagrad(1e-3)),
               ("rowwise adagrad", lambda: FusedSparseRowWiseAdagrad(1e-3)), ("adam", lambda: FusedSparseAdam(1e-3))]
+    if dt == torch.bfloat16:
+        # the same walks with the new bf16 weights rounded stochastically (one Philox call per touched 16-byte vector);
+        # they take turns with the plain ones inside every round
+        sr = dict(stochastic_rounding=True, seed=1234)
+        makers += [("sgd, stoch. rounding", lambda: FusedSparseSGD(1e-3, **sr)),
+                   ("adagrad, stoch. rounding", lambda: FusedSparseAdagrad(1e-3, **sr)),
+                   ("rowwise adagrad, stoch. rounding", lambda: FusedSparseRowWiseAdagrad(1e-3, **sr)),
+                   ("adam, stoch. rounding", lambda: FusedSparseAdam(1e-3, **sr))]
     print(f"fused optimizer step alone, B={B} N={N} E={E} {a.dtype}, {V} rows; {a.rounds} rounds x {a.iters} launches",
           flush=True)
 

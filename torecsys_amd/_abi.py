@@ -23,6 +23,8 @@ _P, _I32, _I64, _SZ, _F32 = c_void_p, c_int32, c_int64, c_size_t, ctypes.c_float
 
 # what both fused-update entries end in: optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream
 _OPTIMIZER_TAIL = [_I32, _F32, _P, _F32, _F32, _F32, _P, _P, _P, _SZ, _P]
+# what the stochastic-rounding entries add behind it: seed, t, t_dev
+_SR_TAIL = [ctypes.c_uint64, ctypes.c_uint64, _P]
 
 # name -> (restype, argtypes); must list every symbol of include/trs_abi.h (tests/test_abi.py checks)
 SIGNATURES = {
@@ -103,6 +105,13 @@ SIGNATURES = {
                                           *_OPTIMIZER_TAIL]),
     "trs_scatter_rows_update_mapped": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, *_OPTIMIZER_TAIL]),
     "trs_adam_step_size": (c_int32, [_P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "trs_scatter_rows_update_sr": (c_int32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _I32, _I64,
+                                             *_OPTIMIZER_TAIL, *_SR_TAIL]),
+    "trs_scatter_rows_update_mapped_sr": (c_int32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I32, _I32, *_OPTIMIZER_TAIL,
+                                                    *_SR_TAIL]),
+    "trs_sr_advance": (c_int32, [_P, _P]),
+    "trs_sr_bf16_host": (c_int32, [_P, _I64, _I64, ctypes.c_uint64, ctypes.c_uint64, _P]),
+    "trs_philox4x32_10_host": (c_int32, [_P, _P, _P]),
     "trs_compact_rows_slots": (_I64, [_I64]),
     "trs_compact_rows": (c_int32, [_P, _I64, _P, _I64, _P, _P]),
     "trs_compact_rows_dense_workspace_bytes": (_SZ, [_I64]),

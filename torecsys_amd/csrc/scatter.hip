@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "trs_common.hpp"
+#include "stochastic_round.hpp"
 
 namespace trs {
 
@@ -471,7 +472,12 @@ struct RowSink {
   // Optional: the step size lives on the DEVICE (one fp32, the entries' lr_dev): a launch captured into a hipGraph then
   // follows set_lr() / Adam's per-step bias correction from replay to replay; `lr` is ignored when this is set
   const float* lr_dev = nullptr;
+  // Stochastic rounding of the stored bf16 weights (the SR instantiations of the sinks; stochastic_round.hpp): the seed and
+  // the update number of this table, the latter by value or -- as lr / lr_dev -- in device memory when t_dev is set
+  uint64_t seed = 0, t = 0;
+  const int64_t* t_dev = nullptr;
 };
+__device__ __forceinline__ uint64_t sink_t(const RowSink& k) { return k.t_dev != nullptr ? (uint64_t)*k.t_dev : k.t; }
 // the step size of this launch: a uniform load (once per touched row, cached) when it lives on the device
 __device__ __forceinline__ float sink_lr(const RowSink& k) { return k.lr_dev != nullptr ? *k.lr_dev : k.lr; }
 // table row a bucketed row lands on; -1 = a row_map entry outside the table (the sinks skip negative positions)
@@ -481,6 +487,22 @@ __device__ __forceinline__ int64_t sink_row(const RowSink& k, int64_t r) {
   return (m >= 0 && m < k.map_rows) ? m : -1;
 }
 
+// SR (compile time, as RW: every other instantiation stays the code it was; T = bf16_t only): the updated weights of
+// vector `vec` (table elements 8*vec .. 8*vec+7) are rounded stochastically, one hash call for the eight of them.
+template <typename T, bool SR>
+__device__ __forceinline__ void store_weights(const RowSink& k, uint4* __restrict__ out, int64_t vec, const float* w) {
+  if constexpr (SR) {
+    static_assert(sizeof(T) == 2, "stochastic rounding is the bf16 store");
+    uint4 o;
+    uint32_t o4[4];
+    sr_bf16x8(w, vec, k.seed, sink_t(k), o4);
+    o.x = o4[0]; o.y = o4[1]; o.z = o4[2]; o.w = o4[3];
+    out[vec] = o;
+  } else {
+    out[vec] = Vec16<T>::pack(w);
+  }
+}
+
 // RW (compile time, so that every other instantiation of the walk kernels is the code it was): the row-wise Adagrad sink,
 // RowSink mode 4.  The 2^LOG2L lanes of the group hold the row (vec = table row * L + lane, VE sums each); `vec` and
 // `touched` are uniform over the group, so its lanes arrive here together -- whatever the other groups of the wave do:
@@ -488,7 +510,7 @@ __device__ __forceinline__ int64_t sink_row(const RowSink& k, int64_t r) {
 //   order of the sum of squares (part of the result):  q = acc[0]^2, then q += acc[i]^2 for i = 1 .. VE-1 in each lane
 //   (every square and every add rounded: no fma); the lanes' q folded by group_sum_up<L> (xor 1, 2, .., L/2); times 1/E
 //   (E = L*VE, a power of two: exact); s' = s[row] + that.  Every lane reads s[row], lane 0 of the group writes s'.
-template <typename T, bool RW = false, int LOG2L = 0>
+template <typename T, bool RW = false, int LOG2L = 0, bool SR = false>
 __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ out, int64_t vec, const float* acc,
                                          bool touched) {
   constexpr int VE = Vec16<T>::VE;
@@ -509,7 +531,7 @@ __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ o
     const float den = sqrtf(s2) + k.eps;
 #pragma unroll
     for (int i = 0; i < VE; ++i) w[i] -= lr * acc[i] / den;
-    out[vec] = Vec16<T>::pack(w);
+    store_weights<T, SR>(k, out, vec, w);
     return;
   }
   if (k.mode == 0) {
@@ -545,10 +567,10 @@ __device__ __forceinline__ void sink_vec(const RowSink& k, uint4* __restrict__ o
       w[i] -= lr * a / (sqrtf(v) + k.eps);
     }
   }
-  out[vec] = Vec16<T>::pack(w);
+  store_weights<T, SR>(k, out, vec, w);
 }
 
-template <typename T>
+template <typename T, bool SR = false>
 __device__ __forceinline__ void sink_elem(const RowSink& k, T* __restrict__ out, int64_t idx, float acc, bool touched) {
   if (idx < 0) return;
   if (k.mode == 0) {
@@ -571,7 +593,12 @@ __device__ __forceinline__ void sink_elem(const RowSink& k, T* __restrict__ out,
     k.state2[idx] = v;
     w -= lr * a / (sqrtf(v) + k.eps);
   }
-  out[idx] = from_f32<T>(w);
+  if constexpr (SR) {
+    static_assert(sizeof(T) == 2, "stochastic rounding is the bf16 store");
+    out[idx] = T{sr_bf16(w, idx, k.seed, sink_t(k))};
+  } else {
+    out[idx] = from_f32<T>(w);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -681,7 +708,7 @@ __device__ __forceinline__ void accumulate_bucket(float* acc, float* gsum, const
 }
 
 template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool HAS_F1 = false, bool SCAL = false, int CHF = 2,
-          bool RW = false>
+          bool RW = false, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm,
@@ -727,7 +754,7 @@ __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
         for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[SCAL ? 0 : k], acc[k]);
       }
     }
-    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && r != padding_row);
+    sink_vec<T, RW, LOG2L, SR>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && r != padding_row);
     if (HAS_F1 && lane_v == 0) grad_first[r] = from_f32<T>(f1);      // dense companion gradient: every row written
   }
 }
@@ -738,7 +765,7 @@ __global__ __launch_bounds__(256) void scatter_rows_group_kernel(
 // of rows in flight; the generic FM kernel needs 92 registers = 5 waves per SIMD and ran 193 us where the plain walk,
 // at 8 waves, takes 105): 32-bit element offsets from uniform bases (BN * L < 2^31 is checked by the host), the sample
 // index by a multiply-shift with a host-computed reciprocal, the table row fetched with the bucket bounds.
-template <typename T, int LOG2L, bool HAS_G, bool RW = false>
+template <typename T, int LOG2L, bool HAS_G, bool RW = false, bool SR = false>
 __global__ __launch_bounds__(256, 8) void scatter_rows_fm1_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ tg, const T* __restrict__ g1,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int V,
@@ -812,7 +839,7 @@ __global__ __launch_bounds__(256, 8) void scatter_rows_fm1_kernel(
         for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum, acc[k]);
       }
     }
-    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && live);
+    sink_vec<T, RW, LOG2L, SR>(sink, grad, sink_row(sink, r) * L + lane_v, acc, end > beg && live);
   }
 }
 
@@ -852,7 +879,7 @@ __global__ __launch_bounds__(256) void scatter_first_long_kernel(const T* __rest
 // rows of 65 ... 300 lookups, for which 7 of its 8 lane-group rounds had nothing to do -- 92 us at the end of the step.)
 // Rows of a single chunk are finished here; otherwise the chunk's partial sums go to scratch[entry][2][E] (fp32)
 // and scatter_long_rows_finish_kernel adds the chunks of the row.
-template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool SCAL = false, bool RW = false>
+template <typename T, int LOG2L, bool HAS_G, bool HAS_FM, bool SCAL = false, bool RW = false, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
     const uint4* __restrict__ g_rows, const uint4* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const uint4* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int N,
@@ -896,7 +923,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
 #pragma unroll
           for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[k], acc[k]);
         }
-        sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
+        sink_vec<T, RW, LOG2L, SR>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
       } else {
         float* sa = scratch + ((size_t)i * 2) * (L * VE) + lane_v * VE;
 #pragma unroll
@@ -906,7 +933,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_kernel(
   }
 }
 
-template <typename T, int LOG2L, bool HAS_FM, bool RW = false>
+template <typename T, int LOG2L, bool HAS_FM, bool RW = false, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_long_rows_finish_kernel(
     const float* __restrict__ fm_sum, const uint4* __restrict__ table, const int32_t* __restrict__ row_start,
     uint4* __restrict__ grad, const int32_t* __restrict__ long_rows, const float* __restrict__ scratch, RowSink sink) {
@@ -959,7 +986,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_finish_kernel(
 #pragma unroll
       for (int k = 0; k < VE; ++k) acc[k] = fmaf(-w[k], gsum[k], acc[k]);
     }
-    sink_vec<T, RW, LOG2L>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
+    sink_vec<T, RW, LOG2L, SR>(sink, grad, sink_row(sink, r) * L + lane_v, acc, true);
   }
 }
 
@@ -1027,7 +1054,7 @@ __device__ __forceinline__ float elem_term(const T* __restrict__ g_rows, const T
   return acc;
 }
 
-template <typename T>
+template <typename T, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_rows_elem_kernel(
     const T* __restrict__ g_rows, const T* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const T* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int64_t V,
@@ -1067,11 +1094,11 @@ __global__ __launch_bounds__(256) void scatter_rows_elem_kernel(
       for (int q = beg; q < end; ++q) acc += elem_term<T>(g_rows, g_fm, fm_sum, perm[q], E, N, gbs, e, &gsum, gcols);
       if (g_fm != nullptr && fm_sum != nullptr && end > beg) acc = fmaf(-to_f32(table[t]), gsum, acc);
     }
-    sink_elem<T>(sink, grad, sink_row(sink, r) * E + e, acc, touched);
+    sink_elem<T, SR>(sink, grad, sink_row(sink, r) * E + e, acc, touched);
   }
 }
 
-template <typename T>
+template <typename T, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_long_rows_elem_kernel(
     const T* __restrict__ g_rows, const T* __restrict__ g_fm, const float* __restrict__ fm_sum,
     const T* __restrict__ table, const int32_t* __restrict__ row_start, const int32_t* __restrict__ perm, int E, int N,
@@ -1103,7 +1130,7 @@ __global__ __launch_bounds__(256) void scatter_long_rows_elem_kernel(
       }
       if (lane == 0) {
         if (g_fm != nullptr && fm_sum != nullptr) acc = fmaf(-to_f32(table[r * E + e]), gsum, acc);
-        sink_elem<T>(sink, grad, sink_row(sink, r) * E + e, acc, true);
+        sink_elem<T, SR>(sink, grad, sink_row(sink, r) * E + e, acc, true);
       }
     }
   }
@@ -1149,7 +1176,7 @@ __global__ __launch_bounds__(256) void scatter_split_rows_elem_kernel(
   }
 }
 
-template <typename T>
+template <typename T, bool SR = false>
 __global__ __launch_bounds__(256) void scatter_split_rows_finish_elem_kernel(
     const T* __restrict__ g_fm, const float* __restrict__ fm_sum, const T* __restrict__ table, int E,
     T* __restrict__ grad, const int32_t* __restrict__ split_rows, const float* __restrict__ split_acc, RowSink sink) {
@@ -1161,7 +1188,7 @@ __global__ __launch_bounds__(256) void scatter_split_rows_finish_elem_kernel(
     const int64_t r = split_rows[1 + 2 * i];
     float acc = split_acc[(size_t)i * 2 * E + e];
     if (g_fm != nullptr && fm_sum != nullptr) acc = fmaf(-to_f32(table[r * E + e]), split_acc[(size_t)i * 2 * E + E + e], acc);
-    sink_elem<T>(sink, grad, sink_row(sink, r) * E + e, acc, true);
+    sink_elem<T, SR>(sink, grad, sink_row(sink, r) * E + e, acc, true);
   }
 }
 
@@ -1203,11 +1230,12 @@ struct WalkJob {
   void* tg = nullptr;
   float* scratch = nullptr;
   RowSink sink = GRAD_SINK;
+  bool sr = false;                 // the _sr entries: a bf16 table takes the stochastic-rounding instantiations
   hipStream_t s = nullptr;
   const char* who = "scatter_rows";      // the entry, for the messages that name it
 };
 
-template <typename T, int LOG2L, bool RW>
+template <typename T, int LOG2L, bool RW, bool SR = false>
 static void scatter_group_launch(const WalkJob& j) {
   const int L = 1 << LOG2L;
   hipStream_t s = j.s;
@@ -1234,10 +1262,10 @@ static void scatter_group_launch(const WalkJob& j) {
   const bool hg = j.g_rows != nullptr, hf = fm != nullptr;
 #define TRS_SC_TAIL(HG, HF, SC)                                                                                 \
   do {                                                                                                          \
-    hipLaunchKernelGGL((scatter_long_rows_kernel<T, LOG2L, HG, HF, SC, RW>), dim3(2048), dim3(256), 0, s,            \
+    hipLaunchKernelGGL((scatter_long_rows_kernel<T, LOG2L, HG, HF, SC, RW, SR>), dim3(2048), dim3(256), 0, s,            \
                        (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
                        j.perm, j.N, j.gbs, (uint4*)j.out, j.long_rows, j.scratch, j.sink, fs);                  \
-    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF, RW>), dim3(64), dim3(256), 0, s, j.fm_sum,    \
+    hipLaunchKernelGGL((scatter_long_rows_finish_kernel<T, LOG2L, HF, RW, SR>), dim3(64), dim3(256), 0, s, j.fm_sum,    \
                        (const uint4*)j.table, j.row_start, (uint4*)j.out, j.long_rows, j.scratch, j.sink);      \
   } while (0)
 #define TRS_SC(HG, HF)                                                                                          \
@@ -1248,14 +1276,14 @@ static void scatter_group_launch(const WalkJob& j) {
                          j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs,        \
                          (const T*)j.g_first, (T*)j.grad_first);                                                \
     else                                                                                                        \
-      hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF, false, false, 2, RW>), dim3(grid), dim3(256), 0, s,             \
+      hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, HF, false, false, 2, RW, SR>), dim3(grid), dim3(256), 0, s,             \
                          (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start, \
                          j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);       \
     TRS_SC_TAIL(HG, HF, false);                                                                                 \
   } while (0)
 #define TRS_SCS(HG, CHF_)                                                                                       \
   do {                                                                                                          \
-    hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, true, false, true, CHF_, RW>), dim3(grid), dim3(256), 0, s, \
+    hipLaunchKernelGGL((scatter_rows_group_kernel<T, LOG2L, HG, true, false, true, CHF_, RW, SR>), dim3(grid), dim3(256), 0, s, \
                        (const uint4*)j.g_rows, (const uint4*)fm, j.fm_sum, (const uint4*)j.table, j.row_start,  \
                        j.perm, j.V, j.N, j.gbs, j.padding_row, (uint4*)j.out, j.long_rows, j.sink, fs);         \
     TRS_SC_TAIL(HG, true, true);                                                                                \
@@ -1265,11 +1293,11 @@ static void scatter_group_launch(const WalkJob& j) {
   if (lean) {
     const unsigned rcpN = (unsigned)((((uint64_t)1 << 32) + (unsigned)j.N - 1) / (unsigned)j.N);
     if (hg)
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true, RW>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, true, RW, SR>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
                          (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
                          (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     else
-      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false, RW>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
+      hipLaunchKernelGGL((scatter_rows_fm1_kernel<T, LOG2L, false, RW, SR>), dim3(grid), dim3(256), 0, s, (const uint4*)j.g_rows,
                          (const uint4*)j.tg, (const T*)fs.g1, (const uint4*)j.table, j.row_start, j.perm, (int)j.V,
                          (unsigned)j.N, rcpN, (int)j.padding_row, (uint4*)j.out, j.long_rows, j.sink);
     if (hg) TRS_SC_TAIL(true, true, true);
@@ -1298,11 +1326,11 @@ static int walk_lanes(const WalkJob& j, int elem_bytes) {
   return al ? lg : -1;
 }
 
-template <typename T>
+template <typename T, bool SR = false>
 static int scatter_launch(const WalkJob& j, int lg /* walk_lanes(j, sizeof(T)): decided once, by scatter_rows_impl */) {
   if (lg >= 0) {
-    if (j.sink.mode == 4) dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, true>(j); });
-    else dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, false>(j); });
+    if (j.sink.mode == 4) dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, true, SR>(j); });
+    else dispatch_lanes(lg, [&](auto lg_c) { scatter_group_launch<T, decltype(lg_c)::value, false, SR>(j); });
   } else {
     // the companion table and the row-wise sink ride only in the 16-byte-vector walk (sink_elem knows no mode 4)
     TRS_REQUIRE(j.sink.mode != 4, TRS_ESHAPE, "%s: row-wise Adagrad has no element walk", j.who);
@@ -1312,16 +1340,16 @@ static int scatter_launch(const WalkJob& j, int lg /* walk_lanes(j, sizeof(T)): 
     // queue of the split rows: behind the plain queue of long rows (long_row_queue_bytes); its counter was zeroed with
     // the other one (scatter_rows_impl)
     int32_t* split_rows = j.long_rows + 1 + (j.B * j.N / LONG_ROW_ELEM + 2);
-    hipLaunchKernelGGL((scatter_rows_elem_kernel<T>), dim3(stream_grid(j.V * j.E, 256, 256 * 32)), dim3(256), 0, s,
+    hipLaunchKernelGGL((scatter_rows_elem_kernel<T, SR>), dim3(stream_grid(j.V * j.E, 256, 256 * 32)), dim3(256), 0, s,
                        (const T*)j.g_rows, (const T*)j.g_fm, j.fm_sum, (const T*)j.table, j.row_start, j.perm, j.V, j.E,
                        j.N, j.gbs, j.padding_row, (T*)j.out, j.long_rows, j.sink, j.g_fm_cols, split_rows, j.scratch);
-    hipLaunchKernelGGL((scatter_long_rows_elem_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)j.g_rows,
+    hipLaunchKernelGGL((scatter_long_rows_elem_kernel<T, SR>), dim3(2048), dim3(256), 0, s, (const T*)j.g_rows,
                        (const T*)j.g_fm, j.fm_sum, (const T*)j.table, j.row_start, j.perm, j.E, j.N, j.gbs, (T*)j.out,
                        j.long_rows, j.sink, j.g_fm_cols);
     hipLaunchKernelGGL((scatter_split_rows_elem_kernel<T>), dim3(512), dim3(256), 0, s, (const T*)j.g_rows,
                        (const T*)j.g_fm, j.fm_sum, j.row_start, j.perm, j.E, j.N, j.gbs, split_rows, j.scratch,
                        j.g_fm_cols);
-    hipLaunchKernelGGL((scatter_split_rows_finish_elem_kernel<T>), dim3(16), dim3(256), 0, s, (const T*)j.g_fm, j.fm_sum,
+    hipLaunchKernelGGL((scatter_split_rows_finish_elem_kernel<T, SR>), dim3(16), dim3(256), 0, s, (const T*)j.g_fm, j.fm_sum,
                        (const T*)j.table, j.E, (T*)j.out, split_rows, j.scratch, j.sink);
   }
   return check_launch("scatter_rows");
@@ -1521,7 +1549,8 @@ static int scatter_rows_impl(WalkJob j, int64_t BN, int32_t dtype, void* workspa
   j.split_count = j.long_rows + 1 + (BN / LONG_ROW_ELEM + 2);
   j.zero_in_build = lg >= 0 && j.g_fm != nullptr && j.fm_sum != nullptr;
   if (!j.zero_in_build) hipLaunchKernelGGL(zero_two_i32_kernel, dim3(1), dim3(64), 0, j.s, j.long_rows, j.split_count);
-  return dtype == TRS_F32 ? scatter_launch<float>(j, lg) : scatter_launch<bf16_t>(j, lg);
+  if (dtype == TRS_F32) return scatter_launch<float>(j, lg);      // (fp32 under an _sr entry: nothing to round)
+  return j.sr ? scatter_launch<bf16_t, true>(j, lg) : scatter_launch<bf16_t>(j, lg);
 }
 
 /* see include/trs_abi.h: the dense gradients of an embedding table AND of its first-order (E = 1) companion in one walk */
@@ -1575,6 +1604,33 @@ static int make_sink(const char* who, const void* table, int32_t optimizer, floa
   return TRS_OK;
 }
 
+// what the _sr entries add to a validated sink (see stochastic rounding in include/trs_abi.h)
+struct SrArgs {
+  bool on = false;
+  uint64_t seed = 0, t = 0;
+  const int64_t* t_dev = nullptr;
+};
+static void sink_sr(RowSink* sink, const SrArgs& sr) {
+  sink->seed = sr.seed;
+  sink->t = sr.t;
+  sink->t_dev = sr.t_dev;
+}
+
+static int update_impl(const char* who, const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
+                       int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
+                       int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype, int64_t padding_row, int32_t optimizer,
+                       float lr, const float* lr_dev, float eps, float beta1, float beta2, float* state, float* state2,
+                       void* workspace, size_t ws_bytes, trs_stream_t stream, const SrArgs& sr) {
+  RowSink sink;
+  if (int rc = make_sink(who, table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, nullptr, 0, &sink)) return rc;
+  sink_sr(&sink, sr);
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
+                                   .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
+                                   .N = N, .padding_row = padding_row, .out = table, .sink = sink, .sr = sr.on,
+                                   .s = (hipStream_t)stream, .who = who},
+                           BN, dtype, workspace, ws_bytes);
+}
+
 /* see include/trs_abi.h: the walk with a fused sparse optimizer step as its sink */
 extern "C" int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm, int32_t g_fm_cols,
                                        const float* fm_sum, void* table, const int32_t* row_start, const int32_t* perm,
@@ -1582,15 +1638,39 @@ extern "C" int trs_scatter_rows_update(const void* g_rows, int64_t g_rows_batch_
                                        int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1,
                                        float beta2, float* state, float* state2, void* workspace, size_t ws_bytes,
                                        trs_stream_t stream) {
+  return update_impl("scatter_rows_update", g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm, BN,
+                     V, E, N, dtype, padding_row, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace,
+                     ws_bytes, stream, SrArgs{});
+}
+
+/* see include/trs_abi.h: the same step, the new bf16 weights rounded stochastically */
+extern "C" int trs_scatter_rows_update_sr(const void* g_rows, int64_t g_rows_batch_stride, const void* g_fm,
+                                          int32_t g_fm_cols, const float* fm_sum, void* table, const int32_t* row_start,
+                                          const int32_t* perm, int64_t BN, int64_t V, int32_t E, int32_t N, int32_t dtype,
+                                          int64_t padding_row, int32_t optimizer, float lr, const float* lr_dev, float eps,
+                                          float beta1, float beta2, float* state, float* state2, void* workspace,
+                                          size_t ws_bytes, trs_stream_t stream, uint64_t seed, uint64_t t,
+                                          const int64_t* t_dev) {
+  return update_impl("scatter_rows_update_sr", g_rows, g_rows_batch_stride, g_fm, g_fm_cols, fm_sum, table, row_start, perm,
+                     BN, V, E, N, dtype, padding_row, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace,
+                     ws_bytes, stream, SrArgs{true, seed, t, t_dev});
+}
+
+static int update_mapped_impl(const char* who, const void* g_rows, void* table, const int32_t* row_map,
+                              const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U, int64_t V, int32_t E,
+                              int32_t dtype, int32_t optimizer, float lr, const float* lr_dev, float eps, float beta1,
+                              float beta2, float* state, float* state2, void* workspace, size_t ws_bytes,
+                              trs_stream_t stream, const SrArgs& sr) {
   RowSink sink;
-  if (int rc = make_sink("scatter_rows_update", table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, nullptr, 0,
-                         &sink))
-    return rc;
-  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .gbs = g_rows_batch_stride, .g_fm = g_fm, .g_fm_cols = g_fm_cols,
-                                   .fm_sum = fm_sum, .table = table, .row_start = row_start, .perm = perm, .V = V, .E = E,
-                                   .N = N, .padding_row = padding_row, .out = table, .sink = sink,
-                                   .s = (hipStream_t)stream, .who = "scatter_rows_update"},
-                           BN, dtype, workspace, ws_bytes);
+  if (int rc = make_sink(who, table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, row_map, V, &sink)) return rc;
+  sink_sr(&sink, sr);
+  TRS_REQUIRE(g_rows && row_map, TRS_EINVAL, "%s: NULL pointer", who);
+  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
+  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
+  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .table = table, .row_start = row_start, .perm = perm, .V = U, .E = E,
+                                   .N = 1, .out = table, .sink = sink, .sr = sr.on, .s = (hipStream_t)stream,
+                                   .who = who},
+                           K, dtype, workspace, ws_bytes);
 }
 
 /* see include/trs_abi.h: the fused sparse optimizer step on a COMPACT list of distinct rows */
@@ -1599,15 +1679,20 @@ extern "C" int trs_scatter_rows_update_mapped(const void* g_rows, void* table, c
                                               int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float lr,
                                               const float* lr_dev, float eps, float beta1, float beta2, float* state,
                                               float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream) {
-  const char* who = "scatter_rows_update_mapped";
-  RowSink sink;
-  if (int rc = make_sink(who, table, optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, row_map, V, &sink)) return rc;
-  TRS_REQUIRE(g_rows && row_map, TRS_EINVAL, "%s: NULL pointer", who);
-  TRS_REQUIRE(U >= 0 && V > 0 && K >= 0, TRS_EINVAL, "%s: bad row counts", who);
-  if (U == 0 || K == 0) return TRS_OK;      // a rank that received no lookups this step: nothing to update
-  return scatter_rows_impl(WalkJob{.g_rows = g_rows, .table = table, .row_start = row_start, .perm = perm, .V = U, .E = E,
-                                   .N = 1, .out = table, .sink = sink, .s = (hipStream_t)stream, .who = who},
-                           K, dtype, workspace, ws_bytes);
+  return update_mapped_impl("scatter_rows_update_mapped", g_rows, table, row_map, row_start, perm, K, U, V, E, dtype,
+                            optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream, SrArgs{});
+}
+
+/* see include/trs_abi.h: the same step, the new bf16 weights rounded stochastically */
+extern "C" int trs_scatter_rows_update_mapped_sr(const void* g_rows, void* table, const int32_t* row_map,
+                                                 const int32_t* row_start, const int32_t* perm, int64_t K, int64_t U,
+                                                 int64_t V, int32_t E, int32_t dtype, int32_t optimizer, float lr,
+                                                 const float* lr_dev, float eps, float beta1, float beta2, float* state,
+                                                 float* state2, void* workspace, size_t ws_bytes, trs_stream_t stream,
+                                                 uint64_t seed, uint64_t t, const int64_t* t_dev) {
+  return update_mapped_impl("scatter_rows_update_mapped_sr", g_rows, table, row_map, row_start, perm, K, U, V, E, dtype,
+                            optimizer, lr, lr_dev, eps, beta1, beta2, state, state2, workspace, ws_bytes, stream,
+                            SrArgs{true, seed, t, t_dev});
 }
 
 namespace trs {
@@ -1631,4 +1716,35 @@ extern "C" int trs_adam_step_size(int64_t* step, const float* lr_dev, double bet
   hipLaunchKernelGGL(adam_step_size_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, lr_dev, beta1, beta2,
                      step_size_dev);
   return check_launch("adam_step_size");
+}
+
+namespace trs {
+// the update counter of a table on the device, one thread: *counter += 1
+__global__ void counter_advance_kernel(int64_t* __restrict__ counter) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  *counter = *counter + 1;
+}
+}  // namespace trs
+
+/* see include/trs_abi.h */
+extern "C" int trs_sr_advance(int64_t* t_dev, trs_stream_t stream) {
+  TRS_REQUIRE(t_dev, TRS_EINVAL, "sr_advance: NULL pointer");
+  hipLaunchKernelGGL(counter_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, t_dev);
+  return check_launch("sr_advance");
+}
+
+/* see include/trs_abi.h: the rounding rule on the host */
+extern "C" int trs_sr_bf16_host(const float* x, int64_t n, int64_t first, uint64_t seed, uint64_t t, uint16_t* out) {
+  TRS_REQUIRE(n >= 0 && first >= 0, TRS_EINVAL, "sr_bf16_host: bad size");
+  TRS_REQUIRE(n == 0 || (x && out), TRS_EINVAL, "sr_bf16_host: NULL pointer");
+  for (int64_t k = 0; k < n; ++k) out[k] = sr_bf16(x[k], first + k, seed, t);
+  return TRS_OK;
+}
+
+/* see include/trs_abi.h: Philox4x32-10 on the host (the known answers of the generator) */
+extern "C" int trs_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+  TRS_REQUIRE(counter && key && out, TRS_EINVAL, "philox4x32_10_host: NULL pointer");
+  const Philox4 p = philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+  for (int k = 0; k < 4; ++k) out[k] = p.w[k];
+  return TRS_OK;
 }

@@ -428,6 +428,20 @@ def _sink_args(opt, table: torch.Tensor, key, operands=()):
     return kind, lr, ptr(lr_dev), float(opt.eps), beta1, beta2, ptr(state), ptr(state2)
 
 
+def _sr_args(opt, table: torch.Tensor, key) -> tuple:
+    """What the stochastic-rounding entries take behind the plain argument list -- (seed, t, t_dev) -- or () when the update
+    goes to the plain entry: the option is off, or the table is fp32 (nothing to round).  Takes the table's next update
+    number: by value from the host counter, or, for a ``capturable`` optimizer, from its device counter, advanced here by
+    one thread (trs_sr_advance) in front of the update on the same stream.  Call it after ``_sink_args`` has accepted the
+    table."""
+    if not getattr(opt, "stochastic_rounding", False) or table.dtype != torch.bfloat16:
+        return ()
+    t, t_dev = opt.next_update(table, key)
+    if t_dev is not None:
+        call("trs_sr_advance", ptr(t_dev), stream_ptr())
+    return opt.seed, t, ptr(t_dev)
+
+
 def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Optional[torch.Tensor] = None,
                         g_bcast: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
                         padding_row: int = -1, key=None, g_rows_batch_stride: int = 0) -> None:
@@ -441,9 +455,11 @@ def scatter_rows_update(rb: RowBuckets, table: torch.Tensor, opt, g_rows: Option
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
     # (a per-sample FM gradient is read as scalars: its own alignment does not matter)
     scal = g_bcast is not None and _bcast_cols(g_bcast, E) == 1 and E > 1 and fm_sum is not None
-    call("trs_scatter_rows_update", ptr(g_rows), g_rows_batch_stride, ptr(g_bcast), _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table),
-         ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N, value_dtype_code(table), padding_row,
-         *_sink_args(opt, table, key, (g_rows, None if scal else g_bcast, fm_sum)), ptr(ws), ws_bytes, stream_ptr())
+    sink = _sink_args(opt, table, key, (g_rows, None if scal else g_bcast, fm_sum))
+    sr = _sr_args(opt, table, key)
+    call("trs_scatter_rows_update_sr" if sr else "trs_scatter_rows_update", ptr(g_rows), g_rows_batch_stride, ptr(g_bcast),
+         _bcast_cols(g_bcast, E), ptr(fm_sum), ptr(table), ptr(rb.row_start), ptr(rb.perm), rb.BN, V, E, rb.N,
+         value_dtype_code(table), padding_row, *sink, ptr(ws), ws_bytes, stream_ptr(), *sr)
 
 
 def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows: torch.Tensor, row_map: torch.Tensor,
@@ -460,9 +476,11 @@ def scatter_rows_update_mapped(rb: RowBuckets, table: torch.Tensor, opt, g_rows:
     ws_bytes = size_query("trs_scatter_workspace_bytes", rb.BN, 1, E, value_dtype_code(table))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
     g_rows = g_rows.contiguous()
-    call("trs_scatter_rows_update_mapped", ptr(g_rows), ptr(table), ptr(row_map), ptr(rb.row_start),
-         ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), *_sink_args(opt, table, key, (g_rows,)), ptr(ws),
-         ws_bytes, stream_ptr())
+    sink = _sink_args(opt, table, key, (g_rows,))
+    sr = _sr_args(opt, table, key)
+    call("trs_scatter_rows_update_mapped_sr" if sr else "trs_scatter_rows_update_mapped", ptr(g_rows), ptr(table),
+         ptr(row_map), ptr(rb.row_start), ptr(rb.perm), rb.BN, rb.V, V, E, value_dtype_code(table), *sink, ptr(ws),
+         ws_bytes, stream_ptr(), *sr)
 
 
 def compact_rows(ids: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None

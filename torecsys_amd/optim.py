@@ -24,6 +24,16 @@ ONE fp32 accumulator per table row (``(V,)``: 0.5 GB for a 125 M-row x 64 bf16 s
 and Adam 64 GB -- sizes by arithmetic), advanced by the mean square of the row's summed gradient.  It lives in the
 lane-group walk only: tables whose rows are not 1, 2, 4 .. 64 whole 16-byte vectors are refused (``E == 1`` excepted,
 where the rule IS element-wise Adagrad and runs as such).
+
+``stochastic_rounding=True`` (every optimizer here; off by default) is for bf16 tables, which are trained in place with no
+fp32 master copy: the new weight of a touched row exists in fp32 only inside the kernel, and stored round-to-nearest an
+update below half a bf16 ulp of the weight (2^-9 at 1.0) is dropped, at every step.  With the option the store rounds up or
+down with the probability that makes its expectation the fp32 value.  The random bits are a counter-based hash of
+``(seed, update number of the table, element position)`` (Philox4x32-10; the rule is spelled out in include/trs_abi.h), so
+a run is reproducible, two lookups of one table in one backward draw different bits, and a checkpointed run resumes the
+same bit stream: ``state_dict`` carries the seed and every table's update counter.  A ``capturable`` optimizer keeps the
+counter on the device, advanced by a one-thread kernel in front of every update, so hipGraph replays draw fresh bits.
+fp32 tables ignore the option: there is nothing to round.
 """
 from __future__ import annotations
 
@@ -36,19 +46,62 @@ class _FusedSparse:
     kind = 0
     _buffers: Tuple[str, ...] = ()          # names of the per-table fp32 state tensors
 
-    def __init__(self, lr: float, eps: float = 0.0, capturable: bool = False):
+    def __init__(self, lr: float, eps: float = 0.0, capturable: bool = False, stochastic_rounding: bool = False,
+                 seed: int = 0):
         if lr < 0:
             raise ValueError(f"invalid learning rate {lr}")
         if not isinstance(capturable, bool):
             raise TypeError(f"capturable must be a bool, got {type(capturable).__name__}")
+        if not isinstance(stochastic_rounding, bool):
+            raise TypeError(f"stochastic_rounding must be a bool, got {type(stochastic_rounding).__name__}")
         self.lr, self.eps = float(lr), float(eps)
         self._capturable = capturable
+        # (flag, seed) in one tuple: 'hyper' of state_dict() collects the plain numbers of __dict__
+        self._sr: Tuple[bool, int] = (stochastic_rounding, self._check_seed(seed))
         self._lr_dev: Dict[torch.device, torch.Tensor] = {}      # capturable: the learning rate, one fp32 per device
         self._state: Dict[object, dict] = {}
 
     @property
     def capturable(self) -> bool:
         return self._capturable
+
+    # ---- stochastic rounding ---------------------------------------------------------------------------
+    @staticmethod
+    def _check_seed(seed) -> int:
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError(f"seed must be an int, got {type(seed).__name__}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed {seed} outside [0, 2^64)")
+        return seed
+
+    @property
+    def stochastic_rounding(self) -> bool:
+        return self._sr[0]
+
+    @property
+    def seed(self) -> int:
+        return self._sr[1]
+
+    def next_update(self, table: torch.Tensor, key=None) -> Tuple[int, Optional[torch.Tensor]]:
+        """The number of the update of ``table`` that starts now (the first is 1), as the stochastic-rounding entries take
+        it: ``(t, None)`` counted on the host, or ``(0, counter)`` for a capturable optimizer, whose int64 counter lives
+        on the device and is advanced by the caller (trs_sr_advance) on the stream of the update."""
+        if not self._sr[0]:
+            raise RuntimeError("next_update: the optimizer was not built with stochastic_rounding=True")
+        st = self._entry(table, key)
+        if self._capturable:
+            return 0, st["sr_t_dev"]
+        if table.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            # the update number is passed by value: a captured launch would draw the capture-time bits at every replay
+            raise RuntimeError("torecsys_amd: stochastic rounding inside a hipGraph capture needs a fused optimizer built "
+                               "with capturable=True (the update counter must live on the device)")
+        st["sr_t"] = st.get("sr_t", 0) + 1
+        return st["sr_t"], None
+
+    @staticmethod
+    def _sr_t_of(st: dict) -> int:
+        # a capturable optimizer counts on the device: one host read per table, at checkpoint time only
+        return int(st["sr_t_dev"].item()) if "sr_t_dev" in st else int(st.get("sr_t", 0))
 
     # ---- learning rate ---------------------------------------------------------------------------------
     def set_lr(self, lr: float) -> None:
@@ -97,10 +150,15 @@ class _FusedSparse:
                                       device=table.device)
             elif t.device != table.device:
                 st[name] = t.to(table.device)
-        for name, dtype in self._scalars:
+        for name, dtype in self._all_scalars:
             t = st.get(name)
             if t is None:
-                st[name] = torch.full((1,), st["step"] if name == "step_dev" else 0, dtype=dtype, device=table.device)
+                if name == "sr_t_dev" and table.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                    # as lr_tensor(): a counter created inside a capture would be reset by every replay
+                    raise RuntimeError("torecsys_amd: a capturable fused optimizer with stochastic rounding met a new "
+                                       "table inside a capture; run one eager step first (GraphedStep's warm-up does)")
+                first = {"step_dev": st["step"], "sr_t_dev": st.get("sr_t", 0)}.get(name, 0)
+                st[name] = torch.full((1,), first, dtype=dtype, device=table.device)
             elif t.device != table.device:
                 st[name] = t.to(table.device)
         return st
@@ -109,6 +167,11 @@ class _FusedSparse:
     def _scalars(self) -> Tuple[tuple, ...]:
         """(name, dtype) of the per-table one-element device tensors of a capturable optimizer"""
         return ()
+
+    @property
+    def _all_scalars(self) -> Tuple[tuple, ...]:
+        sr = (("sr_t_dev", torch.int64),) if self._capturable and self._sr[0] else ()
+        return tuple(self._scalars) + sr
 
     @staticmethod
     def _step_of(st: dict) -> int:
@@ -121,14 +184,20 @@ class _FusedSparse:
     # ---- checkpointing ---------------------------------------------------------------------------------
     def state_dict(self, named_parameters: Optional[Iterable] = None) -> dict:
         """{'hyper': {...}, 'tables': {name: {'step': int, <buffer>: tensor}}}; ``named_parameters`` (e.g.
-        ``model.named_parameters()``) gives the tables their names -- tables it does not cover are 'table<i>'."""
+        ``model.named_parameters()``) gives the tables their names -- tables it does not cover are 'table<i>'.  With
+        ``stochastic_rounding`` also 'stochastic_rounding': {'seed': int} and, per table, 'sr_t': its update counter."""
         names = {id(p): n for n, p in (named_parameters or [])}
         tables = {}
         for i, (k, st) in enumerate(self._state.items()):
             name = names.get(k if isinstance(k, int) else None, f"table{i}")
             tables[name] = {"step": self._step_of(st), **{b: st[b].detach().clone() for b in self._buffers if b in st}}
-        return {"hyper": {k: v for k, v in self.__dict__.items()
-                          if isinstance(v, (int, float)) and not isinstance(v, bool)}, "tables": tables}
+            if self._sr[0]:
+                tables[name]["sr_t"] = self._sr_t_of(st)
+        sd = {"hyper": {k: v for k, v in self.__dict__.items()
+                        if isinstance(v, (int, float)) and not isinstance(v, bool)}, "tables": tables}
+        if self._sr[0]:
+            sd["stochastic_rounding"] = {"seed": self._sr[1]}
+        return sd
 
     def load_state_dict(self, sd: dict, named_parameters: Iterable) -> None:
         """State tensors (a capturable Adam's device step counter included) are re-created: a graph captured before the
@@ -137,11 +206,15 @@ class _FusedSparse:
         for k, v in sd.get("hyper", {}).items():
             setattr(self, k, v)
         self.set_lr(self.lr)          # a capturable optimizer's device scalar follows the loaded learning rate
+        if "stochastic_rounding" in sd:      # the checkpointed run rounded stochastically: continue its bit stream
+            self._sr = (True, self._check_seed(sd["stochastic_rounding"]["seed"]))
         for name, entry in sd.get("tables", {}).items():
             if name not in params:
                 raise KeyError(f"load_state_dict: no parameter named {name!r}")
             p = params[name]
             st = self._state[id(p)] = {"step": int(entry.get("step", 0)), "ref": p}
+            if "sr_t" in entry:
+                st["sr_t"] = int(entry["sr_t"])
             for b in self._buffers:
                 if b in entry:
                     if tuple(entry[b].shape) != self._state_shape(p):
@@ -163,8 +236,8 @@ class FusedSparseAdagrad(_FusedSparse):
     _buffers = ("sum",)
 
     def __init__(self, lr: float = 1e-2, eps: float = 1e-10, initial_accumulator_value: float = 0.0,
-                 capturable: bool = False):
-        super().__init__(lr, eps, capturable)
+                 capturable: bool = False, stochastic_rounding: bool = False, seed: int = 0):
+        super().__init__(lr, eps, capturable, stochastic_rounding, seed)
         self.initial = float(initial_accumulator_value)
 
     def _init_value(self, name: str) -> float:
@@ -191,8 +264,9 @@ class FusedSparseAdam(_FusedSparse):
     kind = 3
     _buffers = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, capturable: bool = False):
-        super().__init__(lr, eps, capturable)
+    def __init__(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, capturable: bool = False,
+                 stochastic_rounding: bool = False, seed: int = 0):
+        super().__init__(lr, eps, capturable, stochastic_rounding, seed)
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"invalid betas {betas}")
         self.beta1, self.beta2 = float(betas[0]), float(betas[1])
