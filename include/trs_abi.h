@@ -712,7 +712,7 @@ int trs_mlp_fused_bwd_data_wlast(const void* gy, int32_t gy_stride, int64_t rows
  * part_out / stride_out [num_layers + 4] and *nparts_out -- set l < L: layer l's bias gradient (pad32(widths[l+1])
  * columns); set L: the input's column sums (with mask_in, else NULL); set L + 1 + j: row j of the output layer's dW
  * (pad32(widths[L-1]) columns, NULL from ``live`` on).  Column c of a set is the sum over p < nparts of
- * part[p * stride + c]; trs_wgrad_finish_many_parts / trs_wgrad_finish_t_many_parts (or trs_colsum_parts_reduce) take that
+ * part[p * stride + c]; trs_wgrad_finish / trs_wgrad_finish_t with gb_nparts (or trs_colsum_parts_reduce) take that
  * sum in the reduce launch's order.  Both buffers must stay allocated until that consumer is enqueued on the stream. */
 int trs_mlp_fused_bwd_data_parts(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
                                  const int32_t* widths, const void* const* weights, const void* const* masks,
@@ -842,15 +842,33 @@ int trs_cat_head_bwd(const void* g, const void* a, const void* d, const void* w,
                      size_t ws_bytes, trs_stream_t stream);
 
 /* ---- finish of a split-K weight gradient (the K = batch GEMM of multilayer_perceptron.py's nn.Linear backward) -----
- * part (S, R, Cc) fp32 partial products  ->  gw (out_rows, out_cols) = sum_s part[s, :out_rows, :out_cols] cast to
- * dtype (the un-padded corner when the GEMMs ran on zero-padded weights); gb (out_rows) = cast(gb_f32) (both or
- * neither; needs out_rows <= 256 * ceil(out_cols / 256)).                                                          */
-int trs_wgrad_finish(const float* part, int32_t S, int32_t R, int32_t Cc, int32_t out_rows, int32_t out_cols,
-                     int32_t dtype, void* gw, const float* gb_f32, void* gb, trs_stream_t stream);
-/* the same for partial products stored transposed, part (S, Cc, R) (slices of x^T g):
- * gw[r, c] = sum_s part[s, c, r] for r < out_rows <= R, c < out_cols <= Cc.                                          */
-int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int32_t out_rows, int32_t out_cols,
-                       int32_t dtype, void* gw, const float* gb_f32, void* gb, trs_stream_t stream);
+ * 1 .. 8 jobs in one launch (HOST arrays, one S, one dtype; every job is checked before anything is launched), the
+ * partials of trs_wgrad_rows[_many] / trs_wgrad_wide[_many] or of a batched library GEMM.  Job k: part[k] (S, R, Cc) fp32
+ * partial products  ->  gw[k] (out_rows, out_cols) = sum_s part[k][s, :out_rows, :out_cols] cast to dtype (the un-padded
+ * corner when the GEMMs ran on zero-padded weights); gb[k] (out_rows) = cast(gb_f32[k]) (both or neither).
+ * trs_wgrad_finish needs out_rows <= 256 * ceil(out_cols / 256) for a job with a gb: its bias cast has one row of
+ * workgroups.  trs_wgrad_finish_t is the same for partials stored transposed, part[k] (S, Cc, R) (slices of x^T g):
+ * gw[r, c] = sum_s part[s, c, r] for r < out_rows <= R, c < out_cols <= Cc, the slices summed in order.
+ * A job WITHOUT a product, part[k] = gw[k] = NULL, only casts: gb[k][c] = gb_f32[k][c] for c < out_cols[k] (R, Cc,
+ * out_rows of the job are not read) -- a gradient that arrives summed in fp32, such as a row of
+ * trs_mlp_fused_bwd_data_wlast's gw_last, rides in the finish of the other layers.
+ * PARTIAL-ROW sources, gb_nparts / gb_stride (both NULL: every source is a summed vector): where gb_nparts[k] > 0,
+ * gb_f32[k] is not a summed vector but gb_nparts[k] rows of per-workgroup partial sums, gb_stride[k] floats apart (>= the
+ * job's columns) -- what trs_mlp_fused_bwd_data_parts reports.  Value c is the sum over p of gb_f32[k][p * gb_stride[k]
+ * + c], taken in the order of the tile backward's own reduce launch, mlp_colsum_reduce_many_kernel (sixteen running sums
+ * over p = w, w + 16, ..., then w = 0 .. 15), so the cast value has the bits that trs_mlp_fused_bwd_data + a finish on
+ * the summed vector give.  gb_nparts[k] = 0: job k's source is a vector.  Applies to the bias row of a product job and
+ * to a job without a product alike.
+ * One trs_wgrad_finish job with a product, a vector source (or none), S >= 64 and ceil(out_cols / 256) * out_rows < 64
+ * (the 400 -> 1 head) runs on a kernel with sixteen threads per column, which adds the slices in another order.     */
+int trs_wgrad_finish(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
+                     const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                     const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts, const int32_t* gb_stride,
+                     trs_stream_t stream);
+int trs_wgrad_finish_t(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
+                       const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                       const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts, const int32_t* gb_stride,
+                       trs_stream_t stream);
 /* dW partials by a hand-written kernel instead of a batched library GEMM: part (S, M, N) fp32, slice s = g[rows_s, :M]^T
  * x[rows_s, :N] over the s-th of S contiguous row ranges (bf16 operands, row strides ldg / ldx, M and N multiples of
  * 8); trs_wgrad_finish then folds the slices.  S comes from trs_wgrad_rows_splits (0: shape not handled -- more than
@@ -868,10 +886,7 @@ int trs_wgrad_rows(const void* g, int32_t ldg, const void* x, int32_t ldx, int64
  * rows on); 0 otherwise -- the caller keeps the per-layer calls.  trs_wgrad_rows_many takes exactly that S and 16-byte
  * aligned operands and partials; every job is checked before anything is launched.  trs_wgrad_rows_many_map (host
  * only) tells where workgroup ``block`` works: out = {job, row range, output block, first row, end row}, returns the
- * grid size (0: not taken / no such block).  trs_wgrad_finish_many = trs_wgrad_finish for every job (one S, one dtype;
- * gb[k] / gb_f32[k] both or neither) in one launch.  A job WITHOUT a product, part[k] = gw[k] = NULL, only casts:
- * gb[k][c] = gb_f32[k][c] for c < out_cols[k] (R, Cc, out_rows of the job are not read) -- a gradient that arrives
- * summed in fp32, such as a row of trs_mlp_fused_bwd_data_wlast's gw_last, rides in the finish of the other layers.  */
+ * grid size (0: not taken / no such block).  trs_wgrad_finish folds all the jobs' partials in one launch.          */
 int32_t trs_wgrad_rows_many_splits(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
                                    const int32_t* ldx, int64_t rows);
 int32_t trs_wgrad_rows_many_map(int32_t n_jobs, const int32_t* M, const int32_t* N, const int32_t* ldg,
@@ -879,9 +894,6 @@ int32_t trs_wgrad_rows_many_map(int32_t n_jobs, const int32_t* M, const int32_t*
 int trs_wgrad_rows_many(int32_t n_jobs, const void* const* g, const int32_t* ldg, const void* const* x,
                         const int32_t* ldx, int64_t rows, const int32_t* M, const int32_t* N, int32_t S,
                         float* const* part, trs_stream_t stream);
-int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
-                          const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
-                          const float* const* gb_f32, void* const* gb, trs_stream_t stream);
 /* the same product for a WIDE input, transposed: part (S, M_x, N_g) fp32, slice s = x[rows_s, :M_x]^T g[rows_s, :N_g] -- what
  * trs_wgrad_finish_t folds -- with no work spent on the padding columns of g.  Taken (trs_wgrad_wide_splits > 0) when M_x
  * is a multiple of 208 (at least two blocks of 13 tiles of 16), N_g a multiple of 16 that cuts into two blocks of 12 | 13
@@ -901,9 +913,7 @@ int trs_wgrad_wide(const void* x, int32_t ldx, const void* g, int32_t ldg, int64
  * least 128 * S; 0 otherwise, and the caller keeps the per-product calls.  trs_wgrad_wide_many takes exactly that S and
  * 16-byte aligned operands and partials; every job is checked before the launch.  trs_wgrad_wide_many_map (host only):
  * out = {job, row range, block of the job, first row, end row} of workgroup ``block``, returns the grid size (0: not
- * taken / no such block).  trs_wgrad_finish_t_many = trs_wgrad_finish_t for every job (one S, one dtype; gb[k] /
- * gb_f32[k] both or neither) in one launch, ranges summed in order; a job with part[k] = gw[k] = NULL only casts
- * gb[k][c] = gb_f32[k][c] for c < out_cols[k], as in trs_wgrad_finish_many.                                            */
+ * taken / no such block).  trs_wgrad_finish_t folds all the jobs' partials in one launch.                            */
 int32_t trs_wgrad_wide_many_splits(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
                                    const int32_t* ldg, int64_t rows);
 int32_t trs_wgrad_wide_many_map(int32_t n_jobs, const int32_t* M_x, const int32_t* ldx, const int32_t* N_g,
@@ -911,23 +921,6 @@ int32_t trs_wgrad_wide_many_map(int32_t n_jobs, const int32_t* M_x, const int32_
 int trs_wgrad_wide_many(int32_t n_jobs, const void* const* x, const int32_t* ldx, const void* const* g,
                         const int32_t* ldg, int64_t rows, const int32_t* M_x, const int32_t* N_g, int32_t S,
                         float* const* part, trs_stream_t stream);
-int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
-                            const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
-                            const float* const* gb_f32, void* const* gb, trs_stream_t stream);
-/* Both batched finishes with PARTIAL-ROW sources: where gb_nparts[k] > 0, gb_f32[k] is not a summed vector but gb_nparts[k]
- * rows of per-workgroup partial sums, gb_stride[k] floats apart (>= the job's columns) -- what trs_mlp_fused_bwd_data_parts
- * reports.  Value c is the sum over p of gb_f32[k][p * gb_stride[k] + c], taken in the order of the tile backward's own
- * reduce launch (sixteen running sums over p = w, w + 16, ..., then w = 0 .. 15), so the cast value has the bits that
- * trs_mlp_fused_bwd_data + the plain finish give.  gb_nparts[k] = 0: job k as in the plain entry.  Applies to the bias
- * row of a product job and to a job without a product alike.                                                         */
-int trs_wgrad_finish_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
-                                const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
-                                const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
-                                const int32_t* gb_stride, trs_stream_t stream);
-int trs_wgrad_finish_t_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
-                                  const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
-                                  const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
-                                  const int32_t* gb_stride, trs_stream_t stream);
 /* n strided 2-D copies in one launch: desc (device, n x 6 int64) = {src address, dst address, rows, cols, src_ld,
  * dst_ld} (sizes in elements of elem_size bytes); max_elems = the largest rows*cols (sizes the grid).  Refreshes the
  * zero-padded copies of an MLP stack's nn.Linear parameters (multilayer_perceptron.py:55-61) before a forward.     */

@@ -1,8 +1,8 @@
 """The deep branch's backward without its single-purpose launches (profiles/deep_bwd_launches.md), every part against the
 launches it replaces, bit for bit:
 
-A. trs_mlp_fused_bwd_data_parts leaves the reduce launch out; trs_wgrad_finish_many_parts / trs_wgrad_finish_t_many_parts
-   fold the per-workgroup partial rows themselves, in the reduce kernel's order -- every (dW, db), the output layer's row
+A. trs_mlp_fused_bwd_data_parts leaves the reduce launch out; trs_wgrad_finish / trs_wgrad_finish_t with partial-row
+   sources fold the per-workgroup partial rows themselves, in the reduce kernel's order -- every (dW, db), the output layer's row
    included, equals reduce + plain finish on the same operands.
 (B, W1's fragment copy riding in the backward's pack launch, was measured and taken out again: no entry, no test.)
 C. the FM walk zeroes its queue counters in the launch that stages the FM rows: two walks on one workspace, dense and
@@ -63,28 +63,13 @@ def _case(dev, name, rows):
     return _cache[key]
 
 
-def _pa(ts):
-    from torecsys_amd import functional as F_
-    return F_._ptr_array(ts)
-
-
-def _ia(vs):
-    from torecsys_amd import functional as F_
-    return F_._i32_array(vs)
-
-
 # ---------------------------------------------------------------------------------------------- A
-def _finish(entry, transposed, parts, S, dims, gws, srcs, gbs):
+def _finish(transposed, parts, S, dims, gws, srcs, gbs):
     """one batched finish over product jobs ``dims`` = [(R, Cc, out_rows, out_cols)] (None: a job without a product) with
-    fp32 sources ``srcs`` -- vectors through the plain entry, partial sets through the ``_parts`` one"""
+    fp32 sources ``srcs`` -- vectors or partial sets"""
     from torecsys_amd import _abi, functional as F_
-    z = [d if d is not None else (0, 0, 0, 0) for d in dims]
-    ocols = [d[3] if d is not None else gbs[k].numel() for k, d in enumerate(dims)]
-    R, Cc = _ia([d[0] for d in z]), _ia([d[1] for d in z])
-    args = [len(dims), _pa(parts), S] + ([Cc, R] if transposed else [R, Cc]) + [_ia([d[2] for d in z]), _ia(ocols),
-                                                                                _abi.TRS_BF16, _pa(gws), _pa(srcs), _pa(gbs)]
-    sets = F_._parts_arrays(srcs)
-    F_.call(entry + ("_parts" if sets is not None else ""), *args, *(sets or ()), F_.stream_ptr())
+    F_.wgrad_finish([(parts[k], gws[k], srcs[k], gbs[k], *(d if d is not None else (0, 0, 0, gbs[k].numel())))
+                     for k, d in enumerate(dims)], S, _abi.TRS_BF16, transposed=transposed)
 
 
 @pytest.mark.parametrize("rows", ROWS_A)
@@ -112,14 +97,14 @@ def test_a_finish_folds_the_partials_bit_for_bit(dev, name, rows):
     src_new = [new[3]] + list(new[2][:L - 1]) + [new[4][:, 0], new[2][L - 1]]
     src_old = [old[3]] + list(old[2][:L - 1]) + [old[4][0], old[2][L - 1]]
     cast_cols = [wb[L - 1], 1]
-    for entry, transposed in (("trs_wgrad_finish_many", False), ("trs_wgrad_finish_t_many", True)):
+    for entry, transposed in (("trs_wgrad_finish", False), ("trs_wgrad_finish_t", True)):
         prods = [torch.randn((S, in_f, _pad32(o)) if transposed else (S, _pad32(o), in_f), generator=g).to(dev) for o in live_w]
         dims = [(_pad32(o), in_f, o, in_f) for o in live_w] + [None, None]
         res = []
         for srcs in (src_old, src_new):
             gws = [torch.zeros(o, in_f, dtype=torch.bfloat16, device=dev) for o in live_w]
             gbs = [torch.zeros(o, dtype=torch.bfloat16, device=dev) for o in live_w + cast_cols]
-            _finish(entry, transposed, prods + [None, None], S, dims, gws + [None, None], srcs, gbs)
+            _finish(transposed, prods + [None, None], S, dims, gws + [None, None], srcs, gbs)
             res.append(gws + gbs)
         assert all(torch.equal(a, b) for a, b in zip(*res)), entry
         assert all(float(t.float().abs().max()) > 0 for t in res[0][:len(live_w)])

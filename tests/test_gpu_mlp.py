@@ -140,13 +140,13 @@ def test_mlp_logit_layer_uses_rowdot(dev):
 def test_wgrad_finish_matches_torch(dev, dtype, S, R, Cc, out_rows, out_cols, with_bias):
     """trs_wgrad_finish = part.sum(0)[:out_rows, :out_cols].to(dtype) (+ the bias-gradient cast) in one launch"""
     from torecsys_amd import _abi
+    from torecsys_amd import functional as F_
     torch.manual_seed(S * R + Cc)
     part = torch.randn(S, R, Cc, device=dev)
     gbf = torch.randn(R, device=dev)
     gw = torch.empty(out_rows, out_cols, dtype=dtype, device=dev)
     gb = torch.empty(out_rows, dtype=dtype, device=dev) if with_bias else None
-    _abi.call("trs_wgrad_finish", _abi.ptr(part), S, R, Cc, out_rows, out_cols, _abi.value_dtype_code(gw), _abi.ptr(gw),
-              _abi.ptr(gbf) if with_bias else _abi.ptr(None), _abi.ptr(gb), _abi.stream_ptr())
+    F_.wgrad_finish([(part, gw, gbf if with_bias else None, gb, R, Cc, out_rows, out_cols)], S, _abi.value_dtype_code(gw))
     ref = part.sum(0)[:out_rows, :out_cols]
     tol = 1e-6 if dtype == torch.float32 else 8e-3
     assert rel_err(gw.float().cpu(), ref.cpu()) <= tol
@@ -155,15 +155,13 @@ def test_wgrad_finish_matches_torch(dev, dtype, S, R, Cc, out_rows, out_cols, wi
 
 
 def test_wgrad_finish_rejects_bad_arguments(dev):
-    from torecsys_amd import _abi
+    from torecsys_amd import functional as F_
     part = torch.zeros(2, 8, 8, device=dev)
     gw = torch.empty(8, 8, device=dev)
     with pytest.raises(RuntimeError):          # out_rows > R
-        _abi.call("trs_wgrad_finish", _abi.ptr(part), 2, 8, 8, 9, 8, 0, _abi.ptr(gw), _abi.ptr(None), _abi.ptr(None),
-                  _abi.stream_ptr())
+        F_.wgrad_finish([(part, gw, None, None, 8, 8, 9, 8)], 2, 0)
     with pytest.raises(RuntimeError):          # gb without gb_f32
-        _abi.call("trs_wgrad_finish", _abi.ptr(part), 2, 8, 8, 8, 8, 0, _abi.ptr(gw), _abi.ptr(None), _abi.ptr(gw),
-                  _abi.stream_ptr())
+        F_.wgrad_finish([(part, gw, None, gw, 8, 8, 8, 8)], 2, 0)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -172,13 +170,14 @@ def test_wgrad_finish_rejects_bad_arguments(dev):
 def test_wgrad_finish_transposed_matches_torch(dev, dtype, S, Cc, R, out_rows, out_cols, with_bias):
     """trs_wgrad_finish_t: part (S, Cc, R) holds slices of x^T g; gw = part.sum(0).t()[:out_rows, :out_cols]"""
     from torecsys_amd import _abi
+    from torecsys_amd import functional as F_
     torch.manual_seed(S * R + Cc)
     part = torch.randn(S, Cc, R, device=dev)
     gbf = torch.randn(R, device=dev)
     gw = torch.empty(out_rows, out_cols, dtype=dtype, device=dev)
     gb = torch.empty(out_rows, dtype=dtype, device=dev) if with_bias else None
-    _abi.call("trs_wgrad_finish_t", _abi.ptr(part), S, Cc, R, out_rows, out_cols, _abi.value_dtype_code(gw),
-              _abi.ptr(gw), _abi.ptr(gbf) if with_bias else _abi.ptr(None), _abi.ptr(gb), _abi.stream_ptr())
+    F_.wgrad_finish([(part, gw, gbf if with_bias else None, gb, R, Cc, out_rows, out_cols)], S, _abi.value_dtype_code(gw),
+                    transposed=True)
     ref = part.sum(0).t()[:out_rows, :out_cols]
     tol = 1e-6 if dtype == torch.float32 else 8e-3
     assert rel_err(gw.float().cpu(), ref.cpu()) <= tol

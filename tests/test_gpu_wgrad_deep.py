@@ -1,4 +1,4 @@
-"""trs_wgrad_wide_many + trs_wgrad_finish_t_many: the weight gradients of a deep branch's wide first layer and of the
+"""trs_wgrad_wide_many + one trs_wgrad_finish_t: the weight gradients of a deep branch's wide first layer and of the
 400 x 400 layers behind it as ONE launch of the four-wave LDS-DMA kernel (csrc/wgrad_rows.hip) and one finish
 (csrc/mlp_epilogue.hip).  16 blocks of 208 x-columns per row range, 16 ranges, 256 workgroups.
 
@@ -6,7 +6,7 @@ Exact sums, as in test_gpu_wgrad_wide.py: operands are integers of magnitude <= 
 product is an integer of at most 4, every fp32 partial and every sum of partials an integer below 2**24 whatever the
 order, and the fp32 output of the finish must equal the int64 product computed on the CPU.
 
-Against today's entries (trs_wgrad_wide + trs_wgrad_finish_t, trs_wgrad_rows_many + trs_wgrad_finish_many) on Gaussian
+Against today's entries (trs_wgrad_wide + trs_wgrad_finish_t, trs_wgrad_rows_many + trs_wgrad_finish) on Gaussian
 operands the two paths group the fp32 sum differently (16 row ranges against 21 and 32) and round it once to bf16: the
 project's bound for that is 2**-7 of the largest entry."""
 import ctypes
@@ -66,9 +66,9 @@ def _finish(jobs, parts, S, dtype, dev, gbf=None, out_rows=None, out_cols=None):
     orows, ocols = out_rows or [j[2] for j in jobs], out_cols or [j[0] for j in jobs]
     gw = [torch.empty(r, c, dtype=dtype, device=dev) for r, c in zip(orows, ocols)]
     gb = [torch.empty(r, dtype=dtype, device=dev) if gbf is not None else None for r in orows]
-    _abi.call("trs_wgrad_finish_t_many", J, _pa(parts), S, _ia([j[0] for j in jobs]), _ia([j[2] for j in jobs]), _ia(orows),
+    _abi.call("trs_wgrad_finish_t", J, _pa(parts), S, _ia([j[0] for j in jobs]), _ia([j[2] for j in jobs]), _ia(orows),
               _ia(ocols), _abi.value_dtype_code(gw[0]), _pa(gw), _pa(gbf if gbf is not None else [None] * J), _pa(gb),
-              _abi.stream_ptr())
+              None, None, _abi.stream_ptr())
     return gw, gb
 
 
@@ -165,9 +165,9 @@ def test_wgrad_deep_against_todays_entries(dev):
     _abi.call("trs_wgrad_wide", _abi.ptr(xs[0]), 2496, _abi.ptr(gs[0]), 512, rows, 2496, 400, S1, _abi.ptr(part), _abi.stream_ptr())
     gw1 = torch.empty(400, 2496, dtype=BF16, device=dev)
     gb1 = torch.empty(400, dtype=BF16, device=dev)
-    _abi.call("trs_wgrad_finish_t", _abi.ptr(part), S1, 2496, 400, 400, 2496, _abi.TRS_BF16, _abi.ptr(gw1), _abi.ptr(gbf[0]),
-              _abi.ptr(gb1), _abi.stream_ptr())
-    # ... and the two tail layers on trs_wgrad_rows_many + trs_wgrad_finish_many (g^T x)
+    _abi.call("trs_wgrad_finish_t", 1, _pa([part]), S1, _ia([2496]), _ia([400]), _ia([400]), _ia([2496]), _abi.TRS_BF16,
+              _pa([gw1]), _pa([gbf[0]]), _pa([gb1]), None, None, _abi.stream_ptr())
+    # ... and the two tail layers on trs_wgrad_rows_many + one trs_wgrad_finish (g^T x)
     Ms, Ns, ldg, ldx = _ia([400, 400]), _ia([400, 400]), _ia([416, 416]), _ia([512, 416])
     S2 = int(_abi.load().trs_wgrad_rows_many_splits(2, Ms, Ns, ldg, ldx, rows))
     assert S2 > 0
@@ -175,8 +175,8 @@ def test_wgrad_deep_against_todays_entries(dev):
     _abi.call("trs_wgrad_rows_many", 2, _pa(gs[1:]), ldg, _pa(xs[1:]), ldx, rows, Ms, Ns, S2, _pa(parts2), _abi.stream_ptr())
     gw2 = [torch.empty(400, 400, dtype=BF16, device=dev) for _ in range(2)]
     gb2 = [torch.empty(400, dtype=BF16, device=dev) for _ in range(2)]
-    _abi.call("trs_wgrad_finish_many", 2, _pa(parts2), S2, Ms, Ns, Ms, Ns, _abi.TRS_BF16, _pa(gw2), _pa(gbf[1:]), _pa(gb2),
-              _abi.stream_ptr())
+    _abi.call("trs_wgrad_finish", 2, _pa(parts2), S2, Ms, Ns, Ms, Ns, _abi.TRS_BF16, _pa(gw2), _pa(gbf[1:]), _pa(gb2),
+              None, None, _abi.stream_ptr())
     torch.cuda.synchronize()
     for k, (old_w, old_b, S_old) in enumerate([(gw1, gb1, S1), (gw2[0], gb2[0], S2), (gw2[1], gb2[1], S2)]):
         diff = float((gw[k].float() - old_w.float()).abs().max()) / float(old_w.float().abs().max())
@@ -203,10 +203,10 @@ def test_finish_t_many_bias_and_cast_only_jobs(dev, dtype):
     gb = [torch.full((r + 64,), 7.0, dtype=dtype, device=dev) for _, _, r, _ in shapes]
     cout = [torch.full((c.numel() + 64,), 7.0, dtype=dtype, device=dev) for c in casts]
     n = len(casts)
-    _abi.call("trs_wgrad_finish_t_many", 3 + n, _pa(parts + [None] * n), S, _ia([s[0] for s in shapes] + [0] * n),
+    _abi.call("trs_wgrad_finish_t", 3 + n, _pa(parts + [None] * n), S, _ia([s[0] for s in shapes] + [0] * n),
               _ia([s[1] for s in shapes] + [0] * n), _ia([s[2] for s in shapes] + [0] * n),
               _ia([s[3] for s in shapes] + [c.numel() for c in casts]), _abi.value_dtype_code(gw[0]), _pa(gw + [None] * n),
-              _pa(gbf + casts), _pa(gb + cout), _abi.stream_ptr())
+              _pa(gbf + casts), _pa(gb + cout), None, None, _abi.stream_ptr())
     torch.cuda.synchronize()
     for k, (Cc, R, r, c) in enumerate(shapes):
         want = parts[k].sum(0).t()[:r, :c].contiguous().to(dtype)
@@ -264,20 +264,26 @@ def _grads(mlp, x, gout):
     return {n: p.grad.clone() for n, p in mlp.model.named_parameters()}, x.grad.clone()
 
 
-ENTRIES = ["trs_wgrad_wide_many", "trs_wgrad_finish_t_many", "trs_wgrad_wide", "trs_wgrad_finish_t", "trs_wgrad_rows_many",
-           "trs_wgrad_finish_many"]
+# a finish entry as (name, batched): a batched finish carries two or more jobs, the finish of one product one
+ENTRIES = ["trs_wgrad_wide_many", ("trs_wgrad_finish_t", True), "trs_wgrad_wide", ("trs_wgrad_finish_t", False),
+           "trs_wgrad_rows_many", ("trs_wgrad_finish", True)]
 
 
 def _counted(fn):
-    from torecsys_amd import _abi
-    for e in ENTRIES:
-        _abi.time_kernel(e, True)
+    """fn() and how often it called each of ENTRIES"""
+    from torecsys_amd import functional as F_
+    seen, call = [], F_.call
+
+    def record(name, *a):
+        seen.append((name, a[0] >= 2) if name in ("trs_wgrad_finish", "trs_wgrad_finish_t") else name)
+        return call(name, *a)
+
+    F_.call = record
     try:
         out = fn()
-        return out, [len(_abi.kernel_times_ms(e)) for e in ENTRIES]
+        return out, [seen.count(e) for e in ENTRIES]
     finally:
-        for e in ENTRIES:
-            _abi.time_kernel(e, False)
+        F_.call = call
 
 
 def _check_layer_grads(got, want, products):

@@ -1,4 +1,4 @@
-"""trs_wgrad_rows_many + trs_wgrad_finish_many: the weight gradients of several dense layers over the same rows in one
+"""trs_wgrad_rows_many + one trs_wgrad_finish: the weight gradients of several dense layers over the same rows in one
 launch of the eight-wave LDS-DMA kernel of csrc/wgrad_rows.hip and one finish (the 400 x 400 tail layers of the deep
 branch: gz[0] (rows, 416) against h1 (rows, 512), gz[1] (rows, 416) against hidden[0] (rows, 416)).
 
@@ -67,8 +67,8 @@ def _run(dev, jobs, gs, xs, rows, S, dtype, gbf=None, rc_only=False, parts=None)
     _abi.call("trs_wgrad_rows_many", *args)
     gw = [torch.empty(j[0], j[1], dtype=dtype, device=dev) for j in jobs]
     gb = [torch.empty(j[0], dtype=dtype, device=dev) if gbf is not None else None for j in jobs]
-    _abi.call("trs_wgrad_finish_many", J, _pa(parts), S, Ms, Ns, Ms, Ns, _abi.value_dtype_code(gw[0]), _pa(gw),
-              _pa(gbf if gbf is not None else [None] * J), _pa(gb), _abi.stream_ptr())
+    _abi.call("trs_wgrad_finish", J, _pa(parts), S, Ms, Ns, Ms, Ns, _abi.value_dtype_code(gw[0]), _pa(gw),
+              _pa(gbf if gbf is not None else [None] * J), _pa(gb), None, None, _abi.stream_ptr())
     torch.cuda.synchronize()
     return gw, gb, parts
 
@@ -172,8 +172,8 @@ def test_wgrad_many_against_the_per_layer_entries(dev, case, rows):
                   _abi.stream_ptr())
         gw1 = torch.empty(M, N, dtype=BF16, device=dev)
         gb1 = torch.empty(M, dtype=BF16, device=dev)
-        _abi.call("trs_wgrad_finish", _abi.ptr(part), S1, M, N, M, N, _abi.TRS_BF16, _abi.ptr(gw1), _abi.ptr(gbf[n]),
-                  _abi.ptr(gb1), _abi.stream_ptr())
+        _abi.call("trs_wgrad_finish", 1, _pa([part]), S1, _ia([M]), _ia([N]), _ia([M]), _ia([N]), _abi.TRS_BF16, _pa([gw1]),
+                  _pa([gbf[n]]), _pa([gb1]), None, None, _abi.stream_ptr())
         torch.cuda.synchronize()
         diff = float((gw[n].float() - gw1.float()).abs().max()) / float(gw1.float().abs().max())
         print(f"job {n} ({M}x{N}, S {S} against {S1}): max difference {diff:.3e} of the maximum")
@@ -253,17 +253,21 @@ def test_hybrid_stack_routes_its_tail_through_the_batched_launch(dev, monkeypatc
     from torecsys_amd import _abi
     from torecsys_amd import functional as F_
     mlp, x, gout = _stack(dev, 8192)
+    n_jobs, call = [], F_.call      # the job count of every trs_wgrad_finish: a batched finish carries two or more
+    monkeypatch.setattr(F_, "call", lambda name, *a: (n_jobs.append(a[0]) if name == "trs_wgrad_finish" else None,
+                                                      call(name, *a))[1])
     _abi.time_kernel("trs_wgrad_rows_many", True)
-    _abi.time_kernel("trs_wgrad_finish_many", True)
+    _abi.time_kernel("trs_wgrad_finish", True)
     try:
         new, gx_new = _grads(mlp, x, gout)
-        assert len(_abi.kernel_times_ms("trs_wgrad_rows_many")) == 1 and len(_abi.kernel_times_ms("trs_wgrad_finish_many")) == 1
+        assert len(_abi.kernel_times_ms("trs_wgrad_rows_many")) == 1 and len(_abi.kernel_times_ms("trs_wgrad_finish")) == 1
+        assert len(n_jobs) == 1 and n_jobs[0] >= 2
         monkeypatch.setattr(F_, "_wgrad_many_splits", lambda jobs: 0)
         old, gx_old = _grads(mlp, x, gout)
         assert len(_abi.kernel_times_ms("trs_wgrad_rows_many")) == 0
     finally:
         _abi.time_kernel("trs_wgrad_rows_many", False)
-        _abi.time_kernel("trs_wgrad_finish_many", False)
+        _abi.time_kernel("trs_wgrad_finish", False)
     batched = [n for n, p in mlp.model.named_parameters() if tuple(p.shape) == (400, 400)]
     assert len(batched) == 2
     assert torch.equal(gx_new, gx_old)

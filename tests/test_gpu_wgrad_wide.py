@@ -78,7 +78,7 @@ def _reference(operands, shape, rows):
 def test_wgrad_wide_exact_sums(dev, operands, shape, which):
     """offset operand views (16-byte aligned, not at the start of their allocations), sentinels around the partials,
     the fp32 output of trs_wgrad_finish_t equal to the int64 product"""
-    from torecsys_amd import _abi
+    from torecsys_amd import _abi, functional as F_
     M, N, ldg = shape
     S = _slices(M, N, ldg)
     rows = _row_counts(S)[which]
@@ -97,8 +97,7 @@ def test_wgrad_wide_exact_sums(dev, operands, shape, which):
     part = pbuf[guard:guard + S * M * N]
     _abi.call("trs_wgrad_wide", _abi.ptr(x), M, _abi.ptr(g), ldg, rows, M, N, S, _abi.ptr(part), _abi.stream_ptr())
     gw = torch.empty(N, M, dtype=torch.float32, device=dev)
-    _abi.call("trs_wgrad_finish_t", _abi.ptr(part), S, M, N, N, M, _abi.value_dtype_code(gw), _abi.ptr(gw),
-              _abi.ptr(None), _abi.ptr(None), _abi.stream_ptr())
+    F_.wgrad_finish([(part, gw, None, None, N, M, N, M)], S, _abi.value_dtype_code(gw), transposed=True)
     torch.cuda.synchronize()
     assert bool((pbuf[:guard] == -12345.0).all()) and bool((pbuf[guard + S * M * N:] == -12345.0).all()), \
         "a sentinel next to the partials was overwritten"

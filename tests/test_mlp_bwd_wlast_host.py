@@ -9,7 +9,7 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["trs_mlp_fused_bwd_wlast_part_bytes", "trs_mlp_fused_bwd_data_wlast", "trs_wgrad_finish_many"]
+NEW = ["trs_mlp_fused_bwd_wlast_part_bytes", "trs_mlp_fused_bwd_data_wlast", "trs_wgrad_finish"]
 TILE, ROW_OWNER, MIXED = 1, 2, 3
 F32, BF16 = 0, 1
 
@@ -119,7 +119,7 @@ def test_bad_arguments_come_back_before_any_launch(lib):
     none = (ctypes.c_void_p * 1)(None)
     zero = _ia([0])
     fin = lambda n=1, S=1, ocols=_ia([400]), gw=none, gbf=fa, gb=fa, dtype=BF16: int(
-        lib.trs_wgrad_finish_many(n, none, S, zero, zero, zero, ocols, dtype, gw, gbf, gb, None))
+        lib.trs_wgrad_finish(n, none, S, zero, zero, zero, ocols, dtype, gw, gbf, gb, None, None, None))
     assert fin(gw=fa) == code["TRS_EINVAL"] and fin(gbf=none) == code["TRS_EINVAL"] and fin(gb=none) == code["TRS_EINVAL"]
     assert fin(ocols=zero) == code["TRS_EINVAL"] and fin(S=0) == code["TRS_EINVAL"]
     assert fin(n=0) == code["TRS_EINVAL"] and fin(n=9) == code["TRS_EINVAL"]

@@ -9,7 +9,7 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["trs_wgrad_wide_many_splits", "trs_wgrad_wide_many_map", "trs_wgrad_wide_many", "trs_wgrad_finish_t_many"]
+NEW = ["trs_wgrad_wide_many_splits", "trs_wgrad_wide_many_map", "trs_wgrad_wide_many", "trs_wgrad_finish_t"]
 # (M_x, ldx, N_g, ldg) per job: the benchmark's three (cur, h1 in 512-wide rows, hidden[0]) and a four-block job behind
 # the first layer
 DEEP = [(2496, 2496, 400, 512), (416, 512, 400, 416), (416, 416, 400, 416)]
@@ -127,12 +127,12 @@ def test_entries_refuse_before_any_launch(lib):
     assert lib.trs_wgrad_wide_many(3, (ctypes.c_void_p * 3)(16, 24, 16), ldx, p3, ldg, 8192, M, N, S, p3, None) == ESHAPE
     assert "aligned" in _abi.last_error()
     z3, none3 = _ia([0, 0, 0]), (ctypes.c_void_p * 3)(0, 0, 0)
-    assert lib.trs_wgrad_finish_t_many(0, none3, S, z3, z3, z3, z3, 1, none3, none3, none3, None) == EINVAL
-    assert lib.trs_wgrad_finish_t_many(9, none3, S, z3, z3, z3, z3, 1, none3, none3, none3, None) == EINVAL
-    assert lib.trs_wgrad_finish_t_many(3, none3, 0, z3, z3, z3, z3, 1, none3, none3, none3, None) == EINVAL
-    assert lib.trs_wgrad_finish_t_many(3, none3, S, z3, z3, z3, _ia([4, 4, 4]), 1, none3, p3, none3, None) == EINVAL
-    assert lib.trs_wgrad_finish_t_many(3, p3, S, z3, z3, z3, z3, 1, p3, none3, none3, None) == EINVAL      # sizes of 0
+    assert lib.trs_wgrad_finish_t(0, none3, S, z3, z3, z3, z3, 1, none3, none3, none3, None, None, None) == EINVAL
+    assert lib.trs_wgrad_finish_t(9, none3, S, z3, z3, z3, z3, 1, none3, none3, none3, None, None, None) == EINVAL
+    assert lib.trs_wgrad_finish_t(3, none3, 0, z3, z3, z3, z3, 1, none3, none3, none3, None, None, None) == EINVAL
+    assert lib.trs_wgrad_finish_t(3, none3, S, z3, z3, z3, _ia([4, 4, 4]), 1, none3, p3, none3, None, None, None) == EINVAL
+    assert lib.trs_wgrad_finish_t(3, p3, S, z3, z3, z3, z3, 1, p3, none3, none3, None, None, None) == EINVAL      # sizes of 0
     sz = _ia([32, 32, 32])
-    assert lib.trs_wgrad_finish_t_many(3, p3, S, sz, sz, _ia([33, 32, 32]), sz, 1, p3, none3, none3, None) == EINVAL
-    assert lib.trs_wgrad_finish_t_many(3, p3, S, sz, sz, sz, sz, 1, p3, p3, none3, None) == EINVAL          # gb_f32 without gb
-    assert lib.trs_wgrad_finish_t_many(3, p3, S, sz, sz, sz, sz, 7, p3, none3, none3, None) == -2           # dtype
+    assert lib.trs_wgrad_finish_t(3, p3, S, sz, sz, _ia([33, 32, 32]), sz, 1, p3, none3, none3, None, None, None) == EINVAL
+    assert lib.trs_wgrad_finish_t(3, p3, S, sz, sz, sz, sz, 1, p3, p3, none3, None, None, None) == EINVAL          # gb_f32 without gb
+    assert lib.trs_wgrad_finish_t(3, p3, S, sz, sz, sz, sz, 7, p3, none3, none3, None, None, None) == -2           # dtype

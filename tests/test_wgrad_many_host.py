@@ -8,7 +8,7 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["trs_wgrad_rows_many_splits", "trs_wgrad_rows_many_map", "trs_wgrad_rows_many", "trs_wgrad_finish_many"]
+NEW = ["trs_wgrad_rows_many_splits", "trs_wgrad_rows_many_map", "trs_wgrad_rows_many", "trs_wgrad_finish"]
 # (M, N, ldg, ldx) the eight-wave LDS-DMA kernel takes: blocks of 12 | 13 tiles, 2 x 2 and 2 x 4 / 4 x 2 of them
 SHAPES = [(400, 400, 416, 512), (400, 400, 416, 416), (416, 416, 416, 416), (384, 416, 384, 416), (400, 800, 416, 800),
           (832, 416, 832, 416)]

@@ -1,7 +1,7 @@
 """Weight gradients of the DeepFM / xDeepFM deep branch (2496-400-400-400): the first layer's cur (rows, 2496) against g1
 (rows, 512) and the two tail layers' h1 (rows, 512) / hidden[0] (rows, 416) against gz[0] / gz[1] (rows, 416).  Today's
-two products with their two finishes (trs_wgrad_rows_many + trs_wgrad_finish_many, trs_wgrad_wide + trs_wgrad_finish_t)
-against the merged pair (trs_wgrad_wide_many + trs_wgrad_finish_t_many), stand-alone with events, interleaved in one
+two products with their two finishes (trs_wgrad_rows_many + trs_wgrad_finish, trs_wgrad_wide + trs_wgrad_finish_t)
+against the merged pair (trs_wgrad_wide_many + one trs_wgrad_finish_t), stand-alone with events, interleaved in one
 process.
 usage (GPU box): python tools/wgrad_deep_probe.py [--rows R [R ...]]"""
 import argparse
@@ -60,16 +60,14 @@ def probe(rows):
         _abi.call("trs_wgrad_rows_many", 2, pa(gs[1:]), ldg, pa(xs[1:]), ldx, rows, Ms, Ns, St, pa(part_t), _abi.stream_ptr())
 
     def tail_finish():
-        _abi.call("trs_wgrad_finish_many", 2, pa(part_t), St, Ms, Ns, Ms, Ns, BF, pa(gw_old[1:]), pa(gbf[1:]), pa(gb[1:]),
-                  _abi.stream_ptr())
+        F_.wgrad_finish([(part_t[k], gw_old[1 + k], gbf[1 + k], gb[1 + k], 400, 400, 400, 400) for k in range(2)], St, BF)
 
     def first_product():
         _abi.call("trs_wgrad_wide", _abi.ptr(xs[0]), 2496, _abi.ptr(gs[0]), 512, rows, 2496, 400, Sw, _abi.ptr(part_w),
                   _abi.stream_ptr())
 
     def first_finish():
-        _abi.call("trs_wgrad_finish_t", _abi.ptr(part_w), Sw, 2496, 400, 400, 2496, BF, _abi.ptr(gw_old[0]), _abi.ptr(gbf[0]),
-                  _abi.ptr(gb[0]), _abi.stream_ptr())
+        F_.wgrad_finish([(part_w, gw_old[0], gbf[0], gb[0], 400, 2496, 400, 2496)], Sw, BF, transposed=True)
 
     def today():
         tail_product()
@@ -81,8 +79,8 @@ def probe(rows):
         _abi.call("trs_wgrad_wide_many", 3, pa(xs), lx, pa(gs), lg, rows, Mx, Ng, S, pa(part), _abi.stream_ptr())
 
     def merged_finish():
-        _abi.call("trs_wgrad_finish_t_many", 3, pa(part), S, Mx, Ng, ia([400] * 3), ia(in_f), BF, pa(gw_new), pa(gbf), pa(gb),
-                  _abi.stream_ptr())
+        F_.wgrad_finish([(part[k], gw_new[k], gbf[k], gb[k], 400, part[k].shape[1], 400, in_f[k]) for k in range(3)], S, BF,
+                        transposed=True)
 
     def merged():
         merged_product()

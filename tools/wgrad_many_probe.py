@@ -1,5 +1,5 @@
 """Weight gradients of the two 400 x 400 tail layers of the deep branch (gz[0] (rows, 416) against h1 (rows, 512) and
-gz[1] (rows, 416) against hidden[0] (rows, 416)): trs_wgrad_rows_many + trs_wgrad_finish_many against the per-layer calls
+gz[1] (rows, 416) against hidden[0] (rows, 416)): trs_wgrad_rows_many + one trs_wgrad_finish against the per-layer calls
 (two trs_wgrad_rows + two trs_wgrad_finish), stand-alone with events at 65 536 rows, interleaved in one process.
 usage (GPU box): python tools/wgrad_many_probe.py [--rows R]"""
 import argparse
@@ -44,8 +44,7 @@ def per_layer():
     for k in range(2):
         _abi.call("trs_wgrad_rows", _abi.ptr(gs[k]), gs[k].shape[1], _abi.ptr(xs[k]), xs[k].shape[1], rows, M, N, _abi.TRS_BF16,
                   S1, _abi.ptr(part1[k]), _abi.stream_ptr())
-        _abi.call("trs_wgrad_finish", _abi.ptr(part1[k]), S1, M, N, M, N, _abi.TRS_BF16, _abi.ptr(gw1[k]), _abi.ptr(gbf[k]),
-                  _abi.ptr(gb[k]), _abi.stream_ptr())
+        F_.wgrad_finish([(part1[k], gw1[k], gbf[k], gb[k], M, N, M, N)], S1, _abi.TRS_BF16)
 
 
 def many_kernel():
@@ -53,7 +52,7 @@ def many_kernel():
 
 
 def many_finish():
-    _abi.call("trs_wgrad_finish_many", 2, pa(part), S, Ms, Ns, Ms, Ns, _abi.TRS_BF16, pa(gw), pa(gbf), pa(gb), _abi.stream_ptr())
+    F_.wgrad_finish([(part[k], gw[k], gbf[k], gb[k], M, N, M, N) for k in range(2)], S, _abi.TRS_BF16)
 
 
 def many():
@@ -70,7 +69,7 @@ def once(fn):
     return a.elapsed_time(b) * 1e3
 
 
-arms = {"per-layer (2 x rows + 2 x finish)": per_layer, "many + finish_many": many, "many, product only": many_kernel,
+arms = {"per-layer (2 x rows + 2 x finish)": per_layer, "many + one finish": many, "many, product only": many_kernel,
         "many, finish only": many_finish}
 for fn in arms.values():
     for _ in range(3):

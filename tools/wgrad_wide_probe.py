@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from torecsys_amd import _abi, layers
+from torecsys_amd import functional as F_
 
 lib = _abi.load()
 dev = torch.device("cuda:0")
@@ -51,8 +52,7 @@ def kernel():
 
 
 def finish():
-    _abi.call("trs_wgrad_finish_t", _abi.ptr(part), S, M, N, N, M, _abi.TRS_BF16, _abi.ptr(gw), _abi.ptr(gbf), _abi.ptr(gb),
-              _abi.stream_ptr())
+    F_.wgrad_finish([(part, gw, gbf, gb, N, M, N, M)], S, _abi.TRS_BF16, transposed=True)
 
 
 kernel()
@@ -65,8 +65,7 @@ print(f"trs_wgrad_wide S={S}: kernel med {tk[0]:.1f} min {tk[1]:.1f} us | finish
 
 def library():
     p = torch.bmm(x.view(16, rows // 16, -1).transpose(1, 2), g.view(16, rows // 16, -1), out_dtype=torch.float32)
-    _abi.call("trs_wgrad_finish_t", _abi.ptr(p), 16, M, ldg, N, M, _abi.TRS_BF16, _abi.ptr(gw), _abi.ptr(gbf), _abi.ptr(gb),
-              _abi.stream_ptr())
+    F_.wgrad_finish([(p, gw, gbf, gb, ldg, M, N, M)], 16, _abi.TRS_BF16, transposed=True)
 
 
 tl = timeit(library)

@@ -37,22 +37,18 @@ SIGNATURES = {
     "trs_cat_head_fwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
     "trs_cat_head_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "trs_cat_head_bwd": (c_int32, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
-    "trs_wgrad_finish": (c_int32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
-    "trs_wgrad_finish_t": (c_int32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "trs_wgrad_finish": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "trs_wgrad_finish_t": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "trs_wgrad_rows_splits": (c_int32, [_I32, _I32, _I64]),
     "trs_wgrad_rows": (c_int32, [_P, _I32, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _P]),
     "trs_wgrad_rows_many_splits": (c_int32, [_I32, _P, _P, _P, _P, _I64]),
     "trs_wgrad_rows_many_map": (c_int32, [_I32, _P, _P, _P, _P, _I64, _I32, _P]),
     "trs_wgrad_rows_many": (c_int32, [_I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _P]),
-    "trs_wgrad_finish_many": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "trs_wgrad_wide_splits": (c_int32, [_I32, _I32, _I32, _I64]),
     "trs_wgrad_wide": (c_int32, [_P, _I32, _P, _I32, _I64, _I32, _I32, _I32, _P, _P]),
     "trs_wgrad_wide_many_splits": (c_int32, [_I32, _P, _P, _P, _P, _I64]),
     "trs_wgrad_wide_many_map": (c_int32, [_I32, _P, _P, _P, _P, _I64, _I32, _P]),
     "trs_wgrad_wide_many": (c_int32, [_I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _P]),
-    "trs_wgrad_finish_t_many": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
-    "trs_wgrad_finish_many_parts": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
-    "trs_wgrad_finish_t_many_parts": (c_int32, [_I32, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "trs_copy_padded_many":(c_int32, [_P, _I32, _I32, _I64, _P]),
     "trs_cin_glue_blocks": (c_int32, [_I64]),
     "trs_cin_glue_stats": (c_int32, [_P, _I64, _I32, _I32, _I32, _P, _P]),
@@ -389,28 +385,21 @@ def kernel_times_ms(name: str):
     return out
 
 
-# A form of an entry that takes its fp32 sources as partial rows launches the entry's own kernel once, like the plain
-# form: time_kernel / kernel_times_ms see it under the entry's name.
-_TIMED_AS = {"trs_wgrad_finish_many_parts": "trs_wgrad_finish_many",
-             "trs_wgrad_finish_t_many_parts": "trs_wgrad_finish_t_many"}
-
-
 def call(name: str, *args):
     """Call an int-returning entry point; raise RuntimeError with the library's message on failure."""
-    timed_as = _TIMED_AS.get(name, name)
-    rec = _timed.get(timed_as)
+    rec = _timed.get(name)
     if rec is not None:
         st = stream_ptr()
         if torch.cuda.is_current_stream_capturing():
             # a captured event pair keeps only the latest replay (and ROCm refuses external event records in a
             # capture): bracket the launch with two device-side timestamp marks instead; each replay appends a sample
-            ring = _mark_ring(timed_as)
+            ring = _mark_ring(name)
             lib = load()
             lib.trs_mark_timestamp(ctypes.c_void_p(ring.data_ptr()), _MARK_CAP, st)
             rc = getattr(lib, name)(*args)
             lib.trs_mark_timestamp(ctypes.c_void_p(ring.data_ptr()), _MARK_CAP, st)
         else:
-            ev = _every[timed_as]
+            ev = _every[name]
             ev[1] += 1
             if ev[1] % ev[0] == 0:
                 a, b = _HipEvent(), _HipEvent()

@@ -314,6 +314,9 @@ __device__ __forceinline__ void wgrad_finish_body(const float* __restrict__ part
   gw[(size_t)r * out_cols + c] = from_f32<T>((a0 + a1) + (a2 + a3));
 }
 
+// One job with loose arguments.  (The table kernel below with gridDim.z == 1 gives the same bits; it measured 21.35 us
+// against 21.03 at 400 x 400, S = 192, and its transposed twin 13.54 against 13.12 at 400 x 2496, S = 16, outside the
+// spread of either: profiles/wgrad_finish_entries.md.)
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restrict__ part, int S, int R, int Cc,
                                                           int out_rows, int out_cols, T* __restrict__ gw,
@@ -434,6 +437,7 @@ __device__ __forceinline__ void wgrad_finish_t_body(const float* __restrict__ pa
   }
 }
 
+// one job with loose arguments, as wgrad_finish_kernel
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_finish_t_kernel(const float* __restrict__ part, int S, int Cc, int R,
                                                             int out_rows, int out_cols, T* __restrict__ gw,
@@ -796,38 +800,8 @@ extern "C" int trs_relu_bwd_bias(const void* gy, const void* y, int64_t rows, in
   return check_launch("relu_bwd_bias");
 }
 
-extern "C" int trs_wgrad_finish(const float* part, int32_t S, int32_t R, int32_t Cc, int32_t out_rows, int32_t out_cols,
-                                int32_t dtype, void* gw, const float* gb_f32, void* gb, trs_stream_t stream) {
-  TRS_REQUIRE(S > 0 && R > 0 && Cc > 0 && out_rows > 0 && out_cols > 0 && out_rows <= R && out_cols <= Cc, TRS_EINVAL,
-              "wgrad_finish: bad size");
-  TRS_REQUIRE(part && gw, TRS_EINVAL, "wgrad_finish: NULL pointer");
-  TRS_REQUIRE((gb == nullptr) == (gb_f32 == nullptr), TRS_EINVAL, "wgrad_finish: gb and gb_f32 go together");
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish: dtype %d", dtype);
-  TRS_REQUIRE(gb == nullptr || out_rows <= ((out_cols + 255) / 256) * 256, TRS_ESHAPE,
-              "wgrad_finish: out_rows %d exceeds the bias row of workgroups", out_rows);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((out_cols + 255) / 256, out_rows + 1);
-  if (S >= 4 * WF_SL && (int64_t)grid.x * out_rows < 64) {      // few rows, many splits: 16 threads per column
-    dim3 gridf((out_cols + WF_COLS - 1) / WF_COLS, out_rows + 1);
-    if (dtype == TRS_F32)
-      hipLaunchKernelGGL((wgrad_finish_few_rows_kernel<float>), gridf, dim3(256), 0, s, part, S, R, Cc, out_rows, out_cols,
-                         (float*)gw, gb_f32, (float*)gb);
-    else
-      hipLaunchKernelGGL((wgrad_finish_few_rows_kernel<bf16_t>), gridf, dim3(256), 0, s, part, S, R, Cc, out_rows, out_cols,
-                         (bf16_t*)gw, gb_f32, (bf16_t*)gb);
-    return check_launch("wgrad_finish");
-  }
-  if (dtype == TRS_F32)
-    hipLaunchKernelGGL((wgrad_finish_kernel<float>), grid, dim3(256), 0, s, part, S, R, Cc, out_rows, out_cols,
-                       (float*)gw, gb_f32, (float*)gb);
-  else
-    hipLaunchKernelGGL((wgrad_finish_kernel<bf16_t>), grid, dim3(256), 0, s, part, S, R, Cc, out_rows, out_cols,
-                       (bf16_t*)gw, gb_f32, (bf16_t*)gb);
-  return check_launch("wgrad_finish");
-}
-
-// gb_nparts / gb_stride (both NULL in the plain entries): per job, gb_f32[k] is gb_nparts[k] > 0 partial rows gb_stride[k]
-// floats apart instead of a summed vector (wf_src)
+// gb_nparts / gb_stride (both NULL: every source is a summed vector): per job, gb_f32[k] is gb_nparts[k] > 0 partial rows
+// gb_stride[k] floats apart instead of a summed vector (wf_src)
 static int wgrad_finish_parts_ok(const char* who, int k, const float* gbf, int cols, const int32_t* gb_nparts,
                                  const int32_t* gb_stride) {
   if (gb_nparts == nullptr || gb_nparts[k] == 0) return TRS_OK;
@@ -836,146 +810,116 @@ static int wgrad_finish_parts_ok(const char* who, int k, const float* gbf, int c
   return TRS_OK;
 }
 
-static int wgrad_finish_many_impl(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
-                                  const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                  void* const* gw, const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
-                                  const int32_t* gb_stride, trs_stream_t stream) {
-  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
-  TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_many: NULL array");
-  TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_many: bad size");
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish_many: dtype %d", dtype);
-  WgradFinishArgs a{};
+// The checks and the job table of both finish entries (R / Cc: the partial's fast and slow dimension as the entry names
+// them).  ``bias_row_limit``: the bias cast of a job has one row of 256-wide workgroups (trs_wgrad_finish only).
+static int wgrad_finish_jobs(const char* who, bool bias_row_limit, int32_t n_jobs, const float* const* part, int32_t S,
+                             const int32_t* R, const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols,
+                             int32_t dtype, void* const* gw, const float* const* gb_f32, void* const* gb,
+                             const int32_t* gb_nparts, const int32_t* gb_stride, WgradFinishArgs& a) {
+  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "%s: %d jobs (1 .. %d)", who, n_jobs, WF_MAXJ);
+  TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "%s: NULL array", who);
+  TRS_REQUIRE((gb_nparts == nullptr) == (gb_stride == nullptr), TRS_EINVAL, "%s: gb_nparts and gb_stride go together", who);
+  TRS_REQUIRE(S > 0, TRS_EINVAL, "%s: bad size", who);
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "%s: dtype %d", who, dtype);
   a.S = S;
-  int max_rows = 0, max_cols = 0;
   for (int k = 0; k < n_jobs; ++k) {
+    const int np = gb_nparts ? gb_nparts[k] : 0, ps = gb_nparts ? gb_stride[k] : 0;
     if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
       TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
-                  "wgrad_finish_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
-      if (int rc = wgrad_finish_parts_ok("wgrad_finish_many", k, gb_f32[k], out_cols[k], gb_nparts, gb_stride)) return rc;
-      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k], gb_nparts ? gb_nparts[k] : 0,
-                                gb_nparts ? gb_stride[k] : 0};
-      max_cols = std::max(max_cols, out_cols[k]);
+                  "%s: a job without a product takes gb_f32, gb and out_cols only (job %d)", who, k);
+      if (int rc = wgrad_finish_parts_ok(who, k, gb_f32[k], out_cols[k], gb_nparts, gb_stride)) return rc;
+      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k], np, ps};
       continue;
     }
     TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
-                TRS_EINVAL, "wgrad_finish_many: bad size (job %d)", k);
-    TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_many: NULL pointer (job %d)", k);
-    TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_many: gb and gb_f32 go together (job %d)", k);
-    TRS_REQUIRE(gb[k] == nullptr || out_rows[k] <= ((out_cols[k] + 255) / 256) * 256, TRS_ESHAPE,
-                "wgrad_finish_many: out_rows %d exceeds the bias row of workgroups", out_rows[k]);
-    if (int rc = wgrad_finish_parts_ok("wgrad_finish_many", k, gb_f32[k], out_rows[k], gb_nparts, gb_stride)) return rc;
-    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k],
-                              gb_nparts ? gb_nparts[k] : 0, gb_nparts ? gb_stride[k] : 0};
-    max_rows = std::max(max_rows, out_rows[k]);
-    max_cols = std::max(max_cols, out_cols[k]);
+                TRS_EINVAL, "%s: bad size (job %d)", who, k);
+    TRS_REQUIRE(gw[k], TRS_EINVAL, "%s: NULL pointer (job %d)", who, k);
+    TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "%s: gb and gb_f32 go together (job %d)", who, k);
+    TRS_REQUIRE(!bias_row_limit || gb[k] == nullptr || out_rows[k] <= ((out_cols[k] + 255) / 256) * 256, TRS_ESHAPE,
+                "%s: out_rows %d exceeds the bias row of workgroups", who, out_rows[k]);
+    if (int rc = wgrad_finish_parts_ok(who, k, gb_f32[k], out_rows[k], gb_nparts, gb_stride)) return rc;
+    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k], np, ps};
+  }
+  return TRS_OK;
+}
+
+extern "C" int trs_wgrad_finish(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R, const int32_t* Cc,
+                                const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                                const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                const int32_t* gb_stride, trs_stream_t stream) {
+  WgradFinishArgs a{};
+  if (int rc = wgrad_finish_jobs("wgrad_finish", true, n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32, gb,
+                                 gb_nparts, gb_stride, a))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const WgradFinishJob& j = a.job[0];
+  if (n_jobs == 1 && j.part != nullptr && j.nparts == 0) {      // one product, its bias a plain vector: loose arguments
+    dim3 grid((j.out_cols + 255) / 256, j.out_rows + 1);
+    const bool few = S >= 4 * WF_SL && (int64_t)grid.x * j.out_rows < 64;      // few rows, many splits: 16 threads per column
+    if (few) grid.x = (j.out_cols + WF_COLS - 1) / WF_COLS;
+    if (dtype == TRS_F32)
+      hipLaunchKernelGGL((few ? wgrad_finish_few_rows_kernel<float> : wgrad_finish_kernel<float>), grid, dim3(256), 0, s, j.part,
+                         S, j.R, j.Cc, j.out_rows, j.out_cols, (float*)j.gw, j.gbf, (float*)j.gb);
+    else
+      hipLaunchKernelGGL((few ? wgrad_finish_few_rows_kernel<bf16_t> : wgrad_finish_kernel<bf16_t>), grid, dim3(256), 0, s,
+                         j.part, S, j.R, j.Cc, j.out_rows, j.out_cols, (bf16_t*)j.gw, j.gbf, (bf16_t*)j.gb);
+    return check_launch("wgrad_finish");
+  }
+  int max_rows = 0, max_cols = 0;      // the grid is sized by the largest job
+  for (int k = 0; k < n_jobs; ++k) {
+    max_rows = std::max(max_rows, a.job[k].out_rows);
+    max_cols = std::max(max_cols, a.job[k].out_cols);
   }
   for (int k = 0; k < n_jobs; ++k)      // a cast-only job on partial rows: 16 columns per workgroup of the (x, y) plane
-    if (part[k] == nullptr && a.job[k].nparts > 0) {
-      const int gx = (max_cols + 255) / 256, need = (out_cols[k] + 15) / 16;
+    if (a.job[k].part == nullptr && a.job[k].nparts > 0) {
+      const int gx = (max_cols + 255) / 256, need = (a.job[k].out_cols + 15) / 16;
       if (gx * (max_rows + 1) < need) max_rows = (need + gx - 1) / gx - 1;
     }
   dim3 grid((max_cols + 255) / 256, max_rows + 1, n_jobs);
   if (dtype == TRS_F32)
-    hipLaunchKernelGGL((wgrad_finish_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((wgrad_finish_many_kernel<float>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((wgrad_finish_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("wgrad_finish_many");
+    hipLaunchKernelGGL((wgrad_finish_many_kernel<bf16_t>), grid, dim3(256), 0, s, a);
+  return check_launch("wgrad_finish");
 }
 
-extern "C" int trs_wgrad_finish_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
-                                     const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                     void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
-  return wgrad_finish_many_impl(n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32, gb, nullptr, nullptr, stream);
-}
-
-/* trs_wgrad_finish_many whose fp32 source per job may be a set of per-workgroup partial rows (gb_nparts[k] > 0 rows,
- * gb_stride[k] floats apart; 0: a summed vector as ever): the partials trs_mlp_fused_bwd_data_parts reports, added in the
- * order of that backward's own reduce launch, so that every cast value keeps its bits */
-extern "C" int trs_wgrad_finish_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* R,
-                                           const int32_t* Cc, const int32_t* out_rows, const int32_t* out_cols,
-                                           int32_t dtype, void* const* gw, const float* const* gb_f32, void* const* gb,
-                                           const int32_t* gb_nparts, const int32_t* gb_stride, trs_stream_t stream) {
-  TRS_REQUIRE(gb_nparts && gb_stride, TRS_EINVAL, "wgrad_finish_many_parts: NULL array");
-  return wgrad_finish_many_impl(n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32, gb, gb_nparts, gb_stride,
-                                stream);
-}
-
-extern "C" int trs_wgrad_finish_t(const float* part, int32_t S, int32_t Cc, int32_t R, int32_t out_rows, int32_t out_cols,
-                                  int32_t dtype, void* gw, const float* gb_f32, void* gb, trs_stream_t stream) {
-  TRS_REQUIRE(S > 0 && R > 0 && Cc > 0 && out_rows > 0 && out_cols > 0 && out_rows <= R && out_cols <= Cc, TRS_EINVAL,
-              "wgrad_finish_t: bad size");
-  TRS_REQUIRE(part && gw, TRS_EINVAL, "wgrad_finish_t: NULL pointer");
-  TRS_REQUIRE((gb == nullptr) == (gb_f32 == nullptr), TRS_EINVAL, "wgrad_finish_t: gb and gb_f32 go together");
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish_t: dtype %d", dtype);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((out_rows + 31) / 32, (out_cols + 31) / 32 + 1);
-  if (dtype == TRS_F32)
-    hipLaunchKernelGGL((wgrad_finish_t_kernel<float>), grid, dim3(256), 0, s, part, S, Cc, R, out_rows, out_cols,
-                       (float*)gw, gb_f32, (float*)gb);
-  else
-    hipLaunchKernelGGL((wgrad_finish_t_kernel<bf16_t>), grid, dim3(256), 0, s, part, S, Cc, R, out_rows, out_cols,
-                       (bf16_t*)gw, gb_f32, (bf16_t*)gb);
-  return check_launch("wgrad_finish_t");
-}
-
-static int wgrad_finish_t_many_impl(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
-                                    const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                    void* const* gw, const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
-                                    const int32_t* gb_stride, trs_stream_t stream) {
-  TRS_REQUIRE(n_jobs >= 1 && n_jobs <= WF_MAXJ, TRS_EINVAL, "wgrad_finish_t_many: %d jobs (1 .. %d)", n_jobs, WF_MAXJ);
-  TRS_REQUIRE(part && R && Cc && out_rows && out_cols && gw && gb_f32 && gb, TRS_EINVAL, "wgrad_finish_t_many: NULL array");
-  TRS_REQUIRE(S > 0, TRS_EINVAL, "wgrad_finish_t_many: bad size");
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "wgrad_finish_t_many: dtype %d", dtype);
+extern "C" int trs_wgrad_finish_t(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc, const int32_t* R,
+                                  const int32_t* out_rows, const int32_t* out_cols, int32_t dtype, void* const* gw,
+                                  const float* const* gb_f32, void* const* gb, const int32_t* gb_nparts,
+                                  const int32_t* gb_stride, trs_stream_t stream) {
   WgradFinishArgs a{};
-  a.S = S;
-  int gx = 1, gy = 1;
-  for (int k = 0; k < n_jobs; ++k) {
-    if (part[k] == nullptr) {      // cast only: gb[k][0 .. out_cols[k]) = gb_f32[k][...], nothing else of the job is read
-      TRS_REQUIRE(gw[k] == nullptr && gb[k] && gb_f32[k] && out_cols[k] > 0, TRS_EINVAL,
-                  "wgrad_finish_t_many: a job without a product takes gb_f32, gb and out_cols only (job %d)", k);
-      if (int rc = wgrad_finish_parts_ok("wgrad_finish_t_many", k, gb_f32[k], out_cols[k], gb_nparts, gb_stride)) return rc;
-      a.job[k] = WgradFinishJob{nullptr, nullptr, gb_f32[k], gb[k], 0, 0, 0, out_cols[k], gb_nparts ? gb_nparts[k] : 0,
-                                gb_nparts ? gb_stride[k] : 0};
-      continue;
-    }
-    TRS_REQUIRE(R[k] > 0 && Cc[k] > 0 && out_rows[k] > 0 && out_cols[k] > 0 && out_rows[k] <= R[k] && out_cols[k] <= Cc[k],
-                TRS_EINVAL, "wgrad_finish_t_many: bad size (job %d)", k);
-    TRS_REQUIRE(part[k] && gw[k], TRS_EINVAL, "wgrad_finish_t_many: NULL pointer (job %d)", k);
-    TRS_REQUIRE((gb[k] == nullptr) == (gb_f32[k] == nullptr), TRS_EINVAL, "wgrad_finish_t_many: gb and gb_f32 go together (job %d)", k);
-    if (int rc = wgrad_finish_parts_ok("wgrad_finish_t_many", k, gb_f32[k], out_rows[k], gb_nparts, gb_stride)) return rc;
-    a.job[k] = WgradFinishJob{part[k], gw[k], gb_f32[k], gb[k], R[k], Cc[k], out_rows[k], out_cols[k],
-                              gb_nparts ? gb_nparts[k] : 0, gb_nparts ? gb_stride[k] : 0};
-    gx = std::max(gx, (out_rows[k] + 31) / 32);
-    gy = std::max(gy, (out_cols[k] + 31) / 32 + 1);
+  if (int rc = wgrad_finish_jobs("wgrad_finish_t", false, n_jobs, part, S, R, Cc, out_rows, out_cols, dtype, gw, gb_f32,
+                                 gb, gb_nparts, gb_stride, a))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const WgradFinishJob& j = a.job[0];
+  if (n_jobs == 1 && j.part != nullptr && j.nparts == 0) {      // one product, its bias a plain vector: loose arguments
+    dim3 grid((j.out_rows + 31) / 32, (j.out_cols + 31) / 32 + 1);
+    if (dtype == TRS_F32)
+      hipLaunchKernelGGL((wgrad_finish_t_kernel<float>), grid, dim3(256), 0, s, j.part, S, j.Cc, j.R, j.out_rows, j.out_cols,
+                         (float*)j.gw, j.gbf, (float*)j.gb);
+    else
+      hipLaunchKernelGGL((wgrad_finish_t_kernel<bf16_t>), grid, dim3(256), 0, s, j.part, S, j.Cc, j.R, j.out_rows, j.out_cols,
+                         (bf16_t*)j.gw, j.gbf, (bf16_t*)j.gb);
+    return check_launch("wgrad_finish_t");
   }
+  int gx = 1, gy = 1;
+  for (int k = 0; k < n_jobs; ++k)
+    if (a.job[k].part != nullptr) {
+      gx = std::max(gx, (a.job[k].out_rows + 31) / 32);
+      gy = std::max(gy, (a.job[k].out_cols + 31) / 32 + 1);
+    }
   for (int k = 0; k < n_jobs; ++k)      // a cast-only job's columns, 256 per workgroup of the (gx, gy) plane
-    if (part[k] == nullptr) {         // (on partial rows: 16 per workgroup)
-      const int need = a.job[k].nparts > 0 ? (out_cols[k] + 15) / 16 : (out_cols[k] + 255) / 256;
+    if (a.job[k].part == nullptr) {   // (on partial rows: 16 per workgroup)
+      const int need = a.job[k].nparts > 0 ? (a.job[k].out_cols + 15) / 16 : (a.job[k].out_cols + 255) / 256;
       if (need > gx * gy) gx = (need + gy - 1) / gy;
     }
   dim3 grid(gx, gy, n_jobs);
   if (dtype == TRS_F32)
-    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<float>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("wgrad_finish_t_many");
-}
-
-extern "C" int trs_wgrad_finish_t_many(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
-                                       const int32_t* R, const int32_t* out_rows, const int32_t* out_cols, int32_t dtype,
-                                       void* const* gw, const float* const* gb_f32, void* const* gb, trs_stream_t stream) {
-  return wgrad_finish_t_many_impl(n_jobs, part, S, Cc, R, out_rows, out_cols, dtype, gw, gb_f32, gb, nullptr, nullptr,
-                                  stream);
-}
-
-/* trs_wgrad_finish_t_many with partial-row sources, as trs_wgrad_finish_many_parts */
-extern "C" int trs_wgrad_finish_t_many_parts(int32_t n_jobs, const float* const* part, int32_t S, const int32_t* Cc,
-                                             const int32_t* R, const int32_t* out_rows, const int32_t* out_cols,
-                                             int32_t dtype, void* const* gw, const float* const* gb_f32, void* const* gb,
-                                             const int32_t* gb_nparts, const int32_t* gb_stride, trs_stream_t stream) {
-  TRS_REQUIRE(gb_nparts && gb_stride, TRS_EINVAL, "wgrad_finish_t_many_parts: NULL array");
-  return wgrad_finish_t_many_impl(n_jobs, part, S, Cc, R, out_rows, out_cols, dtype, gw, gb_f32, gb, gb_nparts, gb_stride,
-                                  stream);
+    hipLaunchKernelGGL((wgrad_finish_t_many_kernel<bf16_t>), grid, dim3(256), 0, s, a);
+  return check_launch("wgrad_finish_t");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1334,7 +1334,7 @@ extern "C" int trs_rows_gemm(const void* x, int64_t rows, int32_t x_stride, cons
  * ``workspace`` / ``wl_part`` -- set l (0 .. L-1): layer l's bias gradient, pad32(widths[l+1]) columns; set L: the input's
  * (with mask_in, else NULL); set L+1+j: row j of the output layer's dW, pad32(widths[L-1]) columns (NULL from ``live`` on).
  * Value c of a set is the sum over p < nparts of part[p * stride + c], taken as mlp_colsum_reduce_many_kernel takes it
- * (trs_wgrad_finish_many_parts / trs_wgrad_finish_t_many_parts do): the buffers must stay allocated until that launch is
+ * (trs_wgrad_finish / trs_wgrad_finish_t with gb_nparts do): the buffers must stay allocated until that launch is
  * enqueued.  TILE and MIXED families, rows > 0. */
 extern "C" int trs_mlp_fused_bwd_data_parts(const void* gy, int32_t gy_stride, int64_t rows, int32_t num_layers,
                                             const int32_t* widths, const void* const* weights, const void* const* masks,

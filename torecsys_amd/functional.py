@@ -3584,12 +3584,35 @@ def _plain_sum(t):
     return colsum_parts_reduce([t])[0] if t is not None and t.dim() == 2 else t
 
 
-def _parts_arrays(srcs):
-    """(gb_nparts, gb_stride) of the ``*_parts`` finishes for fp32 sources that are vectors or partial sets; None: all plain"""
-    if not any(t is not None and t.dim() == 2 for t in srcs):
-        return None
-    return (_i32_array([t.shape[0] if t is not None and t.dim() == 2 else 0 for t in srcs]),
-            _i32_array([t.stride(0) if t is not None and t.dim() == 2 else 0 for t in srcs]))
+def wgrad_bias_rides(out_f: int, in_f: int) -> bool:
+    """the bias cast of an (out_f, in_f) layer fits the one row of workgroups trs_wgrad_finish has for it"""
+    return out_f <= (in_f + 255) // 256 * 256
+
+
+def wgrad_finish(jobs, S: int, dtype_code: int, transposed: bool = False):
+    """The finish of 1 .. 8 split-K weight gradients in one launch: trs_wgrad_finish, or trs_wgrad_finish_t for partial
+    products stored transposed.  ``jobs`` = [(part, gw, gb_f32, gb, R, Cc, out_rows, out_cols)]: gw (out_rows, out_cols)
+    out of part (S, R, Cc) -- (S, Cc, R) transposed --, gb = the cast of gb_f32 (both or neither).  A 2-D gb_f32 is a set
+    of partial rows (fused_mlp_backward_raw with ``parts``), which the launch folds itself.  ``part`` None: a job without a
+    product, gb[:out_cols] = the cast of gb_f32, nothing else of the job is read."""
+    # The entry's ten arrays as two allocations, n entries per array: part, gw, gb_f32, gb | the partial's two dimensions in
+    # the entry's order, out_rows, out_cols, gb_nparts, gb_stride.  (An array object per argument cost 6 us of host time
+    # for one job, against 1 us for the scalar arguments the one-job entries used to take; this is 1.6.)
+    n = len(jobs)
+    ptrs, ints = (ctypes.c_void_p * (4 * n))(), (ctypes.c_int32 * (6 * n))()
+    sets = False
+    for k, (part, gw, gb_f32, gb, R, Cc, out_rows, out_cols) in enumerate(jobs):
+        for f, t in enumerate((part, gw, gb_f32, gb)):
+            if t is not None:
+                ptrs[f * n + k] = t.data_ptr()
+        if gb_f32 is not None and gb_f32.dim() == 2:
+            sets, ints[4 * n + k], ints[5 * n + k] = True, gb_f32.shape[0], gb_f32.stride(0)
+        ints[k], ints[n + k] = (Cc, R) if transposed else (R, Cc)
+        ints[2 * n + k], ints[3 * n + k] = out_rows, out_cols
+    p, i = ctypes.addressof(ptrs), ctypes.addressof(ints)
+    call("trs_wgrad_finish_t" if transposed else "trs_wgrad_finish", n, p, S, i, i + 4 * n, i + 8 * n, i + 12 * n,
+         dtype_code, p + 8 * n, p + 16 * n, p + 24 * n, i + 16 * n if sets else None, i + 20 * n if sets else None,
+         stream_ptr())
 
 
 class _FusedMLP(Function):
@@ -3745,7 +3768,7 @@ def wgrad_deep_splits_for(rows: int, dims) -> int:
 
 
 def _wgrad_deep(jobs, S, casts):
-    """the merged product and its finish; ``casts`` ride as jobs without a product.  Returns [(dW, db or None)] per job."""
+    """the merged product and its finish; ``casts``: jobs without a product (see wgrad_finish) that ride in it.  Returns [(dW, db or None)] per job."""
     dev, rows = jobs[0][0].device, int(jobs[0][0].shape[0])
     parts = [torch.empty(S, j[2], j[3], dtype=torch.float32, device=dev) for j in jobs]
     call("trs_wgrad_wide_many", len(jobs), _ptr_array([j[0] for j in jobs]), _i32_array([j[0].shape[1] for j in jobs]),
@@ -3753,15 +3776,8 @@ def _wgrad_deep(jobs, S, casts):
          _i32_array([j[2] for j in jobs]), _i32_array([j[3] for j in jobs]), S, _ptr_array(parts), stream_ptr())
     gws = [torch.empty(j[4], j[5], dtype=torch.bfloat16, device=dev) for j in jobs]
     gbs = [torch.empty(j[4], dtype=torch.bfloat16, device=dev) if j[6] is not None else None for j in jobs]
-    n = len(casts)
-    srcs = [j[6] for j in jobs] + [c[1] for c in casts]
-    sets = _parts_arrays(srcs)      # fp32 sources that are partial rows of the fused backward: the finish folds them
-    call("trs_wgrad_finish_t_many" if sets is None else "trs_wgrad_finish_t_many_parts", len(jobs) + n,
-         _ptr_array(parts + [None] * n), S,
-         _i32_array([j[2] for j in jobs] + [0] * n), _i32_array([j[3] for j in jobs] + [0] * n),
-         _i32_array([j[4] for j in jobs] + [0] * n), _i32_array([j[5] for j in jobs] + [c[0] for c in casts]),
-         _abi.TRS_BF16, _ptr_array(gws + [None] * n), _ptr_array(srcs),
-         _ptr_array(gbs + [c[2] for c in casts]), *(sets or ()), stream_ptr())
+    wgrad_finish([(p, gw, j[6], gb, j[3], j[2], j[4], j[5]) for p, gw, gb, j in zip(parts, gws, gbs, jobs)] + casts, S,
+                 _abi.TRS_BF16, transposed=True)
     return list(zip(gws, gbs))
 
 
@@ -3783,29 +3799,19 @@ def _tail_grads(layers, gw_last=None, first=None):
     jobs = [(layers[k][0], layers[k][1], min(layers[k][0].shape[1], (layers[k][2] + 7) // 8 * 8),
              min(layers[k][1].shape[1], (layers[k][3] + 7) // 8 * 8)) for k in batch]
     S = _wgrad_many_splits(jobs) if S_deep == 0 and len({layers[k][4] for k in batch}) == 1 else 0
-    # the output layer as cast-only jobs of the finish (part = gw = None): (out_cols, fp32 source, destination) per row
+    # the output layer as cast-only jobs of the finish (part = gw = None, see wgrad_finish), one per row
     casts = []
     if gw_last is not None:
         _, _, out_f, in_f, dt, gb_f32, _, need_b = layers[-1]
         gw = torch.empty(out_f, in_f, dtype=dt, device=gw_last.device)
         gbias = torch.empty(out_f, dtype=dt, device=gw_last.device) if need_b else None
         # (gw_last as partial rows, (nparts, out_f, padded in_f): row r's set is gw_last[:, r])
-        casts = [(in_f, gw_last[r] if gw_last.dim() == 2 else gw_last[:, r], gw[r]) for r in range(out_f)] + \
-                ([(out_f, gb_f32, gbias)] if need_b else [])
+        casts = [(None, None, gw_last[r] if gw_last.dim() == 2 else gw_last[:, r], gw[r], 0, 0, 0, in_f)
+                 for r in range(out_f)] + ([(None, None, gb_f32, gbias, 0, 0, 0, out_f)] if need_b else [])
         out[-1] = (gw, gbias)
 
     # Any fp32 bias gradient (and gw_last) may be a set of partial rows (fused_mlp_backward_raw with ``parts``): the
     # batched finishes fold such a set themselves; whatever does not end in one is summed by colsum_parts_reduce first.
-    def finish(parts, S, R, Cc, orows, ocols, gws, gbfs, gbs, dtype_code, extra):
-        n = len(extra)
-        srcs = gbfs + [c[1] for c in extra]
-        sets = _parts_arrays(srcs)
-        call("trs_wgrad_finish_many" if sets is None else "trs_wgrad_finish_many_parts", len(parts) + n,
-             _ptr_array(parts + [None] * n), S, _i32_array(R + [0] * n),
-             _i32_array(Cc + [0] * n), _i32_array(orows + [0] * n), _i32_array(ocols + [c[0] for c in extra]), dtype_code,
-             _ptr_array(gws + [None] * n), _ptr_array(srcs), _ptr_array(gbs + [c[2] for c in extra]), *(sets or ()),
-             stream_ptr())
-
     first_out = None
     if S_deep > 0:
         ride_casts = casts if casts and layers[-1][4] == torch.bfloat16 and len(deep) + len(casts) <= 8 else []
@@ -3824,12 +3830,12 @@ def _tail_grads(layers, gw_last=None, first=None):
         for k in batch:
             _, _, out_f, in_f, _, gb_f32, _, need_b = layers[k]
             gws.append(torch.empty(out_f, in_f, dtype=dtype, device=dev))
-            ride = need_b and out_f <= (in_f + 255) // 256 * 256      # the bias cast rides in the finish (see _wgrad_rows)
+            ride = need_b and wgrad_bias_rides(out_f, in_f)      # the bias cast rides in the finish (see _wgrad_rows)
             gbs.append(torch.empty(out_f, dtype=dtype, device=dev) if ride else None)
             gbfs.append(gb_f32 if ride else None)
         ride_casts = casts if casts and layers[-1][4] == dtype and len(jobs) + len(casts) <= 8 else []
-        finish(parts, S, [j[2] for j in jobs], [j[3] for j in jobs], [layers[k][2] for k in batch],
-               [layers[k][3] for k in batch], gws, gbfs, gbs, value_dtype_code(gws[0]), ride_casts)
+        wgrad_finish([(parts[n], gws[n], gbfs[n], gbs[n], jobs[n][2], jobs[n][3], layers[k][2], layers[k][3])
+                      for n, k in enumerate(batch)] + ride_casts, S, value_dtype_code(gws[0]))
         if ride_casts:
             casts = []
         for n, k in enumerate(batch):
@@ -3838,7 +3844,7 @@ def _tail_grads(layers, gw_last=None, first=None):
                 gb = _plain_sum(layers[k][5])[:layers[k][2]].to(dtype)
             out[k] = (gws[n], gb)
     if casts:      # no batched finish to ride in: a launch of their own
-        finish([], 1, [], [], [], [], [], [], [], value_dtype_code(casts[0][2]), casts)
+        wgrad_finish(casts, 1, value_dtype_code(casts[0][3]))
     for k, t in enumerate(layers):
         if out[k] is None:
             out[k] = _tail_layer_grads(*t[:5], _plain_sum(t[5]) if t[7] else None, *t[6:])
@@ -3862,7 +3868,7 @@ def _wgrad_rows(g: torch.Tensor, inp: torch.Tensor, out_f: int, in_f: int, dtype
     gradient, at least out_f entries) returns (dW, db): the cast of the bias gradient rides in the same finish launch."""
     if gb_f32 is not None:
         gb = torch.empty(out_f, dtype=dtype, device=g.device)
-        if out_f <= (in_f + 255) // 256 * 256:
+        if wgrad_bias_rides(out_f, in_f):
             return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb), gb
         gb.copy_(gb_f32[:out_f])
         return _wgrad_rows_impl(g, inp, out_f, in_f, dtype, None, None), gb
@@ -3882,8 +3888,7 @@ def _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb):
             call("trs_wgrad_rows", ptr(g), g.shape[1], ptr(inp), inp.shape[1], rows, M, N,
                  _abi.TRS_BF16, S, ptr(part), stream_ptr())
             gw = torch.empty(out_f, in_f, dtype=dtype, device=g.device)
-            call("trs_wgrad_finish", ptr(part), S, M, N, out_f, in_f, value_dtype_code(gw),
-                 ptr(gw), ptr(gb_f32), ptr(gb), stream_ptr())
+            wgrad_finish([(part, gw, gb_f32, gb, M, N, out_f, in_f)], S, value_dtype_code(gw))
             return gw
     S = 0
     # 192 batches measured best at 2.5 M rows (416 x 416: 1.33 ms against 1.48 at 384 and 1.53 at 96; 416 x 64: 0.49 against
@@ -3898,8 +3903,7 @@ def _wgrad_rows_impl(g, inp, out_f, in_f, dtype, gb_f32, gb):
         return (g.t() @ inp)[:out_f, :in_f].contiguous().to(dtype)
     part = torch.bmm(g.view(S, rows // S, -1).transpose(1, 2), inp.view(S, rows // S, -1), out_dtype=torch.float32)
     gw = torch.empty(out_f, in_f, dtype=dtype, device=g.device)
-    call("trs_wgrad_finish", ptr(part), S, part.shape[1], part.shape[2], out_f, in_f, value_dtype_code(gw), ptr(gw),
-         ptr(gb_f32), ptr(gb), stream_ptr())
+    wgrad_finish([(part, gw, gb_f32, gb, part.shape[1], part.shape[2], out_f, in_f)], S, value_dtype_code(gw))
     return gw
 
 

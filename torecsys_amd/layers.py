@@ -812,8 +812,8 @@ def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b
                     F_.ptr(part), F_.stream_ptr())
             with_b = need_b and gbf is not None
             gb = torch.empty(out_f, dtype=wdt, device=xin.device) if with_b else None
-            F_.call("trs_wgrad_finish_t", F_.ptr(part), Sw, in_f, out_f, out_f, in_f, F_.value_dtype_code(gw),
-                    F_.ptr(gw), F_.ptr(gbf) if with_b else F_.ptr(None), F_.ptr(gb), F_.stream_ptr())
+            F_.wgrad_finish([(part, gw, gbf if with_b else None, gb, out_f, in_f, out_f, in_f)], Sw,
+                            F_.value_dtype_code(gw), transposed=True)
             gw_out = gw
             if with_b:
                 gb_out = gb
@@ -828,17 +828,15 @@ def _dense_layer_grads(g2, gbf, xin, W, out_f, in_f, wdt, need_x, need_w, need_b
                                  out_dtype=torch.float32)
                 with_b = need_b and gbf is not None
                 gb = torch.empty(out_f, dtype=wdt, device=xin.device) if with_b else None
-                F_.call("trs_wgrad_finish_t", F_.ptr(part), St, part.shape[1], part.shape[2], out_f, in_f,
-                        F_.value_dtype_code(gw), F_.ptr(gw), F_.ptr(gbf) if with_b else F_.ptr(None), F_.ptr(gb),
-                        F_.stream_ptr())
+                F_.wgrad_finish([(part, gw, gbf if with_b else None, gb, part.shape[2], part.shape[1], out_f, in_f)], St,
+                                F_.value_dtype_code(gw), transposed=True)
             else:
                 part = torch.bmm(g2.view(S, rows // S, -1).transpose(1, 2), xin.view(S, rows // S, -1),
                                  out_dtype=torch.float32)
-                with_b = need_b and gbf is not None and out_f <= (in_f + 255) // 256 * 256
+                with_b = need_b and gbf is not None and F_.wgrad_bias_rides(out_f, in_f)
                 gb = torch.empty(out_f, dtype=wdt, device=xin.device) if with_b else None
-                F_.call("trs_wgrad_finish", F_.ptr(part), S, part.shape[1], part.shape[2], out_f, in_f,
-                        F_.value_dtype_code(gw), F_.ptr(gw), F_.ptr(gbf) if with_b else F_.ptr(None), F_.ptr(gb),
-                        F_.stream_ptr())
+                F_.wgrad_finish([(part, gw, gbf if with_b else None, gb, part.shape[1], part.shape[2], out_f, in_f)], S,
+                                F_.value_dtype_code(gw))
             gw_out = gw
             if with_b:
                 gb_out = gb
