@@ -584,43 +584,38 @@ size_t trs_cin_cl_workspace_bytes(int32_t N, int32_t H, int32_t C);
 int trs_cin_cl_fwd(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* Wc,
                    const void* bias, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E, int32_t dtype,
                    int32_t tri, void* yT, void* workspace, size_t ws_bytes, trs_stream_t stream);
-/* data gradients of the same contraction, channels-last: given gyT (B,E,C)
+/* data gradients of the same contraction, channels-last: given gyT (B,E,>=C) with ldg channels between two pixels
+ * (ldg >= C, ldg % 8 == 0) and Wc = the first C rows of the layer's weight, C = the channels contracted over:
  *   dx0T (B,E,ld0)  : dx0T[b,e,n] = sum_{c,h} gy*Wc*xk   (zeros past N)
  *   dxkT rows of stride ldo (>= 32*ceil(H/32)): dxkT[b*E+e,h] = sum_{c,n} gy*Wc*x0
  * Requirements: C in {32,64,128,256}, E % 16 == 0.  bias gradient = sum of gy over (b,e) (caller).
+ * ldg > C serves a layer whose output channels beyond the first C receive NO gradient: the reference splits EVERY CIN
+ * layer's 2H output channels into a "direct" and a "hidden" half (compress_interaction_network.py:151-156: the
+ * `i != len-1` guard is always true) and never uses the LAST layer's hidden half (:176-181 reads the direct halves only),
+ * so dL/dy of those channels is exactly zero -- through BatchNorm and the activation too, which act per channel.  Their
+ * terms of the contraction over c are zeros that need not be computed: the results are identical to ldg == C on the full
+ * tensors.
  * tri: as in trs_cin_cl_fwd; xkT is x0T there, so the two gradients belong to the same values: dx0T receives
  * their SUM (added in fp32, rounded once) and dxkT is not written (may be NULL).                        */
 size_t trs_cin_cl_bwd_data_workspace_bytes(int32_t N, int32_t H, int32_t C);
-int trs_cin_cl_bwd_data(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* gyT,
-                        const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E,
-                        int32_t dtype, int32_t tri, void* dx0T, void* dxkT, int32_t ldo, void* workspace,
-                        size_t ws_bytes, trs_stream_t stream);
+int trs_cin_cl_bwd_data(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* gyT, int32_t ldg,
+                        const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E, int32_t dtype,
+                        int32_t tri, void* dx0T, void* dxkT, int32_t ldo, void* workspace, size_t ws_bytes,
+                        trs_stream_t stream);
 
 /* weight gradient of the same contraction on the matrix cores; CHANNELS-FIRST operands (the sum runs over
- * pixels, which must be the contiguous axis): gy (B,C,E), x0 (B,N,E), xk (B,H,E) bf16;
+ * pixels, which must be the contiguous axis): gy (B,>=C,E) with gy_batch_stride elements between two samples
+ * (>= C*E, a multiple of 8, < 2^31), x0 (B,N,E), xk (B,H,E) bf16;
  * dW (C, N*H) fp32 is ACCUMULATED into (zero it first).  C in {64,128,256}, E in {32,64,128}.
- * tri != 0 (needs xk == x0, N == H): the first layer, where dW[c,n,h] is symmetric in (n,h) -- only the
- * 16-h blocks at or below the diagonal are computed and the rest is mirrored; the result is the same full
+ * gy_batch_stride > C*E: the layer's channels beyond the first C receive no gradient (see trs_cin_cl_bwd_data); dW is
+ * then the first C rows of the gradient and the caller zero-fills the rest.
+ * tri != 0 (needs xk == x0, N == H, gy_batch_stride == C*E): the first layer, where dW[c,n,h] is symmetric in (n,h) --
+ * only the 16-h blocks at or below the diagonal are computed and the rest is mirrored; the result is the same full
  * (C, N*H) gradient of the UNFOLDED weights.                                                          */
 size_t trs_cin_dw_workspace_bytes(int64_t B, int32_t N, int32_t H, int32_t C);
-int trs_cin_dw(const void* gy, const void* x0, const void* xk, int64_t B, int32_t N, int32_t H, int32_t C,
-               int32_t E, int32_t dtype, int32_t tri, float* dW, void* workspace, size_t ws_bytes,
+int trs_cin_dw(const void* gy, int64_t gy_batch_stride, const void* x0, const void* xk, int64_t B, int32_t N, int32_t H,
+               int32_t C, int32_t E, int32_t dtype, int32_t tri, float* dW, void* workspace, size_t ws_bytes,
                trs_stream_t stream);
-
-/* The same two gradients for a layer whose output channels beyond the first C receive NO gradient: the reference splits
- * EVERY CIN layer's 2H output channels into a "direct" and a "hidden" half (compress_interaction_network.py:151-156: the
- * `i != len-1` guard is always true) and never uses the LAST layer's hidden half (:176-181 reads the direct halves only),
- * so dL/dy of those channels is exactly zero -- through BatchNorm and the activation too, which act per channel.  Their
- * terms of the contraction over c (data gradients) and their rows of dW are zeros that need not be computed:
- *   gyT (B,E,>=C) with ldg channels between two pixels, Wc = the first C rows of the layer's weight; results identical
- *   to trs_cin_cl_bwd_data on the full tensors (the omitted terms are exact zeros);
- *   gy (B,>=C,E) with gy_batch_stride elements between two samples; dW (C, N*H) = the first C rows of the gradient (the
- *   caller zero-fills the rest).                                                                                      */
-int trs_cin_cl_bwd_data_live(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* gyT, int32_t ldg,
-                             const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E, int32_t dtype,
-                             void* dx0T, void* dxkT, int32_t ldo, void* workspace, size_t ws_bytes, trs_stream_t stream);
-int trs_cin_dw_live(const void* gy, int64_t gy_batch_stride, const void* x0, const void* xk, int64_t B, int32_t N, int32_t H,
-                    int32_t C, int32_t E, int32_t dtype, float* dW, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
 /* ---- MLP backward epilogue (the GEMMs stay on hipBLASLt) -----------------------------------------------
  * y = relu(linear(x)):  gz = gy * (y > 0) and gb[c] = sum_r gz[r,c] (fp32) in ONE pass over (rows, C) instead of

@@ -374,7 +374,8 @@ def pair_case(N, E, B):
 
 
 # CIN, channels-last: (form, N, H, C, E, B, k).  'plain': distinct xk; 'fold': xk IS x0, N > 32 (weights folded onto
-# h <= n); 'live': last layer, gy zero on the channels [C/2, C)
+# h <= n); 'live': last layer, gy zero on the channels [C/2, C); 'live_same': a single layer that is first and last, xk IS
+# x0 with N <= 32 (not folded) and the dead half left out
 CIN_SHAPES = [(10, 10, 64, 32), (39, 128, 256, 64), (6, 32, 32, 16), (33, 64, 128, 64)]
 CIN_SMALL_B = [1, 7, 8, 9, 63, 64, 65]
 CIN_FOLD_SHAPES = [(33, 128, 64), (39, 256, 64), (64, 128, 32)]           # (N, C, E)
@@ -382,19 +383,20 @@ CIN_CASES = ([("plain", N, H, C, E, B, 2) for (N, H, C, E) in CIN_SHAPES for B i
              + [("plain", 10, 10, 64, 32, 300, 2), ("plain", 6, 32, 32, 16, 300, 2)]      # nsplit at its cap of 32
              + [("fold", N, N, C, E, B, 2) for (N, C, E) in CIN_FOLD_SHAPES for B in (1, 9, 65)]
              + [("fold", 33, 33, 128, 64, 520, 2)]                                         # nsplit at its cap of 64
-             + [("live", N, H, C, E, B, 2) for (N, H, C, E) in ((39, 128, 256, 64), (33, 64, 128, 64)) for B in (9, 65)])
-# the weight gradient of C = 32 / E = 16 is the generic kernel's (the C / E sets in _CINContractCL.backward)
+             + [("live", N, H, C, E, B, 2) for (N, H, C, E) in ((39, 128, 256, 64), (33, 64, 128, 64)) for B in (9, 65)]
+             + [("live_same", 10, 10, 128, 32, B, 2) for B in (9, 65)])
+# the weight gradient of C = 32 / E = 16 is the generic kernel's (the C / E sets of functional.cin_cl_backward_route)
 CIN_GENERIC_DW = [(6, 32, 32, 16)]
 
 
 @functools.lru_cache(maxsize=2)
 def cin_case(form, N, H, C, E, B, k):
     g = gen(3, len(form), N, H, C, E, B)
-    same = form == "fold"
+    same = form in ("fold", "live_same")
     x0 = ints((B, N, E), g)
     xk = x0 if same else ints((B, H, E), g)
     W, bias, gy = signed_rows(C, N * H, k, g), ints(C, g), ints((B, C, E), g)
-    live = C // 2 if form == "live" else None
+    live = C // 2 if form in ("live", "live_same") else None
     if live:
         gy[:, live:] = 0
     return NS(x0=x0, xk=xk, W=W, bias=bias, gy=gy, live=live, same=same, ref=cin_ref(x0, xk, W, bias, gy, same))

@@ -130,10 +130,33 @@ def test_cin_cases_are_in_the_exact_domain():
         X.assert_exact_domain(c.ref.inter, {"dW": c.ref.dW, "db": c.ref.db})
         if c.live:
             assert float(c.ref.dW[c.live:].abs().max()) == 0.0 and float(c.ref.dW[:c.live].abs().max()) > 0
-    # every plain shape sits in the matrix-core sets of _CINContractCL.backward but the one listed as generic
+    # every plain shape sits in the matrix-core sets of functional.cin_cl_backward_route but the one listed as generic
+    from torecsys_amd.functional import cin_cl_backward_route
     for (N, H, C, E) in X.CIN_SHAPES:
         assert (C in (64, 128, 256) and E in (32, 64, 128)) == ((N, H, C, E) not in X.CIN_GENERIC_DW)
+        assert cin_cl_backward_route(C, E, None, 0) == (C, True, (N, H, C, E) not in X.CIN_GENERIC_DW)
     assert all(N > 32 for N, _, _ in X.CIN_FOLD_SHAPES)
+
+
+def test_cin_backward_route_is_the_kernel_set_rule():
+    """functional.cin_cl_backward_route against the rule written out: the data gradient's kernels cover C in {32, 64, 128,
+    256}, the weight gradient's C in {64, 128, 256} with E in {32, 64, 128}; the dead channels are left out only when live
+    is set, not under the fold, live in {64, 128, 256} and both kernels cover the layer"""
+    from torecsys_amd.functional import cin_cl_backward_route
+    skipped = 0
+    for C in (32, 64, 128, 256, 512):
+        for E in (16, 32, 64, 128):
+            for live in (None, C // 2):
+                for tri in (0, 1):
+                    data = C in (32, 64, 128, 256)
+                    dw = C in (64, 128, 256) and E in (32, 64, 128)
+                    skip = live is not None and not tri and live in (64, 128, 256) and data and dw
+                    Cg, mfma_data, mfma_dw = cin_cl_backward_route(C, E, live, tri)
+                    assert (Cg, mfma_data, mfma_dw) == (live if skip else C, data, dw), (C, E, live, tri)
+                    if tri or live is None:
+                        assert Cg == C
+                    skipped += skip
+    assert skipped == 2 * 3            # C in {128, 256} (live 64, 128) x E in {32, 64, 128}, tri = 0
 
 
 @pytest.mark.parametrize("widths,k", [(tuple(w), k) for w, k in X.MLP_STACKS], ids=str)

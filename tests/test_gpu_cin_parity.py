@@ -289,14 +289,17 @@ def test_transpose_pad_is_the_padded_transposition_bit_for_bit(dev, B, N, E, ld)
     assert not F_.transpose_pad_supported(x, 128) and not F_.transpose_pad_supported(x.float(), ld)
 
 
-@pytest.mark.parametrize("B,N,E,sizes", [(256, 39, 64, [128, 128, 128]), (64, 39, 64, [64, 128]), (96, 10, 32, [32, 64])])
+@pytest.mark.parametrize("B,N,E,sizes", [(256, 39, 64, [128, 128, 128]), (64, 39, 64, [64, 128]), (96, 10, 32, [32, 64]),
+                                          (24, 10, 32, [128]), (24, 40, 32, [128])])
 @pytest.mark.parametrize("train", [True, False])
 def test_last_layer_backward_skips_the_dead_half_exactly(dev, monkeypatch, B, N, E, sizes, train):
     """The last CIN layer's "hidden" half is computed, split off and never used (compress_interaction_network.py:151-156,
     176-181), so its gradient is exactly zero; the backward of that layer's contraction leaves those channels out
-    (trs_cin_cl_bwd_data_live / trs_cin_dw_live).  Leaving out exact zeros must change NOTHING: every gradient of the layer
-    -- input, all convolution weights and biases, BatchNorm affine parameters, fc -- bit-identical with the switch off,
-    and the dead rows of the last convolution's weight gradient exactly zero."""
+    (trs_cin_cl_bwd_data with ldg > C / trs_cin_dw with gy_batch_stride > C*E).  Leaving out exact zeros must change
+    NOTHING: every gradient of the layer -- input, all convolution weights and biases, BatchNorm affine parameters, fc --
+    bit-identical with the switch off, and the dead rows of the last convolution's weight gradient exactly zero.  A single
+    layer is first and last: with N <= 32 its xkT is x0T and the dead half is left out; with N > 32 the symmetric fold wins
+    and both runs are the same code."""
     from torecsys_amd import functional as F_
     from torecsys_amd.layers import CompressInteractionNetworkLayer
     torch.manual_seed(B + N)

@@ -106,8 +106,9 @@ def test_pair_bilinear_exact(dev, N, E, B):
 @pytest.mark.parametrize("form,N,H,C,E,B,k", X.CIN_CASES, ids=lambda v: str(v))
 def test_cin_contraction_exact(dev, form, N, H, C, E, B, k):
     """F_.transpose_pad + F_.cin_contract_cl: the plain form, the folded first-layer form (xkT is x0T, N > 32; the
-    reference uses the unfolded weights, dx0T is the sum of both gradients) and the ``live`` form of a last layer (the
-    dead rows of dW exactly zero); yT, dx0T and dxkT with their padding columns zero, dW, db; bf16 and fp32 parameters"""
+    reference uses the unfolded weights, dx0T is the sum of both gradients), the ``live`` form of a last layer (the
+    dead rows of dW exactly zero) and ``live_same``, a single unfolded layer (xkT is x0T, N <= 32) with its dead half left
+    out; yT, dx0T and dxkT with their padding columns zero, dW, db; bf16 and fp32 parameters"""
     from torecsys_amd import functional as F_
     c = X.cin_case(form, N, H, C, E, B, k)
     r = c.ref
@@ -116,6 +117,7 @@ def test_cin_contraction_exact(dev, form, N, H, C, E, B, k):
     assert F_.cin_cl_supported(x0, [C], [] if H == N else [H])
     assert C in (32, 64, 128, 256)                                              # the data gradient's matrix-core set
     assert (C in (64, 128, 256) and E in (32, 64, 128)) == ((N, H, C, E) not in X.CIN_GENERIC_DW or form != "plain")
+    assert F_.cin_cl_backward_route(C, E, None, 0) == (C, True, (N, H, C, E) not in X.CIN_GENERIC_DW or form != "plain")
     ld0, ldk = X.pad32(N), X.pad32(H)
     assert F_.transpose_pad_supported(x0, ld0)
     x0T_v = F_.transpose_pad(x0, ld0)

@@ -220,7 +220,7 @@ def bench_bwd(B, N, H, C, E, tri):
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
 
     def old():
-        call("trs_cin_cl_bwd_data", ptr(x0T), ld0, ptr(xkTb), ldk, ptr(gyb), ptr(Wb), B, N, H, C, E, _abi.TRS_BF16,
+        call("trs_cin_cl_bwd_data", ptr(x0T), ld0, ptr(xkTb), ldk, ptr(gyb), C, ptr(Wb), B, N, H, C, E, _abi.TRS_BF16,
              int(tri), ptr(dx0T), ptr(dxk), ldo, ptr(ws), wsb, stream_ptr())
     ms0 = timeit(old)
     print(f"   bf16 cin_cl_bwd_data: {ms0:.3f} ms  {flop / ms0 / 1e12:.3f} PFLOP/s")

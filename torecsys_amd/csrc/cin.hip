@@ -3,18 +3,13 @@
 //     y[b,c,e] = bias[c] + sum_{n,h} Wc[c, n*H+h] * x0[b,n,e] * xk[b,h,e]
 // The reference materialises Z = (B, N*H, E) (25-84 GB at the BASELINE shape); here Z never exists.
 //
-// Two implementations behind one entry point:
-//  * generic (any shape, both dtypes): VALU, one sample per workgroup, x0/xk/gy staged in LDS;
-//  * MFMA (bf16; see cin_mfma.hip): Z tiles are generated in registers as the A operand
-//    (rows = (b,e) pairs, K = (n,h)) and contracted with Wc fragments on the matrix cores.
+// Two implementations, each behind its own entries:
+//  * generic (this file; channels-first, any shape, both dtypes): VALU, one sample per workgroup, x0/xk/gy staged in LDS;
+//  * MFMA (bf16, channels-last; trs_cin_cl_* / trs_cin_dw in cin_mfma.hip): Z tiles are generated in registers as the
+//    A operand (rows = (b,e) pairs, K = (n,h)) and contracted with Wc fragments on the matrix cores.
 #include "trs_common.hpp"
 
 namespace trs {
-
-int cin_mfma_fwd(const void* x0, const void* xk, const void* Wc, const void* bias, int64_t B, int N, int H, int C,
-                 int E, void* y, float* stats, hipStream_t s);  // returns 1 if the shape is not covered
-int cin_mfma_bwd(const void* x0, const void* xk, const void* Wc, const void* gy, int64_t B, int N, int H, int C, int E,
-                 float* dWc, void* dx0, void* dxk, int accumulate_dx0, hipStream_t s);
 
 // LDS: x0s[N][E], xks[H][E] (fp32)
 template <typename T>
@@ -136,12 +131,7 @@ extern "C" int trs_cin_fwd(const void* x0, const void* xk, const void* Wc, const
   if (B == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
   TRS_REQUIRE(x0 && xk && Wc && y, TRS_EINVAL, "cin_fwd: NULL pointer");
   TRS_CIN_CHECK("cin_fwd");
-  if (B == 0) return TRS_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_BF16) {
-    const int rc = cin_mfma_fwd(x0, xk, Wc, bias, B, N, H, C, E, y, stats, s);
-    if (rc <= 0) return rc;
-  }
   int EC = E;
   while (EC > 1 && (size_t)(N + H) * EC * 4 > 48 * 1024) EC = (EC + 1) / 2;
   const size_t lds = (size_t)(N + H) * EC * 4;
@@ -162,12 +152,7 @@ extern "C" int trs_cin_bwd(const void* x0, const void* xk, const void* Wc, const
   if (B == 0) return TRS_OK;  // empty batch: nothing to do (pointers may be NULL)
   TRS_REQUIRE(x0 && xk && Wc && gy, TRS_EINVAL, "cin_bwd: NULL pointer");
   TRS_CIN_CHECK("cin_bwd");
-  if (B == 0) return TRS_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_BF16) {
-    const int rc = cin_mfma_bwd(x0, xk, Wc, gy, B, N, H, C, E, dWc, dx0, dxk, accumulate_dx0, s);
-    if (rc <= 0) return rc;
-  }
   int EC = E;
   while (EC > 1 && (size_t)(N + H + C) * EC * 4 > 48 * 1024) EC = (EC + 1) / 2;
   const size_t lds = (size_t)(N + H + C) * EC * 4;

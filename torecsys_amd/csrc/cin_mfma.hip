@@ -594,12 +594,11 @@ size_t cin_mfma_bwd_data_workspace_bytes(int N, int H, int C) {
   return cin_bwd_frag_bytes(KSH, N + 2, KCT) + 256;
 }
 
-int cin_cl_bwd_data(const void* x0T, int ld0, const void* xkT, int ldk, const void* gyT, const void* Wc, int64_t B, int N,
-                    int H, int C, int E, int tri, void* dx0T, void* dxkT, int ldo, void* workspace, size_t ws_bytes,
-                    hipStream_t s, int ldg = 0) {
+// ldg: channels between two pixels of gyT (>= C, multiple of 8: checked by the C entry, the only caller)
+int cin_cl_bwd_data(const void* x0T, int ld0, const void* xkT, int ldk, const void* gyT, int ldg, const void* Wc, int64_t B,
+                    int N, int H, int C, int E, int tri, void* dx0T, void* dxkT, int ldo, void* workspace, size_t ws_bytes,
+                    hipStream_t s) {
   const int KSH = (H + 31) / 32, KCT = C / 32;
-  if (ldg == 0) ldg = C;
-  if (ldg < C || ldg % 8 != 0) return 1;
   if (C % 32 != 0 || E % 16 != 0 || !(KCT == 1 || KCT == 2 || KCT == 4 || KCT == 8) || ld0 % 8 != 0 || ldk % 8 != 0 ||
       ldk < 32 * KSH || ldo < 32 * KSH || ldo % 8 != 0 || workspace == nullptr)
     return 1;
@@ -1030,15 +1029,14 @@ static int cin_dw_tri(const void* gy, const void* x0, int64_t B, int N, int C, i
   return check_launch("cin_dw (first layer)");
 }
 
-// gy (B,C,E), x0 (B,N,E), xk (B,H,E) contiguous bf16; dW (C, N*H) fp32 accumulated into.
+// gy (B,>=C,E) with gy_bs elements between two samples (range checked by the C entry, the only caller), x0 (B,N,E),
+// xk (B,H,E) contiguous bf16; dW (C, N*H) fp32 accumulated into.
 // tri: xk is x0 (same pointer, H == N): the symmetric first-layer form, cin_dw_tri_kernel where it covers the shape
-int cin_dw(const void* gy, const void* x0, const void* xk, int64_t B, int N, int H, int C, int E, int tri, float* dW,
-           void* workspace, size_t ws_bytes, hipStream_t s, int64_t gy_bs = 0) {
+int cin_dw(const void* gy, int64_t gy_bs, const void* x0, const void* xk, int64_t B, int N, int H, int C, int E, int tri,
+           float* dW, void* workspace, size_t ws_bytes, hipStream_t s) {
   if (!(C == 64 || C == 128 || C == 256) || !(E == 32 || E == 64 || E == 128) || workspace == nullptr ||
       !aligned16(gy) || !aligned16(x0) || !aligned16(xk))
     return 1;
-  if (gy_bs == 0) gy_bs = (int64_t)C * E;
-  if (gy_bs < (int64_t)C * E || gy_bs % 8 != 0 || gy_bs >= ((int64_t)1 << 31) || (tri && gy_bs != (int64_t)C * E)) return 1;
   if (ws_bytes < cin_dw_workspace_bytes(B, N, H, C)) return fail(TRS_EWORKSPACE, "cin_dw: workspace too small");
   const int KE = E / 32;
   if (tri && xk == x0 && H == N && C % 128 == 0 && KE <= 2) {
@@ -1110,12 +1108,6 @@ int cin_dw(const void* gy, const void* x0, const void* xk, int64_t B, int N, int
   return check_launch("cin_dw");
 }
 
-// channels-first entry points keep using the generic kernels for now
-int cin_mfma_fwd(const void*, const void*, const void*, const void*, int64_t, int, int, int, int, void*, float*,
-                 hipStream_t) { return 1; }
-int cin_mfma_bwd(const void*, const void*, const void*, const void*, int64_t, int, int, int, int, float*, void*, void*,
-                 int, hipStream_t) { return 1; }
-
 }  // namespace trs
 
 using namespace trs;
@@ -1146,16 +1138,17 @@ extern "C" size_t trs_cin_cl_bwd_data_workspace_bytes(int32_t N, int32_t H, int3
 }
 
 extern "C" int trs_cin_cl_bwd_data(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* gyT,
-                                   const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E,
+                                   int32_t ldg, const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E,
                                    int32_t dtype, int32_t tri, void* dx0T, void* dxkT, int32_t ldo, void* workspace,
                                    size_t ws_bytes, trs_stream_t stream) {
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(x0T && xkT && gyT && Wc && dx0T && (dxkT || tri), TRS_EINVAL, "cin_cl_bwd_data: NULL pointer");
   TRS_REQUIRE(B > 0 && N > 0 && H > 0 && C > 0 && E > 0, TRS_EINVAL, "cin_cl_bwd_data: bad size");
+  TRS_REQUIRE(ldg >= C && ldg % 8 == 0, TRS_EINVAL, "cin_cl_bwd_data: bad ldg %d (C %d)", ldg, C);
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "cin_cl_bwd_data: bf16 only (dtype %d)", dtype);
   TRS_REQUIRE(!tri || (N == H && x0T == xkT && ld0 == ldk), TRS_EINVAL,
               "cin_cl_bwd_data: tri needs xkT to be x0T (N %d, H %d)", N, H);
-  const int rc = cin_cl_bwd_data(x0T, ld0, xkT, ldk, gyT, Wc, B, N, H, C, E, tri != 0, dx0T, dxkT, ldo, workspace,
+  const int rc = cin_cl_bwd_data(x0T, ld0, xkT, ldk, gyT, ldg, Wc, B, N, H, C, E, tri != 0, dx0T, dxkT, ldo, workspace,
                                  ws_bytes, (hipStream_t)stream);
   if (rc == 1) return fail(TRS_ESHAPE, "cin_cl_bwd_data: shape not covered (C in {32,64,128,256}, E%%16==0)");
   return rc;
@@ -1166,44 +1159,18 @@ extern "C" size_t trs_cin_dw_workspace_bytes(int64_t B, int32_t N, int32_t H, in
   return cin_dw_workspace_bytes(B, N, H, C);
 }
 
-extern "C" int trs_cin_dw(const void* gy, const void* x0, const void* xk, int64_t B, int32_t N, int32_t H, int32_t C,
-                          int32_t E, int32_t dtype, int32_t tri, float* dW, void* workspace, size_t ws_bytes,
-                          trs_stream_t stream) {
+extern "C" int trs_cin_dw(const void* gy, int64_t gy_batch_stride, const void* x0, const void* xk, int64_t B, int32_t N,
+                          int32_t H, int32_t C, int32_t E, int32_t dtype, int32_t tri, float* dW, void* workspace,
+                          size_t ws_bytes, trs_stream_t stream) {
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(gy && x0 && xk && dW, TRS_EINVAL, "cin_dw: NULL pointer");
   TRS_REQUIRE(B > 0 && N > 0 && H > 0 && C > 0 && E > 0, TRS_EINVAL, "cin_dw: bad size");
+  TRS_REQUIRE(gy_batch_stride >= (int64_t)C * E && gy_batch_stride % 8 == 0 && gy_batch_stride < ((int64_t)1 << 31) &&
+                  (!tri || gy_batch_stride == (int64_t)C * E),
+              TRS_EINVAL, "cin_dw: bad gy_batch_stride %lld (C*E = %lld)", (long long)gy_batch_stride, (long long)C * E);
   TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "cin_dw: bf16 only (dtype %d)", dtype);
   TRS_REQUIRE(!tri || (xk == x0 && N == H), TRS_EINVAL, "cin_dw: tri needs xk to be x0 (N %d, H %d)", N, H);
-  const int rc = cin_dw(gy, x0, xk, B, N, H, C, E, tri != 0, dW, workspace, ws_bytes, (hipStream_t)stream);
+  const int rc = cin_dw(gy, gy_batch_stride, x0, xk, B, N, H, C, E, tri != 0, dW, workspace, ws_bytes, (hipStream_t)stream);
   if (rc == 1) return fail(TRS_ESHAPE, "cin_dw: shape not covered (C in {64,128,256}, E in {32,64,128})");
-  return rc;
-}
-
-/* see include/trs_abi.h: the two gradients of the contraction when only the first C of the layer's Ct output channels can
- * carry a gradient */
-extern "C" int trs_cin_cl_bwd_data_live(const void* x0T, int32_t ld0, const void* xkT, int32_t ldk, const void* gyT,
-                                        int32_t ldg, const void* Wc, int64_t B, int32_t N, int32_t H, int32_t C, int32_t E,
-                                        int32_t dtype, void* dx0T, void* dxkT, int32_t ldo, void* workspace,
-                                        size_t ws_bytes, trs_stream_t stream) {
-  if (B == 0) return TRS_OK;
-  TRS_REQUIRE(x0T && xkT && gyT && Wc && dx0T && dxkT, TRS_EINVAL, "cin_cl_bwd_data_live: NULL pointer");
-  TRS_REQUIRE(B > 0 && N > 0 && H > 0 && C > 0 && E > 0 && ldg >= C, TRS_EINVAL, "cin_cl_bwd_data_live: bad size");
-  TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "cin_cl_bwd_data_live: bf16 only (dtype %d)", dtype);
-  const int rc = cin_cl_bwd_data(x0T, ld0, xkT, ldk, gyT, Wc, B, N, H, C, E, false, dx0T, dxkT, ldo, workspace, ws_bytes,
-                                 (hipStream_t)stream, ldg);
-  if (rc == 1) return fail(TRS_ESHAPE, "cin_cl_bwd_data_live: shape not covered (C in {32,64,128,256}, E%%16==0, ldg%%8==0)");
-  return rc;
-}
-
-extern "C" int trs_cin_dw_live(const void* gy, int64_t gy_batch_stride, const void* x0, const void* xk, int64_t B, int32_t N,
-                               int32_t H, int32_t C, int32_t E, int32_t dtype, float* dW, void* workspace, size_t ws_bytes,
-                               trs_stream_t stream) {
-  if (B == 0) return TRS_OK;
-  TRS_REQUIRE(gy && x0 && xk && dW, TRS_EINVAL, "cin_dw_live: NULL pointer");
-  TRS_REQUIRE(B > 0 && N > 0 && H > 0 && C > 0 && E > 0 && gy_batch_stride >= (int64_t)C * E, TRS_EINVAL,
-              "cin_dw_live: bad size");
-  TRS_REQUIRE(dtype == TRS_BF16, TRS_EDTYPE, "cin_dw_live: bf16 only (dtype %d)", dtype);
-  const int rc = cin_dw(gy, x0, xk, B, N, H, C, E, false, dW, workspace, ws_bytes, (hipStream_t)stream, gy_batch_stride);
-  if (rc == 1) return fail(TRS_ESHAPE, "cin_dw_live: shape not covered (C in {64,128,256}, E in {32,64,128})");
   return rc;
 }

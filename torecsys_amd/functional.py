@@ -1924,16 +1924,22 @@ def opn_vec(x: torch.Tensor, kern: torch.Tensor, is_num: bool) -> torch.Tensor:
     return _OPNVec.apply(x, kern, is_num)
 
 
+def _glue_colsum(t: torch.Tensor) -> torch.Tensor:
+    """column sums (C,) fp64 of a contiguous bf16 (B, R, C) block that cin_glue_supported accepts: one bf16 read with fp32
+    partials per workgroup (trs_cin_glue_stats) instead of a cast to fp32 plus a two-stage ATen reduction (three passes
+    over a multi-GB tensor)."""
+    B, R, C = t.shape
+    nblk = size_query("trs_cin_glue_blocks", B)
+    part = torch.empty(nblk, 2, C, dtype=torch.float32, device=t.device)
+    call("trs_cin_glue_stats", ptr(t), B, R, C, value_dtype_code(t), ptr(part), stream_ptr())
+    return part[:, 0].double().sum(0)
+
+
 def _pair_bias_grad(g: torch.Tensor, per_pair: bool) -> torch.Tensor:
     """sum of a (B, P, E) gradient over b (per-pair bias) or over (b, p) (shared bias), fp32 accumulation."""
-    B, P, E = g.shape
+    E = g.shape[2]
     if not per_pair and cin_glue_supported(g, 0, 0):
-        # column sums of the (B*P, E) matrix: one bf16 read with fp32 partials per workgroup (trs_cin_glue_stats)
-        # instead of a cast to fp32 plus a two-stage ATen reduction (three passes over a multi-GB tensor)
-        nblk = size_query("trs_cin_glue_blocks", B)
-        part = torch.empty(nblk, 2, E, dtype=torch.float32, device=g.device)
-        call("trs_cin_glue_stats", ptr(g), B, P, E, value_dtype_code(g), ptr(part), stream_ptr())
-        return part[:, 0].double().sum(0).to(g.dtype)
+        return _glue_colsum(g).to(g.dtype)        # column sums of the (B*P, E) matrix
     gb = g.sum(0, dtype=torch.float32) if per_pair else g.reshape(-1, E).sum(0, dtype=torch.float32)
     return gb.to(g.dtype)
 
@@ -2980,7 +2986,6 @@ def cin_cl_supported(x: torch.Tensor, out_channels: Sequence[int], hidden_sizes:
     return all(h in (32, 64, 128, 256) for h in hidden_sizes)
 
 
-CIN_FOLD_SYMMETRIC = os.environ.get("TRS_CIN_FOLD", "1") != "0"
 # the last CIN layer's backward leaves out the output channels that provably carry no gradient (see _CINContractCL.forward)
 CIN_SKIP_DEAD = os.environ.get("TRS_CIN_SKIP_DEAD", "1") != "0"
 
@@ -2992,6 +2997,26 @@ def cin_fold_symmetric(Wc: torch.Tensor, N: int) -> torch.Tensor:
     C = Wc.shape[0]
     W3 = Wc.float().view(C, N, N)
     return (torch.tril(W3) + torch.triu(W3, 1).transpose(1, 2)).reshape(C, N * N)
+
+
+def cin_cl_backward_route(C: int, E: int, live: Optional[int], tri: int) -> Tuple[int, bool, bool]:
+    """Which kernels the channels-last backward of a layer with C output channels runs: (Cg, mfma_data, mfma_dw).
+    mfma_data / mfma_dw: trs_cin_cl_bwd_data / trs_cin_dw cover the shape (else the generic trs_cin_bwd).  Cg: the channels
+    both gradients contract over -- ``live`` (the leading channels that can receive a gradient) where leaving the dead ones
+    out applies: not under the symmetric fold, both matrix-core kernels cover the full AND the live width; else C."""
+    mfma_data = C in (32, 64, 128, 256)
+    mfma_dw = C in (64, 128, 256) and E in (32, 64, 128)
+    skip = bool(live) and not tri and live in (64, 128, 256) and mfma_data and mfma_dw
+    return (int(live) if skip else C), mfma_data, mfma_dw
+
+
+def _cin_cf_operand(cf: Optional[torch.Tensor], T: torch.Tensor, n: int) -> torch.Tensor:
+    """channels-first (B,n,E) form of the first n channels of the channels-last T (B,E,>=n): the caller's copy ``cf`` when
+    it has the right shape and is contiguous, else a transposing copy."""
+    B, E, _ = T.shape
+    if cf is not None and tuple(cf.shape) == (B, n, E) and cf.is_contiguous():
+        return cf
+    return T[:, :, :n].transpose(1, 2).contiguous()
 
 
 class _CINContractCL(Function):
@@ -3006,7 +3031,7 @@ class _CINContractCL(Function):
         # First layer (xk IS x0): the products x0[n]*x0[h] are symmetric in (n,h), so W[n,h] + W[h,n] folded onto h <= n
         # (one fp32 add, one bf16 rounding) gives the same sums from half the weights; the kernels skip the k-steps /
         # h tiles that then hold only zeros.  Pays once a field needs more than one 32-wide k-step.
-        tri = int(xkT.data_ptr() == x0T.data_ptr() and ldk == ld0 and H == N and N > 32 and CIN_FOLD_SYMMETRIC)
+        tri = int(xkT.data_ptr() == x0T.data_ptr() and ldk == ld0 and H == N and N > 32)
         if tri:
             w = cin_fold_symmetric(Wc.detach(), N).to(torch.bfloat16)
         else:
@@ -3033,120 +3058,68 @@ class _CINContractCL(Function):
     def backward(ctx, gyT):
         x0T, xkT, w = ctx.saved_tensors
         N, H, wdt, bdt = ctx.meta
-        B, E, _ = x0T.shape
+        B, E, ld0 = x0T.shape
         C = w.shape[0]
+        tri = ctx.tri
         need_x0, need_xk, need_w, need_b = ctx.needs_input_grad[:4]
         gy_cf = getattr(gyT, '_trs_cf', None)      # (B,C,E) copy emitted by the glue backward, if any
         gyT = gyT.contiguous()
         dev = x0T.device
-        ld0, ldk = x0T.shape[2], xkT.stride(1)
         db = None
         pre = getattr(gyT, '_trs_colsum', None)    # column sums emitted by the glue backward that produced gyT
         if need_b and bdt is not None:
             if pre is not None and pre[1] == gyT._version:
                 db = pre[0].double().sum(0).to(bdt)
             elif cin_glue_supported(gyT, 0, 0):
-                # column sums of the (B,E,C) gradient by the glue statistics kernel (one bf16 read, fp32 partials)
-                nblk = size_query("trs_cin_glue_blocks", B)
-                part = torch.empty(nblk, 2, C, dtype=torch.float32, device=gyT.device)
-                call("trs_cin_glue_stats", ptr(gyT), B, E, C, value_dtype_code(gyT), ptr(part), stream_ptr())
-                db = part[:, 0].double().sum(0).to(bdt)
+                db = _glue_colsum(gyT).to(bdt)
             else:
                 db = gyT.float().sum(dim=(0, 1)).to(bdt)
+        # Cg < C: the channels [Cg, C) carry no gradient, both contractions run over the first Cg channels of the full
+        # tensors (strides C and C*E) and the rest of dW stays zero
+        Cg, mfma_data, mfma_dw = cin_cl_backward_route(C, E, ctx.live, tri)
+        if gy_cf is not None and not gy_cf.is_contiguous():
+            Cg = C
+        generic_data = (need_x0 or need_xk) and not mfma_data
         dx0T = dxkT = dW = None
-        mfma_data = C in (32, 64, 128, 256)
-        mfma_dw = C in (64, 128, 256) and E in (32, 64, 128)
-        Cl = ctx.live
-        if Cl is not None and not (Cl in (64, 128, 256) and mfma_data and mfma_dw and (gy_cf is None or gy_cf.is_contiguous())):
-            Cl = None
-        if Cl is not None:
-            # the channels [Cl, C) carry no gradient: contraction over the first Cl channels only, the rest of dW stays zero
-            if need_x0 or need_xk:
-                ldo = ((H + 31) // 32) * 32
-                dx0T = torch.empty_like(x0T)
-                dxk_pad = torch.empty(B, E, ldo, dtype=torch.bfloat16, device=dev)
-                ws_bytes = size_query("trs_cin_cl_bwd_data_workspace_bytes", N, H, Cl)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                call("trs_cin_cl_bwd_data_live", ptr(x0T), ld0, ptr(xkT), ldk, ptr(gyT), C, ptr(w), B, N, H, Cl, E,
-                     _abi.TRS_BF16, ptr(dx0T), ptr(dxk_pad), ldo, ptr(ws), ws_bytes, stream_ptr())
-                if tuple(dxk_pad.shape) == tuple(xkT.shape):
-                    dxkT = dxk_pad
-                else:
-                    dxkT = torch.zeros(xkT.shape, dtype=xkT.dtype, device=dev)
-                    dxkT[:, :, :H] = dxk_pad[:, :, :H]
-            if need_w:
-                x0_cf, xk_cf = ctx.x0_cf, ctx.xk_cf
-                x0 = x0_cf if (x0_cf is not None and tuple(x0_cf.shape) == (B, N, E) and x0_cf.is_contiguous()) \
-                    else x0T[:, :, :N].transpose(1, 2).contiguous()
-                xk = xk_cf if (xk_cf is not None and tuple(xk_cf.shape) == (B, H, E) and xk_cf.is_contiguous()) \
-                    else xkT[:, :, :H].transpose(1, 2).contiguous()
-                gy = gy_cf if (gy_cf is not None and tuple(gy_cf.shape) == (B, C, E)) else gyT.transpose(1, 2).contiguous()
-                dW = torch.zeros(C, N * H, dtype=torch.float32, device=dev)
-                ws_bytes = size_query("trs_cin_dw_workspace_bytes", B, N, H, Cl)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                call("trs_cin_dw_live", ptr(gy), C * E, ptr(x0), ptr(xk), B, N, H, Cl, E, _abi.TRS_BF16, ptr(dW), ptr(ws),
-                     ws_bytes, stream_ptr())
-            return (dx0T if need_x0 else None, dxkT if need_xk else None, (dW.to(wdt) if need_w else None), db, None, None,
-                    None, None, None)
-        if need_x0 or need_xk:
-            if mfma_data:
-                ldo = ((H + 31) // 32) * 32
-                dx0T = torch.empty_like(x0T)
-                # tri: xkT is x0T, the kernel returns the sum of the two gradients (= the gradient of the quadratic form
-                # under the folded weights = under the original ones) in dx0T and xkT's slot of this function stays None
-                dxk_pad = None if ctx.tri else torch.empty(B, E, ldo, dtype=torch.bfloat16, device=dev)
-                ws_bytes = size_query("trs_cin_cl_bwd_data_workspace_bytes", N, H, C)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-                call("trs_cin_cl_bwd_data", ptr(x0T), ld0, ptr(xkT), ldk, ptr(gyT), ptr(w), B, N, H, C, E, _abi.TRS_BF16,
-                     ctx.tri, ptr(dx0T), ptr(dxk_pad), ldo, ptr(ws), ws_bytes, stream_ptr())
-                if ctx.tri:
-                    dxkT = None
-                elif tuple(dxk_pad.shape) == tuple(xkT.shape):     # already zero past H (zero weight fragments)
-                    dxkT = dxk_pad
-                else:
-                    dxkT = torch.zeros(xkT.shape, dtype=xkT.dtype, device=dev)
-                    dxkT[:, :, :H] = dxk_pad[:, :, :H]
-        if (need_x0 or need_xk) and not mfma_data or (need_w and not mfma_dw):
+        if (need_x0 or need_xk) and mfma_data:
+            ldo = ((H + 31) // 32) * 32
+            dx0T = torch.empty_like(x0T)
+            # tri: xkT is x0T, the kernel returns the sum of the two gradients (= the gradient of the quadratic form
+            # under the folded weights = under the original ones) in dx0T and xkT's slot of this function stays None
+            dxk_pad = None if tri else torch.empty(B, E, ldo, dtype=torch.bfloat16, device=dev)
+            ws_bytes = size_query("trs_cin_cl_bwd_data_workspace_bytes", N, H, Cg)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            call("trs_cin_cl_bwd_data", ptr(x0T), ld0, ptr(xkT), xkT.stride(1), ptr(gyT), C, ptr(w), B, N, H, Cg, E,
+                 _abi.TRS_BF16, tri, ptr(dx0T), ptr(dxk_pad), ldo, ptr(ws), ws_bytes, stream_ptr())
+            if tri or tuple(dxk_pad.shape) == tuple(xkT.shape):     # already zero past H (zero weight fragments)
+                dxkT = dxk_pad
+            else:
+                dxkT = torch.zeros(xkT.shape, dtype=xkT.dtype, device=dev)
+                dxkT[:, :, :H] = dxk_pad[:, :, :H]
+        if need_w or generic_data:
+            # channels-first operands (pixels contiguous): the caller's copies where it has them
+            x0 = _cin_cf_operand(ctx.x0_cf, x0T, N)
+            xk = x0 if (xkT.data_ptr() == x0T.data_ptr() and H == N) else _cin_cf_operand(ctx.xk_cf, xkT, H)
+            gy = _cin_cf_operand(gy_cf, gyT, C)
+        if need_w:
+            dW = torch.zeros(C, N * H, dtype=torch.float32, device=dev)
+        if generic_data or (need_w and not mfma_dw):
             # generic channels-first kernels for shapes the MFMA kernels do not cover
-            x0 = x0T[:, :, :N].transpose(1, 2).contiguous()
-            xk = xkT[:, :, :H].transpose(1, 2).contiguous()
-            gy = gyT.transpose(1, 2).contiguous()
-            gW = torch.zeros(C, N * H, dtype=torch.float32, device=dev) if (need_w and not mfma_dw) else None
-            gx0 = torch.empty_like(x0) if not mfma_data else None
-            gxk = torch.empty_like(xk) if not mfma_data else None
-            call("trs_cin_bwd", ptr(x0), ptr(xk), ptr(w), ptr(gy), B, N, H, C, E, _abi.TRS_BF16, ptr(gW), ptr(gx0),
-                 ptr(gxk), 0, stream_ptr())
-            if not mfma_data:
+            gx0 = torch.empty_like(x0) if generic_data else None
+            gxk = torch.empty_like(xk) if generic_data else None
+            call("trs_cin_bwd", ptr(x0), ptr(xk), ptr(w), ptr(gy), B, N, H, C, E, _abi.TRS_BF16,
+                 ptr(None if mfma_dw else dW), ptr(gx0), ptr(gxk), 0, stream_ptr())
+            if generic_data:
                 dx0T = torch.zeros_like(x0T)
                 dx0T[:, :, :N] = gx0.transpose(1, 2)
                 dxkT = torch.zeros(xkT.shape, dtype=xkT.dtype, device=dev)
                 dxkT[:, :, :H] = gxk.transpose(1, 2)
-            if gW is not None:
-                dW = gW
         if need_w and mfma_dw:
-            x0_cf = ctx.x0_cf
-            if x0_cf is not None and tuple(x0_cf.shape) == (B, N, E) and x0_cf.is_contiguous():
-                x0 = x0_cf
-            else:
-                x0 = x0T[:, :, :N].transpose(1, 2).contiguous()      # channels-first copies: pixels contiguous
-            xk_cf = ctx.xk_cf
-            if xkT.data_ptr() == x0T.data_ptr() and H == N:
-                xk = x0                                               # first layer: xk is x0
-            elif xk_cf is not None and tuple(xk_cf.shape) == (B, H, E) and xk_cf.is_contiguous():
-                xk = xk_cf
-            else:
-                xk = xkT[:, :, :H].transpose(1, 2).contiguous()
-            if gy_cf is not None and tuple(gy_cf.shape) == (B, C, E) and gy_cf.is_contiguous():
-                gy = gy_cf
-            else:
-                gy = gyT.transpose(1, 2).contiguous()
-            dW = torch.zeros(C, N * H, dtype=torch.float32, device=dev)
-            ws_bytes = size_query("trs_cin_dw_workspace_bytes", B, N, H, C)
+            ws_bytes = size_query("trs_cin_dw_workspace_bytes", B, N, H, Cg)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            call("trs_cin_dw", ptr(gy), ptr(x0), ptr(xk), B, N, H, C, E, _abi.TRS_BF16, int(ctx.tri and xk is x0), ptr(dW),
-                 ptr(ws), ws_bytes, stream_ptr())
-        return (dx0T if need_x0 else None, dxkT if (need_xk and dxkT is not None) else None,
-                (dW.to(wdt) if need_w else None), db, None, None,
+            call("trs_cin_dw", ptr(gy), C * E, ptr(x0), ptr(xk), B, N, H, Cg, E, _abi.TRS_BF16, tri, ptr(dW), ptr(ws),
+                 ws_bytes, stream_ptr())
+        return (dx0T if need_x0 else None, dxkT if need_xk else None, None if dW is None else dW.to(wdt), db, None, None,
                 None, None, None)
 
 
