@@ -1390,6 +1390,69 @@ int trs_rank_loss_bwd(const void* pos, int64_t pos_stride, const void* neg, int6
                       const float* gout, const float* denom, void* g_pos, int64_t g_pos_stride, void* g_neg,
                       int64_t g_neg_stride, trs_stream_t stream);
 
+/* ---- row-wise int8 (Q8) tables: forward only, for tables that are read and not trained --------------------------------
+ * The "fused 8-bit row-wise" layout of serving stacks (not in the reference).  A Q8 table of V rows x E columns is V
+ * contiguous rows of S = trs_q8_row_bytes(E) = round_up(E + 8, 16) bytes, so every row starts on a 16-byte boundary:
+ *   [0, E)      codes c[e], 0..255
+ *   [E, E+4)    scale, fp32, little endian
+ *   [E+4, E+8)  bias, fp32, little endian
+ *   [E+8, S)    zero
+ * Dequantization, in every entry:  x[e] = float(c[e]) * scale + bias  in fp32, the product and the sum each rounded (no
+ * fma): a pure function of the row's bytes.  E <= 0: trs_q8_row_bytes returns 0.
+ *
+ * trs_q8_quantize_rows: table (V, E) fp32 / bf16 (bf16 is widened first) -> qrows (V, S), per row with finite values:
+ *   bias  = min_e x[e],  scale = (max_e x[e] - bias) / 255.0f   (one subtraction, one correctly rounded division; a min
+ *           or max of -0 counts as +0, since IEEE leaves min(+0, -0) open and the bytes must not depend on it)
+ *   c[e]  = clamp(rint((x[e] - bias) / scale), 0, 255)  (round-half-even, the same division); scale == 0: all codes 0, so
+ *           a constant row dequantizes to itself
+ * |deq(c[e]) - x[e]| <= (0.5 + 2^-15) * scale + 2^-23 * max|x_row|.  A row that holds inf or NaN gets unspecified codes;
+ * nothing is read or written outside the row.  Any E.  V == 0: TRS_OK.
+ * Paths, here and below: E = 16 * L, L a power of two <= 64, with 16-byte aligned pointers: one group of L lanes per row /
+ * sample / bag, a lane holds 16 columns; tables above 512 MiB are read with streaming loads.  Any other E or alignment:
+ * one thread per element (the quantizer: per row).
+ * TRS_EINVAL: NULL pointer, bad size; TRS_EDTYPE: dtype.  All before any launch.                                       */
+size_t trs_q8_row_bytes(int32_t E);
+int trs_q8_quantize_rows(const void* table, int64_t V, int32_t E, int32_t dtype, void* qrows, trs_stream_t stream);
+
+/* trs_gather_rows on a Q8 table:  out[b,n,:] = deq(qrows[idx[b,n] + offsets[n]])  rounded once to out_dtype (TRS_F32 |
+ * TRS_BF16); out (B, N, E).  An index outside [0, V) reads as a zero row and raises *err_flag.  B == 0: TRS_OK.
+ * TRS_EINVAL: NULL qrows / idx / out, bad size; TRS_EDTYPE: out_dtype / idx_dtype; TRS_ESHAPE: B*N >= 2^32.            */
+int trs_gather_rows_q8(const void* qrows, int64_t V, int32_t E, const void* idx, int32_t idx_dtype,
+                       const int64_t* offsets, int64_t B, int32_t N, void* out, int32_t out_dtype, int32_t* err_flag,
+                       trs_stream_t stream);
+
+/* trs_embed_fm on the dequantized rows x = deq(qrows[idx[b,n] + offsets[n]]) of a Q8 table, one pass:
+ *   emb[b,n,:]  = x                                   (optional, out_dtype)
+ *   fm[b,:]     = 0.5 * ((sum_n x)^2 - sum_n x^2)     (optional, out_dtype, rounded once on store)
+ *   fm_sum[b,:] = sum_n x                             (optional, fp32)
+ *   first[b]    = sum_n first_table[idx[b,n]+offsets[n]]   (optional; first_table is a plain (V,) table of out_dtype, first
+ *                 (B,) of out_dtype: given together or not at all)
+ * Sum and sum of squares are fp32, fields in order.  An index outside [0, V) reads as a zero row (and a zero first-order
+ * value) and raises *err_flag.  B == 0: TRS_OK.
+ * TRS_EINVAL: NULL qrows / idx, bad size, first_table without first or the reverse; TRS_EDTYPE: out_dtype / idx_dtype.  */
+int trs_embed_fm_q8(const void* qrows, int64_t V, int32_t E, const void* idx, int32_t idx_dtype, const int64_t* offsets,
+                    int64_t B, int32_t N, void* emb, void* fm, float* fm_sum, const void* first_table, void* first,
+                    int32_t out_dtype, int32_t* err_flag, trs_stream_t stream);
+
+/* trs_bag_pool_ragged_fwd on a Q8 table: ids (n,), offsets (n_off = B or B + 1) as that entry takes them, out (B, E) of
+ * out_dtype.  mode 0 (sum): out[b,:] = sum_live deq(qrows[ids[p]]);  mode 1 (mean): that sum divided by the live count
+ * (one correctly rounded fp32 division; an empty bag is a zero row), inv_cnt (B,) fp32 = 1 / count or 0, optional.  fp32
+ * accumulation in list order, one rounding to out_dtype on store.  exclude_row >= 0: positions that hold that id issue
+ * no load and do not count.  A live id outside [0, V) reads as a zero row, raises *err_flag and counts.  Offsets are
+ * range-checked on the device exactly as trs_bag_pool_ragged_fwd does: clamped to [0, n], an offset outside it or a bag
+ * whose end lies before its begin (then empty) raises *err_flag.  A bag of more than trs_bag_ragged_long_len() ids is
+ * queued in `workspace` (trs_bag_pool_ragged_q8_workspace_bytes(B)) and reduced by one wave whose 64 / L lane groups stride
+ * the bag and fold their partials in a fixed order: a bag's result depends on its ids and its length alone.
+ * Max pooling and per-sample weights are not served on Q8 tables: mode 2 is TRS_EINVAL and the entry takes no weights.
+ * TRS_EINVAL: NULL qrows / offsets / out / workspace (ids: unless n == 0), mode not 0 or 1, bad size, n_off not B or
+ * B + 1, exclude_row outside [-1, V); TRS_ESHAPE: n or B >= 2^31 - 1; TRS_EDTYPE: out_dtype / ids_dtype / off_dtype;
+ * TRS_EWORKSPACE: ws_bytes below the query.  All before any launch.                                                  */
+size_t trs_bag_pool_ragged_q8_workspace_bytes(int64_t B);
+int trs_bag_pool_ragged_q8_fwd(const void* qrows, int64_t V, int32_t E, const void* ids, int32_t ids_dtype, int64_t n,
+                               const void* offsets, int32_t off_dtype, int64_t n_off, int64_t B, int32_t mode,
+                               int64_t exclude_row, void* out, int32_t out_dtype, float* inv_cnt, void* workspace,
+                               size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,9 @@ one pass -- against F RaggedListIndicesEmbedding calls plus the cat, and against
 permute to (B, F, E) (own inputs, see bench_raggedfields).
 --what rowwise [--shard-rows N]: the fused optimizer step alone (the update walk) for SGD, Adagrad, row-wise Adagrad and
 Adam through gather_rows and embed_fm, uniform and Zipf indices, on a bf16 table plain and with stochastic rounding; with
---shard-rows also the mapped owner update (own inputs, see bench_rowwise)."""
+--shard-rows also the mapped owner update (own inputs, see bench_rowwise).
+--what q8 [--rows 1000000,32000000]: the three forwards on a row-wise int8 (Q8) table against the bf16 kernels they mirror,
+on the same ids (own inputs, see bench_q8)."""
 import argparse
 import os
 import sys
@@ -264,6 +266,57 @@ def bench_ragged(a):
                           f"{ts[0] * 1e6:9.1f} .. {ts[-1] * 1e6:9.1f} us{extra}", flush=True)
             w.grad = None
         del padded, ids
+
+
+def bench_q8(a):
+    """The three Q8 forwards (csrc/q8.hip) against the bf16 kernels they mirror, on the same ids, bf16 out: the plain lookup
+    and lookup + FM (no block, the FM term only) at B x N uniform ids, and sum pooling of the ``longtail`` bags of --what
+    ragged, per table size of --rows.  The Q8 table is drawn as random bytes with a tail of scale 2^-7, bias -1 (a
+    quantizer pass over a 4 GiB float table is not what is timed).  Candidates alternate inside a round; every figure is
+    the median of --rounds per-round medians with their min..max.  GB/s on algorithmic bytes: per looked-up row id 8 +
+    row bytes (Q8: E + 16, bf16: 2 E) read, plus the output written."""
+    from torecsys_amd import quant
+    dev = torch.device("cuda:0")
+    B, N, E = a.B, a.N, a.E
+    S = quant.q8_row_bytes(E)
+    g = torch.Generator(device=dev).manual_seed(4321)
+    ln = torch.randint(0, 10, (B,), generator=g, device=dev)
+    ln[torch.randperm(B, generator=g, device=dev)[:300]] = torch.randint(2000, 6001, (300,), generator=g, device=dev)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), ln.cumsum(0)])
+    n = int(offsets[-1])
+    for V in [int(v) for v in a.rows.split(",")]:
+        w = torch.randn(V, E, generator=g, device=dev, dtype=torch.bfloat16)
+        q = torch.randint(0, 256, (V, S), generator=g, device=dev, dtype=torch.uint8)
+        q[:, E:] = 0
+        q[:, E:E + 8] = torch.tensor([2.0 ** -7, -1.0], device=dev).view(torch.uint8)
+        idx = torch.randint(0, V, (B, N), generator=g, device=dev)
+        ids = torch.randint(1, V, (n,), generator=g, device=dev)
+        print(f"q8 B={B} N={N} E={E} V={V}: bf16 table {V * E * 2 / 2**30:.2f} GiB, Q8 table {V * S / 2**30:.2f} GiB "
+              f"({S} B per row); ragged leg n={n} ids, {a.rounds} rounds x {a.iters} launches", flush=True)
+        out_rows = lambda rows: rows * E * 2
+        legs = [
+            ("gather", lambda: F_.gather_rows_q8(q, E, idx, None, torch.bfloat16), lambda: F_.gather_rows(w, idx),
+             B * N, out_rows(B * N)),
+            ("embed_fm", lambda: F_.embed_fm_q8(q, E, idx, None, None, False, torch.bfloat16),
+             lambda: F_.embed_fm(w, idx, want_emb=False), B * N, out_rows(B)),
+            ("ragged sum", lambda: F_.bag_pool_ragged_q8(q, E, ids, offsets, "sum", include_last_offset=True,
+                                                         out_dtype=torch.bfloat16),
+             lambda: F_.bag_pool_ragged(w, ids, offsets, "sum", include_last_offset=True), n, out_rows(B)),
+        ]
+        with torch.no_grad():
+            for name, fq, fb, rows, written in legs:
+                per = {"q8": [], "bf16": []}
+                for _ in range(a.rounds):
+                    per["q8"].append(timeit(fq, iters=a.iters, warm=2)[0])
+                    per["bf16"].append(timeit(fb, iters=a.iters, warm=2)[0])
+                med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+                alg = {"q8": rows * (8 + S) + written, "bf16": rows * (8 + 2 * E) + written}
+                for k in ("q8", "bf16"):
+                    print(f"V={V:9d} {name:10s} {k:4s} med {med[k] * 1e6:8.1f} us  spread {min(per[k]) * 1e6:8.1f} .. "
+                          f"{max(per[k]) * 1e6:8.1f} us  {alg[k] / med[k] / 1e9:7.0f} GB/s on {alg[k] / 1e6:.0f} MB (alg)",
+                          flush=True)
+                print(f"V={V:9d} {name:10s} bf16 / q8 time = {med['bf16'] / med['q8']:.2f}x", flush=True)
+        del w, q, idx, ids
 
 
 def bench_raggedfields(a):
@@ -1430,7 +1483,10 @@ def main():
     ap.add_argument("--shape", default="fixed,uniform,longtail", help="ragged: bag-length distributions to run")
     ap.add_argument("--modes", default="sum,mean,max", help="ragged / raggedfields: pooling modes to run")
     ap.add_argument("--fields", type=int, default=4, help="raggedfields: the number of multi-valued fields F")
+    ap.add_argument("--rows", default="1000000,32000000", help="q8: table sizes V to run")
     a = ap.parse_args()
+    if a.what == "q8":           # own inputs: not part of "all"
+        return bench_q8(a)
     if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"
         return bench_ragged(a)
     if a.what == "raggedfields":  # own inputs and modules: not part of "all"

@@ -229,6 +229,13 @@ SIGNATURES = {
     "trs_bag_pool_segments": (c_int32, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P]),
     "trs_bag_combine": (c_int32, [_P, _I32, _I64, _I32, _F32, _I32, _P, _P]),
     "trs_bag_expand_grad": (c_int32, [_P, _I32, _I32, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "trs_q8_row_bytes": (_SZ, [_I32]),
+    "trs_q8_quantize_rows": (c_int32, [_P, _I64, _I32, _I32, _P, _P]),
+    "trs_gather_rows_q8": (c_int32, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _I32, _P, _P]),
+    "trs_embed_fm_q8": (c_int32, [_P, _I64, _I32, _P, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    "trs_bag_pool_ragged_q8_workspace_bytes": (_SZ, [_I64]),
+    "trs_bag_pool_ragged_q8_fwd": (c_int32, [_P, _I64, _I32, _P, _I32, _I64, _P, _I32, _I64, _I64, _I32, _I64, _P, _I32, _P,
+                                             _P, _SZ, _P, _P]),
 }
 
 _lib = None

@@ -24,7 +24,10 @@ FLAGS = ["-O3", "-std=c++20", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # backward 1.15 vs 1.04 ms)
 FILE_FLAGS = {"cin_mfma.hip": ["-fno-slp-vectorize"], "cross_mfma.hip": ["-fno-slp-vectorize"],
               "mlp_fused.hip": ["-fno-slp-vectorize"], "mlp_ro.hip": ["-fno-slp-vectorize"],
-              **{f"mlp_ro_{k}.hip": ["-fno-slp-vectorize"] for k in ("dcn_fwd", "dcn_bwd", "tail_fwd", "tail_bwd")}}
+              **{f"mlp_ro_{k}.hip": ["-fno-slp-vectorize"] for k in ("dcn_fwd", "dcn_bwd", "tail_fwd", "tail_bwd")},
+              # the Q8 dequantization is one fp32 multiply and one fp32 add per element by the format's definition: keep
+              # them single instructions, no packed fp32 pairs
+              "q8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

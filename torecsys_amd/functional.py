@@ -4332,3 +4332,119 @@ def rank_loss(pos: torch.Tensor, neg: Optional[torch.Tensor], kind, margin: floa
     pos, neg, mask = strip(pos), strip(neg), strip(mask)
     value_dtype_code(pos)
     return _RankLoss.apply(pos, neg, _rank_kind_code(kind), float(margin), mask, rank_reduction_code(reduction))
+
+
+# --------------------------------------------------------------------------------------------
+# Row-wise int8 (Q8) tables: forward only (csrc/q8.hip).  No autograd Function: a Q8 table is not trained, the outputs
+# never require grad.  ``qrows`` is the (V, S) uint8 tensor of quant.quantize_rows, S = round_up(E + 8, 16).
+# --------------------------------------------------------------------------------------------
+_Q8_OUT = {torch.float32: _abi.TRS_F32, torch.bfloat16: _abi.TRS_BF16}
+
+
+def _q8_table(op: str, qrows: torch.Tensor, E: int, out_dtype: torch.dtype) -> Tuple[torch.Tensor, int, int]:
+    """(contiguous qrows, V, out dtype code) after the checks every Q8 lookup shares."""
+    if not isinstance(E, int) or E <= 0:
+        raise ValueError(f"{op}: E must be a positive int, got {E!r}")
+    if qrows.dtype != torch.uint8:
+        raise TypeError(f"{op}: qrows must be uint8, got {qrows.dtype}")
+    S = (E + 8 + 15) // 16 * 16
+    if qrows.dim() != 2 or qrows.shape[1] != S:
+        raise ValueError(f"{op}: qrows must be (V, {S}) for E={E}, got shape {tuple(qrows.shape)}")
+    if out_dtype not in _Q8_OUT:
+        raise TypeError(f"{op}: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    return qrows.contiguous(), qrows.shape[0], _Q8_OUT[out_dtype]
+
+
+def _q8_offsets(op: str, offsets: Optional[torch.Tensor], N: int) -> Optional[torch.Tensor]:
+    if offsets is None:
+        return None
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] != N:
+        raise ValueError(f"{op}: offsets must be int64 ({N},), got {offsets.dtype} {tuple(offsets.shape)}")
+    return offsets.contiguous()
+
+
+def gather_rows_q8(qrows: torch.Tensor, E: int, idx: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                   out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """out[b,n,:] = dequantized row ``idx[b,n] + offsets[n]`` of a Q8 table, rounded once to ``out_dtype``: (B,N,E)."""
+    q, V, code = _q8_table("gather_rows_q8", qrows, E, out_dtype)
+    idx = _as_index(idx)
+    if idx.dim() == 1:
+        idx = idx.unsqueeze(-1)
+    if idx.dim() != 2:
+        raise ValueError(f"indices must be (B, N), got shape {tuple(idx.shape)}")
+    B, N = idx.shape
+    offsets = _q8_offsets("gather_rows_q8", offsets, N)
+    dev = require_device(q, idx, offsets)
+    out = torch.empty(B, N, E, dtype=out_dtype, device=dev)
+    flag = _ErrFlag(dev)
+    call("trs_gather_rows_q8", ptr(q), V, E, ptr(idx), index_dtype_code(idx), ptr(offsets), B, N, ptr(out), code,
+         ptr(flag.t), stream_ptr())
+    flag.check("gather_rows_q8")
+    return out
+
+
+def embed_fm_q8(qrows: torch.Tensor, E: int, idx: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                first_weight: Optional[torch.Tensor] = None, want_emb: bool = True,
+                out_dtype: torch.dtype = torch.float32
+                ) -> Tuple[Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor]]:
+    """``embed_fm`` on the dequantized rows of a Q8 table, one pass: (emb (B,N,E) | None, fm (B,E), first (B,1) | None)
+    of ``out_dtype``.  ``first_weight`` is a float (V,) | (V,1) table of ``out_dtype`` (one value per row is not worth
+    quantizing)."""
+    q, V, code = _q8_table("embed_fm_q8", qrows, E, out_dtype)
+    idx = _as_index(idx)
+    if idx.dim() != 2:
+        raise ValueError(f"indices must be (B, N), got shape {tuple(idx.shape)}")
+    B, N = idx.shape
+    offsets = _q8_offsets("embed_fm_q8", offsets, N)
+    fw = None
+    if first_weight is not None:
+        if first_weight.dtype != out_dtype or first_weight.numel() != V:
+            raise ValueError(f"embed_fm_q8: the first-order table must hold V={V} values of {out_dtype}, got "
+                             f"{tuple(first_weight.shape)} {first_weight.dtype}")
+        fw = first_weight.detach().contiguous()
+    dev = require_device(q, idx, offsets, fw)
+    emb = torch.empty(B, N, E, dtype=out_dtype, device=dev) if want_emb else None
+    fm = torch.empty(B, E, dtype=out_dtype, device=dev)
+    first = torch.empty(B, 1, dtype=out_dtype, device=dev) if fw is not None else None
+    flag = _ErrFlag(dev)
+    call("trs_embed_fm_q8", ptr(q), V, E, ptr(idx), index_dtype_code(idx), ptr(offsets), B, N, ptr(emb), ptr(fm), None,
+         ptr(fw), ptr(first), code, ptr(flag.t), stream_ptr())
+    flag.check("embed_fm_q8")
+    return emb, fm, first
+
+
+def bag_pool_ragged_q8(qrows: torch.Tensor, E: int, ids: torch.Tensor, offsets: torch.Tensor, mode: str = "mean",
+                       padding_idx: Optional[int] = None, *, exclude_padding: bool = False,
+                       include_last_offset: bool = False, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``bag_pool_ragged`` on a Q8 table: (B,1,E) pooled rows of ragged bags (``ids`` (n,) | (n,1), ``offsets``), ``sum`` or
+    ``mean`` (the sum over the live count, one division).  ``exclude_padding`` leaves the ids equal to ``padding_idx``
+    out.  Max pooling and per-sample weights are not served on Q8 tables.  Offsets are checked on the device as
+    ``bag_pool_ragged`` does (``index_errors_seen()``)."""
+    if mode not in ("sum", "mean"):
+        raise ValueError(f"bag_pool_ragged_q8: mode must be 'sum' or 'mean', got {mode!r}")
+    q, V, code = _q8_table("bag_pool_ragged_q8", qrows, E, out_dtype)
+    ids = _as_index(ids)
+    if ids.dim() == 2 and ids.shape[1] == 1:
+        ids = ids.reshape(-1)
+    if ids.dim() != 1:
+        raise ValueError(f"ids must be (n,) or (n, 1), got shape {tuple(ids.shape)}")
+    offsets = _as_index(offsets)
+    if offsets.dim() != 1:
+        raise ValueError(f"offsets must be one-dimensional, got shape {tuple(offsets.shape)}")
+    B = offsets.shape[0] - 1 if include_last_offset else offsets.shape[0]
+    if B < 0:
+        raise ValueError("bag_pool_ragged_q8: include_last_offset=True needs at least one offset")
+    n = ids.shape[0]
+    if n >= 2 ** 31 - 1:
+        raise ValueError(f"bag_pool_ragged_q8: {n} ids, must be below 2^31 - 1")
+    padding_idx = _norm_padding("bag_pool_ragged_q8", padding_idx, V, exclude_padding)
+    dev = require_device(q, ids, offsets)
+    out = torch.empty(B, E, dtype=out_dtype, device=dev)
+    ws_bytes = size_query("trs_bag_pool_ragged_q8_workspace_bytes", B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    flag = _ErrFlag(dev)
+    call("trs_bag_pool_ragged_q8_fwd", ptr(q), V, E, ptr(ids), index_dtype_code(ids), n, ptr(offsets),
+         index_dtype_code(offsets), offsets.shape[0], B, BAG_MODES[mode], padding_idx if exclude_padding else -1, ptr(out),
+         code, None, ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+    flag.check("bag_pool_ragged_q8")
+    return out.unsqueeze(1)
