@@ -1362,6 +1362,31 @@ int trs_embed_pair_score_bwd(const void* a_table, int64_t Va, const void* a_idx,
                              int64_t B, int32_t K, int32_t sim, const void* g_scores, int32_t g_dtype, void* g_block,
                              void* workspace, size_t ws_bytes, trs_stream_t stream);
 
+/* ---- top-k retrieval over a whole target table (csrc/topk.hip; not in the reference) ---------------------------------
+ * For every sample b the k best rows of the target range, by the similarity of the pair-score entries above:
+ *   score[b, j] = sim(A[anchor_idx[b] + anchor_offset], T[target_lo + j]),  j = 0 .. Vt-1,  Vt = target_hi - target_lo
+ * anchor_table (Va, E) and target_table (at least target_hi rows, E) of one value dtype (the pointers may be equal);
+ * anchor_idx (B) of idx_dtype, or NULL: the anchor of sample b is row b + anchor_offset (anchor_table is then a (B, E)
+ * query matrix).  sim: 0 = inner product, 1 = cosine, dot / (max(|a|, eps) max(|t|, eps)) with eps = 1e-8, the norms
+ * summed in fp32.  exclude (B, X) of excl_dtype, or NULL (X ignored): ids j that must not be returned for sample b;
+ * negative entries are padding.
+ * out_val (B, k) fp32 and out_idx (B, k) int64 hold the k best j of every sample, ordered by score descending and, among
+ * equal scores, by j ascending -- so the result is a pure function of the inputs, whatever the split.  Ids are relative to
+ * target_lo.  Where fewer than k targets remain (exclusion), the trailing slots hold -inf and -1.  A NaN score is never
+ * returned.  An anchor id outside [0, Va) reads as a zero row and raises *err_flag.
+ * Scores come from the matrix cores (fp32 accumulation) and the selection sits next to the accumulators: no (B, Vt)
+ * block exists.  The target range is cut into S ranges, S a pure function of (B, Vt); for S > 1 every (sample, range)
+ * leaves k candidates in the workspace (trs_topk_scores_workspace_bytes; 0 for S = 1) and a second launch merges them.
+ * No host read-back, no allocation: capturable.
+ * 1 <= k <= 128, k <= Vt < 2^31; rows of whole 16-byte vectors, E <= 256 (TRS_ESHAPE); 16-byte aligned tables
+ * (TRS_EALIGN).  B == 0 returns TRS_OK and touches nothing.  Errors, all before any launch: NULL pointer, bad sim, bad
+ * index / exclude dtype, X < 1, bad size or k TRS_EINVAL; value dtype TRS_EDTYPE; workspace TRS_EWORKSPACE.              */
+size_t trs_topk_scores_workspace_bytes(int64_t B, int64_t Vt, int32_t k);
+int trs_topk_scores(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype, int64_t anchor_offset,
+                    int64_t B, const void* target_table, int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype,
+                    int32_t sim, int32_t k, const void* exclude, int32_t excl_dtype, int32_t X, float* out_val,
+                    int64_t* out_idx, void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
 /* ---- ranking losses over (positive, negatives) scores (csrc/rank.hip; losses/ltr/functional.py) ---------------------
  * pos: one value per sample at pos[b * pos_stride]; neg: K values per sample at neg[b * neg_stride + k] (columns 0 and
  * 1 .. K of one (B, 1+K) score matrix: pos = S, neg = S + 1, both strides 1 + K); dtype TRS_F32 | TRS_BF16; mask (B) one

@@ -37,7 +37,9 @@ permute to (B, F, E) (own inputs, see bench_raggedfields).
 Adam through gather_rows and embed_fm, uniform and Zipf indices, on a bf16 table plain and with stochastic rounding; with
 --shard-rows also the mapped owner update (own inputs, see bench_rowwise).
 --what q8 [--rows 1000000,32000000]: the three forwards on a row-wise int8 (Q8) table against the bf16 kernels they mirror,
-on the same ids (own inputs, see bench_q8)."""
+on the same ids (own inputs, see bench_q8).
+--what topk [--k 100] [--sim dot|cosine] [--budget 4]: top-k retrieval over a 1 M-row table against the chunked ATen
+composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk)."""
 import argparse
 import os
 import sys
@@ -1380,6 +1382,76 @@ def bench_rank(a):
               flush=True)
 
 
+def bench_topk(a):
+    """functional.topk_scores (csrc/topk.hip) against the chunked ATen composition: gather the anchors, ``matmul`` against
+    table chunks sized so that a chunk's (B, chunk) scores stay within 1 GiB of fp32, ``topk`` per chunk, ``topk`` over the
+    chunks' candidates (cosine: anchors and chunk rows normalised first).  The composition multiplies in the table's dtype,
+    so its bf16 scores are rounded to bf16 before the selection -- it is a yardstick for time, not for the values; the
+    fp32 values of the two are compared once per shape.  B in {256, 4 096, 65 536} against a 1 M-row table, E = 64, bf16
+    and fp32, uniform random rows; then, at B = 4 096, a table whose scores increase along the rows (every tile inserts).
+    The two candidates take turns launch by launch after 2 warm-ups each; a shape stops after 20 launches of each or once
+    --budget seconds of timed work have passed, with at least 3.  Median and spread of all timed launches; achieved
+    FLOP/s are 2 B V E over the median."""
+    dev = torch.device("cuda:0")
+    V, E, k, sim = a.V, a.E, a.k, a.sim
+    g = torch.Generator(device=dev).manual_seed(77)
+
+    def comp(aw, idx, tw):
+        q = aw[idx]
+        if sim == "cosine":
+            q = torch.nn.functional.normalize(q.float(), dim=1, eps=1e-8).to(q.dtype)
+        chunk = max(4096, min(V, (1 << 28) // idx.shape[0]))
+        vals, ids = [], []
+        for lo in range(0, V, chunk):
+            t = tw[lo:lo + chunk]
+            if sim == "cosine":
+                t = torch.nn.functional.normalize(t.float(), dim=1, eps=1e-8).to(t.dtype)
+            v, i = torch.topk(q @ t.T, min(k, t.shape[0]), dim=1)
+            vals.append(v)
+            ids.append(i + lo)
+        v, j = torch.topk(torch.cat(vals, 1), k, dim=1)
+        return v.float(), torch.cat(ids, 1).gather(1, j)
+
+    def race(ours, aten):
+        for f in (ours, aten):
+            for _ in range(2):
+                f()
+        torch.cuda.synchronize()
+        ts, spent = {"hip": [], "aten": []}, 0.0
+        while len(ts["hip"]) < 3 or (len(ts["hip"]) < 20 and spent < a.budget):
+            for name, f in (("hip", ours), ("aten", aten)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1) * 1e-3)
+                spent += ts[name][-1]
+        return {n: sorted(v) for n, v in ts.items()}
+
+    def show(tag, B, aw, idx, tw):
+        ts = race(lambda: F_.topk_scores(aw, idx, tw, k, sim=sim), lambda: comp(aw, idx, tw))
+        hv, av = F_.topk_scores(aw, idx, tw, k, sim=sim)[0], comp(aw, idx, tw)[0]
+        med = {n: v[len(v) // 2] for n, v in ts.items()}
+        for n in ("hip", "aten"):
+            print(f"{tag:34s} {n:5s} med {med[n] * 1e3:9.3f} ms  spread {ts[n][0] * 1e3:9.3f} .. {ts[n][-1] * 1e3:9.3f} ms "
+                  f"({len(ts[n])} launches)  {2.0 * B * V * E / med[n] / 1e12:7.1f} TFLOP/s", flush=True)
+        print(f"{tag:34s} aten / hip = {med['aten'] / med['hip']:.2f}   max |value difference| = "
+              f"{float((hv - av).abs().max()):.3e}", flush=True)
+
+    print(f"topk: V = {V}, E = {E}, k = {k}, sim = {sim}")
+    for dt in (torch.bfloat16, torch.float32):
+        tw = torch.randn(V, E, generator=g, device=dev).to(dt)
+        aw = torch.randn(100_000, E, generator=g, device=dev).to(dt)
+        for B in (256, 4096, 65536):
+            idx = torch.randint(0, aw.shape[0], (B,), generator=g, device=dev)
+            show(f"{str(dt)[6:]} B={B}", B, aw, idx, tw)
+        up = (torch.arange(V, device=dev, dtype=torch.float32) / V).unsqueeze(1).expand(V, E).to(dt).contiguous()
+        idx = torch.randint(0, aw.shape[0], (4096,), generator=g, device=dev)
+        show(f"{str(dt)[6:]} B=4096 increasing scores", 4096, aw.abs(), idx, up)
+        del tw, aw, up
+
+
 def bench_bagshard(a):
     """Sharded bag pooling (csrc/bag_shard.hip) on ONE GPU at (B, L, E, V), fp32 and bf16: the four kernels alone with this
     process playing rank 0 of ``--world`` (it routes its batch over W owners, pools the segments W senders with batches like
@@ -1484,7 +1556,11 @@ def main():
     ap.add_argument("--modes", default="sum,mean,max", help="ragged / raggedfields: pooling modes to run")
     ap.add_argument("--fields", type=int, default=4, help="raggedfields: the number of multi-valued fields F")
     ap.add_argument("--rows", default="1000000,32000000", help="q8: table sizes V to run")
+    ap.add_argument("--k", type=int, default=100, help="topk: items returned per anchor")
+    ap.add_argument("--budget", type=float, default=4.0, help="topk: seconds of timed launches per shape")
     a = ap.parse_args()
+    if a.what == "topk":         # own inputs: not part of "all"
+        return bench_topk(a)
     if a.what == "q8":           # own inputs: not part of "all"
         return bench_q8(a)
     if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"

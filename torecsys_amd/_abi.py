@@ -215,6 +215,9 @@ SIGNATURES = {
     "trs_pair_score_bwd_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "trs_embed_pair_score_bwd": (c_int32, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P,
                                            _I32, _P, _P, _SZ, _P]),
+    "trs_topk_scores_workspace_bytes": (_SZ, [_I64, _I64, _I32]),
+    "trs_topk_scores": (c_int32, [_P, _I64, _P, _I32, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P,
+                                  _P, _P, _SZ, _P, _P]),
     "trs_rank_loss_workspace_bytes": (_SZ, [_I64]),
     "trs_rank_loss_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _SZ, _P]),
     "trs_rank_loss_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _I64, _P, _I64,

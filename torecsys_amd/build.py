@@ -27,7 +27,9 @@ FILE_FLAGS = {"cin_mfma.hip": ["-fno-slp-vectorize"], "cross_mfma.hip": ["-fno-s
               **{f"mlp_ro_{k}.hip": ["-fno-slp-vectorize"] for k in ("dcn_fwd", "dcn_bwd", "tail_fwd", "tail_bwd")},
               # the Q8 dequantization is one fp32 multiply and one fp32 add per element by the format's definition: keep
               # them single instructions, no packed fp32 pairs
-              "q8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "q8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the cosine scalings between the MFMAs and the selection: single multiplies, as above
+              "topk.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

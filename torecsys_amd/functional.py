@@ -4182,6 +4182,67 @@ def pair_scores(anchor_weight: torch.Tensor, anchor_idx: torch.Tensor, target_we
     return _PairScores.apply(anchor_weight, a_idx, tw, t_idx, a_off, t_off, sim, out_dtype, opt, torch.is_grad_enabled())
 
 
+TOPK_MAX_K, TOPK_MAX_E = 128, 256
+
+
+def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_weight: Optional[torch.Tensor],
+                k: int, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None, sim="dot",
+                exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The best ``k`` rows of ``target_weight[target_lo:target_hi]`` for every anchor, in one HIP pass (csrc/topk.hip):
+    MFMA scores with the selection next to the accumulators, no (B, Vt) block.  Anchor b is row ``anchor_idx[b] +
+    anchor_offset`` of ``anchor_weight``; ``anchor_idx=None``: ``anchor_weight`` is the (B, E) query matrix itself.
+    ``target_weight`` None: the anchor table (the shared layout of ``pair_scores``).  ``sim``: 'dot' | 'cosine', as
+    ``pair_scores``.  ``exclude`` (B, X) ids that must not be returned for sample b (negative entries are padding).
+    Returns ``values (B, k)`` fp32 and ``ids (B, k)`` int64, ids relative to ``target_lo`` (what ``pair_scores`` takes with
+    ``target_offset=target_lo``), by score descending and, among equal scores, id ascending; where fewer than k targets
+    remain the trailing slots hold -inf / -1.  1 <= k <= 128; bf16 or fp32 contiguous tables of one dtype, rows of whole
+    16-byte vectors, E <= 256.  No gradient, no host read-back; an anchor id outside its table scores as a zero row and
+    raises the index flag."""
+    code = _sim_code(sim)
+    aw = anchor_weight.detach()
+    tw = aw if target_weight is None or target_weight is anchor_weight else target_weight.detach()
+    if aw.dim() != 2 or tw.dim() != 2 or aw.shape[1] != tw.shape[1]:
+        raise ValueError(f"topk_scores: two (V, E) tables of one width expected, got {tuple(aw.shape)} and "
+                         f"{tuple(tw.shape)}")
+    if aw.dtype not in (torch.float32, torch.bfloat16) or tw.dtype != aw.dtype:
+        raise TypeError(f"topk_scores: bf16 or fp32 tables of one dtype expected, got {aw.dtype} and {tw.dtype}")
+    E = aw.shape[1]
+    if E < 1 or E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
+        raise NotImplementedError(f"topk_scores: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} "
+                                  f"of {aw.dtype}")
+    lo = int(target_lo)
+    hi = tw.shape[0] if target_hi is None else int(target_hi)
+    if not 0 <= lo < hi <= tw.shape[0]:
+        raise ValueError(f"topk_scores: target range [{lo}, {hi}) is not inside the {tw.shape[0]} target rows")
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K or k > hi - lo:
+        raise ValueError(f"topk_scores: k must be in 1 .. {TOPK_MAX_K} and at most the {hi - lo} targets, got {k}")
+    a_idx = None if anchor_idx is None else _as_index(anchor_idx).reshape(-1)
+    B = aw.shape[0] if a_idx is None else a_idx.shape[0]
+    ex = None
+    if exclude is not None:
+        ex = _as_index(exclude)
+        if ex.dim() != 2 or ex.shape[0] != B or ex.shape[1] < 1:
+            raise ValueError(f"topk_scores: exclude ({B}, X >= 1) expected, got {tuple(ex.shape)}")
+    for name, t in (("anchor_weight", aw), ("target_weight", tw)):
+        if not t.is_contiguous():
+            raise ValueError(f"topk_scores: {name} must be contiguous, got strides {tuple(t.stride())}")
+    dev = require_device(aw, a_idx, tw, ex)
+    values = torch.empty(B, k, dtype=torch.float32, device=dev)
+    ids = torch.empty(B, k, dtype=torch.int64, device=dev)
+    if B == 0:
+        return values, ids
+    ws_bytes = size_query("trs_topk_scores_workspace_bytes", B, hi - lo, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    flag = _ErrFlag(dev)
+    call("trs_topk_scores", ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
+         int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, k, ptr(ex),
+         index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(values), ptr(ids), ptr(ws),
+         ws_bytes, ptr(flag.t), stream_ptr())
+    flag.check("topk_scores")
+    return values, ids
+
+
 _row_ids = {}       # (device, B) -> (2 b, 2 b + 1): the rows of a (B, 2, E) block seen as a (2 B, E) table
 
 

@@ -132,6 +132,14 @@ class EmbeddingPairScorer(nn.Module):
         return F_.pair_scores(self.anchor.weight, anchor_idx, tw, target_idx, self.anchor_offset, self.target_offset,
                               self.similarity, self.out_dtype, self._fused_opt)
 
+    def topk(self, anchor_idx: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None):
+        """The best ``k`` targets of the whole target table for every anchor id (functional.topk_scores): ``(values (B, k)
+        fp32, ids (B, k) int64)``, the ids as ``forward`` takes them.  A shared table is searched from ``target_offset``
+        to its end.  ``exclude`` (B, X): target ids not to return (negative entries are padding)."""
+        tw = None if self.target is None else self.target.weight
+        return F_.topk_scores(self.anchor.weight, anchor_idx, tw, k, anchor_offset=self.anchor_offset,
+                              target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
+
 
 class BCEWithLogitsLoss(nn.Module):
     """``nn.BCEWithLogitsLoss()`` (mean reduction, no weights) on the HIP device: ``loss(logits, labels)`` with logits in
