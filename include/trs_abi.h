@@ -1387,6 +1387,24 @@ int trs_topk_scores(const void* anchor_table, int64_t Va, const void* anchor_idx
                     int32_t sim, int32_t k, const void* exclude, int32_t excl_dtype, int32_t X, float* out_val,
                     int64_t* out_idx, void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
 
+/* trs_topk_scores over a Q8 target table (the format is described with the Q8 entries below): target_q holds at least
+ * target_hi rows of trs_q8_row_bytes(E) bytes; the anchors stay float, anchor_table (Va, E) of anchor_dtype (TRS_F32 |
+ * TRS_BF16), through anchor_idx or as a (B, E) query matrix exactly as above.  Neither a float copy of the table nor a
+ * (B, Vt) block is formed: the codes are converted to anchor_dtype (exact) on their way to the matrix cores, and the
+ * score is taken in the factored form of the format,
+ *   d = sum_e a[e] c[e]  (fp32 accumulation),  sa = sum_e a[e]  (fp32, in order),  score = d * scale + sa * bias
+ * (each product and the sum rounded once), so a score is a function of the row's bytes and the anchor; it is NOT the
+ * product with the twice-rounded x[e] of the dequantizing entries, from which it differs by rounding only.  Cosine:
+ * score / (max(|a|, eps) max(|x|, eps)), |x| the fp32 norm of the dequantized row, summed as squares of c * scale + bias.
+ * Ordering, ids, padding slots, exclusion, the zero row of an anchor id outside [0, Va) (score 0 for every target, ids
+ * 0 .. k-1, *err_flag raised), the split, the workspace (trs_topk_scores_workspace_bytes, the same function of B, Vt, k)
+ * and every limit and error code are those of trs_topk_scores; E * sizeof(anchor_dtype) must be a multiple of 16.       */
+int trs_topk_scores_q8(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                       int64_t anchor_offset, int64_t B, const void* target_q, int64_t target_lo, int64_t target_hi,
+                       int32_t E, int32_t anchor_dtype, int32_t sim, int32_t k, const void* exclude, int32_t excl_dtype,
+                       int32_t X, float* out_val, int64_t* out_idx, void* workspace, size_t ws_bytes, int32_t* err_flag,
+                       trs_stream_t stream);
+
 /* ---- ranking losses over (positive, negatives) scores (csrc/rank.hip; losses/ltr/functional.py) ---------------------
  * pos: one value per sample at pos[b * pos_stride]; neg: K values per sample at neg[b * neg_stride + k] (columns 0 and
  * 1 .. K of one (B, 1+K) score matrix: pos = S, neg = S + 1, both strides 1 + K); dtype TRS_F32 | TRS_BF16; mask (B) one
@@ -1424,6 +1442,8 @@ int trs_rank_loss_bwd(const void* pos, int64_t pos_stride, const void* neg, int6
  *   [E+8, S)    zero
  * Dequantization, in every entry:  x[e] = float(c[e]) * scale + bias  in fp32, the product and the sum each rounded (no
  * fma): a pure function of the row's bytes.  E <= 0: trs_q8_row_bytes returns 0.
+ * Retrieval (trs_topk_scores_q8, above) does not form x[e]: its scores use the factored form d * scale + sa * bias, also a
+ * pure function of the row's bytes and the anchor.
  *
  * trs_q8_quantize_rows: table (V, E) fp32 / bf16 (bf16 is widened first) -> qrows (V, S), per row with finite values:
  *   bias  = min_e x[e],  scale = (max_e x[e] - bias) / 255.0f   (one subtraction, one correctly rounded division; a min

@@ -29,9 +29,21 @@
 //
 // Merge.  S > 1: every (anchor, split) writes its k sorted keys to the workspace and a second kernel, one wave per anchor,
 // folds the S lists through the same sort.  S = 1: the first kernel writes values / ids itself.
+//
+// Q8 targets (template parameter Q8; trs_topk_scores_q8).  The target table is row-wise int8 (q8_common.hpp: a row of E
+// codes, fp32 scale, fp32 bias, S = round_up(E + 8, 16) bytes) and the score is taken in the format's factored form:
+//   d[b, j] = sum_e a_b[e] c_j[e]  (MFMA; the codes 0..255 are exact in bf16 and fp32)      sa[b] = sum_e a_b[e]  (fp32)
+//   score   = d * scale_j + sa * bias_j                                  cosine: * ainv[b] * tinv[j], tinv from the sum of
+// squares of c * scale + bias.  LDS-DMA cannot convert, so a Q8 tile goes through registers: a thread owns up to
+// TK_Q8_UNITS 16-byte vectors of the tile's rows (tails included, consecutive lanes consecutive vectors), loads those of
+// tile t + 1 before the k-loop of tile t, and behind the k-loop converts the codes to the anchor dtype -- each code once per
+// workgroup -- and stores them as ordinary swizzled operand chunks into the other buffer; the (scale, bias) words of the
+// vectors that hold them go to two per-tile LDS arrays next to tinv, sa sits next to ainv.  Operand loads, k-loop,
+// selection and merge are the float kernel's.  Rows past the end of a range stage as code 0, scale 0, bias 0.
 #include <algorithm>
 
 #include "lds_dma.hpp"
+#include "q8_common.hpp"
 
 namespace trs {
 
@@ -43,6 +55,7 @@ constexpr float TK_COS_EPS = 1e-8f;      // rank.hip's COS_EPS
 constexpr int TK_MAX_K = 128, TK_MAX_E = 256, TK_MAX_SPLITS = 64;
 constexpr int TK_SLACK = 16;             // keys one 16-target group can add to a row: 4 lanes x 4 targets
 constexpr size_t TK_MAX_LDS = 160 * 1024;
+constexpr int TK_Q8_UNITS = 9;           // 16-byte vectors of a Q8 tile per thread: TR * 17 / threads <= 8.5 in every arrangement
 
 struct TopkArgs {
   const char* a_table;
@@ -60,6 +73,7 @@ struct TopkArgs {
   int sw_shift, sw_mask;   // g(r) = (r >> sw_shift) & sw_mask
   int sim;
   bool idx64, excl64, dma;
+  int E, q_stride, q_nv;   // Q8 targets: columns, bytes of a row (S) and its 16-byte vectors
 };
 
 __device__ __forceinline__ void tk_wave_sync() {
@@ -126,7 +140,51 @@ __device__ __forceinline__ float tk_row_sq(const char* rows, int r, const TopkAr
   return s;
 }
 
-template <typename T, int AR, int TR>
+// sum of LDS row r (its real chunks, in order), fp32: sa of the factored Q8 score
+template <typename T>
+__device__ __forceinline__ float tk_row_sum(const char* rows, int r, const TopkArgs& p) {
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+  float s = 0.f;
+  for (int c = 0; c < p.nce; ++c) {
+    float f[Vec16<T>::VE];
+    Vec16<T>::unpack(*reinterpret_cast<const uint4*>(rows + ((size_t)r * p.nc + (c ^ g)) * 16), f);
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::VE; ++e) s += f[e];
+  }
+  return s;
+}
+
+// squared norm of the dequantized row whose codes are LDS row r: the sum of squares of c * scale + bias itself (expanded
+// into sums of c and c^2 it cancels where bias = the row minimum < 0)
+template <typename T>
+__device__ __forceinline__ float tk_q8_row_sq(const char* rows, int r, float scale, float bias, const TopkArgs& p) {
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+  float s = 0.f;
+  for (int c = 0; c < p.nce; ++c) {
+    float f[Vec16<T>::VE];
+    Vec16<T>::unpack(*reinterpret_cast<const uint4*>(rows + ((size_t)r * p.nc + (c ^ g)) * 16), f);
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::VE; ++e) {
+      const float x = f[e] * scale + bias;
+      s += x * x;
+    }
+  }
+  return s;
+}
+
+// the 4 codes of a word as fp32 (v_cvt_f32_ubyte<k>) and as bf16: a code has 8 significant bits, its fp32 form ends in 16
+// zero bits and the high half IS the bf16
+__device__ __forceinline__ uint4 tk_codes_f32(uint32_t w) {
+  return make_uint4(__float_as_uint((float)(w & 0xffu)), __float_as_uint((float)((w >> 8) & 0xffu)),
+                    __float_as_uint((float)((w >> 16) & 0xffu)), __float_as_uint((float)(w >> 24)));
+}
+__device__ __forceinline__ uint2 tk_codes_bf16(uint32_t w) {
+  const uint4 f = tk_codes_f32(w);
+  return make_uint2((f.x >> 16) | f.y, (f.z >> 16) | f.w);
+}
+__device__ __forceinline__ uint32_t tk_word(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
+template <typename T, int AR, int TR, bool Q8>
 __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   constexpr int AT = AR / 16, NT = TR / 16;
@@ -140,7 +198,11 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   int* cnt = reinterpret_cast<int*>(tauk + NA);
   float* ainv = reinterpret_cast<float*>(cnt + NA);
   float* tinv = ainv + NA;      // [2][TR]
+  float* tsc = tinv + 2 * TR;   // Q8: [2][TR] scales, [2][TR] biases, [NA] anchor sums
+  float* tbi = tsc + 2 * TR;
+  float* sa = tbi + 2 * TR;
   const bool cosine = p.sim == TK_COS;
+  constexpr int CPV = 16 * (int)sizeof(T) / 16;      // operand chunks the 16 codes of one vector become
 
   // ---- the anchors, once
   const int64_t b0 = (int64_t)blockIdx.x * NA;
@@ -192,16 +254,85 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
     }
   };
   auto tile_norms = [&](int buf) {
-    for (int r = threadIdx.x; r < TR; r += blockDim.x)
-      tinv[buf * TR + r] = 1.f / fmaxf(sqrtf(tk_row_sq<T>(Ts + (size_t)buf * TR * RB, r, p)), TK_COS_EPS);
+    for (int r = threadIdx.x; r < TR; r += blockDim.x) {
+      const char* rows = Ts + (size_t)buf * TR * RB;
+      float sq;
+      if constexpr (Q8) sq = tk_q8_row_sq<T>(rows, r, tsc[buf * TR + r], tbi[buf * TR + r], p);
+      else sq = tk_row_sq<T>(rows, r, p);
+      tinv[buf * TR + r] = 1.f / fmaxf(sqrtf(sq), TK_COS_EPS);
+    }
   };
-  if (ntile > 0) load_tile(0, 0);
+  // Q8: unit i of this thread is vector v of tile row r, packed r | v << 8 (-1: none); consecutive threads take
+  // consecutive vectors of a row, so a wave's load is one contiguous stretch of the table
+  uint4 pre[Q8 ? TK_Q8_UNITS : 1];
+  int prv[Q8 ? TK_Q8_UNITS : 1];
+  if constexpr (Q8) {
+#pragma unroll
+    for (int i = 0; i < TK_Q8_UNITS; ++i) {
+      const int u = threadIdx.x + i * blockDim.x;
+      prv[i] = u < TR * p.q_nv ? ((u / p.q_nv) | ((u % p.q_nv) << 8)) : -1;
+    }
+    // operand chunks behind the last one a vector is converted into are never staged: zero them once, both buffers
+    for (int u = threadIdx.x; u < 2 * TR * p.nc; u += blockDim.x) {
+      const int r = u / p.nc, c = u - r * p.nc;
+      if (c >= CPV * p.q_nv)
+        *reinterpret_cast<uint4*>(Ts + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = make_uint4(0, 0, 0, 0);
+    }
+  }
+  auto q8_fetch = [&](int t) {
+    const int64_t t0 = lo + (int64_t)t * TR;
+#pragma unroll
+    for (int i = 0; i < (Q8 ? TK_Q8_UNITS : 0); ++i) {
+      pre[i] = make_uint4(0, 0, 0, 0);
+      const int r = prv[i] & 0xff, v = prv[i] >> 8;
+      if (prv[i] >= 0 && t0 + r < hi) pre[i] = *reinterpret_cast<const uint4*>(p.t_table + (t0 + r) * p.q_stride + 16 * v);
+    }
+  };
+  auto q8_store = [&](int buf) {
+    char* dst = Ts + (size_t)buf * TR * RB;
+    const int vs = p.E >> 4, ws = (p.E >> 2) & 3, vb = (p.E + 4) >> 4, wb = ((p.E + 4) >> 2) & 3;      // scale, bias: vector, word
+#pragma unroll
+    for (int i = 0; i < (Q8 ? TK_Q8_UNITS : 0); ++i) {
+      if (prv[i] < 0) continue;
+      const int r = prv[i] & 0xff, v = prv[i] >> 8, e0 = 16 * v;
+      const uint4 q4 = pre[i];
+      if (v == vs) tsc[buf * TR + r] = __uint_as_float(tk_word(q4, ws));
+      if (v == vb) tbi[buf * TR + r] = __uint_as_float(tk_word(q4, wb));
+      // E is a multiple of 4: a word is all codes or none
+      const uint32_t w[4] = {e0 < p.E ? q4.x : 0u, e0 + 4 < p.E ? q4.y : 0u, e0 + 8 < p.E ? q4.z : 0u, e0 + 12 < p.E ? q4.w : 0u};
+      char* drow = dst + (size_t)r * RB;
+      const int g = (r >> p.sw_shift) & p.sw_mask;
+#pragma unroll
+      for (int j = 0; j < CPV; ++j) {
+        const int cb = CPV * v + j;
+        if (cb >= p.nc) continue;
+        uint4 o;
+        if constexpr (std::is_same<T, float>::value) {
+          o = tk_codes_f32(w[j]);
+        } else {
+          const uint2 a = tk_codes_bf16(w[2 * j]), b = tk_codes_bf16(w[2 * j + 1]);
+          o = make_uint4(a.x, a.y, b.x, b.y);
+        }
+        *reinterpret_cast<uint4*>(drow + ((cb ^ g) << 4)) = o;
+      }
+    }
+  };
+  if (ntile > 0) {
+    if constexpr (Q8) {
+      q8_fetch(0);
+      q8_store(0);
+    } else {
+      load_tile(0, 0);
+    }
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (cosine) {
-    for (int r = threadIdx.x; r < NA; r += blockDim.x)
-      ainv[r] = 1.f / fmaxf(sqrtf(tk_row_sq<T>(As, r, p)), TK_COS_EPS);
-    if (ntile > 0) tile_norms(0);
+  if (cosine || Q8) {
+    for (int r = threadIdx.x; r < NA; r += blockDim.x) {
+      if (cosine) ainv[r] = 1.f / fmaxf(sqrtf(tk_row_sq<T>(As, r, p)), TK_COS_EPS);
+      if constexpr (Q8) sa[r] = tk_row_sum<T>(As, r, p);
+    }
+    if (cosine && ntile > 0) tile_norms(0);
     __syncthreads();
   }
 
@@ -209,7 +340,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   const int row0 = wave * AR + n;                         // + 16 at
   const int gsw = (n >> p.sw_shift) & p.sw_mask;          // g(r) depends on r & 15 only
   uint64_t tk[AT];
-  float tf[AT], ai[AT];
+  float tf[AT], ai[AT], sav[AT];
   bool rowok[AT];
 #pragma unroll
   for (int at = 0; at < AT; ++at) {
@@ -217,12 +348,16 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
     tf[at] = -INFINITY;
     rowok[at] = b0 + row0 + 16 * at < p.B;
     ai[at] = cosine ? ainv[row0 + 16 * at] : 1.f;
+    sav[at] = Q8 ? sa[row0 + 16 * at] : 0.f;
   }
   const int nks = p.nc >> 2;
 
   for (int t = 0; t < ntile; ++t) {
     const int buf = t & 1;
-    if (t + 1 < ntile) load_tile(t + 1, buf ^ 1);
+    if (t + 1 < ntile) {
+      if constexpr (Q8) q8_fetch(t + 1);
+      else load_tile(t + 1, buf ^ 1);
+    }
     const char* Tb = Ts + (size_t)buf * TR * RB;
     tk_f32x4 acc[AT][NT];
 #pragma unroll
@@ -239,6 +374,22 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
         const uint4 af = *reinterpret_cast<const uint4*>(Tb + (16 * nt + n) * RB + coff);
 #pragma unroll
         for (int at = 0; at < AT; ++at) acc[at][nt] = tk_mma<T>(af, bf[at], acc[at][nt]);
+      }
+    }
+    if constexpr (Q8) {
+      // the next tile: converted behind the issued MFMAs into the buffer the last tile left (the barrier at its end)
+      if (t + 1 < ntile) q8_store(buf ^ 1);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const float4 sc = *reinterpret_cast<const float4*>(tsc + buf * TR + 16 * nt + 4 * q);
+        const float4 bi = *reinterpret_cast<const float4*>(tbi + buf * TR + 16 * nt + 4 * q);
+#pragma unroll
+        for (int at = 0; at < AT; ++at) {
+          acc[at][nt][0] = acc[at][nt][0] * sc.x + sav[at] * bi.x;
+          acc[at][nt][1] = acc[at][nt][1] * sc.y + sav[at] * bi.y;
+          acc[at][nt][2] = acc[at][nt][2] * sc.z + sav[at] * bi.z;
+          acc[at][nt][3] = acc[at][nt][3] * sc.w + sav[at] * bi.w;
+        }
       }
     }
     if (cosine) {
@@ -402,81 +553,76 @@ static int tk_splits(int64_t B, int64_t Vt) {
 struct TopkShape {
   int AR, TR, NW;
 };
-static size_t tk_lds_bytes(const TopkShape& s, int RB, int P) {
+static size_t tk_lds_bytes(const TopkShape& s, int RB, int P, bool q8) {
   const size_t NA = (size_t)s.NW * s.AR;
-  return NA * RB + (size_t)2 * s.TR * RB + NA * P * 8 + NA * 16 + (size_t)2 * s.TR * 4;
+  // Q8: the tiles' scales and biases, the anchors' sums
+  return NA * RB + (size_t)2 * s.TR * RB + NA * P * 8 + NA * 16 + (size_t)2 * s.TR * 4 +
+         (q8 ? (size_t)2 * s.TR * 8 + NA * 4 : 0);
 }
 
-template <typename T>
-static int topk_launch(TopkArgs& p, int RB, hipStream_t s) {
+template <typename T, bool Q8>
+static int topk_launch(const char* op, TopkArgs& p, int RB, hipStream_t s) {
   // the first arrangement whose anchors, two target tiles and candidate buffers fit the 160 KB of LDS
   static const TopkShape shapes[] = {{32, 128, 4}, {16, 128, 4}, {16, 64, 4}, {16, 64, 2}, {16, 32, 2}, {16, 32, 1}};
   const TopkShape* sh = nullptr;
   for (const TopkShape& c : shapes)
-    if (tk_lds_bytes(c, RB, p.P) <= TK_MAX_LDS) {
+    if (tk_lds_bytes(c, RB, p.P, Q8) <= TK_MAX_LDS) {
       sh = &c;
       break;
     }
-  TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "topk_scores: no arrangement fits LDS (row %d bytes, k %d)", RB, p.k);
-  const size_t lds = tk_lds_bytes(*sh, RB, p.P);
+  TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS (row %d bytes, k %d)", op, RB, p.k);
+  TRS_REQUIRE(!Q8 || (sh->TR * p.q_nv + 64 * sh->NW - 1) / (64 * sh->NW) <= TK_Q8_UNITS, TRS_ESHAPE,
+              "%s: a tile of %d rows x %d vectors exceeds %d per thread", op, sh->TR, p.q_nv, TK_Q8_UNITS);
+  const size_t lds = tk_lds_bytes(*sh, RB, p.P, Q8);
   const int NA = sh->NW * sh->AR;
   const dim3 grid((unsigned)((p.B + NA - 1) / NA), (unsigned)p.S);
   auto go = [&](auto kern) -> int {
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TK_MAX_LDS) != hipSuccess) {
       (void)hipGetLastError();
-      return fail(TRS_ELAUNCH,"topk_scores: hipFuncSetAttribute(%zu bytes of LDS) failed", lds);
+      return fail(TRS_ELAUNCH, "%s: hipFuncSetAttribute(%zu bytes of LDS) failed", op, lds);
     }
     hipLaunchKernelGGL(kern, grid, dim3(64 * sh->NW), lds, s, p);
     return TRS_OK;
   };
   int rc;
-  if (sh->AR == 32) rc = go(topk_scores_kernel<T, 32, 128>);
-  else if (sh->TR == 128) rc = go(topk_scores_kernel<T, 16, 128>);
-  else if (sh->TR == 64) rc = go(topk_scores_kernel<T, 16, 64>);
-  else rc = go(topk_scores_kernel<T, 16, 32>);
+  if (sh->AR == 32) rc = go(topk_scores_kernel<T, 32, 128, Q8>);
+  else if (sh->TR == 128) rc = go(topk_scores_kernel<T, 16, 128, Q8>);
+  else if (sh->TR == 64) rc = go(topk_scores_kernel<T, 16, 64, Q8>);
+  else rc = go(topk_scores_kernel<T, 16, 32, Q8>);
   if (rc != TRS_OK) return rc;
   if (p.S > 1)
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)p.B), dim3(64), (size_t)p.P * 8, s, p.ws, p.S, p.k, p.P, p.out_val,
                        p.out_idx);
-  return check_launch("topk_scores");
+  return check_launch(op);
 }
 
-}  // namespace trs
-
-using namespace trs;
-
-extern "C" size_t trs_topk_scores_workspace_bytes(int64_t B, int64_t Vt, int32_t k) {
-  if (B <= 0 || Vt <= 0 || k < 1 || k > TK_MAX_K) return 0;
-  const int S = tk_splits(B, Vt);
-  return S > 1 ? (size_t)B * S * k * sizeof(uint64_t) : 0;
-}
-
-extern "C" int trs_topk_scores(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
-                               int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
-                               int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k, const void* exclude,
-                               int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx, void* workspace,
-                               size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
-  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "topk_scores: dtype %d", dtype);
-  TRS_REQUIRE(sim == TK_DOT || sim == TK_COS, TRS_EINVAL, "topk_scores: sim %d (0 = inner product, 1 = cosine)", sim);
-  TRS_REQUIRE(anchor_idx == nullptr || idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EINVAL,
-              "topk_scores: idx dtype %d", idx_dtype);
+// both entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns
+static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t Va, const void* anchor_idx,
+                      int32_t idx_dtype, int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
+                      int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k, const void* exclude,
+                      int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx, void* workspace, size_t ws_bytes,
+                      int32_t* err_flag, trs_stream_t stream) {
+  TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "%s: dtype %d", op, dtype);
+  TRS_REQUIRE(sim == TK_DOT || sim == TK_COS, TRS_EINVAL, "%s: sim %d (0 = inner product, 1 = cosine)", op, sim);
+  TRS_REQUIRE(anchor_idx == nullptr || idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EINVAL, "%s: idx dtype %d", op,
+              idx_dtype);
   TRS_REQUIRE(exclude == nullptr || ((excl_dtype == TRS_I64 || excl_dtype == TRS_I32) && X >= 1), TRS_EINVAL,
-              "topk_scores: exclude dtype %d, X = %d (X >= 1)", excl_dtype, X);
+              "%s: exclude dtype %d, X = %d (X >= 1)", op, excl_dtype, X);
   const int64_t Vt = target_hi - target_lo;
   TRS_REQUIRE(Va > 0 && B >= 0 && target_lo >= 0 && Vt > 0 && Vt <= INT32_MAX, TRS_EINVAL,
-              "topk_scores: bad size Va=%lld B=%lld targets [%lld, %lld)", (long long)Va, (long long)B,
-              (long long)target_lo, (long long)target_hi);
-  TRS_REQUIRE(k >= 1 && k <= TK_MAX_K && k <= Vt, TRS_EINVAL, "topk_scores: k = %d (1 .. %d, at most the %lld targets)", k,
+              "%s: bad size Va=%lld B=%lld targets [%lld, %lld)", op, (long long)Va, (long long)B, (long long)target_lo,
+              (long long)target_hi);
+  TRS_REQUIRE(k >= 1 && k <= TK_MAX_K && k <= Vt, TRS_EINVAL, "%s: k = %d (1 .. %d, at most the %lld targets)", op, k,
               TK_MAX_K, (long long)Vt);
   const int row_bytes = E * dtype_size(dtype);
   TRS_REQUIRE(E > 0 && E <= TK_MAX_E && row_bytes % 16 == 0, TRS_ESHAPE,
-              "topk_scores: E = %d (rows of whole 16-byte vectors, E <= %d)", E, TK_MAX_E);
+              "%s: E = %d (rows of whole 16-byte vectors, E <= %d)", op, E, TK_MAX_E);
   if (B == 0) return TRS_OK;
-  TRS_REQUIRE(anchor_table && target_table && out_val && out_idx, TRS_EINVAL, "topk_scores: NULL pointer");
-  TRS_REQUIRE(aligned16(anchor_table) && aligned16(target_table), TRS_EALIGN, "topk_scores: tables must be 16-byte aligned");
+  TRS_REQUIRE(anchor_table && target_table && out_val && out_idx, TRS_EINVAL, "%s: NULL pointer", op);
+  TRS_REQUIRE(aligned16(anchor_table) && aligned16(target_table), TRS_EALIGN, "%s: tables must be 16-byte aligned", op);
   const size_t need = trs_topk_scores_workspace_bytes(B, Vt, k);
-  TRS_REQUIRE(need == 0 || (workspace != nullptr && ws_bytes >= need), TRS_EWORKSPACE, "topk_scores: workspace %zu < %zu",
+  TRS_REQUIRE(need == 0 || (workspace != nullptr && ws_bytes >= need), TRS_EWORKSPACE, "%s: workspace %zu < %zu", op,
               ws_bytes, need);
   TopkArgs p;
   p.a_table = static_cast<const char*>(anchor_table);
@@ -508,8 +654,41 @@ extern "C" int trs_topk_scores(const void* anchor_table, int64_t Va, const void*
   p.sim = sim;
   p.idx64 = idx_dtype == TRS_I64;
   p.excl64 = excl_dtype == TRS_I64;
-  p.dma = p.nce == p.nc;
+  p.dma = !q8 && p.nce == p.nc;
+  p.E = E;
+  p.q_stride = (int)q8_stride(E);
+  p.q_nv = p.q_stride / 16;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TRS_F32) return topk_launch<float>(p, p.nc * 16, s);
-  return topk_launch<bf16_t>(p, p.nc * 16, s);
+  if (q8) return dtype == TRS_F32 ? topk_launch<float, true>(op, p, p.nc * 16, s) : topk_launch<bf16_t, true>(op, p, p.nc * 16, s);
+  return dtype == TRS_F32 ? topk_launch<float, false>(op, p, p.nc * 16, s) : topk_launch<bf16_t, false>(op, p, p.nc * 16, s);
+}
+
+}  // namespace trs
+
+using namespace trs;
+
+extern "C" size_t trs_topk_scores_workspace_bytes(int64_t B, int64_t Vt, int32_t k) {
+  if (B <= 0 || Vt <= 0 || k < 1 || k > TK_MAX_K) return 0;
+  const int S = tk_splits(B, Vt);
+  return S > 1 ? (size_t)B * S * k * sizeof(uint64_t) : 0;
+}
+
+extern "C" int trs_topk_scores(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                               int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
+                               int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k, const void* exclude,
+                               int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx, void* workspace,
+                               size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  return topk_entry("topk_scores", false, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
+                    target_hi, E, dtype, sim, k, exclude, excl_dtype, X, out_val, out_idx, workspace, ws_bytes, err_flag,
+                    stream);
+}
+
+extern "C" int trs_topk_scores_q8(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                                  int64_t anchor_offset, int64_t B, const void* target_q, int64_t target_lo,
+                                  int64_t target_hi, int32_t E, int32_t anchor_dtype, int32_t sim, int32_t k,
+                                  const void* exclude, int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx,
+                                  void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  return topk_entry("topk_scores_q8", true, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
+                    target_hi, E, anchor_dtype, sim, k, exclude, excl_dtype, X, out_val, out_idx, workspace, ws_bytes,
+                    err_flag, stream);
 }

@@ -4210,23 +4210,29 @@ def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor],
     if E < 1 or E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
         raise NotImplementedError(f"topk_scores: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} "
                                   f"of {aw.dtype}")
+    return _topk_run("topk_scores", "trs_topk_scores", aw, anchor_idx, anchor_offset, tw, "target_weight", target_lo,
+                     target_hi, E, code, k, exclude)
+
+
+def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, k, exclude):
+    """what topk_scores and topk_scores_q8 share behind their table checks: range, k, exclusion list, outputs, the call"""
     lo = int(target_lo)
     hi = tw.shape[0] if target_hi is None else int(target_hi)
     if not 0 <= lo < hi <= tw.shape[0]:
-        raise ValueError(f"topk_scores: target range [{lo}, {hi}) is not inside the {tw.shape[0]} target rows")
+        raise ValueError(f"{op}: target range [{lo}, {hi}) is not inside the {tw.shape[0]} target rows")
     k = int(k)
     if not 1 <= k <= TOPK_MAX_K or k > hi - lo:
-        raise ValueError(f"topk_scores: k must be in 1 .. {TOPK_MAX_K} and at most the {hi - lo} targets, got {k}")
+        raise ValueError(f"{op}: k must be in 1 .. {TOPK_MAX_K} and at most the {hi - lo} targets, got {k}")
     a_idx = None if anchor_idx is None else _as_index(anchor_idx).reshape(-1)
     B = aw.shape[0] if a_idx is None else a_idx.shape[0]
     ex = None
     if exclude is not None:
         ex = _as_index(exclude)
         if ex.dim() != 2 or ex.shape[0] != B or ex.shape[1] < 1:
-            raise ValueError(f"topk_scores: exclude ({B}, X >= 1) expected, got {tuple(ex.shape)}")
-    for name, t in (("anchor_weight", aw), ("target_weight", tw)):
+            raise ValueError(f"{op}: exclude ({B}, X >= 1) expected, got {tuple(ex.shape)}")
+    for name, t in (("anchor_weight", aw), (tname, tw)):
         if not t.is_contiguous():
-            raise ValueError(f"topk_scores: {name} must be contiguous, got strides {tuple(t.stride())}")
+            raise ValueError(f"{op}: {name} must be contiguous, got strides {tuple(t.stride())}")
     dev = require_device(aw, a_idx, tw, ex)
     values = torch.empty(B, k, dtype=torch.float32, device=dev)
     ids = torch.empty(B, k, dtype=torch.int64, device=dev)
@@ -4235,12 +4241,46 @@ def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor],
     ws_bytes = size_query("trs_topk_scores_workspace_bytes", B, hi - lo, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     flag = _ErrFlag(dev)
-    call("trs_topk_scores", ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
+    call(entry, ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
          int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, k, ptr(ex),
          index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(values), ptr(ids), ptr(ws),
          ws_bytes, ptr(flag.t), stream_ptr())
-    flag.check("topk_scores")
+    flag.check(op)
     return values, ids
+
+
+def topk_scores_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_qweight: torch.Tensor, E: int,
+                   k: int, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None, sim="dot",
+                   exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``topk_scores`` over a row-wise int8 (Q8) target table, in one HIP pass that reads the Q8 rows themselves
+    (csrc/topk.hip): no float copy of the table, no (B, Vt) block.  ``target_qweight``: the contiguous uint8 (V,
+    q8_row_bytes(E)) tensor of ``quant.quantize_rows``; the anchors stay float (bf16 or fp32), rows of ``anchor_weight``
+    through ``anchor_idx`` + ``anchor_offset`` or the (B, E) query matrix itself (``anchor_idx=None``).  The codes enter
+    the matrix cores exactly and a score is ``d * scale + sa * bias`` with ``d = sum a[e] c[e]``, ``sa = sum a[e]`` in fp32;
+    cosine divides by the anchor's norm and the norm of the dequantized row.  Everything else is ``topk_scores``' contract:
+    ``values (B, k)`` fp32 and ``ids (B, k)`` int64 relative to ``target_lo``, by score descending and id ascending among
+    equal scores, -inf / -1 in slots no target is left for, ``exclude`` (B, X), 1 <= k <= 128, rows of whole 16-byte
+    anchor vectors, E <= 256, no gradient, no host read-back; an anchor id outside its table scores 0 everywhere and
+    raises the index flag."""
+    code = _sim_code(sim)
+    aw = anchor_weight.detach()
+    tq = target_qweight.detach()
+    if not isinstance(E, int) or E <= 0:
+        raise ValueError(f"topk_scores_q8: E must be a positive int, got {E!r}")
+    if tq.dtype != torch.uint8:
+        raise TypeError(f"topk_scores_q8: target_qweight must be uint8 Q8 rows, got {tq.dtype}")
+    S = (E + 8 + 15) // 16 * 16
+    if tq.dim() != 2 or tq.shape[1] != S:
+        raise ValueError(f"topk_scores_q8: target_qweight must be (V, {S}) for E={E}, got shape {tuple(tq.shape)}")
+    if aw.dim() != 2 or aw.shape[1] != E:
+        raise ValueError(f"topk_scores_q8: anchors of width E={E} expected, got shape {tuple(aw.shape)}")
+    if aw.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"topk_scores_q8: bf16 or fp32 anchors expected, got {aw.dtype}")
+    if E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
+        raise NotImplementedError(f"topk_scores_q8: anchor rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, "
+                                  f"got E = {E} of {aw.dtype}")
+    return _topk_run("topk_scores_q8", "trs_topk_scores_q8", aw, anchor_idx, anchor_offset, tq, "target_qweight",
+                     target_lo, target_hi, E, code, k, exclude)
 
 
 _row_ids = {}       # (device, B) -> (2 b, 2 b + 1): the rows of a (B, 2, E) block seen as a (2 B, E) table

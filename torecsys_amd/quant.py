@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import functional as F_
 from ._abi import call, ptr, require_device, size_query, stream_ptr, value_dtype_code
-from .fused import EmbeddingFM
+from .fused import EmbeddingFM, EmbeddingPairScorer
 from .inputs import BaseInput, MultiIndicesEmbedding, RaggedListIndicesEmbedding, _strip, field_offsets
 
 
@@ -154,6 +154,65 @@ class QuantizedEmbeddingFM(nn.Module):
             emb.names = ('B', 'N', 'E',)
         fm.names = ('B', 'O',)
         return emb, fm, first
+
+
+class QuantizedEmbeddingPairScorer(nn.Module):
+    """``fused.EmbeddingPairScorer`` for serving on Q8 tables.  Buffers (persistent): ``qweight``, the target table or the
+    one shared table, and ``anchor_qweight``, the anchor table where it is a separate one.  ``topk`` is the retrieval
+    kernel over the Q8 rows (functional.topk_scores_q8); the anchors are dequantized per batch into ``out_dtype``."""
+
+    def __init__(self, embed_size: int, anchor_size: int, target_size: Optional[int] = None, similarity: str = 'dot',
+                 anchor_offset: int = 0, target_offset: int = 0, out_dtype: torch.dtype = torch.float32):
+        super().__init__()
+        if similarity not in F_.PAIR_SIMS:
+            raise ValueError(f"similarity must be one of {sorted(F_.PAIR_SIMS)}, got {similarity!r}")
+        self.register_buffer('qweight', _empty_qweight(anchor_size if target_size is None else target_size, embed_size))
+        self.register_buffer('anchor_qweight', None if target_size is None else _empty_qweight(anchor_size, embed_size))
+        self.embed_size = embed_size
+        self.similarity = similarity
+        self.anchor_offset, self.target_offset = int(anchor_offset), int(target_offset)
+        self.out_dtype = _out_dtype(out_dtype)
+
+    @classmethod
+    def from_float(cls, module: EmbeddingPairScorer, out_dtype: Optional[torch.dtype] = None):
+        if not isinstance(module, EmbeddingPairScorer):
+            raise TypeError(f"from_float needs a fused.EmbeddingPairScorer, got {type(module).__name__}")
+        aw = module.anchor.weight
+        tw = None if module.target is None else module.target.weight
+        q = cls(aw.shape[1], aw.shape[0], None if tw is None else tw.shape[0], module.similarity, module.anchor_offset,
+                module.target_offset, _out_dtype(out_dtype, aw)).to(aw.device)
+        q.qweight.copy_(quantize_rows(aw if tw is None else tw))
+        if tw is not None:
+            q.anchor_qweight.copy_(quantize_rows(aw))
+        return q
+
+    def set_fused_optimizer(self, opt):
+        _no_optimizer(opt)
+        return self
+
+    def _anchors(self, anchor_idx: torch.Tensor) -> torch.Tensor:
+        """(B, E) of ``out_dtype``: the anchors' dequantized rows"""
+        aq = self.qweight if self.anchor_qweight is None else self.anchor_qweight
+        idx = _strip(anchor_idx).reshape(-1, 1) + self.anchor_offset
+        return F_.gather_rows_q8(aq, self.embed_size, idx, None, self.out_dtype).view(-1, self.embed_size)
+
+    def topk(self, anchor_idx: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None):
+        """``EmbeddingPairScorer.topk`` on the Q8 target rows: ``(values (B, k) fp32, ids (B, k) int64)``.  A shared table
+        is searched from ``target_offset`` to its end."""
+        return F_.topk_scores_q8(self._anchors(anchor_idx), None, self.qweight, self.embed_size, k,
+                                 target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
+
+    def forward(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor) -> torch.Tensor:
+        """(B, 1 + K) scores of given pairs.  Not a kernel: a plain composition, both sides dequantized by
+        ``gather_rows_q8`` and a batched product (or cosine, eps 1e-8 on each norm) in ATen, fp32."""
+        t_idx = _strip(target_idx)
+        t_idx = (t_idx.unsqueeze(1) if t_idx.dim() == 1 else t_idx) + self.target_offset
+        a = self._anchors(anchor_idx).float().unsqueeze(1)
+        t = F_.gather_rows_q8(self.qweight, self.embed_size, t_idx, None, self.out_dtype).float()
+        s = (a * t).sum(-1)
+        if self.similarity == 'cosine':
+            s = s / (a.norm(dim=-1).clamp_min(1e-8) * t.norm(dim=-1).clamp_min(1e-8))
+        return s
 
 
 class QuantizedRaggedListIndicesEmbedding(_QuantizedInput):
