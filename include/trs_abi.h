@@ -1405,6 +1405,33 @@ int trs_topk_scores_q8(const void* anchor_table, int64_t Va, const void* anchor_
                        int32_t X, float* out_val, int64_t* out_idx, void* workspace, size_t ws_bytes, int32_t* err_flag,
                        trs_stream_t stream);
 
+/* ---- softmax cross-entropy against a whole target table (csrc/softmax_loss.hip; not in the reference) -----------------
+ * anchors (B, E) and targets (Vt, E), contiguous rows of one value dtype; labels (B) of label_dtype (TRS_I64 | TRS_I32):
+ *   z[b, j] = scale * sum_e A[b, e] T[j, e]      (products of table-dtype operands, fp32 accumulation on the matrix cores)
+ *   lse[b]  = logsumexp_j z[b, j]                 loss[b] = lse[b] - z[b, y_b]                     both (B) fp32
+ *   dA[b]   = scale * sum_j w[b, j] T[j]          dT[j] = scale * sum_b w[b, j] A[b]      w = g_b (exp(z - lse_b) - [j == y_b])
+ * g_loss (B) fp32 is the gradient of the per-sample loss.  A sample whose label is outside [0, Vt) is ignored: loss 0 (lse
+ * is still written), no gradient; where that label is not ignore_index (a negative number) the forward also raises
+ * *err_flag.  Nothing is read out of range.  In-batch softmax: targets = the B positive rows, labels = 0 .. B-1.
+ * No (B, Vt) block is written by either direction: the forward keeps a running (max, sum of exponentials) next to the
+ * accumulators, the backward recomputes the scores tile by tile from lse.  w is the operand of a second MFMA (fp32 as
+ * it is, bf16 as the pair hi + lo), every gradient element is rounded once at the end; sums have one fixed order and no atomics, so the
+ * results are bit-identical from run to run.  d_anchors (B, E) / d_targets (Vt, E) of the value dtype; either may be NULL
+ * and its kernel is then not launched.  Each direction cuts its streamed rows into S ranges, S a pure function of (B, Vt);
+ * for S > 1 partial results pass through the workspace (trs_softmax_loss_workspace_bytes: backward = 0 the forward's
+ * need, 1 the backward's with both gradients; 0 where S = 1) and a second launch folds them in range order.
+ * No host read-back, no allocation: capturable.
+ * 1 <= Vt < 2^31, B < 2^31; rows of whole 16-byte vectors, E <= 256 (TRS_ESHAPE); 16-byte aligned operands, gradients and
+ * workspace (TRS_EALIGN).  B == 0: TRS_OK, the forward touches nothing, the backward zeroes d_targets.  Errors, all
+ * before any launch: NULL pointer, label dtype, bad size TRS_EINVAL; value dtype TRS_EDTYPE; workspace TRS_EWORKSPACE.  */
+size_t trs_softmax_loss_workspace_bytes(int64_t B, int64_t Vt, int32_t E, int32_t backward);
+int trs_softmax_loss_fwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E, int32_t dtype,
+                         const void* labels, int32_t label_dtype, int64_t ignore_index, float scale, float* loss,
+                         float* lse, void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E, int32_t dtype,
+                         const void* labels, int32_t label_dtype, float scale, const float* lse, const float* g_loss,
+                         void* d_anchors, void* d_targets, void* workspace, size_t ws_bytes, trs_stream_t stream);
+
 /* ---- ranking losses over (positive, negatives) scores (csrc/rank.hip; losses/ltr/functional.py) ---------------------
  * pos: one value per sample at pos[b * pos_stride]; neg: K values per sample at neg[b * neg_stride + k] (columns 0 and
  * 1 .. K of one (B, 1+K) score matrix: pos = S, neg = S + 1, both strides 1 + K); dtype TRS_F32 | TRS_BF16; mask (B) one

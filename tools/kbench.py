@@ -40,6 +40,8 @@ Adam through gather_rows and embed_fm, uniform and Zipf indices, on a bf16 table
 on the same ids (own inputs, see bench_q8).
 --what topk --q8 [--k 100] [--sim dot|cosine] [--budget 4]: top-k retrieval over a 1 M-row Q8 table: the float kernel on a
 bf16 copy held in memory, dequantize + float kernel per call, and the Q8 kernel; times and peak memory
+--what softmax [--budget 4]: full-catalogue softmax loss, forward and forward + backward, against a chunked ATen composition
+that recomputes each chunk's logits in its backward; 1 M rows and in batch, bf16 and fp32 (own inputs, see bench_softmax).
 --what topk [--k 100] [--sim dot|cosine] [--budget 4]: top-k retrieval over a 1 M-row table against the chunked ATen
 composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk)."""
 import argparse
@@ -1454,6 +1456,95 @@ def bench_topk(a):
         del tw, aw, up
 
 
+def bench_softmax(a):
+    """functional.softmax_scores_loss (csrc/softmax_loss.hip) against the only ATen composition that runs at these shapes:
+    one autograd.Function over target chunks sized so that a chunk's (B, chunk) fp32 logits stay within 1 GiB -- forward:
+    ``matmul``, ``logsumexp`` per chunk folded by ``logaddexp``, the positive's score by ``gather``; backward: the chunk's
+    logits recomputed, ``exp(z - lse)`` minus the one-hot, two ``matmul``s per chunk.  B in {4 096, 65 536} against a
+    1 M-row table and in batch (Vt = B), E = 64, bf16 and fp32, forward and forward + backward (both gradients).  The two
+    take turns launch by launch after one warm-up each; a shape stops after 10 launches of each or once --budget seconds
+    of timed work have passed, with at least 3.  FLOP/s count 2 B V E per matrix product: 1 forward, 5 forward + backward
+    (scores, and per gradient the scores again and the contraction)."""
+    dev = torch.device("cuda:0")
+    E = a.E
+    g = torch.Generator(device=dev).manual_seed(78)
+
+    class Chunked(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q, t, y):
+            B, V = q.shape[0], t.shape[0]
+            ctx.chunk = chunk = max(4096, min(V, (1 << 28) // B))
+            lse = torch.full((B,), float("-inf"), device=q.device)
+            pos = torch.zeros(B, device=q.device)
+            for lo in range(0, V, chunk):
+                z = (q @ t[lo:lo + chunk].T).float()
+                lse = torch.logaddexp(lse, torch.logsumexp(z, dim=1))
+                here = (y >= lo) & (y < lo + z.shape[1])
+                pos = torch.where(here, z.gather(1, (y - lo).clamp(0, z.shape[1] - 1).unsqueeze(1)).squeeze(1), pos)
+            ctx.save_for_backward(q, t, y, lse)
+            return lse - pos
+
+        @staticmethod
+        def backward(ctx, gl):
+            q, t, y, lse = ctx.saved_tensors
+            dq, dt = torch.zeros_like(q, dtype=torch.float32), torch.empty_like(t)
+            for lo in range(0, t.shape[0], ctx.chunk):
+                tc = t[lo:lo + ctx.chunk]
+                w = torch.exp((q @ tc.T).float() - lse[:, None])
+                here = ((y >= lo) & (y < lo + tc.shape[0])).nonzero().squeeze(1)
+                w[here, y[here] - lo] -= 1.0
+                w = (w * gl[:, None]).to(q.dtype)
+                dq += (w @ tc).float()
+                dt[lo:lo + ctx.chunk] = w.T @ q
+            return dq.to(q.dtype), dt, None
+
+    def race(ours, aten):
+        for f in (ours, aten):
+            f()
+        torch.cuda.synchronize()
+        ts, spent = {"hip": [], "aten": []}, 0.0
+        while len(ts["hip"]) < 3 or (len(ts["hip"]) < 10 and spent < a.budget):
+            for name, f in (("hip", ours), ("aten", aten)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1) * 1e-3)
+                spent += ts[name][-1]
+        return {n: sorted(v) for n, v in ts.items()}
+
+    print(f"softmax: E = {E}")
+    for dt in (torch.bfloat16, torch.float32):
+        for B, V in ((4096, a.V), (65536, a.V), (4096, 4096), (65536, 65536)):
+            q = (0.3 * torch.randn(B, E, generator=g, device=dev)).to(dt).requires_grad_()
+            t = (0.3 * torch.randn(V, E, generator=g, device=dev)).to(dt).requires_grad_()
+            y = torch.arange(B, device=dev) if V == B else torch.randint(0, V, (B,), generator=g, device=dev)
+            gl = torch.rand(B, generator=g, device=dev)
+            tag = f"{str(dt)[6:]} B={B} Vt={V}"
+
+            def fwd_bwd(f):
+                def run():
+                    q.grad = t.grad = None
+                    f(q, t, y).backward(gl)
+                return run
+
+            hip, aten = (lambda q, t, y: F_.softmax_scores_loss(q, t, y)), Chunked.apply
+            with torch.no_grad():
+                diff = float((hip(q, t, y) - aten(q, t, y)).abs().max())
+            for what, fs, mm in (("fwd", (lambda: hip(q.detach(), t.detach(), y), lambda: aten(q.detach(), t.detach(), y)), 1),
+                                 ("fwd+bwd", (fwd_bwd(hip), fwd_bwd(aten)), 5)):
+                ts = race(*fs)
+                med = {n: v[len(v) // 2] for n, v in ts.items()}
+                for n in ("hip", "aten"):
+                    print(f"{tag:30s} {what:8s} {n:5s} med {med[n] * 1e3:10.3f} ms  spread {ts[n][0] * 1e3:10.3f} .. "
+                          f"{ts[n][-1] * 1e3:10.3f} ms ({len(ts[n])} launches)  {2.0 * mm * B * V * E / med[n] / 1e12:7.1f} TFLOP/s",
+                          flush=True)
+                print(f"{tag:30s} {what:8s} aten / hip = {med['aten'] / med['hip']:.2f}", flush=True)
+            print(f"{tag:30s} max |loss difference| = {diff:.3e}", flush=True)
+            del q, t
+
+
 def bench_topk_q8(a):
     """functional.topk_scores_q8 over a 1 M-row Q8 table (E = 64, bf16 anchors as a (B, E) query matrix) against the two
     routes that exist without it: (a) ``topk_scores`` on the bf16 table held in memory -- the float kernel, the speed
@@ -1623,6 +1714,8 @@ def main():
     a = ap.parse_args()
     if a.what == "topk":         # own inputs: not part of "all"
         return bench_topk_q8(a) if a.q8 else bench_topk(a)
+    if a.what == "softmax":      # own inputs: not part of "all"
+        return bench_softmax(a)
     if a.what == "q8":           # own inputs: not part of "all"
         return bench_q8(a)
     if a.what == "ragged":       # own inputs (ids + offsets, and the same bags padded): not part of "all"

@@ -4283,6 +4283,95 @@ def topk_scores_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tenso
                      target_lo, target_hi, E, code, k, exclude)
 
 
+class _SoftmaxScoresLoss(Function):
+    """per-sample softmax cross-entropy against every target row; saves the operands and lse (B), recomputes the scores"""
+
+    @staticmethod
+    def forward(ctx, a, t, y, scale, ignore_index):
+        B, E = a.shape
+        dev = a.device
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        if B > 0:
+            ws_bytes = size_query("trs_softmax_loss_workspace_bytes", B, t.shape[0], E, 0)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+            flag = _ErrFlag(dev)
+            call("trs_softmax_loss_fwd", ptr(a), B, ptr(t), t.shape[0], E, value_dtype_code(a), ptr(y), index_dtype_code(y),
+                 ignore_index, scale, ptr(loss), ptr(lse), ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+            flag.check("softmax_scores_loss")
+        ctx.save_for_backward(a, t, y, lse)
+        ctx.scale = scale
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, t, y, lse = ctx.saved_tensors
+        need_a, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_t):
+            return None, None, None, None, None
+        _adopt_grads(g)
+        B, E = a.shape
+        g = g.to(torch.float32).contiguous()
+        da = torch.empty_like(a) if need_a else None
+        dt = torch.empty_like(t) if need_t else None
+        ws_bytes = size_query("trs_softmax_loss_workspace_bytes", B, t.shape[0], E, 1)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+        call("trs_softmax_loss_bwd", ptr(a), B, ptr(t), t.shape[0], E, value_dtype_code(a), ptr(y), index_dtype_code(y),
+             ctx.scale, ptr(lse), ptr(g), ptr(da), ptr(dt), ptr(ws), ws_bytes, stream_ptr())
+        return da, dt, None, None, None
+
+
+def softmax_scores_loss(anchors: torch.Tensor, targets: torch.Tensor, labels: torch.Tensor, scale: float = 1.0,
+                        ignore_index: int = -1) -> torch.Tensor:
+    """Softmax cross-entropy of every anchor against EVERY row of ``targets``, per sample, in HIP passes that never form the
+    (B, Vt) logits (csrc/softmax_loss.hip): ``loss[b] = logsumexp_j z[b, j] - z[b, labels[b]]`` with ``z = scale *
+    anchors @ targets.T`` (table-dtype products, fp32 accumulation on the matrix cores) -> (B,) fp32.  ``anchors`` (B, E)
+    and ``targets`` (Vt, E): bf16 or fp32 of one dtype, contiguous rows of whole 16-byte vectors, E <= 256 (the contract
+    of ``topk_scores``); a row range of a table is such a ``targets``.  ``labels`` (B,) int32 / int64.  A sample whose
+    label is ``ignore_index`` (negative) has loss 0 and no gradient; any other label outside [0, Vt) is treated the same
+    way and raises the index flag.  Gradients go to whichever of ``anchors`` / ``targets`` requires one (the other kernel
+    is not launched), recomputing the scores from the saved lse (B); they are bit-identical from run to run.  In-batch
+    softmax: pass the looked-up positive rows as ``targets`` with ``labels = arange(B)``.  Inner product only: no cosine,
+    no per-item bias / logQ correction, no label smoothing, no Q8 targets.  No host read-back: capturable."""
+    a, t = anchors, targets
+    if a.dim() != 2 or t.dim() != 2 or a.shape[1] != t.shape[1]:
+        raise ValueError(f"softmax_scores_loss: anchors (B, E) and targets (Vt, E) of one width expected, got "
+                         f"{tuple(a.shape)} and {tuple(t.shape)}")
+    if a.dtype not in (torch.float32, torch.bfloat16) or t.dtype != a.dtype:
+        raise TypeError(f"softmax_scores_loss: bf16 or fp32 operands of one dtype expected, got {a.dtype} and {t.dtype}")
+    E = a.shape[1]
+    if E < 1 or E > TOPK_MAX_E or (E * a.element_size()) % 16 != 0:
+        raise NotImplementedError(f"softmax_scores_loss: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got "
+                                  f"E = {E} of {a.dtype}")
+    if t.shape[0] < 1:
+        raise ValueError("softmax_scores_loss: at least one target row is needed")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"softmax_scores_loss: labels must be int32 or int64, got {labels.dtype}")
+    if labels.dim() != 1 or labels.shape[0] != a.shape[0]:
+        raise ValueError(f"softmax_scores_loss: labels ({a.shape[0]},) expected, got {tuple(labels.shape)}")
+    if int(ignore_index) >= 0:
+        raise ValueError(f"softmax_scores_loss: ignore_index must be negative, got {ignore_index}")
+    for name, x in (("anchors", a), ("targets", t)):
+        if not x.is_contiguous():
+            raise ValueError(f"softmax_scores_loss: {name} must be contiguous, got strides {tuple(x.stride())}")
+    require_device(a, t, labels)
+    return _SoftmaxScoresLoss.apply(a, t, labels.contiguous(), float(scale), int(ignore_index))
+
+
+def reduce_sample_losses(loss: torch.Tensor, labels: torch.Tensor, num_targets: int, reduction: str) -> torch.Tensor:
+    """'none' | 'sum' | 'mean' of the (B,) losses of ``softmax_scores_loss``; the mean is over the samples whose label
+    names a target, counted on the device (no sample: 0)."""
+    if reduction == 'none':
+        return loss
+    if reduction == 'sum':
+        return loss.sum()
+    if reduction != 'mean':
+        raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+    kept = ((labels >= 0) & (labels < num_targets)).sum()
+    return loss.sum() / kept.clamp_min(1).to(torch.float32)
+
+
 _row_ids = {}       # (device, B) -> (2 b, 2 b + 1): the rows of a (B, 2, E) block seen as a (2 B, E) table
 
 

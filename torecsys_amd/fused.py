@@ -140,6 +140,31 @@ class EmbeddingPairScorer(nn.Module):
         return F_.topk_scores(self.anchor.weight, anchor_idx, tw, k, anchor_offset=self.anchor_offset,
                               target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
 
+    def softmax_loss(self, anchor_idx: torch.Tensor, positive_idx: torch.Tensor, scale: float = 1.0,
+                     reduction: str = 'mean', in_batch: bool = False) -> torch.Tensor:
+        """Softmax cross-entropy of every anchor against the WHOLE target table (functional.softmax_scores_loss; a shared
+        table counts from ``target_offset`` to its end), ``positive_idx`` (B,) the ids ``forward`` / ``topk`` take, -1 an
+        ignored sample.  ``in_batch=True``: against the B positives of the batch instead (every id must name a row).
+        The anchors come through the differentiable row lookup, both tables receive dense gradients (a fused optimizer
+        set on the module is not used here).  ``reduction``: 'mean' (over the non-ignored samples) | 'sum' | 'none'.
+        Inner product only."""
+        if self.similarity != 'dot':
+            raise NotImplementedError("EmbeddingPairScorer.softmax_loss: similarity 'dot' only")
+        aw = self.anchor.weight
+        tw = aw if self.target is None else self.target.weight
+        a_idx, y = F_._as_index(anchor_idx).reshape(-1, 1), F_._as_index(positive_idx).reshape(-1)
+        dev = aw.device
+        anchors = F_.gather_rows(aw, a_idx, F_._pair_offset_columns(dev, self.anchor_offset, 0, 1, 0)).rename(None)
+        anchors = anchors.reshape(a_idx.shape[0], -1)
+        if in_batch:
+            rows = F_.gather_rows(tw, y.reshape(-1, 1), F_._pair_offset_columns(dev, self.target_offset, 0, 1, 0))
+            targets = rows.rename(None).reshape(y.shape[0], -1)
+            y = torch.arange(y.shape[0], dtype=torch.int64, device=dev)
+        else:
+            targets = tw[self.target_offset:]
+        loss = F_.softmax_scores_loss(anchors, targets, y, scale)
+        return F_.reduce_sample_losses(loss, y, targets.shape[0], reduction)
+
 
 class BCEWithLogitsLoss(nn.Module):
     """``nn.BCEWithLogitsLoss()`` (mean reduction, no weights) on the HIP device: ``loss(logits, labels)`` with logits in

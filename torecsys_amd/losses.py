@@ -108,6 +108,24 @@ class TripletLoss(PairwiseRankingLoss):
         return F_.rank_loss(pos_out, neg_out, 'bpr', 0.0, mask, self.reduction)
 
 
+class FullSoftmaxLoss(nn.Module):
+    """Softmax cross-entropy of anchors (B, E) against every row of targets (Vt, E) (functional.softmax_scores_loss; not in
+    the reference): ``forward(anchors, targets, labels)`` for callers with their own towers; labels (B,) int, -1 ignored.
+    ``reduction``: 'mean' (over the non-ignored samples) | 'sum' | 'none'.  In batch: targets = the positives' rows,
+    labels = arange(B)."""
+
+    def __init__(self, scale: float = 1.0, reduction: str = 'mean'):
+        super().__init__()
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError(f"torecsys_amd.losses.FullSoftmaxLoss: reduction 'mean', 'sum' or 'none', got {reduction!r}")
+        self.scale = scale
+        self.reduction = reduction
+
+    def forward(self, anchors: torch.Tensor, targets: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        loss = F_.softmax_scores_loss(anchors, targets, labels, self.scale)
+        return F_.reduce_sample_losses(loss, labels, targets.shape[0], self.reduction)
+
+
 class PointwiseLogisticLoss(PointwiseRankingLoss):
     """(1 - sigmoid(p)) + sigmoid(n), mean.  pointwise_ranking_loss.py PointwiseLogisticLoss."""
 
