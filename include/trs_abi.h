@@ -1432,6 +1432,35 @@ int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* targets, in
                          const void* labels, int32_t label_dtype, float scale, const float* lse, const float* g_loss,
                          void* d_anchors, void* d_targets, void* workspace, size_t ws_bytes, trs_stream_t stream);
 
+/* ---- the same loss over a cosine similarity and / or with a per-target logit bias (csrc/softmax_loss.hip) --------------
+ * sim 0 (inner product) | 1 (cosine), anything else TRS_EINVAL; bias (Vt) fp32, finite, or NULL (= 0):
+ *   s[b, j] = <A[b], T[j]>                          sim 0
+ *           = <A[b], T[j]> ra[b] rt[j]              sim 1: ra[b] = 1 / max(|A[b]|, 1e-8), rt[j] = 1 / max(|T[j]|, 1e-8), the
+ *                                                   squares summed in fp32 (the rule of csrc/rank.hip and trs_topk_scores)
+ *   z[b, j] = scale * s[b, j] + bias[j]             lse, loss and w = g_b (exp(z - lse_b) - [j == y_b]) as above
+ *   d_bias[j] = sum_b w[b, j]                       (Vt) fp32
+ *   sim 0:  dA[b] = scale sum_j w[b, j] T[j]                                  dT[j] = scale sum_b w[b, j] A[b]
+ *   sim 1:  dA[b] = scale ra[b] (sum_j (w[b, j] rt[j]) T[j] - ra[b] c[b] A[b])       c[b]  = sum_j w[b, j] s[b, j]
+ *           dT[j] = scale rt[j] (sum_b (w[b, j] ra[b]) A[b] - rt[j] c'[j] T[j])      c'[j] = sum_b w[b, j] s[b, j]
+ * A row whose norm is not above 1e-8 was clamped: the clamp passes no gradient to the norm, the row gets no projection
+ * term (the rule of the pair-score backward of csrc/rank.hip).  A logQ correction is bias = -log Q; -inf as a mask is
+ * not supported.
+ * d_bias is summed by the target-gradient kernel: d_bias without bias or without d_targets is TRS_EINVAL.  sim = 0 with
+ * bias = NULL is exactly trs_softmax_loss_fwd / _bwd (one host path, the same kernels).  The cosine projection is applied
+ * per range before the partials are written, the d_bias partials (S, Vt) follow the target gradient's in the workspace
+ * (trs_softmax_loss_sim_workspace_bytes covers them) and are summed in range order: no atomics, bit-identical results.
+ * Limits, alignment, labels, err_flag, the split and the error order are those of the entries above; B == 0 also zeroes
+ * d_bias.                                                                                                               */
+size_t trs_softmax_loss_sim_workspace_bytes(int64_t B, int64_t Vt, int32_t E, int32_t backward);
+int trs_softmax_loss_sim_fwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E, int32_t dtype,
+                             int32_t sim, const float* bias, const void* labels, int32_t label_dtype, int64_t ignore_index,
+                             float scale, float* loss, float* lse, void* workspace, size_t ws_bytes, int32_t* err_flag,
+                             trs_stream_t stream);
+int trs_softmax_loss_sim_bwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E, int32_t dtype,
+                             int32_t sim, const float* bias, const void* labels, int32_t label_dtype, float scale,
+                             const float* lse, const float* g_loss, void* d_anchors, void* d_targets, float* d_bias,
+                             void* workspace, size_t ws_bytes, trs_stream_t stream);
+
 /* ---- ranking losses over (positive, negatives) scores (csrc/rank.hip; losses/ltr/functional.py) ---------------------
  * pos: one value per sample at pos[b * pos_stride]; neg: K values per sample at neg[b * neg_stride + k] (columns 0 and
  * 1 .. K of one (B, 1+K) score matrix: pos = S, neg = S + 1, both strides 1 + K); dtype TRS_F32 | TRS_BF16; mask (B) one

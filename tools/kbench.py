@@ -42,6 +42,8 @@ on the same ids (own inputs, see bench_q8).
 bf16 copy held in memory, dequantize + float kernel per call, and the Q8 kernel; times and peak memory
 --what softmax [--budget 4]: full-catalogue softmax loss, forward and forward + backward, against a chunked ATen composition
 that recomputes each chunk's logits in its backward; 1 M rows and in batch, bf16 and fp32 (own inputs, see bench_softmax).
+--sim cosine and / or --bias time the cosine / per-target-bias kernels against the same composition over F.normalize'd
+operands with the bias added per chunk.
 --what topk [--k 100] [--sim dot|cosine] [--budget 4]: top-k retrieval over a 1 M-row table against the chunked ATen
 composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk)."""
 import argparse
@@ -1464,39 +1466,51 @@ def bench_softmax(a):
     1 M-row table and in batch (Vt = B), E = 64, bf16 and fp32, forward and forward + backward (both gradients).  The two
     take turns launch by launch after one warm-up each; a shape stops after 10 launches of each or once --budget seconds
     of timed work have passed, with at least 3.  FLOP/s count 2 B V E per matrix product: 1 forward, 5 forward + backward
-    (scores, and per gradient the scores again and the contraction)."""
+    (scores, and per gradient the scores again and the contraction).  --sim cosine: the kernel's sim='cosine' against the
+    composition over ``F.normalize``d operands (autograd carries the normalisation's gradient); --bias: a (Vt,) fp32 bias
+    that requires a gradient, added to each chunk's logits, its gradient the chunk's column sums of w."""
     dev = torch.device("cuda:0")
     E = a.E
+    cos, with_bias = a.sim == "cosine", a.bias
     g = torch.Generator(device=dev).manual_seed(78)
 
     class Chunked(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, q, t, y):
+        def forward(ctx, q, t, y, bias):
             B, V = q.shape[0], t.shape[0]
             ctx.chunk = chunk = max(4096, min(V, (1 << 28) // B))
             lse = torch.full((B,), float("-inf"), device=q.device)
             pos = torch.zeros(B, device=q.device)
             for lo in range(0, V, chunk):
                 z = (q @ t[lo:lo + chunk].T).float()
+                if bias is not None:
+                    z += bias[lo:lo + chunk]
                 lse = torch.logaddexp(lse, torch.logsumexp(z, dim=1))
                 here = (y >= lo) & (y < lo + z.shape[1])
                 pos = torch.where(here, z.gather(1, (y - lo).clamp(0, z.shape[1] - 1).unsqueeze(1)).squeeze(1), pos)
-            ctx.save_for_backward(q, t, y, lse)
+            ctx.save_for_backward(q, t, y, lse, bias)
             return lse - pos
 
         @staticmethod
         def backward(ctx, gl):
-            q, t, y, lse = ctx.saved_tensors
+            q, t, y, lse, bias = ctx.saved_tensors
             dq, dt = torch.zeros_like(q, dtype=torch.float32), torch.empty_like(t)
+            db = None if bias is None else torch.empty_like(bias)
             for lo in range(0, t.shape[0], ctx.chunk):
                 tc = t[lo:lo + ctx.chunk]
-                w = torch.exp((q @ tc.T).float() - lse[:, None])
+                z = (q @ tc.T).float()
+                if bias is not None:
+                    z += bias[lo:lo + ctx.chunk]
+                w = torch.exp(z - lse[:, None])
                 here = ((y >= lo) & (y < lo + tc.shape[0])).nonzero().squeeze(1)
                 w[here, y[here] - lo] -= 1.0
-                w = (w * gl[:, None]).to(q.dtype)
+                w = w * gl[:, None]
+                if db is not None:
+                    db[lo:lo + ctx.chunk] = w.sum(dim=0)
+                w = w.to(q.dtype)
                 dq += (w @ tc).float()
                 dt[lo:lo + ctx.chunk] = w.T @ q
-            return dq.to(q.dtype), dt, None
+            return dq.to(q.dtype), dt, None, db
 
     def race(ours, aten):
         for f in (ours, aten):
@@ -1514,22 +1528,27 @@ def bench_softmax(a):
                 spent += ts[name][-1]
         return {n: sorted(v) for n, v in ts.items()}
 
-    print(f"softmax: E = {E}")
+    print(f"softmax: E = {E} sim = {a.sim} bias = {with_bias}")
     for dt in (torch.bfloat16, torch.float32):
         for B, V in ((4096, a.V), (65536, a.V), (4096, 4096), (65536, 65536)):
             q = (0.3 * torch.randn(B, E, generator=g, device=dev)).to(dt).requires_grad_()
             t = (0.3 * torch.randn(V, E, generator=g, device=dev)).to(dt).requires_grad_()
             y = torch.arange(B, device=dev) if V == B else torch.randint(0, V, (B,), generator=g, device=dev)
             gl = torch.rand(B, generator=g, device=dev)
+            bias = torch.randn(V, generator=g, device=dev).requires_grad_() if with_bias else None
             tag = f"{str(dt)[6:]} B={B} Vt={V}"
 
             def fwd_bwd(f):
                 def run():
                     q.grad = t.grad = None
+                    if bias is not None:
+                        bias.grad = None
                     f(q, t, y).backward(gl)
                 return run
 
-            hip, aten = (lambda q, t, y: F_.softmax_scores_loss(q, t, y)), Chunked.apply
+            norm = (lambda x: torch.nn.functional.normalize(x, dim=1)) if cos else (lambda x: x)
+            hip = lambda q, t, y: F_.softmax_scores_loss(q, t, y, sim=a.sim, bias=bias)
+            aten = lambda q, t, y: Chunked.apply(norm(q), norm(t), y, bias)
             with torch.no_grad():
                 diff = float((hip(q, t, y) - aten(q, t, y)).abs().max())
             for what, fs, mm in (("fwd", (lambda: hip(q.detach(), t.detach(), y), lambda: aten(q.detach(), t.detach(), y)), 1),
@@ -1701,7 +1720,8 @@ def main():
                          "only when given")
     ap.add_argument("--cell", default="lstm", choices=["lstm", "gru", "rnn"], help="seq: the recurrent cell")
     ap.add_argument("--neg", type=int, default=10, help="rank: sampled negatives per sample")
-    ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank: the similarity")
+    ap.add_argument("--sim", default="dot", choices=["dot", "cosine"], help="rank / softmax: the similarity")
+    ap.add_argument("--bias", action="store_true", help="softmax: a per-target logit bias that requires a gradient")
     ap.add_argument("--layers", type=int, default=2, help="prm: encoder layers of the model")
     ap.add_argument("--world", type=int, default=8, help="bagshard: the world size whose rank 0 this process plays")
     ap.add_argument("--shape", default="fixed,uniform,longtail", help="ragged: bag-length distributions to run")

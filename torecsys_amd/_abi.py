@@ -223,6 +223,11 @@ SIGNATURES = {
     "trs_softmax_loss_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
     "trs_softmax_loss_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _P, _I32, _I64, _F32, _P, _P, _P, _SZ, _P, _P]),
     "trs_softmax_loss_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _P, _I32, _F32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "trs_softmax_loss_sim_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
+    "trs_softmax_loss_sim_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _I32, _I64, _F32, _P, _P, _P, _SZ,
+                                           _P, _P]),
+    "trs_softmax_loss_sim_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _I32, _F32, _P, _P, _P, _P, _P, _P,
+                                           _SZ, _P]),
     "trs_rank_loss_workspace_bytes": (_SZ, [_I64]),
     "trs_rank_loss_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _SZ, _P]),
     "trs_rank_loss_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _F32, _I32, _P, _P, _P, _I64, _P, _I64,

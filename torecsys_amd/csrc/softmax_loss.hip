@@ -28,6 +28,20 @@
 // i.e. down a column of the tile (2- or 4-byte reads: see profiles/softmax_loss_kernels.md for why not the transposing
 // read).  The gradient accumulators stay in registers for the whole range; S = 1 rounds and writes them, S > 1 writes fp32
 // partials that sl_bwd_finish_kernel sums in range order.  No floating-point atomics: every sum has one fixed order.
+//
+// Cosine and a per-target bias (template parameter X of the three kernels; SL_PLAIN is the code described above):
+//   s[b, j] = <A[b], T[j]> ra[b] rt[j],  r = 1 / max(|row|, 1e-8) from an fp32 sum of squares (rank.hip, topk.hip)
+//   z[b, j] = scale s[b, j] + bias[j]                       d_bias[j] = sum_b w[b, j]
+//   dA[b]   = scale ra[b] (sum_j (w[b, j] rt[j]) T[j] - ra[b] c[b] A[b]),  c[b] = sum_j w[b, j] s[b, j];  dT alike
+// The inverse norms of the stationary rows are held per lane, those of a streamed tile are computed by the workgroup from
+// the tile in LDS into a [2][TR] array one step ahead of the tile that is scored (tile_norms of topk.hip); a target
+// tile's bias is loaded with it into a second [2][TR] array.  The backward adds w s to one scalar per stationary row
+// before w replaces the score (and, for the target gradient, w to a second one: d_bias), multiplies w by the streamed
+// row's inverse norm and runs the second MFMA as before; behind the last tile the scalars are folded over the row's four
+// lanes and every lane applies scale r (G - r c x) to its columns, x from the stationary rows in LDS.  A row whose norm
+// is not above eps gets no projection term (the clamp passes no gradient).  The projection is linear in a range's sums,
+// so S > 1 writes projected partials and the finish is unchanged; d_bias partials (S, Vt) follow the gradient partials
+// in the workspace and sl_dbias_finish_kernel sums them in range order.
 #include <algorithm>
 
 #include "lds_dma.hpp"
@@ -40,6 +54,8 @@ typedef __attribute__((ext_vector_type(4))) float sl_f32x4;
 constexpr int SL_MAX_E = 256, SL_MAX_SPLITS = 64;
 constexpr size_t SL_MAX_LDS = 160 * 1024;
 constexpr int SL_BWD_AR = 32;      // stationary rows per wave of the backward
+constexpr int SL_PLAIN = 0, SL_BIAS = 1, SL_COS = 2;      // X: inner product; + bias; cosine (+ bias where there is one)
+constexpr float SL_COS_EPS = 1e-8f;                       // rank.hip's COS_EPS
 
 struct SlArgs {
   const char* st;          // stationary rows (Ns, E): the anchors; dT: the targets
@@ -47,6 +63,9 @@ struct SlArgs {
   const void* labels;      // (B)
   const float* lse;        // (B)   backward
   const float* g;          // (B)   backward
+  const float* bias;       // (Vt)  or NULL
+  float* dbias;            // (Vt)  dT, or NULL
+  float* ws_db;            // (S, Vt) partials of dbias, S > 1
   float* loss;             // (B)   forward
   float* lse_out;          // (B)   forward
   float* ws;
@@ -126,8 +145,23 @@ __device__ __forceinline__ void sl_scores(sl_f32x4 (&acc)[AT][NT], const char* S
   }
 }
 
+// 1 / max(|LDS row r|, eps): the squares of its real chunks summed in order, fp32 (tk_row_sq of topk.hip)
+template <typename T>
+__device__ __forceinline__ float sl_row_norm(const char* rows, int r, const SlArgs& p) {
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+  float s = 0.f;
+  for (int c = 0; c < p.nce; ++c) {
+    float f[Vec16<T>::VE];
+    Vec16<T>::unpack(*reinterpret_cast<const uint4*>(rows + ((size_t)r * p.nc + (c ^ g)) * 16), f);
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::VE; ++e) s += f[e] * f[e];
+  }
+  return sqrtf(s);
+}
+__device__ __forceinline__ float sl_inv(float norm) { return 1.f / fmaxf(norm, SL_COS_EPS); }
+
 // ------------------------------------------------------------------------------------------------ forward
-template <typename T, int AR, int TR>
+template <typename T, int AR, int TR, int X>
 __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
   extern __shared__ __attribute__((aligned(16))) char sl_smem[];
   constexpr int AT = AR / 16, NT = TR / 16;
@@ -136,6 +170,9 @@ __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
   const int RB = p.nc * 16;
   char* As = sl_smem;
   char* Ts = As + (size_t)NA * RB;
+  float* t_inv = reinterpret_cast<float*>(Ts + (size_t)2 * TR * RB);      // X != SL_PLAIN: [2][TR] inverse norms (cosine)
+  float* t_bias = t_inv + 2 * TR;                                         //                [2][TR] bias, 0 behind the end
+  float* a_inv = t_bias + 2 * TR;                                         //                [NA] (cosine)
 
   const int64_t b0 = (int64_t)blockIdx.x * NA;
   sl_stage_padded(As, p.st, b0, p.Ns, NA, p);
@@ -143,13 +180,28 @@ __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
   const int64_t hi = std::min<int64_t>(lo + p.rows_per, p.Nr);
   const int ntile = hi > lo ? (int)((hi - lo + TR - 1) / TR) : 0;
   auto load_tile = [&](int t, int buf) {
+    const int64_t t0 = lo + (int64_t)t * TR;
     char* dst = Ts + (size_t)buf * TR * RB;
-    if (p.dma) sl_stage_dma(dst, p.sr, lo + (int64_t)t * TR, hi, TR, p);
-    else sl_stage_padded(dst, p.sr, lo + (int64_t)t * TR, hi, TR, p);
+    if (p.dma) sl_stage_dma(dst, p.sr, t0, hi, TR, p);
+    else sl_stage_padded(dst, p.sr, t0, hi, TR, p);
+    if constexpr (X != SL_PLAIN) {
+      for (int r = threadIdx.x; r < TR; r += blockDim.x)
+        t_bias[buf * TR + r] = p.bias != nullptr && t0 + r < hi ? p.bias[t0 + r] : 0.f;
+    }
+  };
+  // a row behind the range's end is the last row again (LDS-DMA) or zeros (r = 1e8, score 0): finite, and masked below
+  auto tile_norms = [&](int buf) {
+    for (int r = threadIdx.x; r < TR; r += blockDim.x)
+      t_inv[buf * TR + r] = sl_inv(sl_row_norm<T>(Ts + (size_t)buf * TR * RB, r, p));
   };
   if (ntile > 0) load_tile(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+  if constexpr (X == SL_COS) {
+    for (int r = threadIdx.x; r < NA; r += blockDim.x) a_inv[r] = sl_inv(sl_row_norm<T>(As, r, p));
+    if (ntile > 0) tile_norms(0);
+    __syncthreads();
+  }
 
   // per lane: anchor n of each of the wave's AT groups of 16, over the targets 4 q .. 4 q + 3 of every group
   const int row0 = wave * AR + n;
@@ -168,6 +220,9 @@ __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
     s[at] = 0.f;
     zp[at] = 0.f;
   }
+  float ra[AT];
+#pragma unroll
+  for (int at = 0; at < AT; ++at) ra[at] = X == SL_COS ? a_inv[row0 + 16 * at] : 1.f;
 
   for (int t = 0; t < ntile; ++t) {
     const int buf = t & 1;
@@ -181,15 +236,24 @@ __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
       const int yl = y[at] >= t0 && y[at] < t0 + TR ? (int)(y[at] - t0) : -1;      // the positive, where this tile holds it
       float tm = -INFINITY;
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
+      for (int nt = 0; nt < NT; ++nt) {
+        float4 r4 = make_float4(1.f, 1.f, 1.f, 1.f), c4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (X == SL_COS) r4 = *reinterpret_cast<const float4*>(t_inv + buf * TR + 16 * nt + 4 * q);
+        if constexpr (X != SL_PLAIN) c4 = *reinterpret_cast<const float4*>(t_bias + buf * TR + 16 * nt + 4 * q);
+        const float rj[4] = {r4.x, r4.y, r4.z, r4.w}, cj[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int local = 16 * nt + 4 * q + j;
-          const float z = local < valid ? acc[at][nt][j] * p.scale : -INFINITY;
+          float z = acc[at][nt][j];
+          if constexpr (X == SL_COS) z = z * ra[at] * rj[j];
+          z *= p.scale;
+          if constexpr (X != SL_PLAIN) z += cj[j];
+          if (local >= valid) z = -INFINITY;
           acc[at][nt][j] = z;
           tm = fmaxf(tm, z);
           if (local == yl) zp[at] = z;
         }
+      }
       if (tm > m[at]) {      // the max rises: what was summed so far is rescaled (nothing was, where m is -inf)
         s[at] = m[at] == -INFINITY ? 0.f : s[at] * expf(m[at] - tm);
         m[at] = tm;
@@ -203,6 +267,12 @@ __global__ __launch_bounds__(256) void sl_fwd_kernel(SlArgs p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (X == SL_COS) {      // the next tile has landed: its norms, one step ahead
+      if (t + 1 < ntile) {
+        tile_norms(buf ^ 1);
+        __syncthreads();
+      }
+    }
   }
 
   // ---- the four lanes of an anchor
@@ -260,11 +330,12 @@ __device__ __forceinline__ uint32_t sl_lds_elem(const char* rows, int r, int e, 
 
 // DT false: stationary = anchors, streamed = targets (dA).  DT true: stationary = targets, streamed = anchors (dT).
 // EB: 16-column blocks of the gradient a lane holds accumulators for (E <= 16 EB).
-template <typename T, int EB, int TR, bool DT>
+template <typename T, int EB, int TR, bool DT, int X, int AR = SL_BWD_AR>
 __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
   extern __shared__ __attribute__((aligned(16))) char sl_smem[];
-  constexpr int AR = SL_BWD_AR, AT = AR / 16, NT = TR / 16;
+  constexpr int AT = AR / 16, NT = TR / 16;
   constexpr bool F32 = std::is_same<T, float>::value;
+  constexpr bool COS = X == SL_COS, BIAS = X != SL_PLAIN;
   const int NW = blockDim.x >> 6, NA = NW * AR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
   const int RB = p.nc * 16;
@@ -273,6 +344,8 @@ __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
   float* r_lse = reinterpret_cast<float*>(Rs + (size_t)2 * TR * RB);      // DT: [2][TR] each
   float* r_g = r_lse + 2 * TR;
   int* r_y = reinterpret_cast<int*>(r_g + 2 * TR);
+  float* r_inv = DT ? r_lse + 6 * TR : r_lse;      // X != SL_PLAIN: [2][TR] inverse norms of the streamed rows (cosine)
+  float* r_bias = r_inv + 2 * TR;                  //                dA: [2][TR] bias of the streamed targets
 
   const int64_t s0 = (int64_t)blockIdx.x * NA;
   sl_stage_padded(Ss, p.st, s0, p.Ns, NA, p);
@@ -300,18 +373,35 @@ __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
         r_g[buf * TR + r] = g;
         r_y[buf * TR + r] = yy;
       }
+    } else if constexpr (BIAS) {
+      for (int r = threadIdx.x; r < TR; r += blockDim.x)
+        r_bias[buf * TR + r] = p.bias != nullptr && t0 + r < hi ? p.bias[t0 + r] : 0.f;
     }
+  };
+  // a streamed row behind the range's end: the last row again (LDS-DMA) or zeros (r = 1e8, score 0); its w is set to 0
+  auto tile_norms = [&](int buf) {
+    for (int r = threadIdx.x; r < TR; r += blockDim.x)
+      r_inv[buf * TR + r] = sl_inv(sl_row_norm<T>(Rs + (size_t)buf * TR * RB, r, p));
   };
   if (ntile > 0) load_tile(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+  if constexpr (COS) {
+    if (ntile > 0) tile_norms(0);
+    __syncthreads();
+  }
 
   const int row0 = wave * AR + n;
   float s_lse[AT], s_g[AT];
   int64_t s_y[AT];      // dA: the anchor's label; dT: the stationary target's own row number
+  float s_inv[AT], s_bias[AT];      // the stationary row's inverse norm (cosine); dT: its bias
+  float c[AT], db[AT];              // sum of w s (cosine) and, dT, of w over the streamed rows this lane sees
 #pragma unroll
   for (int at = 0; at < AT; ++at) {
     const int64_t sr = s0 + row0 + 16 * at;
+    s_inv[at] = COS ? sl_inv(sl_row_norm<T>(Ss, row0 + 16 * at, p)) : 1.f;
+    s_bias[at] = DT && BIAS && p.bias != nullptr && sr < p.Ns ? p.bias[sr] : 0.f;
+    c[at] = db[at] = 0.f;
     s_lse[at] = INFINITY;
     s_g[at] = 0.f;
     s_y[at] = DT ? sr : -1;
@@ -354,19 +444,30 @@ __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
       }
       const float lj[4] = {l4.x, l4.y, l4.z, l4.w}, gj[4] = {g4.x, g4.y, g4.z, g4.w};
       const int yj[4] = {y4.x, y4.y, y4.z, y4.w};
+      float4 r4 = make_float4(1.f, 1.f, 1.f, 1.f), c4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (COS) r4 = *reinterpret_cast<const float4*>(r_inv + buf * TR + 16 * nt + 4 * q);
+      if constexpr (BIAS && !DT) c4 = *reinterpret_cast<const float4*>(r_bias + buf * TR + 16 * nt + 4 * q);
+      const float rj[4] = {r4.x, r4.y, r4.z, r4.w}, cj[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
       for (int at = 0; at < AT; ++at)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int local = 16 * nt + 4 * q + j;
-          const float z = acc[at][nt][j] * p.scale;
+          float sc = acc[at][nt][j];      // the forward's order: the anchor's inverse norm first
+          if constexpr (COS) sc = DT ? sc * rj[j] * s_inv[at] : sc * s_inv[at] * rj[j];
+          float z = sc * p.scale;
+          if constexpr (BIAS) z += DT ? s_bias[at] : cj[j];
           float w;
           if constexpr (DT) {
             w = gj[j] * (expf(z - lj[j]) - ((int64_t)yj[j] == s_y[at] ? 1.f : 0.f));
+            if (BIAS && local >= valid) w = 0.f;
           } else {
             w = s_g[at] * (expf(z - s_lse[at]) - (local == yl[at] ? 1.f : 0.f));
             if (local >= valid) w = 0.f;
           }
+          if constexpr (COS) c[at] += w * sc;
+          if constexpr (DT && BIAS) db[at] += w;
+          if constexpr (COS) w *= rj[j];
           acc[at][nt][j] = w;
         }
     }
@@ -422,6 +523,25 @@ __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (COS) {      // the next tile has landed: its norms, one step ahead
+      if (t + 1 < ntile) {
+        tile_norms(buf ^ 1);
+        __syncthreads();
+      }
+    }
+  }
+
+  // ---- the four lanes of a stationary row hold a quarter of the streamed rows each
+#pragma unroll
+  for (int at = 0; at < AT; ++at) {
+    if constexpr (COS) {
+      c[at] += __shfl_xor(c[at], 16, 64);
+      c[at] += __shfl_xor(c[at], 32, 64);
+    }
+    if constexpr (DT && BIAS) {
+      db[at] += __shfl_xor(db[at], 16, 64);
+      db[at] += __shfl_xor(db[at], 32, 64);
+    }
   }
 
   // ---- lane (n, q) holds columns 16 eb + 4 q .. + 3 of stationary row n
@@ -429,11 +549,26 @@ __global__ __launch_bounds__(256) void sl_bwd_kernel(SlArgs p) {
   for (int at = 0; at < AT; ++at) {
     const int64_t sr = s0 + row0 + 16 * at;
     if (sr >= p.Ns) continue;
+    if constexpr (DT && BIAS) {
+      if (q == 0 && p.dbias != nullptr) (p.S > 1 ? p.ws_db + (size_t)blockIdx.y * p.Ns : p.dbias)[sr] = db[at];
+    }
+    // cosine: scale r (G - r c x); a norm that is not above eps was clamped and passes no gradient: no projection
+    const float rs = p.scale * s_inv[at];
+    const float pc = COS && sl_row_norm<T>(Ss, row0 + 16 * at, p) > SL_COS_EPS ? s_inv[at] * c[at] : 0.f;
 #pragma unroll
     for (int eb = 0; eb < EB; ++eb) {
       const int e = 16 * eb + 4 * q;
       if (e >= p.E) continue;      // E is a multiple of 4: four columns or none
-      const sl_f32x4 d = dacc[at][eb] * p.scale;
+      sl_f32x4 d;
+      if constexpr (COS) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t xb = sl_lds_elem<T>(Ss, row0 + 16 * at, e + k, RB, p);
+          d[k] = (dacc[at][eb][k] - pc * (F32 ? __uint_as_float(xb) : bf16_bits_to_f32(xb))) * rs;
+        }
+      } else {
+        d = dacc[at][eb] * p.scale;
+      }
       if (p.S > 1) {
         *reinterpret_cast<float4*>(p.ws + ((size_t)blockIdx.y * p.Ns + sr) * p.E + e) = make_float4(d[0], d[1], d[2], d[3]);
       } else if constexpr (F32) {
@@ -496,67 +631,98 @@ static int sl_go(const char* op, K kern, dim3 grid, int threads, size_t lds, hip
   return TRS_OK;
 }
 
+
+// S > 1: d_bias[j] = the S partial sums of target j in range order
+__global__ __launch_bounds__(256) void sl_dbias_finish_kernel(const float* __restrict__ ws, int S, int64_t Vt, float* out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= Vt) return;
+  float a = ws[j];
+  for (int s = 1; s < S; ++s) a += ws[(size_t)s * Vt + j];
+  out[j] = a;
+}
+
 struct SlShape {
   int AR, TR, NW;
 };
 
-template <typename T>
+template <typename T, int X>
 static int sl_fwd_launch(const char* op, SlArgs& p, hipStream_t s) {
-  // the first arrangement whose anchors and two target tiles fit the 160 KB of LDS
+  // the first arrangement whose anchors and two target tiles (X != SL_PLAIN: and their norms and bias) fit the 160 KB of LDS
   static const SlShape shapes[] = {{32, 128, 4}, {16, 128, 4}, {16, 64, 4}, {16, 64, 2}, {16, 32, 2}, {16, 32, 1}};
   const size_t RB = (size_t)p.nc * 16;
+  auto bytes = [&](const SlShape& c) {
+    return ((size_t)c.NW * c.AR + 2 * c.TR) * RB + (X != SL_PLAIN ? (size_t)(4 * c.TR + c.NW * c.AR) * 4 : 0);
+  };
   const SlShape* sh = nullptr;
   for (const SlShape& c : shapes)
-    if (((size_t)c.NW * c.AR + 2 * c.TR) * RB <= SL_MAX_LDS) {
+    if (bytes(c) <= SL_MAX_LDS) {
       sh = &c;
       break;
     }
   TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS (row %zu bytes)", op, RB);
-  const size_t lds = ((size_t)sh->NW * sh->AR + 2 * sh->TR) * RB;
+  const size_t lds = bytes(*sh);
   const int NA = sh->NW * sh->AR;
   const dim3 grid((unsigned)((p.Ns + NA - 1) / NA), (unsigned)p.S);
   int rc;
-  if (sh->AR == 32) rc = sl_go(op, sl_fwd_kernel<T, 32, 128>, grid, 64 * sh->NW, lds, s, p);
-  else if (sh->TR == 128) rc = sl_go(op, sl_fwd_kernel<T, 16, 128>, grid, 64 * sh->NW, lds, s, p);
-  else if (sh->TR == 64) rc = sl_go(op, sl_fwd_kernel<T, 16, 64>, grid, 64 * sh->NW, lds, s, p);
-  else rc = sl_go(op, sl_fwd_kernel<T, 16, 32>, grid, 64 * sh->NW, lds, s, p);
+  if (sh->AR == 32) rc = sl_go(op, sl_fwd_kernel<T, 32, 128, X>, grid, 64 * sh->NW, lds, s, p);
+  else if (sh->TR == 128) rc = sl_go(op, sl_fwd_kernel<T, 16, 128, X>, grid, 64 * sh->NW, lds, s, p);
+  else if (sh->TR == 64) rc = sl_go(op, sl_fwd_kernel<T, 16, 64, X>, grid, 64 * sh->NW, lds, s, p);
+  else rc = sl_go(op, sl_fwd_kernel<T, 16, 32, X>, grid, 64 * sh->NW, lds, s, p);
   if (rc != TRS_OK) return rc;
   if (p.S > 1) hipLaunchKernelGGL(sl_fwd_finish_kernel, dim3((unsigned)((p.Ns + 255) / 256)), dim3(256), 0, s, p);
   return check_launch(op);
 }
 
 // one gradient: `p` already holds stationary / streamed rows and their counts
-template <typename T, bool DT>
+template <typename T, bool DT, int X>
 static int sl_bwd_launch(const char* op, SlArgs& p, hipStream_t s) {
   // E > 64 holds 16 column blocks of accumulators per lane: with tiles of 64 rows that kernel spills, so 32 there
   static const SlShape shapes[] = {{SL_BWD_AR, 64, 4}, {SL_BWD_AR, 64, 2}, {SL_BWD_AR, 32, 4}, {SL_BWD_AR, 32, 2},
                                    {SL_BWD_AR, 32, 1}};
+  // cosine on wide bf16 rows: the inverse norms and the scalar beside 16 column blocks of two row groups spill (5 VGPRs),
+  // so a wave holds one group of 16 stationary rows there
+  constexpr int WAR = X == SL_COS && !std::is_same<T, float>::value ? 16 : SL_BWD_AR;
+  static const SlShape wide_shapes[] = {{WAR, 32, 4}, {WAR, 32, 2}, {WAR, 32, 1}};
   const size_t RB = (size_t)p.nc * 16;
   const bool wide = p.E > 64;
-  auto bytes = [&](const SlShape& c) { return ((size_t)c.NW * c.AR + 2 * c.TR) * RB + (DT ? (size_t)2 * c.TR * 12 : 0); };
+  auto bytes = [&](const SlShape& c) {      // X != SL_PLAIN: the streamed rows' inverse norms and (dA) bias, [2][TR] each
+    return ((size_t)c.NW * c.AR + 2 * c.TR) * RB + (DT ? (size_t)2 * c.TR * 12 : 0) + (X != SL_PLAIN ? (size_t)2 * c.TR * 8 : 0);
+  };
   const SlShape* sh = nullptr;
   for (const SlShape& c : shapes)
-    if (!(wide && c.TR == 64) && bytes(c) <= SL_MAX_LDS) {
-      sh = &c;
-      break;
-    }
+    if (!wide && bytes(c) <= SL_MAX_LDS && sh == nullptr) sh = &c;
+  for (const SlShape& c : wide_shapes)
+    if (wide && bytes(c) <= SL_MAX_LDS && sh == nullptr) sh = &c;
   TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS (row %zu bytes)", op, RB);
   const int NA = sh->NW * sh->AR;
   const dim3 grid((unsigned)((p.Ns + NA - 1) / NA), (unsigned)p.S);
   int rc;
-  if (sh->TR == 64) {
-    rc = sl_go(op, sl_bwd_kernel<T, 4, 64, DT>, grid, 64 * sh->NW, bytes(*sh), s, p);
-  } else {
-    rc = wide ? sl_go(op, sl_bwd_kernel<T, 16, 32, DT>, grid, 64 * sh->NW, bytes(*sh), s, p)
-              : sl_go(op, sl_bwd_kernel<T, 4, 32, DT>, grid, 64 * sh->NW, bytes(*sh), s, p);
-  }
+  if (wide) rc = sl_go(op, sl_bwd_kernel<T, 16, 32, DT, X, WAR>, grid, 64 * sh->NW, bytes(*sh), s, p);
+  else if (sh->TR == 64) rc = sl_go(op, sl_bwd_kernel<T, 4, 64, DT, X>, grid, 64 * sh->NW, bytes(*sh), s, p);
+  else rc = sl_go(op, sl_bwd_kernel<T, 4, 32, DT, X>, grid, 64 * sh->NW, bytes(*sh), s, p);
   if (rc != TRS_OK) return rc;
   if (p.S > 1) {
     const int64_t total = p.Ns * p.E;
     hipLaunchKernelGGL(sl_bwd_finish_kernel<T>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, p.ws, p.S, total,
                        p.out);
+    if (DT && p.dbias != nullptr)
+      hipLaunchKernelGGL(sl_dbias_finish_kernel, dim3((unsigned)((p.Ns + 255) / 256)), dim3(256), 0, s, p.ws_db, p.S, p.Ns,
+                         p.dbias);
   }
   return check_launch(op);
+}
+
+template <typename T>
+static int sl_fwd_pick(const char* op, int X, SlArgs& p, hipStream_t s) {
+  return X == SL_PLAIN ? sl_fwd_launch<T, SL_PLAIN>(op, p, s)
+         : X == SL_BIAS ? sl_fwd_launch<T, SL_BIAS>(op, p, s)
+                        : sl_fwd_launch<T, SL_COS>(op, p, s);
+}
+template <typename T, bool DT>
+static int sl_bwd_pick(const char* op, int X, SlArgs& p, hipStream_t s) {
+  return X == SL_PLAIN ? sl_bwd_launch<T, DT, SL_PLAIN>(op, p, s)
+         : X == SL_BIAS ? sl_bwd_launch<T, DT, SL_BIAS>(op, p, s)
+                        : sl_bwd_launch<T, DT, SL_COS>(op, p, s);
 }
 
 static size_t sl_fwd_ws(int64_t B, int64_t Vt) {
@@ -566,6 +732,11 @@ static size_t sl_fwd_ws(int64_t B, int64_t Vt) {
 static size_t sl_bwd_ws(int64_t Ns, int64_t Nr, int E) {
   const int S = sl_splits(Ns, Nr);
   return S > 1 ? (size_t)S * Ns * E * 4 : 0;
+}
+// the (S, Vt) partials of d_bias behind the target gradient's
+static size_t sl_dbias_ws(int64_t Vt, int64_t B) {
+  const int S = sl_splits(Vt, B);
+  return S > 1 ? (size_t)S * Vt * 4 : 0;
 }
 
 static int sl_check(const char* op, int64_t B, int64_t Vt, int32_t E, int32_t dtype, int32_t label_dtype) {
@@ -578,21 +749,15 @@ static int sl_check(const char* op, int64_t B, int64_t Vt, int32_t E, int32_t dt
   return TRS_OK;
 }
 
-}  // namespace trs
+// X of the kernels: the plain instantiations for the inner product without a bias, and nothing else
+static int sl_variant(int32_t sim, const float* bias) { return sim == 1 ? SL_COS : bias != nullptr ? SL_BIAS : SL_PLAIN; }
 
-using namespace trs;
-
-extern "C" size_t trs_softmax_loss_workspace_bytes(int64_t B, int64_t Vt, int32_t E, int32_t backward) {
-  if (B <= 0 || Vt <= 0 || E <= 0) return 0;
-  return backward ? std::max(sl_bwd_ws(B, Vt, E), sl_bwd_ws(Vt, B, E)) : sl_fwd_ws(B, Vt);
-}
-
-extern "C" int trs_softmax_loss_fwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
-                                    int32_t dtype, const void* labels, int32_t label_dtype, int64_t ignore_index,
-                                    float scale, float* loss, float* lse, void* workspace, size_t ws_bytes,
-                                    int32_t* err_flag, trs_stream_t stream) {
-  const char* op = "softmax_loss_fwd";
+static int sl_fwd_host(const char* op, const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                       int32_t dtype, int32_t sim, const float* bias, const void* labels, int32_t label_dtype,
+                       int64_t ignore_index, float scale, float* loss, float* lse, void* workspace, size_t ws_bytes,
+                       int32_t* err_flag, trs_stream_t stream) {
   if (int rc = sl_check(op, B, Vt, E, dtype, label_dtype)) return rc;
+  TRS_REQUIRE(sim == 0 || sim == 1, TRS_EINVAL, "%s: sim %d (0 inner product, 1 cosine)", op, sim);
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(anchors && targets && labels && loss && lse, TRS_EINVAL, "%s: NULL pointer", op);
   TRS_REQUIRE(aligned16(anchors) && aligned16(targets), TRS_EALIGN, "%s: anchors and targets must be 16-byte aligned", op);
@@ -606,6 +771,7 @@ extern "C" int trs_softmax_loss_fwd(const void* anchors, int64_t B, const void* 
   p.labels = labels;
   p.lab64 = label_dtype == TRS_I64;
   p.ignore = ignore_index;
+  p.bias = bias;
   p.loss = loss;
   p.lse_out = lse;
   p.ws = static_cast<float*>(workspace);
@@ -617,24 +783,30 @@ extern "C" int trs_softmax_loss_fwd(const void* anchors, int64_t B, const void* 
   p.rows_per = (int)((Vt + p.S - 1) / p.S);
   p.scale = scale;
   hipStream_t s = (hipStream_t)stream;
-  return dtype == TRS_F32 ? sl_fwd_launch<float>(op, p, s) : sl_fwd_launch<bf16_t>(op, p, s);
+  const int X = sl_variant(sim, bias);
+  return dtype == TRS_F32 ? sl_fwd_pick<float>(op, X, p, s) : sl_fwd_pick<bf16_t>(op, X, p, s);
 }
 
-extern "C" int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
-                                    int32_t dtype, const void* labels, int32_t label_dtype, float scale, const float* lse,
-                                    const float* g_loss, void* d_anchors, void* d_targets, void* workspace,
-                                    size_t ws_bytes, trs_stream_t stream) {
-  const char* op = "softmax_loss_bwd";
+static int sl_bwd_host(const char* op, const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                       int32_t dtype, int32_t sim, const float* bias, const void* labels, int32_t label_dtype, float scale,
+                       const float* lse, const float* g_loss, void* d_anchors, void* d_targets, float* d_bias,
+                       void* workspace, size_t ws_bytes, trs_stream_t stream) {
   if (int rc = sl_check(op, B, Vt, E, dtype, label_dtype)) return rc;
+  TRS_REQUIRE(sim == 0 || sim == 1, TRS_EINVAL, "%s: sim %d (0 inner product, 1 cosine)", op, sim);
+  TRS_REQUIRE(d_bias == nullptr || (bias != nullptr && d_targets != nullptr), TRS_EINVAL,
+              "%s: d_bias needs bias and d_targets (the sum lives in the target-gradient kernel)", op);
   hipStream_t s = (hipStream_t)stream;
-  if (B == 0) {      // no sample: the target gradient is zero
+  if (B == 0) {      // no sample: the target and bias gradients are zero
+    if (d_bias != nullptr)
+      if (int rc = zero_bytes(d_bias, (size_t)Vt * 4, s)) return rc;
     if (d_targets != nullptr) return zero_bytes(d_targets, (size_t)Vt * E * dtype_size(dtype), s);
     return TRS_OK;
   }
   TRS_REQUIRE(anchors && targets && labels && lse && g_loss, TRS_EINVAL, "%s: NULL pointer", op);
   TRS_REQUIRE(aligned16(anchors) && aligned16(targets) && aligned16(d_anchors) && aligned16(d_targets), TRS_EALIGN,
               "%s: operands and gradients must be 16-byte aligned", op);
-  const size_t need = std::max(d_anchors ? sl_bwd_ws(B, Vt, E) : 0, d_targets ? sl_bwd_ws(Vt, B, E) : 0);
+  const size_t need = std::max(d_anchors ? sl_bwd_ws(B, Vt, E) : 0,
+                               d_targets ? sl_bwd_ws(Vt, B, E) + (d_bias ? sl_dbias_ws(Vt, B) : 0) : 0);
   TRS_REQUIRE(need == 0 || (workspace != nullptr && ws_bytes >= need && aligned16(workspace)), TRS_EWORKSPACE,
               "%s: workspace %zu < %zu (16-byte aligned)", op, ws_bytes, need);
   SlArgs p = {};
@@ -643,9 +815,11 @@ extern "C" int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* 
   p.lab64 = label_dtype == TRS_I64;
   p.lse = lse;
   p.g = g_loss;
+  p.bias = bias;
   p.ws = static_cast<float*>(workspace);
   p.Vt = Vt;
   p.scale = scale;
+  const int X = sl_variant(sim, bias);
   if (d_anchors != nullptr) {
     p.st = static_cast<const char*>(anchors);
     p.sr = static_cast<const char*>(targets);
@@ -654,7 +828,7 @@ extern "C" int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* 
     p.out = d_anchors;
     p.S = sl_splits(B, Vt);
     p.rows_per = (int)((Vt + p.S - 1) / p.S);
-    const int rc = dtype == TRS_F32 ? sl_bwd_launch<float, false>(op, p, s) : sl_bwd_launch<bf16_t, false>(op, p, s);
+    const int rc = dtype == TRS_F32 ? sl_bwd_pick<float, false>(op, X, p, s) : sl_bwd_pick<bf16_t, false>(op, X, p, s);
     if (rc != TRS_OK) return rc;
   }
   if (d_targets != nullptr) {
@@ -663,9 +837,58 @@ extern "C" int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* 
     p.Ns = Vt;
     p.Nr = B;
     p.out = d_targets;
+    p.dbias = d_bias;
     p.S = sl_splits(Vt, B);
+    p.ws_db = p.ws + (size_t)p.S * Vt * E;
     p.rows_per = (int)((B + p.S - 1) / p.S);
-    return dtype == TRS_F32 ? sl_bwd_launch<float, true>(op, p, s) : sl_bwd_launch<bf16_t, true>(op, p, s);
+    return dtype == TRS_F32 ? sl_bwd_pick<float, true>(op, X, p, s) : sl_bwd_pick<bf16_t, true>(op, X, p, s);
   }
   return TRS_OK;
+}
+
+}  // namespace trs
+
+using namespace trs;
+
+extern "C" size_t trs_softmax_loss_workspace_bytes(int64_t B, int64_t Vt, int32_t E, int32_t backward) {
+  if (B <= 0 || Vt <= 0 || E <= 0) return 0;
+  return backward ? std::max(sl_bwd_ws(B, Vt, E), sl_bwd_ws(Vt, B, E)) : sl_fwd_ws(B, Vt);
+}
+
+extern "C" size_t trs_softmax_loss_sim_workspace_bytes(int64_t B, int64_t Vt, int32_t E, int32_t backward) {
+  if (B <= 0 || Vt <= 0 || E <= 0) return 0;
+  return backward ? std::max(sl_bwd_ws(B, Vt, E), sl_bwd_ws(Vt, B, E) + sl_dbias_ws(Vt, B)) : sl_fwd_ws(B, Vt);
+}
+
+extern "C" int trs_softmax_loss_fwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                                    int32_t dtype, const void* labels, int32_t label_dtype, int64_t ignore_index,
+                                    float scale, float* loss, float* lse, void* workspace, size_t ws_bytes,
+                                    int32_t* err_flag, trs_stream_t stream) {
+  return sl_fwd_host("softmax_loss_fwd", anchors, B, targets, Vt, E, dtype, 0, nullptr, labels, label_dtype, ignore_index,
+                     scale, loss, lse, workspace, ws_bytes, err_flag, stream);
+}
+
+extern "C" int trs_softmax_loss_bwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                                    int32_t dtype, const void* labels, int32_t label_dtype, float scale, const float* lse,
+                                    const float* g_loss, void* d_anchors, void* d_targets, void* workspace,
+                                    size_t ws_bytes, trs_stream_t stream) {
+  return sl_bwd_host("softmax_loss_bwd", anchors, B, targets, Vt, E, dtype, 0, nullptr, labels, label_dtype, scale, lse,
+                     g_loss, d_anchors, d_targets, nullptr, workspace, ws_bytes, stream);
+}
+
+extern "C" int trs_softmax_loss_sim_fwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                                        int32_t dtype, int32_t sim, const float* bias, const void* labels,
+                                        int32_t label_dtype, int64_t ignore_index, float scale, float* loss, float* lse,
+                                        void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  return sl_fwd_host("softmax_loss_sim_fwd", anchors, B, targets, Vt, E, dtype, sim, bias, labels, label_dtype,
+                     ignore_index, scale, loss, lse, workspace, ws_bytes, err_flag, stream);
+}
+
+extern "C" int trs_softmax_loss_sim_bwd(const void* anchors, int64_t B, const void* targets, int64_t Vt, int32_t E,
+                                        int32_t dtype, int32_t sim, const float* bias, const void* labels,
+                                        int32_t label_dtype, float scale, const float* lse, const float* g_loss,
+                                        void* d_anchors, void* d_targets, float* d_bias, void* workspace, size_t ws_bytes,
+                                        trs_stream_t stream) {
+  return sl_bwd_host("softmax_loss_sim_bwd", anchors, B, targets, Vt, E, dtype, sim, bias, labels, label_dtype, scale, lse,
+                     g_loss, d_anchors, d_targets, d_bias, workspace, ws_bytes, stream);
 }

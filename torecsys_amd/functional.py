@@ -4322,19 +4322,68 @@ class _SoftmaxScoresLoss(Function):
         return da, dt, None, None, None
 
 
+class _SoftmaxScoresLossSim(Function):
+    """the same over a cosine similarity and / or with a per-target bias (trs_softmax_loss_sim_*); d_bias is summed by the
+    target-gradient kernel, so a bias that alone needs a gradient has d_targets written into a scratch tensor"""
+
+    @staticmethod
+    def forward(ctx, a, t, y, bias, scale, ignore_index, sim):
+        B, E = a.shape
+        dev = a.device
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        if B > 0:
+            ws_bytes = size_query("trs_softmax_loss_sim_workspace_bytes", B, t.shape[0], E, 0)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+            flag = _ErrFlag(dev)
+            call("trs_softmax_loss_sim_fwd", ptr(a), B, ptr(t), t.shape[0], E, value_dtype_code(a), sim, ptr(bias), ptr(y),
+                 index_dtype_code(y), ignore_index, scale, ptr(loss), ptr(lse), ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+            flag.check("softmax_scores_loss")
+        ctx.save_for_backward(a, t, y, lse, bias)
+        ctx.scale, ctx.sim = scale, sim
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, t, y, lse, bias = ctx.saved_tensors
+        need_a, need_t, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if not (need_a or need_t or need_b):
+            return (None,) * 7
+        _adopt_grads(g)
+        B, E = a.shape
+        g = g.to(torch.float32).contiguous()
+        da = torch.empty_like(a) if need_a else None
+        dt = torch.empty_like(t) if need_t or need_b else None
+        db = torch.empty_like(bias) if need_b else None
+        ws_bytes = size_query("trs_softmax_loss_sim_workspace_bytes", B, t.shape[0], E, 1)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+        call("trs_softmax_loss_sim_bwd", ptr(a), B, ptr(t), t.shape[0], E, value_dtype_code(a), ctx.sim, ptr(bias), ptr(y),
+             index_dtype_code(y), ctx.scale, ptr(lse), ptr(g), ptr(da), ptr(dt), ptr(db), ptr(ws), ws_bytes, stream_ptr())
+        return da, dt if need_t else None, None, db, None, None, None
+
+
 def softmax_scores_loss(anchors: torch.Tensor, targets: torch.Tensor, labels: torch.Tensor, scale: float = 1.0,
-                        ignore_index: int = -1) -> torch.Tensor:
+                        ignore_index: int = -1, *, sim: str = 'dot', bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Softmax cross-entropy of every anchor against EVERY row of ``targets``, per sample, in HIP passes that never form the
     (B, Vt) logits (csrc/softmax_loss.hip): ``loss[b] = logsumexp_j z[b, j] - z[b, labels[b]]`` with ``z = scale *
-    anchors @ targets.T`` (table-dtype products, fp32 accumulation on the matrix cores) -> (B,) fp32.  ``anchors`` (B, E)
+    anchors @ targets.T`` (table-dtype products, fp32 accumulation on the matrix cores) -> (B,) fp32.  ``sim='cosine'``
+    divides each product by ``max(|a|, 1e-8) max(|t|, 1e-8)`` (fp32 norms, the rule of ``pair_scores`` / ``topk_scores``; a
+    clamped row gets no gradient through its norm): ``scale`` is then 1 / temperature.  ``bias`` (Vt,) fp32, contiguous,
+    finite, is added to every logit of its target (``bias = -log_q`` is the logQ correction of sampled / in-batch softmax;
+    -inf as a mask is not supported) and receives a gradient where it requires one -- summed by the target-gradient
+    kernel, so a bias that ALONE requires a gradient costs that kernel with its output dropped (rare: a frozen table
+    with a learned bias).  ``sim='dot'`` without a bias is the original path, untouched.  ``anchors`` (B, E)
     and ``targets`` (Vt, E): bf16 or fp32 of one dtype, contiguous rows of whole 16-byte vectors, E <= 256 (the contract
     of ``topk_scores``); a row range of a table is such a ``targets``.  ``labels`` (B,) int32 / int64.  A sample whose
     label is ``ignore_index`` (negative) has loss 0 and no gradient; any other label outside [0, Vt) is treated the same
     way and raises the index flag.  Gradients go to whichever of ``anchors`` / ``targets`` requires one (the other kernel
     is not launched), recomputing the scores from the saved lse (B); they are bit-identical from run to run.  In-batch
-    softmax: pass the looked-up positive rows as ``targets`` with ``labels = arange(B)``.  Inner product only: no cosine,
-    no per-item bias / logQ correction, no label smoothing, no Q8 targets.  No host read-back: capturable."""
+    softmax: pass the looked-up positive rows as ``targets`` with ``labels = arange(B)`` (and their biases).  No label
+    smoothing, no Q8 targets.  No host read-back: capturable."""
     a, t = anchors, targets
+    if sim not in PAIR_SIMS:
+        raise ValueError(f"softmax_scores_loss: sim must be one of {sorted(PAIR_SIMS)}, got {sim!r}")
     if a.dim() != 2 or t.dim() != 2 or a.shape[1] != t.shape[1]:
         raise ValueError(f"softmax_scores_loss: anchors (B, E) and targets (Vt, E) of one width expected, got "
                          f"{tuple(a.shape)} and {tuple(t.shape)}")
@@ -4355,8 +4404,19 @@ def softmax_scores_loss(anchors: torch.Tensor, targets: torch.Tensor, labels: to
     for name, x in (("anchors", a), ("targets", t)):
         if not x.is_contiguous():
             raise ValueError(f"softmax_scores_loss: {name} must be contiguous, got strides {tuple(x.stride())}")
+    if bias is not None:
+        if bias.dtype != torch.float32:
+            raise TypeError(f"softmax_scores_loss: bias must be fp32, got {bias.dtype}")
+        if bias.dim() != 1 or bias.shape[0] != t.shape[0]:
+            raise ValueError(f"softmax_scores_loss: bias ({t.shape[0]},) expected, got {tuple(bias.shape)}")
+        if not bias.is_contiguous():
+            raise ValueError(f"softmax_scores_loss: bias must be contiguous, got strides {tuple(bias.stride())}")
+        if bias.device != a.device:
+            raise ValueError(f"softmax_scores_loss: bias on {bias.device}, anchors on {a.device}")
     require_device(a, t, labels)
-    return _SoftmaxScoresLoss.apply(a, t, labels.contiguous(), float(scale), int(ignore_index))
+    if sim == 'dot' and bias is None:
+        return _SoftmaxScoresLoss.apply(a, t, labels.contiguous(), float(scale), int(ignore_index))
+    return _SoftmaxScoresLossSim.apply(a, t, labels.contiguous(), bias, float(scale), int(ignore_index), PAIR_SIMS[sim])
 
 
 def reduce_sample_losses(loss: torch.Tensor, labels: torch.Tensor, num_targets: int, reduction: str) -> torch.Tensor:

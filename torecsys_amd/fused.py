@@ -141,15 +141,17 @@ class EmbeddingPairScorer(nn.Module):
                               target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
 
     def softmax_loss(self, anchor_idx: torch.Tensor, positive_idx: torch.Tensor, scale: float = 1.0,
-                     reduction: str = 'mean', in_batch: bool = False) -> torch.Tensor:
+                     reduction: str = 'mean', in_batch: bool = False,
+                     target_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Softmax cross-entropy of every anchor against the WHOLE target table (functional.softmax_scores_loss; a shared
         table counts from ``target_offset`` to its end), ``positive_idx`` (B,) the ids ``forward`` / ``topk`` take, -1 an
         ignored sample.  ``in_batch=True``: against the B positives of the batch instead (every id must name a row).
         The anchors come through the differentiable row lookup, both tables receive dense gradients (a fused optimizer
         set on the module is not used here).  ``reduction``: 'mean' (over the non-ignored samples) | 'sum' | 'none'.
-        Inner product only."""
-        if self.similarity != 'dot':
-            raise NotImplementedError("EmbeddingPairScorer.softmax_loss: similarity 'dot' only")
+        The scores are the module's ``similarity`` (cosine: ``scale`` = 1 / temperature).  ``target_bias``: one fp32 value
+        per target id, indexed as ``forward`` / ``topk`` take the ids, added to that target's logit (a logQ correction is
+        ``target_bias = -log_q``); in batch it is gathered through ``positive_idx``.  It receives a gradient if it
+        requires one.  No label smoothing, no Q8 targets."""
         aw = self.anchor.weight
         tw = aw if self.target is None else self.target.weight
         a_idx, y = F_._as_index(anchor_idx).reshape(-1, 1), F_._as_index(positive_idx).reshape(-1)
@@ -159,10 +161,12 @@ class EmbeddingPairScorer(nn.Module):
         if in_batch:
             rows = F_.gather_rows(tw, y.reshape(-1, 1), F_._pair_offset_columns(dev, self.target_offset, 0, 1, 0))
             targets = rows.rename(None).reshape(y.shape[0], -1)
+            if target_bias is not None:
+                target_bias = target_bias[y.long()]
             y = torch.arange(y.shape[0], dtype=torch.int64, device=dev)
         else:
             targets = tw[self.target_offset:]
-        loss = F_.softmax_scores_loss(anchors, targets, y, scale)
+        loss = F_.softmax_scores_loss(anchors, targets, y, scale, sim=self.similarity, bias=target_bias)
         return F_.reduce_sample_losses(loss, y, targets.shape[0], reduction)
 
 

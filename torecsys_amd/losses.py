@@ -110,19 +110,24 @@ class TripletLoss(PairwiseRankingLoss):
 
 class FullSoftmaxLoss(nn.Module):
     """Softmax cross-entropy of anchors (B, E) against every row of targets (Vt, E) (functional.softmax_scores_loss; not in
-    the reference): ``forward(anchors, targets, labels)`` for callers with their own towers; labels (B,) int, -1 ignored.
-    ``reduction``: 'mean' (over the non-ignored samples) | 'sum' | 'none'.  In batch: targets = the positives' rows,
-    labels = arange(B)."""
+    the reference): ``forward(anchors, targets, labels, bias=None)`` for callers with their own towers; labels (B,) int,
+    -1 ignored.  ``reduction``: 'mean' (over the non-ignored samples) | 'sum' | 'none'.  ``similarity``: 'dot' | 'cosine'
+    (``scale`` = 1 / temperature); ``bias`` (Vt,) fp32 per-target logit bias, e.g. -log_q.  In batch: targets = the
+    positives' rows, labels = arange(B)."""
 
-    def __init__(self, scale: float = 1.0, reduction: str = 'mean'):
+    def __init__(self, scale: float = 1.0, reduction: str = 'mean', similarity: str = 'dot'):
         super().__init__()
+        if similarity not in F_.PAIR_SIMS:
+            raise ValueError(f"torecsys_amd.losses.FullSoftmaxLoss: similarity 'dot' or 'cosine', got {similarity!r}")
+        self.similarity = similarity
         if reduction not in ('mean', 'sum', 'none'):
             raise ValueError(f"torecsys_amd.losses.FullSoftmaxLoss: reduction 'mean', 'sum' or 'none', got {reduction!r}")
         self.scale = scale
         self.reduction = reduction
 
-    def forward(self, anchors: torch.Tensor, targets: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        loss = F_.softmax_scores_loss(anchors, targets, labels, self.scale)
+    def forward(self, anchors: torch.Tensor, targets: torch.Tensor, labels: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        loss = F_.softmax_scores_loss(anchors, targets, labels, self.scale, sim=self.similarity, bias=bias)
         return F_.reduce_sample_losses(loss, labels, targets.shape[0], self.reduction)
 
 
