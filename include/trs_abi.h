@@ -1405,6 +1405,33 @@ int trs_topk_scores_q8(const void* anchor_table, int64_t Va, const void* anchor_
                        int32_t X, float* out_val, int64_t* out_idx, void* workspace, size_t ws_bytes, int32_t* err_flag,
                        trs_stream_t stream);
 
+/* ---- rank of held-out targets over a whole target table (csrc/target_rank.hip; not in the reference) ------------------
+ * Anchors, tables, target range, similarity and exclusion list as trs_topk_scores.  labels (B, P) of label_dtype, ids
+ * relative to target_lo, 1 <= P <= 16.  With l = labels[b, p]:
+ *   ranks[b, p] = #{ j in [0, Vt) : j != l, j not in exclude[b, :], (score[b, j], -j) > (score[b, l], -l) }
+ * the 0-based position of l among the targets of sample b by score descending and, among equal scores, id ascending:
+ * what trs_topk_scores with the same exclude would return l at, were k unbounded.  label_scores[b, p] = score[b, l], the
+ * bits trs_topk_scores returns for that pair.  ranks (B, P) int64, label_scores (B, P) fp32.
+ * A negative label is padding: rank -1, score -inf.  A label >= Vt: the same, and *err_flag is raised.  A label that
+ * stands in its own exclusion list is still ranked; the other labels of the sample count like any target.  Negative
+ * entries of exclude and ids >= Vt are ignored, an id listed twice is excluded once.  A NaN score sorts in front of
+ * nothing and nothing sorts in front of it.  An anchor id outside [0, Va) reads as a zero row and raises *err_flag.
+ * Two launches: the scores of every sample against its own P + X listed rows (which decide the thresholds and what the
+ * exclusion list takes away), then the count over the target range cut into S ranges, S a pure function of (B, Vt);
+ * the ranges' counts meet in ranks by integer atomics, so the result does not depend on their order and
+ * trs_target_ranks_workspace_bytes is 0 at every shape (workspace may be NULL).  No host read-back, no allocation:
+ * capturable.
+ * Vt < 2^31; rows of whole 16-byte vectors, E <= 256 (TRS_ESHAPE); 16-byte aligned tables (TRS_EALIGN); X <= 1024 (the
+ * listed ids of a sample are staged on chip, and finding repeated ids is quadratic in X).  B == 0 returns TRS_OK and
+ * touches nothing.  Errors, all before any launch: NULL pointer, bad sim, bad index / label / exclude dtype, P or X out
+ * of range, bad size TRS_EINVAL; value dtype TRS_EDTYPE.                                                               */
+size_t trs_target_ranks_workspace_bytes(int64_t B, int64_t Vt, int32_t P);
+int trs_target_ranks(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype, int64_t anchor_offset,
+                     int64_t B, const void* target_table, int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype,
+                     int32_t sim, const void* labels, int32_t label_dtype, int32_t P, const void* exclude,
+                     int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes,
+                     int32_t* err_flag, trs_stream_t stream);
+
 /* ---- softmax cross-entropy against a whole target table (csrc/softmax_loss.hip; not in the reference) -----------------
  * anchors (B, E) and targets (Vt, E), contiguous rows of one value dtype; labels (B) of label_dtype (TRS_I64 | TRS_I32):
  *   z[b, j] = scale * sum_e A[b, e] T[j, e]      (products of table-dtype operands, fp32 accumulation on the matrix cores)

@@ -45,7 +45,10 @@ that recomputes each chunk's logits in its backward; 1 M rows and in batch, bf16
 --sim cosine and / or --bias time the cosine / per-target-bias kernels against the same composition over F.normalize'd
 operands with the bias added per chunk.
 --what topk [--k 100] [--sim dot|cosine] [--budget 4]: top-k retrieval over a 1 M-row table against the chunked ATen
-composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk)."""
+composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk).
+--what targetrank [--k 100] [--sim dot|cosine] [--budget 4]: rank of one held-out target per anchor over a 1 M-row table
+against the chunked ATen composition (matmul per chunk, compare, sum) and against topk_scores at k, with and without 100
+excluded ids (own inputs, see bench_targetrank)."""
 import argparse
 import os
 import sys
@@ -1458,6 +1461,91 @@ def bench_topk(a):
         del tw, aw, up
 
 
+def bench_targetrank(a):
+    """functional.target_ranks (csrc/target_rank.hip), P = 1, against the two routes that exist without it: (a) the chunked
+    ATen composition -- gather the anchors, the label's score as a row product, ``matmul`` against table chunks sized so
+    that a chunk's (B, chunk) scores stay within 1 GiB of fp32, compare with the label's score, sum (cosine: anchors and
+    chunk rows normalised first; with ``exclude`` the listed rows' scores are gathered and taken off again); it ignores
+    the id rule among equal scores and multiplies in the table's dtype, so it is a yardstick for time, and the median and
+    largest difference between the two ranks are printed once per shape; (b) ``topk_scores`` at k = --k, which answers rank < k only.
+    Shapes, inputs and the race are those of --what topk: B in {256, 4 096, 65 536} against a 1 M-row table, E = 64, bf16
+    and fp32, uniform random rows; B = 4 096 with ``exclude`` of X = 100; B = 4 096 on the table whose scores increase
+    along the rows.  The candidates take turns launch by launch after 2 warm-ups each; a shape stops after 20 launches of
+    each or once --budget seconds of timed work have passed, with at least 3.  The last line of a dtype times the list
+    kernel nearly alone (a 256-row target range, the excluded ids folded into it) with and without the 100 excluded ids."""
+    dev = torch.device("cuda:0")
+    V, E, k, sim = a.V, a.E, a.k, a.sim
+    g = torch.Generator(device=dev).manual_seed(77)
+
+    def comp(aw, idx, tw, y, ex=None):
+        q = aw[idx]
+        if sim == "cosine":
+            q = torch.nn.functional.normalize(q.float(), dim=1, eps=1e-8).to(q.dtype)
+
+        def rows(ids):
+            t = tw[ids]
+            return torch.nn.functional.normalize(t.float(), dim=-1, eps=1e-8).to(t.dtype) if sim == "cosine" else t
+
+        sl = (q * rows(y)).sum(dim=1, keepdim=True)
+        chunk = max(4096, min(V, (1 << 28) // idx.shape[0]))
+        cnt = torch.zeros(idx.shape[0], dtype=torch.int64, device=dev)
+        for lo in range(0, V, chunk):
+            cnt += (q @ rows(slice(lo, lo + chunk)).T > sl).sum(dim=1)
+        if ex is not None:
+            cnt -= (((q[:, None, :] * rows(ex.clamp_min(0))).sum(dim=2) > sl) & (ex >= 0)).sum(dim=1)
+        return cnt
+
+    def race(fns):
+        for f in fns.values():
+            for _ in range(2):
+                f()
+        torch.cuda.synchronize()
+        ts, spent = {n: [] for n in fns}, 0.0
+        while len(ts["rank"]) < 3 or (len(ts["rank"]) < 20 and spent < a.budget):
+            for name, f in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1) * 1e-3)
+                spent += ts[name][-1]
+        return {n: sorted(v) for n, v in ts.items()}
+
+    def show(tag, B, aw, idx, tw, ex=None):
+        y = torch.randint(0, V, (B,), generator=g, device=dev)
+        ts = race({"rank": lambda: F_.target_ranks(aw, idx, tw, y, sim=sim, exclude=ex),
+                   "aten": lambda: comp(aw, idx, tw, y, ex),
+                   "topk": lambda: F_.topk_scores(aw, idx, tw, k, sim=sim, exclude=ex)})
+        med = {n: v[len(v) // 2] for n, v in ts.items()}
+        for n, v in ts.items():
+            print(f"{tag:34s} {n:5s} med {med[n] * 1e3:9.3f} ms  spread {v[0] * 1e3:9.3f} .. {v[-1] * 1e3:9.3f} ms "
+                  f"({len(v)} launches)  {2.0 * B * V * E / med[n] / 1e12:7.1f} TFLOP/s", flush=True)
+        off = (F_.target_ranks(aw, idx, tw, y, sim=sim, exclude=ex)[0][:, 0] - comp(aw, idx, tw, y, ex)).abs().double()
+        print(f"{tag:34s} aten / rank = {med['aten'] / med['rank']:.2f}   topk / rank = {med['topk'] / med['rank']:.2f}   "
+              f"|rank - the composition's|: median {float(off.median()):.0f}, max {float(off.max()):.0f}", flush=True)
+
+    print(f"targetrank: V = {V}, E = {E}, P = 1, topk at k = {k}, sim = {sim}")
+    for dt in (torch.bfloat16, torch.float32):
+        tw = torch.randn(V, E, generator=g, device=dev).to(dt)
+        aw = torch.randn(100_000, E, generator=g, device=dev).to(dt)
+        for B in (256, 4096, 65536):
+            idx = torch.randint(0, aw.shape[0], (B,), generator=g, device=dev)
+            show(f"{str(dt)[6:]} B={B}", B, aw, idx, tw)
+        idx = torch.randint(0, aw.shape[0], (4096,), generator=g, device=dev)
+        ex = torch.randint(0, V, (4096, 100), generator=g, device=dev)
+        show(f"{str(dt)[6:]} B=4096 exclude X=100", 4096, aw, idx, tw, ex)
+        y = torch.randint(0, 256, (4096,), generator=g, device=dev)
+        ex = ex % 256       # inside the range: ids past it are dropped before any work
+        ts = race({"rank": lambda: F_.target_ranks(aw, idx, tw, y, target_hi=256, sim=sim, exclude=ex),
+                   "plain": lambda: F_.target_ranks(aw, idx, tw, y, target_hi=256, sim=sim)})
+        print(f"{str(dt)[6:]} B=4096 against 256 rows only: X=100 med {ts['rank'][len(ts['rank']) // 2] * 1e3:.3f} ms, no "
+              f"exclusion med {ts['plain'][len(ts['plain']) // 2] * 1e3:.3f} ms", flush=True)
+        up = (torch.arange(V, device=dev, dtype=torch.float32) / V).unsqueeze(1).expand(V, E).to(dt).contiguous()
+        show(f"{str(dt)[6:]} B=4096 increasing scores", 4096, aw.abs(), idx, up)
+        del tw, aw, up
+
+
 def bench_softmax(a):
     """functional.softmax_scores_loss (csrc/softmax_loss.hip) against the only ATen composition that runs at these shapes:
     one autograd.Function over target chunks sized so that a chunk's (B, chunk) fp32 logits stay within 1 GiB -- forward:
@@ -1734,6 +1822,8 @@ def main():
     a = ap.parse_args()
     if a.what == "topk":         # own inputs: not part of "all"
         return bench_topk_q8(a) if a.q8 else bench_topk(a)
+    if a.what == "targetrank":   # own inputs: not part of "all"
+        return bench_targetrank(a)
     if a.what == "softmax":      # own inputs: not part of "all"
         return bench_softmax(a)
     if a.what == "q8":           # own inputs: not part of "all"

@@ -2,7 +2,7 @@
 CTR models: drop-in ``nn.Module``s (same names / signatures / tensor names / state_dict keys as
 ``torecsys.inputs`` and ``torecsys.layers``) over hand-written HIP kernels behind a C ABI
 (``include/trs_abi.h`` -> ``torecsys_amd/libtrs_hip.so``).  No CPU path: modules raise off-GPU."""
-from . import functional, fused, graph, inputs, layers, losses, optim, quant, staging  # noqa: F401
+from . import functional, fused, graph, inputs, layers, losses, metrics, optim, quant, staging  # noqa: F401
 from .inputs import (RaggedListIndicesEmbedding, RaggedMultiListIndicesEmbedding,  # noqa: F401
                      SequenceIndicesEmbedding)
 from .layers import DynamicRoutingLayer  # noqa: F401

@@ -30,6 +30,8 @@ FILE_FLAGS = {"cin_mfma.hip": ["-fno-slp-vectorize"], "cross_mfma.hip": ["-fno-s
               "q8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the cosine scalings between the MFMAs and the selection: single multiplies, as above
               "topk.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the same scalings, which must give the bits topk.hip gives
+              "target_rank.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the running max / sum and the probability weights between the two MFMAs: single fp32 operations too
               "softmax_loss.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 

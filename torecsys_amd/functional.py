@@ -4283,6 +4283,78 @@ def topk_scores_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tenso
                      target_lo, target_hi, E, code, k, exclude)
 
 
+TARGET_RANKS_MAX_P, TARGET_RANKS_MAX_X = 16, 1024
+
+
+def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_weight: Optional[torch.Tensor],
+                 labels: torch.Tensor, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None,
+                 sim="dot", exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The position every label takes among ALL rows of ``target_weight[target_lo:target_hi]`` for its anchor, in one HIP
+    pass over the table (csrc/target_rank.hip): MFMA scores counted against the label's own score next to the
+    accumulators, no (B, Vt) block, no selection.  What hit rate@k, NDCG@k, MRR and MAP are computed from
+    (``torecsys_amd.metrics``).  Anchors, tables, range, ``sim`` and ``exclude`` are those of ``topk_scores``; ``labels``
+    (B, P) or (B,) ids relative to ``target_lo``, 1 <= P <= 16.  Returns ``ranks (B, P)`` int64 and ``label_scores (B, P)``
+    fp32: ``ranks[b, p]`` is the number of targets that are neither the label nor in ``exclude[b]`` and sort in front of
+    it, by score descending and id ascending among equal scores -- the index ``topk_scores(..., exclude=exclude)`` returns
+    that id at, were k unbounded; the score is the same bits.  A negative label is padding (rank -1, score -inf); a label
+    past the range gives the same and raises the index flag; a label listed in its own ``exclude`` row is still ranked,
+    and the other labels of a sample count like any target.  ``exclude`` (B, X <= 1024): negative entries and ids past the
+    range are ignored, a repeated id is excluded once.  bf16 or fp32 contiguous tables of one dtype, rows of whole
+    16-byte vectors, E <= 256.  No gradient, no host read-back; an anchor id outside its table scores as a zero row and
+    raises the index flag."""
+    op = "target_ranks"
+    code = _sim_code(sim)
+    aw = anchor_weight.detach()
+    tw = aw if target_weight is None or target_weight is anchor_weight else target_weight.detach()
+    if aw.dim() != 2 or tw.dim() != 2 or aw.shape[1] != tw.shape[1]:
+        raise ValueError(f"{op}: two (V, E) tables of one width expected, got {tuple(aw.shape)} and {tuple(tw.shape)}")
+    if aw.dtype not in (torch.float32, torch.bfloat16) or tw.dtype != aw.dtype:
+        raise TypeError(f"{op}: bf16 or fp32 tables of one dtype expected, got {aw.dtype} and {tw.dtype}")
+    E = aw.shape[1]
+    if E < 1 or E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
+        raise NotImplementedError(f"{op}: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} of "
+                                  f"{aw.dtype}")
+    lo = int(target_lo)
+    hi = tw.shape[0] if target_hi is None else int(target_hi)
+    if not 0 <= lo < hi <= tw.shape[0]:
+        raise ValueError(f"{op}: target range [{lo}, {hi}) is not inside the {tw.shape[0]} target rows")
+    a_idx = None if anchor_idx is None else _as_index(anchor_idx).reshape(-1)
+    B = aw.shape[0] if a_idx is None else a_idx.shape[0]
+    y = _as_index(labels)
+    if y.dim() == 1:
+        y = y.unsqueeze(1)
+    if y.dim() != 2 or y.shape[0] != B or not 1 <= y.shape[1] <= TARGET_RANKS_MAX_P:
+        raise ValueError(f"{op}: labels ({B},) or ({B}, 1 <= P <= {TARGET_RANKS_MAX_P}) expected, got {tuple(labels.shape)}")
+    y = y.contiguous()
+    P = y.shape[1]
+    ex = None
+    if exclude is not None:
+        ex = _as_index(exclude)
+        if ex.dim() != 2 or ex.shape[0] != B or ex.shape[1] < 1:
+            raise ValueError(f"{op}: exclude ({B}, X >= 1) expected, got {tuple(ex.shape)}")
+        if ex.shape[1] > TARGET_RANKS_MAX_X:
+            raise NotImplementedError(f"{op}: at most {TARGET_RANKS_MAX_X} excluded ids per sample (they are staged on "
+                                      f"chip), got X = {ex.shape[1]}")
+        ex = ex.contiguous()
+    for name, t in (("anchor_weight", aw), ("target_weight", tw)):
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous, got strides {tuple(t.stride())}")
+    dev = require_device(aw, a_idx, tw, y, ex)
+    ranks = torch.empty(B, P, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, P, dtype=torch.float32, device=dev)
+    if B == 0:
+        return ranks, scores
+    ws_bytes = size_query("trs_target_ranks_workspace_bytes", B, hi - lo, P)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    flag = _ErrFlag(dev)
+    call("trs_target_ranks", ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
+         int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, ptr(y), index_dtype_code(y), P, ptr(ex),
+         index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(ranks), ptr(scores),
+         ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
+    flag.check(op)
+    return ranks, scores
+
+
 class _SoftmaxScoresLoss(Function):
     """per-sample softmax cross-entropy against every target row; saves the operands and lse (B), recomputes the scores"""
 

@@ -140,6 +140,16 @@ class EmbeddingPairScorer(nn.Module):
         return F_.topk_scores(self.anchor.weight, anchor_idx, tw, k, anchor_offset=self.anchor_offset,
                               target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
 
+    def rank(self, anchor_idx: torch.Tensor, positive_idx: torch.Tensor, exclude: Optional[torch.Tensor] = None):
+        """The position of every held-out target among the whole target table (functional.target_ranks): ``(ranks (B, P)
+        int64, label_scores (B, P) fp32)`` for ``positive_idx`` (B,) or (B, P <= 16), ids as ``forward`` / ``topk`` take
+        and return them, negative entries padding (rank -1).  ``ranks[b, p]`` is the index ``topk`` with the same
+        ``exclude`` would return that id at, were k unbounded; ``torecsys_amd.metrics`` turns it into hit rate@k, NDCG@k,
+        MRR and MAP.  A shared table is ranked from ``target_offset`` to its end."""
+        tw = None if self.target is None else self.target.weight
+        return F_.target_ranks(self.anchor.weight, anchor_idx, tw, positive_idx, anchor_offset=self.anchor_offset,
+                               target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
+
     def softmax_loss(self, anchor_idx: torch.Tensor, positive_idx: torch.Tensor, scale: float = 1.0,
                      reduction: str = 'mean', in_batch: bool = False,
                      target_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
