@@ -1432,6 +1432,25 @@ int trs_target_ranks(const void* anchor_table, int64_t Va, const void* anchor_id
                      int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes,
                      int32_t* err_flag, trs_stream_t stream);
 
+/* trs_target_ranks over a Q8 target table, as trs_topk_scores_q8 stands beside trs_topk_scores: target_q holds at least
+ * target_hi rows of trs_q8_row_bytes(E) bytes, the anchors stay float (anchor_table (Va, E) of anchor_dtype, TRS_F32 |
+ * TRS_BF16, through anchor_idx or as a (B, E) query matrix).  Neither a float copy of the table nor a (B, Vt) block is
+ * formed.  The score is that entry's, in both launches:
+ *   d = sum_e a[e] c[e]  (fp32 accumulation),  sa = sum_e a[e]  (fp32, in order),  score = d * scale + sa * bias
+ * (each product and the sum rounded once); cosine: score * (1 / max(|a|, eps)) * (1 / max(|x|, eps)), |x| the fp32 norm of
+ * the dequantized row, summed as squares of c * scale + bias.  A pair scores to the same bits in the list launch, in the
+ * count launch and in trs_topk_scores_q8 (conversion, matrix instruction and k order, summation order of sa and |x|,
+ * shape of the expression), so ranks[b, p] is the index trs_topk_scores_q8 with the same exclude would return the label
+ * at, were k unbounded, and label_scores[b, p] the value it returns there: the position in the table that is served,
+ * which the rank over a dequantized float copy is not.  Labels, padding, exclusion, the zero row of an anchor id outside
+ * [0, Va), *err_flag, the split, trs_target_ranks_workspace_bytes (0; workspace may be NULL), every limit and every error
+ * code are those of trs_target_ranks; E * sizeof(anchor_dtype) must be a multiple of 16 (so E is a multiple of 4).      */
+int trs_target_ranks_q8(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                        int64_t anchor_offset, int64_t B, const void* target_q, int64_t target_lo, int64_t target_hi,
+                        int32_t E, int32_t anchor_dtype, int32_t sim, const void* labels, int32_t label_dtype, int32_t P,
+                        const void* exclude, int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores,
+                        void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+
 /* ---- softmax cross-entropy against a whole target table (csrc/softmax_loss.hip; not in the reference) -----------------
  * anchors (B, E) and targets (Vt, E), contiguous rows of one value dtype; labels (B) of label_dtype (TRS_I64 | TRS_I32):
  *   z[b, j] = scale * sum_e A[b, e] T[j, e]      (products of table-dtype operands, fp32 accumulation on the matrix cores)

@@ -48,7 +48,10 @@ operands with the bias added per chunk.
 composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own inputs, see bench_topk).
 --what targetrank [--k 100] [--sim dot|cosine] [--budget 4]: rank of one held-out target per anchor over a 1 M-row table
 against the chunked ATen composition (matmul per chunk, compare, sum) and against topk_scores at k, with and without 100
-excluded ids (own inputs, see bench_targetrank)."""
+excluded ids (own inputs, see bench_targetrank).
+--what targetrank --q8 [--k 100] [--sim dot|cosine] [--budget 4]: the same rank over a 1 M-row Q8 table: the float kernel on
+a bf16 copy held in memory, dequantize + float kernel per call, the Q8 kernels, and topk_scores_q8 at k; times and peak
+memory (see bench_targetrank_q8)."""
 import argparse
 import os
 import sys
@@ -1652,14 +1655,46 @@ def bench_softmax(a):
             del q, t
 
 
+def _race_legs(a, tag, B, V, E, fns):
+    """The legs of ``fns`` (name -> call) take turns launch by launch after 2 warm-ups each, up to 20 launches or --budget
+    seconds of timed work (at least 3); prints median, spread and the peak device memory of one call above what is
+    resident (torch's allocator statistics, reset before it); returns the medians."""
+    legs, peak = list(fns), {}
+    for n in legs:
+        for _ in range(2):
+            fns[n]()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fns[n]()
+        torch.cuda.synchronize()
+        peak[n] = torch.cuda.max_memory_allocated() - base
+    ts, spent = {n: [] for n in legs}, 0.0
+    while len(ts[legs[0]]) < 3 or (len(ts[legs[0]]) < 20 and spent < a.budget):
+        for n in legs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fns[n]()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[n].append(e0.elapsed_time(e1) * 1e-3)
+            spent += ts[n][-1]
+    med = {}
+    for n in legs:
+        v = sorted(ts[n])
+        med[n] = v[len(v) // 2]
+        print(f"{tag:30s} {n:11s} med {med[n] * 1e3:9.3f} ms  spread {v[0] * 1e3:9.3f} .. {v[-1] * 1e3:9.3f} ms ({len(v)} "
+              f"launches)  {2.0 * B * V * E / med[n] / 1e12:7.1f} TFLOP/s  peak above resident {peak[n] / 1e6:8.1f} MB",
+              flush=True)
+    return med
+
+
 def bench_topk_q8(a):
     """functional.topk_scores_q8 over a 1 M-row Q8 table (E = 64, bf16 anchors as a (B, E) query matrix) against the two
     routes that exist without it: (a) ``topk_scores`` on the bf16 table held in memory -- the float kernel, the speed
     yardstick; (b) ``dequantize_rows`` of the whole table + ``topk_scores`` per call -- what a Q8 user can do otherwise;
     (c) the Q8 kernel.  B in {256, 4 096, 65 536}, uniform random rows, then B = 4 096 against a table whose scores increase
-    along the rows.  The three take turns launch by launch after 2 warm-ups each, up to 20 launches or --budget seconds of
-    timed work per shape (at least 3); median and spread.  Peak device memory of (b) and (c) above what is resident
-    (tables, queries) comes from torch's allocator statistics, reset before one call of each."""
+    along the rows.  Race and peak memory: ``_race_legs``."""
     from torecsys_amd import quant
     dev = torch.device("cuda:0")
     V, E, k, sim = a.V, a.E, a.k, a.sim
@@ -1667,36 +1702,10 @@ def bench_topk_q8(a):
     legs = ("a bf16", "b deq+bf16", "c q8")
 
     def show(tag, B, q, tw, tq):
-        fns = {legs[0]: lambda: F_.topk_scores(q, None, tw, k, sim=sim),
-               legs[1]: lambda: F_.topk_scores(q, None, quant.dequantize_rows(tq, E, torch.bfloat16), k, sim=sim),
-               legs[2]: lambda: F_.topk_scores_q8(q, None, tq, E, k, sim=sim)}
-        peak = {}
-        for n in legs:
-            for _ in range(2):
-                fns[n]()
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated()
-            torch.cuda.reset_peak_memory_stats()
-            fns[n]()
-            torch.cuda.synchronize()
-            peak[n] = torch.cuda.max_memory_allocated() - base
-        ts, spent = {n: [] for n in legs}, 0.0
-        while len(ts[legs[0]]) < 3 or (len(ts[legs[0]]) < 20 and spent < a.budget):
-            for n in legs:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fns[n]()
-                e1.record()
-                torch.cuda.synchronize()
-                ts[n].append(e0.elapsed_time(e1) * 1e-3)
-                spent += ts[n][-1]
-        med = {}
-        for n in legs:
-            v = sorted(ts[n])
-            med[n] = v[len(v) // 2]
-            print(f"{tag:30s} {n:11s} med {med[n] * 1e3:9.3f} ms  spread {v[0] * 1e3:9.3f} .. {v[-1] * 1e3:9.3f} ms ({len(v)} "
-                  f"launches)  {2.0 * B * V * E / med[n] / 1e12:7.1f} TFLOP/s  peak above resident {peak[n] / 1e6:8.1f} MB",
-                  flush=True)
+        med = _race_legs(a, tag, B, V, E, {
+            legs[0]: lambda: F_.topk_scores(q, None, tw, k, sim=sim),
+            legs[1]: lambda: F_.topk_scores(q, None, quant.dequantize_rows(tq, E, torch.bfloat16), k, sim=sim),
+            legs[2]: lambda: F_.topk_scores_q8(q, None, tq, E, k, sim=sim)})
         print(f"{tag:30s} c / a = {med[legs[2]] / med[legs[0]]:.2f}   c / b = {med[legs[2]] / med[legs[1]]:.2f}", flush=True)
 
     print(f"topk q8: V = {V}, E = {E}, k = {k}, sim = {sim}, Q8 table {V * quant.q8_row_bytes(E) / 1e6:.0f} MB, bf16 table "
@@ -1709,6 +1718,36 @@ def bench_topk_q8(a):
     tq = quant.quantize_rows(up)
     tw = quant.dequantize_rows(tq, E, torch.bfloat16)
     show("B=4096 increasing scores", 4096, torch.randn(4096, E, generator=g, device=dev).abs().bfloat16(), tw, tq)
+
+
+def bench_targetrank_q8(a):
+    """functional.target_ranks_q8, P = 1, over a 1 M-row Q8 table (E = 64, bf16 anchors as a (B, E) query matrix), four legs:
+    (a) ``target_ranks`` on the bf16 copy held in memory -- the float kernel, the speed yardstick (it ranks another
+    table); (b) ``dequantize_rows`` of the whole table + ``target_ranks`` per call; (c) the Q8 kernels; (d)
+    ``topk_scores_q8`` at k = --k, the only route to served positions without (c), which answers rank < k only.  B in
+    {256, 4 096, 65 536}, uniform random rows and labels.  Race and peak memory: ``_race_legs``; the share of labels whose
+    rank differs between (a) and (c) is printed once per shape."""
+    from torecsys_amd import quant
+    dev = torch.device("cuda:0")
+    V, E, k, sim = a.V, a.E, a.k, a.sim
+    g = torch.Generator(device=dev).manual_seed(77)
+    legs = ("a bf16", "b deq+bf16", "c q8", "d topk q8")
+    print(f"targetrank q8: V = {V}, E = {E}, P = 1, topk at k = {k}, sim = {sim}, Q8 table {V * quant.q8_row_bytes(E) / 1e6:.0f} "
+          f"MB, bf16 table {V * E * 2 / 1e6:.0f} MB")
+    tq = quant.quantize_rows(torch.randn(V, E, generator=g, device=dev))
+    tw = quant.dequantize_rows(tq, E, torch.bfloat16)
+    for B in (256, 4096, 65536):
+        q = torch.randn(B, E, generator=g, device=dev).bfloat16()
+        y = torch.randint(0, V, (B,), generator=g, device=dev)
+        tag = f"B={B}"
+        med = _race_legs(a, tag, B, V, E, {
+            legs[0]: lambda: F_.target_ranks(q, None, tw, y, sim=sim),
+            legs[1]: lambda: F_.target_ranks(q, None, quant.dequantize_rows(tq, E, torch.bfloat16), y, sim=sim),
+            legs[2]: lambda: F_.target_ranks_q8(q, None, tq, E, y, sim=sim),
+            legs[3]: lambda: F_.topk_scores_q8(q, None, tq, E, k, sim=sim)})
+        moved = (F_.target_ranks(q, None, tw, y, sim=sim)[0] != F_.target_ranks_q8(q, None, tq, E, y, sim=sim)[0]).double().mean()
+        print(f"{tag:30s} c / a = {med[legs[2]] / med[legs[0]]:.2f}   c / b = {med[legs[2]] / med[legs[1]]:.2f}   c / d = "
+              f"{med[legs[2]] / med[legs[3]]:.2f}   ranks that differ between a and c: {float(moved):.3f}", flush=True)
 
 
 def bench_bagshard(a):
@@ -1818,12 +1857,12 @@ def main():
     ap.add_argument("--rows", default="1000000,32000000", help="q8: table sizes V to run")
     ap.add_argument("--k", type=int, default=100, help="topk: items returned per anchor")
     ap.add_argument("--budget", type=float, default=4.0, help="topk: seconds of timed launches per shape")
-    ap.add_argument("--q8", action="store_true", help="topk: the Q8-table leg (bf16 table / dequantize + bf16 / Q8 kernel)")
+    ap.add_argument("--q8", action="store_true", help="topk, targetrank: the Q8-table legs (bf16 table / dequantize + bf16 / Q8 kernel)")
     a = ap.parse_args()
     if a.what == "topk":         # own inputs: not part of "all"
         return bench_topk_q8(a) if a.q8 else bench_topk(a)
     if a.what == "targetrank":   # own inputs: not part of "all"
-        return bench_targetrank(a)
+        return bench_targetrank_q8(a) if a.q8 else bench_targetrank(a)
     if a.what == "softmax":      # own inputs: not part of "all"
         return bench_softmax(a)
     if a.what == "q8":           # own inputs: not part of "all"

@@ -73,4 +73,17 @@ __device__ __forceinline__ float q8_elem(const uint8_t* __restrict__ q, int64_t 
   return (float)row[e] * q8_f32_at(row + E) + q8_f32_at(row + E + 4);
 }
 
+// ---- Q8 rows as matrix-core operands (topk.hip, target_rank.hip)
+// the 4 codes of a word as fp32 (v_cvt_f32_ubyte<k>) and as bf16: a code has 8 significant bits, its fp32 form ends in 16
+// zero bits and the high half IS the bf16
+__device__ __forceinline__ uint4 tk_codes_f32(uint32_t w) {
+  return make_uint4(__float_as_uint((float)(w & 0xffu)), __float_as_uint((float)((w >> 8) & 0xffu)),
+                    __float_as_uint((float)((w >> 16) & 0xffu)), __float_as_uint((float)(w >> 24)));
+}
+__device__ __forceinline__ uint2 tk_codes_bf16(uint32_t w) {
+  const uint4 f = tk_codes_f32(w);
+  return make_uint2((f.x >> 16) | f.y, (f.z >> 16) | f.w);
+}
+__device__ __forceinline__ uint32_t tk_word(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
 }  // namespace trs

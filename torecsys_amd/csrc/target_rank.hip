@@ -41,9 +41,32 @@
 // (bf16 E <= 64) take 64 x 64 in 49.5 KiB, rows up to 256 bytes 32 x 64; wider rows take the first of (32, 64) and (16, 32)
 // that fits 160 KiB.  Thresholds and counters are registers for P = 1 and P <= 4; above that the thresholds sit in LDS
 // (p-major) and the counters stay registers, with AR <= 32.  The arrangements have not been timed against each other.
+//
+// Q8 targets (template parameter Q8 of both kernels; trs_target_ranks_q8).  The target table is row-wise int8
+// (q8_common.hpp: E codes, fp32 scale, fp32 bias, S = round_up(E + 8, 16) bytes a row) and the score is topk.hip's factored
+//   d[b, j] = sum_e a_b[e] c_j[e]  (MFMA; the codes 0..255 are exact in bf16 and fp32)      sa[b] = sum_e a_b[e]  (fp32)
+//   score   = d * scale_j + sa * bias_j                                  cosine: * ainv[b] * tinv[j], tinv from the sum of
+// squares of c * scale + bias -- in the list kernel, in the streaming kernel and in topk_scores_q8 the same bits (code
+// conversion, MFMA and k order, summation order of sa and the row norm, product, product, sum, each rounded: none of the
+// three is compiled with contraction), through one function each for the staging of a Q8 vector, sa, the row norm and the
+// epilogue.  So the rank is the position at which topk_scores_q8 serves the id.  Streaming kernel: split, arrangements,
+// anchor gather, swizzle, k-loop, count and atomics are the float kernel's; LDS-DMA cannot convert, so a tile goes through
+// registers as in topk.hip: a thread owns up to tr_q8_units 16-byte vectors of the tile's Q8 rows (tails included,
+// consecutive lanes consecutive vectors), loads those of tile t + 1 before the k-loop of tile t and behind the issued
+// MFMAs converts the codes to the anchor dtype -- each code once per workgroup -- into swizzled operand chunks of the other
+// buffer; the vectors that hold scale and bias drop them into two per-tile LDS arrays next to tinv, sa sits next to ainv
+// (2 x 2 x TR + NA more floats); chunks behind the last converted one are zeroed once; rows past the end of a range stage
+// as code 0, scale 0, bias 0 and are set to -inf like any.  List kernel: the 16 listed rows of a group are gathered from
+// the Q8 table vector by vector into the same operand chunks, scale, bias and tinv per row.
+// Registers (compiler's report, no spill anywhere): the unit count is sized by arrangement, because with 5 units 64 x 64
+// took 272 (bf16) / 291 (fp32) registers at P = 1, one wave per SIMD; with the 2 units its rows of at most 192 bytes need
+// it takes 235 / 247 and keeps two, inside 80 KiB as before (bf16 E = 64: 51.5 KiB).  At P <= 4 the Q8 64 x 64 takes 287 /
+// 303 registers, so Q8 with 2 .. 4 labels starts at 32 x 64 (217 / 231, two waves); 32 x 64 at P = 1 takes 190 / 204, 16 x 32
+// at most 111.  Like the float ones, the Q8 arrangements have not been timed against each other.
 #include <algorithm>
 
 #include "lds_dma.hpp"
+#include "q8_common.hpp"
 
 namespace trs {
 
@@ -54,6 +77,9 @@ constexpr int TR_DOT = 0, TR_COS = 1;
 constexpr float TR_COS_EPS = 1e-8f;      // rank.hip's COS_EPS
 constexpr int TR_MAX_P = 16, TR_MAX_X = 1024, TR_MAX_E = 256, TR_MAX_SPLITS = 64;
 constexpr size_t TR_MAX_LDS = 160 * 1024, TR_HALF_LDS = 80 * 1024;
+// 16-byte vectors of a Q8 tile a thread owns, by arrangement (the rows the arrangement is taken for bound the vectors of a
+// row): 64 x 64 rows up to 192 bytes, 7 vectors, 64 x 7 / 256 threads; 32 x 64 up to 17 vectors; 16 x 32 up to 17
+constexpr int tr_q8_units(int AR, int TR) { return AR == 64 ? 2 : TR == 64 ? 5 : 3; }
 
 struct RankArgs {
   const char* a_table;
@@ -71,6 +97,7 @@ struct RankArgs {
   int sw_shift, sw_mask;   // g(r) = (r >> sw_shift) & sw_mask
   int sim;
   bool idx64, lab64, excl64, dma;
+  int E, q_stride, q_nv;   // Q8 targets: columns, bytes of a row (S) and its 16-byte vectors
 };
 
 __device__ __forceinline__ void tr_wave_sync() {
@@ -127,6 +154,96 @@ __device__ __forceinline__ float tr_row_inv(const char* rows, int r, const RankA
   return 1.f / fmaxf(sqrtf(s), TR_COS_EPS);
 }
 
+// ---- Q8 targets.  Every function below is called by both kernels and repeats topk.hip's arithmetic operation for
+// operation (tk_row_sum, tk_q8_row_sq, q8_store, its epilogue), so a pair scores to the same bits in all three places.
+// sa of the factored score: the sum of LDS row r (its real chunks, in order), fp32
+template <typename T>
+__device__ __forceinline__ float tr_row_sum(const char* rows, int r, const RankArgs& p) {
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+  float s = 0.f;
+  for (int c = 0; c < p.nce; ++c) {
+    float f[Vec16<T>::VE];
+    Vec16<T>::unpack(*reinterpret_cast<const uint4*>(rows + ((size_t)r * p.nc + (c ^ g)) * 16), f);
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::VE; ++e) s += f[e];
+  }
+  return s;
+}
+
+// 1 / max(|x|, eps) of the dequantized row whose codes are LDS row r: the squares of c * scale + bias themselves, in order
+template <typename T>
+__device__ __forceinline__ float tr_q8_row_inv(const char* rows, int r, float scale, float bias, const RankArgs& p) {
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+  float s = 0.f;
+  for (int c = 0; c < p.nce; ++c) {
+    float f[Vec16<T>::VE];
+    Vec16<T>::unpack(*reinterpret_cast<const uint4*>(rows + ((size_t)r * p.nc + (c ^ g)) * 16), f);
+#pragma unroll
+    for (int e = 0; e < Vec16<T>::VE; ++e) {
+      const float x = f[e] * scale + bias;
+      s += x * x;
+    }
+  }
+  return 1.f / fmaxf(sqrtf(s), TR_COS_EPS);
+}
+
+// 16-byte vector v of a Q8 row -> LDS row r: its codes, converted exactly to T, as the swizzled operand chunks they fill;
+// the vectors that hold the row's scale and bias drop them into tsc[r], tbi[r]
+template <typename T>
+__device__ __forceinline__ void tr_q8_stage(char* rows, float* tsc, float* tbi, int r, int v, const uint4& q4, const RankArgs& p) {
+  constexpr int CPV = (int)sizeof(T);      // operand chunks the 16 codes of one vector become
+  const int e0 = 16 * v;
+  if (v == p.E >> 4) tsc[r] = __uint_as_float(tk_word(q4, (p.E >> 2) & 3));
+  if (v == (p.E + 4) >> 4) tbi[r] = __uint_as_float(tk_word(q4, ((p.E + 4) >> 2) & 3));
+  // E is a multiple of 4: a word is all codes or none
+  const uint32_t w[4] = {e0 < p.E ? q4.x : 0u, e0 + 4 < p.E ? q4.y : 0u, e0 + 8 < p.E ? q4.z : 0u, e0 + 12 < p.E ? q4.w : 0u};
+  char* drow = rows + (size_t)r * p.nc * 16;
+  const int g = (r >> p.sw_shift) & p.sw_mask;
+#pragma unroll
+  for (int j = 0; j < CPV; ++j) {
+    const int cb = CPV * v + j;
+    if (cb >= p.nc) continue;
+    uint4 o;
+    if constexpr (std::is_same<T, float>::value) {
+      o = tk_codes_f32(w[j]);
+    } else {
+      const uint2 a = tk_codes_bf16(w[2 * j]), b = tk_codes_bf16(w[2 * j + 1]);
+      o = make_uint4(a.x, a.y, b.x, b.y);
+    }
+    *reinterpret_cast<uint4*>(drow + ((cb ^ g) << 4)) = o;
+  }
+}
+
+// operand chunks behind the last one a Q8 vector is converted into are never staged: zero them once
+template <typename T>
+__device__ __forceinline__ void tr_q8_zero_tail(char* rows, int nrows, int first, int step, const RankArgs& p) {
+  for (int u = first; u < nrows * p.nc; u += step) {
+    const int r = u / p.nc, c = u - r * p.nc;
+    if (c >= (int)sizeof(T) * p.q_nv)
+      *reinterpret_cast<uint4*>(rows + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// The epilogue, one function for both kernels: the MFMA sums of a lane's 4 targets against one anchor -> their scores.
+// Q8: d * scale + sa * bias, two products and a sum, each rounded (the library is built without contraction, as topk.hip
+// is: no fused multiply-add in either); cosine: then * ainv, then * tinv.
+template <bool Q8>
+__device__ __forceinline__ void tr_scores(tr_f32x4& acc, const float4& sc, const float4& bi, float sa, bool cosine, float ai,
+                                          const float4& ti) {
+  if constexpr (Q8) {
+    acc[0] = acc[0] * sc.x + sa * bi.x;
+    acc[1] = acc[1] * sc.y + sa * bi.y;
+    acc[2] = acc[2] * sc.z + sa * bi.z;
+    acc[3] = acc[3] * sc.w + sa * bi.w;
+  }
+  if (cosine) {
+    acc[0] = acc[0] * ai * ti.x;
+    acc[1] = acc[1] * ai * ti.y;
+    acc[2] = acc[2] * ai * ti.z;
+    acc[3] = acc[3] * ai * ti.w;
+  }
+}
+
 // chunk c of anchor b's row (zero: past the row, past B, or an id outside the table, which raises the flag)
 __device__ __forceinline__ uint4 tr_anchor_chunk(const RankArgs& p, int64_t b, int c) {
   uint4 v = make_uint4(0, 0, 0, 0);
@@ -142,20 +259,25 @@ __device__ __forceinline__ uint4 tr_anchor_chunk(const RankArgs& p, int64_t b, i
 }
 
 // ------------------------------------------------------------------------------------------------ 1. the listed rows
-// LDS of a wave: the anchor's row, 16 listed rows, ids[LP], scores[LP], tinv[16], dec[16]; LP = P + X rounded up to 16
-static size_t tr_list_wave_bytes(int RB, int L) { return (size_t)17 * RB + (size_t)((L + 15) & ~15) * 8 + 128; }
+// LDS of a wave: the anchor's row, 16 listed rows, ids[LP], scores[LP], tinv[16], dec[16], Q8: scale[16], bias[16]; LP = P +
+// X rounded up to 16
+static size_t tr_list_wave_bytes(int RB, int L, bool q8) {
+  return (size_t)17 * RB + (size_t)((L + 15) & ~15) * 8 + (q8 ? 256 : 128);
+}
 
-template <typename T>
+template <typename T, bool Q8>
 __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
   extern __shared__ __attribute__((aligned(16))) char tr_smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
   const int RB = p.nc * 16, P = p.P, L = P + p.X, LP = (L + 15) & ~15;
-  char* Arow = tr_smem + (size_t)wave * ((size_t)17 * RB + (size_t)LP * 8 + 128);
+  char* Arow = tr_smem + (size_t)wave * ((size_t)17 * RB + (size_t)LP * 8 + (Q8 ? 256 : 128));
   char* Rows = Arow + RB;
   int* ids = reinterpret_cast<int*>(Rows + (size_t)16 * RB);
   float* sc = reinterpret_cast<float*>(ids + LP);
   float* tinv = sc + LP;
   int* dec = reinterpret_cast<int*>(tinv + 16);
+  float* tsc = reinterpret_cast<float*>(dec + 16);
+  float* tbi = tsc + 16;
   const int64_t b = (int64_t)blockIdx.x * 4 + wave;
   if (b >= p.B) return;      // the whole wave; the kernel has no workgroup barrier
   const bool cosine = p.sim == TR_COS;
@@ -172,19 +294,34 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
   }
   if (lane < 16) dec[lane] = 0;
   for (int c = lane; c < p.nc; c += 64) *reinterpret_cast<uint4*>(Arow + 16 * c) = tr_anchor_chunk(p, b, c);
+  if constexpr (Q8) tr_q8_zero_tail<T>(Rows, 16, lane, 64, p);
   tr_wave_sync();
   const float ai = cosine ? tr_row_inv<T>(Arow, 0, p) : 1.f;      // row 0 is not swizzled
+  float sa = 0.f;
+  if constexpr (Q8) sa = tr_row_sum<T>(Arow, 0, p);
   const int gsw = (n >> p.sw_shift) & p.sw_mask, nks = p.nc >> 2;
 
   for (int g0 = 0; g0 < LP; g0 += 16) {
-    for (int u = lane; u < 16 * p.nc; u += 64) {
-      const int r = u / p.nc, c = u - r * p.nc, id = ids[g0 + r];
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (id >= 0 && c < p.nce) v = *reinterpret_cast<const uint4*>(p.t_table + (p.t_lo + id) * p.row_bytes + 16 * c);
-      *reinterpret_cast<uint4*>(Rows + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = v;
+    if constexpr (Q8) {      // the 16 listed Q8 rows, vector by vector (a row that is not listed: code 0, scale 0, bias 0)
+      for (int u = lane; u < 16 * p.q_nv; u += 64) {
+        const int r = u / p.q_nv, v = u - r * p.q_nv, id = ids[g0 + r];
+        uint4 q4 = make_uint4(0, 0, 0, 0);
+        if (id >= 0) q4 = *reinterpret_cast<const uint4*>(p.t_table + (p.t_lo + id) * p.q_stride + 16 * v);
+        tr_q8_stage<T>(Rows, tsc, tbi, r, v, q4, p);
+      }
+    } else {
+      for (int u = lane; u < 16 * p.nc; u += 64) {
+        const int r = u / p.nc, c = u - r * p.nc, id = ids[g0 + r];
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (id >= 0 && c < p.nce) v = *reinterpret_cast<const uint4*>(p.t_table + (p.t_lo + id) * p.row_bytes + 16 * c);
+        *reinterpret_cast<uint4*>(Rows + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = v;
+      }
     }
     tr_wave_sync();
-    if (cosine && lane < 16) tinv[lane] = tr_row_inv<T>(Rows, lane, p);
+    if (cosine && lane < 16) {
+      if constexpr (Q8) tinv[lane] = tr_q8_row_inv<T>(Rows, lane, tsc[lane], tbi[lane], p);
+      else tinv[lane] = tr_row_inv<T>(Rows, lane, p);
+    }
     tr_f32x4 acc = tr_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < nks; ++ks) {
       const uint4 af = *reinterpret_cast<const uint4*>(Rows + n * RB + (((4 * ks + q) ^ gsw) << 4));
@@ -192,12 +329,11 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
       acc = tr_mma<T>(af, bf, acc);
     }
     tr_wave_sync();
-    if (cosine) {
-      const float4 ti = *reinterpret_cast<const float4*>(tinv + 4 * q);
-      acc[0] = acc[0] * ai * ti.x;
-      acc[1] = acc[1] * ai * ti.y;
-      acc[2] = acc[2] * ai * ti.z;
-      acc[3] = acc[3] * ai * ti.w;
+    if (cosine || Q8) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 sc = Q8 ? *reinterpret_cast<const float4*>(tsc + 4 * q) : zero;
+      const float4 bi = Q8 ? *reinterpret_cast<const float4*>(tbi + 4 * q) : zero;
+      tr_scores<Q8>(acc, sc, bi, sa, cosine, ai, cosine ? *reinterpret_cast<const float4*>(tinv + 4 * q) : zero);
     }
     if (n == 0) *reinterpret_cast<float4*>(sc + g0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     tr_wave_sync();      // the scores are written, the rows may be replaced
@@ -220,7 +356,7 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ 2. the count
-template <typename T, int AR, int TR, int PT>
+template <typename T, int AR, int TR, int PT, bool Q8>
 __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
   extern __shared__ __attribute__((aligned(16))) char tr_smem[];
   constexpr int AT = AR / 16, NT = TR / 16, NA = 4 * AR;
@@ -231,7 +367,10 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
   char* Ts = As + (size_t)NA * RB;
   float* ainv = reinterpret_cast<float*>(Ts + (size_t)2 * TR * RB);
   float* tinv = ainv + NA;      // [2][TR]
-  float* thS = tinv + 2 * TR;   // TLDS: [PT][NA] thresholds, the floats under them, label ids
+  float* tsc = tinv + 2 * TR;   // Q8: [2][TR] scales, [2][TR] biases, [NA] anchor sums
+  float* tbi = tsc + 2 * TR;
+  float* sa = tbi + 2 * TR;
+  float* thS = Q8 ? sa + NA : tsc;      // TLDS: [PT][NA] thresholds, the floats under them, label ids
   float* tloS = thS + PT * NA;
   int* lidS = reinterpret_cast<int*>(tloS + PT * NA);
   const bool cosine = p.sim == TR_COS;
@@ -269,9 +408,48 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
     }
   };
   auto tile_norms = [&](int buf) {
-    for (int r = threadIdx.x; r < TR; r += blockDim.x) tinv[buf * TR + r] = tr_row_inv<T>(Ts + (size_t)buf * TR * RB, r, p);
+    for (int r = threadIdx.x; r < TR; r += blockDim.x) {
+      const char* rows = Ts + (size_t)buf * TR * RB;
+      if constexpr (Q8) tinv[buf * TR + r] = tr_q8_row_inv<T>(rows, r, tsc[buf * TR + r], tbi[buf * TR + r], p);
+      else tinv[buf * TR + r] = tr_row_inv<T>(rows, r, p);
+    }
   };
-  if (ntile > 0) load_tile(0, 0);
+  // Q8: unit i of this thread is vector v of tile row r, packed r | v << 8 (-1: none); consecutive threads take
+  // consecutive vectors of a row, so a wave's load is one contiguous stretch of the table
+  constexpr int QU = Q8 ? tr_q8_units(AR, TR) : 0;
+  uint4 pre[Q8 ? QU : 1];
+  int prv[Q8 ? QU : 1];
+  if constexpr (Q8) {
+#pragma unroll
+    for (int i = 0; i < QU; ++i) {
+      const int u = threadIdx.x + i * 256;
+      prv[i] = u < TR * p.q_nv ? ((u / p.q_nv) | ((u % p.q_nv) << 8)) : -1;
+    }
+    tr_q8_zero_tail<T>(Ts, 2 * TR, threadIdx.x, 256, p);      // both buffers
+  }
+  auto q8_fetch = [&](int t) {
+    const int64_t t0 = lo + (int64_t)t * TR;
+#pragma unroll
+    for (int i = 0; i < QU; ++i) {
+      pre[i] = make_uint4(0, 0, 0, 0);      // a row past the end of the range: code 0, scale 0, bias 0
+      const int r = prv[i] & 0xff, v = prv[i] >> 8;
+      if (prv[i] >= 0 && t0 + r < hi) pre[i] = *reinterpret_cast<const uint4*>(p.t_table + (t0 + r) * p.q_stride + 16 * v);
+    }
+  };
+  auto q8_store = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < QU; ++i)
+      if (prv[i] >= 0)
+        tr_q8_stage<T>(Ts + (size_t)buf * TR * RB, tsc + buf * TR, tbi + buf * TR, prv[i] & 0xff, prv[i] >> 8, pre[i], p);
+  };
+  if (ntile > 0) {
+    if constexpr (Q8) {
+      q8_fetch(0);
+      q8_store(0);
+    } else {
+      load_tile(0, 0);
+    }
+  }
 
   // ---- the thresholds: label p of anchor r -> (score, the float under it, id); (+inf, +inf, -1) where nothing is ranked
   auto threshold = [&](int64_t b, int pp, float& th, float& tlo, int& lid) {
@@ -291,9 +469,12 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (cosine) {
-    for (int r = threadIdx.x; r < NA; r += blockDim.x) ainv[r] = tr_row_inv<T>(As, r, p);
-    if (ntile > 0) tile_norms(0);
+  if (cosine || Q8) {
+    for (int r = threadIdx.x; r < NA; r += blockDim.x) {
+      if (cosine) ainv[r] = tr_row_inv<T>(As, r, p);
+      if constexpr (Q8) sa[r] = tr_row_sum<T>(As, r, p);
+    }
+    if (cosine && ntile > 0) tile_norms(0);
     __syncthreads();
   }
 
@@ -301,11 +482,12 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
   const int row0 = wave * AR + n;                         // + 16 at
   const int gsw = (n >> p.sw_shift) & p.sw_mask;          // g(r) depends on r & 15 only
   constexpr int PR = TLDS ? 1 : PT;
-  float thr_[AT][PR], tlor_[AT][PR], ai[AT];
+  float thr_[AT][PR], tlor_[AT][PR], ai[AT], sav[AT];
   int lidr_[AT][PR], cnt[AT][PT];
 #pragma unroll
   for (int at = 0; at < AT; ++at) {
     ai[at] = cosine ? ainv[row0 + 16 * at] : 1.f;
+    sav[at] = Q8 ? sa[row0 + 16 * at] : 0.f;
 #pragma unroll
     for (int pp = 0; pp < PT; ++pp) cnt[at][pp] = 0;
     if constexpr (!TLDS) {
@@ -320,7 +502,10 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
 
   for (int t = 0; t < ntile; ++t) {
     const int buf = t & 1;
-    if (t + 1 < ntile) load_tile(t + 1, buf ^ 1);
+    if (t + 1 < ntile) {
+      if constexpr (Q8) q8_fetch(t + 1);
+      else load_tile(t + 1, buf ^ 1);
+    }
     const char* Tb = Ts + (size_t)buf * TR * RB;
     tr_f32x4 acc[AT][NT];
 #pragma unroll
@@ -339,17 +524,18 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
         for (int at = 0; at < AT; ++at) acc[at][nt] = tr_mma<T>(af, bf[at], acc[at][nt]);
       }
     }
-    if (cosine) {
+    // Q8: the next tile, converted behind the issued MFMAs into the buffer the last tile left (the barrier at its end)
+    if (Q8 && t + 1 < ntile) q8_store(buf ^ 1);
+    if (cosine || Q8) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        const float4 ti = *reinterpret_cast<const float4*>(tinv + buf * TR + 16 * nt + 4 * q);
+        const int j0 = buf * TR + 16 * nt + 4 * q;
+        const float4 sc = Q8 ? *reinterpret_cast<const float4*>(tsc + j0) : zero;
+        const float4 bi = Q8 ? *reinterpret_cast<const float4*>(tbi + j0) : zero;
+        const float4 ti = cosine ? *reinterpret_cast<const float4*>(tinv + j0) : zero;
 #pragma unroll
-        for (int at = 0; at < AT; ++at) {
-          acc[at][nt][0] = acc[at][nt][0] * ai[at] * ti.x;
-          acc[at][nt][1] = acc[at][nt][1] * ai[at] * ti.y;
-          acc[at][nt][2] = acc[at][nt][2] * ai[at] * ti.z;
-          acc[at][nt][3] = acc[at][nt][3] * ai[at] * ti.w;
-        }
+        for (int at = 0; at < AT; ++at) tr_scores<Q8>(acc[at][nt], sc, bi, sav[at], cosine, ai[at], ti);
       }
     }
 
@@ -448,22 +634,27 @@ struct RankShape {
   int AR, TR;
   size_t lds;      // taken where it fits this much
 };
-static size_t tr_lds_bytes(const RankShape& s, int RB, int PT) {
+static size_t tr_lds_bytes(const RankShape& s, int RB, int PT, bool q8) {
   const size_t NA = (size_t)4 * s.AR;
-  return NA * RB + (size_t)2 * s.TR * RB + NA * 4 + (size_t)2 * s.TR * 4 + (PT > 4 ? NA * PT * 12 : 0);
+  // Q8: the tiles' scales and biases, the anchors' sums
+  return NA * RB + (size_t)2 * s.TR * RB + NA * 4 + (size_t)2 * s.TR * 4 + (PT > 4 ? NA * PT * 12 : 0) +
+         (q8 ? (size_t)2 * s.TR * 8 + NA * 4 : 0);
 }
 
-template <typename T, int PT>
+template <typename T, int PT, bool Q8>
 static int tr_count_launch(const char* op, const RankArgs& p, int RB, hipStream_t s) {
   static const RankShape shapes[] = {{64, 64, TR_HALF_LDS}, {32, 64, TR_HALF_LDS}, {32, 64, TR_MAX_LDS}, {16, 32, TR_MAX_LDS}};
+  constexpr int PT64 = Q8 ? 1 : 4;      // the labels up to which 64 x 64 is taken
   const RankShape* sh = nullptr;
   for (const RankShape& c : shapes)
-    if ((PT <= 4 || c.AR <= 32) && tr_lds_bytes(c, RB, PT) <= c.lds) {
+    if ((PT <= PT64 || c.AR <= 32) && tr_lds_bytes(c, RB, PT, Q8) <= c.lds &&
+        (!Q8 || (c.TR * p.q_nv + 255) / 256 <= tr_q8_units(c.AR, c.TR))) {
       sh = &c;
       break;
     }
-  TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS (row %d bytes, P %d)", op, RB, p.P);
-  const size_t lds = tr_lds_bytes(*sh, RB, PT);
+  TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS%s (row %d bytes, P %d)", op,
+              Q8 ? " and the Q8 vectors of a tile its threads" : "", RB, p.P);
+  const size_t lds = tr_lds_bytes(*sh, RB, PT, Q8);
   const int NA = 4 * sh->AR;
   const dim3 grid((unsigned)((p.B + NA - 1) / NA), (unsigned)p.S);
   auto go = [&](auto kern) -> int {
@@ -475,43 +666,35 @@ static int tr_count_launch(const char* op, const RankArgs& p, int RB, hipStream_
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
     return TRS_OK;
   };
-  if constexpr (PT <= 4) {
-    if (sh->AR == 64) return go(target_rank_count_kernel<T, 64, 64, PT>);
+  if constexpr (PT <= PT64) {
+    if (sh->AR == 64) return go(target_rank_count_kernel<T, 64, 64, PT, Q8>);
   }
-  if (sh->AR == 32) return go(target_rank_count_kernel<T, 32, 64, PT>);
-  return go(target_rank_count_kernel<T, 16, 32, PT>);
+  if (sh->AR == 32) return go(target_rank_count_kernel<T, 32, 64, PT, Q8>);
+  return go(target_rank_count_kernel<T, 16, 32, PT, Q8>);
 }
 
-template <typename T>
+template <typename T, bool Q8>
 static int tr_launch(const char* op, const RankArgs& p, hipStream_t s) {
   const int RB = p.nc * 16;
-  const size_t lds = 4 * tr_list_wave_bytes(RB, p.P + p.X);
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)target_rank_list_kernel<T>,
+  const size_t lds = 4 * tr_list_wave_bytes(RB, p.P + p.X, Q8);
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)target_rank_list_kernel<T, Q8>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)TR_MAX_LDS) != hipSuccess) {
     (void)hipGetLastError();
     return fail(TRS_ELAUNCH, "%s: hipFuncSetAttribute(%zu bytes of LDS) failed", op, lds);
   }
-  hipLaunchKernelGGL(target_rank_list_kernel<T>, dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p);
-  const int rc = p.P == 1 ? tr_count_launch<T, 1>(op, p, RB, s)
-                 : p.P <= 4 ? tr_count_launch<T, 4>(op, p, RB, s)
-                            : tr_count_launch<T, TR_MAX_P>(op, p, RB, s);
+  hipLaunchKernelGGL((target_rank_list_kernel<T, Q8>), dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p);
+  const int rc = p.P == 1 ? tr_count_launch<T, 1, Q8>(op, p, RB, s)
+                 : p.P <= 4 ? tr_count_launch<T, 4, Q8>(op, p, RB, s)
+                            : tr_count_launch<T, TR_MAX_P, Q8>(op, p, RB, s);
   return rc != TRS_OK ? rc : check_launch(op);
 }
 
-}  // namespace trs
-
-using namespace trs;
-
-// the counts of the target ranges meet in the output itself (integer atomics): no workspace at any shape
-extern "C" size_t trs_target_ranks_workspace_bytes(int64_t B, int64_t Vt, int32_t P) { return 0; }
-
-extern "C" int trs_target_ranks(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
-                                int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
-                                int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, const void* labels,
-                                int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
-                                int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes, int32_t* err_flag,
-                                trs_stream_t stream) {
-  const char* op = "target_ranks";
+// both entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns
+static int tr_entry(const char* op, bool q8, const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                    int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo, int64_t target_hi,
+                    int32_t E, int32_t dtype, int32_t sim, const void* labels, int32_t label_dtype, int32_t P,
+                    const void* exclude, int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores,
+                    int32_t* err_flag, trs_stream_t stream) {
   TRS_REQUIRE(dtype == TRS_F32 || dtype == TRS_BF16, TRS_EDTYPE, "%s: dtype %d", op, dtype);
   TRS_REQUIRE(sim == TR_DOT || sim == TR_COS, TRS_EINVAL, "%s: sim %d (0 = inner product, 1 = cosine)", op, sim);
   TRS_REQUIRE(anchor_idx == nullptr || idx_dtype == TRS_I64 || idx_dtype == TRS_I32, TRS_EINVAL, "%s: idx dtype %d", op,
@@ -560,7 +743,40 @@ extern "C" int trs_target_ranks(const void* anchor_table, int64_t Va, const void
   p.idx64 = idx_dtype == TRS_I64;
   p.lab64 = label_dtype == TRS_I64;
   p.excl64 = excl_dtype == TRS_I64;
-  p.dma = p.nce == p.nc;
+  p.dma = !q8 && p.nce == p.nc;
+  p.E = E;
+  p.q_stride = (int)q8_stride(E);
+  p.q_nv = p.q_stride / 16;
   hipStream_t s = (hipStream_t)stream;
-  return dtype == TRS_F32 ? tr_launch<float>(op, p, s) : tr_launch<bf16_t>(op, p, s);
+  if (q8) return dtype == TRS_F32 ? tr_launch<float, true>(op, p, s) : tr_launch<bf16_t, true>(op, p, s);
+  return dtype == TRS_F32 ? tr_launch<float, false>(op, p, s) : tr_launch<bf16_t, false>(op, p, s);
+}
+
+}  // namespace trs
+
+using namespace trs;
+
+// the counts of the target ranges meet in the output itself (integer atomics): no workspace at any shape
+extern "C" size_t trs_target_ranks_workspace_bytes(int64_t B, int64_t Vt, int32_t P) { return 0; }
+
+extern "C" int trs_target_ranks(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                                int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
+                                int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, const void* labels,
+                                int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
+                                int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes, int32_t* err_flag,
+                                trs_stream_t stream) {
+  return tr_entry("target_ranks", false, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
+                  target_hi, E, dtype, sim, labels, label_dtype, P, exclude, excl_dtype, X, ranks, label_scores, err_flag,
+                  stream);
+}
+
+extern "C" int trs_target_ranks_q8(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                                   int64_t anchor_offset, int64_t B, const void* target_q, int64_t target_lo,
+                                   int64_t target_hi, int32_t E, int32_t anchor_dtype, int32_t sim, const void* labels,
+                                   int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
+                                   int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes,
+                                   int32_t* err_flag, trs_stream_t stream) {
+  return tr_entry("target_ranks_q8", true, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
+                  target_hi, E, anchor_dtype, sim, labels, label_dtype, P, exclude, excl_dtype, X, ranks, label_scores,
+                  err_flag, stream);
 }

@@ -4249,6 +4249,24 @@ def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, ta
     return values, ids
 
 
+def _q8_table_checks(op, aw, tq, E):
+    """float anchors of width E against the uint8 rows of a Q8 table of E columns"""
+    if not isinstance(E, int) or E <= 0:
+        raise ValueError(f"{op}: E must be a positive int, got {E!r}")
+    if tq.dtype != torch.uint8:
+        raise TypeError(f"{op}: target_qweight must be uint8 Q8 rows, got {tq.dtype}")
+    S = (E + 8 + 15) // 16 * 16
+    if tq.dim() != 2 or tq.shape[1] != S:
+        raise ValueError(f"{op}: target_qweight must be (V, {S}) for E={E}, got shape {tuple(tq.shape)}")
+    if aw.dim() != 2 or aw.shape[1] != E:
+        raise ValueError(f"{op}: anchors of width E={E} expected, got shape {tuple(aw.shape)}")
+    if aw.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: bf16 or fp32 anchors expected, got {aw.dtype}")
+    if E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
+        raise NotImplementedError(f"{op}: anchor rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} "
+                                  f"of {aw.dtype}")
+
+
 def topk_scores_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_qweight: torch.Tensor, E: int,
                    k: int, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None, sim="dot",
                    exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -4265,20 +4283,7 @@ def topk_scores_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tenso
     code = _sim_code(sim)
     aw = anchor_weight.detach()
     tq = target_qweight.detach()
-    if not isinstance(E, int) or E <= 0:
-        raise ValueError(f"topk_scores_q8: E must be a positive int, got {E!r}")
-    if tq.dtype != torch.uint8:
-        raise TypeError(f"topk_scores_q8: target_qweight must be uint8 Q8 rows, got {tq.dtype}")
-    S = (E + 8 + 15) // 16 * 16
-    if tq.dim() != 2 or tq.shape[1] != S:
-        raise ValueError(f"topk_scores_q8: target_qweight must be (V, {S}) for E={E}, got shape {tuple(tq.shape)}")
-    if aw.dim() != 2 or aw.shape[1] != E:
-        raise ValueError(f"topk_scores_q8: anchors of width E={E} expected, got shape {tuple(aw.shape)}")
-    if aw.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"topk_scores_q8: bf16 or fp32 anchors expected, got {aw.dtype}")
-    if E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
-        raise NotImplementedError(f"topk_scores_q8: anchor rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, "
-                                  f"got E = {E} of {aw.dtype}")
+    _q8_table_checks("topk_scores_q8", aw, tq, E)
     return _topk_run("topk_scores_q8", "trs_topk_scores_q8", aw, anchor_idx, anchor_offset, tq, "target_qweight",
                      target_lo, target_hi, E, code, k, exclude)
 
@@ -4314,6 +4319,13 @@ def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor]
     if E < 1 or E > TOPK_MAX_E or (E * aw.element_size()) % 16 != 0:
         raise NotImplementedError(f"{op}: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} of "
                                   f"{aw.dtype}")
+    return _target_ranks_run(op, "trs_target_ranks", aw, anchor_idx, anchor_offset, tw, "target_weight", target_lo,
+                             target_hi, E, code, labels, exclude)
+
+
+def _target_ranks_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, labels, exclude):
+    """what target_ranks and target_ranks_q8 share behind their table checks: range, labels, exclusion list, outputs, the
+    call"""
     lo = int(target_lo)
     hi = tw.shape[0] if target_hi is None else int(target_hi)
     if not 0 <= lo < hi <= tw.shape[0]:
@@ -4336,7 +4348,7 @@ def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor]
             raise NotImplementedError(f"{op}: at most {TARGET_RANKS_MAX_X} excluded ids per sample (they are staged on "
                                       f"chip), got X = {ex.shape[1]}")
         ex = ex.contiguous()
-    for name, t in (("anchor_weight", aw), ("target_weight", tw)):
+    for name, t in (("anchor_weight", aw), (tname, tw)):
         if not t.is_contiguous():
             raise ValueError(f"{op}: {name} must be contiguous, got strides {tuple(t.stride())}")
     dev = require_device(aw, a_idx, tw, y, ex)
@@ -4347,12 +4359,32 @@ def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor]
     ws_bytes = size_query("trs_target_ranks_workspace_bytes", B, hi - lo, P)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     flag = _ErrFlag(dev)
-    call("trs_target_ranks", ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
+    call(entry, ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
          int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, ptr(y), index_dtype_code(y), P, ptr(ex),
          index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(ranks), ptr(scores),
          ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
     flag.check(op)
     return ranks, scores
+
+
+def target_ranks_q8(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_qweight: torch.Tensor, E: int,
+                    labels: torch.Tensor, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None,
+                    sim="dot", exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``target_ranks`` over a row-wise int8 (Q8) target table, in one HIP pass that reads the Q8 rows themselves
+    (csrc/target_rank.hip): no float copy of the table, no (B, Vt) block, no selection.  Tables and anchors are those of
+    ``topk_scores_q8`` (``target_qweight`` the uint8 rows of ``quant.quantize_rows``, float anchors through ``anchor_idx``
+    + ``anchor_offset`` or as the (B, E) query matrix), and so is the score, ``d * scale + sa * bias`` in fp32 (cosine:
+    over the anchor's norm and the norm of the dequantized row); labels, ``exclude``, padding, the index flag and the
+    outputs are those of ``target_ranks``.  ``ranks[b, p]`` is the index ``topk_scores_q8(..., exclude=exclude)`` returns
+    that id at, were k unbounded, and ``label_scores[b, p]`` the same bits as its value: the position at which the
+    quantized table is served, not the rank over a float copy of it.  No gradient, no host read-back."""
+    op = "target_ranks_q8"
+    code = _sim_code(sim)
+    aw = anchor_weight.detach()
+    tq = target_qweight.detach()
+    _q8_table_checks(op, aw, tq, E)
+    return _target_ranks_run(op, "trs_target_ranks_q8", aw, anchor_idx, anchor_offset, tq, "target_qweight", target_lo,
+                             target_hi, E, code, labels, exclude)
 
 
 class _SoftmaxScoresLoss(Function):

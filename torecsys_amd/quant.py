@@ -159,7 +159,8 @@ class QuantizedEmbeddingFM(nn.Module):
 class QuantizedEmbeddingPairScorer(nn.Module):
     """``fused.EmbeddingPairScorer`` for serving on Q8 tables.  Buffers (persistent): ``qweight``, the target table or the
     one shared table, and ``anchor_qweight``, the anchor table where it is a separate one.  ``topk`` is the retrieval
-    kernel over the Q8 rows (functional.topk_scores_q8); the anchors are dequantized per batch into ``out_dtype``."""
+    kernel over the Q8 rows (functional.topk_scores_q8) and ``rank`` the position of held-out targets among them
+    (functional.target_ranks_q8); the anchors are dequantized per batch into ``out_dtype``."""
 
     def __init__(self, embed_size: int, anchor_size: int, target_size: Optional[int] = None, similarity: str = 'dot',
                  anchor_offset: int = 0, target_offset: int = 0, out_dtype: torch.dtype = torch.float32):
@@ -201,6 +202,13 @@ class QuantizedEmbeddingPairScorer(nn.Module):
         is searched from ``target_offset`` to its end."""
         return F_.topk_scores_q8(self._anchors(anchor_idx), None, self.qweight, self.embed_size, k,
                                  target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
+
+    def rank(self, anchor_idx: torch.Tensor, positive_idx: torch.Tensor, exclude: Optional[torch.Tensor] = None):
+        """``EmbeddingPairScorer.rank`` on the Q8 target rows (functional.target_ranks_q8): ``(ranks (B, P) int64,
+        label_scores (B, P) fp32)``, the index ``topk`` with the same ``exclude`` would return each id at, were k unbounded;
+        ``torecsys_amd.metrics`` takes it as it is.  A shared table is ranked from ``target_offset`` to its end."""
+        return F_.target_ranks_q8(self._anchors(anchor_idx), None, self.qweight, self.embed_size, positive_idx,
+                                  target_lo=self.target_offset, sim=self.similarity, exclude=exclude)
 
     def forward(self, anchor_idx: torch.Tensor, target_idx: torch.Tensor) -> torch.Tensor:
         """(B, 1 + K) scores of given pairs.  Not a kernel: a plain composition, both sides dequantized by
