@@ -1451,6 +1451,33 @@ int trs_target_ranks_q8(const void* anchor_table, int64_t Va, const void* anchor
                         const void* exclude, int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores,
                         void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
 
+/* ---- multi-interest top-k and target ranks (csrc/topk.hip, csrc/target_rank.hip; not in the reference) ----------------
+ * A user is G anchors (MIND / ComiRec interest vectors), 1 <= G <= 16, and its score against a target is the best of them:
+ *   score[u, j] = max_g sim(A[anchor_idx[u G + g] + anchor_offset], T[target_lo + j])
+ * The B = U * G anchors are user-major; anchor_idx NULL: anchor_table is the (U G, E) query matrix.  Each sim is the bits
+ * trs_topk_scores / trs_target_ranks give that (anchor, target) pair; the max is fmaxf's (a NaN loses to a number; a
+ * target all of whose G scores are NaN is never returned and never counts).  An anchor id outside [0, Va) scores as a
+ * zero row, takes part in the max and raises *err_flag.  The arguments are those of the single-anchor entries with U and G
+ * behind B; exclude is (U, X), labels (U, P), and the outputs are per user: out_val / out_idx (U, k), ranks / label_scores
+ * (U, P).  Ordering, tie rule, padding slots, labels, exclusion, limits (k <= 128, P <= 16, X <= 1024 for the ranks, E <=
+ * 256, float tables only: there is no Q8 form) and error codes are theirs; G outside 1 .. 16, U < 0 or B != U G: TRS_EINVAL,
+ * before any launch.  The G rows of a user sit in adjacent columns of one matrix-core accumulator group (padded to a power
+ * of two by repeating the last one, on chip), the max is taken across lanes, and selection and count run once per user:
+ * the result is exact over the whole range, which a merge of per-interest top-k lists is not.  The top-k workspace is
+ * (U, S, k) keys, trs_topk_scores_multi_workspace_bytes; the ranks need none (workspace may be NULL).                   */
+size_t trs_topk_scores_multi_workspace_bytes(int64_t U, int32_t G, int64_t Vt, int32_t k);
+int trs_topk_scores_multi(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                          int64_t anchor_offset, int64_t B, int64_t U, int32_t G, const void* target_table,
+                          int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k,
+                          const void* exclude, int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx,
+                          void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream);
+int trs_target_ranks_multi(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                           int64_t anchor_offset, int64_t B, int64_t U, int32_t G, const void* target_table,
+                           int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, const void* labels,
+                           int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
+                           int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes, int32_t* err_flag,
+                           trs_stream_t stream);
+
 /* ---- softmax cross-entropy against a whole target table (csrc/softmax_loss.hip; not in the reference) -----------------
  * anchors (B, E) and targets (Vt, E), contiguous rows of one value dtype; labels (B) of label_dtype (TRS_I64 | TRS_I32):
  *   z[b, j] = scale * sum_e A[b, e] T[j, e]      (products of table-dtype operands, fp32 accumulation on the matrix cores)

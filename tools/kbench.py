@@ -49,6 +49,9 @@ composition (gather, matmul per table chunk, topk, merge), bf16 and fp32 (own in
 --what targetrank [--k 100] [--sim dot|cosine] [--budget 4]: rank of one held-out target per anchor over a 1 M-row table
 against the chunked ATen composition (matmul per chunk, compare, sum) and against topk_scores at k, with and without 100
 excluded ids (own inputs, see bench_targetrank).
+--what topk | targetrank --interests G [--k 100] [--sim dot|cosine] [--budget 4]: the multi-interest path (max over a user's G
+anchors) against the per-interest top-k + ATen merge / the chunked ATen count, and against the single-interest kernel on
+the same rows (see bench_multi).
 --what targetrank --q8 [--k 100] [--sim dot|cosine] [--budget 4]: the same rank over a 1 M-row Q8 table: the float kernel on
 a bf16 copy held in memory, dequantize + float kernel per call, the Q8 kernels, and topk_scores_q8 at k; times and peak
 memory (see bench_targetrank_q8)."""
@@ -1549,6 +1552,85 @@ def bench_targetrank(a):
         del tw, aw, up
 
 
+def bench_multi(a):
+    """--what topk | targetrank with --interests G: ``topk_scores`` / ``target_ranks`` at ``interests=G`` over a 1 M-row
+    table (U in {4 096, 65 536} users of G anchors as a (U G, E) query matrix, E = 64, bf16 and fp32, uniform random rows)
+    against (a) the route that existed before -- top-k: ``topk_scores`` over the U G rows as independent anchors, then the
+    ATen merge of the (U, G k) candidates (the best copy of every id kept, ``topk`` again), which is not exact; ranks (P =
+    1): the chunked ATen matmul, max over G, compare, sum -- and (b) the single-interest kernel on the same U G rows as
+    independent anchors, which shows what the max costs on the streaming path.  The race is that of --what topk."""
+    dev = torch.device("cuda:0")
+    V, E, k, sim, G, rank = a.V, a.E, a.k, a.sim, a.interests, a.what == "targetrank"
+    g = torch.Generator(device=dev).manual_seed(77)
+
+    def merge(q, tw):
+        v, i = F_.topk_scores(q, None, tw, k, sim=sim)
+        v, i = v.view(-1, G * k), i.view(-1, G * k)
+        o = torch.argsort(v, dim=1, descending=True, stable=True)      # best first, then by id: the first of an id is its best
+        v, i = v.gather(1, o), i.gather(1, o)
+        o = torch.argsort(i, dim=1, stable=True)
+        v, i = v.gather(1, o), i.gather(1, o)
+        v[:, 1:][i[:, 1:] == i[:, :-1]] = float("-inf")
+        v, j = torch.topk(v, k, dim=1)
+        return v, i.gather(1, j)
+
+    def count(q, tw, y):
+        def rows(ids):
+            t = tw[ids]
+            return torch.nn.functional.normalize(t.float(), dim=-1, eps=1e-8).to(t.dtype) if sim == "cosine" else t
+        if sim == "cosine":
+            q = torch.nn.functional.normalize(q.float(), dim=1, eps=1e-8).to(q.dtype)
+        U = y.shape[0]
+        sl = (q.view(U, G, E) * rows(y)[:, None, :]).sum(dim=2).amax(dim=1, keepdim=True)
+        chunk = max(4096, min(V, (1 << 28) // q.shape[0]))
+        cnt = torch.zeros(U, dtype=torch.int64, device=dev)
+        for lo in range(0, V, chunk):
+            cnt += ((q @ rows(slice(lo, lo + chunk)).T).view(U, G, -1).amax(dim=1) > sl).sum(dim=1)
+        return cnt
+
+    def race(fns):
+        for f in fns.values():
+            for _ in range(2):
+                f()
+        torch.cuda.synchronize()
+        ts, spent = {n: [] for n in fns}, 0.0
+        while len(ts["multi"]) < 3 or (len(ts["multi"]) < 20 and spent < a.budget):
+            for name, f in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                f()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1) * 1e-3)
+                spent += ts[name][-1]
+        return {n: sorted(v) for n, v in ts.items()}
+
+    print(f"{a.what} interests = {G}: V = {V}, E = {E}, " + ("P = 1" if rank else f"k = {k}") + f", sim = {sim}")
+    for dt in (torch.bfloat16, torch.float32):
+        tw = torch.randn(V, E, generator=g, device=dev).to(dt)
+        for U in (4096, 65536):
+            q = torch.randn(U * G, E, generator=g, device=dev).to(dt)
+            y = torch.randint(0, V, (U,), generator=g, device=dev)
+            if rank:
+                fns = {"multi": lambda: F_.target_ranks(q, None, tw, y, sim=sim, interests=G), "prior": lambda: count(q, tw, y),
+                       "flat": lambda: F_.target_ranks(q, None, tw, y.repeat_interleave(G), sim=sim)}
+                off = (fns["multi"]()[0][:, 0] - fns["prior"]()).abs().double()
+                note = f"|rank - the composition's|: median {float(off.median()):.0f}, max {float(off.max()):.0f}"
+            else:
+                fns = {"multi": lambda: F_.topk_scores(q, None, tw, k, sim=sim, interests=G), "prior": lambda: merge(q, tw),
+                       "flat": lambda: F_.topk_scores(q, None, tw, k, sim=sim)}
+                note = f"users whose merged ids differ from the exact ones: {int((fns['multi']()[1] != fns['prior']()[1]).any(1).sum())}"
+            ts = race(fns)
+            med = {n: v[len(v) // 2] for n, v in ts.items()}
+            tag = f"{str(dt)[6:]} U={U} G={G}"
+            for n, v in ts.items():
+                print(f"{tag:24s} {n:5s} med {med[n] * 1e3:9.3f} ms  spread {v[0] * 1e3:9.3f} .. {v[-1] * 1e3:9.3f} ms "
+                      f"({len(v)} launches)  {2.0 * U * G * V * E / med[n] / 1e12:7.1f} TFLOP/s", flush=True)
+            print(f"{tag:24s} prior / multi = {med['prior'] / med['multi']:.2f}   multi / flat = {med['multi'] / med['flat']:.2f}   "
+                  f"{note}", flush=True)
+        del tw
+
+
 def bench_softmax(a):
     """functional.softmax_scores_loss (csrc/softmax_loss.hip) against the only ATen composition that runs at these shapes:
     one autograd.Function over target chunks sized so that a chunk's (B, chunk) fp32 logits stay within 1 GiB -- forward:
@@ -1857,8 +1939,11 @@ def main():
     ap.add_argument("--rows", default="1000000,32000000", help="q8: table sizes V to run")
     ap.add_argument("--k", type=int, default=100, help="topk: items returned per anchor")
     ap.add_argument("--budget", type=float, default=4.0, help="topk: seconds of timed launches per shape")
+    ap.add_argument("--interests", type=int, default=1, help="topk, targetrank: G > 1 times the multi-interest path (see bench_multi)")
     ap.add_argument("--q8", action="store_true", help="topk, targetrank: the Q8-table legs (bf16 table / dequantize + bf16 / Q8 kernel)")
     a = ap.parse_args()
+    if a.what in ("topk", "targetrank") and a.interests > 1:
+        return bench_multi(a)
     if a.what == "topk":         # own inputs: not part of "all"
         return bench_topk_q8(a) if a.q8 else bench_topk(a)
     if a.what == "targetrank":   # own inputs: not part of "all"

@@ -225,6 +225,11 @@ SIGNATURES = {
                                    _I32, _P, _P, _P, _SZ, _P, _P]),
     "trs_target_ranks_q8": (c_int32, [_P, _I64, _P, _I32, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P,
                                       _I32, _I32, _P, _P, _P, _SZ, _P, _P]),
+    "trs_topk_scores_multi_workspace_bytes": (_SZ, [_I64, _I32, _I64, _I32]),
+    "trs_topk_scores_multi": (c_int32, [_P, _I64, _P, _I32, _I64, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P,
+                                        _I32, _I32, _P, _P, _P, _SZ, _P, _P]),
+    "trs_target_ranks_multi": (c_int32, [_P, _I64, _P, _I32, _I64, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, _P,
+                                         _I32, _I32, _P, _I32, _I32, _P, _P, _P, _SZ, _P, _P]),
     "trs_softmax_loss_workspace_bytes": (_SZ, [_I64, _I64, _I32, _I32]),
     "trs_softmax_loss_fwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _P, _I32, _I64, _F32, _P, _P, _P, _SZ, _P, _P]),
     "trs_softmax_loss_bwd": (c_int32, [_P, _I64, _P, _I64, _I32, _I32, _P, _I32, _F32, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -63,8 +63,29 @@
 // it takes 235 / 247 and keeps two, inside 80 KiB as before (bf16 E = 64: 51.5 KiB).  At P <= 4 the Q8 64 x 64 takes 287 /
 // 303 registers, so Q8 with 2 .. 4 labels starts at 32 x 64 (217 / 231, two waves); 32 x 64 at P = 1 takes 190 / 204, 16 x 32
 // at most 111.  Like the float ones, the Q8 arrangements have not been timed against each other.
+//
+// Multi-interest (template parameter MI of both kernels; trs_target_ranks_multi).  A user is G anchors (1 .. 16) and
+// score[u, j] = max_g sim(a[u, g], t[j]), each sim the bits above; Gp = the power of two >= G is a kernel argument (gsh =
+// log2 Gp), and MI = false compiles to the kernels above unchanged (same registers and occupancy in the compiler's report).
+// Streaming kernel: a workgroup's NA LDS anchor rows hold NA / Gp users, row r slot r % Gp of user r / Gp, gathered from
+// the user's interest min(slot, G - 1) -- padding by repetition, on chip.  Behind the tile's epilogue (and the -inf of rows
+// past the range) the scores of a user's Gp adjacent lanes are replaced by their max, log2 Gp DPP steps per score on the
+// vector ALU (group_max.hpp), each step over the whole tile behind one uniform branch; every score is compared, so there
+// is no ballot shortcut as in topk.hip.  The leader lane (n % Gp == 0) carries the user's thresholds and counts; the
+// other lanes carry (+inf, -1) like rows past B and add nothing.  Boundary tile, tie pass, the 4-lane sum and the atomic
+// are the ones above.  The variant that ORs compare masks on the scalar ALU was not built.  List kernel: one wave per user,
+// its Gp interest rows in LDS (swizzled) where the anchor's row stood; column n of the B operand is interest n % Gp (the
+// waste is (16 - Gp) / 16), then the group max: every lane holds the user's score of its listed row, the same bits as the
+// streaming kernel's (the max of identical bits is exact).  1 .. 4 waves a workgroup, as many as fit 160 KiB.
+// Registers (compiler's report, no spill; vector + accumulator, fp32 / bf16): 64 x 64 at P = 1 144 + 68 / 141 + 64, two
+// waves per SIMD; 64 x 64 at P <= 4 187 + 72 = 259 (fp32), ONE wave, so fp32 with 2 .. 4 labels starts at 32 x 64 (114 + 36,
+// three waves); bf16 187 + 64 keeps two and stays.  32 x 64: P = 1 92 + 36 / 32, four; P = 16 111 + 36 / 32, three.  16 x 32: at
+// most 61 + 8, seven.  List kernel 62 / 41 + 4, seven / eight.
 #include <algorithm>
 
+#include <type_traits>
+
+#include "group_max.hpp"
 #include "lds_dma.hpp"
 #include "q8_common.hpp"
 
@@ -99,6 +120,13 @@ struct RankArgs {
   bool idx64, lab64, excl64, dma;
   int E, q_stride, q_nv;   // Q8 targets: columns, bytes of a row (S) and its 16-byte vectors
 };
+// multi-interest (template parameter MI): B users of G anchors each, in groups of Gp = 1 << gsh LDS rows.  Arguments of
+// their own, so that the kernels of one anchor per sample keep theirs
+struct RankArgsMI : RankArgs {
+  int G, gsh;
+};
+template <bool MI>
+using RankArgsOf = std::conditional_t<MI, RankArgsMI, RankArgs>;
 
 __device__ __forceinline__ void tr_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -258,27 +286,49 @@ __device__ __forceinline__ uint4 tr_anchor_chunk(const RankArgs& p, int64_t b, i
   return v;
 }
 
+// multi-interest: chunk c of slot `slot` of user u's group of LDS rows, its interest min(slot, G - 1) (anchor u G + that);
+// zero past the U users
+__device__ __forceinline__ uint4 tr_interest_chunk(const RankArgsMI& p, int64_t u, int slot, int c) {
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (u < p.B) {
+    const int64_t ia = u * p.G + min(slot, p.G - 1);
+    int64_t ra = (p.a_idx != nullptr ? tr_id(p.a_idx, p.idx64, ia) : ia) + p.a_off;
+    if (ra < 0 || ra >= p.Va) {
+      if (c == 0 && p.err_flag != nullptr) *p.err_flag = 1;
+    } else if (c < p.nce) {
+      v = *reinterpret_cast<const uint4*>(p.a_table + ra * p.row_bytes + 16 * c);
+    }
+  }
+  return v;
+}
+
 // ------------------------------------------------------------------------------------------------ 1. the listed rows
 // LDS of a wave: the anchor's row, 16 listed rows, ids[LP], scores[LP], tinv[16], dec[16], Q8: scale[16], bias[16]; LP = P +
 // X rounded up to 16
-static size_t tr_list_wave_bytes(int RB, int L, bool q8) {
-  return (size_t)17 * RB + (size_t)((L + 15) & ~15) * 8 + (q8 ? 256 : 128);
+// multi-interest (MI): one wave per user, 1 .. 4 waves a workgroup; the anchor's row becomes the user's Gp interest rows,
+// swizzled like any group of LDS rows, and column n of the B operand is interest n % Gp
+static size_t tr_list_wave_bytes(int RB, int L, bool q8, int gsh = 0) {
+  return (size_t)(16 + (1 << gsh)) * RB + (size_t)((L + 15) & ~15) * 8 + (q8 ? 256 : 128);
 }
 
-template <typename T, bool Q8>
-__global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
+template <typename T, bool Q8, bool MI>
+__global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgsOf<MI> p) {
+  static_assert(!(Q8 && MI), "multi-interest ranks are taken over float tables only");
   extern __shared__ __attribute__((aligned(16))) char tr_smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
   const int RB = p.nc * 16, P = p.P, L = P + p.X, LP = (L + 15) & ~15;
-  char* Arow = tr_smem + (size_t)wave * ((size_t)17 * RB + (size_t)LP * 8 + (Q8 ? 256 : 128));
-  char* Rows = Arow + RB;
+  int gsh = 0;
+  if constexpr (MI) gsh = p.gsh;
+  const int GP = 1 << gsh, nw = MI ? (int)(blockDim.x >> 6) : 4;
+  char* Arow = tr_smem + (size_t)wave * ((size_t)(16 + GP) * RB + (size_t)LP * 8 + (Q8 ? 256 : 128));
+  char* Rows = Arow + (size_t)GP * RB;
   int* ids = reinterpret_cast<int*>(Rows + (size_t)16 * RB);
   float* sc = reinterpret_cast<float*>(ids + LP);
   float* tinv = sc + LP;
   int* dec = reinterpret_cast<int*>(tinv + 16);
   float* tsc = reinterpret_cast<float*>(dec + 16);
   float* tbi = tsc + 16;
-  const int64_t b = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t b = (int64_t)blockIdx.x * nw + wave;
   if (b >= p.B) return;      // the whole wave; the kernel has no workgroup barrier
   const bool cosine = p.sim == TR_COS;
 
@@ -293,13 +343,22 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
     ids[i] = id < 0 || id >= p.Vt ? -1 : (int)id;
   }
   if (lane < 16) dec[lane] = 0;
-  for (int c = lane; c < p.nc; c += 64) *reinterpret_cast<uint4*>(Arow + 16 * c) = tr_anchor_chunk(p, b, c);
+  if constexpr (MI) {
+    for (int u = lane; u < GP * p.nc; u += 64) {
+      const int r = u / p.nc, c = u - r * p.nc;
+      *reinterpret_cast<uint4*>(Arow + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = tr_interest_chunk(p, b, r, c);
+    }
+  } else {
+    for (int c = lane; c < p.nc; c += 64) *reinterpret_cast<uint4*>(Arow + 16 * c) = tr_anchor_chunk(p, b, c);
+  }
   if constexpr (Q8) tr_q8_zero_tail<T>(Rows, 16, lane, 64, p);
   tr_wave_sync();
-  const float ai = cosine ? tr_row_inv<T>(Arow, 0, p) : 1.f;      // row 0 is not swizzled
+  const int arow = n & (GP - 1);      // the anchor row of this lane's column: 0, MI: its interest
+  const float ai = cosine ? tr_row_inv<T>(Arow, arow, p) : 1.f;      // row 0 is not swizzled
   float sa = 0.f;
   if constexpr (Q8) sa = tr_row_sum<T>(Arow, 0, p);
   const int gsw = (n >> p.sw_shift) & p.sw_mask, nks = p.nc >> 2;
+  const int asw = (arow >> p.sw_shift) & p.sw_mask;
 
   for (int g0 = 0; g0 < LP; g0 += 16) {
     if constexpr (Q8) {      // the 16 listed Q8 rows, vector by vector (a row that is not listed: code 0, scale 0, bias 0)
@@ -325,7 +384,7 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
     tr_f32x4 acc = tr_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < nks; ++ks) {
       const uint4 af = *reinterpret_cast<const uint4*>(Rows + n * RB + (((4 * ks + q) ^ gsw) << 4));
-      const uint4 bf = *reinterpret_cast<const uint4*>(Arow + ((4 * ks + q) << 4));
+      const uint4 bf = *reinterpret_cast<const uint4*>(Arow + arow * RB + (((4 * ks + q) ^ asw) << 4));
       acc = tr_mma<T>(af, bf, acc);
     }
     tr_wave_sync();
@@ -334,6 +393,10 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
       const float4 sc = Q8 ? *reinterpret_cast<const float4*>(tsc + 4 * q) : zero;
       const float4 bi = Q8 ? *reinterpret_cast<const float4*>(tbi + 4 * q) : zero;
       tr_scores<Q8>(acc, sc, bi, sa, cosine, ai, cosine ? *reinterpret_cast<const float4*>(tinv + 4 * q) : zero);
+    }
+    if constexpr (MI) {      // the user's score of the listed row: the max over its interests, in every lane of the group
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = group_max(acc[j], gsh);
     }
     if (n == 0) *reinterpret_cast<float4*>(sc + g0 + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     tr_wave_sync();      // the scores are written, the rows may be replaced
@@ -356,12 +419,18 @@ __global__ __launch_bounds__(256) void target_rank_list_kernel(RankArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ 2. the count
-template <typename T, int AR, int TR, int PT, bool Q8>
-__global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
+template <typename T, int AR, int TR, int PT, bool Q8, bool MI>
+__global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgsOf<MI> p) {
+  static_assert(!(Q8 && MI), "multi-interest ranks are taken over float tables only");
   extern __shared__ __attribute__((aligned(16))) char tr_smem[];
   constexpr int AT = AR / 16, NT = TR / 16, NA = 4 * AR;
   constexpr bool TLDS = PT > 4;      // thresholds in LDS
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
+  // MI: b counts users; LDS row r is slot r & gm of user r >> gsh.  Behind the epilogue every lane of a user holds the
+  // user's score (the max over its Gp rows); the leader lane (slot 0) counts, the others behave like rows past B
+  int gsh = 0;
+  if constexpr (MI) gsh = p.gsh;
+  const int gm = (1 << gsh) - 1;
   const int RB = p.nc * 16, P = p.P;
   char* As = tr_smem;
   char* Ts = As + (size_t)NA * RB;
@@ -376,11 +445,16 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
   const bool cosine = p.sim == TR_COS;
 
   // ---- the anchors, once
-  const int64_t b0 = (int64_t)blockIdx.x * NA;
+  const int64_t b0 = (int64_t)blockIdx.x * (NA >> gsh);
   for (int u = threadIdx.x; u < NA * p.nc; u += blockDim.x) {
     const int r = u / p.nc, c = u - r * p.nc;
-    *reinterpret_cast<uint4*>(As + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = tr_anchor_chunk(p, b0 + r, c);
+    uint4 v;
+    if constexpr (MI) v = tr_interest_chunk(p, b0 + (r >> gsh), r & gm, c);
+    else v = tr_anchor_chunk(p, b0 + r, c);
+    *reinterpret_cast<uint4*>(As + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = v;
   }
+  // the sample whose labels LDS row r counts against: MI the user on its leader row, none (B) on the others
+  auto row_sample = [&](int r) -> int64_t { return (r & gm) != 0 ? p.B : b0 + (r >> gsh); };
 
   // ---- this workgroup's target rows [lo, hi), absolute row numbers of the target table
   const int64_t lo = p.t_lo + (int64_t)blockIdx.y * p.rows_per;
@@ -465,7 +539,7 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
     }
   };
   if constexpr (TLDS) {
-    for (int u = threadIdx.x; u < PT * NA; u += blockDim.x) threshold(b0 + u % NA, u / NA, thS[u], tloS[u], lidS[u]);
+    for (int u = threadIdx.x; u < PT * NA; u += blockDim.x) threshold(MI ? row_sample(u % NA) : b0 + u % NA, u / NA, thS[u], tloS[u], lidS[u]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -492,7 +566,7 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
     for (int pp = 0; pp < PT; ++pp) cnt[at][pp] = 0;
     if constexpr (!TLDS) {
 #pragma unroll
-      for (int pp = 0; pp < PT; ++pp) threshold(b0 + row0 + 16 * at, pp, thr_[at][pp], tlor_[at][pp], lidr_[at][pp]);
+      for (int pp = 0; pp < PT; ++pp) threshold(MI ? row_sample(row0 + 16 * at) : b0 + row0 + 16 * at, pp, thr_[at][pp], tlor_[at][pp], lidr_[at][pp]);
     }
   }
   auto TH = [&](int at, int pp) { if constexpr (TLDS) return thS[pp * NA + row0 + 16 * at]; else return thr_[at][pp]; };
@@ -551,6 +625,20 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (16 * nt + 4 * q + j >= valid) acc[at][nt][j] = -INFINITY;
+    }
+    if constexpr (MI) {      // the user's scores: log2(Gp) butterfly steps over the tile, each behind one uniform branch
+      auto step = [&](auto ctrl) {
+#pragma unroll
+        for (int at = 0; at < AT; ++at)
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[at][nt][j] = gm_step<decltype(ctrl)::value>(acc[at][nt][j]);
+      };
+      if (gsh >= 1) step(std::integral_constant<int, GM_QUAD_1032>{});
+      if (gsh >= 2) step(std::integral_constant<int, GM_QUAD_2301>{});
+      if (gsh >= 3) step(std::integral_constant<int, GM_ROW_HALF_MIRROR>{});
+      if (gsh >= 4) step(std::integral_constant<int, GM_ROW_MIRROR>{});
     }
     bool slow = false;
 #pragma unroll
@@ -611,7 +699,8 @@ __global__ __launch_bounds__(256) void target_rank_count_kernel(RankArgs p) {
       int c = cnt[at][pp];
       c += __shfl_xor(c, 16);
       c += __shfl_xor(c, 32);
-      const int64_t b = b0 + row0 + 16 * at;
+      // MI: the user, and LID is -1 on every lane but its leader
+      const int64_t b = MI ? b0 + ((row0 + 16 * at) >> gsh) : b0 + row0 + 16 * at;
       if (q == 0 && b < p.B && LID(at, pp) >= 0 && c != 0)
         atomicAdd(reinterpret_cast<unsigned long long*>(p.ranks + b * P + pp), (unsigned long long)c);
     }
@@ -641,10 +730,11 @@ static size_t tr_lds_bytes(const RankShape& s, int RB, int PT, bool q8) {
          (q8 ? (size_t)2 * s.TR * 8 + NA * 4 : 0);
 }
 
-template <typename T, int PT, bool Q8>
-static int tr_count_launch(const char* op, const RankArgs& p, int RB, hipStream_t s) {
+template <typename T, int PT, bool Q8, bool MI>
+static int tr_count_launch(const char* op, const RankArgsMI& p, int RB, hipStream_t s) {
   static const RankShape shapes[] = {{64, 64, TR_HALF_LDS}, {32, 64, TR_HALF_LDS}, {32, 64, TR_MAX_LDS}, {16, 32, TR_MAX_LDS}};
-  constexpr int PT64 = Q8 ? 1 : 4;      // the labels up to which 64 x 64 is taken
+  // the labels up to which 64 x 64 is taken (MI, fp32, 2 .. 4 labels: 259 registers, one wave per SIMD)
+  constexpr int PT64 = Q8 || (MI && std::is_same<T, float>::value) ? 1 : 4;
   const RankShape* sh = nullptr;
   for (const RankShape& c : shapes)
     if ((PT <= PT64 || c.AR <= 32) && tr_lds_bytes(c, RB, PT, Q8) <= c.lds &&
@@ -655,7 +745,7 @@ static int tr_count_launch(const char* op, const RankArgs& p, int RB, hipStream_
   TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS%s (row %d bytes, P %d)", op,
               Q8 ? " and the Q8 vectors of a tile its threads" : "", RB, p.P);
   const size_t lds = tr_lds_bytes(*sh, RB, PT, Q8);
-  const int NA = 4 * sh->AR;
+  const int NA = (4 * sh->AR) >> p.gsh;      // users of a workgroup
   const dim3 grid((unsigned)((p.B + NA - 1) / NA), (unsigned)p.S);
   auto go = [&](auto kern) -> int {
     if (lds > 64 * 1024 &&
@@ -663,34 +753,39 @@ static int tr_count_launch(const char* op, const RankArgs& p, int RB, hipStream_
       (void)hipGetLastError();
       return fail(TRS_ELAUNCH, "%s: hipFuncSetAttribute(%zu bytes of LDS) failed", op, lds);
     }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, static_cast<const RankArgsOf<MI>&>(p));
     return TRS_OK;
   };
   if constexpr (PT <= PT64) {
-    if (sh->AR == 64) return go(target_rank_count_kernel<T, 64, 64, PT, Q8>);
+    if (sh->AR == 64) return go(target_rank_count_kernel<T, 64, 64, PT, Q8, MI>);
   }
-  if (sh->AR == 32) return go(target_rank_count_kernel<T, 32, 64, PT, Q8>);
-  return go(target_rank_count_kernel<T, 16, 32, PT, Q8>);
+  if (sh->AR == 32) return go(target_rank_count_kernel<T, 32, 64, PT, Q8, MI>);
+  return go(target_rank_count_kernel<T, 16, 32, PT, Q8, MI>);
 }
 
-template <typename T, bool Q8>
-static int tr_launch(const char* op, const RankArgs& p, hipStream_t s) {
+template <typename T, bool Q8, bool MI>
+static int tr_launch(const char* op, const RankArgsMI& p, hipStream_t s) {
   const int RB = p.nc * 16;
-  const size_t lds = 4 * tr_list_wave_bytes(RB, p.P + p.X, Q8);
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)target_rank_list_kernel<T, Q8>,
+  // MI: the user's Gp interest rows stand where the one anchor row stood; as many waves (users) a workgroup as fit
+  int nw = 4;
+  while (MI && nw > 1 && nw * tr_list_wave_bytes(RB, p.P + p.X, Q8, p.gsh) > TR_MAX_LDS) nw >>= 1;
+  const size_t lds = nw * tr_list_wave_bytes(RB, p.P + p.X, Q8, p.gsh);
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)target_rank_list_kernel<T, Q8, MI>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)TR_MAX_LDS) != hipSuccess) {
     (void)hipGetLastError();
     return fail(TRS_ELAUNCH, "%s: hipFuncSetAttribute(%zu bytes of LDS) failed", op, lds);
   }
-  hipLaunchKernelGGL((target_rank_list_kernel<T, Q8>), dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p);
-  const int rc = p.P == 1 ? tr_count_launch<T, 1, Q8>(op, p, RB, s)
-                 : p.P <= 4 ? tr_count_launch<T, 4, Q8>(op, p, RB, s)
-                            : tr_count_launch<T, TR_MAX_P, Q8>(op, p, RB, s);
+  hipLaunchKernelGGL((target_rank_list_kernel<T, Q8, MI>), dim3((unsigned)((p.B + nw - 1) / nw)), dim3(64 * nw), lds, s,
+                     static_cast<const RankArgsOf<MI>&>(p));
+  const int rc = p.P == 1 ? tr_count_launch<T, 1, Q8, MI>(op, p, RB, s)
+                 : p.P <= 4 ? tr_count_launch<T, 4, Q8, MI>(op, p, RB, s)
+                            : tr_count_launch<T, TR_MAX_P, Q8, MI>(op, p, RB, s);
   return rc != TRS_OK ? rc : check_launch(op);
 }
 
-// both entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns
-static int tr_entry(const char* op, bool q8, const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+// all entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns;
+// G = 0: one anchor per sample (U unused); G >= 1: the multi-interest entry, B = U * G anchors, user-major
+static int tr_entry(const char* op, bool q8, int64_t U, int32_t G, const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
                     int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo, int64_t target_hi,
                     int32_t E, int32_t dtype, int32_t sim, const void* labels, int32_t label_dtype, int32_t P,
                     const void* exclude, int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores,
@@ -707,13 +802,17 @@ static int tr_entry(const char* op, bool q8, const void* anchor_table, int64_t V
   TRS_REQUIRE(Va > 0 && B >= 0 && target_lo >= 0 && Vt > 0 && Vt <= INT32_MAX, TRS_EINVAL,
               "%s: bad size Va=%lld B=%lld targets [%lld, %lld)", op, (long long)Va, (long long)B, (long long)target_lo,
               (long long)target_hi);
+  const bool multi = G != 0;
+  TRS_REQUIRE(!multi || (G >= 1 && G <= 16 && U >= 0 && B == U * G), TRS_EINVAL,
+              "%s: G = %d (1 .. 16), U = %lld (>= 0), B = %lld (U * G)", op, G, (long long)U, (long long)B);
+  const int gsh = multi ? gm_shift(G) : 0;
   const int row_bytes = E * dtype_size(dtype);
   TRS_REQUIRE(E > 0 && E <= TR_MAX_E && row_bytes % 16 == 0, TRS_ESHAPE,
               "%s: E = %d (rows of whole 16-byte vectors, E <= %d)", op, E, TR_MAX_E);
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(anchor_table && target_table && labels && ranks && label_scores, TRS_EINVAL, "%s: NULL pointer", op);
   TRS_REQUIRE(aligned16(anchor_table) && aligned16(target_table), TRS_EALIGN, "%s: tables must be 16-byte aligned", op);
-  RankArgs p;
+  RankArgsMI p;
   p.a_table = static_cast<const char*>(anchor_table);
   p.a_idx = anchor_idx;
   p.t_table = static_cast<const char*>(target_table);
@@ -724,10 +823,12 @@ static int tr_entry(const char* op, bool q8, const void* anchor_table, int64_t V
   p.err_flag = err_flag;
   p.Va = Va;
   p.a_off = anchor_offset;
-  p.B = B;
+  p.B = multi ? U : B;
+  p.G = multi ? G : 1;
+  p.gsh = gsh;
   p.t_lo = target_lo;
   p.Vt = (int)Vt;
-  p.S = tr_splits(B, Vt);
+  p.S = tr_splits(multi ? U << gsh : B, Vt);      // what the anchor tiles are filled with
   p.rows_per = (int)((Vt + p.S - 1) / p.S);
   p.P = P;
   p.X = exclude != nullptr ? X : 0;
@@ -748,8 +849,9 @@ static int tr_entry(const char* op, bool q8, const void* anchor_table, int64_t V
   p.q_stride = (int)q8_stride(E);
   p.q_nv = p.q_stride / 16;
   hipStream_t s = (hipStream_t)stream;
-  if (q8) return dtype == TRS_F32 ? tr_launch<float, true>(op, p, s) : tr_launch<bf16_t, true>(op, p, s);
-  return dtype == TRS_F32 ? tr_launch<float, false>(op, p, s) : tr_launch<bf16_t, false>(op, p, s);
+  if (multi) return dtype == TRS_F32 ? tr_launch<float, false, true>(op, p, s) : tr_launch<bf16_t, false, true>(op, p, s);
+  if (q8) return dtype == TRS_F32 ? tr_launch<float, true, false>(op, p, s) : tr_launch<bf16_t, true, false>(op, p, s);
+  return dtype == TRS_F32 ? tr_launch<float, false, false>(op, p, s) : tr_launch<bf16_t, false, false>(op, p, s);
 }
 
 }  // namespace trs
@@ -765,7 +867,7 @@ extern "C" int trs_target_ranks(const void* anchor_table, int64_t Va, const void
                                 int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
                                 int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes, int32_t* err_flag,
                                 trs_stream_t stream) {
-  return tr_entry("target_ranks", false, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
+  return tr_entry("target_ranks", false, 0, 0, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
                   target_hi, E, dtype, sim, labels, label_dtype, P, exclude, excl_dtype, X, ranks, label_scores, err_flag,
                   stream);
 }
@@ -776,7 +878,19 @@ extern "C" int trs_target_ranks_q8(const void* anchor_table, int64_t Va, const v
                                    int32_t label_dtype, int32_t P, const void* exclude, int32_t excl_dtype, int32_t X,
                                    int64_t* ranks, float* label_scores, void* workspace, size_t ws_bytes,
                                    int32_t* err_flag, trs_stream_t stream) {
-  return tr_entry("target_ranks_q8", true, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
+  return tr_entry("target_ranks_q8", true, 0, 0, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
                   target_hi, E, anchor_dtype, sim, labels, label_dtype, P, exclude, excl_dtype, X, ranks, label_scores,
+                  err_flag, stream);
+}
+
+extern "C" int trs_target_ranks_multi(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                                      int64_t anchor_offset, int64_t B, int64_t U, int32_t G, const void* target_table,
+                                      int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype, int32_t sim,
+                                      const void* labels, int32_t label_dtype, int32_t P, const void* exclude,
+                                      int32_t excl_dtype, int32_t X, int64_t* ranks, float* label_scores, void* workspace,
+                                      size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  TRS_REQUIRE(G >= 1 && G <= 16, TRS_EINVAL, "target_ranks_multi: G = %d (1 .. 16)", G);
+  return tr_entry("target_ranks_multi", false, U, G, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table,
+                  target_lo, target_hi, E, dtype, sim, labels, label_dtype, P, exclude, excl_dtype, X, ranks, label_scores,
                   err_flag, stream);
 }

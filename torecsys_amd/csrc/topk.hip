@@ -40,8 +40,24 @@
 // workgroup -- and stores them as ordinary swizzled operand chunks into the other buffer; the (scale, bias) words of the
 // vectors that hold them go to two per-tile LDS arrays next to tinv, sa sits next to ainv.  Operand loads, k-loop,
 // selection and merge are the float kernel's.  Rows past the end of a range stage as code 0, scale 0, bias 0.
+//
+// Multi-interest (template parameter MI; trs_topk_scores_multi).  A user is G anchors (1 .. 16) and score[u, j] = max_g
+// sim(a[u, g], t[j]), each sim the bits above.  Gp = the power of two >= G is a kernel argument (gsh = log2 Gp); MI = false
+// compiles to the kernels of one anchor per row unchanged (same registers and occupancy in the compiler's report).  A
+// workgroup's NA LDS anchor rows hold NA / Gp users: row r is slot r % Gp of user r / Gp, gathered from the user's interest
+// min(slot, G - 1), so a G that is no power of two is padded on chip by repeating the last interest, which leaves the max
+// as it is.  A user's Gp rows are Gp adjacent n of one accumulator group, and the max over them is log2 Gp DPP steps on the
+// vector ALU (group_max.hpp).  The first pass is the one above, untouched: every lane compares its own interest's scores
+// with its user's tau (all Gp lanes carry the same tk / tf), because max_g s_g >= tau iff some s_g >= tau -- no max is
+// taken where nothing passes.  Only the revisit pass takes the group max; the leader lane (n % Gp == 0) builds the keys,
+// scans excl[u] and inserts, and a new tau goes to all Gp lanes of the user.  Candidate buffers, tauk and cnt exist per
+// user, so k = 128 fits a larger arrangement than with one anchor per row; sort, write-out, workspace (U, S, k) and merge
+// run per user.  The grid's anchor dimension and the split count U Gp rows.  Registers (compiler's report, no spill):
+// 32 x 128 198 + 76 (fp32) / 198 + 64 (bf16) vector + accumulator registers, one wave per SIMD; 16 x 128 150 + 36 / 32, two;
+// 16 x 64 96 + 24 / 16, four; 16 x 32 62 + 8, seven: the occupancies of the MI = false kernels.
 #include <algorithm>
 
+#include "group_max.hpp"
 #include "lds_dma.hpp"
 #include "q8_common.hpp"
 
@@ -75,6 +91,13 @@ struct TopkArgs {
   bool idx64, excl64, dma;
   int E, q_stride, q_nv;   // Q8 targets: columns, bytes of a row (S) and its 16-byte vectors
 };
+// multi-interest (template parameter MI): B users of G anchors each, in groups of Gp = 1 << gsh LDS rows.  Arguments of
+// their own, so that the kernels of one anchor per row keep theirs
+struct TopkArgsMI : TopkArgs {
+  int G, gsh;
+};
+template <bool MI>
+using TopkArgsOf = std::conditional_t<MI, TopkArgsMI, TopkArgs>;
 
 __device__ __forceinline__ void tk_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -172,8 +195,9 @@ __device__ __forceinline__ float tk_q8_row_sq(const char* rows, int r, float sca
   return s;
 }
 
-template <typename T, int AR, int TR, bool Q8>
-__global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
+template <typename T, int AR, int TR, bool Q8, bool MI>
+__global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgsOf<MI> p) {
+  static_assert(!(Q8 && MI), "multi-interest scores are taken over float tables only");
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   constexpr int AT = AR / 16, NT = TR / 16;
   const int NW = blockDim.x >> 6, NA = NW * AR;
@@ -182,9 +206,14 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   char* As = tk_smem;
   char* Ts = As + (size_t)NA * RB;
   uint64_t* cand = reinterpret_cast<uint64_t*>(Ts + (size_t)2 * TR * RB);
-  uint64_t* tauk = cand + (size_t)NA * P;
-  int* cnt = reinterpret_cast<int*>(tauk + NA);
-  float* ainv = reinterpret_cast<float*>(cnt + NA);
+  // MI: a user is Gp adjacent LDS rows; candidate buffers, tauk and cnt exist per user (16 bytes of them kept whole)
+  int gsh = 0, G = 1;
+  if constexpr (MI) gsh = p.gsh, G = p.G;
+  const int gm = (1 << gsh) - 1, NU = NA >> gsh;
+  uint64_t* tauk = cand + (size_t)NU * P;
+  int* cnt = reinterpret_cast<int*>(tauk + NU);
+  float* ainv = MI ? reinterpret_cast<float*>(reinterpret_cast<char*>(tauk) + ((NU * 12 + 15) & ~15))
+                   : reinterpret_cast<float*>(cnt + NA);
   float* tinv = ainv + NA;      // [2][TR]
   float* tsc = tinv + 2 * TR;   // Q8: [2][TR] scales, [2][TR] biases, [NA] anchor sums
   float* tbi = tsc + 2 * TR;
@@ -193,15 +222,17 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   constexpr int CPV = 16 * (int)sizeof(T) / 16;      // operand chunks the 16 codes of one vector become
 
   // ---- the anchors, once
-  const int64_t b0 = (int64_t)blockIdx.x * NA;
+  // MI: b counts users; LDS row r is slot r & gm of user r >> gsh, loaded from its interest min(slot, G - 1)
+  const int64_t b0 = (int64_t)blockIdx.x * NU;
   for (int u = threadIdx.x; u < NA * p.nc; u += blockDim.x) {
     const int r = u / p.nc, c = u - r * p.nc;
     uint4 v = make_uint4(0, 0, 0, 0);
-    const int64_t b = b0 + r;
+    const int64_t b = b0 + (r >> gsh);
     if (b < p.B) {
-      int64_t ra = b;
+      const int64_t ia = MI ? b * G + std::min(r & gm, G - 1) : b;
+      int64_t ra = ia;
       if (p.a_idx != nullptr)
-        ra = p.idx64 ? static_cast<const int64_t*>(p.a_idx)[b] : (int64_t) static_cast<const int32_t*>(p.a_idx)[b];
+        ra = p.idx64 ? static_cast<const int64_t*>(p.a_idx)[ia] : (int64_t) static_cast<const int32_t*>(p.a_idx)[ia];
       ra += p.a_off;
       if (ra < 0 || ra >= p.Va) {      // reads as a zero row
         if (c == 0 && p.err_flag != nullptr) *p.err_flag = 1;
@@ -211,7 +242,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
     }
     *reinterpret_cast<uint4*>(As + ((size_t)r * p.nc + (c ^ ((r >> p.sw_shift) & p.sw_mask))) * 16) = v;
   }
-  for (int r = threadIdx.x; r < NA; r += blockDim.x) {
+  for (int r = threadIdx.x; r < NU; r += blockDim.x) {
     cnt[r] = 0;
     tauk[r] = 0;
   }
@@ -334,7 +365,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   for (int at = 0; at < AT; ++at) {
     tk[at] = 0;
     tf[at] = -INFINITY;
-    rowok[at] = b0 + row0 + 16 * at < p.B;
+    rowok[at] = (MI ? b0 + ((row0 + 16 * at) >> gsh) : b0 + row0 + 16 * at) < p.B;
     ai[at] = cosine ? ainv[row0 + 16 * at] : 1.f;
     sav[at] = Q8 ? sa[row0 + 16 * at] : 0.f;
   }
@@ -425,8 +456,13 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
             tkey = tk[a];
             ok = rowok[a];
           }
-      const int row = row0 + 16 * at;
+      const int row = (row0 + 16 * at) >> gsh;      // the row of the buffers: MI the user, whose leader lane inserts
       const int64_t b = b0 + row;
+      if constexpr (MI) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s4[j] = group_max(s4[j], gsh);
+        ok = ok && (n & gm) == 0;
+      }
       bool full = false;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -452,7 +488,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
       while (need != 0) {
         const int rn = (__builtin_ffsll((long long)need) - 1) & 15;
         need &= ~(0x0001000100010001ull << rn);
-        const int r = wave * AR + 16 * at + rn;
+        const int r = (wave * AR + 16 * at + rn) >> gsh;
         uint64_t* c = cand + (size_t)r * P;
         tk_sort_row(c, P, cnt[r], lane);
         const uint64_t nk = c[k - 1];
@@ -462,7 +498,7 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
           tauk[r] = nk;
         }
         tk_wave_sync();
-        if (n == rn) {
+        if ((n & ~gm) == rn) {      // the row's lanes: MI every interest of the user
 #pragma unroll
           for (int a = 0; a < AT; ++a)
             if (a == at) {
@@ -481,8 +517,8 @@ __global__ __launch_bounds__(256) void topk_scores_kernel(TopkArgs p) {
   }
 
   // ---- every row's best k, sorted: to the output (S == 1) or to the workspace as keys
-  for (int rr = 0; rr < AR; ++rr) {
-    const int r = wave * AR + rr;
+  for (int rr = 0; rr < (AR >> gsh); ++rr) {
+    const int r = wave * (AR >> gsh) + rr;
     const int64_t b = b0 + r;
     if (b >= p.B) break;
     uint64_t* c = cand + (size_t)r * P;
@@ -541,28 +577,28 @@ static int tk_splits(int64_t B, int64_t Vt) {
 struct TopkShape {
   int AR, TR, NW;
 };
-static size_t tk_lds_bytes(const TopkShape& s, int RB, int P, bool q8) {
-  const size_t NA = (size_t)s.NW * s.AR;
+static size_t tk_lds_bytes(const TopkShape& s, int RB, int P, bool q8, int gsh) {
+  const size_t NA = (size_t)s.NW * s.AR, NU = NA >> gsh;      // candidate buffers, tauk and cnt: one per user
   // Q8: the tiles' scales and biases, the anchors' sums
-  return NA * RB + (size_t)2 * s.TR * RB + NA * P * 8 + NA * 16 + (size_t)2 * s.TR * 4 +
+  return NA * RB + (size_t)2 * s.TR * RB + NU * P * 8 + ((NU * 12 + 15) & ~(size_t)15) + NA * 4 + (size_t)2 * s.TR * 4 +
          (q8 ? (size_t)2 * s.TR * 8 + NA * 4 : 0);
 }
 
-template <typename T, bool Q8>
-static int topk_launch(const char* op, TopkArgs& p, int RB, hipStream_t s) {
+template <typename T, bool Q8, bool MI>
+static int topk_launch(const char* op, const TopkArgsMI& p, int RB, hipStream_t s) {
   // the first arrangement whose anchors, two target tiles and candidate buffers fit the 160 KB of LDS
   static const TopkShape shapes[] = {{32, 128, 4}, {16, 128, 4}, {16, 64, 4}, {16, 64, 2}, {16, 32, 2}, {16, 32, 1}};
   const TopkShape* sh = nullptr;
   for (const TopkShape& c : shapes)
-    if (tk_lds_bytes(c, RB, p.P, Q8) <= TK_MAX_LDS) {
+    if (tk_lds_bytes(c, RB, p.P, Q8, p.gsh) <= TK_MAX_LDS) {
       sh = &c;
       break;
     }
   TRS_REQUIRE(sh != nullptr, TRS_ESHAPE, "%s: no arrangement fits LDS (row %d bytes, k %d)", op, RB, p.k);
   TRS_REQUIRE(!Q8 || (sh->TR * p.q_nv + 64 * sh->NW - 1) / (64 * sh->NW) <= TK_Q8_UNITS, TRS_ESHAPE,
               "%s: a tile of %d rows x %d vectors exceeds %d per thread", op, sh->TR, p.q_nv, TK_Q8_UNITS);
-  const size_t lds = tk_lds_bytes(*sh, RB, p.P, Q8);
-  const int NA = sh->NW * sh->AR;
+  const size_t lds = tk_lds_bytes(*sh, RB, p.P, Q8, p.gsh);
+  const int NA = (sh->NW * sh->AR) >> p.gsh;      // users of a workgroup
   const dim3 grid((unsigned)((p.B + NA - 1) / NA), (unsigned)p.S);
   auto go = [&](auto kern) -> int {
     if (lds > 64 * 1024 &&
@@ -570,14 +606,14 @@ static int topk_launch(const char* op, TopkArgs& p, int RB, hipStream_t s) {
       (void)hipGetLastError();
       return fail(TRS_ELAUNCH, "%s: hipFuncSetAttribute(%zu bytes of LDS) failed", op, lds);
     }
-    hipLaunchKernelGGL(kern, grid, dim3(64 * sh->NW), lds, s, p);
+    hipLaunchKernelGGL(kern, grid, dim3(64 * sh->NW), lds, s, static_cast<const TopkArgsOf<MI>&>(p));
     return TRS_OK;
   };
   int rc;
-  if (sh->AR == 32) rc = go(topk_scores_kernel<T, 32, 128, Q8>);
-  else if (sh->TR == 128) rc = go(topk_scores_kernel<T, 16, 128, Q8>);
-  else if (sh->TR == 64) rc = go(topk_scores_kernel<T, 16, 64, Q8>);
-  else rc = go(topk_scores_kernel<T, 16, 32, Q8>);
+  if (sh->AR == 32) rc = go(topk_scores_kernel<T, 32, 128, Q8, MI>);
+  else if (sh->TR == 128) rc = go(topk_scores_kernel<T, 16, 128, Q8, MI>);
+  else if (sh->TR == 64) rc = go(topk_scores_kernel<T, 16, 64, Q8, MI>);
+  else rc = go(topk_scores_kernel<T, 16, 32, Q8, MI>);
   if (rc != TRS_OK) return rc;
   if (p.S > 1)
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)p.B), dim3(64), (size_t)p.P * 8, s, p.ws, p.S, p.k, p.P, p.out_val,
@@ -585,8 +621,16 @@ static int topk_launch(const char* op, TopkArgs& p, int RB, hipStream_t s) {
   return check_launch(op);
 }
 
-// both entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns
-static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t Va, const void* anchor_idx,
+// the workspace of `users` result rows whose anchor tiles are filled as by `rows` anchor rows: (users, S, k) keys, S > 1
+static size_t tk_workspace_bytes(int64_t users, int64_t rows, int64_t Vt, int32_t k) {
+  if (users <= 0 || Vt <= 0 || k < 1 || k > TK_MAX_K) return 0;
+  const int S = tk_splits(rows, Vt);
+  return S > 1 ? (size_t)users * S * k * sizeof(uint64_t) : 0;
+}
+
+// all entries: `dtype` is the anchors' (and, for float targets, the table's); q8: target_table holds Q8 rows of E columns;
+// G = 0: one anchor per result row (U unused); G >= 1: the multi-interest entry, B = U * G anchors, user-major
+static int topk_entry(const char* op, bool q8, int64_t U, int32_t G, const void* anchor_table, int64_t Va, const void* anchor_idx,
                       int32_t idx_dtype, int64_t anchor_offset, int64_t B, const void* target_table, int64_t target_lo,
                       int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k, const void* exclude,
                       int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx, void* workspace, size_t ws_bytes,
@@ -603,16 +647,21 @@ static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t
               (long long)target_hi);
   TRS_REQUIRE(k >= 1 && k <= TK_MAX_K && k <= Vt, TRS_EINVAL, "%s: k = %d (1 .. %d, at most the %lld targets)", op, k,
               TK_MAX_K, (long long)Vt);
+  const bool multi = G != 0;
+  TRS_REQUIRE(!multi || (G >= 1 && G <= 16 && U >= 0 && B == U * G), TRS_EINVAL,
+              "%s: G = %d (1 .. 16), U = %lld (>= 0), B = %lld (U * G)", op, G, (long long)U, (long long)B);
+  const int gsh = multi ? gm_shift(G) : 0;
+  const int64_t users = multi ? U : B, rows = multi ? U << gsh : B;      // rows: what the anchor tiles are filled with
   const int row_bytes = E * dtype_size(dtype);
   TRS_REQUIRE(E > 0 && E <= TK_MAX_E && row_bytes % 16 == 0, TRS_ESHAPE,
               "%s: E = %d (rows of whole 16-byte vectors, E <= %d)", op, E, TK_MAX_E);
   if (B == 0) return TRS_OK;
   TRS_REQUIRE(anchor_table && target_table && out_val && out_idx, TRS_EINVAL, "%s: NULL pointer", op);
   TRS_REQUIRE(aligned16(anchor_table) && aligned16(target_table), TRS_EALIGN, "%s: tables must be 16-byte aligned", op);
-  const size_t need = trs_topk_scores_workspace_bytes(B, Vt, k);
+  const size_t need = tk_workspace_bytes(users, rows, Vt, k);
   TRS_REQUIRE(need == 0 || (workspace != nullptr && ws_bytes >= need), TRS_EWORKSPACE, "%s: workspace %zu < %zu", op,
               ws_bytes, need);
-  TopkArgs p;
+  TopkArgsMI p;
   p.a_table = static_cast<const char*>(anchor_table);
   p.a_idx = anchor_idx;
   p.t_table = static_cast<const char*>(target_table);
@@ -623,10 +672,12 @@ static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t
   p.err_flag = err_flag;
   p.Va = Va;
   p.a_off = anchor_offset;
-  p.B = B;
+  p.B = users;
+  p.G = multi ? G : 1;
+  p.gsh = gsh;
   p.t_lo = target_lo;
   p.Vt = (int)Vt;
-  p.S = tk_splits(B, Vt);
+  p.S = tk_splits(rows, Vt);
   p.rows_per = (int)((Vt + p.S - 1) / p.S);
   p.k = k;
   p.P = tk_buffer_keys(k);
@@ -647,8 +698,14 @@ static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t
   p.q_stride = (int)q8_stride(E);
   p.q_nv = p.q_stride / 16;
   hipStream_t s = (hipStream_t)stream;
-  if (q8) return dtype == TRS_F32 ? topk_launch<float, true>(op, p, p.nc * 16, s) : topk_launch<bf16_t, true>(op, p, p.nc * 16, s);
-  return dtype == TRS_F32 ? topk_launch<float, false>(op, p, p.nc * 16, s) : topk_launch<bf16_t, false>(op, p, p.nc * 16, s);
+  if (multi)
+    return dtype == TRS_F32 ? topk_launch<float, false, true>(op, p, p.nc * 16, s)
+                            : topk_launch<bf16_t, false, true>(op, p, p.nc * 16, s);
+  if (q8)
+    return dtype == TRS_F32 ? topk_launch<float, true, false>(op, p, p.nc * 16, s)
+                            : topk_launch<bf16_t, true, false>(op, p, p.nc * 16, s);
+  return dtype == TRS_F32 ? topk_launch<float, false, false>(op, p, p.nc * 16, s)
+                          : topk_launch<bf16_t, false, false>(op, p, p.nc * 16, s);
 }
 
 }  // namespace trs
@@ -656,9 +713,12 @@ static int topk_entry(const char* op, bool q8, const void* anchor_table, int64_t
 using namespace trs;
 
 extern "C" size_t trs_topk_scores_workspace_bytes(int64_t B, int64_t Vt, int32_t k) {
-  if (B <= 0 || Vt <= 0 || k < 1 || k > TK_MAX_K) return 0;
-  const int S = tk_splits(B, Vt);
-  return S > 1 ? (size_t)B * S * k * sizeof(uint64_t) : 0;
+  return tk_workspace_bytes(B, B, Vt, k);
+}
+
+extern "C" size_t trs_topk_scores_multi_workspace_bytes(int64_t U, int32_t G, int64_t Vt, int32_t k) {
+  if (G < 1 || G > 16) return 0;
+  return tk_workspace_bytes(U, U << gm_shift(G), Vt, k);
 }
 
 extern "C" int trs_topk_scores(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
@@ -666,7 +726,7 @@ extern "C" int trs_topk_scores(const void* anchor_table, int64_t Va, const void*
                                int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k, const void* exclude,
                                int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx, void* workspace,
                                size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
-  return topk_entry("topk_scores", false, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
+  return topk_entry("topk_scores", false, 0, 0, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table, target_lo,
                     target_hi, E, dtype, sim, k, exclude, excl_dtype, X, out_val, out_idx, workspace, ws_bytes, err_flag,
                     stream);
 }
@@ -676,7 +736,18 @@ extern "C" int trs_topk_scores_q8(const void* anchor_table, int64_t Va, const vo
                                   int64_t target_hi, int32_t E, int32_t anchor_dtype, int32_t sim, int32_t k,
                                   const void* exclude, int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx,
                                   void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
-  return topk_entry("topk_scores_q8", true, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
+  return topk_entry("topk_scores_q8", true, 0, 0, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_q, target_lo,
                     target_hi, E, anchor_dtype, sim, k, exclude, excl_dtype, X, out_val, out_idx, workspace, ws_bytes,
+                    err_flag, stream);
+}
+
+extern "C" int trs_topk_scores_multi(const void* anchor_table, int64_t Va, const void* anchor_idx, int32_t idx_dtype,
+                                     int64_t anchor_offset, int64_t B, int64_t U, int32_t G, const void* target_table,
+                                     int64_t target_lo, int64_t target_hi, int32_t E, int32_t dtype, int32_t sim, int32_t k,
+                                     const void* exclude, int32_t excl_dtype, int32_t X, float* out_val, int64_t* out_idx,
+                                     void* workspace, size_t ws_bytes, int32_t* err_flag, trs_stream_t stream) {
+  TRS_REQUIRE(G >= 1 && G <= 16, TRS_EINVAL, "topk_scores_multi: G = %d (1 .. 16)", G);
+  return topk_entry("topk_scores_multi", false, U, G, anchor_table, Va, anchor_idx, idx_dtype, anchor_offset, B, target_table,
+                    target_lo, target_hi, E, dtype, sim, k, exclude, excl_dtype, X, out_val, out_idx, workspace, ws_bytes,
                     err_flag, stream);
 }

@@ -4187,7 +4187,7 @@ TOPK_MAX_K, TOPK_MAX_E = 128, 256
 
 def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_weight: Optional[torch.Tensor],
                 k: int, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None, sim="dot",
-                exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                exclude: Optional[torch.Tensor] = None, interests: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """The best ``k`` rows of ``target_weight[target_lo:target_hi]`` for every anchor, in one HIP pass (csrc/topk.hip):
     MFMA scores with the selection next to the accumulators, no (B, Vt) block.  Anchor b is row ``anchor_idx[b] +
     anchor_offset`` of ``anchor_weight``; ``anchor_idx=None``: ``anchor_weight`` is the (B, E) query matrix itself.
@@ -4197,8 +4197,15 @@ def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor],
     ``target_offset=target_lo``), by score descending and, among equal scores, id ascending; where fewer than k targets
     remain the trailing slots hold -inf / -1.  1 <= k <= 128; bf16 or fp32 contiguous tables of one dtype, rows of whole
     16-byte vectors, E <= 256.  No gradient, no host read-back; an anchor id outside its table scores as a zero row and
-    raises the index flag."""
+    raises the index flag.
+    ``interests`` = G in 2 .. 16: multi-interest retrieval (MIND, ComiRec).  The anchors are U * G rows, user-major -- (u, g)
+    is ``anchor_idx[u * G + g]``, or row ``u * G + g`` of the (U * G, E) query matrix, e.g. ``DynamicRoutingLayer``'s output
+    reshaped -- and ``score[u, j] = max_g sim(a[u, g], t[j])``, each ``sim`` the bits the single-interest call gives that
+    pair, the max as ``fmaxf`` (a NaN loses to a number).  ``exclude`` is (U, X) and the result (U, k), the exact best k of
+    the max score over the whole range, selected once per user in the same pass; a zero row of an interest id outside its
+    table takes part in the max.  Float tables only (``topk_scores_q8`` has no such keyword)."""
     code = _sim_code(sim)
+    G = _interests("topk_scores", interests)
     aw = anchor_weight.detach()
     tw = aw if target_weight is None or target_weight is anchor_weight else target_weight.detach()
     if aw.dim() != 2 or tw.dim() != 2 or aw.shape[1] != tw.shape[1]:
@@ -4211,11 +4218,26 @@ def topk_scores(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor],
         raise NotImplementedError(f"topk_scores: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} "
                                   f"of {aw.dtype}")
     return _topk_run("topk_scores", "trs_topk_scores", aw, anchor_idx, anchor_offset, tw, "target_weight", target_lo,
-                     target_hi, E, code, k, exclude)
+                     target_hi, E, code, k, exclude, G)
 
 
-def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, k, exclude):
-    """what topk_scores and topk_scores_q8 share behind their table checks: range, k, exclusion list, outputs, the call"""
+def _interests(op, interests) -> int:
+    G = int(interests)
+    if not 1 <= G <= 16:
+        raise ValueError(f"{op}: interests must be in 1 .. 16, got {interests!r}")
+    return G
+
+
+def _users(op, rows, G) -> int:
+    """the result rows of ``rows`` anchors, ``G`` a user"""
+    if rows % G != 0:
+        raise ValueError(f"{op}: {rows} anchor rows are not a multiple of interests = {G}")
+    return rows // G
+
+
+def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, k, exclude, G=1):
+    """what topk_scores and topk_scores_q8 share behind their table checks: range, k, exclusion list, outputs, the call;
+    ``G`` > 1: B users of G anchors each, through the multi-interest entry"""
     lo = int(target_lo)
     hi = tw.shape[0] if target_hi is None else int(target_hi)
     if not 0 <= lo < hi <= tw.shape[0]:
@@ -4224,7 +4246,7 @@ def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, ta
     if not 1 <= k <= TOPK_MAX_K or k > hi - lo:
         raise ValueError(f"{op}: k must be in 1 .. {TOPK_MAX_K} and at most the {hi - lo} targets, got {k}")
     a_idx = None if anchor_idx is None else _as_index(anchor_idx).reshape(-1)
-    B = aw.shape[0] if a_idx is None else a_idx.shape[0]
+    B = _users(op, aw.shape[0] if a_idx is None else a_idx.shape[0], G)
     ex = None
     if exclude is not None:
         ex = _as_index(exclude)
@@ -4238,11 +4260,16 @@ def _topk_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, ta
     ids = torch.empty(B, k, dtype=torch.int64, device=dev)
     if B == 0:
         return values, ids
-    ws_bytes = size_query("trs_topk_scores_workspace_bytes", B, hi - lo, k)
+    if G > 1:
+        entry, rows = "trs_topk_scores_multi", (B * G, B, G)
+        ws_bytes = size_query("trs_topk_scores_multi_workspace_bytes", B, G, hi - lo, k)
+    else:
+        rows = (B,)
+        ws_bytes = size_query("trs_topk_scores_workspace_bytes", B, hi - lo, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     flag = _ErrFlag(dev)
     call(entry, ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
-         int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, k, ptr(ex),
+         int(anchor_offset), *rows, ptr(tw), lo, hi, E, value_dtype_code(aw), code, k, ptr(ex),
          index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(values), ptr(ids), ptr(ws),
          ws_bytes, ptr(flag.t), stream_ptr())
     flag.check(op)
@@ -4293,7 +4320,7 @@ TARGET_RANKS_MAX_P, TARGET_RANKS_MAX_X = 16, 1024
 
 def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor], target_weight: Optional[torch.Tensor],
                  labels: torch.Tensor, *, anchor_offset: int = 0, target_lo: int = 0, target_hi: Optional[int] = None,
-                 sim="dot", exclude: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 sim="dot", exclude: Optional[torch.Tensor] = None, interests: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """The position every label takes among ALL rows of ``target_weight[target_lo:target_hi]`` for its anchor, in one HIP
     pass over the table (csrc/target_rank.hip): MFMA scores counted against the label's own score next to the
     accumulators, no (B, Vt) block, no selection.  What hit rate@k, NDCG@k, MRR and MAP are computed from
@@ -4306,9 +4333,13 @@ def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor]
     and the other labels of a sample count like any target.  ``exclude`` (B, X <= 1024): negative entries and ids past the
     range are ignored, a repeated id is excluded once.  bf16 or fp32 contiguous tables of one dtype, rows of whole
     16-byte vectors, E <= 256.  No gradient, no host read-back; an anchor id outside its table scores as a zero row and
-    raises the index flag."""
+    raises the index flag.
+    ``interests`` = G in 2 .. 16: the anchors are U * G rows, user-major, and the score is ``max_g sim(a[u, g], t[j])`` as in
+    ``topk_scores(..., interests=G)``; ``labels`` (U,) or (U, P), ``exclude`` (U, X), the result (U, P): the index that call
+    returns the label at, were k unbounded, and the same score bits.  Float tables only."""
     op = "target_ranks"
     code = _sim_code(sim)
+    G = _interests(op, interests)
     aw = anchor_weight.detach()
     tw = aw if target_weight is None or target_weight is anchor_weight else target_weight.detach()
     if aw.dim() != 2 or tw.dim() != 2 or aw.shape[1] != tw.shape[1]:
@@ -4320,18 +4351,19 @@ def target_ranks(anchor_weight: torch.Tensor, anchor_idx: Optional[torch.Tensor]
         raise NotImplementedError(f"{op}: rows of whole 16-byte vectors with E <= {TOPK_MAX_E} expected, got E = {E} of "
                                   f"{aw.dtype}")
     return _target_ranks_run(op, "trs_target_ranks", aw, anchor_idx, anchor_offset, tw, "target_weight", target_lo,
-                             target_hi, E, code, labels, exclude)
+                             target_hi, E, code, labels, exclude, G)
 
 
-def _target_ranks_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, labels, exclude):
+def _target_ranks_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, target_lo, target_hi, E, code, labels, exclude,
+                      G=1):
     """what target_ranks and target_ranks_q8 share behind their table checks: range, labels, exclusion list, outputs, the
-    call"""
+    call; ``G`` > 1: B users of G anchors each, through the multi-interest entry"""
     lo = int(target_lo)
     hi = tw.shape[0] if target_hi is None else int(target_hi)
     if not 0 <= lo < hi <= tw.shape[0]:
         raise ValueError(f"{op}: target range [{lo}, {hi}) is not inside the {tw.shape[0]} target rows")
     a_idx = None if anchor_idx is None else _as_index(anchor_idx).reshape(-1)
-    B = aw.shape[0] if a_idx is None else a_idx.shape[0]
+    B = _users(op, aw.shape[0] if a_idx is None else a_idx.shape[0], G)
     y = _as_index(labels)
     if y.dim() == 1:
         y = y.unsqueeze(1)
@@ -4359,8 +4391,12 @@ def _target_ranks_run(op, entry, aw, anchor_idx, anchor_offset, tw, tname, targe
     ws_bytes = size_query("trs_target_ranks_workspace_bytes", B, hi - lo, P)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     flag = _ErrFlag(dev)
+    if G > 1:
+        entry, rows = "trs_target_ranks_multi", (B * G, B, G)
+    else:
+        rows = (B,)
     call(entry, ptr(aw), aw.shape[0], ptr(a_idx), index_dtype_code(a_idx) if a_idx is not None else 0,
-         int(anchor_offset), B, ptr(tw), lo, hi, E, value_dtype_code(aw), code, ptr(y), index_dtype_code(y), P, ptr(ex),
+         int(anchor_offset), *rows, ptr(tw), lo, hi, E, value_dtype_code(aw), code, ptr(y), index_dtype_code(y), P, ptr(ex),
          index_dtype_code(ex) if ex is not None else 0, ex.shape[1] if ex is not None else 0, ptr(ranks), ptr(scores),
          ptr(ws), ws_bytes, ptr(flag.t), stream_ptr())
     flag.check(op)
